@@ -19,9 +19,13 @@ through ONE RCCL all-gather + the merge kernel.
 HDB_BENCH_REHEARSAL=1 rehearses the N > 1 control flow on ONE GPU (every rank on device 0, gloo for the bookkeeping
 collectives): it checks that the multi-rank path runs end to end; its timings mean nothing.
 
-One JSON line is printed by rank 0.  Besides the contract fields it carries
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the --steps query calls and prints the line: the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step) and
   roofline      -- dominant kernel (the pass over all of V) timed with HIP events on its launch
                    stream inside the timed region; algorithmic bytes = rows * d * sizeof(elem).
+--dump-outputs DIR writes what the last timed step returned to its caller (top-k row indices as float64, scores as float32)
+to DIR/indices.npy and DIR/scores.npy; with the same arguments the inputs are the same from run to run.
+Everything else is measured only with --full (the keys below are null or absent without it):
   cpu_baseline  -- the numpy restatement of the reference (oracle/), timed on this host on a bounded
                    row prefix and scaled linearly to N (rank 0, --gpus 1 only).
   batched       -- config 3 of BASELINE.json (Q=256 dot-product) measured in the same run.
@@ -61,9 +65,10 @@ import torch
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense fp16 MFMA
 BLOCK_ROWS = 250_000
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all arrays together
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -73,15 +78,32 @@ def parse():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
     ap.add_argument("--metric", default="cosine_similarity")
-    ap.add_argument("--batch-q", type=int, default=256, help="batched leg (config 3); 0 disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k indices and scores to DIR/indices.npy, DIR/scores.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: batched, api, cpu baseline, extra legs, exchange_alt, rccl")
+    ap.add_argument("--batch-q", type=int, default=256, help="(--full) batched leg (config 3); 0 disables")
     ap.add_argument("--batch-steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-rows", type=int, default=1_000_000, help="row prefix the CPU baseline is timed on (BASELINE.md section 4)")
+    ap.add_argument("--cpu-rows", type=int, default=1_000_000, help="(--full) row prefix the CPU baseline is timed on (BASELINE.md section 4)")
     ap.add_argument("--extra", default="c2,c5,hamming,shard,f32batch,small",
-                    help="comma list of extra legs timed after the headline (one GPU): c2,c5,hamming,shard,f32batch,small; '' = none")
+                    help="(--full) comma list of extra legs timed after the headline (one GPU): c2,c5,hamming,shard,f32batch,small; '' = none")
     ap.add_argument("--pmc-traffic", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, idx, sc):
+    """What the timed path returned in its last step: row indices (int64, exact in float64) and scores (float32).  Above
+    DUMP_MAX_BYTES (a --k near N) a fixed, seeded sample of the ranks is written, the same columns of both arrays."""
+    idx, sc = np.asarray(idx), np.asarray(sc)
+    per_rank = idx.shape[0] * (8 + 4)
+    if idx.shape[1] * per_rank > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(idx.shape[1], DUMP_MAX_BYTES // per_rank, replace=False))
+        idx, sc = idx[:, keep], sc[:, keep]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "indices.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), sc.astype(np.float32))
 
 
 def make_shard(n_total, d, dtype, rank, world, device):
@@ -371,13 +393,16 @@ def main():
     local.set_option("profile", 1)
     barrier()
     lat = np.empty(args.steps)
+    last = None
     t_start = time.perf_counter()
     for i in range(args.steps):
         t0 = time.perf_counter()
-        sharded.query(Q[args.warmup + i:args.warmup + i + 1], args.k, mid)   # ends with D2H + sync
+        last = sharded.query(Q[args.warmup + i:args.warmup + i + 1], args.k, mid)   # ends with D2H + sync
         lat[i] = time.perf_counter() - t0
     barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, *last)
     scan_ns = local.stat("scan_time_ns")
     scan_launches = local.stat("scan_launches")
     local.set_option("profile", 0)
@@ -398,7 +423,7 @@ def main():
 
     # ---------------- batched leg: config 3 (Q=256 dot product) ----------------------------------
     batched = None
-    if args.batch_q > 0:
+    if args.full and args.batch_q > 0:
         bq = args.batch_q
         QB = make_queries(bq, args.d, tdtype, device).to(torch.float32)
         bmid = METRIC_IDS["dot_product"]
@@ -473,7 +498,7 @@ def main():
 
     exchange_desc = kind_of(sharded)
     rccl = None
-    if dist and world > 1:
+    if args.full and dist and world > 1:
         barrier()
         try:
             rccl = rccl_block(args, dist, rank, world, device, exchange_desc, tdtype, mid)
@@ -481,15 +506,16 @@ def main():
             rccl = {"error": repr(e)[:300]}
     exchange_alt = None
     if alt is not None:
-        barrier()
-        exchange_alt = {"kind": kind_of(alt), "p50_ms": 1e3 * p50_of(alt, min(args.steps, 50)),
-                        "calibration_p50_ms": {k: 1e3 * v for k, v in (calib or {}).items()}}
+        if args.full:
+            barrier()
+            exchange_alt = {"kind": kind_of(alt), "p50_ms": 1e3 * p50_of(alt, min(args.steps, 50)),
+                            "calibration_p50_ms": {k: 1e3 * v for k, v in (calib or {}).items()}}
         alt.close()
     sharded.close()
 
     # ---------------- the drop-in API on the same matrix (one GPU) ----------------------------------
     api = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         import hyperdb.ranking_algorithm as ranking
         from hyperdb import HyperDB
         steps_api = min(args.steps, 200)
@@ -533,11 +559,11 @@ def main():
                "entry_points": "hyperdb.ranking_algorithm.hyperDB_ranking_algorithm_sort(handle, q, top_k) / HyperDB.query(q, top_k)"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, V, Q)
 
     extras = []
-    if rank == 0 and world == 1 and args.extra:
+    if args.full and rank == 0 and world == 1 and args.extra:
         local.close()
         del sharded, local, V
         torch.cuda.empty_cache()

@@ -45,7 +45,7 @@ def stats(src, dst):
 
 
 def legs(src, dst, ratio=1.35):
-    """Per-launch-size statistics out of the kernel TRACE (one row per dispatch): the default bench command runs the same kernel
+    """Per-launch-size statistics out of the kernel TRACE (one row per dispatch): `bench.py --full` runs the same kernel
     on several matrices (headline 10M rows, the 1.25M-row shard leg, the small leg), which the plain --stats table averages together.
     The dispatches of each hdb_* kernel are sorted by duration and cut into clusters wherever two neighbours differ by more than
     `ratio`; every cluster is one line: name, calls, average / min / max ns.  bench.py's kernel_us of a leg is the average of the

@@ -49,7 +49,7 @@ trace)
   tail -4 $O/trace_overhead.log; guard $rc;;
 bench)
   step bench
-  timeout -k 10 600 python bench.py --steps 200 --warmup 10 > $O/bench_r2.log 2>&1; rc=$?
+  timeout -k 10 600 python bench.py --full --steps 200 --warmup 10 > $O/bench_r2.log 2>&1; rc=$?
   tail -2 $O/bench_r2.log; guard $rc;;
 esac
 done
