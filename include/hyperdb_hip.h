@@ -101,6 +101,30 @@ int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t m, void* de
 
 void hdb_index_destroy(hdb_index* ix);
 
+/* Opt-in int8 shadow of the matrix: quantized row scan with exact rescoring (local-hyperdb_amd/csrc/hdb_quant.hip).
+ * HDB_QUANT_I8 builds, next to the float16 / float32 matrix, an owned int8 copy -- one code per element at a row pitch
+ * P = round_up(d, 16) bytes -- and 12 bytes of per-row caches: N x (P + 12) bytes of device memory.  HDB_QUANT_NONE frees it.
+ * float64 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
+ * hdb_index_gather moves codes and caches with the kept rows, hdb_index_update rebuilds it, hdb_index_rebase leaves it alone.
+ *
+ * The bound.  Row r: s_r = max_j |v_rj| / 127, c_rj = rne(v_rj / s_r), eps_r = v_r - s_r c_r; the query likewise (s_q, c_q,
+ * delta_q = q - s_q c_q).  C_qr = c_q . c_r is exact in int32, and
+ *     |q.v_r - s_q s_r C_qr| <= ||q|| ||eps_r|| + ||delta_q|| s_r ||c_r||  (Cauchy-Schwarz),
+ * widened by the float32 rounding of the VALU scan's own sum (gamma_{d+8} ||q|| ||v_r||) and of the bound's evaluation; cosine
+ * and euclidean (through d^2 = ||v||^2 + ||q||^2 - 2 q.v) map the interval through the scan's epilogue, which is monotone, and the
+ * bias is added to both ends.  hdb_quant.hip derives it line by line.
+ *
+ * Dispatch.  hdb_topk takes the shadow for 1-4 dot / cosine / euclidean queries with k <= quant_max_k (<= 128) on a finite
+ * matrix of more than HDB_CAND_CAP rows, at least quant_min_n of them (-1: the measured rule), when use_quant is on, the call is
+ * not exact and force_exact is off.  Every row whose upper bound reaches T_s (the 16th largest lower bound of a strided row
+ * sample) is rescored from the original matrix in the lane split, chunk order and reduction order of the VALU scan, so the top-k
+ * -- indices and float32 score bits -- is the one hdb_scores / hdb_topk with use_mfma = 0 return.  A query whose list
+ * overflowed, or whose k-th rescored candidate does not score above T_s, gets HDB_Q_OVERFLOW / HDB_Q_UNDERFLOW like any sampled
+ * call (hdb_topk_host re-runs it exactly).  hdb_topk_exact never takes the shadow.
+ * Stats: quant (the last call took it), quant_cands (largest candidate list of that call; synchronises), quant_bytes. */
+enum hdb_quant { HDB_QUANT_NONE = 0, HDB_QUANT_I8 = 1 };
+int hdb_index_quantize(hdb_index* ix, int mode, void* stream);
+
 /* 1 if the matrix contains a NaN (synchronises `stream` of the create/update call). */
 int hdb_index_has_nan(hdb_index* ix, int* out_flag);
 
@@ -234,10 +258,11 @@ void hdb_group_destroy(hdb_group* g);
  *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
+ *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
- *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes. */
+ *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_bytes. */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

@@ -10,6 +10,7 @@
 //                 -> finalize.  Used for hamming (integer scores, massive ties), for queries whose
 //                 sampled threshold failed, and by tests as the on-device cross-check.
 #include "hdb_common.h"
+#include "hdb_quant.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
 #include <cmath>
@@ -72,6 +73,18 @@ int hdb_launch_full_sort(const float* scores, int64_t n, int64_t k, int64_t row_
                          int64_t* idx_out, float* score_out, void* stream);
 int hdb_launch_gather_rows(const void* V, const int64_t* rows, int64_t m, int row_bytes, void* out, const float* inv_in,
                            const float* sq_in, float* inv_out, float* sq_out, int* nan_flag, void* stream);
+int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype, int P, int8_t* codes, float* aux, int* nan_flag, double gamma,
+                          void* stream);
+int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m, int P, int8_t* codes_out,
+                            float* aux_out, void* stream);
+int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, void* stream);
+int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
+int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
+                             const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
+                             const uint32_t* cnt, uint32_t cap, void* stream);
+int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
+                              int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
+                              const float* qaux, const float* thr, int* stat, void* stream);
 int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
                               const float* Q, const float* qsq, int q0, const float* bias, void* stream);
 }
@@ -128,6 +141,13 @@ struct hdb_index {
     // device copy of the result record of hdb_topk_host (owned)
     char* rec = nullptr;
     size_t rec_bytes = 0;
+    // int8 shadow of the matrix (owned, hdb_index_quantize; hdb_quant.hip): codes [rows][qP], caches [rows][3]
+    int qmode = HDB_QUANT_NONE;
+    int8_t* qcodes = nullptr;
+    float* qaux = nullptr;
+    int64_t q_rows = 0;               // capacity in rows
+    int32_t qP = 0;                   // code pitch: d rounded up to 16 bytes
+    int* qstat = nullptr;             // device word: largest candidate count of the last quantized call
     // scratch (owned)
     char* ws = nullptr;
     size_t ws_bytes = 0;
@@ -164,6 +184,10 @@ struct hdb_index {
     int64_t fused_timeout_us = 2000;  // bound of every in-kernel spin of those kernels
     int64_t finalize_threads = 1024;  // workgroup size of hdb_finalize_kernel (256 | 512 | 1024)
     int64_t mfma_variant = 16;        // MFMA shape of the d=384 256-query pass (16 | 32)
+    int64_t use_quant = 1;            // 0: never the int8 shadow, even where one exists
+    int64_t quant_min_n = -1;         // ... from this many rows on (-1: the measured rule, quant_min_rows)
+    int64_t quant_max_k = 128;        // ... for k up to this (<= 128)
+    int64_t st_quant = 0;             // the last hdb_topk call took the int8 shadow
     // stats of the last hdb_topk call
     int64_t st_sample_rows = 0, st_sample_m = 0, st_path = 0, st_chunks = 0, st_mfma = 0, st_host_direct = 0, st_fused = 0, st_local = 0, st_f32s = 0;
     // host-side timing of hdb_topk_host (always on: four clock reads per call), cumulative since "host_timing_reset":
@@ -199,7 +223,7 @@ static int ensure_ws(hdb_index* ix, size_t bytes) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 100; }
+extern "C" int hdb_version(void) { return 101; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -215,6 +239,70 @@ static int build_caches(hdb_index* ix, hipStream_t st) {
     ix->flags_host = -1;
     ix->bits_valid = false; ix->bits_done = 0;         // a new matrix: nothing of the lazy caches survives
     ix->pscale_valid = false; ix->pscale_done = 0;
+    ix->build_stream = st;
+    return HDB_OK;
+}
+
+// ---- int8 shadow (hdb_quant.hip) --------------------------------------------------------------
+// gamma_{d+8} of the float32 VALU scan (hdb_quant.hip, bound (2)), with a relative margin for its own evaluation
+static double quant_gamma(int d) {
+    const double u = std::ldexp(1.0, -24), m = (double)(d + 8) * u;
+    return m / (1.0 - m) * (1.0 + std::ldexp(1.0, -20));
+}
+static size_t quant_elem(const hdb_index* ix) { return ix->dtype == HDB_F16 ? 2 : 4; }
+static void quant_free(hdb_index* ix) {
+    if (ix->qcodes) (void)hipFree(ix->qcodes);
+    if (ix->qaux) (void)hipFree(ix->qaux);
+    ix->qcodes = nullptr; ix->qaux = nullptr; ix->q_rows = 0;
+}
+// room for `need` rows; the first `keep` rows of codes and caches survive a reallocation
+static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t st) {
+    if (need <= ix->q_rows && ix->qcodes) return HDB_OK;
+    const int64_t rows = need + need / 2 + 64;
+    int8_t* c2 = nullptr; float* a2 = nullptr;
+    HIP_TRY(hipMalloc((void**)&c2, (size_t)rows * ix->qP));
+    hipError_t e = hipMalloc((void**)&a2, (size_t)rows * 3 * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(c2); return fail(HDB_ERR_NOMEM, std::string("hdb_index_quantize: ") + hipGetErrorString(e)); }
+    if (keep > 0 && ix->qcodes) {
+        HIP_TRY(hipMemcpyAsync(c2, ix->qcodes, (size_t)keep * ix->qP, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a2, ix->qaux, (size_t)keep * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    quant_free(ix);
+    ix->qcodes = c2; ix->qaux = a2; ix->q_rows = rows;
+    return HDB_OK;
+}
+// quantize rows [row0, row0 + m) of the current matrix into the shadow
+static int quant_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
+    if (m <= 0) return HDB_OK;
+    const char* src = (const char*)ix->V + (size_t)row0 * ix->d * quant_elem(ix);
+    LAUNCH_TRY(hdb_launch_quant_rows(src, m, ix->d, ix->dtype, ix->qP, ix->qcodes + (size_t)row0 * ix->qP, ix->qaux + (size_t)row0 * 3,
+                                     ix->nan_flag, quant_gamma(ix->d), st));
+    return HDB_OK;
+}
+
+extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
+    if (!ix) return fail(HDB_ERR_ARG, "hdb_index_quantize: null index");
+    if (mode != HDB_QUANT_NONE && mode != HDB_QUANT_I8) return fail(HDB_ERR_ARG, "hdb_index_quantize: mode must be HDB_QUANT_NONE or HDB_QUANT_I8");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == HDB_QUANT_NONE) {
+        if (ix->qcodes) HIP_TRY(hipStreamSynchronize(st));
+        quant_free(ix);
+        ix->qmode = HDB_QUANT_NONE;
+        return HDB_OK;
+    }
+    if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
+    if (!ix->qstat) {
+        HIP_TRY(hipMalloc((void**)&ix->qstat, sizeof(int)));
+        HIP_TRY(hipMemsetAsync(ix->qstat, 0, sizeof(int), st));
+    }
+    ix->qP = (int32_t)align_up((size_t)ix->d, 16);
+    int rc = quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st);
+    if (rc) return rc;
+    rc = quant_rows(ix, 0, ix->n, st);
+    if (rc) return rc;
+    ix->qmode = HDB_QUANT_I8;
     ix->build_stream = st;
     return HDB_OK;
 }
@@ -245,7 +333,12 @@ extern "C" int hdb_index_update(hdb_index* ix, const void* dev_V, int64_t n, voi
     HIP_TRY(hipSetDevice(ix->device));
     ix->V = dev_V; ix->n = n;
     ix->bias = nullptr; ix->mask = nullptr;
-    return build_caches(ix, (hipStream_t)stream);
+    int rc = build_caches(ix, (hipStream_t)stream);
+    if (rc == HDB_OK && ix->qmode == HDB_QUANT_I8) {          // a new matrix: the whole shadow is rebuilt
+        rc = quant_reserve(ix, std::max<int64_t>(n, 1), 0, (hipStream_t)stream);
+        if (rc == HDB_OK) rc = quant_rows(ix, 0, n, (hipStream_t)stream);
+    }
+    return rc;
 }
 
 extern "C" int hdb_index_rebase(hdb_index* ix, const void* dev_V) {
@@ -288,6 +381,11 @@ extern "C" int hdb_index_extend(hdb_index* ix, int64_t new_n, void* stream) {
     const char* tail = (const char*)ix->V + (size_t)old_n * ix->d * elem;
     LAUNCH_TRY(hdb_launch_rownorm(tail, new_n - old_n, ix->d, ix->dtype, ix->inv_norm + old_n, ix->sqnorm + old_n, ix->nan_flag, st));
     ix->n = new_n;
+    if (ix->qmode == HDB_QUANT_I8) {                   // the shadow: the appended rows only
+        int rc = quant_reserve(ix, new_n, old_n, st);
+        if (rc == HDB_OK) rc = quant_rows(ix, old_n, new_n - old_n, st);
+        if (rc) return rc;
+    }
     ix->flags_host = -1;
     ix->bits_valid = false;                            // (bits_done / pscale_done stay: the next hamming / pearson call packs the appended rows only)
     ix->pscale_valid = false;
@@ -311,8 +409,21 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     HIP_TRY(hipMemsetAsync(ix->nan_flag, 0, sizeof(int), st));
     int rc = hdb_launch_gather_rows(ix->V, dev_rows, m, (int)(ix->d * elem), dev_V_out, ix->inv_norm, ix->sqnorm, inv2, sq2,
                                     ix->nan_flag, st);
+    // the shadow travels with its rows too
+    int8_t* qc2 = nullptr; float* qa2 = nullptr;
+    if (rc == 0 && ix->qmode == HDB_QUANT_I8) {
+        rc = (int)hipMalloc((void**)&qc2, (size_t)rows * ix->qP);
+        if (rc == 0) rc = (int)hipMalloc((void**)&qa2, (size_t)rows * 3 * sizeof(float));
+        if (rc == 0) rc = hdb_launch_quant_gather(ix->qcodes, ix->qaux, dev_rows, m, ix->qP, qc2, qa2, st);
+    }
     if (rc == 0) rc = (int)hipStreamSynchronize(st);          // the old caches (and the caller's old matrix) are free after this
-    if (rc != 0) { (void)hipFree(inv2); (void)hipFree(sq2); return fail(HDB_ERR_HIP, std::string("hdb_index_gather: ") + hipGetErrorString((hipError_t)rc)); }
+    if (rc != 0) {
+        (void)hipFree(inv2); (void)hipFree(sq2);
+        if (qc2) (void)hipFree(qc2);
+        if (qa2) (void)hipFree(qa2);
+        return fail(HDB_ERR_HIP, std::string("hdb_index_gather: ") + hipGetErrorString((hipError_t)rc));
+    }
+    if (ix->qmode == HDB_QUANT_I8) { quant_free(ix); ix->qcodes = qc2; ix->qaux = qa2; ix->q_rows = rows; }
     if (ix->inv_norm) { (void)hipFree(ix->inv_norm); (void)hipFree(ix->sqnorm); }
     ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
     ix->V = dev_V_out; ix->n = m;
@@ -337,6 +448,8 @@ extern "C" void hdb_index_destroy(hdb_index* ix) {
     if (ix->bctl) (void)hipFree(ix->bctl);
     if (ix->ws) (void)hipFree(ix->ws);
     if (ix->rec) (void)hipFree(ix->rec);
+    quant_free(ix);
+    if (ix->qstat) (void)hipFree(ix->qstat);
     for (hipEvent_t e : ix->ev_pool) (void)hipEventDestroy(e);
     delete ix;
 }
@@ -402,6 +515,9 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "f32_split")) ix->f32_split = value;
     else if (!strcmp(name, "f32_split_min_q")) ix->f32_split_min_q = value;
     else if (!strcmp(name, "bits_max_q")) ix->bits_max_q = value;
+    else if (!strcmp(name, "use_quant")) ix->use_quant = value;
+    else if (!strcmp(name, "quant_min_n")) ix->quant_min_n = value;
+    else if (!strcmp(name, "quant_max_k")) ix->quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -420,6 +536,17 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "fused")) *value = ix->st_fused;
     else if (!strcmp(name, "local")) *value = ix->st_local;
     else if (!strcmp(name, "cand_cap")) *value = HDB_CAND_CAP;
+    else if (!strcmp(name, "quant")) *value = ix->st_quant;
+    else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
+    else if (!strcmp(name, "quant_cands")) {          // synchronises the device
+        int h = 0;
+        if (ix->st_quant && ix->qstat) {
+            HIP_TRY(hipSetDevice(ix->device));
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(&h, ix->qstat, sizeof(int), hipMemcpyDeviceToHost));
+        }
+        *value = h;
+    }
     else if (!strcmp(name, "n")) *value = ix->n;
     else if (!strcmp(name, "ws_bytes")) *value = (int64_t)ix->ws_bytes;
     else if (!strcmp(name, "scan_launches")) *value = (int64_t)(ix->ev_used / 2);
@@ -587,6 +714,65 @@ static void sample_plan(const hdb_index* ix, uint32_t kk, int nq, int tile_rows,
     stride = std::max<int64_t>(1, all_tiles / std::max<int64_t>(tiles, 1));
 }
 
+// Smallest matrix that takes the int8 shadow when quant_min_n is -1 (measured): below it the extra launches
+// of the quantized pipeline cost more than the bytes it saves.
+static int64_t quant_min_rows(const hdb_index* ix) {
+    return ix->dtype == HDB_F16 ? 1250000 : 500000;
+}
+
+// 1-4 dot / cosine / euclidean queries through the int8 shadow (hdb_quant.hip): quantized query prep, lower bounds on a strided row
+// sample, T_s = 16th largest of them, the pass over the shadow that keeps rows whose upper bound reaches T_s, exact rescoring of
+// those from the matrix, finalize with the floor T_s.  The sample aims at ~512 rows of the whole matrix with a lower bound above
+// T_s (the upper bounds let several times that many through; a sample of 16 keeps P(fewer than k = 128 such rows) near 1e-5).
+static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
+                      float* dev_score, int32_t* dev_status, hipStream_t st) {
+    const int64_t n = ix->n;
+    const int P = ix->qP;
+    const uint32_t m = 16;
+    const int64_t all_tiles = n / 16;
+    int64_t s_tiles = ((std::max<int64_t>((int64_t)((double)m * (double)n / 512.0), 16 * (int64_t)m)) + 15) / 16;
+    s_tiles = std::max<int64_t>(1, std::min(s_tiles, all_tiles));
+    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
+    const int64_t s_rows = s_tiles * 16;
+    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    size_t need = 8 * align_up((size_t)nq * 4, 256) + 4096;
+    need += align_up((size_t)nq * P, 256) + align_up((size_t)nq * HDB_QQ_WORDS * 4, 256);
+    need += align_up((size_t)nq * 4 * HDB_CNT_STRIDE, 256) + 256;
+    need += align_up((size_t)nq * HDB_CAND_CAP * 8, 256) + align_up((size_t)nq * ld_s * 4, 256);
+    int rc = ensure_ws(ix, need);
+    if (rc) return rc;
+    Bump b(ix->ws, ix->ws_bytes);
+    float* qinv = b.take<float>(nq); float* qsq = b.take<float>(nq); int* qnan = b.take<int>(nq);
+    int8_t* qcodes = b.take<int8_t>((size_t)nq * P);
+    float* qaux = b.take<float>((size_t)nq * HDB_QQ_WORDS);
+    float* thr = b.take<float>(nq);
+    uint32_t* cnt = b.take<uint32_t>((size_t)nq * HDB_CNT_STRIDE);
+    unsigned long long* cand = b.take<unsigned long long>((size_t)nq * HDB_CAND_CAP);
+    float* sbuf = b.take<float>((size_t)nq * ld_s);
+    // 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||)
+    LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
+    LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, st));
+    QuantArgs a; memset(&a, 0, sizeof(a));
+    a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
+    a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = nq;
+    a.gamma = (float)quant_gamma(ix->d);
+    a.ntiles = s_tiles; a.tile_stride = s_stride; a.scores = sbuf; a.ld = ld_s;
+    LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->max_blocks, st));
+    LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, nq, m, thr, cnt, nullptr, st));
+    a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
+    a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
+    prof_begin(ix, st);
+    LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->max_blocks, st));
+    prof_end(ix, st);
+    LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, qinv, ix->bias, ix->mask,
+                                        cand, cnt, HDB_CAND_CAP, st));
+    LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, qnan,
+                                         qaux, thr, ix->qstat, st));
+    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
+    ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
+    return HDB_OK;
+}
+
 static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
                      float* dev_score, int32_t* dev_status, void* stream, bool exact) {
     if (!ix || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, "hdb_topk: null argument");
@@ -598,6 +784,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (metric == HDB_PEARSON && ix->d < 1) return fail(HDB_ERR_ARG, "hdb_topk: pearson needs d >= 1");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
+    ix->st_quant = 0;
     const bool f64 = ix->dtype == HDB_F64;
     const int64_t n = ix->n;
     const uint32_t kk = (uint32_t)std::min<int64_t>(k, n);
@@ -617,6 +804,15 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (is_ham && !small && !ix->bits_fused) exact = true;
     if (ix->force_exact && !small) exact = true;
     if (!small && (int64_t)kk * 32 > n) exact = true;        // k is a large share of the rows: a sampled threshold cannot help
+    // the int8 shadow (hdb_index_quantize): 1-4 dot / cosine / euclidean queries on a finite float16 / float32 matrix; same answer
+    if (ix->qmode == HDB_QUANT_I8 && ix->use_quant && !exact && !small && dev_status != nullptr && nq >= 1 && nq <= 4 &&
+        k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN) &&
+        (ix->dtype == HDB_F16 || ix->dtype == HDB_F32) && n >= (ix->quant_min_n >= 0 ? ix->quant_min_n : quant_min_rows(ix))) {
+        bool finite = false;
+        const int rcf = matrix_is_finite(ix, &finite);
+        if (rcf != HDB_OK) return rcf;
+        if (finite) return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st);
+    }
     // fp32 matrices: the VALU scan serves up to 4 queries in one pass at HBM speed; the fp32 MFMA scan (matrix-pipe
     // bound at 157 TFLOP/s) takes over where a second VALU pass would start
     // (rows that need K slices -- float32 d >= 1024, fp16 d >= 2048 -- likewise: up to 4 queries are one VALU pass at HBM speed, the
@@ -1117,12 +1313,14 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     const size_t qbytes = (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4);
     std::vector<char> bad(nq);
     for (int q = 0; q < nq; ++q) bad[q] = (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) != 0;     // the re-run rewrites h_st
+    const int64_t quant_first = ix->st_quant;            // ("quant" reports the call's first attempt)
     for (int q = 0; q < nq; ++q) {
         if (!bad[q]) continue;
         rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, k, metric, d_idx + (size_t)q * k,
                        d_sc + (size_t)q * k, d_st + q, stream, true);
         if (rc) return rc;
     }
+    ix->st_quant = quant_first;
     if (!direct) HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HDB_OK;

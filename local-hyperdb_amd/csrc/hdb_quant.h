@@ -1,0 +1,37 @@
+// hdb_quant.h -- arguments of the int8 shadow kernels (hdb_quant.hip), shared with hdb_api.hip.
+#pragma once
+#include <stdint.h>
+
+// Per-row cache of the shadow: three floats per row, [row][3].
+#define HDB_QROW_S 0      // s_r = max_j |v_rj| / 127
+#define HDB_QROW_E 1      // ||eps_r||_2 + gamma_d ||v_r||_2, rounded up
+#define HDB_QROW_T 2      // s_r ||c_r||_2, rounded up
+// Per-query record written by the quantized query prep: eight floats per query.
+#define HDB_QQ_S 0        // s_q
+#define HDB_QQ_N 1        // ||q||_2, rounded up
+#define HDB_QQ_D 2        // ||delta_q||_2, rounded up
+#define HDB_QQ_SQ 3       // ||q||^2 (float64 sum rounded to nearest)
+#define HDB_QQ_BAD 4      // non-zero: the query is not finite (the call leaves it to the exact re-run)
+#define HDB_QQ_WORDS 8
+
+struct QuantArgs {
+    const int8_t* codes;      // [n][P] int8 codes of the rows, zero-padded
+    int64_t n;
+    int32_t d;
+    int32_t P;                // code pitch in bytes: d rounded up to 16
+    const float* aux;         // [n][3] per-row cache
+    const float* sqnorm;      // [n] ||v||^2 of the float32 row cache (euclidean)
+    const float* inv_norm;    // [n] 1/||v|| (cosine)
+    const int8_t* qcodes;     // [nq][P]
+    const float* qaux;        // [nq][HDB_QQ_WORDS]
+    const float* qinv;        // [nq] 1/||q|| as the VALU scan's query prep computes it
+    const float* bias;        // [n] or nullptr
+    const uint8_t* mask;      // [n] or nullptr
+    int32_t metric;
+    int32_t nq;
+    float gamma;              // rounding-error factor of the float32 VALU scan, gamma_{d+8}
+    int64_t ntiles;           // 16-row tiles to visit
+    int64_t tile_stride;      // 1 = dense; > 1 = strided sample (hdb_tile_index)
+    float* scores; int64_t ld;                            // MODE 0: lower bounds of the sampled rows
+    const float* thr; uint32_t* cnt; unsigned long long* cand; uint32_t cap;   // MODE 1: candidate lists
+};

@@ -1,0 +1,558 @@
+// hdb_quant.hip -- the opt-in int8 shadow of the stored matrix: quantized row scan with exact rescoring (gfx950).
+//
+// The index may keep an int8 copy of its N x d matrix (hdb_index_quantize): one code byte per element at a row pitch
+// P = round_up(d, 16) bytes (zero-padded, so every row streams in 16-byte pieces whatever d is) and three floats per row.
+// A top-k call of 1-4 dot / cosine / euclidean queries then reads P + 12 bytes per row instead of 2d or 4d, scores every row
+// approximately with v_dot4_i32_i8 (exact int32 sums), keeps the rows whose UPPER bound can still reach a sampled threshold,
+// rescores those from the original matrix with the VALU scan's own float32 arithmetic and selects.  The answer is the same
+// bits as the VALU scan (hdb_scan_kernel / hdb_scan_generic_kernel + hdb_emit) gives, not an approximation of it.
+//
+// ---- The bound ---------------------------------------------------------------------------------------------------------
+// Row r (values v_rj, j < d):   s_r = max_j |v_rj| / 127 (float32),  c_rj = rne(v_rj / s_r) in [-127, 127],
+//                               eps_r = v_r - s_r c_r (float64 at quantization time).
+// Query q (float32):            s_q, c_q, delta_q = q - s_q c_q, formed the same way.
+// C_qr = sum_j c_qj c_rj is exact in int32 (|C| <= 127^2 d < 2^31 for every d the index takes).
+// Since q.v_r = s_r (s_q C_qr + delta_q.c_r) + q.eps_r, Cauchy-Schwarz gives
+//     |q.v_r - s_q s_r C_qr| <= ||q|| ||eps_r|| + ||delta_q|| (s_r ||c_r||)  =: B_qr.                              (1)
+// The target is not the real dot product but the float32 sum S_f the VALU scan forms: per lane an fma chain of ceil(d/16)
+// steps, then a 4-level DPP tree (hdb_rows4_sum).  Each product enters at most d/16 + 5 <= d + 8 roundings, so
+//     |S_f - q.v_r| <= gamma ||q|| ||v_r||,  gamma = gamma_{d+8} = (d+8) u / (1 - (d+8) u),  u = 2^-24                (2)
+// (an absolute 2^-100 (d+8) covers underflow).  The per-row cache holds (all rounded UP from float64):
+//     aux[r] = { s_r,  E_r = ||eps_r|| + gamma ||v_r||,  T_r = s_r ||c_r|| }                 (12 bytes per row)
+// and the query prep: s_q, N_q = ||q|| (up), D_q = ||delta_q|| (up), ||q||^2.  With A = fl(fl(s_q s_r) fl(C)):
+//     B = (N_q E_r + D_q T_r)(1 + 2^-10) + |A| 2^-10 + 2^-100 (d+8)                                               (3)
+// bounds |S_f - A| by (1) + (2): the 2^-10 terms dominate every float32 rounding of A (<= 3u |A|, fl(C) adds u when
+// |C| >= 2^24) and of B itself (a few u relative), and later the rounding of A -/+ B (u (|A| + B)).
+// dot / cosine: the raw-sum interval is [A - B, A + B].
+// euclidean: the scan sums fl(x - q)^2 directly; with D2 = ||v||^2 + ||q||^2 - 2 q.v (real), E_f (its float sum) lies in
+//     D2 (1 -/+ 2 gamma) (one more rounding per element than (2)).  ||v||^2 comes from the float32 row cache sqnorm, itself within
+//     gamma of the real value: ||v||^2 in sq (1 -/+ 2 gamma).  So with c = sq + ||q||^2 - 2A and
+//     err = 2 gamma sq + 2B + 2^-10 (sq + ||q||^2 + 2|A|) + 2^-100 (d+8):
+//     E_f in [max(0, c - err)(1 - 2 gamma - 2^-10), (c + err)(1 + 2 gamma + 2^-10)].
+// Score domain: every map of hdb_emit is monotone in the raw sum (x -> fl(fl(x a) b) with a, b > 0 for cosine, x -> 1/(1+sqrt x)
+// non-increasing for euclidean, then + bias), so the same float operations applied to the raw bounds bound the final score.  The
+// compiler may contract hdb_emit's multiply and bias add into one fma, i.e. round once less than the bound's evaluation: the
+// bounds are pushed outward by |s| 2^-20 + 1e-30 (many ulps) to cover that.  NaN never reaches a bound (finite matrix, finite
+// query; a NaN upper bound would count as +inf).
+//
+// ---- The pipeline (hdb_api.hip, quant_topk) ----------------------------------------------------------------------------
+//   query prep (hdb_qprep_kernel: 1/||q||, NaN flags) -> quantized query prep (codes, s_q, N_q, D_q)
+//   -> int8 scan over a strided row sample (MODE 0: lower bounds)  -> T_s = m-th largest sampled lower bound (hdb_sample_thr)
+//   -> int8 scan over all rows (MODE 1: row r is a candidate of q when its upper bound >= T_s)
+//   -> exact rescoring of the candidates from the original matrix -> finalize with the floor T_s.
+// Completeness: every row that was not emitted has exact score <= its upper bound < T_s.  The finalize checks that the kk-th
+// best rescored candidate scores ABOVE T_s (hdb_finalize_fast's floor); then every row missing from the list scores strictly
+// below the kk-th best, so the top kk, ties at the kk-th score included, are all in the list.  If the check fails (HDB_Q_UNDERFLOW)
+// or the list overflowed (HDB_Q_OVERFLOW) the status word says so and hdb_topk_host re-runs that query through the exact path.
+#include "hdb_common.h"
+#include "hdb_quant.h"
+#include "hdb_finalize.h"
+#include "../../include/hyperdb_hip.h"
+
+// Float32 of a non-negative float64, rounded up (the double itself carries a relative margin of 2^-40 for its own sums).
+__device__ __forceinline__ float hq_up(double x) {
+    x = x * (1.0 + 0x1p-40);
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+__device__ __forceinline__ float hq_f(__half v) { return __half2float(v); }
+__device__ __forceinline__ float hq_f(float v) { return v; }
+
+template <typename T> struct HqElem;
+template <> struct HqElem<__half> { static constexpr int EPC = 8; };
+template <> struct HqElem<float> { static constexpr int EPC = 4; };
+
+__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[8], __half*) {
+    const __half2* h = reinterpret_cast<const __half2*>(&raw);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { float2 f = __half22float2(h[i]); x[2 * i] = f.x; x[2 * i + 1] = f.y; }
+}
+__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[4], float*) {
+    x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
+    x[2] = __uint_as_float(raw.z); x[3] = __uint_as_float(raw.w);
+}
+
+// code of one element: rne(x / s) clamped to [-127, 127] (|x| <= 127 s up to the rounding of s), 0 for s == 0
+__device__ __forceinline__ int hq_code(double x, float s) {
+    if (!(s > 0.f)) return 0;
+    double c = rint(x / (double)s);
+    c = c > 127.0 ? 127.0 : (c < -127.0 ? -127.0 : c);
+    return (int)c;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Row quantization: one wave per row.  codes[r][0..P) (zero past d), aux[r] = {s_r, E_r, T_r}; non-finite rows raise the
+// index's NaN flag (1: a NaN, 2: an infinity), as hdb_rownorm_kernel does -- the quantized path is declined on such matrices.
+// ------------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void hdb_quant_rows_kernel(const T* V, int64_t n, int d, int P, int8_t* codes, float* aux,
+                                                             int* nan_flag, double gamma) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
+    for (int64_t r = wave; r < n; r += nwaves) {
+        const T* row = V + r * (int64_t)d;
+        float amax = 0.f;
+        double ss = 0.0;
+        bool has_nan = false, has_inf = false;
+        for (int e = lane; e < d; e += 64) {
+            const float x = hq_f(row[e]);
+            if (x != x) has_nan = true;
+            else if (x - x != 0.f) has_inf = true;
+            amax = fmaxf(amax, fabsf(x));
+            ss += (double)x * (double)x;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { amax = fmaxf(amax, __shfl_xor(amax, o, 64)); ss += __shfl_xor(ss, o, 64); }
+        const bool nanr = __ballot(has_nan) != 0ull, infr = __ballot(has_inf) != 0ull;
+        const bool bad = nanr || infr;
+        const float s = bad ? 0.f : amax / 127.f;
+        double ee = 0.0, cc = 0.0;
+        for (int e = lane; e < P; e += 64) {
+            int c = 0;
+            if (e < d && !bad) {
+                const double x = (double)hq_f(row[e]);
+                c = hq_code(x, s);
+                const double eps = x - (double)s * (double)c;       // exact in float64: s has 24 bits, c 8
+                ee += eps * eps;
+                cc += (double)c * (double)c;
+            }
+            codes[r * (int64_t)P + e] = (int8_t)c;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { ee += __shfl_xor(ee, o, 64); cc += __shfl_xor(cc, o, 64); }
+        if (lane == 0) {
+            if (nanr) atomicOr(nan_flag, 1);
+            else if (infr) atomicOr(nan_flag, 2);
+            aux[3 * r + HDB_QROW_S] = s;
+            aux[3 * r + HDB_QROW_E] = bad ? 0.f : hq_up(sqrt(ee) + gamma * sqrt(ss));
+            aux[3 * r + HDB_QROW_T] = bad ? 0.f : hq_up((double)s * sqrt(cc));
+        }
+    }
+}
+
+// Compaction: codes and caches travel with their rows (hdb_index_gather).  One wave per kept row.
+__global__ __launch_bounds__(256) void hdb_quant_gather_kernel(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m,
+                                                               int P, int8_t* codes_out, float* aux_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
+    for (int64_t j = wave; j < m; j += nwaves) {
+        const int64_t r = rows[j];
+        for (int c = lane * 16; c < P; c += 64 * 16)
+            *reinterpret_cast<uint4*>(codes_out + j * (int64_t)P + c) = *reinterpret_cast<const uint4*>(codes + r * (int64_t)P + c);
+        if (lane < 3) aux_out[3 * j + lane] = aux[3 * r + lane];
+    }
+}
+
+// Quantized query prep: one wave per query (float32 queries).  qcodes[q][0..P), qaux[q] = {s_q, N_q, D_q, ||q||^2, bad}.
+// Word 0 of `stat` (the largest candidate count of the call) is reset here, ahead of the finalize that raises it.
+__global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (q >= nq) return;
+    if (q == 0 && lane == 0 && stat) stat[0] = 0;
+    const float* qr = Q + (int64_t)q * d;
+    float amax = 0.f;
+    bool bad = false;
+    for (int e = lane; e < d; e += 64) {
+        const float x = qr[e];
+        if (!(x - x == 0.f)) bad = true;
+        amax = fmaxf(amax, fabsf(x));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    bad = __ballot(bad) != 0ull;
+    const float s = bad ? 0.f : amax / 127.f;
+    double nn = 0.0, dd = 0.0;
+    for (int e = lane; e < P; e += 64) {
+        int c = 0;
+        if (e < d && !bad) {
+            const double x = (double)qr[e];
+            c = hq_code(x, s);
+            const double del = x - (double)s * (double)c;
+            nn += x * x;
+            dd += del * del;
+        }
+        qcodes[(int64_t)q * P + e] = (int8_t)c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64); }
+    if (lane == 0) {
+        float* o = qaux + (int64_t)q * HDB_QQ_WORDS;
+        const float sq = (float)nn;
+        const bool big = !(sq - sq == 0.f);                 // ||q||^2 overflows float32: leave the query to the exact re-run
+        o[HDB_QQ_S] = s;
+        o[HDB_QQ_N] = bad ? 0.f : hq_up(sqrt(nn));
+        o[HDB_QQ_D] = bad ? 0.f : hq_up(sqrt(dd));
+        o[HDB_QQ_SQ] = sq;
+        o[HDB_QQ_BAD] = (bad || big) ? 1.f : 0.f;
+        o[5] = 0.f; o[6] = 0.f; o[7] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// int8 scan.  Tiling as hdb_scan_kernel: a wave covers 16 consecutive rows, lane group g = lane >> 4 owns rows 4g..4g+3 and its
+// 16 lanes stride over the row's 16-byte pieces (non-temporal loads; the shadow is streamed once per call).  The NQ queries'
+// codes sit in LDS; sums are exact int32 (v_dot4_i32_i8), so the 16-lane reduction may take any order.
+// MODE 0: lower bounds of the sampled rows -> scores[q][ld];  MODE 1: rows whose upper bound reaches thr[q] -> candidate lists.
+// NJ > 0: rows of at most NJ * 256 bytes, all loads of a tile issued before the first dot product; NJ == 0: any width.
+// ------------------------------------------------------------------------------------------------------------------------
+#define HQ_STAGE_CAP 128
+struct HqStage {
+    unsigned long long buf[4][HQ_STAGE_CAP];
+    unsigned int cnt[4];
+    unsigned int base;
+};
+
+__device__ __forceinline__ int hq_dpp_i(int x, int ctrl_id) {
+    switch (ctrl_id) {
+    case 0: return __builtin_amdgcn_update_dpp(0, x, HDB_DPP_MIRROR, 0xF, 0xF, false);
+    case 1: return __builtin_amdgcn_update_dpp(0, x, HDB_DPP_HALF_MIRROR, 0xF, 0xF, false);
+    case 2: return __builtin_amdgcn_update_dpp(0, x, HDB_DPP_XOR2, 0xF, 0xF, false);
+    default: return __builtin_amdgcn_update_dpp(0, x, HDB_DPP_XOR1, 0xF, 0xF, false);
+    }
+}
+// hdb_rows4_sum for int32 partial sums: on return lane l16 holds the sum of row hdb_owned_row(l16) of its group
+__device__ __forceinline__ int hq_rows4_sum(int a0, int a1, int a2, int a3, int l16) {
+    const bool b3 = (l16 & 8) != 0, b2 = (l16 & 4) != 0;
+    const int v01 = (b3 ? a1 : a0) + hq_dpp_i(b3 ? a0 : a1, 0);
+    const int v23 = (b3 ? a3 : a2) + hq_dpp_i(b3 ? a2 : a3, 0);
+    int w = (b2 ? v23 : v01) + hq_dpp_i(b2 ? v01 : v23, 1);
+    w += hq_dpp_i(w, 2);
+    w += hq_dpp_i(w, 3);
+    return w;
+}
+
+template <int MODE, int NQ, int NJ>
+__global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int4* qs = reinterpret_cast<int4*>(smem);                       // [NQ][nch]
+    __shared__ HqStage stage;
+    const int nch = a.P >> 4;
+    if (MODE == 1 && threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
+    for (int i = threadIdx.x; i < NQ * nch; i += 256) qs[i] = reinterpret_cast<const int4*>(a.qcodes)[i];
+    float q_s[NQ], q_n[NQ], q_d[NQ], q_sq[NQ], q_inv[NQ], q_thr[NQ];
+    bool q_bad[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const float* o = a.qaux + (int64_t)q * HDB_QQ_WORDS;
+        q_s[q] = o[HDB_QQ_S]; q_n[q] = o[HDB_QQ_N]; q_d[q] = o[HDB_QQ_D]; q_sq[q] = o[HDB_QQ_SQ]; q_bad[q] = o[HDB_QQ_BAD] != 0.f;
+        q_inv[q] = a.metric == HDB_COSINE ? a.qinv[q] : 1.f;
+        q_thr[q] = MODE == 1 ? a.thr[q] : 0.f;
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, l16 = lane & 15;
+    const int nj = NJ > 0 ? NJ : (nch + 15) >> 4;
+    constexpr int G = NJ > 0 ? NJ : 2;
+    const float absmin = 0x1p-100f * (float)(a.d + 8);
+    const float g2 = 2.f * a.gamma;
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < a.ntiles; t += (int64_t)gridDim.x * 4) {
+        const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
+        const int8_t* p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = a.codes + min(r0 + u, a.n - 1) * (int64_t)a.P;
+        int acc[4][NQ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) acc[u][q] = 0;
+        for (int j0 = 0; j0 < nj; j0 += G) {
+            uint4 raw[G][4];
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const int c = l16 + 16 * (j0 + j);
+                const bool live = (j0 + j) < nj && c < nch;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (live) {
+                        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p[u] + (int64_t)c * 16));
+                        raw[j][u] = make_uint4(v.x, v.y, v.z, v.w);
+                    } else {
+                        raw[j][u] = make_uint4(0u, 0u, 0u, 0u);
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);           // loads ahead of every use
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const int c = l16 + 16 * (j0 + j);
+                const int cc = c < nch ? c : 0;          // (dead pieces are zero: any query piece gives 0)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int4 qv = qs[q * nch + cc];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        int s = acc[u][q];
+                        s = __builtin_amdgcn_sdot4((int)raw[j][u].x, qv.x, s, false);
+                        s = __builtin_amdgcn_sdot4((int)raw[j][u].y, qv.y, s, false);
+                        s = __builtin_amdgcn_sdot4((int)raw[j][u].z, qv.z, s, false);
+                        s = __builtin_amdgcn_sdot4((int)raw[j][u].w, qv.w, s, false);
+                        acc[u][q] = s;
+                    }
+                }
+            }
+        }
+        const int u_own = hdb_owned_row(l16);
+        const int64_t row = r0 + u_own;
+        int C[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) C[q] = hq_rows4_sum(acc[0][q], acc[1][q], acc[2][q], acc[3][q], l16);
+        if ((l16 & 3) != 0) continue;
+        const int64_t out_i = t * 16 + 4 * g + u_own;
+        if (row >= a.n) {
+            if (MODE == 0)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) a.scores[(int64_t)q * a.ld + out_i] = -INFINITY;
+            continue;
+        }
+        const float s_r = a.aux[3 * row + HDB_QROW_S], e_r = a.aux[3 * row + HDB_QROW_E], t_r = a.aux[3 * row + HDB_QROW_T];
+        const bool masked = a.mask && !a.mask[row];
+        const float bias = a.bias ? a.bias[row] : 0.f;
+        const float invn = a.metric == HDB_COSINE ? a.inv_norm[row] : 1.f;
+        const float sqv = a.metric == HDB_EUCLIDEAN ? a.sqnorm[row] : 0.f;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            float lo = -INFINITY, hi = -INFINITY;
+            if (!q_bad[q] && !masked) {
+                const float A = (q_s[q] * s_r) * (float)C[q];
+                const float aA = fabsf(A);
+                const float B = (q_n[q] * e_r + q_d[q] * t_r) * (1.f + 0x1p-10f) + aA * 0x1p-10f + absmin;
+                if (a.metric == HDB_EUCLIDEAN) {
+                    const float ctr = sqv + q_sq[q] - 2.f * A;
+                    const float err = g2 * sqv + 2.f * B + 0x1p-10f * (sqv + q_sq[q] + 2.f * aA) + absmin;
+                    const float elo = fmaxf(ctr - err, 0.f) * (1.f - g2 - 0x1p-10f);
+                    const float ehi = (ctr + err) * (1.f + g2 + 0x1p-10f);
+                    hi = (float)(1.f / (1.f + sqrt(elo)));
+                    lo = (float)(1.f / (1.f + sqrt(ehi)));
+                } else {
+                    lo = A - B; hi = A + B;
+                    if (a.metric == HDB_COSINE) { lo = lo * invn * q_inv[q]; hi = hi * invn * q_inv[q]; }
+                }
+                if (a.bias) { lo += bias; hi += bias; }
+                lo = lo - fabsf(lo) * 0x1p-20f - 1e-30f;
+                hi = hi + fabsf(hi) * 0x1p-20f + 1e-30f;
+                if (lo != lo) lo = -INFINITY;
+                if (hi != hi) hi = INFINITY;
+            }
+            if (MODE == 0) {
+                a.scores[(int64_t)q * a.ld + out_i] = lo;
+            } else if (!masked && !q_bad[q] && hi >= q_thr[q]) {
+                const unsigned long long ent = hdb_pack(hi, (uint32_t)row);
+                const unsigned int lp = atomicAdd(&stage.cnt[q], 1u);                    // LDS
+                if (lp < HQ_STAGE_CAP) stage.buf[q][lp] = ent;
+                else {
+                    const uint32_t pos = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], 1u);      // the slot is full: straight to the list
+                    if (pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = ent;
+                }
+            }
+        }
+    }
+    if (MODE == 1) {                                     // one atomic per block and query (hdb_stage_flush)
+        __syncthreads();
+        for (int q = 0; q < NQ; ++q) {
+            const unsigned int have = min(stage.cnt[q], (unsigned int)HQ_STAGE_CAP);
+            if (have == 0u) continue;
+            if (threadIdx.x == 0) stage.base = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], have);
+            __syncthreads();
+            const unsigned int base = stage.base;
+            for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
+                if (base + e < a.cap) a.cand[(int64_t)q * a.cap + base + e] = stage.buf[q][e];
+            __syncthreads();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Exact rescoring of the candidates from the ORIGINAL matrix.  A 16-lane group takes one candidate and forms its lanes' partial
+// sums exactly as hdb_scan_kernel (VEC: 16-byte pieces, lane l16 takes pieces l16 + 16 j, a dead piece adds (0 * q)) or
+// hdb_scan_generic_kernel (elements l16 + 16 i) does, then runs hdb_rows4_sum with the candidate in all four row slots and keeps
+// the lane that owns row slot (row & 3) -- the slot the row has in its dense tile -- so the same tree adds the same partials in the
+// same order.  hdb_emit's epilogue follows; the packed key is rewritten.
+// ------------------------------------------------------------------------------------------------------------------------
+struct RescoreArgs {
+    const void* V; int32_t d; int32_t row_bytes; int32_t nchunks;
+    const float* Q;           // [nq][d] float32, as the caller passed them
+    int32_t metric;
+    const float* inv_norm; const float* qinv; const float* bias; const uint8_t* mask;
+    unsigned long long* cand; const uint32_t* cnt; uint32_t cap;
+};
+
+template <typename T, int ACC, bool VEC>
+__global__ __launch_bounds__(256) void hdb_quant_rescore_kernel(RescoreArgs a) {
+    using Acc = float;
+    constexpr int EPC = HqElem<T>::EPC;
+    const int q = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, l16 = lane & 15;
+    const uint32_t total = min(a.cnt[q * HDB_CNT_STRIDE], a.cap);
+    const float* qv = a.Q + (int64_t)q * a.d;
+    const char* Vb = reinterpret_cast<const char*>(a.V);
+    const T* Vt = reinterpret_cast<const T*>(a.V);
+    for (uint32_t base = ((uint32_t)blockIdx.x * 4 + wave) * 4; base < total; base += gridDim.x * 16) {     // (wave-uniform)
+        const uint32_t i = base + g;
+        const bool valid = i < total;
+        const unsigned long long ent = valid ? a.cand[(int64_t)q * a.cap + i] : 0ull;
+        const uint32_t row = valid ? 0xFFFFFFFFu - (uint32_t)(ent & 0xFFFFFFFFull) : 0u;
+        Acc acc = Acc(0);
+        if constexpr (VEC) {
+            const char* pr = Vb + (int64_t)row * a.row_bytes;
+            const int nj = (a.nchunks + 15) >> 4;
+            for (int j = 0; j < nj; ++j) {
+                const int c = l16 + 16 * j;
+                const bool live = c < a.nchunks;
+                const int cc = live ? c : a.nchunks - 1;
+                const uint4 raw = *reinterpret_cast<const uint4*>(pr + (int64_t)cc * 16);
+                Acc x[EPC];
+                hq_unpack(raw, x, (T*)nullptr);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    const Acc qe = qv[cc * EPC + e];
+                    if (ACC == 1) {
+                        const Acc df = live ? x[e] - qe : Acc(0);
+                        acc += df * df;
+                    } else {
+                        acc += (live ? x[e] : Acc(0)) * qe;
+                    }
+                }
+            }
+        } else {
+            for (int e = l16; e < a.d; e += 16) {
+                const Acc qe = qv[e];
+                const Acc x = (Acc)hq_f(Vt[(int64_t)row * a.d + e]);
+                if (ACC == 1) { const Acc df = x - qe; acc += df * df; }
+                else acc += x * qe;
+            }
+        }
+        const Acc sum = hdb_rows4_sum(acc, acc, acc, acc, l16);
+        if (valid && (l16 & 3) == 0 && hdb_owned_row(l16) == (int)(row & 3u)) {
+            float s;                                      // hdb_emit, MODE 1
+            if (a.metric == HDB_EUCLIDEAN) {
+                s = (float)(Acc(1) / (Acc(1) + sqrt(sum)));
+            } else if (a.metric == HDB_COSINE) {
+                s = (float)sum * a.inv_norm[row] * a.qinv[q];
+            } else {
+                s = (float)sum;
+            }
+            if (a.bias) s += a.bias[row];
+            const bool masked = a.mask && !a.mask[row];
+            if (masked) s = -INFINITY;
+            s = hdb_canon(s);
+            a.cand[(int64_t)q * a.cap + i] = hdb_pack(s, row);
+        }
+    }
+}
+
+// Finalize: hdb_finalize_fast over the rescored list with the floor T_s (see "Completeness" above).  A query with an infinite
+// element, or one the quantized prep could not take, is reported as HDB_Q_UNDERFLOW: hdb_topk_host re-runs it exactly.
+__global__ __launch_bounds__(1024) void hdb_quant_finalize_kernel(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, uint32_t k,
+                                                                  uint32_t kk, int64_t row_base, int64_t* idx_out, float* score_out,
+                                                                  int32_t* status, const int* qnan, const float* qaux, const float* thr,
+                                                                  int* stat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long buf[];
+    const int q = blockIdx.x;
+    const uint32_t total = cnt[q * HDB_CNT_STRIDE];
+    if (threadIdx.x == 0 && stat) atomicMax(stat, (int)min(total, 0x7FFFFFFFu));
+    const int qn = qnan[q];
+    const bool bad = qaux[(int64_t)q * HDB_QQ_WORDS + HDB_QQ_BAD] != 0.f;
+    hdb_finalize_fast(buf, cand + (int64_t)q * cap, total, q, cap, k, kk, row_base, idx_out, score_out, status,
+                      qn & 1, ((qn & 2) || bad) ? (int32_t)HDB_Q_UNDERFLOW : 0, thr + q, 1.f);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// host-side launchers
+// ------------------------------------------------------------------------------------------------------------------------
+extern "C" int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype, int P, int8_t* codes, float* aux, int* nan_flag,
+                                     double gamma, void* stream) {
+    if (n <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = hdb_grid_for(n, 4, 8192);
+    if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_quant_rows_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, P, codes, aux, nan_flag, gamma);
+    else hipLaunchKernelGGL(hdb_quant_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, P, codes, aux, nan_flag, gamma);
+    return (int)hipGetLastError();
+}
+
+extern "C" int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m, int P, int8_t* codes_out,
+                                       float* aux_out, void* stream) {
+    if (m <= 0) return 0;
+    hipLaunchKernelGGL(hdb_quant_gather_kernel, dim3(hdb_grid_for(m, 4, 8192)), dim3(256), 0, (hipStream_t)stream, codes, aux, rows, m, P,
+                       codes_out, aux_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, void* stream) {
+    hipLaunchKernelGGL(hdb_quant_qprep_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, nq, d, P, qcodes, qaux, stat);
+    return (int)hipGetLastError();
+}
+
+template <int MODE, int NQ>
+static void hq_launch_scan_nq(const QuantArgs& a, int blocks, size_t lds, hipStream_t st) {
+    const int nch = a.P >> 4;
+    const int nj = (nch + 15) >> 4;
+    if (nj == 1) hipLaunchKernelGGL((hdb_quant_scan_kernel<MODE, NQ, 1>), dim3(blocks), dim3(256), lds, st, a);
+    else if (nj == 2) hipLaunchKernelGGL((hdb_quant_scan_kernel<MODE, NQ, 2>), dim3(blocks), dim3(256), lds, st, a);
+    else if (nj == 3) hipLaunchKernelGGL((hdb_quant_scan_kernel<MODE, NQ, 3>), dim3(blocks), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((hdb_quant_scan_kernel<MODE, NQ, 0>), dim3(blocks), dim3(256), lds, st, a);
+}
+template <int MODE>
+static void hq_launch_scan_mode(const QuantArgs& a, int blocks, size_t lds, hipStream_t st) {
+    switch (a.nq) {
+    case 1: hq_launch_scan_nq<MODE, 1>(a, blocks, lds, st); break;
+    case 2: hq_launch_scan_nq<MODE, 2>(a, blocks, lds, st); break;
+    case 3: hq_launch_scan_nq<MODE, 3>(a, blocks, lds, st); break;
+    default: hq_launch_scan_nq<MODE, 4>(a, blocks, lds, st); break;
+    }
+}
+// mode 0: lower bounds of the sampled tiles; mode 1: candidate emission over a.ntiles dense tiles.  1 <= a.nq <= 4.
+extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream) {
+    const QuantArgs& a = *args;
+    if (a.nq < 1 || a.nq > 4 || (a.P & 15) != 0) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)a.nq * a.P;
+    const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : 1024);
+    if (mode == 0) hq_launch_scan_mode<0>(a, blocks, lds, (hipStream_t)stream);
+    else hq_launch_scan_mode<1>(a, blocks, lds, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
+                                        const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
+                                        const uint32_t* cnt, uint32_t cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    RescoreArgs a;
+    a.V = V; a.d = d; a.Q = Q; a.metric = metric; a.inv_norm = inv_norm; a.qinv = qinv; a.bias = bias; a.mask = mask;
+    a.cand = cand; a.cnt = cnt; a.cap = cap;
+    const int elem = dtype == HDB_F16 ? 2 : 4;
+    a.row_bytes = d * elem;
+    a.nchunks = a.row_bytes / 16;
+    // the same choice as hdb_launch_scan: 16-byte pieces when rows are whole pieces of an aligned matrix
+    const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(V) & 15) == 0) && ((size_t)d * 4 <= 60 * 1024);
+    const bool euc = metric == HDB_EUCLIDEAN;
+    const dim3 grid((cap + 15) / 16 < 128 ? (cap + 15) / 16 : 128, nq);
+#define HQ_RESCORE(T_, ACC_, VEC_) hipLaunchKernelGGL((hdb_quant_rescore_kernel<T_, ACC_, VEC_>), grid, dim3(256), 0, st, a)
+    if (dtype == HDB_F16) {
+        if (vec) { if (euc) HQ_RESCORE(__half, 1, true); else HQ_RESCORE(__half, 0, true); }
+        else { if (euc) HQ_RESCORE(__half, 1, false); else HQ_RESCORE(__half, 0, false); }
+    } else {
+        if (vec) { if (euc) HQ_RESCORE(float, 1, true); else HQ_RESCORE(float, 0, true); }
+        else { if (euc) HQ_RESCORE(float, 1, false); else HQ_RESCORE(float, 0, false); }
+    }
+#undef HQ_RESCORE
+    return (int)hipGetLastError();
+}
+
+extern "C" int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
+                                         int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
+                                         const float* qaux, const float* thr, int* stat, void* stream) {
+    const size_t lds = (size_t)cap * 16 + 2048 * 4 + 64;
+    static unsigned long long attr_done = 0;
+    hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(hdb_quant_finalize_kernel), (int)lds, &attr_done);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(hdb_quant_finalize_kernel, dim3(nq), dim3(1024), lds, (hipStream_t)stream, cand, cnt, cap, k, kk, row_base,
+                       idx_out, score_out, status, qnan, qaux, thr, stat);
+    return (int)hipGetLastError();
+}

@@ -28,6 +28,8 @@ METRIC_IDS = {
 }
 EUCLIDEAN_DIST = 7
 Q_UNDERFLOW, Q_OVERFLOW, Q_NAN = 1, 2, 4
+HDB_QUANT_NONE, HDB_QUANT_I8 = 0, 1
+QUANT_MODES = {None: HDB_QUANT_NONE, "int8": HDB_QUANT_I8}
 HDB_MAX_K = 2048
 MERGE_DEVICE_CAP = 8192      # hdb_merge_topk / hdb_merge_topk_packed rank parts*k entries per query in LDS; beyond: hdb_merge_topk_host
 
@@ -40,6 +42,7 @@ EXPORTS = (
     "hdb_index_has_nan", "hdb_index_set_bias", "hdb_index_set_row_mask", "hdb_scores", "hdb_topk",
     "hdb_topk_exact", "hdb_merge_topk", "hdb_set_option", "hdb_get_stat", "hdb_recency_bias", "hdb_recency_bias_twice",
     "hdb_packed_bytes", "hdb_merge_topk_packed", "hdb_merge_topk_host", "hdb_host_exchange_merge", "hdb_topk_host",
+    "hdb_index_quantize",
 )
 
 
@@ -63,6 +66,7 @@ def _load():
     lib.hdb_index_extend.argtypes = [vp, i64, vp]
     lib.hdb_index_gather.argtypes = [vp, vp, i64, vp, vp]
     lib.hdb_index_set_row_base.argtypes = [vp, i64]
+    lib.hdb_index_quantize.argtypes = [vp, ctypes.c_int, vp]
     lib.hdb_group_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), i32]
     lib.hdb_group_topk_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp]
     lib.hdb_group_destroy.argtypes = [vp]
@@ -180,6 +184,7 @@ class GpuIndex:
         self._mask = None
         self._nan = None
         self._buf = None
+        self.quant = HDB_QUANT_NONE             # int8 shadow (quantize)
         self._qstage = OrderedDict()           # (nq, dtype) -> (pinned host tensor, its numpy view, device tensor or None, address the kernels read)
         self._host_records = OrderedDict()     # (nq, k) -> pinned record + views, owned by THIS index (small LRU)
         with torch.cuda.device(self.device):
@@ -245,6 +250,16 @@ class GpuIndex:
         self._buf = None                                    # the old capacity buffer is released with the old matrix
         _check(_lib.hdb_index_update(self._h, ctypes.c_void_p(t.data_ptr()), self.n, _stream_ptr(self.device)),
                "hdb_index_update")
+
+    def quantize(self, mode="int8"):
+        """Build (``"int8"``) or drop (``None``) the int8 shadow of the matrix (hdb_index_quantize): 1-4-query dot / cosine /
+        euclidean calls with k <= 128 then stream one byte per element and rescore the surviving rows exactly -- the same
+        indices and float32 scores as without it.  The shadow follows append / update / compact; it costs N x (round_up(d, 16)
+        + 12) bytes of device memory."""
+        mode = quant_mode(mode)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_index_quantize(self._h, mode, _stream_ptr(self.device)), "hdb_index_quantize")
+        self.quant = mode
 
     def set_row_base(self, row_base):
         self.row_base = int(row_base)
@@ -493,6 +508,15 @@ class GpuIndex:
         if (st[0] & Q_NAN) if len(st) == 1 else (st & Q_NAN).any():      # (one query: a scalar test instead of two array operations)
             raise ValueError(NAN_MESSAGE)
         return idx.copy(), sc.copy()
+
+
+def quant_mode(mode):
+    """Library code of a ``quantize=`` argument: None or "int8"; anything else raises ValueError."""
+    if mode is not None and not isinstance(mode, str):
+        raise ValueError(f"quantize must be None or 'int8', got {mode!r}")
+    if mode not in QUANT_MODES:
+        raise ValueError(f"quantize must be None or 'int8', got {mode!r}")
+    return QUANT_MODES[mode]
 
 
 def packed_bytes(nq, k):

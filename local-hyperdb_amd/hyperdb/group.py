@@ -155,6 +155,12 @@ class GpuGroup:
                 s.set_recency(ts[lo:hi], recency_bias, ts_max=ts_max)
         self._settle()
 
+    def quantize(self, mode="int8"):
+        """The int8 shadow on every shard (GpuIndex.quantize)."""
+        _native.quant_mode(mode)
+        for s in self.shards:
+            s.quantize(mode)
+
     def set_option(self, name, value):
         for s in self.shards:
             s.set_option(name, value)

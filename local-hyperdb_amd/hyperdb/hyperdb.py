@@ -52,6 +52,7 @@ import numpy as np
 import torch
 
 from . import ranking_algorithm as ranking
+from . import _native
 from ._native import GpuIndex, METRIC_IDS
 from .group import GpuGroup
 
@@ -64,7 +65,7 @@ _METRICS = ['dot_product', 'cosine_similarity', 'euclidean_metric', 'manhattan_d
 class HyperDB:
     def __init__(self, documents=None, vectors=None, select_keys=None, embedding_function=None, fp_precision="float32",
                  add_timestamp=False, metadata_keys=None, ann_metric="cosine", n_trees=10, cache_size=256, device=None,
-                 devices=None):
+                 devices=None, quantize=None):
         if fp_precision not in ["float16", "float32", "float64"]:
             raise ValueError("Unsupported floating-point precision.")                       # hyperdb.py:65-66
         accepted = ["angular", "euclidean", "manhattan", "hamming", "dot", "cosine"]
@@ -80,6 +81,8 @@ class HyperDB:
         self.ann_metric, self.n_trees = ann_metric, n_trees          # accepted for compatibility; no ANN is built
         self.device = device
         self.devices = list(devices) if devices else None      # several GPUs: the matrix is row-sharded over them (GpuGroup)
+        _native.quant_mode(quantize)                  # None | "int8": keep an int8 shadow of the matrix (GpuIndex.quantize; not saved)
+        self.quantize = quantize
         self.documents, self.source_indices = [], []
         self._index = None
         self._dead = np.zeros(0, dtype=np.int64)     # tombstoned device rows (ascending); see remove_document
@@ -134,6 +137,8 @@ class HyperDB:
         self._invalidate_rows()
         if self._index is None:
             self._index = GpuGroup(vectors, self.devices) if self.devices else GpuIndex(vectors, device=self.device)
+            if self.quantize is not None:             # (append / compact / update keep the shadow current from here on)
+                self._index.quantize(self.quantize)
         else:
             self._index.append(vectors)
 

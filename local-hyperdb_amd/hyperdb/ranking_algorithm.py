@@ -43,8 +43,11 @@ _ALL_METRICS = tuple(METRIC_IDS)
 class ResidentVectors:
     """Handle for a matrix registered on the GPU; pass it wherever ``vectors`` is expected."""
 
-    def __init__(self, vectors, device=None, devices=None):
+    def __init__(self, vectors, device=None, devices=None, quantize=None):
+        _native.quant_mode(quantize)                     # (ValueError before anything is uploaded)
         self.index = GpuGroup(vectors, devices) if devices else GpuIndex(vectors, device=device)
+        if quantize is not None:
+            self.index.quantize(quantize)
         arr_dtype = vectors.dtype if hasattr(vectors, "dtype") else None
         self.np_dtype = _np_dtype_of(arr_dtype, self.index)
 
@@ -59,10 +62,12 @@ class ResidentVectors:
         self.index.close()
 
 
-def register_vectors(vectors, device=None, devices=None):
+def register_vectors(vectors, device=None, devices=None, quantize=None):
     """Upload ``vectors`` once; returns a handle usable in place of ``vectors``.  ``devices=[...]`` row-shards the matrix
-    over several GPUs behind the same handle (single process, see hyperdb/group.py)."""
-    return ResidentVectors(vectors, device=device, devices=devices)
+    over several GPUs behind the same handle (single process, see hyperdb/group.py).  ``quantize="int8"`` also keeps an int8
+    shadow of the matrix that 1-4-query dot / cosine / euclidean calls scan first, rescoring the surviving rows exactly (same
+    answer, fewer bytes read; see GpuIndex.quantize)."""
+    return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize)
 
 
 _TORCH2NP = {torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64}
