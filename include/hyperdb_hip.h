@@ -121,7 +121,24 @@ void hdb_index_destroy(hdb_index* ix);
  * -- indices and float32 score bits -- is the one hdb_scores / hdb_topk with use_mfma = 0 return.  A query whose list
  * overflowed, or whose k-th rescored candidate does not score above T_s, gets HDB_Q_OVERFLOW / HDB_Q_UNDERFLOW like any sampled
  * call (hdb_topk_host re-runs it exactly).  hdb_topk_exact never takes the shadow.
- * Stats: quant (the last call took it), quant_cands (largest candidate list of that call; synchronises), quant_bytes. */
+ * Stats: quant (the last call took it), quant_cands (largest candidate list of that call; synchronises), quant_bytes.
+ *
+ * The automatic shadow (option auto_quant, default 1).  A float16 index answers 1-4 dot / cosine queries on the matrix cores, and
+ * those float32 score bits differ from the VALU scan's.  When auto_quant, use_quant and use_mfma are on, the index has no explicit
+ * shadow, the matrix is float16 and finite, and a call is eligible -- 1-4 queries the matrix cores would take, dot or cosine,
+ * k <= quant_max_k, not exact, no force_exact, a status pointer, and at least 2 000 000 rows of at most 512 elements (quant_min_n
+ * >= 0 replaces that rule: any row count from there on, any width the matrix cores take) -- the index builds the shadow on the
+ * first such call and answers it, and every later one, from it.  The candidates are then rescored on the matrix cores (gathered
+ * into a compact matrix and scored by the launch hdb_topk_exact uses for all rows), so indices and score bits are those of the
+ * default path and of hdb_topk_exact; the bound targets the matrix-core sum of the fp16-rounded query with gamma_m = (d + 8) 2^-22
+ * (hdb_quant.hip, bound (2m)).  Stats of such a call: quant = 1, mfma = 1 (the arithmetic the scores come from), path = 1,
+ * fused = 0; quant_auto = 1 while the index holds a shadow it built itself.
+ * Cost: the index grows by n x (round_up(d, 16) + 12) bytes of device memory (10M x 384: 3.96 GB beside 7.68 GB) and the first
+ * eligible call also pays the allocation and one pass over the matrix (10M x 384: 11.8 ms, 2.5M: 3.1 ms).  The build is skipped, silently
+ * and for good (until hdb_index_update), when hipMemGetInfo does not show room for the shadow, the call's workspace and 1 GiB
+ * beside them, or when an allocation fails.  hdb_index_quantize(HDB_QUANT_NONE) drops the shadow AND sets auto_quant = 0 for the
+ * handle; hdb_index_quantize(HDB_QUANT_I8) turns it into an explicit one (VALU bits, the rule above).  An index that only serves
+ * batches of 5+ queries, other metrics or small matrices never builds one. */
 enum hdb_quant { HDB_QUANT_NONE = 0, HDB_QUANT_I8 = 1 };
 int hdb_index_quantize(hdb_index* ix, int mode, void* stream);
 
@@ -258,11 +275,12 @@ void hdb_group_destroy(hdb_group* g);
  *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
- *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128).
+ *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),
+ *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
- *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_bytes. */
+ *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_bytes, quant_auto. */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

@@ -82,9 +82,16 @@ int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void*
 int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
                              const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
                              const uint32_t* cnt, uint32_t cap, void* stream);
+int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
+                            int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, void* stream);
+int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks);
+int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
+                             const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv, float* gbias,
+                             void* stream);
 int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
                               int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
-                              const float* qaux, const float* thr, int* stat, void* stream);
+                              const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
+                              void* stream);
 int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
                               const float* Q, const float* qsq, int q0, const float* bias, void* stream);
 }
@@ -148,6 +155,8 @@ struct hdb_index {
     int64_t q_rows = 0;               // capacity in rows
     int32_t qP = 0;                   // code pitch: d rounded up to 16 bytes
     int* qstat = nullptr;             // device word: largest candidate count of the last quantized call
+    bool qauto = false;               // the shadow was built by the index itself (auto_quant): its calls return the matrix cores' bits
+    bool qauto_declined = false;      // ... or could not be (memory): the decision stands until the matrix changes
     // scratch (owned)
     char* ws = nullptr;
     size_t ws_bytes = 0;
@@ -187,6 +196,7 @@ struct hdb_index {
     int64_t use_quant = 1;            // 0: never the int8 shadow, even where one exists
     int64_t quant_min_n = -1;         // ... from this many rows on (-1: the measured rule, quant_min_rows)
     int64_t quant_max_k = 128;        // ... for k up to this (<= 128)
+    int64_t auto_quant = 1;           // fp16 matrix, 1-4 dot / cosine queries on the matrix cores: build the shadow on the first eligible call of a large index
     int64_t st_quant = 0;             // the last hdb_topk call took the int8 shadow
     // stats of the last hdb_topk call
     int64_t st_sample_rows = 0, st_sample_m = 0, st_path = 0, st_chunks = 0, st_mfma = 0, st_host_direct = 0, st_fused = 0, st_local = 0, st_f32s = 0;
@@ -223,7 +233,7 @@ static int ensure_ws(hdb_index* ix, size_t bytes) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 101; }
+extern "C" int hdb_version(void) { return 102; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -249,6 +259,9 @@ static double quant_gamma(int d) {
     const double u = std::ldexp(1.0, -24), m = (double)(d + 8) * u;
     return m / (1.0 - m) * (1.0 + std::ldexp(1.0, -20));
 }
+// gamma_m of the matrix-core sum (hdb_quant.hip, bound (2m)); the per-row cache E_r takes the larger of the two
+static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -22); }
+static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
 static size_t quant_elem(const hdb_index* ix) { return ix->dtype == HDB_F16 ? 2 : 4; }
 static void quant_free(hdb_index* ix) {
     if (ix->qcodes) (void)hipFree(ix->qcodes);
@@ -256,9 +269,9 @@ static void quant_free(hdb_index* ix) {
     ix->qcodes = nullptr; ix->qaux = nullptr; ix->q_rows = 0;
 }
 // room for `need` rows; the first `keep` rows of codes and caches survive a reallocation
-static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t st) {
+static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t st, bool tight = false) {
     if (need <= ix->q_rows && ix->qcodes) return HDB_OK;
-    const int64_t rows = need + need / 2 + 64;
+    const int64_t rows = tight ? need + 64 : need + need / 2 + 64;      // (tight: the automatic build -- no room for appends until one comes)
     int8_t* c2 = nullptr; float* a2 = nullptr;
     HIP_TRY(hipMalloc((void**)&c2, (size_t)rows * ix->qP));
     hipError_t e = hipMalloc((void**)&a2, (size_t)rows * 3 * sizeof(float));
@@ -277,7 +290,7 @@ static int quant_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
     if (m <= 0) return HDB_OK;
     const char* src = (const char*)ix->V + (size_t)row0 * ix->d * quant_elem(ix);
     LAUNCH_TRY(hdb_launch_quant_rows(src, m, ix->d, ix->dtype, ix->qP, ix->qcodes + (size_t)row0 * ix->qP, ix->qaux + (size_t)row0 * 3,
-                                     ix->nan_flag, quant_gamma(ix->d), st));
+                                     ix->nan_flag, quant_gamma_rows(ix->d), st));
     return HDB_OK;
 }
 
@@ -290,6 +303,8 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
         if (ix->qcodes) HIP_TRY(hipStreamSynchronize(st));
         quant_free(ix);
         ix->qmode = HDB_QUANT_NONE;
+        ix->qauto = false;
+        ix->auto_quant = 0;                            // dropped on request: the index does not build one for itself again
         return HDB_OK;
     }
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
@@ -303,8 +318,36 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     rc = quant_rows(ix, 0, ix->n, st);
     if (rc) return rc;
     ix->qmode = HDB_QUANT_I8;
+    ix->qauto = false;                                 // an explicit shadow: the VALU scan's bits
     ix->build_stream = st;
     return HDB_OK;
+}
+
+// The automatic shadow (auto_quant): built on the first eligible call.  Memory guard: the shadow, n x (P + 12) bytes, must fit
+// the device's free memory beside the workspace the call is about to take and a floor of 1 GiB for everybody else (the caller's
+// own allocations, other indexes); a refusal or a failed allocation is remembered -- no error, no retry on every call.
+static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
+    if (ix->qauto_declined) return false;
+    const int32_t P = (int32_t)align_up((size_t)ix->d, 16);
+    const size_t shadow = (size_t)(ix->n + 64) * ((size_t)P + 12);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
+    const size_t ws_grow = ws_need > ix->ws_bytes ? ws_need + (ws_need >> 2) + ((size_t)1 << 20) : 0;
+    if (free_b < shadow + ws_grow + ((size_t)1 << 30)) { ix->qauto_declined = true; return false; }
+    if (!ix->qstat) {
+        if (hipMalloc((void**)&ix->qstat, sizeof(int)) != hipSuccess) { (void)hipGetLastError(); ix->qstat = nullptr; ix->qauto_declined = true; return false; }
+        (void)hipMemsetAsync(ix->qstat, 0, sizeof(int), st);
+    }
+    ix->qP = P;
+    if (quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st, true) != HDB_OK || quant_rows(ix, 0, ix->n, st) != HDB_OK) {
+        (void)hipGetLastError();
+        quant_free(ix);
+        ix->qauto_declined = true;
+        return false;
+    }
+    ix->qmode = HDB_QUANT_I8;
+    ix->qauto = true;
+    return true;
 }
 
 extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, int32_t d, int dtype, int device,
@@ -333,6 +376,7 @@ extern "C" int hdb_index_update(hdb_index* ix, const void* dev_V, int64_t n, voi
     HIP_TRY(hipSetDevice(ix->device));
     ix->V = dev_V; ix->n = n;
     ix->bias = nullptr; ix->mask = nullptr;
+    ix->qauto_declined = false;                        // a new matrix: the memory question is asked again
     int rc = build_caches(ix, (hipStream_t)stream);
     if (rc == HDB_OK && ix->qmode == HDB_QUANT_I8) {          // a new matrix: the whole shadow is rebuilt
         rc = quant_reserve(ix, std::max<int64_t>(n, 1), 0, (hipStream_t)stream);
@@ -517,6 +561,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "bits_max_q")) ix->bits_max_q = value;
     else if (!strcmp(name, "use_quant")) ix->use_quant = value;
     else if (!strcmp(name, "quant_min_n")) ix->quant_min_n = value;
+    else if (!strcmp(name, "auto_quant")) ix->auto_quant = value;
     else if (!strcmp(name, "quant_max_k")) ix->quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
@@ -537,6 +582,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "local")) *value = ix->st_local;
     else if (!strcmp(name, "cand_cap")) *value = HDB_CAND_CAP;
     else if (!strcmp(name, "quant")) *value = ix->st_quant;
+    else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
     else if (!strcmp(name, "quant_cands")) {          // synchronises the device
         int h = 0;
@@ -720,26 +766,56 @@ static int64_t quant_min_rows(const hdb_index* ix) {
     return ix->dtype == HDB_F16 ? 1250000 : 500000;
 }
 
-// 1-4 dot / cosine / euclidean queries through the int8 shadow (hdb_quant.hip): quantized query prep, lower bounds on a strided row
-// sample, T_s = 16th largest of them, the pass over the shadow that keeps rows whose upper bound reaches T_s, exact rescoring of
-// those from the matrix, finalize with the floor T_s.  The sample aims at ~512 rows of the whole matrix with a lower bound above
-// T_s (the upper bounds let several times that many through; a sample of 16 keeps P(fewer than k = 128 such rows) near 1e-5).
-static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
-                      float* dev_score, int32_t* dev_status, hipStream_t st) {
-    const int64_t n = ix->n;
-    const int P = ix->qP;
-    const uint32_t m = 16;
+// ... and the smallest fp16 matrix that builds a shadow for itself (auto_quant; measured, profiles/auto_quant_time.txt, DESIGN.md
+// section 4.9).  It lies above the sizes at which the suite pins the default path's statistics (up to 1.6M rows).
+#define HDB_QUANT_AUTO_MIN_ROWS 2000000
+// Rows of the whole matrix the sampled threshold T_s aims to leave with a LOWER bound above it: 512 (a sample of 16 keeps P(fewer
+// than k = 128 such rows) near 1e-5).  The UPPER bounds let exp(z delta - delta^2 / 2) times as many through, delta = 2B / sigma =
+// 0.029 sqrt(d) standard deviations of the scores for Gaussian rows: ~8x at d = 384, 10-14x at d = 768, where 512 would overflow
+// the candidate list.  Rows wider than 512 elements therefore aim at 4k (at least 256: the sample is 16 n / target rows).
+static int64_t quant_sample_target(const hdb_index* ix, uint32_t kk) {
+    return ix->d > 512 ? std::min<int64_t>(512, std::max<int64_t>(256, 4 * (int64_t)kk)) : 512;
+}
+static int64_t quant_sample_tiles(int64_t n, int64_t target) {
     const int64_t all_tiles = n / 16;
-    int64_t s_tiles = ((std::max<int64_t>((int64_t)((double)m * (double)n / 512.0), 16 * (int64_t)m)) + 15) / 16;
-    s_tiles = std::max<int64_t>(1, std::min(s_tiles, all_tiles));
-    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
-    const int64_t s_rows = s_tiles * 16;
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    int64_t s_tiles = ((std::max<int64_t>((int64_t)(16.0 * (double)n / (double)target), 256)) + 15) / 16;
+    return std::max<int64_t>(1, std::min(s_tiles, all_tiles));
+}
+static size_t quant_ws_need(const hdb_index* ix, int nq, int64_t n, bool mflavour) {
+    const int P = (int)align_up((size_t)ix->d, 16);
+    const int64_t s_tiles = quant_sample_tiles(n, quant_sample_target(ix, 1));       // (the largest sample any k takes)
+    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_tiles * 16, 4), 4);
     size_t need = 8 * align_up((size_t)nq * 4, 256) + 4096;
     need += align_up((size_t)nq * P, 256) + align_up((size_t)nq * HDB_QQ_WORDS * 4, 256);
     need += align_up((size_t)nq * 4 * HDB_CNT_STRIDE, 256) + 256;
     need += align_up((size_t)nq * HDB_CAND_CAP * 8, 256) + align_up((size_t)nq * ld_s * 4, 256);
-    int rc = ensure_ws(ix, need);
+    if (mflavour) {
+        const size_t crow = (size_t)nq * HDB_CAND_CAP;              // rows of the compact matrix
+        need += align_up((size_t)nq * ix->d * 2, 256) + 256;        // fp16 queries, qscl
+        need += align_up((size_t)nq * HDB_QUANT_NSUB_MAX * 4, 256); // per-wave maxima of the sample pass
+        need += align_up(crow * ix->d * 2, 256) + 2 * align_up(crow * 4, 256) + align_up((size_t)nq * crow * 4, 256);
+    }
+    return need;
+}
+
+// 1-4 dot / cosine / euclidean queries through the int8 shadow (hdb_quant.hip): quantized query prep, lower bounds on a strided row
+// sample, T_s = 16th largest of them, the pass over the shadow that keeps rows whose upper bound reaches T_s, exact rescoring of
+// those from the matrix, finalize with the floor T_s.  The sample aims at ~512 rows of the whole matrix with a lower bound above
+// T_s (the upper bounds let several times that many through; a sample of 16 keeps P(fewer than k = 128 such rows) near 1e-5).
+// mflavour (the automatic shadow of an fp16 index): the scores are the matrix cores' -- one launch prepares the queries (1/||q||,
+// the scaled fp16 copy, codes of the rounded query), the candidates are gathered into a compact matrix and scored by the MODE 0
+// launch of the matrix-core scan, the finalize packs those scores into the list before it selects.  Seven launches either way.
+static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
+                      float* dev_score, int32_t* dev_status, hipStream_t st, bool mflavour) {
+    const int64_t n = ix->n;
+    const int P = ix->qP;
+    const uint32_t m = 16;
+    const int64_t all_tiles = n / 16;
+    const int64_t s_tiles = quant_sample_tiles(n, quant_sample_target(ix, kk));
+    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
+    const int64_t s_rows = s_tiles * 16;
+    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    int rc = ensure_ws(ix, quant_ws_need(ix, nq, n, mflavour));
     if (rc) return rc;
     Bump b(ix->ws, ix->ws_bytes);
     float* qinv = b.take<float>(nq); float* qsq = b.take<float>(nq); int* qnan = b.take<int>(nq);
@@ -749,26 +825,54 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     uint32_t* cnt = b.take<uint32_t>((size_t)nq * HDB_CNT_STRIDE);
     unsigned long long* cand = b.take<unsigned long long>((size_t)nq * HDB_CAND_CAP);
     float* sbuf = b.take<float>((size_t)nq * ld_s);
-    // 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||)
-    LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
-    LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, st));
+    const size_t crow = (size_t)nq * HDB_CAND_CAP;
+    uint32_t* wmax = nullptr; int nsub = 0;
+    void* q16 = nullptr; float* qscl = nullptr; char* G = nullptr; float* ginv = nullptr; float* gbias = nullptr; float* gsc = nullptr;
+    if (mflavour) {
+        q16 = b.take<uint16_t>((size_t)nq * ix->d); qscl = b.take<float>(nq);
+        G = b.take<char>(crow * ix->d * 2); ginv = b.take<float>(crow); gbias = b.take<float>(crow); gsc = b.take<float>((size_t)nq * crow);
+        wmax = b.take<uint32_t>((size_t)nq * HDB_QUANT_NSUB_MAX);
+        // the threshold folded into the two passes (QuantArgs::nsub) while the sample's grid has at least the 1024 subsets
+        // hdb_sample_thr_kernel works with; smaller samples keep that kernel
+        nsub = 4 * hdb_quant_scan_blocks(s_tiles, (int)ix->max_blocks);
+        if (nsub < 1024 || nsub > HDB_QUANT_NSUB_MAX) nsub = 0;
+        LAUNCH_TRY(hdb_launch_quant_qprep_m((const float*)dev_Q, nq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, ix->qstat,
+                                            nsub ? cnt : nullptr, st));
+    } else {
+        // 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||)
+        LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
+        LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, st));
+    }
     QuantArgs a; memset(&a, 0, sizeof(a));
     a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
     a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = nq;
     a.gamma = (float)quant_gamma(ix->d);
     a.ntiles = s_tiles; a.tile_stride = s_stride; a.scores = sbuf; a.ld = ld_s;
+    a.wmax = wmax; a.nsub = nsub; a.thr_out = thr;
     LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->max_blocks, st));
-    LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, nq, m, thr, cnt, nullptr, st));
+    if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, nq, m, thr, cnt, nullptr, st));
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
     a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
     prof_begin(ix, st);
     LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->max_blocks, st));
     prof_end(ix, st);
-    LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, qinv, ix->bias, ix->mask,
-                                        cand, cnt, HDB_CAND_CAP, st));
+    if (mflavour) {
+        const bool has_bias = ix->bias != nullptr || ix->mask != nullptr;
+        LAUNCH_TRY(hdb_launch_quant_cgather(ix->V, ix->d * 2, ix->inv_norm, ix->bias, ix->mask, cand, cnt, HDB_CAND_CAP, nq, G,
+                                            metric == HDB_COSINE ? ginv : nullptr, has_bias ? gbias : nullptr, st));
+        ScanArgs s; memset(&s, 0, sizeof(s));
+        s.V = G; s.n = (int64_t)crow; s.d = ix->d; s.Q = dev_Q; s.metric = metric; s.inv_norm = ginv; s.qinv = qinv;
+        s.bias = has_bias ? gbias : nullptr; s.mask = nullptr; s.nq = nq;
+        s.tile_stride = 1; s.ntiles = (int64_t)crow / hdb_mfma_tile_rows(ix->dtype, ix->d); s.cap = HDB_CAND_CAP;
+        s.scores = gsc; s.ld = (int64_t)crow;
+        LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, q16, ginv, qsq, qscl, (int)ix->max_blocks, (int)ix->mfma_variant, st, nullptr));
+    } else {
+        LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, qinv, ix->bias, ix->mask,
+                                            cand, cnt, HDB_CAND_CAP, st));
+    }
     LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, qnan,
-                                         qaux, thr, ix->qstat, st));
-    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
+                                         qaux, thr, ix->qstat, mflavour ? cand : nullptr, gsc, (int64_t)crow, st));
+    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = mflavour ? 1 : 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
     ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
     return HDB_OK;
 }
@@ -805,13 +909,13 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (ix->force_exact && !small) exact = true;
     if (!small && (int64_t)kk * 32 > n) exact = true;        // k is a large share of the rows: a sampled threshold cannot help
     // the int8 shadow (hdb_index_quantize): 1-4 dot / cosine / euclidean queries on a finite float16 / float32 matrix; same answer
-    if (ix->qmode == HDB_QUANT_I8 && ix->use_quant && !exact && !small && dev_status != nullptr && nq >= 1 && nq <= 4 &&
+    if (ix->qmode == HDB_QUANT_I8 && !ix->qauto && ix->use_quant && !exact && !small && dev_status != nullptr && nq >= 1 && nq <= 4 &&
         k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN) &&
         (ix->dtype == HDB_F16 || ix->dtype == HDB_F32) && n >= (ix->quant_min_n >= 0 ? ix->quant_min_n : quant_min_rows(ix))) {
         bool finite = false;
         const int rcf = matrix_is_finite(ix, &finite);
         if (rcf != HDB_OK) return rcf;
-        if (finite) return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st);
+        if (finite) return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, false);
     }
     // fp32 matrices: the VALU scan serves up to 4 queries in one pass at HBM speed; the fp32 MFMA scan (matrix-pipe
     // bound at 157 TFLOP/s) takes over where a second VALU pass would start
@@ -832,6 +936,19 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
                               : ix->dtype == HDB_F32 ? HDB_FUSED_MAXQ_RULE : (n >= 1500000 ? 3 : 1);
     const bool mfma = ix->use_mfma && !is_ham && !small && nq >= min_q &&
                       hdb_mfma_supported(ix->dtype, ix->d, is_pearson ? (int)HDB_COSINE : metric);
+    // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
+    // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
+    // the shadow on its first such call; an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
+    if (ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
+        dev_status != nullptr && nq >= 1 && nq <= 4 && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE) &&
+        // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
+        (ix->quant_min_n >= 0 ? n >= ix->quant_min_n : (n >= (int64_t)HDB_QUANT_AUTO_MIN_ROWS && ix->d <= 512))) {
+        bool finite = false;
+        const int rcf = matrix_is_finite(ix, &finite);
+        if (rcf != HDB_OK) return rcf;
+        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_ws_need(ix, nq, n, true), st)))
+            return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, true);
+    }
     // 1-4 dot / cosine queries, k <= 128: one launch does everything (hdb_mfma_fused.h; fp16 on the matrix cores,
     // float32 in the VALU from the same staged tiles)
     // Short matrices: the single launch in its LOCAL flavour -- no row sample, no exchange; every workgroup parks the scores of all

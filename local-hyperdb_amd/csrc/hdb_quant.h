@@ -34,4 +34,11 @@ struct QuantArgs {
     int64_t tile_stride;      // 1 = dense; > 1 = strided sample (hdb_tile_index)
     float* scores; int64_t ld;                            // MODE 0: lower bounds of the sampled rows
     const float* thr; uint32_t* cnt; unsigned long long* cand; uint32_t cap;   // MODE 1: candidate lists
+    // Threshold folded into the two passes (nsub > 0; matrix-core flavour): MODE 0 leaves, instead of the scores, the largest lower
+    // bound every WAVE of its grid saw -- wmax[q][nsub], nsub = 4 x workgroups, as orderable keys (0: nothing seen) -- and every
+    // workgroup of MODE 1 starts by taking the 16th largest of those (a lower bound of the 16th largest sampled lower bound, equal to
+    // it unless two of the top 16 fell to one wave: hdb_sample_thr_kernel's argument with 4x the subsets) and workgroup 0 stores it
+    // to thr_out for the finalize.  No launch in between, nothing to wait for.
+    uint32_t* wmax; int32_t nsub; float* thr_out;
 };
+#define HDB_QUANT_NSUB_MAX 4096      // (MODE 1 holds nsub / 256 keys per thread)

@@ -35,11 +35,31 @@
 // bounds are pushed outward by |s| 2^-20 + 1e-30 (many ulps) to cover that.  NaN never reaches a bound (finite matrix, finite
 // query; a NaN upper bound would count as +inf).
 //
+//
+// ---- The matrix-core flavour (automatic shadow of an fp16 index, hdb_api.hip) --------------------------------------------
+// A default fp16 index answers 1-4-query calls on the matrix cores, so the shadow it builds for itself must return THOSE bits.
+// The rescoring then gathers the candidate rows (with their 1/||v|| and bias) into a compact matrix and scores it with the
+// MODE 0 launch of hdb_mfma_kernel.h -- the launch hdb_topk_exact uses for every row.  Its target sum S_m is the matrix-core
+// sum of the ROUNDED query q' = fp16(q * scale) / scale (scale a power of two, hdb_q16_scale), so the query prep quantizes q'
+// (hdb_quant_qprep_m_kernel: N_q = ||q'||, delta_q = q' - s_q c_q, exact for what is multiplied) and (1) holds for q'.  For (2):
+// fp16 x fp16 products are exact in float32; v_mfma_f32_16x16x32_f16 adds 32 of them and the accumulator per step, d/32 steps in a
+// chain, in an order and with a rounding (possibly truncation, unit 2^-23) the hardware does not document.  Whatever the order,
+// at most d + d/32 additions each err by at most 2^-23 of a partial sum of magnitude <= sum_j |q'_j v_rj| <= ||q'|| ||v_r||, so
+//     |S_m - q'.v_r| <= gamma_m ||q'|| ||v_r||,  gamma_m = (d + 8) 2^-22                                            (2m)
+// with a factor two to spare.  Measured on MI355X (tests/test_auto_quant.py::test_gamma_m_measured: random and adversarial rows
+// against float64 dot products of the same fp16 values): the largest |S_m - q'.v| / (||q'|| ||v||) is 2.7e-7 at d = 128, 4.3e-7 at
+// d = 384, 8.2e-7 at d = 768, i.e. 0.8 %, 0.5 %, 0.4 % of gamma_m; the test asserts it stays at or below gamma_m / 4.
+// E_r is built with the larger of gamma and gamma_m, so one shadow serves both flavours; the int8 error ||eps_r|| ~ 7e-3 ||v_r||
+// dwarfs either.  The epilogue (x qscl, a power of two; cosine x 1/||v|| x 1/||q||; + bias, possibly fused) is the same monotone
+// map up to the contraction the outward push of the bounds already covers.
+//
 // ---- The pipeline (hdb_api.hip, quant_topk) ----------------------------------------------------------------------------
 //   query prep (hdb_qprep_kernel: 1/||q||, NaN flags) -> quantized query prep (codes, s_q, N_q, D_q)
 //   -> int8 scan over a strided row sample (MODE 0: lower bounds)  -> T_s = m-th largest sampled lower bound (hdb_sample_thr)
 //   -> int8 scan over all rows (MODE 1: row r is a candidate of q when its upper bound >= T_s)
 //   -> exact rescoring of the candidates from the original matrix -> finalize with the floor T_s.
+// (matrix-core flavour: ONE query prep launch; the threshold rides in the two passes -- QuantArgs::nsub, hdb_quant.h -- when the
+//  sample is large enough; rescoring = hdb_quant_cgather_kernel + the MODE 0 launch of hdb_mfma_kernel.h.)
 // Completeness: every row that was not emitted has exact score <= its upper bound < T_s.  The finalize checks that the kk-th
 // best rescored candidate scores ABOVE T_s (hdb_finalize_fast's floor); then every row missing from the list scores strictly
 // below the kk-th best, so the top kk, ties at the kk-th score included, are all in the list.  If the check fails (HDB_Q_UNDERFLOW)
@@ -192,6 +212,73 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
     }
 }
 
+// The same for the matrix-core flavour, and the whole query preparation of that call in ONE launch: 1/||q||, ||q||^2 and the NaN
+// flags with hdb_qprep_kernel's own operations (same fma chain per lane, same butterfly: the cosine epilogue multiplies by these
+// bits), the scaled fp16 copy q16 / qscl the matrix cores multiply with, and codes / norms of the ROUNDED query q' = q16 * qscl.
+__global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan,
+                                                               _Float16* q16, float* qscl, int8_t* qcodes, float* qaux, int* stat,
+                                                               uint32_t* cnt_init) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (q >= nq) return;
+    if (q == 0 && lane == 0 && stat) stat[0] = 0;
+    if (lane == 0 && cnt_init) cnt_init[q * HDB_CNT_STRIDE] = 0u;     // an empty candidate list (the folded threshold has no kernel that would do it)
+    const float* qr = Q + (int64_t)q * d;
+    float s = 0.f, amax = 0.f;
+    bool bad = false;
+    for (int e = lane; e < d; e += 64) {
+        const float x = qr[e];
+        s = fma(x, x, s);
+        amax = fmaxf(amax, fabsf(x));
+        if (!(x - x == 0.f)) bad = true;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const float scale = hdb_q16_scale(amax);
+    const float inv_scale = 1.f / scale;
+    float amax2 = 0.f;
+    for (int e = lane; e < d; e += 64) {
+        const _Float16 h = (_Float16)(qr[e] * scale);
+        q16[(int64_t)q * d + e] = h;
+        const float xr = (float)h * inv_scale;              // exact: a power of two
+        if (!(xr - xr == 0.f)) bad = true;
+        amax2 = fmaxf(amax2, fabsf(xr));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); amax2 = fmaxf(amax2, __shfl_xor(amax2, o, 64)); }
+    bad = __ballot(bad) != 0ull;
+    const float sq_ = bad ? 0.f : amax2 / 127.f;
+    double nn = 0.0, dd = 0.0;
+    for (int e = lane; e < P; e += 64) {
+        int c = 0;
+        if (e < d && !bad) {
+            const double x = (double)((float)(_Float16)(qr[e] * scale) * inv_scale);
+            c = hq_code(x, sq_);
+            const double del = x - (double)sq_ * (double)c;
+            nn += x * x;
+            dd += del * del;
+        }
+        qcodes[(int64_t)q * P + e] = (int8_t)c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64); }
+    if (lane == 0) {
+        const float ss = s;
+        qsq[q] = ss;
+        qinv[q] = (s == 0.f) ? 1.0f : (float)(1.f / sqrt(s));
+        qnan[q] = (ss != ss) ? 1 : (ss - ss != 0.f) ? 2 : 0;
+        qscl[q] = inv_scale;
+        float* o = qaux + (int64_t)q * HDB_QQ_WORDS;
+        const float sq = (float)nn;
+        const bool big = !(sq - sq == 0.f);
+        o[HDB_QQ_S] = sq_;
+        o[HDB_QQ_N] = bad ? 0.f : hq_up(sqrt(nn));
+        o[HDB_QQ_D] = bad ? 0.f : hq_up(sqrt(dd));
+        o[HDB_QQ_SQ] = sq;
+        o[HDB_QQ_BAD] = (bad || big) ? 1.f : 0.f;
+        o[5] = 0.f; o[6] = 0.f; o[7] = 0.f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // int8 scan.  Tiling as hdb_scan_kernel: a wave covers 16 consecutive rows, lane group g = lane >> 4 owns rows 4g..4g+3 and its
 // 16 lanes stride over the row's 16-byte pieces (non-temporal loads; the shadow is streamed once per call).  The NQ queries'
@@ -240,9 +327,61 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
         const float* o = a.qaux + (int64_t)q * HDB_QQ_WORDS;
         q_s[q] = o[HDB_QQ_S]; q_n[q] = o[HDB_QQ_N]; q_d[q] = o[HDB_QQ_D]; q_sq[q] = o[HDB_QQ_SQ]; q_bad[q] = o[HDB_QQ_BAD] != 0.f;
         q_inv[q] = a.metric == HDB_COSINE ? a.qinv[q] : 1.f;
-        q_thr[q] = MODE == 1 ? a.thr[q] : 0.f;
+        q_thr[q] = (MODE == 1 && a.nsub == 0) ? a.thr[q] : 0.f;
     }
     __syncthreads();
+    if (MODE == 1 && a.nsub > 0) {
+        // T_s = 16th largest of the per-wave maxima of the sample pass: every wave extracts the 16 largest of its quarter, wave 0
+        // the 16 largest of those 64 (hdb_sample_thr_kernel's scheme; exact for the nsub keys)
+        __shared__ uint32_t s_top[4 * 16];
+        __shared__ float s_thr[NQ];
+        const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        for (int q = 0; q < NQ; ++q) {
+            uint32_t c[HDB_QUANT_NSUB_MAX / 256];
+#pragma unroll
+            for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) {
+                const int e = (int)threadIdx.x + 256 * j;
+                c[j] = e < a.nsub ? a.wmax[(int64_t)q * a.nsub + e] : 0u;
+            }
+            for (int r = 0; r < 16; ++r) {
+                uint32_t lm = 0u;
+#pragma unroll
+                for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) lm = max(lm, c[j]);
+                uint32_t wm = lm;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+                const unsigned long long who = __ballot(lm == wm);
+                if (ln == (int)__ffsll((long long)who) - 1) {
+                    bool gone = false;
+#pragma unroll
+                    for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j)
+                        if (!gone && c[j] == wm) { c[j] = 0u; gone = true; }
+                }
+                if (ln == 0) s_top[wv * 16 + r] = wm;
+            }
+            __syncthreads();
+            if (wv == 0) {
+                uint32_t v = s_top[ln];
+                uint32_t kth = 0u;
+                for (int r = 0; r < 16; ++r) {
+                    uint32_t wm = v;
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+                    const unsigned long long who = __ballot(v == wm);
+                    if (ln == (int)__ffsll((long long)who) - 1) v = 0u;
+                    kth = wm;
+                }
+                if (ln == 0) {
+                    const float t = kth == 0u ? -INFINITY : hdb_key2f(kth);
+                    s_thr[q] = t;
+                    if (blockIdx.x == 0) a.thr_out[q] = t;
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) q_thr[q] = s_thr[q];
+    }
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, l16 = lane & 15;
@@ -251,6 +390,9 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
     const float absmin = 0x1p-100f * (float)(a.d + 8);
     const float g2 = 2.f * a.gamma;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    uint32_t wbest[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) wbest[q] = 0u;
 
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < a.ntiles; t += (int64_t)gridDim.x * 4) {
         const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
@@ -306,7 +448,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
         if ((l16 & 3) != 0) continue;
         const int64_t out_i = t * 16 + 4 * g + u_own;
         if (row >= a.n) {
-            if (MODE == 0)
+            if (MODE == 0 && a.nsub == 0)
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) a.scores[(int64_t)q * a.ld + out_i] = -INFINITY;
             continue;
@@ -341,7 +483,8 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
                 if (hi != hi) hi = INFINITY;
             }
             if (MODE == 0) {
-                a.scores[(int64_t)q * a.ld + out_i] = lo;
+                if (a.nsub > 0) wbest[q] = max(wbest[q], hdb_f2key(lo));
+                else a.scores[(int64_t)q * a.ld + out_i] = lo;
             } else if (!masked && !q_bad[q] && hi >= q_thr[q]) {
                 const unsigned long long ent = hdb_pack(hi, (uint32_t)row);
                 const unsigned int lp = atomicAdd(&stage.cnt[q], 1u);                    // LDS
@@ -351,6 +494,15 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
                     if (pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = ent;
                 }
             }
+        }
+    }
+    if (MODE == 0 && a.nsub > 0) {                       // (every wave of the grid writes its slot: a wave without tiles writes 0)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            uint32_t wm = wbest[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+            if (lane == 0) a.wmax[(int64_t)q * a.nsub + blockIdx.x * 4 + wave] = wm;
         }
     }
     if (MODE == 1) {                                     // one atomic per block and query (hdb_stage_flush)
@@ -448,15 +600,48 @@ __global__ __launch_bounds__(256) void hdb_quant_rescore_kernel(RescoreArgs a) {
     }
 }
 
+// Matrix-core flavour of the rescoring, first half: the candidate rows of query q go to rows [q cap, q cap + count) of a compact
+// matrix G (row_bytes a multiple of 256, as every MFMA geometry has it), their 1/||v|| and bias beside them -- the bias as the
+// matrix-core scan takes it, the row mask folded in (hdb_maskbias_kernel).  One wave per candidate.  Rows past a query's count
+// are left as they are: the MODE 0 launch scores them too (its grid is set by the host, which does not know the counts) and
+// nobody reads those scores.
+__global__ __launch_bounds__(256) void hdb_quant_cgather_kernel(const char* V, int row_bytes, const float* inv_norm, const float* bias,
+                                                                const uint8_t* mask, const unsigned long long* cand, const uint32_t* cnt,
+                                                                uint32_t cap, char* G, float* ginv, float* gbias) {
+    const int q = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t total = min(cnt[q * HDB_CNT_STRIDE], cap);
+    for (uint32_t i = blockIdx.x * 4 + wave; i < total; i += gridDim.x * 4) {
+        const int64_t slot = (int64_t)q * cap + i;
+        const uint32_t row = 0xFFFFFFFFu - (uint32_t)(cand[slot] & 0xFFFFFFFFull);
+        const char* src = V + (int64_t)row * row_bytes;
+        char* dst = G + slot * row_bytes;
+        for (int c = lane * 16; c < row_bytes; c += 64 * 16) *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(src + c);
+        if (lane == 0) {
+            if (ginv) ginv[slot] = inv_norm[row];
+            if (gbias) gbias[slot] = mask ? (mask[row] ? (bias ? bias[row] : 0.f) : -INFINITY) : bias[row];
+        }
+    }
+}
+
 // Finalize: hdb_finalize_fast over the rescored list with the floor T_s (see "Completeness" above).  A query with an infinite
 // element, or one the quantized prep could not take, is reported as HDB_Q_UNDERFLOW: hdb_topk_host re-runs it exactly.
 __global__ __launch_bounds__(1024) void hdb_quant_finalize_kernel(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, uint32_t k,
                                                                   uint32_t kk, int64_t row_base, int64_t* idx_out, float* score_out,
                                                                   int32_t* status, const int* qnan, const float* qaux, const float* thr,
-                                                                  int* stat) {
+                                                                  int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long buf[];
     const int q = blockIdx.x;
     const uint32_t total = cnt[q * HDB_CNT_STRIDE];
+    if (sc) {          // matrix-core flavour, second half: the MODE 0 launch left the score of list entry i at sc[q][q cap + i]
+        const uint32_t nc = min(total, cap);
+        for (uint32_t i = threadIdx.x; i < nc; i += blockDim.x) {
+            const int64_t slot = (int64_t)q * cap + i;
+            const uint32_t row = 0xFFFFFFFFu - (uint32_t)(cand_rw[slot] & 0xFFFFFFFFull);
+            cand_rw[slot] = hdb_pack(sc[(int64_t)q * ld + slot], row);
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
     if (threadIdx.x == 0 && stat) atomicMax(stat, (int)min(total, 0x7FFFFFFFu));
     const int qn = qnan[q];
     const bool bad = qaux[(int64_t)q * HDB_QQ_WORDS + HDB_QQ_BAD] != 0.f;
@@ -490,6 +675,22 @@ extern "C" int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8
     return (int)hipGetLastError();
 }
 
+extern "C" int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
+                                        int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, void* stream) {
+    hipLaunchKernelGGL(hdb_quant_qprep_m_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, nq, d, P, qinv, qsq, qnan, (_Float16*)q16,
+                       qscl, qcodes, qaux, stat, cnt_init);
+    return (int)hipGetLastError();
+}
+
+extern "C" int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
+                                        const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv,
+                                        float* gbias, void* stream) {
+    if (row_bytes % 16 != 0 || (reinterpret_cast<uintptr_t>(V) & 15) != 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(hdb_quant_cgather_kernel, dim3(256, nq), dim3(256), 0, (hipStream_t)stream, (const char*)V, row_bytes, inv_norm, bias,
+                       mask, cand, cnt, cap, (char*)G, ginv, gbias);
+    return (int)hipGetLastError();
+}
+
 template <int MODE, int NQ>
 static void hq_launch_scan_nq(const QuantArgs& a, int blocks, size_t lds, hipStream_t st) {
     const int nch = a.P >> 4;
@@ -508,12 +709,15 @@ static void hq_launch_scan_mode(const QuantArgs& a, int blocks, size_t lds, hipS
     default: hq_launch_scan_nq<MODE, 4>(a, blocks, lds, st); break;
     }
 }
+// workgroups a launch over `ntiles` tiles takes (the folded threshold keeps 4 x that many per-wave maxima of the sample pass)
+extern "C" int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for(ntiles, 4, max_blocks > 0 ? max_blocks : 1024); }
 // mode 0: lower bounds of the sampled tiles; mode 1: candidate emission over a.ntiles dense tiles.  1 <= a.nq <= 4.
 extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream) {
     const QuantArgs& a = *args;
     if (a.nq < 1 || a.nq > 4 || (a.P & 15) != 0) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)a.nq * a.P;
-    const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : 1024);
+    const int blocks = hdb_quant_scan_blocks(a.ntiles, max_blocks);
+    if (a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || (mode == 0 ? a.nsub != 4 * blocks : !a.thr_out))) return (int)hipErrorInvalidValue;
     if (mode == 0) hq_launch_scan_mode<0>(a, blocks, lds, (hipStream_t)stream);
     else hq_launch_scan_mode<1>(a, blocks, lds, (hipStream_t)stream);
     return (int)hipGetLastError();
@@ -547,12 +751,13 @@ extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const f
 
 extern "C" int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
                                          int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
-                                         const float* qaux, const float* thr, int* stat, void* stream) {
+                                         const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc,
+                                         int64_t ld, void* stream) {
     const size_t lds = (size_t)cap * 16 + 2048 * 4 + 64;
     static unsigned long long attr_done = 0;
     hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(hdb_quant_finalize_kernel), (int)lds, &attr_done);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(hdb_quant_finalize_kernel, dim3(nq), dim3(1024), lds, (hipStream_t)stream, cand, cnt, cap, k, kk, row_base,
-                       idx_out, score_out, status, qnan, qaux, thr, stat);
+                       idx_out, score_out, status, qnan, qaux, thr, stat, cand_rw, sc, ld);
     return (int)hipGetLastError();
 }

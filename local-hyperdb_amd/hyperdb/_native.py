@@ -255,7 +255,10 @@ class GpuIndex:
         """Build (``"int8"``) or drop (``None``) the int8 shadow of the matrix (hdb_index_quantize): 1-4-query dot / cosine /
         euclidean calls with k <= 128 then stream one byte per element and rescore the surviving rows exactly -- the same
         indices and float32 scores as without it.  The shadow follows append / update / compact; it costs N x (round_up(d, 16)
-        + 12) bytes of device memory."""
+        + 12) bytes of device memory.  A large fp16 index also builds a shadow for itself on its first 1-4-query dot / cosine
+        call (option ``auto_quant``; that flavour returns the matrix cores' bits, i.e. exactly what the call returned before);
+        ``quantize(None)`` drops either kind and switches the automatic build off for this handle, ``quantize("int8")`` keeps
+        the explicit meaning."""
         mode = quant_mode(mode)
         with torch.cuda.device(self.device):
             _check(_lib.hdb_index_quantize(self._h, mode, _stream_ptr(self.device)), "hdb_index_quantize")
