@@ -138,7 +138,30 @@ void hdb_index_destroy(hdb_index* ix);
  * and for good (until hdb_index_update), when hipMemGetInfo does not show room for the shadow, the call's workspace and 1 GiB
  * beside them, or when an allocation fails.  hdb_index_quantize(HDB_QUANT_NONE) drops the shadow AND sets auto_quant = 0 for the
  * handle; hdb_index_quantize(HDB_QUANT_I8) turns it into an explicit one (VALU bits, the rule above).  An index that only serves
- * batches of 5+ queries, other metrics or small matrices never builds one. */
+ * other metrics or small matrices never builds one.
+ *
+ * Batches through the automatic shadow (local-hyperdb_amd/csrc/hdb_quant_mfma.hip).  A call of 5 or more dot / cosine queries under
+ * the same conditions, on rows of 128, 256, 384 or 512 elements with mfma_variant = 16, is answered from the shadow as well, in
+ * chunks of up to 256 queries: quantized query prep, an int8 matrix-core pass (v_mfma_i32_16x16x64_i8) over a tenth of the rows
+ * that leaves per-slot maxima of the lower bounds, T_s = the 32nd largest of them per query, an int8 matrix-core pass over all
+ * rows that emits the (row, query) pairs whose upper bound reaches T_s, rescoring of every list from the fp16 matrix with the
+ * instruction, K walk and epilogue of the default batched path (query q against its own list only), finalize with the floor T_s.
+ * Indices and score bits are those of the default path and of hdb_topk_exact; a query whose floor check fails or whose list
+ * overflows says so in its status word.  The pass tests every pair with a cheap conservative form of the bound -- convert,
+ * multiply, four fma, compare, on per-row and per-query values folded outside the pair loop; it passes every pair whose upper
+ * bound (bound (3) of hdb_quant.hip, score-domain map and outward push included) reaches T_s - c0, c0 = 1.001 (d + 8) 2^-36 for
+ * cosine and 1.001 (d + 8) 2^-100 + 4e-30 for the dot product -- and holds the survivors against the exact bound, so the lists
+ * are those the v_dot4 scan would emit (derivation in the kernel's header comment).
+ * Row rule: quant_batch_min_n (-1: the measured rule -- d = 384: 5-16 queries from 3 000 000 rows, 17-24 from 5 000 000; d = 512:
+ * 5-16 queries from 10 000 000 rows; nothing else, DESIGN.md section 4.9 has the table -- never below 2 000 000 rows; >= 0: every
+ * query count from that many rows on).  It is separate from quant_min_n, which keeps governing 1-4-query calls only.  quant_batch_kernel
+ * (default 1) = 0 runs the filter with the v_dot4 scan of the 1-4-query flavour, four queries per pass over the shadow: the A/B
+ * switch for timing and an independent kernel for the tests.  Stats as above (quant = 1, quant_auto = 1, mfma = 1, path = 1,
+ * fused = 0), chunks = launches of up to 256 queries, quant_cands = the largest list of the call, quant_cands_min /
+ * quant_cands_median = the smallest / median list of its last chunk (both synchronise).
+ * Workspace of a chunk of cq queries: the lists, cq x HDB_CAND_CAP x 8 bytes (16 MiB at 256 queries), at most cq x 8192 floats of
+ * sample maxima, cq x d fp16 query values and the per-query words; no compact matrix and no score block.  A batch call can be
+ * the one that builds the shadow and pays for it. */
 enum hdb_quant { HDB_QUANT_NONE = 0, HDB_QUANT_I8 = 1 };
 int hdb_index_quantize(hdb_index* ix, int mode, void* stream);
 
@@ -276,11 +299,14 @@ void hdb_group_destroy(hdb_group* g);
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),
- *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never).
+ *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never), quant_batch_min_n (batches
+ *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
+ *   cores, 0: the v_dot4 scan four queries at a time).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
- *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_bytes, quant_auto. */
+ *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
+ *   quant_bytes, quant_auto. */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

@@ -92,6 +92,14 @@ int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cn
                               int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
                               const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
                               void* stream);
+int hdb_qb_supported(int d);
+int hdb_qb_scan_blocks(int64_t ntiles, int nq, int max_blocks);
+int64_t hdb_qb_slots(int blocks, int nq);
+int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
+int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);
+int hdb_launch_qb_rescore(const void* V, int d, const void* q16, const float* qscl, const float* qinv, const float* inv_norm,
+                          const float* bias, const uint8_t* mask, int metric, unsigned long long* cand, const uint32_t* cnt,
+                          uint32_t cap, int nq, void* stream);
 int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
                               const float* Q, const float* qsq, int q0, const float* bias, void* stream);
 }
@@ -197,7 +205,11 @@ struct hdb_index {
     int64_t quant_min_n = -1;         // ... from this many rows on (-1: the measured rule, quant_min_rows)
     int64_t quant_max_k = 128;        // ... for k up to this (<= 128)
     int64_t auto_quant = 1;           // fp16 matrix, 1-4 dot / cosine queries on the matrix cores: build the shadow on the first eligible call of a large index
+    int64_t quant_batch_min_n = -1;   // ... batches of 5+ queries: from this many rows on (-1: the measured rule, quant_batch_rule)
+    int64_t quant_batch_kernel = 1;   // ... their filter pass: 1 = int8 matrix cores (hdb_quant_mfma.hip), 0 = the v_dot4 scan, four queries per pass
     int64_t st_quant = 0;             // the last hdb_topk call took the int8 shadow
+    const uint32_t* qb_cnt = nullptr; // ... as a batch: the list counters of its last chunk (in the workspace) and their number
+    int qb_cnt_n = 0;
     // stats of the last hdb_topk call
     int64_t st_sample_rows = 0, st_sample_m = 0, st_path = 0, st_chunks = 0, st_mfma = 0, st_host_direct = 0, st_fused = 0, st_local = 0, st_f32s = 0;
     // host-side timing of hdb_topk_host (always on: four clock reads per call), cumulative since "host_timing_reset":
@@ -562,6 +574,8 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "use_quant")) ix->use_quant = value;
     else if (!strcmp(name, "quant_min_n")) ix->quant_min_n = value;
     else if (!strcmp(name, "auto_quant")) ix->auto_quant = value;
+    else if (!strcmp(name, "quant_batch_min_n")) ix->quant_batch_min_n = value;
+    else if (!strcmp(name, "quant_batch_kernel")) ix->quant_batch_kernel = value ? 1 : 0;
     else if (!strcmp(name, "quant_max_k")) ix->quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
@@ -592,6 +606,19 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
             HIP_TRY(hipMemcpy(&h, ix->qstat, sizeof(int), hipMemcpyDeviceToHost));
         }
         *value = h;
+    }
+    else if (!strcmp(name, "quant_cands_min") || !strcmp(name, "quant_cands_median")) {     // batches: over the lists of the last chunk; synchronises
+        int64_t v = 0;
+        if (ix->st_quant && ix->qb_cnt && ix->qb_cnt_n > 0) {
+            HIP_TRY(hipSetDevice(ix->device));
+            HIP_TRY(hipDeviceSynchronize());
+            std::vector<uint32_t> raw((size_t)ix->qb_cnt_n * HDB_CNT_STRIDE), c((size_t)ix->qb_cnt_n);
+            HIP_TRY(hipMemcpy(raw.data(), ix->qb_cnt, raw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (int q = 0; q < ix->qb_cnt_n; ++q) c[q] = raw[(size_t)q * HDB_CNT_STRIDE];
+            std::sort(c.begin(), c.end());
+            v = name[13] == 'i' ? c.front() : c[c.size() / 2];
+        }
+        *value = v;
     }
     else if (!strcmp(name, "n")) *value = ix->n;
     else if (!strcmp(name, "ws_bytes")) *value = (int64_t)ix->ws_bytes;
@@ -877,6 +904,121 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     return HDB_OK;
 }
 
+// ---- batches of 5+ queries through the automatic shadow (hdb_quant_mfma.hip) ---------------------------------------------------
+// Sample plan of a batch.  T_s is the m-th largest sampled lower bound; the rows of the whole matrix with a LOWER bound above it
+// number about target x Gamma(m) / m.  A batch pays for its worst query on both sides (too few: the floor check fails; too many: the
+// upper bounds, exp(z delta) times as many, overflow the list), so the batch plan narrows the spread with m = 32 instead of 16 and
+// aims lower, at 320 rows: P(fewer than k = 128 such rows) = P(Gamma(32) < 12.8) ~ 1e-5 per query, and the +3 sigma query of 256
+// stands at 320 x 49 / 32 = 490 rows where the 1-4-query plan's would stand at 512 x 28 / 16 = 896.  The sample is m / target = a
+// tenth of the rows (the CPU model's m = 64 / target 256 would read a quarter of the shadow a second time).
+#define HDB_QB_SAMPLE_M 32
+#define HDB_QB_SAMPLE_TARGET 320
+static int64_t quant_batch_sample_tiles(int64_t n) {
+    const int64_t all_tiles = n / 16;
+    const int64_t rows = std::max<int64_t>((int64_t)((double)HDB_QB_SAMPLE_M * (double)n / (double)HDB_QB_SAMPLE_TARGET), 16 * HDB_QB_SAMPLE_M);
+    return std::max<int64_t>(1, std::min((rows + 15) / 16, all_tiles));
+}
+// The measured rule of quant_batch_min_n = -1: the smallest matrix from which a batch of nq queries is at least 1.10x faster through
+// the shadow than through the fp16 single launch, 0 = never (profiles/quant_batch_time.txt, one box, interleaved, p50 in us, parent ->
+// shadow).  The filter kernel reads its row fragments straight from global memory, so a workgroup has one tile per wave in flight:
+// it wins while one query tile per wave keeps the pass near the shadow's bytes and loses once the waves share tiles.
+//   d = 384, 5-16 queries: 2M 269 -> 261 (1.03), 3M 373 -> 336 (1.11) / 430 -> 378 (1.14), 4M 1.16 / 1.13, 5M 1.18-1.19, 10M 1.18-1.21
+//   d = 384, 24 queries: 5M 674 -> 568 (1.19), 10M 1167 -> 1002 (1.17); 32 queries: 1.03 / 1.13, at 3M-4M 0.93 / 1.00; 48: 0.94 / 1.03
+//   d = 384, 64 / 128 / 256 queries at 10M: 1137 -> 1776 (0.64), 1342 -> 3485 (0.39), 2292 -> 6545 (0.35): excluded
+//   d = 512, 5 / 8 / 16 queries: 10M 1.21 / 1.18 / 1.11; 5M 1.10 / 1.09 / 0.99; 2M 0.98 and below
+//   d = 128: 0.78-0.91 at every size (the fp16 pass over 256-byte rows is short already); d = 256: not measured, so not admitted
+static int64_t quant_batch_rule(const hdb_index* ix, int nq) {
+    int64_t rows = 0;
+    if (ix->d == 384) rows = nq <= 16 ? 3000000 : nq <= 24 ? 5000000 : 0;
+    else if (ix->d == 512) rows = nq <= 16 ? 10000000 : 0;
+    return rows > 0 ? std::max<int64_t>(rows, HDB_QUANT_AUTO_MIN_ROWS) : 0;
+}
+static size_t quant_batch_ws_need(const hdb_index* ix, int cq, int64_t n) {
+    const int P = (int)align_up((size_t)ix->d, 16);
+    const int64_t s_tiles = quant_batch_sample_tiles(n);
+    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_tiles * 16, 4), 4);
+    const int64_t wld = align_up((size_t)hdb_qb_slots(512, 1), 4);              // (the most slots any launch leaves per query)
+    size_t need = 8 * align_up((size_t)cq * 4, 256) + 4096;
+    need += align_up((size_t)cq * P, 256) + align_up((size_t)cq * HDB_QQ_WORDS * 4, 256);
+    need += align_up((size_t)cq * 4 * HDB_CNT_STRIDE, 256) + 256;
+    need += align_up((size_t)cq * HDB_CAND_CAP * 8, 256);
+    need += align_up((size_t)cq * ix->d * 2, 256);
+    need += align_up(std::max((size_t)cq * wld, (size_t)4 * ld_s) * 4, 256);
+    return need;
+}
+// One call: chunks of up to 256 queries, each through query prep, sample pass, thresholds, filter pass, block-diagonal rescoring
+// and finalize.  Workspace per chunk: the lists (cq x 8192 x 8 bytes = 16 MiB at 256 queries), the slot maxima of the sample pass
+// (cq x 8192 floats at most) and the per-query words; no compact matrix and no nq x nq score block.
+static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
+                            float* dev_score, int32_t* dev_status, hipStream_t st) {
+    const int64_t n = ix->n;
+    const int P = ix->qP;
+    const uint32_t m = HDB_QB_SAMPLE_M;
+    const int64_t all_tiles = n / 16;
+    const int64_t s_tiles = quant_batch_sample_tiles(n);
+    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
+    const int64_t s_rows = s_tiles * 16;
+    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    const int cq_max = std::min<int>(nq, 256);
+    int rc = ensure_ws(ix, quant_batch_ws_need(ix, cq_max, n));
+    if (rc) return rc;
+    const int64_t wld = align_up((size_t)hdb_qb_slots(512, 1), 4);
+    Bump b(ix->ws, ix->ws_bytes);
+    float* qinv = b.take<float>(cq_max); float* qsq = b.take<float>(cq_max); int* qnan = b.take<int>(cq_max); float* qscl = b.take<float>(cq_max);
+    int8_t* qcodes = b.take<int8_t>((size_t)cq_max * P);
+    float* qaux = b.take<float>((size_t)cq_max * HDB_QQ_WORDS);
+    float* thr = b.take<float>(cq_max);
+    uint32_t* cnt = b.take<uint32_t>((size_t)cq_max * HDB_CNT_STRIDE);
+    unsigned long long* cand = b.take<unsigned long long>((size_t)cq_max * HDB_CAND_CAP);
+    void* q16 = b.take<uint16_t>((size_t)cq_max * ix->d);
+    float* wbuf = b.take<float>(std::max((size_t)cq_max * wld, (size_t)4 * ld_s));       // slot maxima (kernel 1) / sampled lower bounds of four queries (kernel 0)
+    ix->st_chunks = 0;
+    for (int q0 = 0; q0 < nq; q0 += cq_max) {
+        const int cq = std::min(cq_max, nq - q0);
+        ix->st_chunks++;
+        const float* Qc = (const float*)dev_Q + (size_t)q0 * ix->d;
+        // (the stat word is reset by the first chunk only: quant_cands is the largest list of the CALL)
+        LAUNCH_TRY(hdb_launch_quant_qprep_m(Qc, cq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, q0 == 0 ? ix->qstat : nullptr, cnt, st));
+        QuantArgs a; memset(&a, 0, sizeof(a));
+        a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
+        a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = cq;
+        a.gamma = (float)quant_gamma(ix->d);
+        a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
+        if (ix->quant_batch_kernel) {
+            a.ntiles = s_tiles; a.tile_stride = s_stride;
+            const int sblocks = hdb_qb_scan_blocks(s_tiles, cq, (int)ix->max_blocks);
+            LAUNCH_TRY(hdb_launch_qb_scan(&a, 0, wbuf, wld, (int)ix->max_blocks, st));
+            LAUNCH_TRY(hdb_launch_qb_thr(wbuf, hdb_qb_slots(sblocks, cq), wld, cq, m, thr, st));
+            a.ntiles = (n + 15) / 16; a.tile_stride = 1;
+            prof_begin(ix, st);
+            LAUNCH_TRY(hdb_launch_qb_scan(&a, 1, nullptr, 0, (int)ix->max_blocks, st));
+            prof_end(ix, st);
+        } else {
+            // the v_dot4 scan of the 1-4-query flavour, four queries per pass over the sample and over the shadow
+            for (int g0 = 0; g0 < cq; g0 += 4) {
+                QuantArgs g = a;
+                g.nq = std::min(4, cq - g0);
+                g.qcodes = qcodes + (size_t)g0 * P; g.qaux = qaux + (size_t)g0 * HDB_QQ_WORDS; g.qinv = qinv + g0;
+                g.thr = thr + g0; g.cnt = cnt + (size_t)g0 * HDB_CNT_STRIDE; g.cand = cand + (size_t)g0 * HDB_CAND_CAP;
+                g.ntiles = s_tiles; g.tile_stride = s_stride; g.scores = wbuf; g.ld = ld_s;
+                LAUNCH_TRY(hdb_launch_quant_scan(&g, 0, (int)ix->max_blocks, st));
+                LAUNCH_TRY(hdb_launch_qb_thr(wbuf, s_rows, ld_s, g.nq, m, thr + g0, st));
+                g.ntiles = (n + 15) / 16; g.tile_stride = 1; g.scores = nullptr; g.ld = 0;
+                prof_begin(ix, st);
+                LAUNCH_TRY(hdb_launch_quant_scan(&g, 1, (int)ix->max_blocks, st));
+                prof_end(ix, st);
+            }
+        }
+        LAUNCH_TRY(hdb_launch_qb_rescore(ix->V, ix->d, q16, qscl, qinv, ix->inv_norm, ix->bias, ix->mask, metric, cand, cnt, HDB_CAND_CAP, cq, st));
+        LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, cq, (uint32_t)k, kk, ix->row_base, dev_idx + (int64_t)q0 * k,
+                                             dev_score + (int64_t)q0 * k, dev_status + q0, qnan, qaux, thr, ix->qstat, nullptr, nullptr, 0, st));
+    }
+    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = 1; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
+    ix->st_sample_rows = s_rows; ix->st_sample_m = m;
+    ix->qb_cnt = cnt; ix->qb_cnt_n = nq - (nq - 1) / cq_max * cq_max;
+    return HDB_OK;
+}
+
 static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
                      float* dev_score, int32_t* dev_status, void* stream, bool exact) {
     if (!ix || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, "hdb_topk: null argument");
@@ -888,7 +1030,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (metric == HDB_PEARSON && ix->d < 1) return fail(HDB_ERR_ARG, "hdb_topk: pearson needs d >= 1");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    ix->st_quant = 0;
+    ix->st_quant = 0; ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
     const bool f64 = ix->dtype == HDB_F64;
     const int64_t n = ix->n;
     const uint32_t kk = (uint32_t)std::min<int64_t>(k, n);
@@ -948,6 +1090,18 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
         if (rcf != HDB_OK) return rcf;
         if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_ws_need(ix, nq, n, true), st)))
             return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, true);
+    }
+    // ... and batches of 5+ queries (hdb_quant_mfma.hip): the same conditions under a row rule of their own (quant_batch_min_n), for the
+    // widths the int8 matrix-core pass takes and the 16x16x32 form of the fp16 scan, whose bits the rescoring returns
+    if (ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
+        dev_status != nullptr && nq >= 5 && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE) &&
+        hdb_qb_supported(ix->d) && ix->mfma_variant == 16 &&
+        (ix->quant_batch_min_n >= 0 ? n >= ix->quant_batch_min_n : (quant_batch_rule(ix, nq) > 0 && n >= quant_batch_rule(ix, nq)))) {
+        bool finite = false;
+        const int rcf = matrix_is_finite(ix, &finite);
+        if (rcf != HDB_OK) return rcf;
+        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_batch_ws_need(ix, std::min<int>(nq, 256), n), st)))
+            return quant_batch_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st);
     }
     // 1-4 dot / cosine queries, k <= 128: one launch does everything (hdb_mfma_fused.h; fp16 on the matrix cores,
     // float32 in the VALU from the same staged tiles)

@@ -10,6 +10,9 @@ crossover quant_min_n; --only times shape I alone, for a rocprofv3 run).
 the rescoring returns the matrix cores' bits): fp16 shapes from 2M to 10M rows, one and four queries, the check is bit identity
 with the default path (use_quant = 0), and the last column is the one-off cost of the first eligible call (allocation + one pass
 over the matrix).  The automatic row threshold (HDB_QUANT_AUTO_MIN_ROWS, hdb_api.hip) cites this table.
+
+--auto --batch [--rows ...] [--dims ...] [--queries ...] times batches of 5+ queries through the automatic shadow (batch_table
+below); the row rule of batches (quant_batch_rule, hdb_api.hip) cites that table, profiles/quant_batch_time.txt.
 """
 import argparse
 import sys
@@ -55,13 +58,70 @@ def flat(r):
     return [np.asarray(x) for pair in r for x in pair]
 
 
+def batch_table(args):
+    """--auto --batch: batches of 5+ queries through the automatic shadow (hdb_quant_mfma.hip).  Per (rows, d): one matrix, one
+    index, one process; per query count the parent path (use_quant = 0), the shadow with the int8 matrix-core filter
+    (quant_batch_kernel = 1) and the shadow with the v_dot4 scan (quant_batch_kernel = 0) alternate, p50 of --reps calls each (the
+    v_dot4 column takes a quarter of the repetitions: it reads the shadow once per four queries).  Lists: min / median / max
+    candidates per query of the matrix-core call.  same: indices and score bits of both shadow calls equal the parent's.  The
+    first shadow call of an index builds the shadow; its wall time is the last column of that row."""
+    g = torch.Generator(device="cuda").manual_seed(5)
+    print(f"{'rows':>10s} {'d':>4s} {'nq':>4s} {'parent us':>10s} {'i8 mfma us':>10s} {'speed-up':>8s} {'v_dot4 us':>10s} "
+          f"{'lists min/med/max':>18s} same  first call ms", flush=True)
+    for n in args.rows:
+        for d in args.dims:
+            V = torch.randn((n, d), generator=g, device="cuda", dtype=torch.float32).to(torch.float16)
+            h = ranking.register_vectors(V)
+            ix = h.index
+            ix.set_option("quant_batch_min_n", 0)
+            first = True
+            for nq in args.queries:
+                Q = np.random.default_rng(n + nq).standard_normal((nq, d)).astype(np.float32)
+                k = 100
+
+                def run(use_quant, kernel):
+                    ix.set_option("use_quant", use_quant)
+                    ix.set_option("quant_batch_kernel", kernel)
+                    return call(h, Q, k)
+
+                a = run(0, 1)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter(); b = run(1, 1); first_ms = (time.perf_counter() - t0) * 1e3
+                took = ix.stat("quant") & ix.stat("quant_auto") & ix.stat("mfma")
+                lists = (ix.stat("quant_cands_min"), ix.stat("quant_cands_median"), ix.stat("quant_cands"))
+                c = run(1, 0)
+                took &= ix.stat("quant")
+                same = all(np.array_equal(x, y) for x, y in zip(flat(a), flat(b))) and all(np.array_equal(x, y) for x, y in zip(flat(a), flat(c)))
+                for _ in range(3):
+                    run(0, 1); run(1, 1)
+                ta, tb, tc = [], [], []
+                for r in range(args.reps):
+                    t0 = time.perf_counter(); run(0, 1); ta.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter(); run(1, 1); tb.append(time.perf_counter() - t0)
+                    if r % 4 == 0:
+                        t0 = time.perf_counter(); run(1, 0); tc.append(time.perf_counter() - t0)
+                pa, pb, pc = np.median(ta) * 1e6, np.median(tb) * 1e6, np.median(tc) * 1e6
+                print(f"{n:10d} {d:4d} {nq:4d} {pa:10.1f} {pb:10.1f} {pa / pb:8.2f} {pc:10.1f} "
+                      f"{'%d/%d/%d' % lists:>18s} {same and took == 1}" + (f"  {first_ms:8.2f}" if first else ""), flush=True)
+                first = False
+            h.close()
+            del V, h, ix
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true", help="with --auto: batches of 5+ queries (parent path, int8 matrix cores, v_dot4 scan)")
+    ap.add_argument("--rows", type=int, nargs="+", default=[2_000_000, 5_000_000, 10_000_000])
+    ap.add_argument("--dims", type=int, nargs="+", default=[128, 384, 512])
+    ap.add_argument("--queries", type=int, nargs="+", default=[5, 8, 16, 64, 128, 256])
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--extra", action="store_true")
     ap.add_argument("--only", type=int, default=-1, help="time only shape number ONLY of the list (profiling runs)")
     ap.add_argument("--auto", action="store_true", help="the automatic shadow (matrix-core bits) instead of the explicit one")
     args = ap.parse_args()
+    if args.batch:
+        return batch_table(args)
     g = torch.Generator(device="cuda").manual_seed(5)
     print(f"{'dtype':8s} {'rows':>10s} {'d':>4s} {'nq':>3s} {'plain us':>9s} {'int8 us':>9s} {'speed-up':>8s} {'cands':>6s} same"
           + ("  first call ms" if args.auto else ""), flush=True)
