@@ -28,8 +28,9 @@ extern "C" {
 
 typedef struct hdb_index hdb_index;
 
-/* dtype of the stored matrix: HyperDB(fp_precision=...) accepts float16/32/64 (hyperdb.py:65-66). */
-enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2 };
+/* dtype of the stored matrix: HyperDB(fp_precision=...) accepts float16/32/64 (hyperdb.py:65-66); bfloat16 (the upper 16 bits of
+ * a float32, 2 bytes per element) is this library's addition for embedding models that emit it. */
+enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3 };
 
 /* metric strings of hyperDB_ranking_algorithm_sort's dispatch table (ranking_algorithm.py:155-163). */
 enum hdb_metric {
@@ -104,7 +105,7 @@ void hdb_index_destroy(hdb_index* ix);
 /* Opt-in int8 shadow of the matrix: quantized row scan with exact rescoring (local-hyperdb_amd/csrc/hdb_quant.hip).
  * HDB_QUANT_I8 builds, next to the float16 / float32 matrix, an owned int8 copy -- one code per element at a row pitch
  * P = round_up(d, 16) bytes -- and 12 bytes of per-row caches: N x (P + 12) bytes of device memory.  HDB_QUANT_NONE frees it.
- * float64 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
+ * float64 and bfloat16 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
  * hdb_index_gather moves codes and caches with the kept rows, hdb_index_update rebuilds it, hdb_index_rebase leaves it alone.
  *
  * The bound.  Row r: s_r = max_j |v_rj| / 127, c_rj = rne(v_rj / s_r), eps_r = v_r - s_r c_r; the query likewise (s_q, c_q,
@@ -192,7 +193,7 @@ int hdb_index_set_row_mask(hdb_index* ix, const uint8_t* dev_mask);
 
 /* Full score vector of one query: the per-metric functions dot_product / cosine_similarity /
  * euclidean_metric / hamming_distance (... :24,:32,:44,:128).  dev_q: d elements, float32 for
- * F16/F32 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
+ * F16/F32/BF16 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
 int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, void* stream);
 
 /* Top-k of nq independent queries: metric scoring + NaN->-inf + bias + argpartition/argsort of
@@ -211,7 +212,21 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  * Calls of 1-4 dot / cosine queries with k <= 128 on an fp16 matrix (d = 256 .. 768; 1-2 queries for d = 1024 .. 1536), or of 1-2 on a float32 matrix
  * (d in {128,256,384}; one query at d = 768 and, from 1.5 M rows on, at d = 512), run as ONE kernel launch (query preparation, row sample, threshold exchange between the
  * workgroups, filter pass, final sort: hdb_mfma_fused.h); everything else is the same pipeline as separate launches.
- * Results are bit-identical either way. */
+ * Results are bit-identical either way.
+ * bfloat16 matrices (HDB_BF16).  Queries are float32.  Every stored value widens to float32 exactly, and the contract is the
+ * float32 one: scores within 1e-5 of the reference's arithmetic on the widened matrix (hamming exact, jaccard 1e-6), on every path.
+ *   - 1-4 queries, every metric, any d, any k, bias and row mask: the VALU scan (float32 arithmetic on the widened values, unrounded
+ *     float32 queries), through the small, sampled, exact and full-sort pipelines, as separate launches.  hamming / jaccard calls
+ *     of 1-4 queries may take their single launch (it reads the packed sign bits only).  Manhattan batches stay on the
+ *     4-queries-per-pass scan (no LDS tile kernel).
+ *   - 5+ dot / cosine / euclidean / pearson queries on a FINITE matrix of d = 128, 256, 384 or 512 with use_mfma on: the matrix
+ *     cores (hdb_mfma_bf16.hip), multi-kernel pipeline.  A float32 query travels as three bf16 parts that add up to it exactly,
+ *     a row is one bf16: three v_mfma_f32_16x16x32_bf16 per k-step, every product exact, float32 accumulation.  A query element
+ *     that is not finite keeps its first part only, so no inf - inf is formed and the status words stay 0.  A matrix with an
+ *     infinite (or overflowing) row stays on the VALU scan (inf x 0 would be NaN where np.dot gives inf).  Other widths stay on the VALU scan.
+ *   - never: the single launches of the matrix-core paths (fused = 0 always), the int8 shadow (hdb_index_quantize returns
+ *     HDB_ERR_UNSUPPORTED, auto_quant does not apply).
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch), path as for the other dtypes. */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 

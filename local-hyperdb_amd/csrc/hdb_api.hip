@@ -245,7 +245,7 @@ static int ensure_ws(hdb_index* ix, size_t bytes) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 102; }
+extern "C" int hdb_version(void) { return 103; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -274,7 +274,7 @@ static double quant_gamma(int d) {
 // gamma_m of the matrix-core sum (hdb_quant.hip, bound (2m)); the per-row cache E_r takes the larger of the two
 static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -22); }
 static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
-static size_t quant_elem(const hdb_index* ix) { return ix->dtype == HDB_F16 ? 2 : 4; }
+static size_t quant_elem(const hdb_index* ix) { return (size_t)hdb_elem_bytes(ix->dtype); }
 static void quant_free(hdb_index* ix) {
     if (ix->qcodes) (void)hipFree(ix->qcodes);
     if (ix->qaux) (void)hipFree(ix->qaux);
@@ -319,6 +319,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
         ix->auto_quant = 0;                            // dropped on request: the index does not build one for itself again
         return HDB_OK;
     }
+    if (ix->dtype == HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     if (!ix->qstat) {
         HIP_TRY(hipMalloc((void**)&ix->qstat, sizeof(int)));
@@ -367,7 +368,7 @@ extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, i
     if (!out) return fail(HDB_ERR_ARG, "hdb_index_create: out is null");
     if (n < 0 || d <= 0) return fail(HDB_ERR_ARG, "hdb_index_create: need n >= 0 and d > 0");
     if (n > 0 && !dev_V) return fail(HDB_ERR_ARG, "hdb_index_create: matrix pointer is null");
-    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64");
+    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16");
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_create: at most 2^32-2 rows per shard");
     if ((int64_t)d * 8 > 60 * 1024) return fail(HDB_ERR_ARG, "hdb_index_create: d too large for the query LDS tile");
     HIP_TRY(hipSetDevice(device));
@@ -433,7 +434,7 @@ extern "C" int hdb_index_extend(hdb_index* ix, int64_t new_n, void* stream) {
         if (ix->inv_norm) { HIP_TRY(hipFree(ix->inv_norm)); HIP_TRY(hipFree(ix->sqnorm)); }
         ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
     }
-    const size_t elem = ix->dtype == HDB_F16 ? 2 : ix->dtype == HDB_F32 ? 4 : 8;
+    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     const char* tail = (const char*)ix->V + (size_t)old_n * ix->d * elem;
     LAUNCH_TRY(hdb_launch_rownorm(tail, new_n - old_n, ix->d, ix->dtype, ix->inv_norm + old_n, ix->sqnorm + old_n, ix->nan_flag, st));
     ix->n = new_n;
@@ -457,7 +458,7 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     if (m > 0 && dev_V_out == ix->V) return fail(HDB_ERR_ARG, "hdb_index_gather: the gather is out of place");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t elem = ix->dtype == HDB_F16 ? 2 : ix->dtype == HDB_F32 ? 4 : 8;
+    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     float *inv2 = nullptr, *sq2 = nullptr;
     const int64_t rows = m + m / 4 + 64;
     HIP_TRY(hipMalloc((void**)&inv2, rows * sizeof(float)));
@@ -663,7 +664,7 @@ static bool is_bits_metric(int metric) { return metric == HDB_HAMMING || metric 
 
 static int ensure_pscale(hdb_index* ix, hipStream_t st) {
     if (ix->pscale_valid) return HDB_OK;
-    const size_t elem = ix->dtype == HDB_F16 ? 2 : ix->dtype == HDB_F32 ? 4 : 8;
+    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     int64_t keep = ix->pscale ? std::min(ix->pscale_done, ix->n) : 0;          // rows whose scale is still good (appended matrix)
     if (ix->n > ix->pscale_rows) {
         const int64_t rows = ix->n + ix->n / 4 + 64;
@@ -684,7 +685,7 @@ static int ensure_bits(hdb_index* ix, hipStream_t st) {
     if (ix->bits_valid) return HDB_OK;
     const int W = (ix->d + 31) / 32;
     if (W > 512) return fail(HDB_ERR_UNSUPPORTED, "hamming: d > 16384 not supported");
-    const size_t elem = ix->dtype == HDB_F16 ? 2 : ix->dtype == HDB_F32 ? 4 : 8;
+    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     const int64_t npad = align_up((size_t)std::max<int64_t>(ix->n, 4), 256);      // whole 256-row blocks (hdb_bits_word)
     // rows packed before the matrix grew stay where they are: the layout is a sequence of 256-row blocks, so a bigger buffer takes
     // the old blocks as a prefix (hdb_index_extend / HyperDB.add: the next bit-metric call packs the appended rows only)
@@ -1068,7 +1069,8 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     // d = 768: 1 030 vs 1 714, the VALU pass stays)
     const int64_t f32_min_q = ix->f32_min_q >= 0 ? ix->f32_min_q : ((ix->d <= 384 && n >= 300000) ? 3 : 5);
     // (widths without a geometry of their own ride the next wider one through the multi-kernel pipeline: like the K slices, from five queries on)
-    const int64_t min_q = (hdb_mfma_ksplit_slices(ix->dtype, ix->d) > 0 || hdb_mfma_anyd_pad(ix->dtype, ix->d) > 0) ? std::max<int64_t>(ix->mfma_min_q, 5)
+    // (bfloat16 rows, hdb_mfma_bf16.hip, likewise: up to 4 queries are one VALU pass with unrounded float32 queries)
+    const int64_t min_q = (hdb_mfma_ksplit_slices(ix->dtype, ix->d) > 0 || hdb_mfma_anyd_pad(ix->dtype, ix->d) > 0 || ix->dtype == HDB_BF16) ? std::max<int64_t>(ix->mfma_min_q, 5)
                         : ix->dtype == HDB_F32 ? std::max<int64_t>(ix->mfma_min_q, f32_min_q) : ix->mfma_min_q;
     // hdb_mfma_fused_kernel is built around ONE multiplying wave and two selector waves: with 2-4 fp16 queries its sample phase and
     // epilogue cost more than the batched single launch (eight multiplying waves) until the pass itself dominates -- n = 100k x 384,
@@ -1076,8 +1078,11 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     // float32 (VALU flavour, two queries): the single launch wins at every size.
     const int64_t fused_max_q = ix->fused_max_q >= 0 ? ix->fused_max_q
                               : ix->dtype == HDB_F32 ? HDB_FUSED_MAXQ_RULE : (n >= 1500000 ? 3 : 1);
-    const bool mfma = ix->use_mfma && !is_ham && !small && nq >= min_q &&
-                      hdb_mfma_supported(ix->dtype, ix->d, is_pearson ? (int)HDB_COSINE : metric);
+    bool mfma = ix->use_mfma && !is_ham && !small && nq >= min_q &&
+                hdb_mfma_supported(ix->dtype, ix->d, is_pearson ? (int)HDB_COSINE : metric);
+    // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
+    // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
+    if (mfma && ix->dtype == HDB_BF16) { const int rcf = matrix_is_finite(ix, &mfma); if (rcf != HDB_OK) return rcf; }
     // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call; an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.

@@ -6,6 +6,19 @@
 
 #define HDB_WAVE 64
 
+// ---- element types -------------------------------------------------------------------------------
+// Bytes of one stored matrix element per hdb_dtype (include/hyperdb_hip.h: 0 float16, 1 float32, 2 float64, 3 bfloat16); 0 = no such
+// dtype.  Every row pitch in the library comes from here.
+__host__ __device__ __forceinline__ int hdb_elem_bytes(int dtype) {
+    return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : 0;
+}
+// A bfloat16 as it lies in memory: the upper 16 bits of the float32 of the same value, so widening is a shift and exact.
+struct hdb_bf16 { unsigned short bits; };
+__host__ __device__ __forceinline__ float hdb_bf16_to_f(hdb_bf16 v) {
+    const unsigned int u = (unsigned int)v.bits << 16;
+    return __builtin_bit_cast(float, u);
+}
+
 // ---- candidate / selection geometry -------------------------------------------------------
 // Candidates that pass the per-query threshold are appended to a per-query list of CAP packed
 // 64-bit entries: (orderable score key << 32) | (0xFFFFFFFF - local row).  Sorting those

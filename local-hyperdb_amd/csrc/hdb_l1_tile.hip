@@ -284,7 +284,7 @@ extern "C" int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int
     hipStream_t st = (hipStream_t)stream;
     if (a.mask || a.tile_stride != 1) return (int)hipErrorNotSupported;
     const int cus = hdb_cu_count();
-    const int rowb = a.d * (dtype == HDB_F16 ? 2 : 4);
+    const int rowb = a.d * hdb_elem_bytes(dtype);
     const int R = rowb <= 768 ? 64 : rowb <= 1536 ? 32 : 16;
     const int64_t tiles = (a.n + R - 1) / R;
     int blocks = (int)(tiles < cus ? tiles : cus);

@@ -44,6 +44,9 @@ __global__ __launch_bounds__(64) void hdb_q_to_f16_kernel(const float* Q, int nq
 // the rounding of the expansion, ~1e-6 (||v||^2 + ||q||^2), exceeds 4e-5 of the distance itself -- are re-scored
 // from the stored row with the direct difference, like the reference (:49); beyond that the expansion is good to
 // 5e-6 in the similarity.  One wave per entry.
+__device__ __forceinline__ float hdb_row_f(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float hdb_row_f(float v) { return v; }
+__device__ __forceinline__ float hdb_row_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 template <typename T, bool HAS_BIAS>
 __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long long* cand, const uint32_t* cnt, uint32_t cap,
                                                                  const T* V, int d, const float* Q, const float* qsq, int q0,
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long l
         const float dist = 1.f / sim - 1.f;
         if (sim > 0.f && dist * dist < close2) {                   // wave-uniform: one entry per wave
             float acc = 0.f;
-            for (int k = lane; k < d; k += 64) { const float df = (float)V[(int64_t)row * d + k] - qv[k]; acc += df * df; }
+            for (int k = lane; k < d; k += 64) { const float df = hdb_row_f(V[(int64_t)row * d + k]) - qv[k]; acc += df * df; }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
             s = hdb_canon(1.f / (1.f + sqrtf(acc)) + b);
@@ -81,8 +84,15 @@ extern "C" int hdb_mfma_ksplit_slices(int dtype, int d);
 extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                                       const float* qsq, const float* qscl, int blocks, void* stream);
 
+// bfloat16 rows (hdb_mfma_bf16.hip): d = 128, 256, 384 and 512 -- the query fragments of 16 queries take 48, 96, 144 and 192
+// registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted
+extern "C" int hdb_mfma_bf16_tile_rows(int d);
+extern "C" int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                         const float* qsq, int blocks, void* stream);
+
 static int mfma_exact_tile_rows(int dtype, int d) {
-    const int elem = dtype == HDB_F16 ? 2 : dtype == HDB_F32 ? 4 : 0;
+    if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
+    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
     if (!elem || d <= 0) return 0;
     if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
     const int row_bytes = d * elem;
@@ -96,7 +106,7 @@ static int mfma_exact_tile_rows(int dtype, int d) {
 // Rows of any width that is a multiple of 16 bytes and has no geometry of its own ride the next wider one as a single K slice
 // (hdb_mfma_anyd.h): -> that width, or 0.  fp16 d % 8 == 0 up to 1024, float32 d % 4 == 0 up to 768.
 extern "C" int hdb_mfma_anyd_pad(int dtype, int d) {
-    const int elem = dtype == HDB_F16 ? 2 : dtype == HDB_F32 ? 4 : 0;
+    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;      // (bfloat16: its own widths only)
     if (!elem || d <= 0 || (d * elem) % 16 != 0 || mfma_exact_tile_rows(dtype, d) > 0) return 0;
     static const int w16[] = {128, 256, 384, 512, 768, 1024}, w32[] = {128, 256, 384, 512, 768};
     if (dtype == HDB_F16) { for (int w : w16) if (w >= d) return w; }
@@ -117,6 +127,7 @@ extern "C" int hdb_mfma_tile_rows(int dtype, int d) {
 // queries ONE launch of the MFMA scan covers (grid.y == 1): what a single-launch (mode 2) call can take
 extern "C" int hdb_mfma_batch_capacity(int dtype, int d) {
     if (hdb_mfma_tile_rows(dtype, d) <= 0 || hdb_mfma_ksplit_slices(dtype, d) > 0 || hdb_mfma_anyd_pad(dtype, d) > 0) return 0;      // (K slices, odd widths: the multi-kernel pipeline)
+    if (dtype == HDB_BF16) return 0;                                     // (bfloat16 rows likewise: no single launch is built)
     if (dtype == HDB_F32) return (d == 512 || d == 768) ? 64 : 128;      // (d = 512 / 768: the bf16-part flavour pairs its waves over K, hdb_mfma_kernel.h KP)
     return (d == 384 || d == 128 || d == 256 || d == 512 || d == 640) ? 256 : 128;      // two query tiles per wave (hdb_mfma_qt2.hip)
 }
@@ -193,6 +204,7 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
     }
     if (dtype == HDB_F32) return (a.f32_split > 0 && hdb_mfma_f32_split_min_q(a.d) > 0) ? hdb_launch_mfma_scan_f32s(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f)
                                                                                    : hdb_launch_mfma_scan_f32(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f);
+    if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);
     if (dtype != HDB_F16) return (int)hipErrorNotSupported;
     // (mode 2 promises hdb_mfma_batch_capacity() queries in ONE launch: only the two-tile launcher holds more than 128, whatever the variant)
     if (nq_launch > 128 && hdb_mfma_qt2_supported(a.d) && (g_mfma_variant != 32 || (mode == 2 && a.d != 384)))
@@ -219,6 +231,9 @@ extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_
     if (dtype == HDB_F16) {
         if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);
         else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);
+    } else if (dtype == HDB_BF16) {
+        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_bf16, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_bf16*)V, d, Q, qsq, q0, bias);
+        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_bf16, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_bf16*)V, d, Q, qsq, q0, bias);
     } else {
         if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<float, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const float*)V, d, Q, qsq, q0, bias);
         else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<float, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const float*)V, d, Q, qsq, q0, bias);

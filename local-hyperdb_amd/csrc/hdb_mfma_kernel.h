@@ -183,6 +183,32 @@ __device__ __forceinline__ HdbParts3 hdb_split3(const HdbRaw8& r) {
     return o;
 }
 
+// The same split for the flavour whose rows ARE bf16 in memory (MfmaShape<16, hdb_bf16>): an element that is not finite keeps its
+// first part only -- p0 = the infinity (a NaN stays a NaN: its quiet bit is set in case the payload sat in the lower 16 bits), p1 =
+// p2 = 0 -- so inf - inf is never formed and a finite row times such a query gives what float32 arithmetic gives.
+__device__ __forceinline__ HdbParts3 hdb_split3_finite(const HdbRaw8& r) {
+    HdbParts3 o;
+    const float x[8] = {r.lo[0], r.lo[1], r.lo[2], r.lo[3], r.hi[0], r.hi[1], r.hi[2], r.hi[3]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        unsigned int hb[2], wb[2], tb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float v = x[2 * j + i];
+            const unsigned int u = hdb_fbits(v);
+            const bool nonfin = (u & 0x7F800000u) == 0x7F800000u;
+            hb[i] = (u & 0xFFFF0000u) | ((nonfin && (u & 0x007FFFFFu) != 0u) ? 0x00400000u : 0u);
+            const float r1 = nonfin ? 0.f : v - hdb_bitsf(hb[i]);
+            wb[i] = hdb_fbits(r1) & 0xFFFF0000u;
+            tb[i] = hdb_fbits(r1 - hdb_bitsf(wb[i]));
+        }
+        o.p0[j] = __builtin_amdgcn_perm(hb[1], hb[0], 0x07060302u);
+        o.p1[j] = __builtin_amdgcn_perm(wb[1], wb[0], 0x07060302u);
+        o.p2[j] = __builtin_amdgcn_perm(tb[1], tb[0], 0x07060302u);
+    }
+    return o;
+}
+
 // MF: rows / queries per MFMA tile; E: element type of V and of the query fragments.  CPS = 16-byte chunks per k-step
 // (one ds_read_b128 per lane and k-step: lane group h = lane / MF holds chunk CPS*s + h of its row).
 // Eight floats -> [bf16(v) x 8][bf16(v - bf16(v)) x 8], round to nearest even; element order = the order hdb_split3 packs in
@@ -255,6 +281,26 @@ template <> struct MfmaShape<16, hdb_f32s> {
     }
 };
 
+// bfloat16 rows (HDB_BF16): the bytes in memory are the A fragments as they stand -- the LDS ring, swizzle and fragment map of the fp16
+// flavour, no conversion, one 16-byte chunk per lane and k-step.  The float32 queries travel as three exact bf16 parts
+// (hdb_split3_finite), built once per launch in the prologue: v . q = v p2 + v p1 + v p0, smallest part first, every product exact
+// (8 x 8 significant bits), the only rounding is the float32 accumulation.  3 x d/8 registers of query fragments per 16 queries.
+template <> struct MfmaShape<16, hdb_bf16> {
+    using Acc = f32x4; using Vec = u32x4; using BVec = HdbParts3;
+    static constexpr int RPF = 1;
+    static constexpr bool CONV = false;
+    static constexpr int CPS = 4, NGRP = 1;
+    __device__ static __forceinline__ Acc mma(const Vec& a, const HdbParts3& b, Acc c) {
+#define HDB_BF(x) __builtin_bit_cast(hdb_bf16x8, x)
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(a), HDB_BF(b.p2), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(a), HDB_BF(b.p1), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(a), HDB_BF(b.p0), c, 0, 0, 0);
+#undef HDB_BF
+    }
+};
+template <typename E> struct HdbIsBf16Rows { static constexpr bool value = false; };
+template <> struct HdbIsBf16Rows<hdb_bf16> { static constexpr bool value = true; };
+
 // METRIC: 0 dot, 1 cosine (aux0 = 1/||v||), 2 euclidean similarity (aux0 = ||v||^2)
 // Fragment maps (lane l):  MF=32: row/query l&31, k = 16s + 8(l>>5) + j, C reg e -> row (e&3) + 8(e>>2) + 4(l>>5)
 //                          MF=16: row/query l&15, k = 32s + 8(l>>4) + j, C reg e -> row 4(l>>4) + e
@@ -319,6 +365,9 @@ __global__ __launch_bounds__(NW * 64) void hdb_mfma_kernel(ScanArgs a, const E* 
     static_assert(MODE != 3 || (KSL && METRIC == 0 && !HAS_BIAS), "MODE 3 = raw partial sums of a K slice");
     static_assert(!KSL || (MODE != 2 && NW == 8), "K slices run in the multi-kernel pipeline");
 
+    constexpr bool BF16R = HdbIsBf16Rows<E>::value; // bf16 rows, float32 queries in three parts: the multi-kernel pipeline, whole rows
+    static_assert(!BF16R || (MODE != 2 && MODE != 3 && !KSL && KP == 1 && NW == 8 && MF == 16), "bf16 rows: MODE 0 / 1 only");
+
     constexpr bool FILT = MODE == 1 || MODE == 2;   // the pass over all rows filters against per-query thresholds
     constexpr bool ONE = MODE == 2;             // the whole call in this launch
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -357,6 +406,15 @@ __global__ __launch_bounds__(NW * 64) void hdb_mfma_kernel(ScanArgs a, const E* 
         q_ok[qt] = q < nq_end;
         ql[qt] = q - a.q0;
         const int qq = q_ok[qt] ? q : (nq_end - 1);
+        if constexpr (BF16R) {          // the lane's 8 k slots of step s are floats 8 (CPS s + h) .. + 7 of the float32 query
+            const float4* qf = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(q16) + (int64_t)qq * D) + 2 * h;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                float4 x0 = qf[2 * CPS * s], x1 = qf[2 * CPS * s + 1];
+                if (!q_ok[qt]) { x0 = make_float4(0.f, 0.f, 0.f, 0.f); x1 = x0; }
+                Bq[qt][s] = hdb_split3_finite(HdbRaw8{f32x4{x0.x, x0.y, x0.z, x0.w}, f32x4{x1.x, x1.y, x1.z, x1.w}});
+            }
+        } else {
         const uint4* src = reinterpret_cast<const uint4*>(KSL ? q16 + (int64_t)qq * a.ks_dfull + a.ks_off / ES : q16 + (int64_t)qq * D) + RPF * h;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
@@ -368,6 +426,7 @@ __global__ __launch_bounds__(NW * 64) void hdb_mfma_kernel(ScanArgs a, const E* 
             }
             if constexpr (RPF == 1) Bq[qt][s] = *reinterpret_cast<Vec*>(&v[0]);
             else Bq[qt][s] = hdb_split3(HdbRaw8{*reinterpret_cast<f32x4*>(&v[0]), *reinterpret_cast<f32x4*>(&v[RPF - 1])});
+        }
         }
         thr_l[qt] = 0.f; qinv_l[qt] = 1.f; qsq_l[qt] = 0.f;
         if (q_ok[qt]) {
@@ -1427,6 +1486,14 @@ static int launch_metric(const ScanArgs& a, const void* q16, const float* sqnorm
                                          : launch_one<E, MF, QT, D, R, RS, MODE, 1, false, KP>(a, q16, a.inv_norm, qsq, qscl, nq_launch, blocks, st, f);
     if (a.metric == HDB_EUCLIDEAN) return b ? launch_one<E, MF, QT, D, R, RS, MODE, 2, true, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f)
                                             : launch_one<E, MF, QT, D, R, RS, MODE, 2, false, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
+    return (int)hipErrorNotSupported;
+}
+
+// the multi-kernel pipeline only (bf16 rows): MODE 0 = scores, MODE 1 = filter; no single launch is instantiated
+template <typename E, int MF, int QT, int D, int R, int RS = 1>
+static int launch_mode01(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+    if (mode == 0) return launch_metric<E, MF, QT, D, R, RS, 0>(a, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, nullptr);
+    if (mode == 1) return launch_metric<E, MF, QT, D, R, RS, 1>(a, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, nullptr);
     return (int)hipErrorNotSupported;
 }
 

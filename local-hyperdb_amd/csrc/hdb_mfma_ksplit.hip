@@ -31,7 +31,7 @@ extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode,
     const KsGeom g = ks_geom(dtype, args->d);
     if (!g.slices || !args->ks_partial_out) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    const int es = dtype == HDB_F16 ? 2 : 4;
+    const int es = hdb_elem_bytes(dtype);
     for (int s = 0; s < g.slices; ++s) {
         ScanArgs a = *args;
         a.ks_pitch = (int64_t)args->d * es; a.ks_off = s * g.dslice * es; a.ks_dfull = args->d;

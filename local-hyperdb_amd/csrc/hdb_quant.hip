@@ -730,7 +730,7 @@ extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const f
     RescoreArgs a;
     a.V = V; a.d = d; a.Q = Q; a.metric = metric; a.inv_norm = inv_norm; a.qinv = qinv; a.bias = bias; a.mask = mask;
     a.cand = cand; a.cnt = cnt; a.cap = cap;
-    const int elem = dtype == HDB_F16 ? 2 : 4;
+    const int elem = hdb_elem_bytes(dtype);
     a.row_bytes = d * elem;
     a.nchunks = a.row_bytes / 16;
     // the same choice as hdb_launch_scan: 16-byte pieces when rows are whole pieces of an aligned matrix

@@ -17,6 +17,7 @@
 
 template <typename T> struct Elem;
 template <> struct Elem<__half> { using Acc = float;  static constexpr int EPC = 8; };
+template <> struct Elem<hdb_bf16> { using Acc = float; static constexpr int EPC = 8; };
 template <> struct Elem<float>  { using Acc = float;  static constexpr int EPC = 4; };
 template <> struct Elem<double> { using Acc = double; static constexpr int EPC = 2; };
 
@@ -24,6 +25,12 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[8], __ha
     const __half2* h = reinterpret_cast<const __half2*>(&raw);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { float2 f = __half22float2(h[i]); x[2 * i] = f.x; x[2 * i + 1] = f.y; }
+}
+// bfloat16 pairs: the even element is the low half of its word (a shift), the odd one the high half (a mask)
+__device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[8], hdb_bf16*) {
+    const unsigned int w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(w[i] << 16); x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
 }
 __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[4], float*) {
     x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
@@ -35,6 +42,7 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, double (&x)[2], dou
 }
 
 __device__ __forceinline__ float hdb_to_f(__half v) { return __half2float(v); }
+__device__ __forceinline__ float hdb_to_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 __device__ __forceinline__ float hdb_to_f(float v) { return v; }
 __device__ __forceinline__ double hdb_to_f(double v) { return v; }
 
@@ -533,7 +541,7 @@ static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec
 extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream) {
     ScanArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
-    const int elem = dtype == HDB_F16 ? 2 : dtype == HDB_F32 ? 4 : 8;
+    const int elem = hdb_elem_bytes(dtype);
     a.row_bytes = a.d * elem;
     a.nchunks = a.row_bytes / 16;
     const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(a.V) & 15) == 0) &&
@@ -548,6 +556,7 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
     const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : auto_blocks);
     if (dtype == HDB_F16) { if (mode == 0) launch_scan_t<__half, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<__half, 1>(a, nq_launch, blocks, vec, st); }
     else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1>(a, nq_launch, blocks, vec, st); }
+    else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1>(a, nq_launch, blocks, vec, st); }
     else { if (mode == 0) launch_scan_t<double, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1>(a, nq_launch, blocks, vec, st); }
     return (int)hipGetLastError();
 }
@@ -558,6 +567,7 @@ extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, fl
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rownorm_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rownorm_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, inv_norm, sqnorm, nan_flag);
+    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, inv_norm, sqnorm, nan_flag);
     else hipLaunchKernelGGL(hdb_rownorm_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, inv_norm, sqnorm, nan_flag);
     return (int)hipGetLastError();
 }
@@ -580,12 +590,14 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
         const int blocks = hdb_grid_for((n + 7) / 8, 4, 4096);      // a wave per eight rows
         if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
         else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_wide_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
+        else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
         else hipLaunchKernelGGL(hdb_signpack_wide_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
         return (int)hipGetLastError();
     }
     const int blocks = hdb_grid_for(n, 4, 4096);
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
+    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
     else hipLaunchKernelGGL(hdb_signpack_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
     return (int)hipGetLastError();
 }
@@ -716,6 +728,7 @@ extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, f
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rowstats_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, pscale);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rowstats_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, pscale);
+    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, pscale);
     else hipLaunchKernelGGL(hdb_rowstats_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, pscale);
     return (int)hipGetLastError();
 }

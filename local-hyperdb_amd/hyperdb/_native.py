@@ -16,7 +16,7 @@ import torch  # must be imported before the .so so that ONE libamdhip64 (torch's
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HYPERDB_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libhyperdb_hip.so")
 
-HDB_F16, HDB_F32, HDB_F64 = 0, 1, 2
+HDB_F16, HDB_F32, HDB_F64, HDB_BF16 = 0, 1, 2, 3
 METRIC_IDS = {
     "dot_product": 0,
     "cosine_similarity": 1,
@@ -122,7 +122,8 @@ def require_gpu():
 
 
 _NP2HDB = {np.dtype(np.float16): HDB_F16, np.dtype(np.float32): HDB_F32, np.dtype(np.float64): HDB_F64}
-_TORCH2HDB = {torch.float16: HDB_F16, torch.float32: HDB_F32, torch.float64: HDB_F64}
+# (numpy has no bfloat16: a bf16 matrix arrives as a torch tensor and leaves as its exact float32 widening)
+_TORCH2HDB = {torch.float16: HDB_F16, torch.float32: HDB_F32, torch.float64: HDB_F64, torch.bfloat16: HDB_BF16}
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)      # the current stream's handle without building a Stream object (0.3 vs 1.5 us)
@@ -141,8 +142,8 @@ def _stream_ptr(device):
 def to_device_matrix(vectors, device):
     """numpy / list / torch -> C-contiguous 2-D torch tensor on `device` in a supported dtype.
 
-    Dtype policy mirrors HyperDB.fp_precision (hyperdb.py:65-66): float16/32/64 stay as they are,
-    anything else numeric (ints, bools) is widened to float64 like numpy would promote it."""
+    Dtype policy mirrors HyperDB.fp_precision (hyperdb.py:65-66): float16/32/64 stay as they are (and so does a
+    torch.bfloat16 tensor: 2 bytes per element on the device), anything else numeric (ints, bools) is widened to float64 like numpy would promote it."""
     if isinstance(vectors, torch.Tensor):
         t = vectors
         if t.dtype not in _TORCH2HDB:
@@ -243,6 +244,8 @@ class GpuIndex:
     def update(self, vectors):
         """Point the handle at a new matrix (after add/remove) and rebuild the row caches."""
         t = to_device_matrix(vectors, self.device)
+        if self.dtype == HDB_BF16 and t.dtype != torch.bfloat16:
+            t = t.to(torch.bfloat16)                        # float data into a bf16 index: round to nearest even, as append does
         if t.dim() != 2 or int(t.shape[1]) != self.d or _TORCH2HDB[t.dtype] != self.dtype:
             raise ValueError("update: matrix must keep d and dtype")
         self.V, self.n = t, int(t.shape[0])
@@ -269,7 +272,10 @@ class GpuIndex:
         _check(_lib.hdb_index_set_row_base(self._h, self.row_base), "hdb_index_set_row_base")
 
     def host_matrix(self):
-        """The stored rows as a host array (one D2H copy; the resident copy stays the only one kept)."""
+        """The stored rows as a host array (one D2H copy; the resident copy stays the only one kept).  A bfloat16 index returns
+        the exact float32 widening (numpy has no bfloat16)."""
+        if self.V.dtype == torch.bfloat16:
+            return self.V.float().cpu().numpy()
         return self.V.cpu().numpy()
 
     def compact(self, keep_rows):

@@ -66,12 +66,14 @@ class HyperDB:
     def __init__(self, documents=None, vectors=None, select_keys=None, embedding_function=None, fp_precision="float32",
                  add_timestamp=False, metadata_keys=None, ann_metric="cosine", n_trees=10, cache_size=256, device=None,
                  devices=None, quantize=None):
-        if fp_precision not in ["float16", "float32", "float64"]:
+        # ("bfloat16" is this build's addition: host arrays stay float32, the resident matrix is torch.bfloat16)
+        if fp_precision not in ["float16", "float32", "float64", "bfloat16"]:
             raise ValueError("Unsupported floating-point precision.")                       # hyperdb.py:65-66
         accepted = ["angular", "euclidean", "manhattan", "hamming", "dot", "cosine"]
         if ann_metric not in accepted:
             raise ValueError(f"Unsupported ANN metric. Accepted values are: {', '.join(accepted)}")  # :69-71
-        self.fp_precision = getattr(np, fp_precision)
+        self.bf16 = fp_precision == "bfloat16"
+        self.fp_precision = np.float32 if self.bf16 else getattr(np, fp_precision)
         self.embedding_function = embedding_function
         self.select_keys = [select_keys] if isinstance(select_keys, str) else select_keys
         self.metadata_keys = [metadata_keys] if isinstance(metadata_keys, str) else (metadata_keys or [])
@@ -136,6 +138,8 @@ class HyperDB:
         self.source_indices = list(self.source_indices) + list(range(start, start + len(documents)))
         self._invalidate_rows()
         if self._index is None:
+            if self.bf16:                             # round to nearest even at upload; later appends convert the same way (GpuIndex.append)
+                vectors = torch.from_numpy(np.ascontiguousarray(vectors)).to(torch.bfloat16)
             self._index = GpuGroup(vectors, self.devices) if self.devices else GpuIndex(vectors, device=self.device)
             if self.quantize is not None:             # (append / compact / update keep the shadow current from here on)
                 self._index.quantize(self.quantize)
