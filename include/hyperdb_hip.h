@@ -162,9 +162,24 @@ void hdb_index_destroy(hdb_index* ix);
  * quant_cands_median = the smallest / median list of its last chunk (both synchronise).
  * Workspace of a chunk of cq queries: the lists, cq x HDB_CAND_CAP x 8 bytes (16 MiB at 256 queries), at most cq x 8192 floats of
  * sample maxima, cq x d fp16 query values and the per-query words; no compact matrix and no score block.  A batch call can be
- * the one that builds the shadow and pays for it. */
+ * the one that builds the shadow and pays for it.
+ *
+ * The 5-bit plane (one dot / cosine query; hdb_quant.hip, "The 5-bit plane").  Beside the codes the index keeps their high five
+ * bits -- a nibble plane, a bit plane and a 16-byte record per row, 20 bytes per 32 elements + 16 (10M x 384: 2.56 GB) -- derived
+ * from the codes wherever the shadow's rows are written (build, extend, update, gather) for rows of up to 512 elements.  A
+ * one-query call of at least plane_min_n rows (-1: the measured rule, 2 000 000) with use_plane on first streams the plane
+ * (pass 1) and keeps the rows whose coarse upper bound hi5 reaches T_s in a list of n / 8 row numbers (plane_cap_rows overrides
+ * the capacity), then runs the int8 pass over those rows only (pass 2).  hi5 >= the int8 pass's own upper bound for every row, so
+ * the candidate list, and the answer, are those of the call without the plane.  A list that overflows makes pass 2 scan all rows
+ * instead (correct, one wasted pass; there is no automatic switch-off: use_plane = 0 is the manual one).  Euclidean calls, 2-4
+ * queries and batches never take the plane.  The plane is under the automatic build's memory guard: when the shadow fits and
+ * the plane does not, the shadow is built alone.  Stats: plane (the last call took it), plane_bytes, plane_survivors (rows pass 1
+ * kept in the last call) and plane_overflows (calls of this index whose list overflowed); the last two synchronise. */
 enum hdb_quant { HDB_QUANT_NONE = 0, HDB_QUANT_I8 = 1 };
 int hdb_index_quantize(hdb_index* ix, int mode, void* stream);
+/* Test entry: the upper bound of every row for ONE float32 query (dot or cosine) as the int8 pass computes it (dev_hi, n floats)
+ * and as pass 1 over the 5-bit plane computes it (dev_hi5, n floats).  Needs a shadow with its plane; nothing is selected. */
+int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int metric, float* dev_hi, float* dev_hi5, void* stream);
 
 /* 1 if the matrix contains a NaN (synchronises `stream` of the create/update call). */
 int hdb_index_has_nan(hdb_index* ix, int* out_flag);
@@ -316,12 +331,13 @@ void hdb_group_destroy(hdb_group* g);
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),
  *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never), quant_batch_min_n (batches
  *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
- *   cores, 0: the v_dot4 scan four queries at a time).
+ *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane),
+ *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; the survivor list's capacity, for tests).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
  *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
- *   quant_bytes, quant_auto. */
+ *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows. */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

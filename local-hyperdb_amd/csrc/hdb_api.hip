@@ -77,13 +77,18 @@ int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype, int P, int
                           void* stream);
 int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m, int P, int8_t* codes_out,
                             float* aux_out, void* stream);
-int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, void* stream);
+int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt, void* stream);
+int hdb_quant_plane_units(int P);
+int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
+                                float* rec, void* stream);
+int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream);
+int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
                              const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
                              const uint32_t* cnt, uint32_t cap, void* stream);
 int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
-                            int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, void* stream);
+                            int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
 int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks);
 int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
                              const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv, float* gbias,
@@ -162,7 +167,14 @@ struct hdb_index {
     float* qaux = nullptr;
     int64_t q_rows = 0;               // capacity in rows
     int32_t qP = 0;                   // code pitch: d rounded up to 16 bytes
-    int* qstat = nullptr;             // device word: largest candidate count of the last quantized call
+    int* qstat = nullptr;             // device words (HDB_QSTAT_WORDS): [0] largest candidate count of the last quantized call,
+                                      // [1] survivors of its pass over the 5-bit plane, [2] calls whose survivor list overflowed
+    // the 5-bit plane beside the shadow (hdb_quant.hip): nibbles [rows][pU][16], bits [rows][pU], records [rows][4]; q_rows rows each
+    uint8_t* pnib = nullptr;
+    uint32_t* pbit = nullptr;
+    float* prec = nullptr;
+    int32_t pU = 0;                   // 32-element units per row
+    bool plane_declined = false;      // no memory for it (the shadow alone serves): stands until hdb_index_update / hdb_index_quantize
     bool qauto = false;               // the shadow was built by the index itself (auto_quant): its calls return the matrix cores' bits
     bool qauto_declined = false;      // ... or could not be (memory): the decision stands until the matrix changes
     // scratch (owned)
@@ -207,7 +219,11 @@ struct hdb_index {
     int64_t auto_quant = 1;           // fp16 matrix, 1-4 dot / cosine queries on the matrix cores: build the shadow on the first eligible call of a large index
     int64_t quant_batch_min_n = -1;   // ... batches of 5+ queries: from this many rows on (-1: the measured rule, quant_batch_rule)
     int64_t quant_batch_kernel = 1;   // ... their filter pass: 1 = int8 matrix cores (hdb_quant_mfma.hip), 0 = the v_dot4 scan, four queries per pass
+    int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
+    int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
+    int64_t plane_cap_rows = 0;       // ... survivor list capacity in rows (0: n / 8; tests)
     int64_t st_quant = 0;             // the last hdb_topk call took the int8 shadow
+    int64_t st_plane = 0;             // ... behind the 5-bit plane
     const uint32_t* qb_cnt = nullptr; // ... as a batch: the list counters of its last chunk (in the workspace) and their number
     int qb_cnt_n = 0;
     // stats of the last hdb_topk call
@@ -275,10 +291,54 @@ static double quant_gamma(int d) {
 static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -22); }
 static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
 static size_t quant_elem(const hdb_index* ix) { return (size_t)hdb_elem_bytes(ix->dtype); }
+#define HDB_QSTAT_WORDS 4
+static void plane_free(hdb_index* ix) {
+    if (ix->pnib) (void)hipFree(ix->pnib);
+    if (ix->pbit) (void)hipFree(ix->pbit);
+    if (ix->prec) (void)hipFree(ix->prec);
+    ix->pnib = nullptr; ix->pbit = nullptr; ix->prec = nullptr;
+}
 static void quant_free(hdb_index* ix) {
     if (ix->qcodes) (void)hipFree(ix->qcodes);
     if (ix->qaux) (void)hipFree(ix->qaux);
     ix->qcodes = nullptr; ix->qaux = nullptr; ix->q_rows = 0;
+    plane_free(ix);
+}
+// The 5-bit plane of the shadow (hdb_quant.hip): 20 bytes per 32-element unit and a 16-byte record per row, for rows of up to 512
+// elements (the widths the plane path takes).
+static bool plane_possible(const hdb_index* ix) { return ix->d <= 512; }
+// an index whose caller switched the path off (use_plane = 0) before the shadow was built does not pay for a plane
+static bool plane_wanted(const hdb_index* ix) { return plane_possible(ix) && ix->use_plane; }
+static size_t plane_row_bytes(int P) { return (size_t)hdb_quant_plane_units(P) * 20 + 16; }
+static bool plane_alloc(hdb_index* ix, int64_t rows, uint8_t** nib, uint32_t** bit, float** rec) {
+    const size_t U = (size_t)hdb_quant_plane_units(ix->qP);
+    *nib = nullptr; *bit = nullptr; *rec = nullptr;
+    if (hipMalloc((void**)nib, (size_t)rows * U * 16) == hipSuccess && hipMalloc((void**)bit, (size_t)rows * U * 4) == hipSuccess &&
+        hipMalloc((void**)rec, (size_t)rows * 16) == hipSuccess) return true;
+    (void)hipGetLastError();
+    if (*nib) (void)hipFree(*nib);
+    if (*bit) (void)hipFree(*bit);
+    if (*rec) (void)hipFree(*rec);
+    *nib = nullptr; *bit = nullptr; *rec = nullptr;
+    return false;
+}
+// Derive the plane of rows [row0, row0 + m) from their codes; called wherever the shadow's rows are written.  The plane's arrays
+// have the shadow's capacity (q_rows >= n rows; pass 1 loads the rows below n only); a reallocated shadow has dropped
+// them (quant_free), and every row is derived again.  No memory: the index goes on without a plane.
+static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
+    if (!plane_possible(ix) || ix->plane_declined) return HDB_OK;
+    if (!ix->pnib && !plane_wanted(ix)) return HDB_OK;
+    if (!ix->pnib) {
+        // the automatic build's floor holds for every allocation of the plane (a shadow that grew on extend included): 1 GiB stays free
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->plane_declined = true; return HDB_OK; }
+        if (free_b < (size_t)ix->q_rows * plane_row_bytes(ix->qP) + ((size_t)1 << 30)) { ix->plane_declined = true; return HDB_OK; }
+        if (!plane_alloc(ix, ix->q_rows, &ix->pnib, &ix->pbit, &ix->prec)) { ix->plane_declined = true; return HDB_OK; }
+        ix->pU = hdb_quant_plane_units(ix->qP);
+        m = row0 + m; row0 = 0;
+    }
+    LAUNCH_TRY(hdb_launch_quant_plane_rows(ix->qcodes, ix->qaux, row0, m, ix->d, ix->qP, ix->pnib, ix->pbit, ix->prec, st));
+    return HDB_OK;
 }
 // room for `need` rows; the first `keep` rows of codes and caches survive a reallocation
 static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t st, bool tight = false) {
@@ -294,16 +354,16 @@ static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t 
     }
     HIP_TRY(hipStreamSynchronize(st));
     quant_free(ix);
-    ix->qcodes = c2; ix->qaux = a2; ix->q_rows = rows;
+    ix->qcodes = c2; ix->qaux = a2; ix->q_rows = rows;          // (quant_free dropped the plane: plane_rows derives all of it again)
     return HDB_OK;
 }
-// quantize rows [row0, row0 + m) of the current matrix into the shadow
+// quantize rows [row0, row0 + m) of the current matrix into the shadow, and derive their part of the plane
 static int quant_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
     if (m <= 0) return HDB_OK;
     const char* src = (const char*)ix->V + (size_t)row0 * ix->d * quant_elem(ix);
     LAUNCH_TRY(hdb_launch_quant_rows(src, m, ix->d, ix->dtype, ix->qP, ix->qcodes + (size_t)row0 * ix->qP, ix->qaux + (size_t)row0 * 3,
                                      ix->nan_flag, quant_gamma_rows(ix->d), st));
-    return HDB_OK;
+    return plane_rows(ix, row0, m, st);
 }
 
 extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
@@ -322,10 +382,11 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     if (ix->dtype == HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     if (!ix->qstat) {
-        HIP_TRY(hipMalloc((void**)&ix->qstat, sizeof(int)));
-        HIP_TRY(hipMemsetAsync(ix->qstat, 0, sizeof(int), st));
+        HIP_TRY(hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int)));
+        HIP_TRY(hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st));
     }
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
+    ix->plane_declined = false;
     int rc = quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st);
     if (rc) return rc;
     rc = quant_rows(ix, 0, ix->n, st);
@@ -339,6 +400,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
 // The automatic shadow (auto_quant): built on the first eligible call.  Memory guard: the shadow, n x (P + 12) bytes, must fit
 // the device's free memory beside the workspace the call is about to take and a floor of 1 GiB for everybody else (the caller's
 // own allocations, other indexes); a refusal or a failed allocation is remembered -- no error, no retry on every call.
+// The 5-bit plane is under the same guard: where the shadow fits and the plane beside it does not, the shadow is built alone.
 static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     if (ix->qauto_declined) return false;
     const int32_t P = (int32_t)align_up((size_t)ix->d, 16);
@@ -347,9 +409,11 @@ static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
     const size_t ws_grow = ws_need > ix->ws_bytes ? ws_need + (ws_need >> 2) + ((size_t)1 << 20) : 0;
     if (free_b < shadow + ws_grow + ((size_t)1 << 30)) { ix->qauto_declined = true; return false; }
+    const size_t plane = plane_possible(ix) ? (size_t)(ix->n + 64) * plane_row_bytes(P) : 0;
+    ix->plane_declined = plane_wanted(ix) && free_b < shadow + plane + ws_grow + ((size_t)1 << 30);
     if (!ix->qstat) {
-        if (hipMalloc((void**)&ix->qstat, sizeof(int)) != hipSuccess) { (void)hipGetLastError(); ix->qstat = nullptr; ix->qauto_declined = true; return false; }
-        (void)hipMemsetAsync(ix->qstat, 0, sizeof(int), st);
+        if (hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); ix->qstat = nullptr; ix->qauto_declined = true; return false; }
+        (void)hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st);
     }
     ix->qP = P;
     if (quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st, true) != HDB_OK || quant_rows(ix, 0, ix->n, st) != HDB_OK) {
@@ -390,6 +454,7 @@ extern "C" int hdb_index_update(hdb_index* ix, const void* dev_V, int64_t n, voi
     ix->V = dev_V; ix->n = n;
     ix->bias = nullptr; ix->mask = nullptr;
     ix->qauto_declined = false;                        // a new matrix: the memory question is asked again
+    ix->plane_declined = false;
     int rc = build_caches(ix, (hipStream_t)stream);
     if (rc == HDB_OK && ix->qmode == HDB_QUANT_I8) {          // a new matrix: the whole shadow is rebuilt
         rc = quant_reserve(ix, std::max<int64_t>(n, 1), 0, (hipStream_t)stream);
@@ -484,6 +549,10 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     if (ix->inv_norm) { (void)hipFree(ix->inv_norm); (void)hipFree(ix->sqnorm); }
     ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
     ix->V = dev_V_out; ix->n = m;
+    if (ix->qmode == HDB_QUANT_I8) {                   // the plane is derived again from the gathered codes
+        const int rcp = plane_rows(ix, 0, m, st);
+        if (rcp != HDB_OK) return rcp;
+    }
     ix->flags_host = -1;
     ix->bits_valid = false; ix->pscale_valid = false; ix->bits_done = 0; ix->pscale_done = 0;
     ix->bias = nullptr; ix->mask = nullptr;
@@ -578,6 +647,9 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "quant_batch_min_n")) ix->quant_batch_min_n = value;
     else if (!strcmp(name, "quant_batch_kernel")) ix->quant_batch_kernel = value ? 1 : 0;
     else if (!strcmp(name, "quant_max_k")) ix->quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
+    else if (!strcmp(name, "use_plane")) ix->use_plane = value;
+    else if (!strcmp(name, "plane_min_n")) ix->plane_min_n = value;
+    else if (!strcmp(name, "plane_cap_rows")) ix->plane_cap_rows = std::max<int64_t>(0, value);
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -599,6 +671,19 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "quant")) *value = ix->st_quant;
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
+    else if (!strcmp(name, "plane")) *value = ix->st_plane;
+    else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
+    else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
+        // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
+        // of this index so far whose survivor list overflowed (they scanned all rows in pass 2)
+        int h[HDB_QSTAT_WORDS] = {0, 0, 0, 0};
+        if (ix->qstat) {
+            HIP_TRY(hipSetDevice(ix->device));
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipMemcpy(h, ix->qstat, sizeof(h), hipMemcpyDeviceToHost));
+        }
+        *value = name[6] == 's' ? (ix->st_plane ? (int64_t)(uint32_t)h[1] : 0) : (int64_t)(uint32_t)h[2];
+    }
     else if (!strcmp(name, "quant_cands")) {          // synchronises the device
         int h = 0;
         if (ix->st_quant && ix->qstat) {
@@ -809,6 +894,14 @@ static int64_t quant_sample_tiles(int64_t n, int64_t target) {
     int64_t s_tiles = ((std::max<int64_t>((int64_t)(16.0 * (double)n / (double)target), 256)) + 15) / 16;
     return std::max<int64_t>(1, std::min(s_tiles, all_tiles));
 }
+// Smallest matrix whose one-query calls go through the 5-bit plane when plane_min_n is -1: the smallest measured size from which the
+// plane column of profiles/quant_plane_time.txt beats the plane-off column by at least 5 % in both runs, at that size and every
+// larger one (2M: 1.10x / 1.09x, 10M: 1.29x / 1.30x).  It is also the smallest size that has an automatic shadow.
+#define HDB_PLANE_MIN_ROWS 2000000
+// capacity of the survivor list in rows: an eighth of the matrix (the plane keeps under 5 % of Gaussian rows), or what the tests ask for
+static uint32_t plane_list_cap(const hdb_index* ix, int64_t n) {
+    return (uint32_t)(ix->plane_cap_rows > 0 ? std::min<int64_t>(ix->plane_cap_rows, n) : std::max<int64_t>(n / 8, 16));
+}
 static size_t quant_ws_need(const hdb_index* ix, int nq, int64_t n, bool mflavour) {
     const int P = (int)align_up((size_t)ix->d, 16);
     const int64_t s_tiles = quant_sample_tiles(n, quant_sample_target(ix, 1));       // (the largest sample any k takes)
@@ -817,6 +910,7 @@ static size_t quant_ws_need(const hdb_index* ix, int nq, int64_t n, bool mflavou
     need += align_up((size_t)nq * P, 256) + align_up((size_t)nq * HDB_QQ_WORDS * 4, 256);
     need += align_up((size_t)nq * 4 * HDB_CNT_STRIDE, 256) + 256;
     need += align_up((size_t)nq * HDB_CAND_CAP * 8, 256) + align_up((size_t)nq * ld_s * 4, 256);
+    if (nq == 1 && ix->pnib) need += align_up((size_t)plane_list_cap(ix, n) * 4, 256) + 256;     // survivor list of the plane pass
     if (mflavour) {
         const size_t crow = (size_t)nq * HDB_CAND_CAP;              // rows of the compact matrix
         need += align_up((size_t)nq * ix->d * 2, 256) + 256;        // fp16 queries, qscl
@@ -843,6 +937,11 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
     const int64_t s_rows = s_tiles * 16;
     const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    // (a shadow that was built without a plane -- use_plane was off then -- gets it on the first call that asks for the path)
+    const bool pl_call = nq == 1 && (metric == HDB_DOT || metric == HDB_COSINE) && plane_wanted(ix) &&
+                         n >= (ix->plane_min_n >= 0 ? ix->plane_min_n : (int64_t)HDB_PLANE_MIN_ROWS);
+    if (pl_call && !ix->pnib) { const int rcp = plane_rows(ix, 0, n, st); if (rcp) return rcp; }
+    const bool use_pl = pl_call && ix->pnib != nullptr;
     int rc = ensure_ws(ix, quant_ws_need(ix, nq, n, mflavour));
     if (rc) return rc;
     Bump b(ix->ws, ix->ws_bytes);
@@ -853,6 +952,10 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     uint32_t* cnt = b.take<uint32_t>((size_t)nq * HDB_CNT_STRIDE);
     unsigned long long* cand = b.take<unsigned long long>((size_t)nq * HDB_CAND_CAP);
     float* sbuf = b.take<float>((size_t)nq * ld_s);
+    // one dot / cosine query: pass 1 over the 5-bit plane, pass 2 (MODE 1 itself) over the rows it keeps (hdb_quant.hip)
+    const uint32_t pl_cap = plane_list_cap(ix, n);
+    uint32_t* pl_list = (nq == 1 && ix->pnib) ? b.take<uint32_t>(pl_cap) : nullptr;
+    uint32_t* pl_cnt = use_pl ? reinterpret_cast<uint32_t*>(ix->qstat) + 1 : nullptr;
     const size_t crow = (size_t)nq * HDB_CAND_CAP;
     uint32_t* wmax = nullptr; int nsub = 0;
     void* q16 = nullptr; float* qscl = nullptr; char* G = nullptr; float* ginv = nullptr; float* gbias = nullptr; float* gsc = nullptr;
@@ -865,11 +968,11 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
         nsub = 4 * hdb_quant_scan_blocks(s_tiles, (int)ix->max_blocks);
         if (nsub < 1024 || nsub > HDB_QUANT_NSUB_MAX) nsub = 0;
         LAUNCH_TRY(hdb_launch_quant_qprep_m((const float*)dev_Q, nq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, ix->qstat,
-                                            nsub ? cnt : nullptr, st));
+                                            nsub ? cnt : nullptr, pl_cnt, st));
     } else {
         // 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||)
         LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
-        LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, st));
+        LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, pl_cnt, st));
     }
     QuantArgs a; memset(&a, 0, sizeof(a));
     a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
@@ -882,7 +985,16 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
     a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
     prof_begin(ix, st);
-    LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->max_blocks, st));
+    if (use_pl) {
+        // pass 1 takes the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for pass 2 and the finalize
+        a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
+        a.pl_list = pl_list; a.pl_cnt = pl_cnt; a.pl_cap = pl_cap;
+        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->max_blocks, st));
+        a.nsub = 0; a.wmax = nullptr;
+        LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 1, (int)ix->max_blocks, st));
+    } else {
+        LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->max_blocks, st));
+    }
     prof_end(ix, st);
     if (mflavour) {
         const bool has_bias = ix->bias != nullptr || ix->mask != nullptr;
@@ -901,7 +1013,43 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, qnan,
                                          qaux, thr, ix->qstat, mflavour ? cand : nullptr, gsc, (int64_t)crow, st));
     ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = mflavour ? 1 : 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
+    ix->st_plane = use_pl ? 1 : 0;
     ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
+    return HDB_OK;
+}
+
+// Test entry: the upper bound of every row for ONE float32 query, as the MODE 1 pass computes it (dev_hi[n]) and as pass 1 over the
+// 5-bit plane computes it (dev_hi5[n]); masked rows give -inf in both.  The index needs a shadow with its plane.
+extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int metric, float* dev_hi, float* dev_hi5, void* stream) {
+    if (!ix || !dev_q || !dev_hi || !dev_hi5) return fail(HDB_ERR_ARG, "hdb_debug_quant_bounds: null argument");
+    if (metric != HDB_DOT && metric != HDB_COSINE) return fail(HDB_ERR_ARG, "hdb_debug_quant_bounds: dot or cosine");
+    if (ix->qmode != HDB_QUANT_I8 || !ix->pnib || ix->n < 1) return fail(HDB_ERR_UNSUPPORTED, "hdb_debug_quant_bounds: the index has no 5-bit plane");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int P = ix->qP;
+    int rc = ensure_ws(ix, quant_ws_need(ix, 1, ix->n, true));
+    if (rc) return rc;
+    Bump b(ix->ws, ix->ws_bytes);
+    float* qinv = b.take<float>(1); float* qsq = b.take<float>(1); int* qnan = b.take<int>(1);
+    int8_t* qcodes = b.take<int8_t>((size_t)P);
+    float* qaux = b.take<float>(HDB_QQ_WORDS);
+    void* q16 = b.take<uint16_t>((size_t)ix->d); float* qscl = b.take<float>(1);
+    if (ix->qauto) {
+        LAUNCH_TRY(hdb_launch_quant_qprep_m(dev_q, 1, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, nullptr, nullptr, nullptr, st));
+    } else {
+        LAUNCH_TRY(hdb_launch_qprep(dev_q, 1, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
+        LAUNCH_TRY(hdb_launch_quant_qprep(dev_q, 1, ix->d, P, qcodes, qaux, nullptr, nullptr, st));
+    }
+    QuantArgs a; memset(&a, 0, sizeof(a));
+    a.codes = ix->qcodes; a.n = ix->n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
+    a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = 1;
+    a.gamma = (float)quant_gamma(ix->d);
+    a.ntiles = (ix->n + 15) / 16; a.tile_stride = 1;
+    a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
+    a.dbg = dev_hi;
+    LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 2, (int)ix->max_blocks, st));
+    a.dbg = dev_hi5;
+    LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 1, (int)ix->max_blocks, st));
     return HDB_OK;
 }
 
@@ -979,7 +1127,7 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
         ix->st_chunks++;
         const float* Qc = (const float*)dev_Q + (size_t)q0 * ix->d;
         // (the stat word is reset by the first chunk only: quant_cands is the largest list of the CALL)
-        LAUNCH_TRY(hdb_launch_quant_qprep_m(Qc, cq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, q0 == 0 ? ix->qstat : nullptr, cnt, st));
+        LAUNCH_TRY(hdb_launch_quant_qprep_m(Qc, cq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, q0 == 0 ? ix->qstat : nullptr, cnt, nullptr, st));
         QuantArgs a; memset(&a, 0, sizeof(a));
         a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
         a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = cq;
@@ -1031,7 +1179,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (metric == HDB_PEARSON && ix->d < 1) return fail(HDB_ERR_ARG, "hdb_topk: pearson needs d >= 1");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    ix->st_quant = 0; ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    ix->st_quant = 0; ix->st_plane = 0; ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
     const bool f64 = ix->dtype == HDB_F64;
     const int64_t n = ix->n;
     const uint32_t kk = (uint32_t)std::min<int64_t>(k, n);

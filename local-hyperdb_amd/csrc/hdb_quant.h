@@ -12,6 +12,8 @@
 #define HDB_QQ_D 2        // ||delta_q||_2, rounded up
 #define HDB_QQ_SQ 3       // ||q||^2 (float64 sum rounded to nearest)
 #define HDB_QQ_BAD 4      // non-zero: the query is not finite (the call leaves it to the exact re-run)
+#define HDB_QQ_CN 5       // ||c_q||_2, rounded up (the 5-bit plane's residual bound)
+#define HDB_QQ_CS 6       // sum_j c_qj (an integer, exact in float32)
 #define HDB_QQ_WORDS 8
 
 struct QuantArgs {
@@ -40,5 +42,12 @@ struct QuantArgs {
     // it unless two of the top 16 fell to one wave: hdb_sample_thr_kernel's argument with 4x the subsets) and workgroup 0 stores it
     // to thr_out for the finalize.  No launch in between, nothing to wait for.
     uint32_t* wmax; int32_t nsub; float* thr_out;
+    // The 5-bit plane (hdb_quant.hip, "The 5-bit plane"): pass 1 (hdb_quant_plane_scan_kernel) streams the plane and appends the rows
+    // whose coarse upper bound reaches T_s to pl_list (pl_cap entries; pl_cnt[0] counts past the capacity, those writes are dropped);
+    // the LIST flavour of MODE 1 then visits those rows only -- or all rows when the counter passed the capacity (pl_cnt[1] counts
+    // such calls).  dbg: test-only output of one upper bound per row (hdb_debug_quant_bounds).
+    const uint8_t* pl_nib; const uint32_t* pl_bit; const float* pl_rec; int32_t pl_units;
+    uint32_t* pl_list; uint32_t* pl_cnt; uint32_t pl_cap;
+    float* dbg;
 };
 #define HDB_QUANT_NSUB_MAX 4096      // (MODE 1 holds nsub / 256 keys per thread)

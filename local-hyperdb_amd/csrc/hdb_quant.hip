@@ -64,6 +64,32 @@
 // best rescored candidate scores ABOVE T_s (hdb_finalize_fast's floor); then every row missing from the list scores strictly
 // below the kk-th best, so the top kk, ties at the kk-th score included, are all in the list.  If the check fails (HDB_Q_UNDERFLOW)
 // or the list overflowed (HDB_Q_OVERFLOW) the status word says so and hdb_topk_host re-runs that query through the exact path.
+//
+// ---- The 5-bit plane (one dot / cosine query; hdb_quant_plane_scan_kernel) -----------------------------------------------------
+// The MODE 1 pass rejects all but a few thousand rows at full int8 resolution.  Beside the codes the index keeps their high five
+// bits: for a code c in [-127, 127], h = c >> 3 (arithmetic), u = h + 16 in [0, 31], rho = c - (8h + 4) in [-4, 3].  Per row, in
+// units of 32 elements (U = ceil(P / 32) units): a 16-byte piece of nibbles u >> 1 (byte b of word i = elements 8i + b | 8i + 4 + b
+// << 4, so w & 0x0F0F0F0F and (w >> 4) & 0x0F0F0F0F pair with consecutive query-code words), one word of bits u & 1 (element
+// 4g + b at bit 8b + g, so (w >> g) & 0x01010101 pairs with query word g), both as arrays of their own (a 16-row tile is
+// contiguous), and one record {s_r, E_r, T_r, R_r}, R_r = ||rho_r||_2 over j < d rounded up (an integer sum of at most 16 d).
+// The bound.  c = 8u - 124 + rho, so with C5 = sum_j c_qj (8 u_rj - 124) = 8 sum_j c_qj u_rj - 124 sum_j c_qj (exact in int32)
+//     |C - C5| = |sum_j c_qj rho_rj| <= ||c_q|| ||rho_r|| <= N_c R_r =: U                                            (4)
+// (Cauchy-Schwarz on integers; the query prep leaves N_c = ||c_q|| rounded up and sum_j c_qj in qaux).  In float32:
+//     ch = fl(fl(C5) + fl(N_c R_r)) + (|.| 2^-20 + 1) >= C5 + U >= C, and ch is a float, so ch >= fl(C);  cl likewise <= fl(C)
+// (fl(C5) errs by 2^-24 |C5|, the product and the sum by 2^-24 (|C5| + 2U), U <= 508 d: the absolute 1 covers what the relative term
+// does not).  MODE 1 forms A = fl(k fl(C)), k = fl(s_q s_r) >= 0: two multiplies, nothing to contract, monotone in fl(C).  So
+// A5 = fl(k ch) >= A >= Al = fl(k cl), and |A| <= Amax = max(|A5|, |Al|).  The raw upper bound of (3) is, in real numbers,
+// g(A) = A + c0 + |A| 2^-10 + absmin with c0 = (N_q E_r + D_q T_r)(1 + 2^-10): non-decreasing in A.  ANY float32 evaluation F(A) of it
+// (whatever the compiler contracts) errs by at most 8u (|A| + B(A)) <= 8u Mx, Mx = Amax + Bmax, Bmax = B at |A| = Amax.  Hence
+//     X = F5(A5) + Mx 2^-18 >= g(A5) - 8u Mx + 64u Mx - (own roundings, < 4u Mx) >= g(A) + 8u Mx >= F(A).
+// The cosine scalings are two multiplies by positive numbers in both kernels: y5 = m(X) >= m(F(A)) = y8, and both magnitudes are at
+// most mM = m(Mx (1 + 2^-17)).  The bias add may be contracted into the last multiply in either kernel: each side errs by at most
+// 2u (|y| + |bias|) <= 2u Z, Z = mM + |bias|; MODE 1 then pushes its value by |hi| 2^-20 + 1e-30 <= Z 2^-20 (1 + 4u) + 1e-30.  With
+//     hi5 = fl(y5 + bias) + Z 2^-18 + 4e-30
+// the sum of all of that (< Z 2^-20 x 1.5 + 1e-30) is covered: hi5 >= hi for every row, hi as MODE 1 computes it.  A row pass 1
+// drops (hi5 < T_s; a NaN never drops) would have been dropped by MODE 1: the candidate set, and every later stage, is unchanged.
+// Z 2^-18 is relative to magnitudes that do not cancel, at most 2^-8 of the bound's own width B: pass 1 loses nothing by it.
+// Pass 2 is MODE 1 itself (LIST flavour) over the survivor list; when the list overflowed it scans all rows densely instead.
 #include "hdb_common.h"
 #include "hdb_quant.h"
 #include "hdb_finalize.h"
@@ -169,10 +195,12 @@ __global__ __launch_bounds__(256) void hdb_quant_gather_kernel(const int8_t* cod
 
 // Quantized query prep: one wave per query (float32 queries).  qcodes[q][0..P), qaux[q] = {s_q, N_q, D_q, ||q||^2, bad}.
 // Word 0 of `stat` (the largest candidate count of the call) is reset here, ahead of the finalize that raises it.
-__global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat) {
+__global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat,
+                                                             uint32_t* pl_cnt) {
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= nq) return;
     if (q == 0 && lane == 0 && stat) stat[0] = 0;
+    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // an empty survivor list (5-bit plane)
     const float* qr = Q + (int64_t)q * d;
     float amax = 0.f;
     bool bad = false;
@@ -186,6 +214,7 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
     bad = __ballot(bad) != 0ull;
     const float s = bad ? 0.f : amax / 127.f;
     double nn = 0.0, dd = 0.0;
+    int cs = 0, c2 = 0;                                     // sum c, sum c^2 (exact: at most 127^2 d < 2^31)
     for (int e = lane; e < P; e += 64) {
         int c = 0;
         if (e < d && !bad) {
@@ -196,9 +225,13 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
             dd += del * del;
         }
         qcodes[(int64_t)q * P + e] = (int8_t)c;
+        cs += c; c2 += c * c;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64); }
+    for (int o = 32; o > 0; o >>= 1) {
+        nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64);
+        cs += __shfl_xor(cs, o, 64); c2 += __shfl_xor(c2, o, 64);
+    }
     if (lane == 0) {
         float* o = qaux + (int64_t)q * HDB_QQ_WORDS;
         const float sq = (float)nn;
@@ -208,7 +241,9 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
         o[HDB_QQ_D] = bad ? 0.f : hq_up(sqrt(dd));
         o[HDB_QQ_SQ] = sq;
         o[HDB_QQ_BAD] = (bad || big) ? 1.f : 0.f;
-        o[5] = 0.f; o[6] = 0.f; o[7] = 0.f;
+        o[HDB_QQ_CN] = hq_up(sqrt((double)c2));
+        o[HDB_QQ_CS] = (float)cs;                           // |sum| <= 127 d < 2^24: exact
+        o[7] = 0.f;
     }
 }
 
@@ -217,10 +252,11 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
 // bits), the scaled fp16 copy q16 / qscl the matrix cores multiply with, and codes / norms of the ROUNDED query q' = q16 * qscl.
 __global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan,
                                                                _Float16* q16, float* qscl, int8_t* qcodes, float* qaux, int* stat,
-                                                               uint32_t* cnt_init) {
+                                                               uint32_t* cnt_init, uint32_t* pl_cnt) {
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= nq) return;
     if (q == 0 && lane == 0 && stat) stat[0] = 0;
+    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // an empty survivor list (5-bit plane)
     if (lane == 0 && cnt_init) cnt_init[q * HDB_CNT_STRIDE] = 0u;     // an empty candidate list (the folded threshold has no kernel that would do it)
     const float* qr = Q + (int64_t)q * d;
     float s = 0.f, amax = 0.f;
@@ -248,6 +284,7 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, i
     bad = __ballot(bad) != 0ull;
     const float sq_ = bad ? 0.f : amax2 / 127.f;
     double nn = 0.0, dd = 0.0;
+    int cs = 0, c2 = 0;                                     // sum c, sum c^2 (exact: at most 127^2 d < 2^31)
     for (int e = lane; e < P; e += 64) {
         int c = 0;
         if (e < d && !bad) {
@@ -258,9 +295,13 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, i
             dd += del * del;
         }
         qcodes[(int64_t)q * P + e] = (int8_t)c;
+        cs += c; c2 += c * c;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64); }
+    for (int o = 32; o > 0; o >>= 1) {
+        nn += __shfl_xor(nn, o, 64); dd += __shfl_xor(dd, o, 64);
+        cs += __shfl_xor(cs, o, 64); c2 += __shfl_xor(c2, o, 64);
+    }
     if (lane == 0) {
         const float ss = s;
         qsq[q] = ss;
@@ -275,7 +316,9 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, i
         o[HDB_QQ_D] = bad ? 0.f : hq_up(sqrt(dd));
         o[HDB_QQ_SQ] = sq;
         o[HDB_QQ_BAD] = (bad || big) ? 1.f : 0.f;
-        o[5] = 0.f; o[6] = 0.f; o[7] = 0.f;
+        o[HDB_QQ_CN] = hq_up(sqrt((double)c2));
+        o[HDB_QQ_CS] = (float)cs;                           // |sum| <= 127 d < 2^24: exact
+        o[7] = 0.f;
     }
 }
 
@@ -312,12 +355,72 @@ __device__ __forceinline__ int hq_rows4_sum(int a0, int a1, int a2, int a3, int 
     return w;
 }
 
-template <int MODE, int NQ, int NJ>
+// The threshold folded into the passes (QuantArgs::nsub > 0), every thread of a 256-thread workgroup calls it:
+template <int NQ>
+__device__ __forceinline__ void hq_fold_thr(const QuantArgs& a, float (&q_thr)[NQ]) {
+    // T_s = 16th largest of the per-wave maxima of the sample pass: every wave extracts the 16 largest of its quarter, wave 0
+    // the 16 largest of those 64 (hdb_sample_thr_kernel's scheme; exact for the nsub keys)
+    __shared__ uint32_t s_top[4 * 16];
+    __shared__ float s_thr[NQ];
+    const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int q = 0; q < NQ; ++q) {
+        uint32_t c[HDB_QUANT_NSUB_MAX / 256];
+#pragma unroll
+        for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) {
+            const int e = (int)threadIdx.x + 256 * j;
+            c[j] = e < a.nsub ? a.wmax[(int64_t)q * a.nsub + e] : 0u;
+        }
+        for (int r = 0; r < 16; ++r) {
+            uint32_t lm = 0u;
+#pragma unroll
+            for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) lm = max(lm, c[j]);
+            uint32_t wm = lm;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+            const unsigned long long who = __ballot(lm == wm);
+            if (ln == (int)__ffsll((long long)who) - 1) {
+                bool gone = false;
+#pragma unroll
+                for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j)
+                    if (!gone && c[j] == wm) { c[j] = 0u; gone = true; }
+            }
+            if (ln == 0) s_top[wv * 16 + r] = wm;
+        }
+        __syncthreads();
+        if (wv == 0) {
+            uint32_t v = s_top[ln];
+            uint32_t kth = 0u;
+            for (int r = 0; r < 16; ++r) {
+                uint32_t wm = v;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+                const unsigned long long who = __ballot(v == wm);
+                if (ln == (int)__ffsll((long long)who) - 1) v = 0u;
+                kth = wm;
+            }
+            if (ln == 0) {
+                const float t = kth == 0u ? -INFINITY : hdb_key2f(kth);
+                s_thr[q] = t;
+                if (blockIdx.x == 0) a.thr_out[q] = t;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) q_thr[q] = s_thr[q];
+}
+
+// MODE 2 (tests): MODE 1's upper bound of every row -> dbg[row], nothing emitted.
+// LIST (MODE 1, one query; pass 2 behind the 5-bit plane): a tile's 16 rows are 16 consecutive entries of the survivor list, the tile
+// count comes from the device counter (fixed grid, no host sync); a counter past the list's capacity means entries were dropped,
+// and the launch scans all rows densely instead.
+template <int MODE, int NQ, int NJ, bool LIST = false>
 __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int4* qs = reinterpret_cast<int4*>(smem);                       // [NQ][nch]
     __shared__ HqStage stage;
     const int nch = a.P >> 4;
+    static_assert(!LIST || (MODE == 1 && NQ == 1), "the list flavour is pass 2 of a one-query call");
     if (MODE == 1 && threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
     for (int i = threadIdx.x; i < NQ * nch; i += 256) qs[i] = reinterpret_cast<const int4*>(a.qcodes)[i];
     float q_s[NQ], q_n[NQ], q_d[NQ], q_sq[NQ], q_inv[NQ], q_thr[NQ];
@@ -330,58 +433,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
         q_thr[q] = (MODE == 1 && a.nsub == 0) ? a.thr[q] : 0.f;
     }
     __syncthreads();
-    if (MODE == 1 && a.nsub > 0) {
-        // T_s = 16th largest of the per-wave maxima of the sample pass: every wave extracts the 16 largest of its quarter, wave 0
-        // the 16 largest of those 64 (hdb_sample_thr_kernel's scheme; exact for the nsub keys)
-        __shared__ uint32_t s_top[4 * 16];
-        __shared__ float s_thr[NQ];
-        const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        for (int q = 0; q < NQ; ++q) {
-            uint32_t c[HDB_QUANT_NSUB_MAX / 256];
-#pragma unroll
-            for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) {
-                const int e = (int)threadIdx.x + 256 * j;
-                c[j] = e < a.nsub ? a.wmax[(int64_t)q * a.nsub + e] : 0u;
-            }
-            for (int r = 0; r < 16; ++r) {
-                uint32_t lm = 0u;
-#pragma unroll
-                for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) lm = max(lm, c[j]);
-                uint32_t wm = lm;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
-                const unsigned long long who = __ballot(lm == wm);
-                if (ln == (int)__ffsll((long long)who) - 1) {
-                    bool gone = false;
-#pragma unroll
-                    for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j)
-                        if (!gone && c[j] == wm) { c[j] = 0u; gone = true; }
-                }
-                if (ln == 0) s_top[wv * 16 + r] = wm;
-            }
-            __syncthreads();
-            if (wv == 0) {
-                uint32_t v = s_top[ln];
-                uint32_t kth = 0u;
-                for (int r = 0; r < 16; ++r) {
-                    uint32_t wm = v;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
-                    const unsigned long long who = __ballot(v == wm);
-                    if (ln == (int)__ffsll((long long)who) - 1) v = 0u;
-                    kth = wm;
-                }
-                if (ln == 0) {
-                    const float t = kth == 0u ? -INFINITY : hdb_key2f(kth);
-                    s_thr[q] = t;
-                    if (blockIdx.x == 0) a.thr_out[q] = t;
-                }
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) q_thr[q] = s_thr[q];
-    }
+    if (MODE == 1 && a.nsub > 0) hq_fold_thr<NQ>(a, q_thr);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, l16 = lane & 15;
@@ -394,11 +446,26 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) wbest[q] = 0u;
 
-    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < a.ntiles; t += (int64_t)gridDim.x * 4) {
+    int64_t ntiles = a.ntiles;
+    uint32_t pl_n = 0u;
+    bool pl_list = false;
+    if (LIST) {
+        pl_n = a.pl_cnt[0];
+        pl_list = pl_n <= a.pl_cap;
+        if (pl_list) ntiles = ((int64_t)pl_n + 15) >> 4;
+        else if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.pl_cnt[1], 1u);      // (stat plane_overflows)
+    }
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
         const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
+        int64_t rr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            rr[u] = r0 + u;
+            if (LIST && pl_list) rr[u] = (uint64_t)(r0 + u) < (uint64_t)pl_n ? (int64_t)a.pl_list[r0 + u] : a.n;      // (a.n: no row)
+        }
         const int8_t* p[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = a.codes + min(r0 + u, a.n - 1) * (int64_t)a.P;
+        for (int u = 0; u < 4; ++u) p[u] = a.codes + min(rr[u], a.n - 1) * (int64_t)a.P;
         int acc[4][NQ];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -441,7 +508,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
             }
         }
         const int u_own = hdb_owned_row(l16);
-        const int64_t row = r0 + u_own;
+        const int64_t row = LIST ? (u_own == 0 ? rr[0] : u_own == 1 ? rr[1] : u_own == 2 ? rr[2] : rr[3]) : r0 + u_own;
         int C[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) C[q] = hq_rows4_sum(acc[0][q], acc[1][q], acc[2][q], acc[3][q], l16);
@@ -482,7 +549,9 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
                 if (lo != lo) lo = -INFINITY;
                 if (hi != hi) hi = INFINITY;
             }
-            if (MODE == 0) {
+            if (MODE == 2) {
+                a.dbg[row] = hi;
+            } else if (MODE == 0) {
                 if (a.nsub > 0) wbest[q] = max(wbest[q], hdb_f2key(lo));
                 else a.scores[(int64_t)q * a.ld + out_i] = lo;
             } else if (!masked && !q_bad[q] && hi >= q_thr[q]) {
@@ -516,6 +585,204 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
             for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
                 if (base + e < a.cap) a.cand[(int64_t)q * a.cap + base + e] = stage.buf[q][e];
             __syncthreads();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The 5-bit plane.  Derivation from the codes of rows [row0, row0 + m): 16 lanes per row, lane l16 packs unit l16 (32 elements:
+// one 16-byte piece of nibbles, one word of bits), the group sums the squared residuals of the elements below d.
+// ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P,
+                                                                   int U, uint8_t* nib, uint32_t* bitw, float* rec) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
+    for (int64_t base = wave * 4; base < m; base += nwaves * 4) {            // (wave-uniform)
+        const int64_t r = row0 + base + g;
+        const bool valid = base + g < m;
+        int ss = 0;
+        if (valid && l16 < U) {
+            const int8_t* src = codes + r * (int64_t)P + 32 * l16;
+            uint4 raw[2];
+            raw[0] = *reinterpret_cast<const uint4*>(src);
+            raw[1] = (32 * l16 + 16 < P) ? *reinterpret_cast<const uint4*>(src + 16) : make_uint4(0u, 0u, 0u, 0u);
+            const uint32_t* cw = reinterpret_cast<const uint32_t*>(raw);      // query-aligned words: word w holds elements 4w .. 4w + 3
+            uint32_t nw[4] = {0u, 0u, 0u, 0u}, bw = 0u;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int c = (int)(int8_t)((cw[w] >> (8 * b)) & 0xFFu);
+                    const int h = c >> 3;
+                    const uint32_t u5 = (uint32_t)(h + 16);
+                    const int rho = c - (8 * h + 4);
+                    if (32 * l16 + 4 * w + b < d) ss += rho * rho;
+                    nw[w >> 1] |= (u5 >> 1) << (8 * b + 4 * (w & 1));
+                    bw |= (u5 & 1u) << (8 * b + w);
+                }
+            }
+            *reinterpret_cast<uint4*>(nib + (r * (int64_t)U + l16) * 16) = make_uint4(nw[0], nw[1], nw[2], nw[3]);
+            bitw[r * (int64_t)U + l16] = bw;
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+        if (valid && l16 == 0) {
+            const float R = sqrtf((float)ss) * (1.f + 0x1p-20f);             // ss <= 16 d is exact; sqrtf errs by half an ulp
+            *reinterpret_cast<float4*>(rec + 4 * r) = make_float4(aux[3 * r + HDB_QROW_S], aux[3 * r + HDB_QROW_E], aux[3 * r + HDB_QROW_T], R);
+        }
+    }
+}
+
+// Pass 1: the coarse upper bound hi5 (header, "The 5-bit plane") of every row; rows with hi5 >= T_s go to the survivor list.
+// A wave takes two 16-row tiles per step.  A tile of the nibble plane is 16 U contiguous 16-byte pieces and lane l takes pieces
+// l + 64 j, j < J = ceil(U / 4), i.e. whole-wave contiguous loads with every lane busy (U = 12 at d = 384: exactly 3 per lane); piece
+// f belongs to row f / U, unit f % U -- the same for every tile, so a lane keeps the query words of its J units in registers.
+// The per-piece sums meet in LDS (wave-private), lanes 0-31 add the U pieces of one row each and evaluate the bound.
+#define HQ_PL_STAGE 1024
+template <int J, bool DBG>
+__global__ __launch_bounds__(256) void hdb_quant_plane_scan_kernel(QuantArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int4* qs = reinterpret_cast<int4*>(smem);                       // [2 U] query codes, zero past P
+    __shared__ int part[4][2][64 * J];
+    __shared__ uint32_t st_buf[HQ_PL_STAGE];
+    __shared__ uint32_t st_cnt, st_base;
+    const int U = a.pl_units, nch = a.P >> 4;
+    if (threadIdx.x == 0) st_cnt = 0u;
+    for (int i = threadIdx.x; i < 2 * U; i += 256) qs[i] = i < nch ? reinterpret_cast<const int4*>(a.qcodes)[i] : make_int4(0, 0, 0, 0);
+    const float* qo = a.qaux;
+    const float q_s = qo[HDB_QQ_S], q_n = qo[HDB_QQ_N], q_d = qo[HDB_QQ_D], q_cn = qo[HDB_QQ_CN];
+    const int q_cs = (int)qo[HDB_QQ_CS];
+    const bool q_bad = qo[HDB_QQ_BAD] != 0.f;
+    const bool cosine = a.metric == HDB_COSINE;
+    const float q_inv = cosine ? a.qinv[0] : 1.f;
+    float thr1[1] = {(!DBG && a.nsub == 0) ? a.thr[0] : 0.f};
+    __syncthreads();
+    if (!DBG && a.nsub > 0) hq_fold_thr<1>(a, thr1);
+    const float q_thr = thr1[0];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int npieces = 16 * U;
+    int qw[J][8];
+    int prow[J];                                                    // row of piece j within its tile (16: no such piece)
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int f = lane + 64 * j;
+        const int unit = f < npieces ? f % U : 0;
+        prow[j] = f < npieces ? f / U : 16;
+        const int4 x = qs[2 * unit], y = qs[2 * unit + 1];
+        qw[j][0] = x.x; qw[j][1] = x.y; qw[j][2] = x.z; qw[j][3] = x.w;
+        qw[j][4] = y.x; qw[j][5] = y.y; qw[j][6] = y.z; qw[j][7] = y.w;
+    }
+    const float absmin = 0x1p-100f * (float)(a.d + 8);
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const int64_t ntiles = a.ntiles;
+    const int et = lane >> 4, er = lane & 15;                       // epilogue lanes 0-31: tile et of the pair, row er
+
+    for (int64_t t = ((int64_t)blockIdx.x * 4 + wave) * 2; t < ntiles; t += (int64_t)gridDim.x * 8) {
+        u32x4 nv[2][J];
+        uint32_t bv[2][J];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const int64_t rows_left = a.n - (t + tt) * 16;          // (<= 0 past the last tile; the ragged tile loads its own rows only)
+            const uint8_t* nb = a.pl_nib + (t + tt) * (int64_t)npieces * 16;
+            const uint32_t* bb = a.pl_bit + (t + tt) * (int64_t)npieces;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const int f = lane + 64 * j;
+                if ((int64_t)prow[j] < rows_left && prow[j] < 16) {
+                    nv[tt][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(nb + (int64_t)f * 16));
+                    bv[tt][j] = __builtin_nontemporal_load(bb + f);
+                } else {
+                    nv[tt][j] = u32x4{0u, 0u, 0u, 0u};
+                    bv[tt][j] = 0u;
+                }
+            }
+        }
+        // the row terms of the epilogue lanes, issued with the plane loads
+        const int64_t row = (t + et) * 16 + er;
+        const bool rvalid = lane < 32 && t + et < ntiles && row < a.n;
+        f32x4 rc = f32x4{0.f, 0.f, 0.f, 0.f};
+        float invn = 1.f, bias = 0.f;
+        bool masked = false;
+        if (rvalid) {
+            rc = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.pl_rec) + row);
+            if (cosine) invn = a.inv_norm[row];
+            if (a.bias) bias = a.bias[row];
+            if (a.mask) masked = !a.mask[row];
+        }
+        __builtin_amdgcn_sched_barrier(0);               // loads ahead of every use
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const uint32_t bw = bv[tt][j];
+                const uint32_t w4[4] = {nv[tt][j].x, nv[tt][j].y, nv[tt][j].z, nv[tt][j].w};
+                int s = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t lo = ((w4[i] << 1) & 0x1E1E1E1Eu) | ((bw >> (2 * i)) & 0x01010101u);
+                    const uint32_t hi = ((w4[i] >> 3) & 0x1E1E1E1Eu) | ((bw >> (2 * i + 1)) & 0x01010101u);
+                    s = __builtin_amdgcn_sdot4((int)lo, qw[j][2 * i], s, false);
+                    s = __builtin_amdgcn_sdot4((int)hi, qw[j][2 * i + 1], s, false);
+                }
+                part[wave][tt][lane + 64 * j] = s;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        int S = 0;
+        if (lane < 32)
+            for (int i = 0; i < U; ++i) S += part[wave][et][er * U + i];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();                 // (the next step's stores stay behind these loads)
+        if (!rvalid) continue;
+        float hi5 = -INFINITY;
+        const bool dead = masked || q_bad;
+        if (!dead) {
+            const float fc = (float)(8 * S - 124 * q_cs);
+            const float Uf = q_cn * rc.w;
+            float ch = fc + Uf, cl = fc - Uf;
+            ch = ch + (fabsf(ch) * 0x1p-20f + 1.f);
+            cl = cl - (fabsf(cl) * 0x1p-20f + 1.f);
+            const float k = q_s * rc.x;
+            const float A5 = k * ch, Al = k * cl;
+            const float Amax = fmaxf(fabsf(A5), fabsf(Al));
+            const float c0 = (q_n * rc.y + q_d * rc.z) * (1.f + 0x1p-10f);
+            const float B5 = c0 + fabsf(A5) * 0x1p-10f + absmin;
+            const float Bmax = c0 + Amax * 0x1p-10f + absmin;
+            const float Mx = Amax + Bmax;
+            float X = (A5 + B5) + (Mx * 0x1p-18f + 1e-30f);
+            float mM = Mx * (1.f + 0x1p-17f);
+            if (cosine) { X = X * invn * q_inv; mM = mM * invn * q_inv; }
+            const float Z = mM + fabsf(bias);
+            float h = X;
+            if (a.bias) h += bias;
+            hi5 = h + (Z * 0x1p-18f + 4e-30f);
+            if (hi5 != hi5) hi5 = INFINITY;
+        }
+        if (DBG) {
+            a.dbg[row] = hi5;
+        } else if (!dead && !(hi5 < q_thr)) {
+            const unsigned int lp = atomicAdd(&st_cnt, 1u);                              // LDS
+            if (lp < HQ_PL_STAGE) st_buf[lp] = (uint32_t)row;
+            else {
+                const uint32_t pos = atomicAdd(&a.pl_cnt[0], 1u);                        // the stage is full: straight to the list
+                if (pos < a.pl_cap) a.pl_list[pos] = (uint32_t)row;
+            }
+        }
+    }
+    if (!DBG) {                                          // one atomic per block
+        __syncthreads();
+        const unsigned int have = min(st_cnt, (unsigned int)HQ_PL_STAGE);
+        if (have != 0u) {
+            if (threadIdx.x == 0) st_base = atomicAdd(&a.pl_cnt[0], have);
+            __syncthreads();
+            const unsigned int base = st_base;
+            for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
+                if (base + e < a.pl_cap) a.pl_list[base + e] = st_buf[e];
         }
     }
 }
@@ -670,15 +937,16 @@ extern "C" int hdb_launch_quant_gather(const int8_t* codes, const float* aux, co
     return (int)hipGetLastError();
 }
 
-extern "C" int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, void* stream) {
-    hipLaunchKernelGGL(hdb_quant_qprep_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, nq, d, P, qcodes, qaux, stat);
+extern "C" int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt,
+                                      void* stream) {
+    hipLaunchKernelGGL(hdb_quant_qprep_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, nq, d, P, qcodes, qaux, stat, pl_cnt);
     return (int)hipGetLastError();
 }
 
 extern "C" int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
-                                        int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, void* stream) {
+                                        int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream) {
     hipLaunchKernelGGL(hdb_quant_qprep_m_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, nq, d, P, qinv, qsq, qnan, (_Float16*)q16,
-                       qscl, qcodes, qaux, stat, cnt_init);
+                       qscl, qcodes, qaux, stat, cnt_init, pl_cnt);
     return (int)hipGetLastError();
 }
 
@@ -720,6 +988,49 @@ extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_bl
     if (a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || (mode == 0 ? a.nsub != 4 * blocks : !a.thr_out))) return (int)hipErrorInvalidValue;
     if (mode == 0) hq_launch_scan_mode<0>(a, blocks, lds, (hipStream_t)stream);
     else hq_launch_scan_mode<1>(a, blocks, lds, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+// The 5-bit plane: units of a row, bytes per row, derivation, pass 1 and pass 2 (one query; dot / cosine).
+extern "C" int hdb_quant_plane_units(int P) { return (P + 31) / 32; }
+extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib,
+                                           uint32_t* bitw, float* rec, void* stream) {
+    if (m <= 0) return 0;
+    const int U = hdb_quant_plane_units(P);
+    if (U > 16 || (P & 15) != 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(hdb_quant_plane_rows_kernel, dim3(hdb_grid_for(m, 16, 8192)), dim3(256), 0, (hipStream_t)stream, codes, aux, row0, m, d,
+                       P, U, nib, bitw, rec);
+    return (int)hipGetLastError();
+}
+// dbg = false: pass 1 (survivor list); dbg = true: hi5 of every row -> a.dbg (tests)
+extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream) {
+    const QuantArgs& a = *args;
+    const int U = a.pl_units;
+    if (a.nq != 1 || U < 1 || U > 16 || U != hdb_quant_plane_units(a.P) || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
+    if (!dbg && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)U * 32;
+    const int blocks = hdb_grid_for((a.ntiles + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024);
+    hipStream_t st = (hipStream_t)stream;
+    const int J = (U + 3) / 4;
+#define HQ_PLANE(J_) do { if (dbg) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, true>), dim3(blocks), dim3(256), lds, st, a); \
+                          else hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, false>), dim3(blocks), dim3(256), lds, st, a); } while (0)
+    if (J == 1) HQ_PLANE(1); else if (J == 2) HQ_PLANE(2); else if (J == 3) HQ_PLANE(3); else HQ_PLANE(4);
+#undef HQ_PLANE
+    return (int)hipGetLastError();
+}
+// mode 1: pass 2 (MODE 1 over the survivor list, a.ntiles = the dense tile count for the overflow case); mode 2: MODE 1's upper
+// bound of every row -> a.dbg (tests)
+extern "C" int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream) {
+    const QuantArgs& a = *args;
+    if (a.nq != 1 || (a.P & 15) != 0 || a.nsub != 0 || (mode != 1 && mode != 2)) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)a.P;
+    const int blocks = hdb_quant_scan_blocks(a.ntiles, max_blocks);
+    const int nj = ((a.P >> 4) + 15) >> 4;
+    hipStream_t st = (hipStream_t)stream;
+#define HQ_ONE(NJ_) do { if (mode == 1) hipLaunchKernelGGL((hdb_quant_scan_kernel<1, 1, NJ_, true>), dim3(blocks), dim3(256), lds, st, a); \
+                         else hipLaunchKernelGGL((hdb_quant_scan_kernel<2, 1, NJ_, false>), dim3(blocks), dim3(256), lds, st, a); } while (0)
+    if (nj == 1) HQ_ONE(1); else if (nj == 2) HQ_ONE(2); else if (nj == 3) HQ_ONE(3); else HQ_ONE(0);
+#undef HQ_ONE
     return (int)hipGetLastError();
 }
 

@@ -42,7 +42,7 @@ EXPORTS = (
     "hdb_index_has_nan", "hdb_index_set_bias", "hdb_index_set_row_mask", "hdb_scores", "hdb_topk",
     "hdb_topk_exact", "hdb_merge_topk", "hdb_set_option", "hdb_get_stat", "hdb_recency_bias", "hdb_recency_bias_twice",
     "hdb_packed_bytes", "hdb_merge_topk_packed", "hdb_merge_topk_host", "hdb_host_exchange_merge", "hdb_topk_host",
-    "hdb_index_quantize",
+    "hdb_index_quantize", "hdb_debug_quant_bounds",
 )
 
 
@@ -67,6 +67,7 @@ def _load():
     lib.hdb_index_gather.argtypes = [vp, vp, i64, vp, vp]
     lib.hdb_index_set_row_base.argtypes = [vp, i64]
     lib.hdb_index_quantize.argtypes = [vp, ctypes.c_int, vp]
+    lib.hdb_debug_quant_bounds.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
     lib.hdb_group_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), i32]
     lib.hdb_group_topk_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp]
     lib.hdb_group_destroy.argtypes = [vp]
@@ -266,6 +267,19 @@ class GpuIndex:
         with torch.cuda.device(self.device):
             _check(_lib.hdb_index_quantize(self._h, mode, _stream_ptr(self.device)), "hdb_index_quantize")
         self.quant = mode
+
+    def quant_bounds(self, q, metric_id):
+        """Test helper (hdb_debug_quant_bounds): per row, the int8 pass's upper bound and the 5-bit plane's, for one float32 query
+        -> two float32 numpy arrays of n entries.  The index needs a shadow with its plane."""
+        qd = torch.from_numpy(np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1))).to(self.device)
+        if qd.numel() != self.d:
+            raise ValueError(f"query must have {self.d} entries")
+        hi = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        hi5 = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_debug_quant_bounds(self._h, ctypes.c_void_p(qd.data_ptr()), int(metric_id), ctypes.c_void_p(hi.data_ptr()),
+                                               ctypes.c_void_p(hi5.data_ptr()), _stream_ptr(self.device)), "hdb_debug_quant_bounds")
+        return hi.cpu().numpy(), hi5.cpu().numpy()
 
     def set_row_base(self, row_base):
         self.row_base = int(row_base)

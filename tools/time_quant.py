@@ -9,7 +9,10 @@ crossover quant_min_n; --only times shape I alone, for a rocprofv3 run).
 --auto times the AUTOMATIC shadow instead (option auto_quant: a default fp16 index builds the shadow on its first eligible call and
 the rescoring returns the matrix cores' bits): fp16 shapes from 2M to 10M rows, one and four queries, the check is bit identity
 with the default path (use_quant = 0), and the last column is the one-off cost of the first eligible call (allocation + one pass
-over the matrix).  The automatic row threshold (HDB_QUANT_AUTO_MIN_ROWS, hdb_api.hip) cites this table.
+over the matrix).  The automatic row threshold (HDB_QUANT_AUTO_MIN_ROWS, hdb_api.hip) cites this table.  The int8 column is the
+shadow WITHOUT the 5-bit plane (use_plane = 0); one-query shapes get two more columns, the shadow behind the plane (plane_min_n =
+0) and the rows its first pass kept (plane_survivors), all columns interleaved in one process on one index.  The plane's row rule
+(HDB_PLANE_MIN_ROWS, hdb_api.hip) cites that table, profiles/quant_plane_time.txt.
 
 --auto --batch [--rows ...] [--dims ...] [--queries ...] times batches of 5+ queries through the automatic shadow (batch_table
 below); the row rule of batches (quant_batch_rule, hdb_api.hip) cites that table, profiles/quant_batch_time.txt.
@@ -124,7 +127,7 @@ def main():
         return batch_table(args)
     g = torch.Generator(device="cuda").manual_seed(5)
     print(f"{'dtype':8s} {'rows':>10s} {'d':>4s} {'nq':>3s} {'plain us':>9s} {'int8 us':>9s} {'speed-up':>8s} {'cands':>6s} same"
-          + ("  first call ms" if args.auto else ""), flush=True)
+          + ("  first call ms  plane us  vs int8  survivors" if args.auto else ""), flush=True)
     shapes = AUTO if args.auto else SHAPES + (EXTRA if args.extra else [])
     if args.only >= 0:
         shapes = [shapes[args.only]]
@@ -139,9 +142,11 @@ def main():
             ix.set_option("use_quant", 0)
             return call(h, Q, k)
 
-        def quant():
+        def quant(plane=0):
             ix.set_option("use_quant", 1)
             ix.set_option("quant_min_n", 0)
+            ix.set_option("use_plane", plane)
+            ix.set_option("plane_min_n", 0)
             return call(h, Q, k)
 
         first_ms = 0.0
@@ -160,17 +165,34 @@ def main():
             a = call(h, Q, k)                     # the VALU scan's answer, which the shadow reproduces bit for bit
             ix.set_option("use_mfma", 1); ix.set_option("use_fused", 1)
         same = all(np.array_equal(x, y) for x, y in zip(flat(a), flat(b)))
+        with_plane = args.auto and nq == 1
+        surv = 0
+        if with_plane:
+            c = quant(1)
+            took &= ix.stat("plane")
+            surv = ix.stat("plane_survivors")
+            same = same and all(np.array_equal(x, y) for x, y in zip(flat(a), flat(c))) and ix.stat("quant_cands") == cands
         for _ in range(5):
-            plain(); quant()
-        ta, tb = [], []
+            plain(); quant(0)
+            if with_plane:
+                quant(1)
+        ta, tb, tc = [], [], []
         for _ in range(args.reps):
             ix.set_option("use_quant", 0)
             t0 = time.perf_counter(); call(h, Q, k); ta.append(time.perf_counter() - t0)
-            ix.set_option("use_quant", 1)
+            ix.set_option("use_quant", 1); ix.set_option("use_plane", 0)
             t0 = time.perf_counter(); call(h, Q, k); tb.append(time.perf_counter() - t0)
+            if with_plane:
+                ix.set_option("use_plane", 1)
+                t0 = time.perf_counter(); call(h, Q, k); tc.append(time.perf_counter() - t0)
         pa, pb = np.median(ta) * 1e6, np.median(tb) * 1e6
-        print(f"{str(dt)[6:]:8s} {n:10d} {d:4d} {nq:3d} {pa:9.1f} {pb:9.1f} {pa / pb:8.2f} {cands:6d} {same and took == 1}"
-              + (f"  {first_ms:8.2f}" if args.auto else ""), flush=True)
+        tail = ""
+        if args.auto:
+            tail = f"  {first_ms:8.2f}"
+            if with_plane:
+                pc = np.median(tc) * 1e6
+                tail += f"      {pc:9.1f} {pb / pc:8.2f} {surv:10d}"
+        print(f"{str(dt)[6:]:8s} {n:10d} {d:4d} {nq:3d} {pa:9.1f} {pb:9.1f} {pa / pb:8.2f} {cands:6d} {same and took == 1}" + tail, flush=True)
         h.close()
         del V, h, ix
         torch.cuda.empty_cache()
