@@ -11,6 +11,7 @@
 //                 sampled threshold failed, and by tests as the on-device cross-check.
 #include "hdb_common.h"
 #include "hdb_quant.h"
+#include "hdb_ws.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
 #include <cmath>
@@ -20,94 +21,6 @@
 #include <vector>
 #include <chrono>
 #include <atomic>
-
-// launchers implemented in the kernel translation units
-extern "C" {
-int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
-int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, float* inv_norm, float* sqnorm, int* nan_flag, void* stream);
-int hdb_launch_qprep(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl, void* stream);
-int hdb_launch_qprep2(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
-                      float* thr_init, uint32_t* cnt_init, uint32_t* qbits, int W, void* stream);
-int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, int64_t row0, uint32_t* bits, void* stream);
-int hdb_launch_qsign(const void* Q, int nq, int d, bool f64, int W, uint32_t* qbits, void* stream);
-int hdb_launch_hamming(const ScanArgs* args, int mode, int nq_launch, const uint32_t* bits, int64_t npad, int W,
-                       const uint32_t* qbits, void* stream);
-int hdb_launch_hist(const float* scores, int64_t n, int64_t ld, int nq, uint32_t* hist, int pass, uint32_t k, void* stream);
-int hdb_launch_thr(const uint32_t* hist, int nq, int npass, uint32_t m, uint32_t sample_n, float* thr, uint32_t* cnt, void* stream);
-int hdb_launch_fill_thr(float* thr, uint32_t* cnt, int nq, float v, void* stream);
-int hdb_launch_sample_thr(const float* scores, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, uint32_t* cnt, uint32_t* tile_ctr, void* stream);
-int hdb_launch_collect(const float* scores, int64_t n, int64_t ld, int nq, const uint32_t* hist, int npass, uint32_t k, uint32_t* cnt,
-                       unsigned long long* cand, uint32_t cap, uint32_t* tie_info, void* stream);
-int hdb_launch_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
-                        int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan, int threads, int inf_status, void* stream);
-int hdb_launch_status_nan(const int* qnan, int nq, int32_t* status, void* stream);
-int hdb_launch_merge(const void* idx_base, int64_t idx_stride, const void* score_base, int64_t score_stride,
-                     const void* status_base, int64_t status_stride, int parts, int nq, uint32_t k, int64_t* idx_out,
-                     float* score_out, int32_t* status_out, void* stream);
-int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, float* pscale, void* stream);
-int hdb_launch_qcentre(const void* Q, int nq, int d, bool f64, void* Qc, float* qscale, void* stream);
-int hdb_launch_recency(const double* ts, int64_t n, double rb, double ts_max, float* out, void* stream);
-int hdb_launch_recency2(const double* ts, const uint8_t* mask, int64_t n, double rb, double ts_max, double first_max, float* out, void* stream);
-int hdb_launch_maskbias(const uint8_t* mask, const float* bias, int64_t n, float* out, void* stream);
-int hdb_mfma_supported(int dtype, int d, int metric);
-int hdb_mfma_tile_rows(int dtype, int d);
-int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                         const float* qsq, const float* qscl, int max_blocks, int variant, void* stream, const BatchArgs* f);
-int hdb_mfma_batch_capacity(int dtype, int d);
-int hdb_mfma_ksplit_slices(int dtype, int d);
-int hdb_mfma_anyd_pad(int dtype, int d);
-int hdb_mfma_f32_split_min_q(int d);
-int hdb_mfma_f32_split_max_q(int d);
-int hdb_l1_tile_supported(int dtype, int d);
-int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
-int hdb_bits_fused_supported(int metric, int nq, int W, uint32_t kk);
-int hdb_launch_bits_fused(const BitsArgs* args, int jaccard, int max_blocks, void* stream);
-size_t hdb_mfma_batch_ctl_bytes(int wgs);
-int hdb_mfma_fused_supported(int dtype, int d, int metric, int nq, uint32_t kk);
-size_t hdb_mfma_fused_ctl_bytes(void);
-int hdb_launch_mfma_fused(const ScanArgs* args, int dtype, const FusedArgs* fa, int max_blocks, void* stream);
-int hdb_mfma_fused_local_tiles(int dtype, int d, int metric, int nq);
-int hdb_launch_q_to_f16(const float* Q, int nq, int d, void* q16, float* qscl, void* stream);
-int hdb_sort_temp_bytes(int64_t n, size_t* bytes);
-int hdb_launch_full_sort(const float* scores, int64_t n, int64_t k, int64_t row_base, uint32_t* work, void* temp, size_t temp_bytes,
-                         int64_t* idx_out, float* score_out, void* stream);
-int hdb_launch_gather_rows(const void* V, const int64_t* rows, int64_t m, int row_bytes, void* out, const float* inv_in,
-                           const float* sq_in, float* inv_out, float* sq_out, int* nan_flag, void* stream);
-int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype, int P, int8_t* codes, float* aux, int* nan_flag, double gamma,
-                          void* stream);
-int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m, int P, int8_t* codes_out,
-                            float* aux_out, void* stream);
-int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt, void* stream);
-int hdb_quant_plane_units(int P);
-int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
-                                float* rec, void* stream);
-int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream);
-int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
-int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
-int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
-                             const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
-                             const uint32_t* cnt, uint32_t cap, void* stream);
-int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
-                            int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
-int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks);
-int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
-                             const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv, float* gbias,
-                             void* stream);
-int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
-                              int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
-                              const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
-                              void* stream);
-int hdb_qb_supported(int d);
-int hdb_qb_scan_blocks(int64_t ntiles, int nq, int max_blocks);
-int64_t hdb_qb_slots(int blocks, int nq);
-int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
-int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);
-int hdb_launch_qb_rescore(const void* V, int d, const void* q16, const float* qscl, const float* qinv, const float* inv_norm,
-                          const float* bias, const uint8_t* mask, int metric, unsigned long long* cand, const uint32_t* cnt,
-                          uint32_t cap, int nq, void* stream);
-int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
-                              const float* Q, const float* qsq, int q0, const float* bias, void* stream);
-}
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -239,25 +152,22 @@ struct hdb_index {
     size_t ev_used = 0;
 };
 
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Bump {
-    char* base; size_t off = 0, cap;
-    Bump(char* b, size_t c) : base(b), cap(c) {}
-    template <typename T> T* take(size_t count) {
-        off = align_up(off, 256);
-        T* p = reinterpret_cast<T*>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 static int ensure_ws(hdb_index* ix, size_t bytes) {
     if (bytes <= ix->ws_bytes) return HDB_OK;
     if (ix->ws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->ws)); ix->ws = nullptr; ix->ws_bytes = 0; }
     bytes = align_up(bytes + (bytes >> 2), 1 << 20);
     HIP_TRY(hipMalloc((void**)&ix->ws, bytes));
     ix->ws_bytes = bytes;
+    return HDB_OK;
+}
+// Lay a workspace out (hdb_ws.h): a dry run of the layout gives the size, the second run places the pointers.
+template <typename WS, typename... Ext>
+static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
+    const int rc = ensure_ws(ix, ws_bytes_for<WS>(ext...));
+    if (rc) return rc;
+    Bump b(ix->ws, ix->ws_bytes);
+    w.lay(b, ext...);
+    if (b.off > b.cap) return fail(HDB_ERR_NOMEM, "workspace: a layout ran past the size it reported");
     return HDB_OK;
 }
 
@@ -292,6 +202,13 @@ static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -2
 static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
 static size_t quant_elem(const hdb_index* ix) { return (size_t)hdb_elem_bytes(ix->dtype); }
 #define HDB_QSTAT_WORDS 4
+// the device words of hdb_index::qstat, zeroed on `st`; qstat stays null when the allocation itself fails
+static hipError_t qstat_alloc(hdb_index* ix, hipStream_t st) {
+    if (ix->qstat) return hipSuccess;
+    const hipError_t e = hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int));
+    if (e != hipSuccess) { ix->qstat = nullptr; return e; }
+    return hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st);
+}
 static void plane_free(hdb_index* ix) {
     if (ix->pnib) (void)hipFree(ix->pnib);
     if (ix->pbit) (void)hipFree(ix->pbit);
@@ -381,10 +298,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     }
     if (ix->dtype == HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
-    if (!ix->qstat) {
-        HIP_TRY(hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st));
-    }
+    HIP_TRY(qstat_alloc(ix, st));
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
     ix->plane_declined = false;
     int rc = quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st);
@@ -411,10 +325,8 @@ static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     if (free_b < shadow + ws_grow + ((size_t)1 << 30)) { ix->qauto_declined = true; return false; }
     const size_t plane = plane_possible(ix) ? (size_t)(ix->n + 64) * plane_row_bytes(P) : 0;
     ix->plane_declined = plane_wanted(ix) && free_b < shadow + plane + ws_grow + ((size_t)1 << 30);
-    if (!ix->qstat) {
-        if (hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); ix->qstat = nullptr; ix->qauto_declined = true; return false; }
-        (void)hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st);
-    }
+    // (no memory for the words: declined; a failed memset is not this function's to report, the launches behind it do)
+    if (qstat_alloc(ix, st) != hipSuccess && !ix->qstat) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
     ix->qP = P;
     if (quant_reserve(ix, std::max<int64_t>(ix->n, 1), 0, st, true) != HDB_OK || quant_rows(ix, 0, ix->n, st) != HDB_OK) {
         (void)hipGetLastError();
@@ -829,12 +741,10 @@ extern "C" int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* d
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     const int W = (ix->d + 31) / 32;
-    int rc = ensure_ws(ix, 8192 + (size_t)W * 4 + (size_t)ix->d * 8);
+    ScoresWs w;
+    int rc = ws_lay(ix, w, ix->d, W);
     if (rc) return rc;
-    Bump b(ix->ws, ix->ws_bytes);
-    float* qinv = b.take<float>(1); float* qsq = b.take<float>(1); int* qnan = b.take<int>(1);
-    uint32_t* qbits = b.take<uint32_t>(W);
-    void* qc = b.take<double>(ix->d);
+    float* qinv = w.qinv; float* qsq = w.qsq; int* qnan = w.qnan; uint32_t* qbits = w.qbits; void* qc = w.qc;
     LAUNCH_TRY(hdb_launch_qprep(dev_q, 1, ix->d, ix->dtype == HDB_F64, qinv, qsq, qnan, nullptr, nullptr, st));
     if (is_bits_metric(metric)) {
         rc = ensure_bits(ix, st); if (rc) return rc;
@@ -882,18 +792,6 @@ static int64_t quant_min_rows(const hdb_index* ix) {
 // ... and the smallest fp16 matrix that builds a shadow for itself (auto_quant; measured, profiles/auto_quant_time.txt, DESIGN.md
 // section 4.9).  It lies above the sizes at which the suite pins the default path's statistics (up to 1.6M rows).
 #define HDB_QUANT_AUTO_MIN_ROWS 2000000
-// Rows of the whole matrix the sampled threshold T_s aims to leave with a LOWER bound above it: 512 (a sample of 16 keeps P(fewer
-// than k = 128 such rows) near 1e-5).  The UPPER bounds let exp(z delta - delta^2 / 2) times as many through, delta = 2B / sigma =
-// 0.029 sqrt(d) standard deviations of the scores for Gaussian rows: ~8x at d = 384, 10-14x at d = 768, where 512 would overflow
-// the candidate list.  Rows wider than 512 elements therefore aim at 4k (at least 256: the sample is 16 n / target rows).
-static int64_t quant_sample_target(const hdb_index* ix, uint32_t kk) {
-    return ix->d > 512 ? std::min<int64_t>(512, std::max<int64_t>(256, 4 * (int64_t)kk)) : 512;
-}
-static int64_t quant_sample_tiles(int64_t n, int64_t target) {
-    const int64_t all_tiles = n / 16;
-    int64_t s_tiles = ((std::max<int64_t>((int64_t)(16.0 * (double)n / (double)target), 256)) + 15) / 16;
-    return std::max<int64_t>(1, std::min(s_tiles, all_tiles));
-}
 // Smallest matrix whose one-query calls go through the 5-bit plane when plane_min_n is -1: the smallest measured size from which the
 // plane column of profiles/quant_plane_time.txt beats the plane-off column by at least 5 % in both runs, at that size and every
 // larger one (2M: 1.10x / 1.09x, 10M: 1.29x / 1.30x).  It is also the smallest size that has an automatic shadow.
@@ -902,22 +800,40 @@ static int64_t quant_sample_tiles(int64_t n, int64_t target) {
 static uint32_t plane_list_cap(const hdb_index* ix, int64_t n) {
     return (uint32_t)(ix->plane_cap_rows > 0 ? std::min<int64_t>(ix->plane_cap_rows, n) : std::max<int64_t>(n / 8, 16));
 }
-static size_t quant_ws_need(const hdb_index* ix, int nq, int64_t n, bool mflavour) {
-    const int P = (int)align_up((size_t)ix->d, 16);
-    const int64_t s_tiles = quant_sample_tiles(n, quant_sample_target(ix, 1));       // (the largest sample any k takes)
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_tiles * 16, 4), 4);
-    size_t need = 8 * align_up((size_t)nq * 4, 256) + 4096;
-    need += align_up((size_t)nq * P, 256) + align_up((size_t)nq * HDB_QQ_WORDS * 4, 256);
-    need += align_up((size_t)nq * 4 * HDB_CNT_STRIDE, 256) + 256;
-    need += align_up((size_t)nq * HDB_CAND_CAP * 8, 256) + align_up((size_t)nq * ld_s * 4, 256);
-    if (nq == 1 && ix->pnib) need += align_up((size_t)plane_list_cap(ix, n) * 4, 256) + 256;     // survivor list of the plane pass
+// Extents of the workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h), handed to f: the memory guard of the automatic build sizes
+// with them, the call lays out with them.  The score buffer takes the extent of the largest sample any k takes (quant_ld_max) -- the
+// call's own ld_s is only its leading dimension -- so calls that differ in k never regrow the workspace.  (P from d: the automatic
+// build asks before the index has a pitch.)
+static int quant_pitch(const hdb_index* ix) { return (int)align_up((size_t)ix->d, 16); }
+template <typename F>
+static auto quant_ws_extents(const hdb_index* ix, int nq, bool mflavour, F f) {
+    const uint32_t pl_cap = (nq == 1 && ix->pnib) ? plane_list_cap(ix, ix->n) : 0;      // survivor list of the plane pass
+    return f(nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
+}
+static size_t quant_ws_bytes(const hdb_index* ix, int nq, bool mflavour) {
+    return quant_ws_extents(ix, nq, mflavour, [](auto... ext) { return ws_bytes_for<QuantWs>(ext...); });
+}
+static int quant_ws_lay(hdb_index* ix, QuantWs& w, int nq, bool mflavour) {
+    return quant_ws_extents(ix, nq, mflavour, [&](auto... ext) { return ws_lay(ix, w, ext...); });
+}
+// The shadow's counterpart of base_args: the index's side and the prepared queries; every pass sets its own tiles, outputs and lists.
+static void quant_base_args(const hdb_index* ix, QuantArgs& a, const int8_t* qcodes, const float* qaux, const float* qinv, int metric, int nq) {
+    memset(&a, 0, sizeof(a));
+    a.codes = ix->qcodes; a.n = ix->n; a.d = ix->d; a.P = ix->qP; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
+    a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = nq;
+    a.gamma = (float)quant_gamma(ix->d);
+}
+// Query prep of a 1-4-query shadow call.  mflavour: one launch (1/||q||, the scaled fp16 copy, codes of the rounded query); otherwise
+// 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||), then the codes.
+static int quant_query_prep(hdb_index* ix, const float* Q, int nq, const QuantWs& w, bool mflavour, int* stat, uint32_t* cnt_init,
+                            uint32_t* pl_cnt, hipStream_t st) {
     if (mflavour) {
-        const size_t crow = (size_t)nq * HDB_CAND_CAP;              // rows of the compact matrix
-        need += align_up((size_t)nq * ix->d * 2, 256) + 256;        // fp16 queries, qscl
-        need += align_up((size_t)nq * HDB_QUANT_NSUB_MAX * 4, 256); // per-wave maxima of the sample pass
-        need += align_up(crow * ix->d * 2, 256) + 2 * align_up(crow * 4, 256) + align_up((size_t)nq * crow * 4, 256);
+        LAUNCH_TRY(hdb_launch_quant_qprep_m(Q, nq, ix->d, ix->qP, w.qinv, w.qsq, w.qnan, w.q16, w.qscl, w.qcodes, w.qaux, stat, cnt_init, pl_cnt, st));
+    } else {
+        LAUNCH_TRY(hdb_launch_qprep(Q, nq, ix->d, false, w.qinv, w.qsq, w.qnan, nullptr, nullptr, st));
+        LAUNCH_TRY(hdb_launch_quant_qprep(Q, nq, ix->d, ix->qP, w.qcodes, w.qaux, stat, pl_cnt, st));
     }
-    return need;
+    return HDB_OK;
 }
 
 // 1-4 dot / cosine / euclidean queries through the int8 shadow (hdb_quant.hip): quantized query prep, lower bounds on a strided row
@@ -930,65 +846,41 @@ static size_t quant_ws_need(const hdb_index* ix, int nq, int64_t n, bool mflavou
 static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
                       float* dev_score, int32_t* dev_status, hipStream_t st, bool mflavour) {
     const int64_t n = ix->n;
-    const int P = ix->qP;
     const uint32_t m = 16;
-    const int64_t all_tiles = n / 16;
-    const int64_t s_tiles = quant_sample_tiles(n, quant_sample_target(ix, kk));
-    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
-    const int64_t s_rows = s_tiles * 16;
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    const QuantSample sp = quant_call_sample(n, ix->d, kk);
     // (a shadow that was built without a plane -- use_plane was off then -- gets it on the first call that asks for the path)
     const bool pl_call = nq == 1 && (metric == HDB_DOT || metric == HDB_COSINE) && plane_wanted(ix) &&
                          n >= (ix->plane_min_n >= 0 ? ix->plane_min_n : (int64_t)HDB_PLANE_MIN_ROWS);
     if (pl_call && !ix->pnib) { const int rcp = plane_rows(ix, 0, n, st); if (rcp) return rcp; }
     const bool use_pl = pl_call && ix->pnib != nullptr;
-    int rc = ensure_ws(ix, quant_ws_need(ix, nq, n, mflavour));
+    QuantWs w;
+    int rc = quant_ws_lay(ix, w, nq, mflavour);
     if (rc) return rc;
-    Bump b(ix->ws, ix->ws_bytes);
-    float* qinv = b.take<float>(nq); float* qsq = b.take<float>(nq); int* qnan = b.take<int>(nq);
-    int8_t* qcodes = b.take<int8_t>((size_t)nq * P);
-    float* qaux = b.take<float>((size_t)nq * HDB_QQ_WORDS);
-    float* thr = b.take<float>(nq);
-    uint32_t* cnt = b.take<uint32_t>((size_t)nq * HDB_CNT_STRIDE);
-    unsigned long long* cand = b.take<unsigned long long>((size_t)nq * HDB_CAND_CAP);
-    float* sbuf = b.take<float>((size_t)nq * ld_s);
     // one dot / cosine query: pass 1 over the 5-bit plane, pass 2 (MODE 1 itself) over the rows it keeps (hdb_quant.hip)
     const uint32_t pl_cap = plane_list_cap(ix, n);
-    uint32_t* pl_list = (nq == 1 && ix->pnib) ? b.take<uint32_t>(pl_cap) : nullptr;
     uint32_t* pl_cnt = use_pl ? reinterpret_cast<uint32_t*>(ix->qstat) + 1 : nullptr;
     const size_t crow = (size_t)nq * HDB_CAND_CAP;
-    uint32_t* wmax = nullptr; int nsub = 0;
-    void* q16 = nullptr; float* qscl = nullptr; char* G = nullptr; float* ginv = nullptr; float* gbias = nullptr; float* gsc = nullptr;
+    int nsub = 0;
     if (mflavour) {
-        q16 = b.take<uint16_t>((size_t)nq * ix->d); qscl = b.take<float>(nq);
-        G = b.take<char>(crow * ix->d * 2); ginv = b.take<float>(crow); gbias = b.take<float>(crow); gsc = b.take<float>((size_t)nq * crow);
-        wmax = b.take<uint32_t>((size_t)nq * HDB_QUANT_NSUB_MAX);
         // the threshold folded into the two passes (QuantArgs::nsub) while the sample's grid has at least the 1024 subsets
         // hdb_sample_thr_kernel works with; smaller samples keep that kernel
-        nsub = 4 * hdb_quant_scan_blocks(s_tiles, (int)ix->max_blocks);
+        nsub = 4 * hdb_quant_scan_blocks(sp.s_tiles, (int)ix->max_blocks);
         if (nsub < 1024 || nsub > HDB_QUANT_NSUB_MAX) nsub = 0;
-        LAUNCH_TRY(hdb_launch_quant_qprep_m((const float*)dev_Q, nq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, ix->qstat,
-                                            nsub ? cnt : nullptr, pl_cnt, st));
-    } else {
-        // 1/||q|| and the NaN flags exactly as every other path computes them (the cosine epilogue multiplies by this 1/||q||)
-        LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
-        LAUNCH_TRY(hdb_launch_quant_qprep((const float*)dev_Q, nq, ix->d, P, qcodes, qaux, ix->qstat, pl_cnt, st));
     }
-    QuantArgs a; memset(&a, 0, sizeof(a));
-    a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
-    a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = nq;
-    a.gamma = (float)quant_gamma(ix->d);
-    a.ntiles = s_tiles; a.tile_stride = s_stride; a.scores = sbuf; a.ld = ld_s;
-    a.wmax = wmax; a.nsub = nsub; a.thr_out = thr;
+    rc = quant_query_prep(ix, (const float*)dev_Q, nq, w, mflavour, ix->qstat, nsub ? w.cnt : nullptr, pl_cnt, st);
+    if (rc) return rc;
+    QuantArgs a; quant_base_args(ix, a, w.qcodes, w.qaux, w.qinv, metric, nq);
+    a.ntiles = sp.s_tiles; a.tile_stride = sp.s_stride; a.scores = w.sbuf; a.ld = sp.ld_s;
+    a.wmax = w.wmax; a.nsub = nsub; a.thr_out = w.thr;
     LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->max_blocks, st));
-    if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, nq, m, thr, cnt, nullptr, st));
+    if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(w.sbuf, sp.s_rows, sp.ld_s, nq, m, w.thr, w.cnt, nullptr, st));
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
-    a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
+    a.thr = w.thr; a.cnt = w.cnt; a.cand = w.cand; a.cap = HDB_CAND_CAP;
     prof_begin(ix, st);
     if (use_pl) {
         // pass 1 takes the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for pass 2 and the finalize
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
-        a.pl_list = pl_list; a.pl_cnt = pl_cnt; a.pl_cap = pl_cap;
+        a.pl_list = w.pl_list; a.pl_cnt = pl_cnt; a.pl_cap = pl_cap;
         LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->max_blocks, st));
         a.nsub = 0; a.wmax = nullptr;
         LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 1, (int)ix->max_blocks, st));
@@ -998,23 +890,23 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
     prof_end(ix, st);
     if (mflavour) {
         const bool has_bias = ix->bias != nullptr || ix->mask != nullptr;
-        LAUNCH_TRY(hdb_launch_quant_cgather(ix->V, ix->d * 2, ix->inv_norm, ix->bias, ix->mask, cand, cnt, HDB_CAND_CAP, nq, G,
-                                            metric == HDB_COSINE ? ginv : nullptr, has_bias ? gbias : nullptr, st));
+        LAUNCH_TRY(hdb_launch_quant_cgather(ix->V, ix->d * 2, ix->inv_norm, ix->bias, ix->mask, w.cand, w.cnt, HDB_CAND_CAP, nq, w.G,
+                                            metric == HDB_COSINE ? w.ginv : nullptr, has_bias ? w.gbias : nullptr, st));
         ScanArgs s; memset(&s, 0, sizeof(s));
-        s.V = G; s.n = (int64_t)crow; s.d = ix->d; s.Q = dev_Q; s.metric = metric; s.inv_norm = ginv; s.qinv = qinv;
-        s.bias = has_bias ? gbias : nullptr; s.mask = nullptr; s.nq = nq;
+        s.V = w.G; s.n = (int64_t)crow; s.d = ix->d; s.Q = dev_Q; s.metric = metric; s.inv_norm = w.ginv; s.qinv = w.qinv;
+        s.bias = has_bias ? w.gbias : nullptr; s.mask = nullptr; s.nq = nq;
         s.tile_stride = 1; s.ntiles = (int64_t)crow / hdb_mfma_tile_rows(ix->dtype, ix->d); s.cap = HDB_CAND_CAP;
-        s.scores = gsc; s.ld = (int64_t)crow;
-        LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, q16, ginv, qsq, qscl, (int)ix->max_blocks, (int)ix->mfma_variant, st, nullptr));
+        s.scores = w.gsc; s.ld = (int64_t)crow;
+        LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, w.q16, w.ginv, w.qsq, w.qscl, (int)ix->max_blocks, (int)ix->mfma_variant, st, nullptr));
     } else {
-        LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, qinv, ix->bias, ix->mask,
-                                            cand, cnt, HDB_CAND_CAP, st));
+        LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, w.qinv, ix->bias, ix->mask,
+                                            w.cand, w.cnt, HDB_CAND_CAP, st));
     }
-    LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, qnan,
-                                         qaux, thr, ix->qstat, mflavour ? cand : nullptr, gsc, (int64_t)crow, st));
+    LAUNCH_TRY(hdb_launch_quant_finalize(w.cand, w.cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, w.qnan,
+                                         w.qaux, w.thr, ix->qstat, mflavour ? w.cand : nullptr, w.gsc, (int64_t)crow, st));
     ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = mflavour ? 1 : 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
     ix->st_plane = use_pl ? 1 : 0;
-    ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
+    ix->st_sample_rows = sp.s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
     return HDB_OK;
 }
 
@@ -1026,24 +918,12 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     if (ix->qmode != HDB_QUANT_I8 || !ix->pnib || ix->n < 1) return fail(HDB_ERR_UNSUPPORTED, "hdb_debug_quant_bounds: the index has no 5-bit plane");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const int P = ix->qP;
-    int rc = ensure_ws(ix, quant_ws_need(ix, 1, ix->n, true));
+    QuantWs w;
+    int rc = quant_ws_lay(ix, w, 1, true);
     if (rc) return rc;
-    Bump b(ix->ws, ix->ws_bytes);
-    float* qinv = b.take<float>(1); float* qsq = b.take<float>(1); int* qnan = b.take<int>(1);
-    int8_t* qcodes = b.take<int8_t>((size_t)P);
-    float* qaux = b.take<float>(HDB_QQ_WORDS);
-    void* q16 = b.take<uint16_t>((size_t)ix->d); float* qscl = b.take<float>(1);
-    if (ix->qauto) {
-        LAUNCH_TRY(hdb_launch_quant_qprep_m(dev_q, 1, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, nullptr, nullptr, nullptr, st));
-    } else {
-        LAUNCH_TRY(hdb_launch_qprep(dev_q, 1, ix->d, false, qinv, qsq, qnan, nullptr, nullptr, st));
-        LAUNCH_TRY(hdb_launch_quant_qprep(dev_q, 1, ix->d, P, qcodes, qaux, nullptr, nullptr, st));
-    }
-    QuantArgs a; memset(&a, 0, sizeof(a));
-    a.codes = ix->qcodes; a.n = ix->n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
-    a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = 1;
-    a.gamma = (float)quant_gamma(ix->d);
+    rc = quant_query_prep(ix, dev_q, 1, w, ix->qauto, nullptr, nullptr, nullptr, st);
+    if (rc) return rc;
+    QuantArgs a; quant_base_args(ix, a, w.qcodes, w.qaux, w.qinv, metric, 1);
     a.ntiles = (ix->n + 15) / 16; a.tile_stride = 1;
     a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
     a.dbg = dev_hi;
@@ -1054,19 +934,6 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
 }
 
 // ---- batches of 5+ queries through the automatic shadow (hdb_quant_mfma.hip) ---------------------------------------------------
-// Sample plan of a batch.  T_s is the m-th largest sampled lower bound; the rows of the whole matrix with a LOWER bound above it
-// number about target x Gamma(m) / m.  A batch pays for its worst query on both sides (too few: the floor check fails; too many: the
-// upper bounds, exp(z delta) times as many, overflow the list), so the batch plan narrows the spread with m = 32 instead of 16 and
-// aims lower, at 320 rows: P(fewer than k = 128 such rows) = P(Gamma(32) < 12.8) ~ 1e-5 per query, and the +3 sigma query of 256
-// stands at 320 x 49 / 32 = 490 rows where the 1-4-query plan's would stand at 512 x 28 / 16 = 896.  The sample is m / target = a
-// tenth of the rows (the CPU model's m = 64 / target 256 would read a quarter of the shadow a second time).
-#define HDB_QB_SAMPLE_M 32
-#define HDB_QB_SAMPLE_TARGET 320
-static int64_t quant_batch_sample_tiles(int64_t n) {
-    const int64_t all_tiles = n / 16;
-    const int64_t rows = std::max<int64_t>((int64_t)((double)HDB_QB_SAMPLE_M * (double)n / (double)HDB_QB_SAMPLE_TARGET), 16 * HDB_QB_SAMPLE_M);
-    return std::max<int64_t>(1, std::min((rows + 15) / 16, all_tiles));
-}
 // The measured rule of quant_batch_min_n = -1: the smallest matrix from which a batch of nq queries is at least 1.10x faster through
 // the shadow than through the fp16 single launch, 0 = never (profiles/quant_batch_time.txt, one box, interleaved, p50 in us, parent ->
 // shadow).  The filter kernel reads its row fragments straight from global memory, so a workgroup has one tile per wave in flight:
@@ -1082,18 +949,18 @@ static int64_t quant_batch_rule(const hdb_index* ix, int nq) {
     else if (ix->d == 512) rows = nq <= 16 ? 10000000 : 0;
     return rows > 0 ? std::max<int64_t>(rows, HDB_QUANT_AUTO_MIN_ROWS) : 0;
 }
-static size_t quant_batch_ws_need(const hdb_index* ix, int cq, int64_t n) {
-    const int P = (int)align_up((size_t)ix->d, 16);
-    const int64_t s_tiles = quant_batch_sample_tiles(n);
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_tiles * 16, 4), 4);
-    const int64_t wld = align_up((size_t)hdb_qb_slots(512, 1), 4);              // (the most slots any launch leaves per query)
-    size_t need = 8 * align_up((size_t)cq * 4, 256) + 4096;
-    need += align_up((size_t)cq * P, 256) + align_up((size_t)cq * HDB_QQ_WORDS * 4, 256);
-    need += align_up((size_t)cq * 4 * HDB_CNT_STRIDE, 256) + 256;
-    need += align_up((size_t)cq * HDB_CAND_CAP * 8, 256);
-    need += align_up((size_t)cq * ix->d * 2, 256);
-    need += align_up(std::max((size_t)cq * wld, (size_t)4 * ld_s) * 4, 256);
-    return need;
+// Extents of the workspace of one chunk of a batch (QuantBatchWs, hdb_ws.h), handed to f like quant_ws_extents; wld: the most slots
+// any launch leaves per query.
+static int64_t quant_batch_wld() { return (int64_t)align_up((size_t)hdb_qb_slots(512, 1), 4); }
+template <typename F>
+static auto quant_batch_ws_extents(const hdb_index* ix, int cq, F f) {
+    return f(cq, quant_pitch(ix), (int)ix->d, quant_batch_sample(ix->n).ld_s, quant_batch_wld());
+}
+static size_t quant_batch_ws_bytes(const hdb_index* ix, int cq) {
+    return quant_batch_ws_extents(ix, cq, [](auto... ext) { return ws_bytes_for<QuantBatchWs>(ext...); });
+}
+static int quant_batch_ws_lay(hdb_index* ix, QuantBatchWs& w, int cq) {
+    return quant_batch_ws_extents(ix, cq, [&](auto... ext) { return ws_lay(ix, w, ext...); });
 }
 // One call: chunks of up to 256 queries, each through query prep, sample pass, thresholds, filter pass, block-diagonal rescoring
 // and finalize.  Workspace per chunk: the lists (cq x 8192 x 8 bytes = 16 MiB at 256 queries), the slot maxima of the sample pass
@@ -1103,24 +970,16 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
     const int64_t n = ix->n;
     const int P = ix->qP;
     const uint32_t m = HDB_QB_SAMPLE_M;
-    const int64_t all_tiles = n / 16;
-    const int64_t s_tiles = quant_batch_sample_tiles(n);
-    const int64_t s_stride = std::max<int64_t>(1, all_tiles / s_tiles);
-    const int64_t s_rows = s_tiles * 16;
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
+    const QuantSample sp = quant_batch_sample(n);
+    const int64_t s_tiles = sp.s_tiles, s_stride = sp.s_stride, s_rows = sp.s_rows, ld_s = sp.ld_s;
     const int cq_max = std::min<int>(nq, 256);
-    int rc = ensure_ws(ix, quant_batch_ws_need(ix, cq_max, n));
+    QuantBatchWs w;
+    const int rc = quant_batch_ws_lay(ix, w, cq_max);
     if (rc) return rc;
-    const int64_t wld = align_up((size_t)hdb_qb_slots(512, 1), 4);
-    Bump b(ix->ws, ix->ws_bytes);
-    float* qinv = b.take<float>(cq_max); float* qsq = b.take<float>(cq_max); int* qnan = b.take<int>(cq_max); float* qscl = b.take<float>(cq_max);
-    int8_t* qcodes = b.take<int8_t>((size_t)cq_max * P);
-    float* qaux = b.take<float>((size_t)cq_max * HDB_QQ_WORDS);
-    float* thr = b.take<float>(cq_max);
-    uint32_t* cnt = b.take<uint32_t>((size_t)cq_max * HDB_CNT_STRIDE);
-    unsigned long long* cand = b.take<unsigned long long>((size_t)cq_max * HDB_CAND_CAP);
-    void* q16 = b.take<uint16_t>((size_t)cq_max * ix->d);
-    float* wbuf = b.take<float>(std::max((size_t)cq_max * wld, (size_t)4 * ld_s));       // slot maxima (kernel 1) / sampled lower bounds of four queries (kernel 0)
+    const int64_t wld = quant_batch_wld();
+    float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
+    int8_t* const qcodes = w.qcodes; float* const qaux = w.qaux; float* const thr = w.thr; uint32_t* const cnt = w.cnt;
+    unsigned long long* const cand = w.cand; void* const q16 = w.q16; float* const wbuf = w.wbuf;
     ix->st_chunks = 0;
     for (int q0 = 0; q0 < nq; q0 += cq_max) {
         const int cq = std::min(cq_max, nq - q0);
@@ -1128,10 +987,7 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
         const float* Qc = (const float*)dev_Q + (size_t)q0 * ix->d;
         // (the stat word is reset by the first chunk only: quant_cands is the largest list of the CALL)
         LAUNCH_TRY(hdb_launch_quant_qprep_m(Qc, cq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, q0 == 0 ? ix->qstat : nullptr, cnt, nullptr, st));
-        QuantArgs a; memset(&a, 0, sizeof(a));
-        a.codes = ix->qcodes; a.n = n; a.d = ix->d; a.P = P; a.aux = ix->qaux; a.sqnorm = ix->sqnorm; a.inv_norm = ix->inv_norm;
-        a.qcodes = qcodes; a.qaux = qaux; a.qinv = qinv; a.bias = ix->bias; a.mask = ix->mask; a.metric = metric; a.nq = cq;
-        a.gamma = (float)quant_gamma(ix->d);
+        QuantArgs a; quant_base_args(ix, a, qcodes, qaux, qinv, metric, cq);
         a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
         if (ix->quant_batch_kernel) {
             a.ntiles = s_tiles; a.tile_stride = s_stride;
@@ -1165,6 +1021,27 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
     ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = 1; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
     ix->st_sample_rows = s_rows; ix->st_sample_m = m;
     ix->qb_cnt = cnt; ix->qb_cnt_n = nq - (nq - 1) / cq_max * cq_max;
+    return HDB_OK;
+}
+
+// What the two automatic-shadow tests of topk_impl share (auto_quant): a call the matrix cores would answer on an fp16 matrix that
+// has no shadow or an automatic one, sampled path, status words, k within the shadow's limits, dot or cosine.
+static bool auto_quant_call(const hdb_index* ix, bool mfma, bool exact, bool small, const int32_t* dev_status, int32_t k, int metric) {
+    return ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
+           dev_status != nullptr && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE);
+}
+// The single-launch pipelines: a fresh epoch per launch on a control block (31 bits, never 0: bit 31 of a tag is the "final" flag
+// of the threshold words), the bound of every in-kernel spin in 100 MHz ticks, and the control block itself, zero when allocated.
+static uint32_t next_epoch(hdb_index* ix) {
+    ix->fused_epoch = (ix->fused_epoch + 1) & 0x7FFFFFFFu;
+    if (ix->fused_epoch == 0) ix->fused_epoch = 1;
+    return ix->fused_epoch;
+}
+static uint32_t timeout_ticks(const hdb_index* ix) { return (uint32_t)std::min<int64_t>(ix->fused_timeout_us * 100, 0x7FFFFFFF); }
+static int ensure_ctl(char** ctl, size_t bytes) {
+    if (*ctl) return HDB_OK;
+    HIP_TRY(hipMalloc((void**)ctl, bytes));
+    HIP_TRY(hipMemset(*ctl, 0, bytes));
     return HDB_OK;
 }
 
@@ -1234,26 +1111,24 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call; an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
-    if (ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
-        dev_status != nullptr && nq >= 1 && nq <= 4 && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE) &&
+    const bool auto_q = auto_quant_call(ix, mfma, exact, small, dev_status, k, metric);
+    if (auto_q && nq >= 1 && nq <= 4 &&
         // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
         (ix->quant_min_n >= 0 ? n >= ix->quant_min_n : (n >= (int64_t)HDB_QUANT_AUTO_MIN_ROWS && ix->d <= 512))) {
         bool finite = false;
         const int rcf = matrix_is_finite(ix, &finite);
         if (rcf != HDB_OK) return rcf;
-        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_ws_need(ix, nq, n, true), st)))
+        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_ws_bytes(ix, nq, true), st)))
             return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, true);
     }
     // ... and batches of 5+ queries (hdb_quant_mfma.hip): the same conditions under a row rule of their own (quant_batch_min_n), for the
     // widths the int8 matrix-core pass takes and the 16x16x32 form of the fp16 scan, whose bits the rescoring returns
-    if (ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
-        dev_status != nullptr && nq >= 5 && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE) &&
-        hdb_qb_supported(ix->d) && ix->mfma_variant == 16 &&
+    if (auto_q && nq >= 5 && hdb_qb_supported(ix->d) && ix->mfma_variant == 16 &&
         (ix->quant_batch_min_n >= 0 ? n >= ix->quant_batch_min_n : (quant_batch_rule(ix, nq) > 0 && n >= quant_batch_rule(ix, nq)))) {
         bool finite = false;
         const int rcf = matrix_is_finite(ix, &finite);
         if (rcf != HDB_OK) return rcf;
-        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_batch_ws_need(ix, std::min<int>(nq, 256), n), st)))
+        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_batch_ws_bytes(ix, std::min<int>(nq, 256)), st)))
             return quant_batch_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st);
     }
     // 1-4 dot / cosine queries, k <= 128: one launch does everything (hdb_mfma_fused.h; fp16 on the matrix cores,
@@ -1307,31 +1182,16 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), ix->exact_bytes / (ld_n * 4)));
     cq_max = std::min(cq_max, (int)nq);
 
-    size_t need = 0;
-    need += 4 * align_up((size_t)nq * 4, 256) + 1024;                        // qinv, qsq, qnan, qscl
-    need += align_up((size_t)nq * W * 4, 256);                               // qbits
-    need += align_up((size_t)nq * ix->d * 2, 256);                           // fp16 queries (MFMA)
-    need += align_up((size_t)nq * ix->d * 8, 256);                           // centred queries (pearson)
-    need += align_up((size_t)cq_max * 4, 256) + align_up((size_t)cq_max * 4 * HDB_CNT_STRIDE, 256) + 256;     // thr, cnt (a cache line per query), tile counter
-    need += align_up((size_t)cq_max * 4 * HDB_RADIX_BINS * 4, 256);          // hist
-    need += align_up((size_t)cq_max * 16, 256);                              // tie_info
-    need += align_up((size_t)cq_max * HDB_CAND_CAP * 8, 256);                // cand
-    need += align_up((size_t)cq_max * (exact && !small ? ld_n : ld_s) * 4, 256) + 4096;
-    if (ksplit) need += align_up((size_t)cq_max * ld_n * 4, 256);
-    int rc = ensure_ws(ix, need);
+    // full sort (k > HDB_MAX_K): all scores of one query, the sort's work array and its scratch live in the same layout
+    size_t sort_temp = 0;
+    if (full_sort) LAUNCH_TRY(hdb_sort_temp_bytes(n, &sort_temp));
+    TopkWs w;
+    int rc = ws_lay(ix, w, (int)nq, (int)ix->d, W, cq_max, exact && !small ? ld_n : ld_s, ksplit ? ld_n : (int64_t)0, full_sort ? n : (int64_t)0, sort_temp);
     if (rc) return rc;
-    Bump b(ix->ws, ix->ws_bytes);
-    float* qinv = b.take<float>(nq); float* qsq = b.take<float>(nq); int* qnan = b.take<int>(nq); float* qscl = b.take<float>(nq);
-    uint32_t* qbits = b.take<uint32_t>((size_t)nq * W);
-    void* q16 = b.take<uint16_t>((size_t)nq * ix->d);
-    void* qc = b.take<double>((size_t)nq * ix->d);
-    float* thr = b.take<float>(cq_max); uint32_t* cnt = b.take<uint32_t>((size_t)cq_max * HDB_CNT_STRIDE);
-    uint32_t* tile_ctr = b.take<uint32_t>(64);
-    uint32_t* hist = b.take<uint32_t>((size_t)cq_max * 4 * HDB_RADIX_BINS);
-    uint32_t* tie_info = b.take<uint32_t>((size_t)cq_max * 4);
-    unsigned long long* cand = b.take<unsigned long long>((size_t)cq_max * HDB_CAND_CAP);
-    float* sbuf = b.take<float>((size_t)cq_max * (exact && !small ? ld_n : ld_s));
-    float* kbuf = ksplit ? b.take<float>((size_t)cq_max * ld_n) : nullptr;
+    float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
+    uint32_t* const qbits = w.qbits; void* const q16 = w.q16; void* const qc = w.qc;
+    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
+    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
 
     const bool fused = fused_shape && !full_sort && (m == 8 || local_ok);           // (no prep kernel either)
     // the MFMA scan multiplies with fp16 queries: written by the same kernel (pearson converts its centred copy later)
@@ -1365,35 +1225,18 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     }
     if (full_sort) {
         // cold path for huge k: one query at a time, all scores -> stable radix sort (hdb_sort.hip)
-        size_t tb = 0;
-        LAUNCH_TRY(hdb_sort_temp_bytes(n, &tb));
-        const size_t extra = align_up((size_t)n * 4, 256) + align_up((size_t)n * 16, 256) + align_up(tb, 256) + 4096;
-        // the workspace was sized before this branch was known: grow it now (all pointers above are re-derived)
-        const size_t base_need = need;
-        rc = ensure_ws(ix, base_need + extra); if (rc) return rc;
-        Bump b2(ix->ws, ix->ws_bytes);
-        float* qinv2 = b2.take<float>(nq); float* qsq2 = b2.take<float>(nq); int* qnan2 = b2.take<int>(nq); (void)b2.take<float>(nq);
-        uint32_t* qbits2 = b2.take<uint32_t>((size_t)nq * W);
-        (void)b2.take<uint16_t>((size_t)nq * ix->d);
-        void* qc2 = b2.take<double>((size_t)nq * ix->d);
-        float* sc1 = b2.take<float>((size_t)ld_n);
-        uint32_t* work = b2.take<uint32_t>((size_t)n * 4);
-        void* temp = b2.take<char>(tb);
-        LAUNCH_TRY(hdb_launch_qprep(dev_Q, nq, ix->d, f64, qinv2, qsq2, qnan2, nullptr, nullptr, st));
-        if (is_ham) LAUNCH_TRY(hdb_launch_qsign(dev_Q, nq, ix->d, f64, W, qbits2, st));
-        const void* Q2 = dev_Q;
-        if (is_pearson) { LAUNCH_TRY(hdb_launch_qcentre(dev_Q, nq, ix->d, f64, qc2, qinv2, st)); Q2 = qc2; }
+        // (the queries are prepared: this branch excludes the single launches, so the prep, sign and centring launches above ran)
         ix->st_path = 3; ix->st_mfma = 0; ix->st_chunks = nq;
         for (int q0 = 0; q0 < nq; ++q0) {
-            QueryBufs qb{qinv2, qsq2, qbits2, nullptr, nullptr};
-            ScanArgs s2; base_args(ix, s2, Q2, metric_eff);
+            QueryBufs qb{qinv, qsq, qbits, nullptr, nullptr};
+            ScanArgs s2; base_args(ix, s2, Qeff, metric_eff);
             if (is_pearson) s2.inv_norm = ix->pscale;
-            s2.q0 = q0; s2.bias = ix->bias; s2.scores = sc1; s2.ld = ld_n;
+            s2.q0 = q0; s2.bias = ix->bias; s2.scores = w.sc1; s2.ld = ld_n;
             rc = run_scan(ix, s2, 0, 1, qb, false, st); if (rc) return rc;
-            LAUNCH_TRY(hdb_launch_full_sort(sc1, n, k, ix->row_base, work, temp, tb, dev_idx + (int64_t)q0 * k,
+            LAUNCH_TRY(hdb_launch_full_sort(w.sc1, n, k, ix->row_base, w.work, w.temp, sort_temp, dev_idx + (int64_t)q0 * k,
                                             dev_score + (int64_t)q0 * k, st));
         }
-        if (dev_status) LAUNCH_TRY(hdb_launch_status_nan(qnan2, nq, dev_status, st));     // HDB_Q_NAN survives on this path too
+        if (dev_status) LAUNCH_TRY(hdb_launch_status_nan(qnan, nq, dev_status, st));     // HDB_Q_NAN survives on this path too
         return HDB_OK;
     }
     // the MFMA scan has no mask input: excluded rows get a bias of -inf instead (never appended, like the VALU scan)
@@ -1414,11 +1257,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     ix->st_fused = 0; ix->st_local = 0;
     if (fused) {
         // ---- the whole call in ONE launch (hdb_mfma_fused.h): prep + sample + threshold + filter pass + finalize ----
-        if (!ix->fctl) {
-            const size_t cb = hdb_mfma_fused_ctl_bytes();
-            HIP_TRY(hipMalloc((void**)&ix->fctl, cb));
-            HIP_TRY(hipMemset(ix->fctl, 0, cb));
-        }
+        rc = ensure_ctl(&ix->fctl, hdb_mfma_fused_ctl_bytes()); if (rc) return rc;
         ScanArgs a; base_args(ix, a, dev_Q, metric);
         a.bias = bias_eff; a.mask = nullptr;
         if (metric == HDB_EUCLIDEAN) a.inv_norm = ix->sqnorm;          // the per-row aux value of the euclidean expansion
@@ -1428,10 +1267,8 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
         FusedArgs fa; memset(&fa, 0, sizeof(fa));
         fa.Qraw = static_cast<const float*>(dev_Q); fa.nq = nq;
         fa.s_tiles = s_tiles; fa.s_stride = s_stride;
-        ix->fused_epoch = (ix->fused_epoch + 1) & 0x7FFFFFFFu;          // 31 bits: bit 31 of a tag is the "final" flag of the threshold words
-        if (ix->fused_epoch == 0) ix->fused_epoch = 1;
-        fa.epoch = ix->fused_epoch;
-        fa.timeout_ticks = (uint32_t)std::min<int64_t>(ix->fused_timeout_us * 100, 0x7FFFFFFF);
+        fa.epoch = next_epoch(ix);
+        fa.timeout_ticks = timeout_ticks(ix);
         fa.ctl = reinterpret_cast<uint32_t*>(ix->fctl);
         fa.cand = cand; fa.cap = HDB_CAND_CAP; fa.k = (uint32_t)k; fa.kk = kk; fa.row_base = ix->row_base;
         fa.idx_out = dev_idx; fa.score_out = dev_score; fa.status = dev_status; fa.thr_out = thr;
@@ -1457,11 +1294,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     // kernel (hdb_bits_fused.hip); larger batches go through it four queries at a time (as the multi-kernel scan re-reads the bits)
     const bool bits1 = bits1_pre;
     if (bits1) {
-        if (!ix->bctl) {
-            const size_t cb = hdb_mfma_batch_ctl_bytes(hdb_cu_count());
-            HIP_TRY(hipMalloc((void**)&ix->bctl, cb));
-            HIP_TRY(hipMemset(ix->bctl, 0, cb));
-        }
+        rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
         ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 0; ix->st_path = 1; ix->st_mfma = 0; ix->st_fused = 3;
         {   // (the launcher's rule: the local flavour from 2 k workgroups on, hdb_bits_fused.hip)
             int64_t bl = hdb_cu_count();
@@ -1479,10 +1312,8 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
             ba.ntiles = (n + 15) / 16; ba.s_tiles = s_tiles; ba.s_stride = s_stride;
             ba.bias = ix->bias; ba.mask = ix->mask;
             ba.local = ix->bits_local ? 1 : 0;
-            ix->fused_epoch = (ix->fused_epoch + 1) & 0x7FFFFFFFu;
-            if (ix->fused_epoch == 0) ix->fused_epoch = 1;
-            ba.epoch = ix->fused_epoch;
-            ba.timeout_ticks = (uint32_t)std::min<int64_t>(ix->fused_timeout_us * 100, 0x7FFFFFFF);
+            ba.epoch = next_epoch(ix);
+            ba.timeout_ticks = timeout_ticks(ix);
             ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
             ba.cand = cand; ba.cap = HDB_CAND_CAP; ba.k = (uint32_t)k; ba.kk = kk; ba.row_base = ix->row_base;
             ba.idx_out = dev_idx + (int64_t)q0 * k; ba.score_out = dev_score + (int64_t)q0 * k; ba.status = dev_status + q0;
@@ -1495,12 +1326,7 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
         return HDB_OK;
     }
     if (batch1) {
-        const int cus = hdb_cu_count();
-        if (!ix->bctl) {
-            const size_t cb = hdb_mfma_batch_ctl_bytes(cus);
-            HIP_TRY(hipMalloc((void**)&ix->bctl, cb));
-            HIP_TRY(hipMemset(ix->bctl, 0, cb));
-        }
+        rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
         ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 0; ix->st_path = 1; ix->st_mfma = 1; ix->st_fused = 2;
         const size_t qrow = (size_t)ix->d * 4;
         for (int q0 = 0; q0 < nq; q0 += cq_max) {
@@ -1515,10 +1341,8 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
             BatchArgs fa; memset(&fa, 0, sizeof(fa));
             fa.Qraw = static_cast<const char*>(dev_Q) + (size_t)q0 * qrow;
             fa.s_tiles = s_tiles; fa.s_stride = s_stride; fa.centre = is_pearson ? 1 : 0;
-            ix->fused_epoch = (ix->fused_epoch + 1) & 0x7FFFFFFFu;
-            if (ix->fused_epoch == 0) ix->fused_epoch = 1;
-            fa.epoch = ix->fused_epoch;
-            fa.timeout_ticks = (uint32_t)std::min<int64_t>(ix->fused_timeout_us * 100, 0x7FFFFFFF);
+            fa.epoch = next_epoch(ix);
+            fa.timeout_ticks = timeout_ticks(ix);
             fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
             fa.k = (uint32_t)k; fa.kk = kk; fa.row_base = ix->row_base;
             fa.idx_out = dev_idx + (int64_t)q0 * k; fa.score_out = dev_score + (int64_t)q0 * k; fa.status = dev_status + q0;
@@ -1601,8 +1425,6 @@ extern "C" int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k,
                         float* dev_score, int32_t* dev_status, void* stream) {
     return topk_impl(ix, dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, stream, false);
 }
-
-extern "C" int64_t hdb_packed_bytes(int32_t nq, int32_t k);
 
 // k-way merge of `parts` packed records in host memory (recs[p] = record of shard p) into out_record
 static void merge_host_records(const char* const* recs, int32_t parts, int32_t nq, int32_t k, void* out_record) {

@@ -277,3 +277,6 @@ static inline int hdb_grid_for(int64_t work_items, int per_block, int max_blocks
     if (b < 1) b = 1;
     return (int)(b < (int64_t)max_blocks ? b : (int64_t)max_blocks);
 }
+
+// ---- what crosses a translation unit: declared once, seen by every unit ----------------------
+#include "hdb_launch.h"

@@ -1,0 +1,153 @@
+// hdb_launch.h -- every function that crosses a translation unit of the library and is not part of the public ABI
+// (include/hyperdb_hip.h): the launchers of the kernel units and the capability / size helpers beside them.
+//
+// The names are extern "C", so a call through a stale prototype would still link and the callee would read the wrong
+// registers.  Each function is therefore declared HERE ONLY, and every unit that defines one sees this header (through
+// hdb_common.h): a definition that drifts from its declaration fails to compile with "conflicting types".
+// tests/test_launchers_declared_once.py keeps both halves of that true.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+struct ScanArgs;        // hdb_common.h
+struct FusedArgs;
+struct BatchArgs;
+struct BitsArgs;
+struct QuantArgs;       // hdb_quant.h
+
+// shards of the matrix-core scan: one launcher per geometry, all with the same arguments
+#define HDB_ANYD_DECL(name) int name(const ScanArgs* args, int dpad, int mode, int nq_launch, const void* q, const float* sqnorm, \
+                                     const float* qsq, const float* qscl, int blocks, void* stream)
+#define HDB_GEOM_DECL(name) int name(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm, \
+                                     const float* qsq, const float* qscl, int blocks, int variant, void* stream, const BatchArgs* f)
+
+extern "C" {
+// ---- hdb_scan.hip: the VALU row scan, per-row caches, query prep ----
+int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
+int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, float* inv_norm, float* sqnorm, int* nan_flag, void* stream);
+int hdb_launch_qprep(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl, void* stream);
+int hdb_launch_qprep2(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
+                      float* thr_init, uint32_t* cnt_init, uint32_t* qbits, int W, void* stream);
+int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, int64_t row0, uint32_t* bits, void* stream);
+int hdb_launch_qsign(const void* Q, int nq, int d, bool f64, int W, uint32_t* qbits, void* stream);
+int hdb_launch_hamming(const ScanArgs* args, int mode, int nq_launch, const uint32_t* bits, int64_t npad, int W,
+                       const uint32_t* qbits, void* stream);
+int hdb_launch_maskbias(const uint8_t* mask, const float* bias, int64_t n, float* out, void* stream);
+int hdb_launch_recency(const double* ts, int64_t n, double rb, double ts_max, float* out, void* stream);
+int hdb_launch_recency2(const double* ts, const uint8_t* mask, int64_t n, double rb, double ts_max, double first_max, float* out, void* stream);
+int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, float* pscale, void* stream);
+int hdb_launch_qcentre(const void* Q, int nq, int d, bool f64, void* Qc, float* qscale, void* stream);
+
+// ---- hdb_select.hip: thresholds, collection, finalize, merge ----
+int hdb_launch_hist(const float* scores, int64_t n, int64_t ld, int nq, uint32_t* hist, int pass, uint32_t k, void* stream);
+int hdb_launch_thr(const uint32_t* hist, int nq, int npass, uint32_t m, uint32_t sample_n, float* thr, uint32_t* cnt, void* stream);
+int hdb_launch_fill_thr(float* thr, uint32_t* cnt, int nq, float v, void* stream);
+int hdb_launch_sample_thr(const float* scores, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, uint32_t* cnt, uint32_t* tile_ctr, void* stream);
+int hdb_launch_collect(const float* scores, int64_t n, int64_t ld, int nq, const uint32_t* hist, int npass, uint32_t k, uint32_t* cnt,
+                       unsigned long long* cand, uint32_t cap, uint32_t* tie_info, void* stream);
+int hdb_launch_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
+                        int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan, int threads, int inf_status, void* stream);
+int hdb_launch_status_nan(const int* qnan, int nq, int32_t* status, void* stream);
+int hdb_launch_merge(const void* idx_base, int64_t idx_stride, const void* score_base, int64_t score_stride,
+                     const void* status_base, int64_t status_stride, int parts, int nq, uint32_t k, int64_t* idx_out,
+                     float* score_out, int32_t* status_out, void* stream);
+
+// ---- hdb_sort.hip, hdb_rows.hip ----
+int hdb_sort_temp_bytes(int64_t n, size_t* bytes);
+int hdb_launch_full_sort(const float* scores, int64_t n, int64_t k, int64_t row_base, uint32_t* work, void* temp, size_t temp_bytes,
+                         int64_t* idx_out, float* score_out, void* stream);
+int hdb_launch_gather_rows(const void* V, const int64_t* rows, int64_t m, int row_bytes, void* out, const float* inv_in,
+                           const float* sq_in, float* inv_out, float* sq_out, int* nan_flag, void* stream);
+
+// ---- hdb_mfma.hip: the matrix-core scan and what it can take ----
+int hdb_mfma_supported(int dtype, int d, int metric);
+int hdb_mfma_tile_rows(int dtype, int d);
+int hdb_mfma_batch_capacity(int dtype, int d);
+int hdb_mfma_anyd_pad(int dtype, int d);
+int hdb_mfma_f32_split_min_q(int d);
+int hdb_mfma_f32_split_max_q(int d);
+size_t hdb_mfma_batch_ctl_bytes(int wgs);
+int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q16, const float* sqnorm,
+                         const float* qsq, const float* qscl, int max_blocks, int variant, void* stream, const BatchArgs* f);
+int hdb_launch_q_to_f16(const float* Q, int nq, int d, void* q16, float* qscl, void* stream);
+int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
+                              const float* Q, const float* qsq, int q0, const float* bias, void* stream);
+// ... its shards (hdb_mfma_<geometry>.hip)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_d384);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_narrow);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_mid);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_1k);
+int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
+                                  const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
+int hdb_mfma_qt2_supported(int d);
+int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
+                                 const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
+int hdb_launch_mfma_scan_f32(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                             const float* qsq, int blocks, void* stream, const BatchArgs* f);
+int hdb_launch_mfma_scan_f32_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                  const float* qsq, int blocks, void* stream, const BatchArgs* f);
+int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                              const float* qsq, int blocks, void* stream, const BatchArgs* f);
+int hdb_launch_mfma_scan_f32s_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                   const float* qsq, int blocks, void* stream, const BatchArgs* f);
+int hdb_mfma_bf16_tile_rows(int d);
+int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                              const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_bf16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                   const float* qsq, int blocks, void* stream);
+int hdb_mfma_ksplit_slices(int dtype, int d);
+int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
+                           const float* qsq, const float* qscl, int blocks, void* stream);
+int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                const float* qsq, int blocks, void* stream);
+HDB_ANYD_DECL(hdb_launch_mfma_anyd_a); HDB_ANYD_DECL(hdb_launch_mfma_anyd_b);       // fp16 rows
+HDB_ANYD_DECL(hdb_launch_mfma_anyd_c); HDB_ANYD_DECL(hdb_launch_mfma_anyd_d);       // float32 rows
+HDB_ANYD_DECL(hdb_launch_mfma_anyd_e); HDB_ANYD_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts
+
+// ---- the single launches: hdb_mfma_fused*.hip, hdb_bits_fused.hip; hdb_l1_tile.hip ----
+int hdb_mfma_fused_supported(int dtype, int d, int metric, int nq, uint32_t kk);
+int hdb_mfma_fused_local_tiles(int dtype, int d, int metric, int nq);
+size_t hdb_mfma_fused_ctl_bytes(void);
+int hdb_launch_mfma_fused(const ScanArgs* args, int dtype, const FusedArgs* fa, int max_blocks, void* stream);
+int hdb_launch_mfma_fused_wide(const ScanArgs* args, const FusedArgs* fa, int blocks, void* stream);
+int hdb_bits_fused_supported(int metric, int nq, int W, uint32_t kk);
+int hdb_launch_bits_fused(const BitsArgs* args, int jaccard, int max_blocks, void* stream);
+int hdb_l1_tile_supported(int dtype, int d);
+int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
+
+// ---- hdb_quant.hip: the int8 shadow and its 5-bit plane ----
+int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype, int P, int8_t* codes, float* aux, int* nan_flag, double gamma,
+                          void* stream);
+int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t* rows, int64_t m, int P, int8_t* codes_out,
+                            float* aux_out, void* stream);
+int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt, void* stream);
+int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
+                             int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
+int hdb_quant_plane_units(int P);
+int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
+                                float* rec, void* stream);
+int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream);
+int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks);
+int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
+int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
+int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
+                             const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
+                             const uint32_t* cnt, uint32_t cap, void* stream);
+int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
+                             const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv, float* gbias,
+                             void* stream);
+int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
+                              int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
+                              const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
+                              void* stream);
+
+// ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
+int hdb_qb_supported(int d);
+int hdb_qb_scan_blocks(int64_t ntiles, int nq, int max_blocks);
+int64_t hdb_qb_slots(int blocks, int nq);
+int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
+int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);
+int hdb_launch_qb_rescore(const void* V, int d, const void* q16, const float* qscl, const float* qinv, const float* inv_norm,
+                          const float* bias, const uint8_t* mask, int metric, unsigned long long* cand, const uint32_t* cnt,
+                          uint32_t cap, int nq, void* stream);
+}

@@ -80,15 +80,8 @@ __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long l
 // fp16: 16x16x32 MFMAs, 128 queries per pass (d <= 640 with more than 128 queries: two query tiles per wave, 256 per pass).
 // fp32: 16x16x4 MFMAs, 128 queries per pass; the matrix pipe (157 TFLOP/s) binds from ~16 queries on, so the VALU scan
 // keeps the calls of up to 4 queries (one pass at HBM speed) and this path takes the batches.
-extern "C" int hdb_mfma_ksplit_slices(int dtype, int d);
-extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                      const float* qsq, const float* qscl, int blocks, void* stream);
-
 // bfloat16 rows (hdb_mfma_bf16.hip): d = 128, 256, 384 and 512 -- the query fragments of 16 queries take 48, 96, 144 and 192
 // registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted
-extern "C" int hdb_mfma_bf16_tile_rows(int d);
-extern "C" int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                         const float* qsq, int blocks, void* stream);
 
 static int mfma_exact_tile_rows(int dtype, int d) {
     if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
@@ -114,11 +107,6 @@ extern "C" int hdb_mfma_anyd_pad(int dtype, int d) {
     return 0;
 }
 
-#define HDB_ANYD_DECL(name) extern "C" int name(const ScanArgs* args, int dpad, int mode, int nq_launch, const void* q, const float* sqnorm, \
-                                              const float* qsq, const float* qscl, int blocks, void* stream)
-HDB_ANYD_DECL(hdb_launch_mfma_anyd_a); HDB_ANYD_DECL(hdb_launch_mfma_anyd_b); HDB_ANYD_DECL(hdb_launch_mfma_anyd_c); HDB_ANYD_DECL(hdb_launch_mfma_anyd_d);
-HDB_ANYD_DECL(hdb_launch_mfma_anyd_e); HDB_ANYD_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts
-
 extern "C" int hdb_mfma_tile_rows(int dtype, int d) {
     const int pad = hdb_mfma_anyd_pad(dtype, d);
     return mfma_exact_tile_rows(dtype, pad ? pad : d);
@@ -143,19 +131,6 @@ extern "C" int hdb_mfma_supported(int dtype, int d, int metric) {
 // for N=10M, Q=256), 32 = 32x32x16 with one query tile per wave (kept for A/B measurements).
 // (per index: hdb_set_option(ix, "mfma_variant", 16 | 32), passed down as `variant`)
 
-#define HDB_GEOM_DECL(name) extern "C" int name(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm, \
-                                              const float* qsq, const float* qscl, int blocks, int variant, void* stream, const BatchArgs* f)
-HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_d384);       // hdb_mfma_d384.hip
-HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_narrow);     // hdb_mfma_narrow.hip
-HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_mid);        // hdb_mfma_mid.hip
-HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_1k);         // hdb_mfma_1k.hip
-extern "C" int hdb_mfma_qt2_supported(int d);
-extern "C" int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                            const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
-extern "C" int hdb_launch_mfma_scan_f32(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                        const float* qsq, int blocks, void* stream, const BatchArgs* f);
-extern "C" int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                         const float* qsq, int blocks, void* stream, const BatchArgs* f);
 // float32 widths whose scan also exists in bf16 parts (hdb_mfma_f32s.hip) -> the number of queries of a CALL from which that
 // flavour is used (0: no such flavour; the API decides per call, ScanArgs::f32_split).  d <= 384: measured from 16 queries up, never
 // slower than the float32 MFMAs and 1.5-1.7x faster from 48 (profiles/r4_f32_bf16_parts.txt); d = 512 / 768: one wave cannot hold the
@@ -171,8 +146,6 @@ extern "C" int hdb_mfma_f32_split_min_q(int d) {
     const int g = (d == 128 || d == 256 || d == 384 || d == 512 || d == 768) ? d : hdb_mfma_anyd_pad(HDB_F32, d);
     return (g == 128 || g == 256 || g == 384) ? 9 : (g == 512 || g == 768) ? 1 : 0;
 }
-extern "C" int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                             const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
 
 // a.ntiles / a.tile_stride are in units of hdb_mfma_tile_rows(dtype, d) rows here.  q: the query fragments' source --
 // scaled fp16 copies (+ qscl) for fp16 matrices, the float32 queries themselves (qscl = nullptr) for fp32 ones.

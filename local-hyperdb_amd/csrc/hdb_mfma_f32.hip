@@ -3,9 +3,6 @@
 // hyperdb.py:51) keep the 1e-5 parity contract while up to 128 queries ride on one pass over V instead of 4.
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f32_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                             const float* qsq, int blocks, void* stream, const BatchArgs* f);
-
 extern "C" int hdb_launch_mfma_scan_f32(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                         const float* qsq, int blocks, void* stream, const BatchArgs* f) {
     const ScanArgs& a = *args;

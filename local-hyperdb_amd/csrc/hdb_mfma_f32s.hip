@@ -7,9 +7,6 @@
 // (translation units of their own so that the instantiations compile in parallel).
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f32s_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                              const float* qsq, int blocks, void* stream, const BatchArgs* f);
-
 extern "C" int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                          const float* qsq, int blocks, void* stream, const BatchArgs* f) {
     const ScanArgs& a = *args;

@@ -2,9 +2,6 @@
 // hdb_mfma.hip: a whole hdb_topk call of 1..4 dot / cosine / pearson queries (one euclidean query) in ONE kernel.
 #include "hdb_mfma_fused.h"
 
-extern "C" int hdb_mfma_tile_rows(int dtype, int d);
-extern "C" int hdb_launch_mfma_fused_wide(const ScanArgs* args, const FusedArgs* f, int blocks, void* stream);
-
 extern "C" int hdb_mfma_fused_supported(int dtype, int d, int metric, int nq, uint32_t kk) {
     // fp16: every width the batched scan takes (multiples of 128 up to 1536); beyond d = 768 the query fragments (d/8
     // registers) leave no room for the selectors' state: they stay in LDS, up to 2 queries (hdb_mfma_fused_wide.hip)

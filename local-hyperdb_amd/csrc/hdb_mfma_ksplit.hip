@@ -21,8 +21,6 @@ static KsGeom ks_geom(int dtype, int d) {
     return {0, 0};
 }
 extern "C" int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtype, d).slices; }
-extern "C" int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                           const float* qsq, int blocks, void* stream);      // hdb_mfma_ksplit_s.hip
 
 // args->ks_partial_out: [nq_launch][ks_ld] float32 scratch of the caller (MODE 0 passes may alias it with args->scores: the last
 // slice overwrites the sums with the scores, element by element, by the lane that read them)
