@@ -1,6 +1,11 @@
 // hdb_api.hip -- the C ABI of include/hyperdb_hip.h: handle, workspace and the top-k pipeline.
 //
-// Pipeline of hdb_topk for a chunk of queries (everything enqueued on the caller's stream):
+// hdb_topk = validate, plan, execute (topk_impl).  Which path a call takes is decided in ONE place, plan_topk (hdb_plan.h), a pure
+// function that sees plain facts and no hdb_index; its TopkPlan carries everything the executors here consume and the statistics of
+// the call (ix->st = plan.stats, the only place they are written).  One executor per path: quant_topk, quant_batch_topk,
+// run_fused, run_bits1, run_batch1, run_full_sort, run_pipeline -- launches, workspace layouts and ensure_* calls, no rule.
+//
+// The multi-kernel pipeline (run_pipeline) for a chunk of queries (everything enqueued on the caller's stream):
 //   n <= CAP            : thr = -inf -> scan(filter) -> finalize                (every row is a candidate)
 //   otherwise           : scan(scores) over a strided row sample
 //                         -> 4 radix-histogram passes -> thr[q] = m-th largest sample score
@@ -12,6 +17,7 @@
 #include "hdb_common.h"
 #include "hdb_quant.h"
 #include "hdb_ws.h"
+#include "hdb_plan.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
 #include <cmath>
@@ -93,54 +99,13 @@ struct hdb_index {
     // scratch (owned)
     char* ws = nullptr;
     size_t ws_bytes = 0;
-    // options
-    int64_t max_blocks = 0;           // 0 = automatic (row scan: 2-4 workgroups per CU, see hdb_launch_scan)
-    int64_t force_exact = 0;
-    int64_t sample_target = 0;        // 0 = automatic
-    int64_t mfma_min_q = 1;
-    int64_t use_mfma = 1;
-    int64_t exact_bytes = (int64_t)1 << 30;
-    int64_t bits_fused = 1;           // hamming / jaccard: try the sampled-threshold path first (exact path when it fails)
-    int64_t bits_local = 1;           // ... its single launch without row sample and exchange: every workgroup its own threshold (hdb_bits_fused.hip, round 4)
-    // knobs of the dispatch: -1 = the measured rule (tools/sweep_dispatch.py, profiles/r3_dispatch_few_queries.txt), else a fixed limit
-    int64_t fused_max_q = -1;         // hdb_mfma_fused_kernel takes calls of up to this many queries
-    int64_t f32_min_q = -1;           // float32 matrices: the matrix-core scan from this many queries on
-    int64_t f32_split = 1;            // ... as bf16 parts (hdb_mfma_f32s.hip) where that flavour exists, the matrix is finite and the call has at least
-    int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
+    hdb_options opt;                  // hdb_set_option (hdb_plan.h)
     int flags_host = -1;              // host copy of *nan_flag (1 = a NaN row, 2 = a row with an infinite sum of squares); -1 = not fetched since the last build
-    int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
-    int64_t host_direct = 1;          // hdb_topk_host: kernels write a pinned host record themselves (no D2H copy)
-    int64_t dyn_tiles = 1;            // MFMA filter pass: hand tiles out from a counter (0: static split)
-    int64_t dyn_min_mb = 16;          // ... for passes of at least this many MiB of V per workgroup
-    int64_t dyn_heavy = 0;            // ... also when all eight waves multiply (measured: 1.3-5 % slower at 256 queries, profiles/r3_q256_clock.json)
-    int64_t host_poll = 1;            // hdb_topk_host + single-launch pipeline + pinned record: poll the status words instead of the stream
-    int64_t use_fused = 1;            // 1-4 dot / cosine queries on an fp16 matrix: the whole call in ONE kernel (hdb_mfma_fused.h)
-    int64_t use_local = 1;            // ... short matrices: its local flavour (no row sample, no exchange; every workgroup its own threshold)
-    int64_t local_m = 0;              // ... rows every workgroup emits at least (0 = automatic: ~3072 / workgroups, 8 .. 32)
-    int64_t local_max_tiles = 4;      // ... while a workgroup has at most this many tiles (the parking area holds 16)
-    int64_t local_small = 0;          // ... 1: also for matrices of up to 8192 rows (measured slower than the three launches)
-    int64_t local_max_q = 1;          // ... for calls of up to this many queries (two to four: the batched single launch is faster -- 36 vs 45 us at 20k rows, profiles/r4_latency_map.txt)
-    int64_t use_l1_tile = 1;          // manhattan: dense passes through the LDS-staged tile kernel (hdb_l1_tile.hip)
-    int64_t l1_packed = 1;            // ... fp16 rows and fp16-valued queries: packed fp16 differences (0: always float32, for A/B runs)
-    int64_t use_batch1 = 1;           // 5+ queries (euclidean: 1+) on the matrix cores, k <= 128: the whole call in ONE launch per <= 256 queries (needs use_fused)
-    int64_t fused_timeout_us = 2000;  // bound of every in-kernel spin of those kernels
-    int64_t finalize_threads = 1024;  // workgroup size of hdb_finalize_kernel (256 | 512 | 1024)
-    int64_t mfma_variant = 16;        // MFMA shape of the d=384 256-query pass (16 | 32)
-    int64_t use_quant = 1;            // 0: never the int8 shadow, even where one exists
-    int64_t quant_min_n = -1;         // ... from this many rows on (-1: the measured rule, quant_min_rows)
-    int64_t quant_max_k = 128;        // ... for k up to this (<= 128)
-    int64_t auto_quant = 1;           // fp16 matrix, 1-4 dot / cosine queries on the matrix cores: build the shadow on the first eligible call of a large index
-    int64_t quant_batch_min_n = -1;   // ... batches of 5+ queries: from this many rows on (-1: the measured rule, quant_batch_rule)
-    int64_t quant_batch_kernel = 1;   // ... their filter pass: 1 = int8 matrix cores (hdb_quant_mfma.hip), 0 = the v_dot4 scan, four queries per pass
-    int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
-    int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
-    int64_t plane_cap_rows = 0;       // ... survivor list capacity in rows (0: n / 8; tests)
-    int64_t st_quant = 0;             // the last hdb_topk call took the int8 shadow
-    int64_t st_plane = 0;             // ... behind the 5-bit plane
-    const uint32_t* qb_cnt = nullptr; // ... as a batch: the list counters of its last chunk (in the workspace) and their number
+    // stats of the last hdb_topk call: the plan's (topk_impl), and whether hdb_topk_host wrote the caller's record directly
+    TopkStats st;
+    int64_t st_host_direct = 0;
+    const uint32_t* qb_cnt = nullptr; // a batch through the shadow: the list counters of its last chunk (in the workspace) and their number
     int qb_cnt_n = 0;
-    // stats of the last hdb_topk call
-    int64_t st_sample_rows = 0, st_sample_m = 0, st_path = 0, st_chunks = 0, st_mfma = 0, st_host_direct = 0, st_fused = 0, st_local = 0, st_f32s = 0;
     // host-side timing of hdb_topk_host (always on: four clock reads per call), cumulative since "host_timing_reset":
     // entry -> launch, the launch call itself, launch -> record complete (poll / stream wait), calls
     int64_t ht_pre_ns = 0, ht_launch_ns = 0, ht_wait_ns = 0, ht_calls = 0;
@@ -221,11 +186,7 @@ static void quant_free(hdb_index* ix) {
     ix->qcodes = nullptr; ix->qaux = nullptr; ix->q_rows = 0;
     plane_free(ix);
 }
-// The 5-bit plane of the shadow (hdb_quant.hip): 20 bytes per 32-element unit and a 16-byte record per row, for rows of up to 512
-// elements (the widths the plane path takes).
-static bool plane_possible(const hdb_index* ix) { return ix->d <= 512; }
-// an index whose caller switched the path off (use_plane = 0) before the shadow was built does not pay for a plane
-static bool plane_wanted(const hdb_index* ix) { return plane_possible(ix) && ix->use_plane; }
+// bytes of the 5-bit plane per row: 20 per 32-element unit and a 16-byte record (plane_possible, hdb_plan.h: rows of up to 512 elements)
 static size_t plane_row_bytes(int P) { return (size_t)hdb_quant_plane_units(P) * 20 + 16; }
 static bool plane_alloc(hdb_index* ix, int64_t rows, uint8_t** nib, uint32_t** bit, float** rec) {
     const size_t U = (size_t)hdb_quant_plane_units(ix->qP);
@@ -243,8 +204,8 @@ static bool plane_alloc(hdb_index* ix, int64_t rows, uint8_t** nib, uint32_t** b
 // have the shadow's capacity (q_rows >= n rows; pass 1 loads the rows below n only); a reallocated shadow has dropped
 // them (quant_free), and every row is derived again.  No memory: the index goes on without a plane.
 static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
-    if (!plane_possible(ix) || ix->plane_declined) return HDB_OK;
-    if (!ix->pnib && !plane_wanted(ix)) return HDB_OK;
+    if (!plane_possible(ix->d) || ix->plane_declined) return HDB_OK;
+    if (!ix->pnib && !plane_wanted(ix->d, ix->opt)) return HDB_OK;
     if (!ix->pnib) {
         // the automatic build's floor holds for every allocation of the plane (a shadow that grew on extend included): 1 GiB stays free
         size_t free_b = 0, total_b = 0;
@@ -293,7 +254,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
         quant_free(ix);
         ix->qmode = HDB_QUANT_NONE;
         ix->qauto = false;
-        ix->auto_quant = 0;                            // dropped on request: the index does not build one for itself again
+        ix->opt.auto_quant = 0;                            // dropped on request: the index does not build one for itself again
         return HDB_OK;
     }
     if (ix->dtype == HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
@@ -323,8 +284,8 @@ static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
     const size_t ws_grow = ws_need > ix->ws_bytes ? ws_need + (ws_need >> 2) + ((size_t)1 << 20) : 0;
     if (free_b < shadow + ws_grow + ((size_t)1 << 30)) { ix->qauto_declined = true; return false; }
-    const size_t plane = plane_possible(ix) ? (size_t)(ix->n + 64) * plane_row_bytes(P) : 0;
-    ix->plane_declined = plane_wanted(ix) && free_b < shadow + plane + ws_grow + ((size_t)1 << 30);
+    const size_t plane = plane_possible(ix->d) ? (size_t)(ix->n + 64) * plane_row_bytes(P) : 0;
+    ix->plane_declined = plane_wanted(ix->d, ix->opt) && free_b < shadow + plane + ws_grow + ((size_t)1 << 30);
     // (no memory for the words: declined; a failed memset is not this function's to report, the launches behind it do)
     if (qstat_alloc(ix, st) != hipSuccess && !ix->qstat) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
     ix->qP = P;
@@ -523,45 +484,45 @@ extern "C" int hdb_index_set_row_mask(hdb_index* ix, const uint8_t* dev_mask) {
 
 extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(HDB_ERR_ARG, "hdb_set_option: null argument");
-    if (!strcmp(name, "max_blocks")) ix->max_blocks = value;
-    else if (!strcmp(name, "force_exact")) ix->force_exact = value;
-    else if (!strcmp(name, "sample_target")) ix->sample_target = value;
-    else if (!strcmp(name, "mfma_min_q")) ix->mfma_min_q = value;
-    else if (!strcmp(name, "use_mfma")) ix->use_mfma = value;
-    else if (!strcmp(name, "exact_bytes")) ix->exact_bytes = std::max<int64_t>(1 << 20, value);
-    else if (!strcmp(name, "finalize_threads")) { if (value == 256 || value == 512 || value == 1024) ix->finalize_threads = value; }
-    else if (!strcmp(name, "mfma_variant")) { if (value == 16 || value == 32 || value == 64) ix->mfma_variant = value; }
-    else if (!strcmp(name, "host_direct")) ix->host_direct = value;
-    else if (!strcmp(name, "use_fused")) ix->use_fused = value;
-    else if (!strcmp(name, "use_batch1")) ix->use_batch1 = value;
-    else if (!strcmp(name, "use_local")) ix->use_local = value;
-    else if (!strcmp(name, "local_max_q")) ix->local_max_q = value;
-    else if (!strcmp(name, "local_max_tiles")) ix->local_max_tiles = std::max<int64_t>(1, value);
-    else if (!strcmp(name, "local_small")) ix->local_small = value;
-    else if (!strcmp(name, "local_m")) ix->local_m = std::max<int64_t>(0, std::min<int64_t>(value, 64));
-    else if (!strcmp(name, "use_l1_tile")) ix->use_l1_tile = value;
-    else if (!strcmp(name, "l1_packed")) ix->l1_packed = value;
-    else if (!strcmp(name, "host_poll")) ix->host_poll = value;
-    else if (!strcmp(name, "dyn_tiles")) ix->dyn_tiles = value;
-    else if (!strcmp(name, "dyn_min_mb")) ix->dyn_min_mb = std::max<int64_t>(0, value);
-    else if (!strcmp(name, "dyn_heavy")) ix->dyn_heavy = value;
-    else if (!strcmp(name, "fused_timeout_us")) ix->fused_timeout_us = std::max<int64_t>(1, value);
-    else if (!strcmp(name, "bits_fused")) ix->bits_fused = value;
-    else if (!strcmp(name, "bits_local")) ix->bits_local = value;
-    else if (!strcmp(name, "fused_max_q")) ix->fused_max_q = value;
-    else if (!strcmp(name, "f32_min_q")) ix->f32_min_q = value;
-    else if (!strcmp(name, "f32_split")) ix->f32_split = value;
-    else if (!strcmp(name, "f32_split_min_q")) ix->f32_split_min_q = value;
-    else if (!strcmp(name, "bits_max_q")) ix->bits_max_q = value;
-    else if (!strcmp(name, "use_quant")) ix->use_quant = value;
-    else if (!strcmp(name, "quant_min_n")) ix->quant_min_n = value;
-    else if (!strcmp(name, "auto_quant")) ix->auto_quant = value;
-    else if (!strcmp(name, "quant_batch_min_n")) ix->quant_batch_min_n = value;
-    else if (!strcmp(name, "quant_batch_kernel")) ix->quant_batch_kernel = value ? 1 : 0;
-    else if (!strcmp(name, "quant_max_k")) ix->quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
-    else if (!strcmp(name, "use_plane")) ix->use_plane = value;
-    else if (!strcmp(name, "plane_min_n")) ix->plane_min_n = value;
-    else if (!strcmp(name, "plane_cap_rows")) ix->plane_cap_rows = std::max<int64_t>(0, value);
+    if (!strcmp(name, "max_blocks")) ix->opt.max_blocks = value;
+    else if (!strcmp(name, "force_exact")) ix->opt.force_exact = value;
+    else if (!strcmp(name, "sample_target")) ix->opt.sample_target = value;
+    else if (!strcmp(name, "mfma_min_q")) ix->opt.mfma_min_q = value;
+    else if (!strcmp(name, "use_mfma")) ix->opt.use_mfma = value;
+    else if (!strcmp(name, "exact_bytes")) ix->opt.exact_bytes = std::max<int64_t>(1 << 20, value);
+    else if (!strcmp(name, "finalize_threads")) { if (value == 256 || value == 512 || value == 1024) ix->opt.finalize_threads = value; }
+    else if (!strcmp(name, "mfma_variant")) { if (value == 16 || value == 32 || value == 64) ix->opt.mfma_variant = value; }
+    else if (!strcmp(name, "host_direct")) ix->opt.host_direct = value;
+    else if (!strcmp(name, "use_fused")) ix->opt.use_fused = value;
+    else if (!strcmp(name, "use_batch1")) ix->opt.use_batch1 = value;
+    else if (!strcmp(name, "use_local")) ix->opt.use_local = value;
+    else if (!strcmp(name, "local_max_q")) ix->opt.local_max_q = value;
+    else if (!strcmp(name, "local_max_tiles")) ix->opt.local_max_tiles = std::max<int64_t>(1, value);
+    else if (!strcmp(name, "local_small")) ix->opt.local_small = value;
+    else if (!strcmp(name, "local_m")) ix->opt.local_m = std::max<int64_t>(0, std::min<int64_t>(value, 64));
+    else if (!strcmp(name, "use_l1_tile")) ix->opt.use_l1_tile = value;
+    else if (!strcmp(name, "l1_packed")) ix->opt.l1_packed = value;
+    else if (!strcmp(name, "host_poll")) ix->opt.host_poll = value;
+    else if (!strcmp(name, "dyn_tiles")) ix->opt.dyn_tiles = value;
+    else if (!strcmp(name, "dyn_min_mb")) ix->opt.dyn_min_mb = std::max<int64_t>(0, value);
+    else if (!strcmp(name, "dyn_heavy")) ix->opt.dyn_heavy = value;
+    else if (!strcmp(name, "fused_timeout_us")) ix->opt.fused_timeout_us = std::max<int64_t>(1, value);
+    else if (!strcmp(name, "bits_fused")) ix->opt.bits_fused = value;
+    else if (!strcmp(name, "bits_local")) ix->opt.bits_local = value;
+    else if (!strcmp(name, "fused_max_q")) ix->opt.fused_max_q = value;
+    else if (!strcmp(name, "f32_min_q")) ix->opt.f32_min_q = value;
+    else if (!strcmp(name, "f32_split")) ix->opt.f32_split = value;
+    else if (!strcmp(name, "f32_split_min_q")) ix->opt.f32_split_min_q = value;
+    else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
+    else if (!strcmp(name, "use_quant")) ix->opt.use_quant = value;
+    else if (!strcmp(name, "quant_min_n")) ix->opt.quant_min_n = value;
+    else if (!strcmp(name, "auto_quant")) ix->opt.auto_quant = value;
+    else if (!strcmp(name, "quant_batch_min_n")) ix->opt.quant_batch_min_n = value;
+    else if (!strcmp(name, "quant_batch_kernel")) ix->opt.quant_batch_kernel = value ? 1 : 0;
+    else if (!strcmp(name, "quant_max_k")) ix->opt.quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
+    else if (!strcmp(name, "use_plane")) ix->opt.use_plane = value;
+    else if (!strcmp(name, "plane_min_n")) ix->opt.plane_min_n = value;
+    else if (!strcmp(name, "plane_cap_rows")) ix->opt.plane_cap_rows = std::max<int64_t>(0, value);
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -570,20 +531,20 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
 
 extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     if (!ix || !name || !value) return fail(HDB_ERR_ARG, "hdb_get_stat: null argument");
-    if (!strcmp(name, "sample_rows")) *value = ix->st_sample_rows;
-    else if (!strcmp(name, "sample_m")) *value = ix->st_sample_m;
-    else if (!strcmp(name, "path")) *value = ix->st_path;
-    else if (!strcmp(name, "chunks")) *value = ix->st_chunks;
-    else if (!strcmp(name, "mfma")) *value = ix->st_mfma;
-    else if (!strcmp(name, "f32_split")) *value = ix->st_f32s;
+    if (!strcmp(name, "sample_rows")) *value = ix->st.sample_rows;
+    else if (!strcmp(name, "sample_m")) *value = ix->st.sample_m;
+    else if (!strcmp(name, "path")) *value = ix->st.path;
+    else if (!strcmp(name, "chunks")) *value = ix->st.chunks;
+    else if (!strcmp(name, "mfma")) *value = ix->st.mfma;
+    else if (!strcmp(name, "f32_split")) *value = ix->st.f32s;
     else if (!strcmp(name, "host_direct")) *value = ix->st_host_direct;
-    else if (!strcmp(name, "fused")) *value = ix->st_fused;
-    else if (!strcmp(name, "local")) *value = ix->st_local;
+    else if (!strcmp(name, "fused")) *value = ix->st.fused;
+    else if (!strcmp(name, "local")) *value = ix->st.local;
     else if (!strcmp(name, "cand_cap")) *value = HDB_CAND_CAP;
-    else if (!strcmp(name, "quant")) *value = ix->st_quant;
+    else if (!strcmp(name, "quant")) *value = ix->st.quant;
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
-    else if (!strcmp(name, "plane")) *value = ix->st_plane;
+    else if (!strcmp(name, "plane")) *value = ix->st.plane;
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
@@ -594,11 +555,11 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
             HIP_TRY(hipDeviceSynchronize());
             HIP_TRY(hipMemcpy(h, ix->qstat, sizeof(h), hipMemcpyDeviceToHost));
         }
-        *value = name[6] == 's' ? (ix->st_plane ? (int64_t)(uint32_t)h[1] : 0) : (int64_t)(uint32_t)h[2];
+        *value = name[6] == 's' ? (ix->st.plane ? (int64_t)(uint32_t)h[1] : 0) : (int64_t)(uint32_t)h[2];
     }
     else if (!strcmp(name, "quant_cands")) {          // synchronises the device
         int h = 0;
-        if (ix->st_quant && ix->qstat) {
+        if (ix->st.quant && ix->qstat) {
             HIP_TRY(hipSetDevice(ix->device));
             HIP_TRY(hipDeviceSynchronize());
             HIP_TRY(hipMemcpy(&h, ix->qstat, sizeof(int), hipMemcpyDeviceToHost));
@@ -607,7 +568,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     }
     else if (!strcmp(name, "quant_cands_min") || !strcmp(name, "quant_cands_median")) {     // batches: over the lists of the last chunk; synchronises
         int64_t v = 0;
-        if (ix->st_quant && ix->qb_cnt && ix->qb_cnt_n > 0) {
+        if (ix->st.quant && ix->qb_cnt && ix->qb_cnt_n > 0) {
             HIP_TRY(hipSetDevice(ix->device));
             HIP_TRY(hipDeviceSynchronize());
             std::vector<uint32_t> raw((size_t)ix->qb_cnt_n * HDB_CNT_STRIDE), c((size_t)ix->qb_cnt_n);
@@ -656,8 +617,6 @@ static void prof_end(hdb_index* ix, hipStream_t st) {
 }
 
 static bool metric_ok(int metric) { return metric >= HDB_DOT && metric <= HDB_EUCLIDEAN_DIST; }
-#define HDB_FUSED_MAXQ_RULE 4
-static bool is_bits_metric(int metric) { return metric == HDB_HAMMING || metric == HDB_JACCARD; }
 
 static int ensure_pscale(hdb_index* ix, hipStream_t st) {
     if (ix->pscale_valid) return HDB_OK;
@@ -711,25 +670,25 @@ static void base_args(const hdb_index* ix, ScanArgs& a, const void* Q, int metri
     a.inv_norm = ix->inv_norm; a.mask = ix->mask;
     a.tile_stride = 1; a.ntiles = (ix->n + 15) / 16;
     a.cap = HDB_CAND_CAP;
-    a.dyn_min_bytes = ix->dyn_min_mb << 20; a.dyn_heavy = (int32_t)ix->dyn_heavy;
+    a.dyn_min_bytes = ix->opt.dyn_min_mb << 20; a.dyn_heavy = (int32_t)ix->opt.dyn_heavy;
 }
 
 // One scan launch (VALU, hamming or MFMA flavour) for queries [a.q0, a.q0+cq).
 struct QueryBufs { const float* qinv; const float* qsq; const uint32_t* qbits; const void* q16; const float* qscl; };
-static int run_scan(hdb_index* ix, ScanArgs& a, int mode, int cq, const QueryBufs& qb, bool mfma, hipStream_t st) {
+static int run_scan(hdb_index* ix, ScanArgs& a, int mode, int cq, const QueryBufs& qb, bool l1tile, bool mfma, hipStream_t st) {
     a.qinv = qb.qinv;
     if (is_bits_metric(a.metric)) {
         LAUNCH_TRY(hdb_launch_hamming(&a, mode, cq, ix->bits, ix->bits_npad, ix->W, qb.qbits, st));
-    } else if (a.metric == HDB_MANHATTAN && ix->use_l1_tile && cq >= 2 && a.tile_stride == 1 && !a.mask && !a.raw && a.n > HDB_CAND_CAP &&
-               hdb_l1_tile_supported(ix->dtype, ix->d)) {
-        // dense manhattan passes: tiles staged once in LDS, queries in registers, 8-16 queries per pass (hdb_l1_tile.hip)
+    } else if (l1tile && cq >= 2 && a.tile_stride == 1) {
+        // dense manhattan passes of a call the plan gave to the tile kernel (TopkPlan::l1tile; the mask is folded into the bias):
+        // tiles staged once in LDS, queries in registers, 8-16 queries per pass (hdb_l1_tile.hip)
         // (the tile kernel has no use for ScanArgs::dyn_heavy: 77 there = "keep the float32 arithmetic", set_option l1_packed 0)
-        ScanArgs al = a; al.dyn_heavy = ix->l1_packed ? 0 : 77;
-        LAUNCH_TRY(hdb_launch_l1_tile(&al, ix->dtype, mode, cq, (int)ix->max_blocks, st));
+        ScanArgs al = a; al.dyn_heavy = ix->opt.l1_packed ? 0 : 77;
+        LAUNCH_TRY(hdb_launch_l1_tile(&al, ix->dtype, mode, cq, (int)ix->opt.max_blocks, st));
     } else if (mfma) {
-        LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, mode, cq, qb.q16, ix->sqnorm, qb.qsq, qb.qscl, (int)ix->max_blocks, (int)ix->mfma_variant, st, nullptr));
+        LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, mode, cq, qb.q16, ix->sqnorm, qb.qsq, qb.qscl, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, st, nullptr));
     } else {
-        LAUNCH_TRY(hdb_launch_scan(&a, ix->dtype, mode, cq, (int)ix->max_blocks, st));
+        LAUNCH_TRY(hdb_launch_scan(&a, ix->dtype, mode, cq, (int)ix->opt.max_blocks, st));
     }
     return HDB_OK;
 }
@@ -760,61 +719,34 @@ extern "C" int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* d
     a.raw = 1;                          // ... and return NaN where the reference does (pearson, jaccard)
     a.scores = dev_out; a.ld = ix->n;
     QueryBufs qb{qinv, qsq, qbits, nullptr, nullptr};
-    return run_scan(ix, a, 0, 1, qb, false, st);
+    return run_scan(ix, a, 0, 1, qb, false, false, st);
 }
 
-// Row sample for the threshold estimate: `tiles` tiles of `tile_rows` rows, evenly strided over V.
-// The m-th largest of the sampled scores is exceeded by about T rows of the full matrix (Gamma(m)
-// spread), T >= 8k..16k and <= CAP/2, so both "fewer than k pass" and "more than CAP pass" are
-// < 1e-9 events for exchangeable row orders; either one only costs the exact-path re-run.
-// coarse: the scores take few distinct values (bit metrics), so the rows at the threshold's own level all survive; aim lower.
-// Batches of 32+ queries aim at 1024 survivors per query instead of 2048: every survivor costs the filter's slow path
-// (d=384, 64 queries: 1.28 -> 1.20 ms per call; 256 queries: -1 %), the sample doubles to 0.8 % of the rows, and
-// P(fewer than k=100 pass) = P(Gamma(8) < 0.78) = 1.7e-6 per query, paid with one exact re-run of that query.
-static void sample_plan(const hdb_index* ix, uint32_t kk, int nq, int tile_rows, bool coarse, int64_t& tiles, int64_t& stride, uint32_t& m) {
-    int64_t T = ix->sample_target > 0 ? ix->sample_target : (kk <= 128 ? (nq >= 32 ? 1024 : 2048) : 4096);
-    if (coarse && ix->sample_target <= 0) T /= 2;
-    m = kk <= 128 ? 8u : (kk <= 512 ? 64u : 256u);
-    int64_t rows = (int64_t)((double)m * (double)ix->n / (double)T);
-    rows = std::max<int64_t>(rows, 16 * (int64_t)m);         // at least 16 m sample rows
-    tiles = (rows + tile_rows - 1) / tile_rows;
-    const int64_t all_tiles = ix->n / tile_rows;             // full tiles only: sample rows always exist
-    tiles = std::min(tiles, all_tiles);
-    stride = std::max<int64_t>(1, all_tiles / std::max<int64_t>(tiles, 1));
+// ---- hdb_topk: validate, plan (hdb_plan.h), execute -----------------------------------------------------------------------------
+// The arguments of one call, as the executors take them, and the index as the planner sees it.
+struct TopkArgs { const void* Q; int32_t nq, k; int metric; int64_t* idx; float* score; int32_t* status; hipStream_t st; };
+static TopkFacts topk_facts(const hdb_index* ix) {
+    return {ix->n, ix->d, ix->dtype, ix->qmode, ix->qauto, ix->qauto_declined, ix->pnib != nullptr, ix->plane_declined,
+            ix->mask != nullptr, ix->bias != nullptr, hdb_cu_count()};
 }
 
-// Smallest matrix that takes the int8 shadow when quant_min_n is -1 (measured): below it the extra launches
-// of the quantized pipeline cost more than the bytes it saves.
-static int64_t quant_min_rows(const hdb_index* ix) {
-    return ix->dtype == HDB_F16 ? 1250000 : 500000;
-}
-
-// ... and the smallest fp16 matrix that builds a shadow for itself (auto_quant; measured, profiles/auto_quant_time.txt, DESIGN.md
-// section 4.9).  It lies above the sizes at which the suite pins the default path's statistics (up to 1.6M rows).
-#define HDB_QUANT_AUTO_MIN_ROWS 2000000
-// Smallest matrix whose one-query calls go through the 5-bit plane when plane_min_n is -1: the smallest measured size from which the
-// plane column of profiles/quant_plane_time.txt beats the plane-off column by at least 5 % in both runs, at that size and every
-// larger one (2M: 1.10x / 1.09x, 10M: 1.29x / 1.30x).  It is also the smallest size that has an automatic shadow.
-#define HDB_PLANE_MIN_ROWS 2000000
-// capacity of the survivor list in rows: an eighth of the matrix (the plane keeps under 5 % of Gaussian rows), or what the tests ask for
-static uint32_t plane_list_cap(const hdb_index* ix, int64_t n) {
-    return (uint32_t)(ix->plane_cap_rows > 0 ? std::min<int64_t>(ix->plane_cap_rows, n) : std::max<int64_t>(n / 8, 16));
-}
-// Extents of the workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h), handed to f: the memory guard of the automatic build sizes
-// with them, the call lays out with them.  The score buffer takes the extent of the largest sample any k takes (quant_ld_max) -- the
-// call's own ld_s is only its leading dimension -- so calls that differ in k never regrow the workspace.  (P from d: the automatic
-// build asks before the index has a pitch.)
+// The workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h): the memory guard of the automatic build sizes with these extents,
+// the call lays out with them.  The score buffer takes the extent of the largest sample any k takes (quant_ld_max) -- the call's own
+// ld_s is only its leading dimension -- so calls that differ in k never regrow the workspace.  (P from d: the automatic build asks
+// before the index has a pitch.)  pl_cap: entries of the plane's survivor list (one query on an index that holds a plane).
 static int quant_pitch(const hdb_index* ix) { return (int)align_up((size_t)ix->d, 16); }
-template <typename F>
-static auto quant_ws_extents(const hdb_index* ix, int nq, bool mflavour, F f) {
-    const uint32_t pl_cap = (nq == 1 && ix->pnib) ? plane_list_cap(ix, ix->n) : 0;      // survivor list of the plane pass
-    return f(nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
+static size_t quant_ws_bytes(const hdb_index* ix, int nq, uint32_t pl_cap, bool mflavour) {
+    return ws_bytes_for<QuantWs>(nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
 }
-static size_t quant_ws_bytes(const hdb_index* ix, int nq, bool mflavour) {
-    return quant_ws_extents(ix, nq, mflavour, [](auto... ext) { return ws_bytes_for<QuantWs>(ext...); });
+static int quant_ws_lay(hdb_index* ix, QuantWs& w, int nq, uint32_t pl_cap, bool mflavour) {
+    return ws_lay(ix, w, nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
 }
-static int quant_ws_lay(hdb_index* ix, QuantWs& w, int nq, bool mflavour) {
-    return quant_ws_extents(ix, nq, mflavour, [&](auto... ext) { return ws_lay(ix, w, ext...); });
+// ... and of one chunk of a batch (QuantBatchWs)
+static size_t quant_batch_ws_bytes(const hdb_index* ix, int cq) {
+    return ws_bytes_for<QuantBatchWs>(cq, quant_pitch(ix), (int)ix->d, quant_batch_sample(ix->n).ld_s, quant_batch_wld());
+}
+static int quant_batch_ws_lay(hdb_index* ix, QuantBatchWs& w, int cq) {
+    return ws_lay(ix, w, cq, quant_pitch(ix), (int)ix->d, quant_batch_sample(ix->n).ld_s, quant_batch_wld());
 }
 // The shadow's counterpart of base_args: the index's side and the prepared queries; every pass sets its own tiles, outputs and lists.
 static void quant_base_args(const hdb_index* ix, QuantArgs& a, const int8_t* qcodes, const float* qaux, const float* qinv, int metric, int nq) {
@@ -836,6 +768,22 @@ static int quant_query_prep(hdb_index* ix, const float* Q, int nq, const QuantWs
     return HDB_OK;
 }
 
+// What a planned shadow path needs before it can run: the shadow itself (the automatic build, on the first eligible call) and
+// the plane (a shadow that was built without one -- use_plane was off then -- gets it on the first call that asks for the path).
+// Either may be declined for memory: the index remembers that, *declined is set and topk_impl plans once more on the new facts.
+static int shadow_prepare(hdb_index* ix, const TopkPlan& p, int nq, hipStream_t st, bool* declined) {
+    if (p.build_needed) {
+        const size_t ws_need = p.path == HDB_PATH_QUANT ? quant_ws_bytes(ix, nq, 0, true) : quant_batch_ws_bytes(ix, p.cq_max);
+        if (!quant_auto_build(ix, ws_need, st)) { *declined = true; return HDB_OK; }
+    }
+    if (p.plane_wanted && !ix->pnib) {
+        const int rc = plane_rows(ix, 0, ix->n, st);
+        if (rc) return rc;
+        *declined = ix->pnib == nullptr;
+    }
+    return HDB_OK;
+}
+
 // 1-4 dot / cosine / euclidean queries through the int8 shadow (hdb_quant.hip): quantized query prep, lower bounds on a strided row
 // sample, T_s = 16th largest of them, the pass over the shadow that keeps rows whose upper bound reaches T_s, exact rescoring of
 // those from the matrix, finalize with the floor T_s.  The sample aims at ~512 rows of the whole matrix with a lower bound above
@@ -843,36 +791,27 @@ static int quant_query_prep(hdb_index* ix, const float* Q, int nq, const QuantWs
 // mflavour (the automatic shadow of an fp16 index): the scores are the matrix cores' -- one launch prepares the queries (1/||q||,
 // the scaled fp16 copy, codes of the rounded query), the candidates are gathered into a compact matrix and scored by the MODE 0
 // launch of the matrix-core scan, the finalize packs those scores into the list before it selects.  Seven launches either way.
-static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
-                      float* dev_score, int32_t* dev_status, hipStream_t st, bool mflavour) {
+static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
+    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
+    const uint32_t kk = p.kk; const bool mflavour = p.mflavour, use_pl = p.plane_wanted;
     const int64_t n = ix->n;
     const uint32_t m = 16;
-    const QuantSample sp = quant_call_sample(n, ix->d, kk);
-    // (a shadow that was built without a plane -- use_plane was off then -- gets it on the first call that asks for the path)
-    const bool pl_call = nq == 1 && (metric == HDB_DOT || metric == HDB_COSINE) && plane_wanted(ix) &&
-                         n >= (ix->plane_min_n >= 0 ? ix->plane_min_n : (int64_t)HDB_PLANE_MIN_ROWS);
-    if (pl_call && !ix->pnib) { const int rcp = plane_rows(ix, 0, n, st); if (rcp) return rcp; }
-    const bool use_pl = pl_call && ix->pnib != nullptr;
+    const QuantSample sp = p.qs;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, nq, mflavour);
+    int rc = quant_ws_lay(ix, w, nq, (nq == 1 && ix->pnib) ? p.pl_cap : 0, mflavour);
     if (rc) return rc;
     // one dot / cosine query: pass 1 over the 5-bit plane, pass 2 (MODE 1 itself) over the rows it keeps (hdb_quant.hip)
-    const uint32_t pl_cap = plane_list_cap(ix, n);
+    const uint32_t pl_cap = p.pl_cap;
     uint32_t* pl_cnt = use_pl ? reinterpret_cast<uint32_t*>(ix->qstat) + 1 : nullptr;
     const size_t crow = (size_t)nq * HDB_CAND_CAP;
-    int nsub = 0;
-    if (mflavour) {
-        // the threshold folded into the two passes (QuantArgs::nsub) while the sample's grid has at least the 1024 subsets
-        // hdb_sample_thr_kernel works with; smaller samples keep that kernel
-        nsub = 4 * hdb_quant_scan_blocks(sp.s_tiles, (int)ix->max_blocks);
-        if (nsub < 1024 || nsub > HDB_QUANT_NSUB_MAX) nsub = 0;
-    }
+    const int nsub = p.nsub;
     rc = quant_query_prep(ix, (const float*)dev_Q, nq, w, mflavour, ix->qstat, nsub ? w.cnt : nullptr, pl_cnt, st);
     if (rc) return rc;
     QuantArgs a; quant_base_args(ix, a, w.qcodes, w.qaux, w.qinv, metric, nq);
     a.ntiles = sp.s_tiles; a.tile_stride = sp.s_stride; a.scores = w.sbuf; a.ld = sp.ld_s;
     a.wmax = w.wmax; a.nsub = nsub; a.thr_out = w.thr;
-    LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->max_blocks, st));
+    LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->opt.max_blocks, st));
     if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(w.sbuf, sp.s_rows, sp.ld_s, nq, m, w.thr, w.cnt, nullptr, st));
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
     a.thr = w.thr; a.cnt = w.cnt; a.cand = w.cand; a.cap = HDB_CAND_CAP;
@@ -881,11 +820,11 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
         // pass 1 takes the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for pass 2 and the finalize
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
         a.pl_list = w.pl_list; a.pl_cnt = pl_cnt; a.pl_cap = pl_cap;
-        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->max_blocks, st));
+        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->opt.max_blocks, st));
         a.nsub = 0; a.wmax = nullptr;
-        LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 1, (int)ix->max_blocks, st));
+        LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 1, (int)ix->opt.max_blocks, st));
     } else {
-        LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->max_blocks, st));
+        LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->opt.max_blocks, st));
     }
     prof_end(ix, st);
     if (mflavour) {
@@ -897,16 +836,13 @@ static int quant_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, u
         s.bias = has_bias ? w.gbias : nullptr; s.mask = nullptr; s.nq = nq;
         s.tile_stride = 1; s.ntiles = (int64_t)crow / hdb_mfma_tile_rows(ix->dtype, ix->d); s.cap = HDB_CAND_CAP;
         s.scores = w.gsc; s.ld = (int64_t)crow;
-        LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, w.q16, w.ginv, w.qsq, w.qscl, (int)ix->max_blocks, (int)ix->mfma_variant, st, nullptr));
+        LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, w.q16, w.ginv, w.qsq, w.qscl, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, st, nullptr));
     } else {
         LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, w.qinv, ix->bias, ix->mask,
                                             w.cand, w.cnt, HDB_CAND_CAP, st));
     }
     LAUNCH_TRY(hdb_launch_quant_finalize(w.cand, w.cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, w.qnan,
                                          w.qaux, w.thr, ix->qstat, mflavour ? w.cand : nullptr, w.gsc, (int64_t)crow, st));
-    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = mflavour ? 1 : 0; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
-    ix->st_plane = use_pl ? 1 : 0;
-    ix->st_sample_rows = sp.s_rows; ix->st_sample_m = m; ix->st_chunks = 1;
     return HDB_OK;
 }
 
@@ -919,7 +855,7 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, 1, true);
+    int rc = quant_ws_lay(ix, w, 1, plane_list_cap(ix->opt, ix->n), true);
     if (rc) return rc;
     rc = quant_query_prep(ix, dev_q, 1, w, ix->qauto, nullptr, nullptr, nullptr, st);
     if (rc) return rc;
@@ -927,52 +863,26 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     a.ntiles = (ix->n + 15) / 16; a.tile_stride = 1;
     a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
     a.dbg = dev_hi;
-    LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 2, (int)ix->max_blocks, st));
+    LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 2, (int)ix->opt.max_blocks, st));
     a.dbg = dev_hi5;
-    LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 1, (int)ix->max_blocks, st));
+    LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 1, (int)ix->opt.max_blocks, st));
     return HDB_OK;
 }
 
 // ---- batches of 5+ queries through the automatic shadow (hdb_quant_mfma.hip) ---------------------------------------------------
-// The measured rule of quant_batch_min_n = -1: the smallest matrix from which a batch of nq queries is at least 1.10x faster through
-// the shadow than through the fp16 single launch, 0 = never (profiles/quant_batch_time.txt, one box, interleaved, p50 in us, parent ->
-// shadow).  The filter kernel reads its row fragments straight from global memory, so a workgroup has one tile per wave in flight:
-// it wins while one query tile per wave keeps the pass near the shadow's bytes and loses once the waves share tiles.
-//   d = 384, 5-16 queries: 2M 269 -> 261 (1.03), 3M 373 -> 336 (1.11) / 430 -> 378 (1.14), 4M 1.16 / 1.13, 5M 1.18-1.19, 10M 1.18-1.21
-//   d = 384, 24 queries: 5M 674 -> 568 (1.19), 10M 1167 -> 1002 (1.17); 32 queries: 1.03 / 1.13, at 3M-4M 0.93 / 1.00; 48: 0.94 / 1.03
-//   d = 384, 64 / 128 / 256 queries at 10M: 1137 -> 1776 (0.64), 1342 -> 3485 (0.39), 2292 -> 6545 (0.35): excluded
-//   d = 512, 5 / 8 / 16 queries: 10M 1.21 / 1.18 / 1.11; 5M 1.10 / 1.09 / 0.99; 2M 0.98 and below
-//   d = 128: 0.78-0.91 at every size (the fp16 pass over 256-byte rows is short already); d = 256: not measured, so not admitted
-static int64_t quant_batch_rule(const hdb_index* ix, int nq) {
-    int64_t rows = 0;
-    if (ix->d == 384) rows = nq <= 16 ? 3000000 : nq <= 24 ? 5000000 : 0;
-    else if (ix->d == 512) rows = nq <= 16 ? 10000000 : 0;
-    return rows > 0 ? std::max<int64_t>(rows, HDB_QUANT_AUTO_MIN_ROWS) : 0;
-}
-// Extents of the workspace of one chunk of a batch (QuantBatchWs, hdb_ws.h), handed to f like quant_ws_extents; wld: the most slots
-// any launch leaves per query.
-static int64_t quant_batch_wld() { return (int64_t)align_up((size_t)hdb_qb_slots(512, 1), 4); }
-template <typename F>
-static auto quant_batch_ws_extents(const hdb_index* ix, int cq, F f) {
-    return f(cq, quant_pitch(ix), (int)ix->d, quant_batch_sample(ix->n).ld_s, quant_batch_wld());
-}
-static size_t quant_batch_ws_bytes(const hdb_index* ix, int cq) {
-    return quant_batch_ws_extents(ix, cq, [](auto... ext) { return ws_bytes_for<QuantBatchWs>(ext...); });
-}
-static int quant_batch_ws_lay(hdb_index* ix, QuantBatchWs& w, int cq) {
-    return quant_batch_ws_extents(ix, cq, [&](auto... ext) { return ws_lay(ix, w, ext...); });
-}
 // One call: chunks of up to 256 queries, each through query prep, sample pass, thresholds, filter pass, block-diagonal rescoring
 // and finalize.  Workspace per chunk: the lists (cq x 8192 x 8 bytes = 16 MiB at 256 queries), the slot maxima of the sample pass
 // (cq x 8192 floats at most) and the per-query words; no compact matrix and no nq x nq score block.
-static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, uint32_t kk, int metric, int64_t* dev_idx,
-                            float* dev_score, int32_t* dev_status, hipStream_t st) {
+static int quant_batch_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
+    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
+    const uint32_t kk = p.kk;
     const int64_t n = ix->n;
     const int P = ix->qP;
     const uint32_t m = HDB_QB_SAMPLE_M;
-    const QuantSample sp = quant_batch_sample(n);
+    const QuantSample sp = p.qs;
     const int64_t s_tiles = sp.s_tiles, s_stride = sp.s_stride, s_rows = sp.s_rows, ld_s = sp.ld_s;
-    const int cq_max = std::min<int>(nq, 256);
+    const int cq_max = p.cq_max;
     QuantBatchWs w;
     const int rc = quant_batch_ws_lay(ix, w, cq_max);
     if (rc) return rc;
@@ -980,23 +890,21 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
     float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
     int8_t* const qcodes = w.qcodes; float* const qaux = w.qaux; float* const thr = w.thr; uint32_t* const cnt = w.cnt;
     unsigned long long* const cand = w.cand; void* const q16 = w.q16; float* const wbuf = w.wbuf;
-    ix->st_chunks = 0;
     for (int q0 = 0; q0 < nq; q0 += cq_max) {
         const int cq = std::min(cq_max, nq - q0);
-        ix->st_chunks++;
         const float* Qc = (const float*)dev_Q + (size_t)q0 * ix->d;
         // (the stat word is reset by the first chunk only: quant_cands is the largest list of the CALL)
         LAUNCH_TRY(hdb_launch_quant_qprep_m(Qc, cq, ix->d, P, qinv, qsq, qnan, q16, qscl, qcodes, qaux, q0 == 0 ? ix->qstat : nullptr, cnt, nullptr, st));
         QuantArgs a; quant_base_args(ix, a, qcodes, qaux, qinv, metric, cq);
         a.thr = thr; a.cnt = cnt; a.cand = cand; a.cap = HDB_CAND_CAP;
-        if (ix->quant_batch_kernel) {
+        if (p.qb_int8) {
             a.ntiles = s_tiles; a.tile_stride = s_stride;
-            const int sblocks = hdb_qb_scan_blocks(s_tiles, cq, (int)ix->max_blocks);
-            LAUNCH_TRY(hdb_launch_qb_scan(&a, 0, wbuf, wld, (int)ix->max_blocks, st));
+            const int sblocks = hdb_qb_scan_blocks(s_tiles, cq, hdb_cu_count(), (int)ix->opt.max_blocks);
+            LAUNCH_TRY(hdb_launch_qb_scan(&a, 0, wbuf, wld, (int)ix->opt.max_blocks, st));
             LAUNCH_TRY(hdb_launch_qb_thr(wbuf, hdb_qb_slots(sblocks, cq), wld, cq, m, thr, st));
             a.ntiles = (n + 15) / 16; a.tile_stride = 1;
             prof_begin(ix, st);
-            LAUNCH_TRY(hdb_launch_qb_scan(&a, 1, nullptr, 0, (int)ix->max_blocks, st));
+            LAUNCH_TRY(hdb_launch_qb_scan(&a, 1, nullptr, 0, (int)ix->opt.max_blocks, st));
             prof_end(ix, st);
         } else {
             // the v_dot4 scan of the 1-4-query flavour, four queries per pass over the sample and over the shadow
@@ -1006,11 +914,11 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
                 g.qcodes = qcodes + (size_t)g0 * P; g.qaux = qaux + (size_t)g0 * HDB_QQ_WORDS; g.qinv = qinv + g0;
                 g.thr = thr + g0; g.cnt = cnt + (size_t)g0 * HDB_CNT_STRIDE; g.cand = cand + (size_t)g0 * HDB_CAND_CAP;
                 g.ntiles = s_tiles; g.tile_stride = s_stride; g.scores = wbuf; g.ld = ld_s;
-                LAUNCH_TRY(hdb_launch_quant_scan(&g, 0, (int)ix->max_blocks, st));
+                LAUNCH_TRY(hdb_launch_quant_scan(&g, 0, (int)ix->opt.max_blocks, st));
                 LAUNCH_TRY(hdb_launch_qb_thr(wbuf, s_rows, ld_s, g.nq, m, thr + g0, st));
                 g.ntiles = (n + 15) / 16; g.tile_stride = 1; g.scores = nullptr; g.ld = 0;
                 prof_begin(ix, st);
-                LAUNCH_TRY(hdb_launch_quant_scan(&g, 1, (int)ix->max_blocks, st));
+                LAUNCH_TRY(hdb_launch_quant_scan(&g, 1, (int)ix->opt.max_blocks, st));
                 prof_end(ix, st);
             }
         }
@@ -1018,18 +926,10 @@ static int quant_batch_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
         LAUNCH_TRY(hdb_launch_quant_finalize(cand, cnt, HDB_CAND_CAP, cq, (uint32_t)k, kk, ix->row_base, dev_idx + (int64_t)q0 * k,
                                              dev_score + (int64_t)q0 * k, dev_status + q0, qnan, qaux, thr, ix->qstat, nullptr, nullptr, 0, st));
     }
-    ix->st_quant = 1; ix->st_path = 1; ix->st_mfma = 1; ix->st_fused = 0; ix->st_local = 0; ix->st_f32s = 0;
-    ix->st_sample_rows = s_rows; ix->st_sample_m = m;
     ix->qb_cnt = cnt; ix->qb_cnt_n = nq - (nq - 1) / cq_max * cq_max;
     return HDB_OK;
 }
 
-// What the two automatic-shadow tests of topk_impl share (auto_quant): a call the matrix cores would answer on an fp16 matrix that
-// has no shadow or an automatic one, sampled path, status words, k within the shadow's limits, dot or cosine.
-static bool auto_quant_call(const hdb_index* ix, bool mfma, bool exact, bool small, const int32_t* dev_status, int32_t k, int metric) {
-    return ix->auto_quant && ix->use_quant && mfma && ix->dtype == HDB_F16 && (ix->qmode == HDB_QUANT_NONE || ix->qauto) && !exact && !small &&
-           dev_status != nullptr && k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE);
-}
 // The single-launch pipelines: a fresh epoch per launch on a control block (31 bits, never 0: bit 31 of a tag is the "final" flag
 // of the threshold words), the bound of every in-kernel spin in 100 MHz ticks, and the control block itself, zero when allocated.
 static uint32_t next_epoch(hdb_index* ix) {
@@ -1037,7 +937,7 @@ static uint32_t next_epoch(hdb_index* ix) {
     if (ix->fused_epoch == 0) ix->fused_epoch = 1;
     return ix->fused_epoch;
 }
-static uint32_t timeout_ticks(const hdb_index* ix) { return (uint32_t)std::min<int64_t>(ix->fused_timeout_us * 100, 0x7FFFFFFF); }
+static uint32_t timeout_ticks(const hdb_index* ix) { return (uint32_t)std::min<int64_t>(ix->opt.fused_timeout_us * 100, 0x7FFFFFFF); }
 static int ensure_ctl(char** ctl, size_t bytes) {
     if (*ctl) return HDB_OK;
     HIP_TRY(hipMalloc((void**)ctl, bytes));
@@ -1045,206 +945,45 @@ static int ensure_ctl(char** ctl, size_t bytes) {
     return HDB_OK;
 }
 
-static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
-                     float* dev_score, int32_t* dev_status, void* stream, bool exact) {
-    if (!ix || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, "hdb_topk: null argument");
-    if (nq < 0 || k < 0) return fail(HDB_ERR_ARG, "hdb_topk: nq and k must be >= 0");
-    if (nq == 0 || k == 0) return HDB_OK;
-    if (!dev_Q) return fail(HDB_ERR_ARG, "hdb_topk: query pointer is null");
-    const bool full_sort = k > HDB_MAX_K && ix->n > HDB_CAND_CAP;
-    if (metric == HDB_EUCLIDEAN_DIST || !metric_ok(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk: metric not built");
-    if (metric == HDB_PEARSON && ix->d < 1) return fail(HDB_ERR_ARG, "hdb_topk: pearson needs d >= 1");
-    HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t st = (hipStream_t)stream;
-    ix->st_quant = 0; ix->st_plane = 0; ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+// nothing stored: all -1 / -inf
+static int run_empty(const TopkArgs& c) {
+    HIP_TRY(hipMemsetAsync(c.idx, 0xFF, (size_t)c.nq * c.k * sizeof(int64_t), c.st));
+    HIP_TRY(hipMemsetAsync(c.score, 0xFF, (size_t)c.nq * c.k * sizeof(float), c.st));   // NaN pattern; no rows exist
+    if (c.status) HIP_TRY(hipMemsetAsync(c.status, 0, (size_t)c.nq * sizeof(int32_t), c.st));
+    return HDB_OK;
+}
+
+// What every path outside the shadow starts with: the workspace (TopkWs, extents from the plan) and the shared prologue -- query
+// prep, sign bits, centring, the mask folded into a bias -- each where the plan says so.
+struct TopkEnv {
+    TopkWs w; size_t sort_temp;
+    const void* Qeff; int metric_eff;                  // pearson: the centred queries through the cosine pipeline
+    const float* bias_eff; const uint8_t* mask_eff;    // the MFMA scan has no mask input: excluded rows get a bias of -inf instead
+};
+static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkEnv& e) {
+    hipStream_t st = c.st;
     const bool f64 = ix->dtype == HDB_F64;
     const int64_t n = ix->n;
-    const uint32_t kk = (uint32_t)std::min<int64_t>(k, n);
-    const int W = (ix->d + 31) / 32;
-    if (n == 0) {   // nothing stored: all -1 / -inf
-        HIP_TRY(hipMemsetAsync(dev_idx, 0xFF, (size_t)nq * k * sizeof(int64_t), st));
-        HIP_TRY(hipMemsetAsync(dev_score, 0xFF, (size_t)nq * k * sizeof(float), st));   // NaN pattern; no rows exist
-        if (dev_status) HIP_TRY(hipMemsetAsync(dev_status, 0, (size_t)nq * sizeof(int32_t), st));
-        return HDB_OK;
-    }
-    const bool small = n <= HDB_CAND_CAP;
-    const bool is_ham = is_bits_metric(metric);
-    const bool is_pearson = metric == HDB_PEARSON;
-    // bit metrics tie massively by construction; the sampled threshold still works while the rows at and above its
-    // level fit the candidate list (random data: yes), and the status word sends the rest through the exact path
-    const bool exact_req = exact;                            // the caller asked for the exact selection (tests; the re-run of a failed call)
-    if (is_ham && !small && !ix->bits_fused) exact = true;
-    if (ix->force_exact && !small) exact = true;
-    if (!small && (int64_t)kk * 32 > n) exact = true;        // k is a large share of the rows: a sampled threshold cannot help
-    // the int8 shadow (hdb_index_quantize): 1-4 dot / cosine / euclidean queries on a finite float16 / float32 matrix; same answer
-    if (ix->qmode == HDB_QUANT_I8 && !ix->qauto && ix->use_quant && !exact && !small && dev_status != nullptr && nq >= 1 && nq <= 4 &&
-        k <= ix->quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN) &&
-        (ix->dtype == HDB_F16 || ix->dtype == HDB_F32) && n >= (ix->quant_min_n >= 0 ? ix->quant_min_n : quant_min_rows(ix))) {
-        bool finite = false;
-        const int rcf = matrix_is_finite(ix, &finite);
-        if (rcf != HDB_OK) return rcf;
-        if (finite) return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, false);
-    }
-    // fp32 matrices: the VALU scan serves up to 4 queries in one pass at HBM speed; the fp32 MFMA scan (matrix-pipe
-    // bound at 157 TFLOP/s) takes over where a second VALU pass would start
-    // (rows that need K slices -- float32 d >= 1024, fp16 d >= 2048 -- likewise: up to 4 queries are one VALU pass at HBM speed, the
-    // slices pay a second launch and the partial sums)
-    // float32: up to 4 queries are one VALU pass at HBM speed and the float32 matrix pipe binds early -- but three or four queries on
-    // rows of up to 384 elements are faster through the batched single launch from ~300k rows on (n = 2M x 384: 595 / 640 -> 510 us;
-    // d = 768: 1 030 vs 1 714, the VALU pass stays)
-    const int64_t f32_min_q = ix->f32_min_q >= 0 ? ix->f32_min_q : ((ix->d <= 384 && n >= 300000) ? 3 : 5);
-    // (widths without a geometry of their own ride the next wider one through the multi-kernel pipeline: like the K slices, from five queries on)
-    // (bfloat16 rows, hdb_mfma_bf16.hip, likewise: up to 4 queries are one VALU pass with unrounded float32 queries)
-    const int64_t min_q = (hdb_mfma_ksplit_slices(ix->dtype, ix->d) > 0 || hdb_mfma_anyd_pad(ix->dtype, ix->d) > 0 || ix->dtype == HDB_BF16) ? std::max<int64_t>(ix->mfma_min_q, 5)
-                        : ix->dtype == HDB_F32 ? std::max<int64_t>(ix->mfma_min_q, f32_min_q) : ix->mfma_min_q;
-    // hdb_mfma_fused_kernel is built around ONE multiplying wave and two selector waves: with 2-4 fp16 queries its sample phase and
-    // epilogue cost more than the batched single launch (eight multiplying waves) until the pass itself dominates -- n = 100k x 384,
-    // three queries: 124 vs 57 us; 500k: 128 vs 97; 1M: 162 vs 149; 2M: 267 vs 268; 5M: 591 vs 608 (four queries never win).
-    // float32 (VALU flavour, two queries): the single launch wins at every size.
-    const int64_t fused_max_q = ix->fused_max_q >= 0 ? ix->fused_max_q
-                              : ix->dtype == HDB_F32 ? HDB_FUSED_MAXQ_RULE : (n >= 1500000 ? 3 : 1);
-    bool mfma = ix->use_mfma && !is_ham && !small && nq >= min_q &&
-                hdb_mfma_supported(ix->dtype, ix->d, is_pearson ? (int)HDB_COSINE : metric);
-    // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
-    // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
-    if (mfma && ix->dtype == HDB_BF16) { const int rcf = matrix_is_finite(ix, &mfma); if (rcf != HDB_OK) return rcf; }
-    // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
-    // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
-    // the shadow on its first such call; an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
-    const bool auto_q = auto_quant_call(ix, mfma, exact, small, dev_status, k, metric);
-    if (auto_q && nq >= 1 && nq <= 4 &&
-        // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
-        (ix->quant_min_n >= 0 ? n >= ix->quant_min_n : (n >= (int64_t)HDB_QUANT_AUTO_MIN_ROWS && ix->d <= 512))) {
-        bool finite = false;
-        const int rcf = matrix_is_finite(ix, &finite);
-        if (rcf != HDB_OK) return rcf;
-        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_ws_bytes(ix, nq, true), st)))
-            return quant_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st, true);
-    }
-    // ... and batches of 5+ queries (hdb_quant_mfma.hip): the same conditions under a row rule of their own (quant_batch_min_n), for the
-    // widths the int8 matrix-core pass takes and the 16x16x32 form of the fp16 scan, whose bits the rescoring returns
-    if (auto_q && nq >= 5 && hdb_qb_supported(ix->d) && ix->mfma_variant == 16 &&
-        (ix->quant_batch_min_n >= 0 ? n >= ix->quant_batch_min_n : (quant_batch_rule(ix, nq) > 0 && n >= quant_batch_rule(ix, nq)))) {
-        bool finite = false;
-        const int rcf = matrix_is_finite(ix, &finite);
-        if (rcf != HDB_OK) return rcf;
-        if (finite && (ix->qmode == HDB_QUANT_I8 || quant_auto_build(ix, quant_batch_ws_bytes(ix, std::min<int>(nq, 256)), st)))
-            return quant_batch_topk(ix, dev_Q, nq, k, kk, metric, dev_idx, dev_score, dev_status, st);
-    }
-    // 1-4 dot / cosine queries, k <= 128: one launch does everything (hdb_mfma_fused.h; fp16 on the matrix cores,
-    // float32 in the VALU from the same staged tiles)
-    // Short matrices: the single launch in its LOCAL flavour -- no row sample, no exchange; every workgroup parks the scores of all
-    // its tiles and emits the rows at or above its own local_m-th best (hdb_mfma_fused.h).  Possible while a workgroup's tiles fit
-    // its parking area (up to 16); used, by measurement (profiles/r4_latency_map.txt, same box, interleaved), up to local_max_tiles =
-    // 4 tiles per workgroup (fp16 d = 384: 65 536 rows): 35 vs 37 us at 20k rows, 45 vs 45 at 100k, 62 vs 59 at 250k -- beyond that
-    // the exchange flavour filters while it streams and the local one selects after its last tile.  Matrices of up to 8192 rows keep
-    // the three launches (thr = -inf, scan, finalize): 26 us at 1000 rows against 31 for this kernel's launch ramp and last workgroup.
-    const int fl_rows = hdb_mfma_tile_rows(ix->dtype, ix->d);
-    const int64_t fl_tiles = fl_rows > 0 ? (n + fl_rows - 1) / fl_rows : 0;
-    int64_t fl_grid = std::min<int64_t>(fl_tiles, hdb_cu_count());
-    if (ix->max_blocks > 0) fl_grid = std::min<int64_t>(fl_grid, ix->max_blocks);
-    const int fl_cap = fl_rows > 0 && nq >= 1 && nq <= HDB_FUSED_MAXQ_RULE && nq <= ix->local_max_q ? hdb_mfma_fused_local_tiles(ix->dtype, ix->d, metric, nq) : 0;
-    const bool local_ok = fl_grid * 32 <= HDB_CAND_CAP && ix->use_fused && ix->use_local && !ix->force_exact && !exact_req && (ix->dtype == HDB_F32 || (ix->use_mfma && nq >= ix->mfma_min_q)) && fl_grid > 0 && fl_cap > 0 && (fl_tiles + fl_grid - 1) / fl_grid <= std::min<int64_t>(fl_cap, ix->local_max_tiles) && (!small || ix->local_small) &&
-                          !is_ham && kk <= 128 && dev_status != nullptr && hdb_mfma_fused_supported(ix->dtype, ix->d, metric, nq, kk);
-    if (local_ok) exact = false;                       // (k a large share of the rows: every workgroup then emits all its rows)
-    const bool fused_shape = ix->use_fused && !exact && (!small || local_ok) && k <= HDB_MAX_K && dev_status != nullptr && !is_ham &&
-                             hdb_mfma_fused_supported(ix->dtype, ix->d, metric, nq, kk) && (ix->dtype == HDB_F32 || mfma || local_ok) && (nq <= fused_max_q || local_ok) &&
-                             // float32 d = 512 streams 32-KiB tiles (16 rows): below ~3 GB the five-kernel VALU pipeline is
-                             // 2-5 % faster end to end (200 vs 210 us at 0.5 M rows, 376 vs 385 at 1 M; 728 vs 687 at 2 M)
-                             !(ix->dtype == HDB_F32 && ix->d == 512 && n < 1500000) &&
-                             // fp16 d = 1024 (32-KiB tiles, 32 k-steps in one wave): 189 vs 195 us at 0.5 M rows, 619 vs 627 at 2 M,
-                             // but 1 491 vs 1 466 at 5 M -- the single launch up to 4 M rows
-                             !(ix->dtype == HDB_F16 && ix->d == 1024 && n > 4000000);
-    const int tile_rows = (mfma || fused_shape) ? hdb_mfma_tile_rows(ix->dtype, ix->d) : 16;
-    // float32 rows on the matrix cores multiply in three bf16 parts (hdb_mfma_f32s.hip: 2.7x the rate of the float32 MFMAs, same
-    // 1e-5 contract) -- on finite matrices: the parts of an infinite element would cancel to NaN where np.dot keeps the infinity
-    bool f32s = false;
-    const int f32s_auto = hdb_mfma_f32_split_min_q(ix->d);
-    const int f32s_min = f32s_auto > 0 ? (int)(ix->f32_split_min_q > 0 ? ix->f32_split_min_q : f32s_auto) : 0;       // queries of the CALL (every launch of a call multiplies the same way)
-    if (mfma && ix->dtype == HDB_F32 && ix->f32_split && f32s_min > 0 && nq >= f32s_min && nq <= hdb_mfma_f32_split_max_q(ix->d)) { const int rc = matrix_is_finite(ix, &f32s); if (rc != HDB_OK) return rc; }
-    ix->st_f32s = f32s ? 1 : 0;
-    // anything else the matrix-core scan takes (5-256 dot / cosine queries, 1-256 euclidean ones), k <= 128: one launch per
-    // <= bcap queries does preparation, sample, thresholds, the pass and every query's final sort (hdb_mfma_kernel.h, MODE 2)
-    const int bcap = mfma ? hdb_mfma_batch_capacity(ix->dtype, ix->d) : 0;
-    const bool batch1 = ix->use_fused && ix->use_batch1 && mfma && !fused_shape && !exact && !small && !full_sort && kk <= 128 &&
-                        dev_status != nullptr && bcap > 0;
-
-    // ---- plan the chunking --------------------------------------------------------------------
-    int64_t s_tiles = 0, s_stride = 1; uint32_t m = 0;
-    if (!small && !exact) sample_plan(ix, kk, nq, tile_rows, is_ham, s_tiles, s_stride, m);
-    const int64_t s_rows = s_tiles * tile_rows;
-    const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
-    const int64_t ld_n = align_up((size_t)n, 4);
-    int cq_max = batch1 ? bcap : 256;
-    if (exact && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(256, ix->exact_bytes / (ld_n * 4)));
-    // wide rows on the matrix cores go through K slices with a [query][rows] buffer of partial sums (hdb_mfma_ksplit.hip)
-    const bool ksplit = mfma && hdb_mfma_ksplit_slices(ix->dtype, ix->d) > 0;
-    if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), ix->exact_bytes / (ld_n * 4)));
-    cq_max = std::min(cq_max, (int)nq);
-
-    // full sort (k > HDB_MAX_K): all scores of one query, the sort's work array and its scratch live in the same layout
-    size_t sort_temp = 0;
-    if (full_sort) LAUNCH_TRY(hdb_sort_temp_bytes(n, &sort_temp));
-    TopkWs w;
-    int rc = ws_lay(ix, w, (int)nq, (int)ix->d, W, cq_max, exact && !small ? ld_n : ld_s, ksplit ? ld_n : (int64_t)0, full_sort ? n : (int64_t)0, sort_temp);
+    e.sort_temp = 0;
+    if (p.sort_n > 0) LAUNCH_TRY(hdb_sort_temp_bytes(p.sort_n, &e.sort_temp));
+    TopkWs& w = e.w;
+    int rc = ws_lay(ix, w, (int)c.nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, p.sort_n, e.sort_temp);
     if (rc) return rc;
-    float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
-    uint32_t* const qbits = w.qbits; void* const q16 = w.q16; void* const qc = w.qc;
-    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
-    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
-
-    const bool fused = fused_shape && !full_sort && (m == 8 || local_ok);           // (no prep kernel either)
-    // the MFMA scan multiplies with fp16 queries: written by the same kernel (pearson converts its centred copy later)
-    const bool f16_queries = mfma && ix->dtype == HDB_F16;          // fp32 matrices multiply with the float32 queries as they are
-    const bool q16_in_prep = f16_queries && !is_pearson && !full_sort;
-    // hamming / jaccard: the single launch for every call (with the two-level hand-out of the pass: one query 120-124 vs 125-132 us
-    // for the six launches at N=10M, 78 vs 77 at 5M, 60 vs 63 at 1.25M, 44 vs 52 at 250k rows; four queries 135 vs 172 at N=10M --
-    // profiles/r3_bits_variants.txt; bits_fused = 3 keeps one-query calls on 1M+ rows with the six launches, for comparison)
-    const bool bits1_pre = ix->use_fused && ix->bits_fused && is_ham && !exact && !small && !full_sort && !f64 && dev_status != nullptr &&
-                           hdb_bits_fused_supported(metric, 1, W, kk) && (nq >= 2 || n < 1000000 || ix->bits_fused != 3) &&
-                           // (more than four queries: the six launches take them all in one go, grid.y = query groups -- 16 queries on
-                           // 100k rows 50 vs 148 us for four single launches in a row, 64 queries 67 vs 642; 10M rows 464 vs 524)
-                           nq <= (ix->bits_max_q >= 0 ? ix->bits_max_q : 4);
-                           // (the single launch prepares its queries itself)
-    // matrices of up to 8192 rows, one chunk of queries: the prep kernel also sets thr = -inf / an empty list and packs the query sign
-    // bits -- four (five) launches become three; the reference's own sizes live here (151 .. 10 000 documents)
-    const bool fold_small = small && !fused && !batch1 && !bits1_pre && !full_sort && nq <= cq_max;
-    if (!fused && !batch1 && !bits1_pre)
-        LAUNCH_TRY(hdb_launch_qprep2(dev_Q, nq, ix->d, f64, qinv, qsq, qnan, q16_in_prep ? q16 : nullptr, qscl, fold_small ? thr : nullptr,
-                                     fold_small ? cnt : nullptr, (fold_small && is_ham) ? qbits : nullptr, W, st));
-    if (is_ham) {
+    if (p.prep)
+        LAUNCH_TRY(hdb_launch_qprep2(c.Q, c.nq, ix->d, f64, w.qinv, w.qsq, w.qnan, p.q16_in_prep ? w.q16 : nullptr, w.qscl, p.fold_small ? w.thr : nullptr,
+                                     p.fold_small ? w.cnt : nullptr, (p.fold_small && p.bits) ? w.qbits : nullptr, p.W, st));
+    if (p.bits) {
         rc = ensure_bits(ix, st); if (rc) return rc;
-        if (!bits1_pre && !fold_small) LAUNCH_TRY(hdb_launch_qsign(dev_Q, nq, ix->d, f64, W, qbits, st));
+        if (p.prep && !p.fold_small) LAUNCH_TRY(hdb_launch_qsign(c.Q, c.nq, ix->d, f64, p.W, w.qbits, st));
     }
-    const void* Qeff = dev_Q;
-    int metric_eff = metric;
-    if (is_pearson) {
+    e.Qeff = c.Q; e.metric_eff = c.metric;
+    if (p.pearson) {
         rc = ensure_pscale(ix, st); if (rc) return rc;
-        if (!fused && !batch1) LAUNCH_TRY(hdb_launch_qcentre(dev_Q, nq, ix->d, f64, qc, qinv, st));     // qinv <- 1/sd_q (the single launches centre their queries themselves)
-        Qeff = qc; metric_eff = HDB_COSINE;
+        if (p.prep) LAUNCH_TRY(hdb_launch_qcentre(c.Q, c.nq, ix->d, f64, w.qc, w.qinv, st));     // qinv <- 1/sd_q (the single launches centre their queries themselves)
+        e.Qeff = w.qc; e.metric_eff = HDB_COSINE;
     }
-    if (full_sort) {
-        // cold path for huge k: one query at a time, all scores -> stable radix sort (hdb_sort.hip)
-        // (the queries are prepared: this branch excludes the single launches, so the prep, sign and centring launches above ran)
-        ix->st_path = 3; ix->st_mfma = 0; ix->st_chunks = nq;
-        for (int q0 = 0; q0 < nq; ++q0) {
-            QueryBufs qb{qinv, qsq, qbits, nullptr, nullptr};
-            ScanArgs s2; base_args(ix, s2, Qeff, metric_eff);
-            if (is_pearson) s2.inv_norm = ix->pscale;
-            s2.q0 = q0; s2.bias = ix->bias; s2.scores = w.sc1; s2.ld = ld_n;
-            rc = run_scan(ix, s2, 0, 1, qb, false, st); if (rc) return rc;
-            LAUNCH_TRY(hdb_launch_full_sort(w.sc1, n, k, ix->row_base, w.work, w.temp, sort_temp, dev_idx + (int64_t)q0 * k,
-                                            dev_score + (int64_t)q0 * k, st));
-        }
-        if (dev_status) LAUNCH_TRY(hdb_launch_status_nan(qnan, nq, dev_status, st));     // HDB_Q_NAN survives on this path too
-        return HDB_OK;
-    }
-    // the MFMA scan has no mask input: excluded rows get a bias of -inf instead (never appended, like the VALU scan)
-    const float* bias_eff = ix->bias;
-    const uint8_t* mask_eff = ix->mask;
-    // (run_scan hands manhattan calls of two or more queries to the tile kernel; a single query keeps the VALU scan and its mask input)
-    const bool l1tile = metric == HDB_MANHATTAN && ix->use_l1_tile && !small && nq >= 2 && hdb_l1_tile_supported(ix->dtype, ix->d);
-    if ((mfma || fused || l1tile) && ix->mask) {
+    e.bias_eff = ix->bias; e.mask_eff = ix->mask;
+    if (p.mask_fold) {
         if (n > ix->mbias_rows) {
             if (ix->mbias) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->mbias)); ix->mbias = nullptr; }
             const int64_t rows = n + n / 4 + 64;
@@ -1252,116 +991,136 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
             ix->mbias_rows = rows;
         }
         LAUNCH_TRY(hdb_launch_maskbias(ix->mask, ix->bias, n, ix->mbias, st));
-        bias_eff = ix->mbias; mask_eff = nullptr;
+        e.bias_eff = ix->mbias; e.mask_eff = nullptr;
     }
-    ix->st_fused = 0; ix->st_local = 0;
-    if (fused) {
-        // ---- the whole call in ONE launch (hdb_mfma_fused.h): prep + sample + threshold + filter pass + finalize ----
-        rc = ensure_ctl(&ix->fctl, hdb_mfma_fused_ctl_bytes()); if (rc) return rc;
-        ScanArgs a; base_args(ix, a, dev_Q, metric);
-        a.bias = bias_eff; a.mask = nullptr;
-        if (metric == HDB_EUCLIDEAN) a.inv_norm = ix->sqnorm;          // the per-row aux value of the euclidean expansion
-        if (is_pearson) a.inv_norm = ix->pscale;                       // 1/(sd_v d); the kernel centres the queries itself
-        a.ntiles = (n + tile_rows - 1) / tile_rows;
-        a.thr = thr; a.cnt = cnt; a.cand = cand; a.nq = nq;
-        FusedArgs fa; memset(&fa, 0, sizeof(fa));
-        fa.Qraw = static_cast<const float*>(dev_Q); fa.nq = nq;
-        fa.s_tiles = s_tiles; fa.s_stride = s_stride;
+    return HDB_OK;
+}
+
+// k > HDB_MAX_K: one query at a time, all scores -> stable radix sort (hdb_sort.hip)
+static int run_full_sort(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    for (int q0 = 0; q0 < c.nq; ++q0) {
+        QueryBufs qb{e.w.qinv, e.w.qsq, e.w.qbits, nullptr, nullptr};
+        ScanArgs s2; base_args(ix, s2, e.Qeff, e.metric_eff);
+        if (p.pearson) s2.inv_norm = ix->pscale;
+        s2.q0 = q0; s2.bias = ix->bias; s2.scores = e.w.sc1; s2.ld = p.ld_n;
+        rc = run_scan(ix, s2, 0, 1, qb, false, false, c.st); if (rc) return rc;
+        LAUNCH_TRY(hdb_launch_full_sort(e.w.sc1, ix->n, c.k, ix->row_base, e.w.work, e.w.temp, e.sort_temp, c.idx + (int64_t)q0 * c.k,
+                                        c.score + (int64_t)q0 * c.k, c.st));
+    }
+    if (c.status) LAUNCH_TRY(hdb_launch_status_nan(e.w.qnan, c.nq, c.status, c.st));     // HDB_Q_NAN survives on this path too
+    return HDB_OK;
+}
+
+// 1-4 dot / cosine queries, k <= 128: the whole call in ONE launch (hdb_mfma_fused.h): prep + sample + threshold + filter pass +
+// finalize; fp16 on the matrix cores, float32 in the VALU from the same staged tiles.  Exchange or local flavour (p.local).
+static int run_fused(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    rc = ensure_ctl(&ix->fctl, hdb_mfma_fused_ctl_bytes()); if (rc) return rc;
+    ScanArgs a; base_args(ix, a, c.Q, c.metric);
+    a.bias = e.bias_eff; a.mask = nullptr;
+    if (c.metric == HDB_EUCLIDEAN) a.inv_norm = ix->sqnorm;        // the per-row aux value of the euclidean expansion
+    if (p.pearson) a.inv_norm = ix->pscale;                        // 1/(sd_v d); the kernel centres the queries itself
+    a.ntiles = (ix->n + p.tile_rows - 1) / p.tile_rows;
+    a.thr = e.w.thr; a.cnt = e.w.cnt; a.cand = e.w.cand; a.nq = c.nq;
+    FusedArgs fa; memset(&fa, 0, sizeof(fa));
+    fa.Qraw = static_cast<const float*>(c.Q); fa.nq = c.nq;
+    fa.s_tiles = p.s_tiles; fa.s_stride = p.s_stride;
+    fa.epoch = next_epoch(ix);
+    fa.timeout_ticks = timeout_ticks(ix);
+    fa.ctl = reinterpret_cast<uint32_t*>(ix->fctl);
+    fa.cand = e.w.cand; fa.cap = HDB_CAND_CAP; fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
+    fa.idx_out = c.idx; fa.score_out = c.score; fa.status = c.status; fa.thr_out = e.w.thr;
+    fa.local = p.local ? 1 : 0; fa.local_slot = p.local_slot; fa.local_m = p.local_m;
+    prof_begin(ix, c.st);
+    ix->ht_l0 = std::chrono::steady_clock::now();
+    LAUNCH_TRY(hdb_launch_mfma_fused(&a, ix->dtype, &fa, (int)ix->opt.max_blocks, c.st));
+    ix->ht_l1 = std::chrono::steady_clock::now();
+    prof_end(ix, c.st);
+    return HDB_OK;
+}
+
+// 1-4 hamming / jaccard queries per launch: prep, sample, threshold, the pass over the sign bits and the final sort in ONE
+// kernel (hdb_bits_fused.hip); larger batches go through it four queries at a time (as the multi-kernel scan re-reads the bits)
+static int run_bits1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
+    for (int q0 = 0; q0 < c.nq; q0 += 4) {
+        const int cq = std::min(4, c.nq - q0);
+        BitsArgs ba; memset(&ba, 0, sizeof(ba));
+        ba.bits = ix->bits; ba.npad = ix->bits_npad; ba.W = p.W; ba.n = ix->n; ba.d = ix->d;
+        ba.Qraw = static_cast<const float*>(c.Q) + (size_t)q0 * ix->d; ba.nq = cq;
+        ba.ntiles = (ix->n + 15) / 16; ba.s_tiles = p.s_tiles; ba.s_stride = p.s_stride;
+        ba.bias = ix->bias; ba.mask = ix->mask;
+        ba.local = p.bits_local;
+        ba.epoch = next_epoch(ix);
+        ba.timeout_ticks = timeout_ticks(ix);
+        ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
+        ba.cand = e.w.cand; ba.cap = HDB_CAND_CAP; ba.k = (uint32_t)c.k; ba.kk = p.kk; ba.row_base = ix->row_base;
+        ba.idx_out = c.idx + (int64_t)q0 * c.k; ba.score_out = c.score + (int64_t)q0 * c.k; ba.status = c.status + q0;
+        prof_begin(ix, c.st);
+        ix->ht_l0 = std::chrono::steady_clock::now();
+        LAUNCH_TRY(hdb_launch_bits_fused(&ba, c.metric == HDB_JACCARD ? 1 : 0, (int)ix->opt.max_blocks, c.st));
+        ix->ht_l1 = std::chrono::steady_clock::now();
+        prof_end(ix, c.st);
+    }
+    return HDB_OK;
+}
+
+// anything else the matrix-core scan takes (5-256 dot / cosine queries, 1-256 euclidean ones), k <= 128: one launch per
+// <= cq_max queries does preparation, sample, thresholds, the pass and every query's final sort (hdb_mfma_kernel.h, MODE 2)
+static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
+    const size_t qrow = (size_t)ix->d * 4;
+    for (int q0 = 0; q0 < c.nq; q0 += p.cq_max) {
+        const int cq = std::min(p.cq_max, c.nq - q0);
+        ScanArgs a; base_args(ix, a, c.Q, e.metric_eff);                                  // pearson: the cosine launch on queries the kernel centres, ...
+        if (p.pearson) a.inv_norm = ix->pscale;                                           // ... row scale 1/(sd_v d)
+        a.bias = e.bias_eff; a.mask = nullptr; a.q0 = 0; a.nq = cq; a.f32_split = p.f32s ? 1 : 0;
+        a.ntiles = (ix->n + p.tile_rows - 1) / p.tile_rows;
+        a.cand = e.w.cand;
+        a.tile_ctr = ix->opt.dyn_tiles ? reinterpret_cast<uint32_t*>(ix->bctl) + HDB_BATCH_CTL_TILE : nullptr;
+        BatchArgs fa; memset(&fa, 0, sizeof(fa));
+        fa.Qraw = static_cast<const char*>(c.Q) + (size_t)q0 * qrow;
+        fa.s_tiles = p.s_tiles; fa.s_stride = p.s_stride; fa.centre = p.pearson ? 1 : 0;
         fa.epoch = next_epoch(ix);
         fa.timeout_ticks = timeout_ticks(ix);
-        fa.ctl = reinterpret_cast<uint32_t*>(ix->fctl);
-        fa.cand = cand; fa.cap = HDB_CAND_CAP; fa.k = (uint32_t)k; fa.kk = kk; fa.row_base = ix->row_base;
-        fa.idx_out = dev_idx; fa.score_out = dev_score; fa.status = dev_status; fa.thr_out = thr;
-        if (local_ok) {
-            fa.local = 1;
-            // rows every workgroup emits at least: ~3072 candidates in all (8 .. 32 per workgroup); a grid too small to hold 4 k rows
-            // that way emits everything (64 = every lane maximum of a tile)
-            // slots of a workgroup in the (slotted) lists: 64 while the grid leaves room for them, else 32; never fewer than twice local_m
-            fa.local_slot = fl_grid * 64 <= HDB_CAND_CAP ? 64u : 32u;
-            fa.local_m = ix->local_m > 0 ? (uint32_t)ix->local_m
-                       : fl_grid * 32 >= 4 * (int64_t)kk ? (uint32_t)std::min<int64_t>(fa.local_slot / 2, std::max<int64_t>(8, (3072 + fl_grid - 1) / fl_grid)) : 64u;
-        }
-        ix->st_local = local_ok ? 1 : 0;
-        ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 1; ix->st_path = 1; ix->st_mfma = ix->dtype == HDB_F16 ? 1 : 0; ix->st_fused = 1;
-        prof_begin(ix, st);
+        fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
+        fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
+        fa.idx_out = c.idx + (int64_t)q0 * c.k; fa.score_out = c.score + (int64_t)q0 * c.k; fa.status = c.status + q0;
+        prof_begin(ix, c.st);
         ix->ht_l0 = std::chrono::steady_clock::now();
-        LAUNCH_TRY(hdb_launch_mfma_fused(&a, ix->dtype, &fa, (int)ix->max_blocks, st));
+        LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, 2, cq, nullptr, ix->sqnorm, nullptr, nullptr, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, c.st, &fa));
         ix->ht_l1 = std::chrono::steady_clock::now();
-        prof_end(ix, st);
-        return HDB_OK;
+        prof_end(ix, c.st);
     }
-    // 1-4 hamming / jaccard queries per launch: prep, sample, threshold, the pass over the sign bits and the final sort in ONE
-    // kernel (hdb_bits_fused.hip); larger batches go through it four queries at a time (as the multi-kernel scan re-reads the bits)
-    const bool bits1 = bits1_pre;
-    if (bits1) {
-        rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
-        ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 0; ix->st_path = 1; ix->st_mfma = 0; ix->st_fused = 3;
-        {   // (the launcher's rule: the local flavour from 2 k workgroups on, hdb_bits_fused.hip)
-            int64_t bl = hdb_cu_count();
-            const int64_t items = ((n + 15) / 16) * 4;
-            if (bl * 1024 > items) bl = (items + 1023) / 1024;
-            if (ix->max_blocks > 0 && ix->max_blocks < bl) bl = ix->max_blocks;
-            ix->st_local = (ix->bits_local && bl >= 2 * (int64_t)kk) ? 1 : 0;
-        }
-        for (int q0 = 0; q0 < nq; q0 += 4) {
-            const int cq = std::min(4, nq - q0);
-            ix->st_chunks++;
-            BitsArgs ba; memset(&ba, 0, sizeof(ba));
-            ba.bits = ix->bits; ba.npad = ix->bits_npad; ba.W = W; ba.n = n; ba.d = ix->d;
-            ba.Qraw = static_cast<const float*>(dev_Q) + (size_t)q0 * ix->d; ba.nq = cq;
-            ba.ntiles = (n + 15) / 16; ba.s_tiles = s_tiles; ba.s_stride = s_stride;
-            ba.bias = ix->bias; ba.mask = ix->mask;
-            ba.local = ix->bits_local ? 1 : 0;
-            ba.epoch = next_epoch(ix);
-            ba.timeout_ticks = timeout_ticks(ix);
-            ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
-            ba.cand = cand; ba.cap = HDB_CAND_CAP; ba.k = (uint32_t)k; ba.kk = kk; ba.row_base = ix->row_base;
-            ba.idx_out = dev_idx + (int64_t)q0 * k; ba.score_out = dev_score + (int64_t)q0 * k; ba.status = dev_status + q0;
-            prof_begin(ix, st);
-            ix->ht_l0 = std::chrono::steady_clock::now();
-            LAUNCH_TRY(hdb_launch_bits_fused(&ba, metric == HDB_JACCARD ? 1 : 0, (int)ix->max_blocks, st));
-            ix->ht_l1 = std::chrono::steady_clock::now();
-            prof_end(ix, st);
-        }
-        return HDB_OK;
-    }
-    if (batch1) {
-        rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
-        ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 0; ix->st_path = 1; ix->st_mfma = 1; ix->st_fused = 2;
-        const size_t qrow = (size_t)ix->d * 4;
-        for (int q0 = 0; q0 < nq; q0 += cq_max) {
-            const int cq = std::min(cq_max, nq - q0);
-            ix->st_chunks++;
-            ScanArgs a; base_args(ix, a, dev_Q, is_pearson ? (int)HDB_COSINE : metric);      // pearson: the cosine launch on queries the kernel centres, ...
-            if (is_pearson) a.inv_norm = ix->pscale;                                          // ... row scale 1/(sd_v d)
-            a.bias = bias_eff; a.mask = nullptr; a.q0 = 0; a.nq = cq; a.f32_split = f32s ? 1 : 0;
-            a.ntiles = (n + tile_rows - 1) / tile_rows;
-            a.cand = cand;
-            a.tile_ctr = ix->dyn_tiles ? reinterpret_cast<uint32_t*>(ix->bctl) + HDB_BATCH_CTL_TILE : nullptr;
-            BatchArgs fa; memset(&fa, 0, sizeof(fa));
-            fa.Qraw = static_cast<const char*>(dev_Q) + (size_t)q0 * qrow;
-            fa.s_tiles = s_tiles; fa.s_stride = s_stride; fa.centre = is_pearson ? 1 : 0;
-            fa.epoch = next_epoch(ix);
-            fa.timeout_ticks = timeout_ticks(ix);
-            fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
-            fa.k = (uint32_t)k; fa.kk = kk; fa.row_base = ix->row_base;
-            fa.idx_out = dev_idx + (int64_t)q0 * k; fa.score_out = dev_score + (int64_t)q0 * k; fa.status = dev_status + q0;
-            prof_begin(ix, st);
-            ix->ht_l0 = std::chrono::steady_clock::now();
-            LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, 2, cq, nullptr, ix->sqnorm, nullptr, nullptr, (int)ix->max_blocks, (int)ix->mfma_variant, st, &fa));
-            ix->ht_l1 = std::chrono::steady_clock::now();
-            prof_end(ix, st);
-        }
-        return HDB_OK;
-    }
-    bool q16_ready = q16_in_prep;
-    ix->st_sample_rows = s_rows; ix->st_sample_m = m; ix->st_chunks = 0;
-    ix->st_path = small ? 0 : (exact ? 2 : 1);
-    ix->st_mfma = mfma ? 1 : 0;
+    return HDB_OK;
+}
 
+// The multi-kernel pipeline, cq_max queries at a time.  small: thr = -inf -> scan(filter) -> finalize; sampled: scan(scores) over the
+// row sample -> threshold -> scan(filter) over all rows -> finalize; exact: scan(scores) over all rows -> radix passes -> collect.
+static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
+    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
+    const TopkWs& w = e.w;
+    float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
+    uint32_t* const qbits = w.qbits; void* const q16 = w.q16;
+    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
+    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
+    const void* Qeff = e.Qeff; const int metric_eff = e.metric_eff; const float* bias_eff = e.bias_eff; const uint8_t* mask_eff = e.mask_eff;
+    const bool small = p.small, exact = p.exact, mfma = p.mfma, f32s = p.f32s, fold_small = p.fold_small, f16_queries = p.f16_queries, is_pearson = p.pearson, q16_in_prep = p.q16_in_prep;
+    const int64_t n = ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
+    const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, tile_rows = p.tile_rows, npass = p.npass;
+    bool q16_ready = q16_in_prep;
     for (int q0 = 0; q0 < nq; q0 += cq_max) {
         const int cq = std::min(cq_max, nq - q0);
-        ix->st_chunks++;
         if (f16_queries && !q16_ready) { LAUNCH_TRY(hdb_launch_q_to_f16((const float*)Qeff, nq, ix->d, q16, qscl, st)); q16_ready = true; }
         QueryBufs qb{qinv, qsq, qbits, f16_queries ? q16 : Qeff, f16_queries ? qscl : nullptr};
         ScanArgs a; base_args(ix, a, Qeff, metric_eff);
@@ -1373,52 +1132,82 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
 
         if (small) {
             if (!fold_small) LAUNCH_TRY(hdb_launch_fill_thr(thr, cnt, cq, -INFINITY, st));
-            rc = run_scan(ix, a, 1, cq, qb, mfma, st); if (rc) return rc;
+            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
         } else if (!exact) {
             // 1) strided row sample -> sample scores
             ScanArgs s = a;
             s.ntiles = s_tiles; s.tile_stride = s_stride; s.scores = sbuf; s.ld = ld_s;
-            rc = run_scan(ix, s, 0, cq, qb, mfma, st); if (rc) return rc;
+            rc = run_scan(ix, s, 0, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
             // 2) m-th largest sample score per query
             if (m <= 16) {
                 LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, cq, m, thr, cnt, tile_ctr, st));
-                if (mfma && ix->dyn_tiles) a.tile_ctr = tile_ctr;       // zeroed just now: dynamic tile hand-out in the pass
+                if (mfma && ix->opt.dyn_tiles) a.tile_ctr = tile_ctr;       // zeroed just now: dynamic tile hand-out in the pass
             } else {
                 HIP_TRY(hipMemsetAsync(hist, 0, (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
-                for (int p = 0; p < 4; ++p) LAUNCH_TRY(hdb_launch_hist(sbuf, s_rows, ld_s, cq, hist, p, m, st));
+                for (int ps = 0; ps < 4; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, s_rows, ld_s, cq, hist, ps, m, st));
                 LAUNCH_TRY(hdb_launch_thr(hist, cq, 4, m, (uint32_t)s_rows, thr, cnt, st));
             }
             // 3) the pass over all of V
             prof_begin(ix, st);
-            rc = run_scan(ix, a, 1, cq, qb, mfma, st); if (rc) return rc;
+            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
             prof_end(ix, st);
         } else {
             ScanArgs s = a;
             s.scores = sbuf; s.ld = ld_n;
             prof_begin(ix, st);
-            rc = run_scan(ix, s, 0, cq, qb, mfma, st); if (rc) return rc;
+            rc = run_scan(ix, s, 0, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
             prof_end(ix, st);
             // cnt and hist are neighbours in the workspace: one memset clears both
             HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)((char*)hist - (char*)cnt) + (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
-            // hamming scores are integers in [0, d]: their float keys are zero below the top 8 + bits(d) bits, so the
-            // last radix pass (the last two for d < 128) would only re-read the scores to find every key in bin 0
-            int npass = 4;
-            if (metric == HDB_HAMMING && !ix->bias && !ix->mask) {
-                int bits = 0;
-                while ((ix->d >> bits) != 0) ++bits;
-                npass = std::min(4, (8 + bits + 7) / 8);
-            }
-            for (int p = 0; p < npass; ++p) LAUNCH_TRY(hdb_launch_hist(sbuf, n, ld_n, cq, hist, p, kk, st));
+            for (int ps = 0; ps < npass; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, n, ld_n, cq, hist, ps, kk, st));
             LAUNCH_TRY(hdb_launch_collect(sbuf, n, ld_n, cq, hist, npass, kk, cnt, cand, HDB_CAND_CAP, tie_info, st));
         }
         if (mfma && metric == HDB_EUCLIDEAN)     // the MFMA path scores through ||v||^2+||q||^2-2v.q: redo near-duplicates directly
             LAUNCH_TRY(hdb_launch_rescore_euclid(cand, cnt, HDB_CAND_CAP, cq, ix->V, ix->dtype, ix->d, (const float*)dev_Q, qsq, q0, ix->bias, st));
         LAUNCH_TRY(hdb_launch_finalize(cand, cnt, HDB_CAND_CAP, cq, (uint32_t)k, kk, ix->row_base,
                                        dev_idx + (int64_t)q0 * k, dev_score + (int64_t)q0 * k,
-                                       dev_status ? dev_status + q0 : nullptr, qnan + q0, (int)ix->finalize_threads,
+                                       dev_status ? dev_status + q0 : nullptr, qnan + q0, (int)ix->opt.finalize_threads,
                                        a.f32_split ? HDB_Q_UNDERFLOW : 0, st));      // (parts of an infinite query element cancel to NaN: exact re-run)
     }
     return HDB_OK;
+}
+
+static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
+                     float* dev_score, int32_t* dev_status, void* stream, bool exact) {
+    if (!ix || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, "hdb_topk: null argument");
+    if (nq < 0 || k < 0) return fail(HDB_ERR_ARG, "hdb_topk: nq and k must be >= 0");
+    if (nq == 0 || k == 0) return HDB_OK;
+    if (!dev_Q) return fail(HDB_ERR_ARG, "hdb_topk: query pointer is null");
+    if (metric == HDB_EUCLIDEAN_DIST || !metric_ok(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk: metric not built");
+    if (metric == HDB_PEARSON && ix->d < 1) return fail(HDB_ERR_ARG, "hdb_topk: pearson needs d >= 1");
+    HIP_TRY(hipSetDevice(ix->device));
+    const TopkArgs c{dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, (hipStream_t)stream};
+    const TopkCall call{nq, k, metric, dev_status != nullptr, exact};
+    // the planner's one question to the device: the cached flag word of the last build, fetched where it decides something
+    int frc = HDB_OK;
+    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
+    TopkPlan p = plan_topk(topk_facts(ix), ix->opt, call, finite);
+    if (frc != HDB_OK) return frc;
+    if (p.shadow()) {                // a declined build or plane is a new fact: plan once more, and only once
+        bool declined = false;
+        const int rc = shadow_prepare(ix, p, nq, c.st, &declined);
+        if (rc) return rc;
+        if (declined) p = plan_topk(topk_facts(ix), ix->opt, call, finite);
+        if (frc != HDB_OK) return frc;
+    }
+    ix->st = p.stats;                // the statistics of the call: written here and nowhere else
+    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    switch (p.path) {
+    case HDB_PATH_EMPTY: return run_empty(c);
+    case HDB_PATH_QUANT: return quant_topk(ix, c, p);
+    case HDB_PATH_QUANT_BATCH: return quant_batch_topk(ix, c, p);
+    case HDB_PATH_FUSED: return run_fused(ix, c, p);
+    case HDB_PATH_BITS1: return run_bits1(ix, c, p);
+    case HDB_PATH_BATCH1: return run_batch1(ix, c, p);
+    case HDB_PATH_FULL_SORT: return run_full_sort(ix, c, p);
+    case HDB_PATH_PIPELINE: return run_pipeline(ix, c, p);
+    }
+    return fail(HDB_ERR_ARG, "hdb_topk: no path");
 }
 
 extern "C" int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
@@ -1500,7 +1289,7 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     // Pinned (device-visible) host memory: the last kernels of the pipeline store the record there themselves and the
     // D2H copy disappears from the critical path; anything else goes through a device record and one hipMemcpyAsync.
     bool direct = false;
-    if (ix->host_direct) {
+    if (ix->opt.host_direct) {
         hipPointerAttribute_t attr;
         if (hipPointerGetAttributes(&attr, host_record) == hipSuccess) direct = attr.type == hipMemoryTypeHost && attr.devicePointer == host_record;
         else (void)hipGetLastError();
@@ -1525,13 +1314,13 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     // ordered: the next launch queues behind the kernels.
     constexpr int32_t SENTINEL = 0x7FFFFFFF;
     volatile int32_t* poll = reinterpret_cast<volatile int32_t*>(static_cast<char*>(host_record) + (size_t)nq * k * 12);
-    if (direct && ix->host_poll) for (int q = 0; q < nq; ++q) poll[q] = SENTINEL;
+    if (direct && ix->opt.host_poll) for (int q = 0; q < nq; ++q) poll[q] = SENTINEL;
     ix->ht_l0 = ix->ht_l1 = std::chrono::steady_clock::now();      // (pipelines of several launches: everything counts as "pre")
     int rc = topk_impl(ix, dev_Q, nq, k, metric, d_idx, d_sc, d_st, stream, false);
     if (rc) return rc;
     if (!direct) HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
     bool polled = false;
-    if (direct && ix->host_poll && (ix->st_fused || ix->st_path != 3)) {      // (the k > 2048 full sort writes its status words elsewhere)
+    if (direct && ix->opt.host_poll && (ix->st.fused || ix->st.path != 3)) {      // (the k > 2048 full sort writes its status words elsewhere)
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned spins = 0;; ++spins) {
             bool done = true;
@@ -1559,14 +1348,14 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     const size_t qbytes = (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4);
     std::vector<char> bad(nq);
     for (int q = 0; q < nq; ++q) bad[q] = (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) != 0;     // the re-run rewrites h_st
-    const int64_t quant_first = ix->st_quant;            // ("quant" reports the call's first attempt)
+    const int64_t quant_first = ix->st.quant;            // ("quant" reports the call's first attempt)
     for (int q = 0; q < nq; ++q) {
         if (!bad[q]) continue;
         rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, k, metric, d_idx + (size_t)q * k,
                        d_sc + (size_t)q * k, d_st + q, stream, true);
         if (rc) return rc;
     }
-    ix->st_quant = quant_first;
+    ix->st.quant = quant_first;
     if (!direct) HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HDB_OK;
@@ -1713,10 +1502,10 @@ static void group_worker(hdb_group* g, int p) {
                 dq = g->qdev[p];
             }
             if (rc == HDB_OK) {
-                const int64_t saved = ix->use_fused;
-                if (g->shared_dev[p]) ix->use_fused = 0;             // for this call only (one call in flight per handle)
+                const int64_t saved = ix->opt.use_fused;
+                if (g->shared_dev[p]) ix->opt.use_fused = 0;             // for this call only (one call in flight per handle)
                 rc = hdb_topk_host(ix, dq, g->nq, g->k, g->metric, g->gather + (size_t)p * g->stride, st);
-                ix->use_fused = saved;
+                ix->opt.use_fused = saved;
                 if (rc != HDB_OK) msg = hdb_last_error();
             }
         } else {                                                     // an empty shard contributes padding

@@ -53,9 +53,6 @@ extern "C" int hdb_debug_read_bits_stamps(unsigned long long* host_out, int wgs)
 typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) unsigned long long hdb_bgu64;
 
-#ifndef HDB_BITS_THREADS
-#define HDB_BITS_THREADS 1024
-#endif
 #ifndef HDB_BITS_TAIL
 #define HDB_BITS_TAIL 1                  // the last ~15 % of the pass is handed out in quarter chunks (tools/exp_bits_variants.py: 5M rows 83 -> 78 us,
                                          // four queries -2..3 %; 8 waves per workgroup instead of 16: +5..20 %)
@@ -73,7 +70,6 @@ typedef __attribute__((address_space(1))) unsigned long long hdb_bgu64;
 #define HDB_BITS_POLL 0                  // how the threshold words and the arrival counter are polled: 0 = sc1 loads, 1 = returning atomics (or 0)
 #endif
 #define HDB_BITS_WAVES (HDB_BITS_THREADS / 64)
-#define HDB_BITS_MAXW 512
 
 // The eight largest of the (up to two, a >= b) keys every thread brings: each wave extracts its eight largest (DPP maxima),
 // wave 0 the eight largest of those.  Returns, in lane r < 8 of wave 0, the r-th largest (0 elsewhere).  scratch: waves x 8 words.
@@ -534,23 +530,13 @@ __global__ __launch_bounds__(HDB_BITS_THREADS) void hdb_bits_fused_kernel(BitsAr
     }
 }
 
-extern "C" int hdb_bits_fused_supported(int metric, int nq, int W, uint32_t kk) {
-    return (metric == HDB_HAMMING || metric == HDB_JACCARD) && nq >= 1 && nq <= 4 && W <= HDB_BITS_MAXW && kk <= 128;
-}
-
 extern "C" int hdb_launch_bits_fused(const BitsArgs* args, int jaccard, int max_blocks, void* stream) {
     const BitsArgs& a = *args;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)HDB_CAND_CAP * 16 + 2048 * 4 + 64 + (size_t)4 * HDB_BITS_MAXW * 4 + 128 * 4 + 4 * 4 + 16 * 4 + 64;
-    int blocks = hdb_cu_count();
-    const int64_t items = a.ntiles * 4;
-    if ((int64_t)blocks * HDB_BITS_THREADS > items) blocks = (int)((items + HDB_BITS_THREADS - 1) / HDB_BITS_THREADS);
-    if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
-    if (blocks < 1) blocks = 1;
-    // the local flavour needs every workgroup's share of the k best rows far below the 8 it emits at least: grids of 2 k workgroups
-    // and more (k = 100: matrices of 820k rows and more; P(Poisson(0.5) >= 8) = 2e-7 per workgroup), else the exchange flavour
+    const int blocks = hdb_bits_fused_blocks(a.ntiles, hdb_cu_count(), max_blocks);
     BitsArgs a_eff = a;
-    if ((int64_t)blocks < 2 * (int64_t)a.kk) a_eff.local = 0;
+    if (!hdb_bits_fused_local(blocks, a.kk)) a_eff.local = 0;      // (small grids: the exchange flavour)
     const bool nt = (size_t)a.npad * a.W * 4 > ((size_t)256 << 20);      // the sign bits do not fit the Infinity Cache: stream them past it (5M x 384 = 240 MB still gain from it)
 #define HDB_BITS_LAUNCH(JAC_, QH_)                                                                                          \
     do {                                                                                                                    \

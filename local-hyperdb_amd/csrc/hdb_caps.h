@@ -1,0 +1,193 @@
+// hdb_caps.h -- what each kernel unit can take and the grids its launcher uses, as plain inline functions of plain numbers.
+//
+// Two readers: the launchers (each calls the rule of its own unit from here) and the planner of hdb_topk (hdb_plan.h), which
+// must reach the same answers without a launch.  Nothing here touches HIP: the grid rules take the CU count as an argument, so a
+// host program without a GPU can call every function (tests/test_topk_plan.py).  The constants a rule reads live beside it.
+// Included at the end of hdb_common.h (hdb_elem_bytes, hdb_grid_for).
+#pragma once
+#include "../../include/hyperdb_hip.h"
+
+// ---- hdb_mfma_ksplit.hip: K slices of rows too wide for one wave's query fragments ----
+struct KsGeom { int slices; int dslice; };
+static inline KsGeom ks_geom(int dtype, int d) {
+    if (dtype == HDB_F32 && d == 1024) return {2, 512};
+    if (dtype == HDB_F32 && d == 1536) return {2, 768};
+    if (dtype == HDB_F16 && d == 2048) return {2, 1024};
+    if (dtype == HDB_F16 && d == 3072) return {2, 1536};
+    if (dtype == HDB_F16 && d == 4096) return {4, 1024};
+    return {0, 0};
+}
+static inline int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtype, d).slices; }
+
+// ---- hdb_mfma_bf16.hip ----
+// rows per LDS stage (hdb_mfma_tile_rows): the query fragments of 16 queries take 3 d / 8 registers, so the wider the row the fewer
+// row tiles a wave keeps in flight beside them -- 64 rows up to d = 256, 32 at d = 384, 16 at d = 512
+static inline int hdb_mfma_bf16_tile_rows(int d) { return (d == 128 || d == 256) ? 64 : d == 384 ? 32 : d == 512 ? 16 : 0; }
+
+// ---- hdb_mfma_qt2.hip: two query tiles per wave ----
+static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
+
+// ---- hdb_mfma.hip: the matrix-core scan ----
+// Geometry: rows per LDS stage = the largest of 64 / 32 / 16 whose stage (R * row bytes) fits 48 KiB (three stages + lists
+// <= 160 KiB).  Rows are multiples of 256 bytes (the XOR swizzle works on 16 chunks of 16 bytes), so every d that is a
+// multiple of 128 (fp16) / 64 (fp32) works; the upper limits are the query fragments a wave holds in registers: d/8
+// (fp16) or d/4 (fp32) registers for 16 queries, 192 at most.
+// fp16: 16x16x32 MFMAs, 128 queries per pass (d <= 640 with more than 128 queries: two query tiles per wave, 256 per pass).
+// fp32: 16x16x4 MFMAs, 128 queries per pass; the matrix pipe (157 TFLOP/s) binds from ~16 queries on, so the VALU scan
+// keeps the calls of up to 4 queries (one pass at HBM speed) and this path takes the batches.
+// bfloat16 rows (hdb_mfma_bf16.hip): d = 128, 256, 384 and 512 -- the query fragments of 16 queries take 48, 96, 144 and 192
+// registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted
+
+static inline int mfma_exact_tile_rows(int dtype, int d) {
+    if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
+    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
+    if (!elem || d <= 0) return 0;
+    if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
+    const int row_bytes = d * elem;
+    if (row_bytes % 256 != 0 || row_bytes > 3072) return 0;          // d <= 1536 (fp16) / 768 (fp32)
+    if (dtype == HDB_F32 && d != 128 && d != 256 && d != 384 && d != 512 && d != 768) return 0;     // instantiated fp32 widths
+    for (int r = 64; r >= 16; r >>= 1)
+        if (r * row_bytes <= 48 * 1024) return r;
+    return 0;
+}
+
+// Rows of any width that is a multiple of 16 bytes and has no geometry of its own ride the next wider one as a single K slice
+// (hdb_mfma_anyd.h): -> that width, or 0.  fp16 d % 8 == 0 up to 1024, float32 d % 4 == 0 up to 768.
+static inline int hdb_mfma_anyd_pad(int dtype, int d) {
+    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;      // (bfloat16: its own widths only)
+    if (!elem || d <= 0 || (d * elem) % 16 != 0 || mfma_exact_tile_rows(dtype, d) > 0) return 0;
+    static const int w16[] = {128, 256, 384, 512, 768, 1024}, w32[] = {128, 256, 384, 512, 768};
+    if (dtype == HDB_F16) { for (int w : w16) if (w >= d) return w; }
+    else { for (int w : w32) if (w >= d) return w; }
+    return 0;
+}
+
+static inline int hdb_mfma_tile_rows(int dtype, int d) {
+    const int pad = hdb_mfma_anyd_pad(dtype, d);
+    return mfma_exact_tile_rows(dtype, pad ? pad : d);
+}
+
+// queries ONE launch of the MFMA scan covers (grid.y == 1): what a single-launch (mode 2) call can take
+static inline int hdb_mfma_batch_capacity(int dtype, int d) {
+    if (hdb_mfma_tile_rows(dtype, d) <= 0 || hdb_mfma_ksplit_slices(dtype, d) > 0 || hdb_mfma_anyd_pad(dtype, d) > 0) return 0;      // (K slices, odd widths: the multi-kernel pipeline)
+    if (dtype == HDB_BF16) return 0;                                     // (bfloat16 rows likewise: no single launch is built)
+    if (dtype == HDB_F32) return (d == 512 || d == 768) ? 64 : 128;      // (d = 512 / 768: the bf16-part flavour pairs its waves over K, hdb_mfma_kernel.h KP)
+    return (d == 384 || d == 128 || d == 256 || d == 512 || d == 640) ? 256 : 128;      // two query tiles per wave (hdb_mfma_qt2.hip)
+}
+
+static inline int hdb_mfma_supported(int dtype, int d, int metric) {
+    return hdb_mfma_tile_rows(dtype, d) > 0 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN);
+}
+
+// float32 widths whose scan also exists in bf16 parts (hdb_mfma_f32s.hip) -> the number of queries of a CALL from which that
+// flavour is used (0: no such flavour; the API decides per call, ScanArgs::f32_split).  d <= 384: measured from 16 queries up, never
+// slower than the float32 MFMAs and 1.5-1.7x faster from 48 (profiles/r4_f32_bf16_parts.txt); d = 512 / 768: one wave cannot hold the
+// query fragments of a whole row, the float32 flavour runs 16-row tiles on one SIMD per 16 queries (2x a pass at any batch size), the
+// bf16-part flavour splits K over two waves.
+// Other float32 widths ride these geometries (any multiple of 4 up to 768 as one padded slice, hdb_mfma_anyd.h; 1024 / 1536 as two
+// slices of 512 / 768, hdb_mfma_ksplit.hip) and follow the geometry's rule.
+// ... and the largest call that flavour takes (d = 1024: the paired waves hold 64 queries per launch row, so 65-128 queries read the
+// two slices twice -- 2 650 against 2 350 us at 128 queries on 1M rows, profiles/r4_f32_bf16_parts.txt)
+static inline int hdb_mfma_f32_split_max_q(int d) { return d == 1024 ? 64 : 1 << 30; }
+static inline int hdb_mfma_f32_split_min_q(int d) {
+    if (d == 1024 || d == 1536) return 1;
+    const int g = (d == 128 || d == 256 || d == 384 || d == 512 || d == 768) ? d : hdb_mfma_anyd_pad(HDB_F32, d);
+    return (g == 128 || g == 256 || g == 384) ? 9 : (g == 512 || g == 768) ? 1 : 0;
+}
+
+// ---- hdb_mfma_fused*.hip: the single launch of 1-4 queries ----
+#define HDB_FUSED_MAXQ 4            // queries per fused call
+#define HDB_FUSED_MAX_WG 1024
+static inline int hdb_mfma_fused_supported(int dtype, int d, int metric, int nq, uint32_t kk) {
+    // fp16: every width the batched scan takes (multiples of 128 up to 1536); beyond d = 768 the query fragments (d/8
+    // registers) leave no room for the selectors' state: they stay in LDS, up to 2 queries (hdb_mfma_fused_wide.hip)
+    // (d = 896: 28-KiB tiles of 28 k-steps keep the one multiplying wave busier than the stream: five kernels are 6 % faster)
+    // (d = 128: 16-KiB tiles -- a round of this kernel costs ~1 us whatever the tile holds: 660 vs 400 us at 10 M rows)
+    const bool shape = (dtype == HDB_F16 && hdb_mfma_tile_rows(dtype, d) > 0 && d % 128 == 0 && d != 896 && d != 128 && d <= 1536) ||
+                       (dtype == HDB_F32 && (d == 128 || d == 256 || d == 384 || d == 512 || d == 768));   // float32: VALU flavour
+    // float32 queries live in registers as d/4 floats per lane group: 48 registers = 2 queries up to d = 384, 1 beyond
+    const int maxq = dtype == HDB_F32 ? (d <= 384 ? 2 : 1) : (d <= 768 ? HDB_FUSED_MAXQ : 2);
+    // euclidean (the MFMA expansion + direct re-score of near-duplicates in the last workgroup): fp16 matrices only -- the
+    // float32 VALU pipelines compute the direct difference, which this kernel's float32 flavour does not; d = 768 would spill
+    // three registers (those calls take the batched single launch, hdb_mfma_kernel.h MODE 2)
+    // (euclidean, 2-4 queries: wave 0 pays sqrt + rcp on all 16 MFMA columns -- 199 vs 182 us at N=1.25M d=384 with four queries; those
+    // calls take the batched single launch, where eight waves share the epilogue)
+    // float32 (round 3): the VALU flavour accumulates (v - q)^2 directly, as hdb_scan.hip does -- no cancellation, nothing to
+    // re-score, one or two queries like dot / cosine
+    const bool euclid = metric == HDB_EUCLIDEAN && ((dtype == HDB_F16 && d != 768 && nq == 1) || dtype == HDB_F32);
+    return shape && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_PEARSON || euclid) && nq >= 1 && nq <= maxq && kk <= 128;
+}
+
+// Local flavour (FusedArgs::local, hdb_mfma_fused.h): how many tiles of a workgroup fit its parking area -- 0 where the kernel
+// does not park at all (fp16 d = 768; euclidean d = 640: the parking state would spill there).  Mirrors PARK / pend_max.
+static inline int hdb_mfma_fused_local_tiles(int dtype, int d, int metric, int nq) {
+    if (dtype == HDB_F32) return nq <= 1 || d > 384 ? 16 : 8;
+    const bool park = (d <= 640 && !(metric == HDB_EUCLIDEAN && d > 512)) || d > 768;
+    if (!park) return 0;
+    return nq <= 2 ? 16 : 32 / nq;
+}
+// workgroups of hdb_launch_mfma_fused over `ntiles` tiles: one per CU at most
+static inline int hdb_mfma_fused_blocks(int64_t ntiles, int cus, int max_blocks) {
+    int blocks = (int)(ntiles < cus ? ntiles : cus);
+    if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
+    if (blocks > HDB_FUSED_MAX_WG) blocks = HDB_FUSED_MAX_WG;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+
+// ---- hdb_bits_fused.hip: the single launch of the bit metrics ----
+#ifndef HDB_BITS_THREADS
+#define HDB_BITS_THREADS 1024
+#endif
+#define HDB_BITS_MAXW 512
+static inline int hdb_bits_fused_supported(int metric, int nq, int W, uint32_t kk) {
+    return (metric == HDB_HAMMING || metric == HDB_JACCARD) && nq >= 1 && nq <= 4 && W <= HDB_BITS_MAXW && kk <= 128;
+}
+// workgroups of hdb_launch_bits_fused over `ntiles` 16-row tiles
+static inline int hdb_bits_fused_blocks(int64_t ntiles, int cus, int max_blocks) {
+    int blocks = cus;
+    const int64_t items = ntiles * 4;
+    if ((int64_t)blocks * HDB_BITS_THREADS > items) blocks = (int)((items + HDB_BITS_THREADS - 1) / HDB_BITS_THREADS);
+    if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+// the local flavour needs every workgroup's share of the k best rows far below the 8 it emits at least: grids of 2 k workgroups
+// and more (k = 100: matrices of 820k rows and more; P(Poisson(0.5) >= 8) = 2e-7 per workgroup), else the exchange flavour
+static inline bool hdb_bits_fused_local(int blocks, uint32_t kk) { return (int64_t)blocks >= 2 * (int64_t)kk; }
+
+// ---- hdb_l1_tile.hip: dense manhattan passes ----
+// rows that are multiples of 256 bytes up to 1536 bytes (fp16 d <= 768, float32 d <= 384: two or four float32 queries per wave in registers)
+// Measured against the 4-query scan in one process (profiles/r3_manhattan_tile_vs_scan.txt): fp16 d=384, 5 M rows: 800 vs 1 372 us
+// (2 queries), 1 187 vs 2 558 (5), 1 390 vs 2 728 (8); fp16 d=128: 559 vs 986 (5); float32 d=384, 2 M rows: 594 vs 1 083 (5).
+// One query: equal (the single-query scan keeps it).  fp16 d = 512 keeps two queries per wave, d = 640 / 768 one (two copies of a
+// 768-element query are 96 registers next to the tile chunks: spills); they still share the staged tile between the waves:
+// d = 768, 2.5 M rows: 589 vs 1 231 us (2 queries), 1 531 vs 2 484 (5), 3 674 vs 4 813 (16); d = 512, 4 M rows: 1 275 vs 2 686 (5).
+static inline int hdb_l1_tile_supported(int dtype, int d) {
+    if (dtype == HDB_F16) return d == 128 || d == 256 || d == 384 || d == 512 || d == 640 || d == 768;      // (512: two queries per wave; 640 / 768: one)
+    if (dtype == HDB_F32) return d == 128 || d == 256 || d == 384 || d == 512 || d == 768;      // (512: two queries per wave, 16-row tiles; 768: one)
+    return 0;
+}
+
+// ---- hdb_quant.hip: the int8 shadow and its 5-bit plane ----
+// workgroups a launch over `ntiles` tiles takes (the folded threshold keeps 4 x that many per-wave maxima of the sample pass)
+static inline int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for(ntiles, 4, max_blocks > 0 ? max_blocks : 1024); }
+// The 5-bit plane: units of a row
+static inline int hdb_quant_plane_units(int P) { return (P + 31) / 32; }
+
+// ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
+// widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan
+static inline int hdb_qb_supported(int d) { return d == 128 || d == 256 || d == 384 || d == 512; }
+// wave groups over the queries and query tiles per wave for a chunk of nq queries
+static inline void qb_shape(int nq, int& wq, int& nqt) {
+    const int tq = (nq + 15) / 16;
+    wq = tq <= 4 ? 1 : tq <= 8 ? 2 : 4;
+    nqt = (tq + wq - 1) / wq;
+}
+static inline int hdb_qb_scan_blocks(int64_t ntiles, int nq, int cus, int max_blocks) {
+    int wq, nqt; qb_shape(nq, wq, nqt);
+    const int64_t lim = max_blocks > 0 ? max_blocks : 2 * (int64_t)cus;
+    return hdb_grid_for(ntiles, 4 / wq, (int)(lim < 512 ? lim : 512));
+}
+// slots of wstat every query has after a MODE 0 launch of that many workgroups
+static inline int64_t hdb_qb_slots(int blocks, int nq) { int wq, nqt; qb_shape(nq, wq, nqt); return (int64_t)blocks * (4 / wq) * 4; }

@@ -280,3 +280,5 @@ static inline int hdb_grid_for(int64_t work_items, int per_block, int max_blocks
 
 // ---- what crosses a translation unit: declared once, seen by every unit ----------------------
 #include "hdb_launch.h"
+// ---- what each unit can take, and its launcher's grid: inline rules shared with the planner ----
+#include "hdb_caps.h"

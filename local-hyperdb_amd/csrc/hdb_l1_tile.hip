@@ -266,18 +266,6 @@ static int l1_launch(const ScanArgs& a, int mode, int nq_launch, int blocks, hip
     return b ? l1_launch_one<E, D, R, NQH, 1, true>(a, nq_launch, blocks, st) : l1_launch_one<E, D, R, NQH, 1, false>(a, nq_launch, blocks, st);
 }
 
-// rows that are multiples of 256 bytes up to 1536 bytes (fp16 d <= 768, float32 d <= 384: two or four float32 queries per wave in registers)
-// Measured against the 4-query scan in one process (profiles/r3_manhattan_tile_vs_scan.txt): fp16 d=384, 5 M rows: 800 vs 1 372 us
-// (2 queries), 1 187 vs 2 558 (5), 1 390 vs 2 728 (8); fp16 d=128: 559 vs 986 (5); float32 d=384, 2 M rows: 594 vs 1 083 (5).
-// One query: equal (the single-query scan keeps it).  fp16 d = 512 keeps two queries per wave, d = 640 / 768 one (two copies of a
-// 768-element query are 96 registers next to the tile chunks: spills); they still share the staged tile between the waves:
-// d = 768, 2.5 M rows: 589 vs 1 231 us (2 queries), 1 531 vs 2 484 (5), 3 674 vs 4 813 (16); d = 512, 4 M rows: 1 275 vs 2 686 (5).
-extern "C" int hdb_l1_tile_supported(int dtype, int d) {
-    if (dtype == HDB_F16) return d == 128 || d == 256 || d == 384 || d == 512 || d == 640 || d == 768;      // (512: two queries per wave; 640 / 768: one)
-    if (dtype == HDB_F32) return d == 128 || d == 256 || d == 384 || d == 512 || d == 768;      // (512: two queries per wave, 16-row tiles; 768: one)
-    return 0;
-}
-
 // dense passes only (a.tile_stride == 1): the row sample stays with the 4-query scan.  The caller folds a row mask into the bias.
 extern "C" int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream) {
     const ScanArgs& a = *args;

@@ -1,5 +1,6 @@
 // hdb_launch.h -- every function that crosses a translation unit of the library and is not part of the public ABI
-// (include/hyperdb_hip.h): the launchers of the kernel units and the capability / size helpers beside them.
+// (include/hyperdb_hip.h): the launchers of the kernel units and the size helpers beside them.  (What a unit can take and the grid
+// its launcher uses are inline rules in hdb_caps.h: definitions, not prototypes.)
 //
 // The names are extern "C", so a call through a stale prototype would still link and the callee would read the wrong
 // registers.  Each function is therefore declared HERE ONLY, and every unit that defines one sees this header (through
@@ -59,13 +60,7 @@ int hdb_launch_full_sort(const float* scores, int64_t n, int64_t k, int64_t row_
 int hdb_launch_gather_rows(const void* V, const int64_t* rows, int64_t m, int row_bytes, void* out, const float* inv_in,
                            const float* sq_in, float* inv_out, float* sq_out, int* nan_flag, void* stream);
 
-// ---- hdb_mfma.hip: the matrix-core scan and what it can take ----
-int hdb_mfma_supported(int dtype, int d, int metric);
-int hdb_mfma_tile_rows(int dtype, int d);
-int hdb_mfma_batch_capacity(int dtype, int d);
-int hdb_mfma_anyd_pad(int dtype, int d);
-int hdb_mfma_f32_split_min_q(int d);
-int hdb_mfma_f32_split_max_q(int d);
+// ---- hdb_mfma.hip: the matrix-core scan ----
 size_t hdb_mfma_batch_ctl_bytes(int wgs);
 int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q16, const float* sqnorm,
                          const float* qsq, const float* qscl, int max_blocks, int variant, void* stream, const BatchArgs* f);
@@ -79,7 +74,6 @@ HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_mid);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_1k);
 int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
                                   const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
-int hdb_mfma_qt2_supported(int d);
 int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
                                  const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
 int hdb_launch_mfma_scan_f32(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
@@ -90,12 +84,10 @@ int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, con
                               const float* qsq, int blocks, void* stream, const BatchArgs* f);
 int hdb_launch_mfma_scan_f32s_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                    const float* qsq, int blocks, void* stream, const BatchArgs* f);
-int hdb_mfma_bf16_tile_rows(int d);
 int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                               const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_scan_bf16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                    const float* qsq, int blocks, void* stream);
-int hdb_mfma_ksplit_slices(int dtype, int d);
 int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                            const float* qsq, const float* qscl, int blocks, void* stream);
 int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
@@ -105,14 +97,10 @@ HDB_ANYD_DECL(hdb_launch_mfma_anyd_c); HDB_ANYD_DECL(hdb_launch_mfma_anyd_d);   
 HDB_ANYD_DECL(hdb_launch_mfma_anyd_e); HDB_ANYD_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts
 
 // ---- the single launches: hdb_mfma_fused*.hip, hdb_bits_fused.hip; hdb_l1_tile.hip ----
-int hdb_mfma_fused_supported(int dtype, int d, int metric, int nq, uint32_t kk);
-int hdb_mfma_fused_local_tiles(int dtype, int d, int metric, int nq);
 size_t hdb_mfma_fused_ctl_bytes(void);
 int hdb_launch_mfma_fused(const ScanArgs* args, int dtype, const FusedArgs* fa, int max_blocks, void* stream);
 int hdb_launch_mfma_fused_wide(const ScanArgs* args, const FusedArgs* fa, int blocks, void* stream);
-int hdb_bits_fused_supported(int metric, int nq, int W, uint32_t kk);
 int hdb_launch_bits_fused(const BitsArgs* args, int jaccard, int max_blocks, void* stream);
-int hdb_l1_tile_supported(int dtype, int d);
 int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
 
 // ---- hdb_quant.hip: the int8 shadow and its 5-bit plane ----
@@ -123,11 +111,9 @@ int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t
 int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt, void* stream);
 int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
                              int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
-int hdb_quant_plane_units(int P);
 int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
                                 float* rec, void* stream);
 int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream);
-int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks);
 int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
@@ -142,9 +128,6 @@ int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cn
                               void* stream);
 
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
-int hdb_qb_supported(int d);
-int hdb_qb_scan_blocks(int64_t ntiles, int nq, int max_blocks);
-int64_t hdb_qb_slots(int blocks, int nq);
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);
 int hdb_launch_qb_rescore(const void* V, int d, const void* q16, const float* qscl, const float* qinv, const float* inv_norm,

@@ -73,79 +73,13 @@ __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long l
     }
 }
 
-// Geometry: rows per LDS stage = the largest of 64 / 32 / 16 whose stage (R * row bytes) fits 48 KiB (three stages + lists
-// <= 160 KiB).  Rows are multiples of 256 bytes (the XOR swizzle works on 16 chunks of 16 bytes), so every d that is a
-// multiple of 128 (fp16) / 64 (fp32) works; the upper limits are the query fragments a wave holds in registers: d/8
-// (fp16) or d/4 (fp32) registers for 16 queries, 192 at most.
-// fp16: 16x16x32 MFMAs, 128 queries per pass (d <= 640 with more than 128 queries: two query tiles per wave, 256 per pass).
-// fp32: 16x16x4 MFMAs, 128 queries per pass; the matrix pipe (157 TFLOP/s) binds from ~16 queries on, so the VALU scan
-// keeps the calls of up to 4 queries (one pass at HBM speed) and this path takes the batches.
-// bfloat16 rows (hdb_mfma_bf16.hip): d = 128, 256, 384 and 512 -- the query fragments of 16 queries take 48, 96, 144 and 192
-// registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted
-
-static int mfma_exact_tile_rows(int dtype, int d) {
-    if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
-    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
-    if (!elem || d <= 0) return 0;
-    if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
-    const int row_bytes = d * elem;
-    if (row_bytes % 256 != 0 || row_bytes > 3072) return 0;          // d <= 1536 (fp16) / 768 (fp32)
-    if (dtype == HDB_F32 && d != 128 && d != 256 && d != 384 && d != 512 && d != 768) return 0;     // instantiated fp32 widths
-    for (int r = 64; r >= 16; r >>= 1)
-        if (r * row_bytes <= 48 * 1024) return r;
-    return 0;
-}
-
-// Rows of any width that is a multiple of 16 bytes and has no geometry of its own ride the next wider one as a single K slice
-// (hdb_mfma_anyd.h): -> that width, or 0.  fp16 d % 8 == 0 up to 1024, float32 d % 4 == 0 up to 768.
-extern "C" int hdb_mfma_anyd_pad(int dtype, int d) {
-    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;      // (bfloat16: its own widths only)
-    if (!elem || d <= 0 || (d * elem) % 16 != 0 || mfma_exact_tile_rows(dtype, d) > 0) return 0;
-    static const int w16[] = {128, 256, 384, 512, 768, 1024}, w32[] = {128, 256, 384, 512, 768};
-    if (dtype == HDB_F16) { for (int w : w16) if (w >= d) return w; }
-    else { for (int w : w32) if (w >= d) return w; }
-    return 0;
-}
-
-extern "C" int hdb_mfma_tile_rows(int dtype, int d) {
-    const int pad = hdb_mfma_anyd_pad(dtype, d);
-    return mfma_exact_tile_rows(dtype, pad ? pad : d);
-}
-
-// queries ONE launch of the MFMA scan covers (grid.y == 1): what a single-launch (mode 2) call can take
-extern "C" int hdb_mfma_batch_capacity(int dtype, int d) {
-    if (hdb_mfma_tile_rows(dtype, d) <= 0 || hdb_mfma_ksplit_slices(dtype, d) > 0 || hdb_mfma_anyd_pad(dtype, d) > 0) return 0;      // (K slices, odd widths: the multi-kernel pipeline)
-    if (dtype == HDB_BF16) return 0;                                     // (bfloat16 rows likewise: no single launch is built)
-    if (dtype == HDB_F32) return (d == 512 || d == 768) ? 64 : 128;      // (d = 512 / 768: the bf16-part flavour pairs its waves over K, hdb_mfma_kernel.h KP)
-    return (d == 384 || d == 128 || d == 256 || d == 512 || d == 640) ? 256 : 128;      // two query tiles per wave (hdb_mfma_qt2.hip)
-}
 // bytes of the control block of the single-launch batched call for a grid of `wgs` workgroups
 extern "C" size_t hdb_mfma_batch_ctl_bytes(int wgs) { return (size_t)HDB_BATCH_GRAN_BYTE + (size_t)HDB_BATCH_MAXQ * (size_t)wgs * 8 * 8; }
-
-extern "C" int hdb_mfma_supported(int dtype, int d, int metric) {
-    return hdb_mfma_tile_rows(dtype, d) > 0 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN);
-}
 
 // d=384, more than 128 queries: 16 = 16x16x32 with two query tiles per wave (default: the same FLOPs and LDS
 // traffic as the 32x32x16 form, but the chip holds a higher clock on this shape: 1.78-1.85 ms against 2.07-2.25 ms
 // for N=10M, Q=256), 32 = 32x32x16 with one query tile per wave (kept for A/B measurements).
 // (per index: hdb_set_option(ix, "mfma_variant", 16 | 32), passed down as `variant`)
-
-// float32 widths whose scan also exists in bf16 parts (hdb_mfma_f32s.hip) -> the number of queries of a CALL from which that
-// flavour is used (0: no such flavour; the API decides per call, ScanArgs::f32_split).  d <= 384: measured from 16 queries up, never
-// slower than the float32 MFMAs and 1.5-1.7x faster from 48 (profiles/r4_f32_bf16_parts.txt); d = 512 / 768: one wave cannot hold the
-// query fragments of a whole row, the float32 flavour runs 16-row tiles on one SIMD per 16 queries (2x a pass at any batch size), the
-// bf16-part flavour splits K over two waves.
-// Other float32 widths ride these geometries (any multiple of 4 up to 768 as one padded slice, hdb_mfma_anyd.h; 1024 / 1536 as two
-// slices of 512 / 768, hdb_mfma_ksplit.hip) and follow the geometry's rule.
-// ... and the largest call that flavour takes (d = 1024: the paired waves hold 64 queries per launch row, so 65-128 queries read the
-// two slices twice -- 2 650 against 2 350 us at 128 queries on 1M rows, profiles/r4_f32_bf16_parts.txt)
-extern "C" int hdb_mfma_f32_split_max_q(int d) { return d == 1024 ? 64 : 1 << 30; }
-extern "C" int hdb_mfma_f32_split_min_q(int d) {
-    if (d == 1024 || d == 1536) return 1;
-    const int g = (d == 128 || d == 256 || d == 384 || d == 512 || d == 768) ? d : hdb_mfma_anyd_pad(HDB_F32, d);
-    return (g == 128 || g == 256 || g == 384) ? 9 : (g == 512 || g == 768) ? 1 : 0;
-}
 
 // a.ntiles / a.tile_stride are in units of hdb_mfma_tile_rows(dtype, d) rows here.  q: the query fragments' source --
 // scaled fp16 copies (+ qscl) for fp16 matrices, the float32 queries themselves (qscl = nullptr) for fp32 ones.

@@ -6,10 +6,6 @@
 // d = 128 / 256 here, 384 / 512 in hdb_mfma_bf16_b.hip (translation units of their own so that the instantiations compile in parallel).
 #include "hdb_mfma_kernel.h"
 
-// rows per LDS stage (hdb_mfma_tile_rows): the query fragments of 16 queries take 3 d / 8 registers, so the wider the row the fewer
-// row tiles a wave keeps in flight beside them -- 64 rows up to d = 256, 32 at d = 384, 16 at d = 512
-extern "C" int hdb_mfma_bf16_tile_rows(int d) { return (d == 128 || d == 256) ? 64 : d == 384 ? 32 : d == 512 ? 16 : 0; }
-
 extern "C" int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                          const float* qsq, int blocks, void* stream) {
     const ScanArgs& a = *args;

@@ -58,10 +58,8 @@ static __device__ unsigned long long hdb_fused_stamps[16 * HDB_CLOCK_WGS_F];
 
 #include "hdb_mfma_kernel.h"          // (includes hdb_finalize.h: the stamp macros above must come first)
 
-#define HDB_FUSED_MAXQ 4            // queries per fused call
 #define HDB_FUSED_M 8               // sample order statistic (k <= 128)
 #define HDB_FUSED_GRAN_PER_WG 32    // HDB_FUSED_MAXQ * HDB_FUSED_M granules per workgroup
-#define HDB_FUSED_MAX_WG 1024
 // Control block (FusedArgs::ctl, zero when allocated, tagged by epoch afterwards), in bytes:
 //   0   ticket, abort word, per-query candidate counts (uint32 [0..5])
 //   128 tile counter (a line of its own: ~35-70 atomics per us)

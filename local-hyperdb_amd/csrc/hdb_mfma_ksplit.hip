@@ -11,17 +11,6 @@
 // float32 d = 1536 matrix: 2 x 2 launches instead of 64 passes).
 #include "hdb_mfma_kernel.h"
 
-struct KsGeom { int slices; int dslice; };
-static KsGeom ks_geom(int dtype, int d) {
-    if (dtype == HDB_F32 && d == 1024) return {2, 512};
-    if (dtype == HDB_F32 && d == 1536) return {2, 768};
-    if (dtype == HDB_F16 && d == 2048) return {2, 1024};
-    if (dtype == HDB_F16 && d == 3072) return {2, 1536};
-    if (dtype == HDB_F16 && d == 4096) return {4, 1024};
-    return {0, 0};
-}
-extern "C" int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtype, d).slices; }
-
 // args->ks_partial_out: [nq_launch][ks_ld] float32 scratch of the caller (MODE 0 passes may alias it with args->scores: the last
 // slice overwrites the sums with the scores, element by element, by the lane that read them)
 extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,

@@ -3,8 +3,6 @@
 // 129..256 queries then reads V once instead of once per 128 queries.  d = 768 spills with two tiles and keeps one.
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
-
 extern "C" int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
                                             const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f) {
     const ScanArgs& a = *args;

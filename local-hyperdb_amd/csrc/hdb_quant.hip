@@ -977,8 +977,6 @@ static void hq_launch_scan_mode(const QuantArgs& a, int blocks, size_t lds, hipS
     default: hq_launch_scan_nq<MODE, 4>(a, blocks, lds, st); break;
     }
 }
-// workgroups a launch over `ntiles` tiles takes (the folded threshold keeps 4 x that many per-wave maxima of the sample pass)
-extern "C" int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for(ntiles, 4, max_blocks > 0 ? max_blocks : 1024); }
 // mode 0: lower bounds of the sampled tiles; mode 1: candidate emission over a.ntiles dense tiles.  1 <= a.nq <= 4.
 extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream) {
     const QuantArgs& a = *args;
@@ -991,8 +989,7 @@ extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_bl
     return (int)hipGetLastError();
 }
 
-// The 5-bit plane: units of a row, bytes per row, derivation, pass 1 and pass 2 (one query; dot / cosine).
-extern "C" int hdb_quant_plane_units(int P) { return (P + 31) / 32; }
+// The 5-bit plane: derivation, pass 1 and pass 2 (one query; dot / cosine).
 extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib,
                                            uint32_t* bitw, float* rec, void* stream) {
     if (m <= 0) return 0;

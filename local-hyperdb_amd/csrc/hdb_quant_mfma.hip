@@ -324,23 +324,6 @@ __global__ __launch_bounds__(256) void hdb_qb_rescore_kernel(QbRescoreArgs a) {
 // ------------------------------------------------------------------------------------------------------------------------
 // host-side launchers
 // ------------------------------------------------------------------------------------------------------------------------
-// widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan
-extern "C" int hdb_qb_supported(int d) { return d == 128 || d == 256 || d == 384 || d == 512; }
-
-// wave groups over the queries and query tiles per wave for a chunk of nq queries
-static void qb_shape(int nq, int& wq, int& nqt) {
-    const int tq = (nq + 15) / 16;
-    wq = tq <= 4 ? 1 : tq <= 8 ? 2 : 4;
-    nqt = (tq + wq - 1) / wq;
-}
-extern "C" int hdb_qb_scan_blocks(int64_t ntiles, int nq, int max_blocks) {
-    int wq, nqt; qb_shape(nq, wq, nqt);
-    const int64_t lim = max_blocks > 0 ? max_blocks : 2 * (int64_t)hdb_cu_count();
-    return hdb_grid_for(ntiles, 4 / wq, (int)(lim < 512 ? lim : 512));
-}
-// slots of wstat every query has after a MODE 0 launch of that many workgroups
-extern "C" int64_t hdb_qb_slots(int blocks, int nq) { int wq, nqt; qb_shape(nq, wq, nqt); return (int64_t)blocks * (4 / wq) * 4; }
-
 template <int MODE, int KS>
 static void qb_launch_ks(const QbArgs& g, int nqt, int blocks, hipStream_t st) {
     switch (nqt) {
@@ -369,7 +352,7 @@ extern "C" int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat,
     const QuantArgs& a = g.q;
     if (a.nq < 1 || a.nq > 256 || !hdb_qb_supported(a.d) || a.P != a.d || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
     int nqt; qb_shape(a.nq, g.wq, nqt);
-    const int blocks = hdb_qb_scan_blocks(a.ntiles, a.nq, max_blocks);
+    const int blocks = hdb_qb_scan_blocks(a.ntiles, a.nq, hdb_cu_count(), max_blocks);
     if (mode == 0 && (!wstat || wld < hdb_qb_slots(blocks, a.nq))) return (int)hipErrorInvalidValue;
     return mode == 0 ? qb_launch_mode<0>(g, nqt, blocks, (hipStream_t)stream) : qb_launch_mode<1>(g, nqt, blocks, (hipStream_t)stream);
 }
