@@ -238,7 +238,15 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     cores (hdb_mfma_bf16.hip), multi-kernel pipeline.  A float32 query travels as three bf16 parts that add up to it exactly,
  *     a row is one bf16: three v_mfma_f32_16x16x32_bf16 per k-step, every product exact, float32 accumulation.  A query element
  *     that is not finite keeps its first part only, so no inf - inf is formed and the status words stay 0.  A matrix with an
- *     infinite (or overflowing) row stays on the VALU scan (inf x 0 would be NaN where np.dot gives inf).  Other widths stay on the VALU scan.
+ *     infinite (or overflowing) row stays on the VALU scan (inf x 0 would be NaN where np.dot gives inf).
+ *   - the same calls on wider rows -- d = 640, 768, 896, 1024, 1152, 1280, 1408, 1536, 2048, 3072 or 4096 -- take the matrix cores
+ *     through K slices (hdb_mfma_bf16_ks.hip): a wave holds the three query parts of 512 elements at most, so a row is cut into the
+ *     fewest slices of 512 / 384 / 256 elements, the widest first (768 = 2 x 384, 1024 = 2 x 512, 1280 = 512 + 2 x 384, 1536 = 3 x 512,
+ *     4096 = 8 x 512), one launch per slice and pass, at most 128 queries per chunk.  The matrix is still read once per pass; the
+ *     partial sums travel through a [query][rows] float32 workspace: +8 bytes per row, query and extra slice.  Same arithmetic, same
+ *     treatment of non-finite values, pearson as cosine on centred queries.  The slices start where they were measured to beat
+ *     the two VALU passes that 5-8 queries cost: from 5 queries at d = 1024 and 4096, from 9 at the other widths (option
+ *     bf16_ks_min_q: -1 = that rule, else a fixed number of queries, never fewer than 5).  Other widths stay on the VALU scan.
  *   - never: the single launches of the matrix-core paths (fused = 0 always), the int8 shadow (hdb_index_quantize returns
  *     HDB_ERR_UNSUPPORTED, auto_quant does not apply).
  * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch), path as for the other dtypes. */

@@ -8,14 +8,65 @@
 #include "../../include/hyperdb_hip.h"
 
 // ---- hdb_mfma_ksplit.hip: K slices of rows too wide for one wave's query fragments ----
-struct KsGeom { int slices; int dslice; };
+// The slice list of a width: slice s covers `width[s]` elements of every row from byte `off[s]` of the stored row on; the widths
+// add up to d and every one of them is a slice geometry that is instantiated for the dtype (float32 512 / 768, fp16 1024 / 1536,
+// bfloat16 256 / 384 / 512).
+#define HDB_KS_MAX_SLICES 8
+struct KsGeom {
+    int slices;                           // 0: the width has no K slices
+    int width[HDB_KS_MAX_SLICES];
+    int off[HDB_KS_MAX_SLICES];
+};
+// n0 slices of w0 elements, then n1 of w1
+static inline KsGeom ks_list(int elem_bytes, int n0, int w0, int n1 = 0, int w1 = 0) {
+    KsGeom g = {};
+    int at = 0;
+    for (int s = 0; s < n0 + n1 && s < HDB_KS_MAX_SLICES; ++s) {
+        g.width[s] = s < n0 ? w0 : w1; g.off[s] = at * elem_bytes;
+        at += g.width[s];
+    }
+    g.slices = n0 + n1;
+    return g;
+}
+// bfloat16 (hdb_mfma_bf16_ks.hip): the query fragments of 16 queries take 3/8 of a register per element (three bf16 parts), so a
+// slice is 512 elements at most -- every multiple of 128 from 640 to 1536 as the fewest slices of 512 / 384 / 256, the widest first,
+// and 2048 / 3072 / 4096 as slices of 512
+static inline KsGeom ks_geom_bf16(int d) {
+    switch (d) {
+        case 640: return ks_list(2, 1, 384, 1, 256);
+        case 768: return ks_list(2, 2, 384);
+        case 896: return ks_list(2, 1, 512, 1, 384);
+        case 1024: return ks_list(2, 2, 512);
+        case 1152: return ks_list(2, 3, 384);
+        case 1280: return ks_list(2, 1, 512, 2, 384);
+        case 1408: return ks_list(2, 2, 512, 1, 384);
+        case 1536: return ks_list(2, 3, 512);
+        case 2048: return ks_list(2, 4, 512);
+        case 3072: return ks_list(2, 6, 512);
+        case 4096: return ks_list(2, 8, 512);
+        default: return ks_list(2, 0, 0);
+    }
+}
+// ... and the number of queries of a call from which the bfloat16 slices are used (the planner's bf16_ks_min_q = -1).  Up to 8 queries
+// are two VALU passes at HBM speed; the slices read the matrix once, but in 16-row stages of 8-16 KiB (two tiles in flight per CU)
+// and with one launch per slice and pass.  Measured, one box, the two paths alternating call by call, cosine top-100, p50 in us, slices vs
+// VALU scan at 5 / 8 / 16 queries on ~1.5 GB of rows (profiles/bf16_wide_time.txt):
+//   640: 591 vs 515, 621 vs 534, 653 vs 1035     768: 547 vs 510, 576 vs 524, 593 vs 1017     896: 521 vs 517, 539 vs 516, 566 vs 1008
+//  1024: 621 vs 669, 641 vs 668, 678 vs 1318    1152: 613 vs 510, 630 vs 510, 654 vs 1000    1280: 595 vs 517, 615 vs 522, 647 vs 1015
+//  1408: 574 vs 523, 594 vs 530, 616 vs 1029    1536: 556 vs 522, 578 vs 531, 595 vs 1026    2048: 632 vs 593, 654 vs 586, 676 vs 1093
+//  3072: 654 vs 652, 684 vs 653, 700 vs 1067    4096: 746 vs 1386, 785 vs 2144, 790 vs 4196
+// The slices win from 5 queries at d = 1024 and 4096 and lose by 1-19 % at 5 and 8 queries everywhere else; at 16 they win 1.5-5.3x
+// at every width.  9-15 queries were not measured: a third VALU pass is 1.5 x the two-pass figure (>= 765 us), above every slice time
+// at 8 and 16 queries, so the other widths start at 9.
+static inline int hdb_mfma_bf16_ks_min_q(int d) { return (d == 1024 || d == 4096) ? 5 : 9; }
 static inline KsGeom ks_geom(int dtype, int d) {
-    if (dtype == HDB_F32 && d == 1024) return {2, 512};
-    if (dtype == HDB_F32 && d == 1536) return {2, 768};
-    if (dtype == HDB_F16 && d == 2048) return {2, 1024};
-    if (dtype == HDB_F16 && d == 3072) return {2, 1536};
-    if (dtype == HDB_F16 && d == 4096) return {4, 1024};
-    return {0, 0};
+    if (dtype == HDB_F32 && d == 1024) return ks_list(4, 2, 512);
+    if (dtype == HDB_F32 && d == 1536) return ks_list(4, 2, 768);
+    if (dtype == HDB_F16 && d == 2048) return ks_list(2, 2, 1024);
+    if (dtype == HDB_F16 && d == 3072) return ks_list(2, 2, 1536);
+    if (dtype == HDB_F16 && d == 4096) return ks_list(2, 4, 1024);
+    if (dtype == HDB_BF16) return ks_geom_bf16(d);
+    return ks_list(1, 0, 0);
 }
 static inline int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtype, d).slices; }
 
@@ -36,9 +87,11 @@ static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 ||
 // fp32: 16x16x4 MFMAs, 128 queries per pass; the matrix pipe (157 TFLOP/s) binds from ~16 queries on, so the VALU scan
 // keeps the calls of up to 4 queries (one pass at HBM speed) and this path takes the batches.
 // bfloat16 rows (hdb_mfma_bf16.hip): d = 128, 256, 384 and 512 -- the query fragments of 16 queries take 48, 96, 144 and 192
-// registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted
+// registers (three bf16 parts); the d = 512 kernels build with 241-256 registers and no scratch, so the width is admitted.  Wider
+// bfloat16 rows (640 .. 1536 in steps of 128, 2048 / 3072 / 4096) are cut into K slices of those widths (ks_geom_bf16)
 
 static inline int mfma_exact_tile_rows(int dtype, int d) {
+    if (dtype == HDB_BF16 && d > 0 && hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;     // 640 .. 4096: K slices of 16-row stages (hdb_mfma_bf16_ks.hip)
     if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
     const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
     if (!elem || d <= 0) return 0;

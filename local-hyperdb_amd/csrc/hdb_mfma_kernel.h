@@ -284,7 +284,8 @@ template <> struct MfmaShape<16, hdb_f32s> {
 // bfloat16 rows (HDB_BF16): the bytes in memory are the A fragments as they stand -- the LDS ring, swizzle and fragment map of the fp16
 // flavour, no conversion, one 16-byte chunk per lane and k-step.  The float32 queries travel as three exact bf16 parts
 // (hdb_split3_finite), built once per launch in the prologue: v . q = v p2 + v p1 + v p0, smallest part first, every product exact
-// (8 x 8 significant bits), the only rounding is the float32 accumulation.  3 x d/8 registers of query fragments per 16 queries.
+// (8 x 8 significant bits), the only rounding is the float32 accumulation.  3 x d/8 registers of query fragments per 16 queries:
+// 192 at d = 512, the widest row (or K slice, KSL: rows of 640 .. 4096 elements, hdb_mfma_bf16_ks.hip) a wave takes.
 template <> struct MfmaShape<16, hdb_bf16> {
     using Acc = f32x4; using Vec = u32x4; using BVec = HdbParts3;
     static constexpr int RPF = 1;
@@ -365,8 +366,8 @@ __global__ __launch_bounds__(NW * 64) void hdb_mfma_kernel(ScanArgs a, const E* 
     static_assert(MODE != 3 || (KSL && METRIC == 0 && !HAS_BIAS), "MODE 3 = raw partial sums of a K slice");
     static_assert(!KSL || (MODE != 2 && NW == 8), "K slices run in the multi-kernel pipeline");
 
-    constexpr bool BF16R = HdbIsBf16Rows<E>::value; // bf16 rows, float32 queries in three parts: the multi-kernel pipeline, whole rows
-    static_assert(!BF16R || (MODE != 2 && MODE != 3 && !KSL && KP == 1 && NW == 8 && MF == 16), "bf16 rows: MODE 0 / 1 only");
+    constexpr bool BF16R = HdbIsBf16Rows<E>::value; // bf16 rows, float32 queries in three parts: the multi-kernel pipeline, whole rows or K slices
+    static_assert(!BF16R || (MODE != 2 && KP == 1 && NW == 8 && MF == 16), "bf16 rows: MODE 0 / 1, MODE 3 in K slices");
 
     constexpr bool FILT = MODE == 1 || MODE == 2;   // the pass over all rows filters against per-query thresholds
     constexpr bool ONE = MODE == 2;             // the whole call in this launch
@@ -407,7 +408,10 @@ __global__ __launch_bounds__(NW * 64) void hdb_mfma_kernel(ScanArgs a, const E* 
         ql[qt] = q - a.q0;
         const int qq = q_ok[qt] ? q : (nq_end - 1);
         if constexpr (BF16R) {          // the lane's 8 k slots of step s are floats 8 (CPS s + h) .. + 7 of the float32 query
-            const float4* qf = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(q16) + (int64_t)qq * D) + 2 * h;
+            // (a K slice: the query's pitch is the full row and ks_off counts bytes of the STORED row, two per element.  Whole slices
+            //  only: bf16 rows have no padded widths, ks_valid is not looked at)
+            const float* qrow = reinterpret_cast<const float*>(q16) + (KSL ? (int64_t)qq * a.ks_dfull + a.ks_off / ES : (int64_t)qq * D);
+            const float4* qf = reinterpret_cast<const float4*>(qrow) + 2 * h;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 float4 x0 = qf[2 * CPS * s], x1 = qf[2 * CPS * s + 1];

@@ -25,6 +25,7 @@ struct hdb_options {
     int64_t f32_min_q = -1;           // float32 matrices: the matrix-core scan from this many queries on
     int64_t f32_split = 1;            // ... as bf16 parts (hdb_mfma_f32s.hip) where that flavour exists, the matrix is finite and the call has at least
     int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
+    int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
     int64_t host_direct = 1;          // hdb_topk_host: kernels write a pinned host record themselves (no D2H copy)
     int64_t dyn_tiles = 1;            // MFMA filter pass: hand tiles out from a counter (0: static split)
@@ -242,7 +243,10 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int64_t f32_min_q = o.f32_min_q >= 0 ? o.f32_min_q : ((ix.d <= 384 && n >= 300000) ? 3 : 5);
     // (widths without a geometry of their own ride the next wider one through the multi-kernel pipeline: like the K slices, from five queries on)
     // (bfloat16 rows, hdb_mfma_bf16.hip, likewise: up to 4 queries are one VALU pass with unrounded float32 queries)
-    const int64_t min_q = (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || hdb_mfma_anyd_pad(ix.dtype, ix.d) > 0 || ix.dtype == HDB_BF16) ? std::max<int64_t>(o.mfma_min_q, 5)
+    // (... and in K slices, d > 512, from the width's measured crossover with the two VALU passes that 5-8 queries cost: hdb_mfma_bf16_ks_min_q)
+    const int64_t bf16_ks_min_q = (ix.dtype == HDB_BF16 && hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0)
+                                      ? (o.bf16_ks_min_q >= 0 ? o.bf16_ks_min_q : (int64_t)hdb_mfma_bf16_ks_min_q(ix.d)) : 0;
+    const int64_t min_q = (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || hdb_mfma_anyd_pad(ix.dtype, ix.d) > 0 || ix.dtype == HDB_BF16) ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), bf16_ks_min_q)
                         : ix.dtype == HDB_F32 ? std::max<int64_t>(o.mfma_min_q, f32_min_q) : o.mfma_min_q;
     // hdb_mfma_fused_kernel is built around ONE multiplying wave and two selector waves: with 2-4 fp16 queries its sample phase and
     // epilogue cost more than the batched single launch (eight multiplying waves) until the pass itself dominates -- n = 100k x 384,
