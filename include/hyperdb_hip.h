@@ -206,6 +206,32 @@ int hdb_recency_bias_twice(const double* dev_ts, const uint8_t* dev_mask, int64_
  * while at least k rows are included. */
 int hdb_index_set_row_mask(hdb_index* ix, const uint8_t* dev_mask);
 
+/* Row mask plus the ascending list of the rows it keeps: a selective filter reads only the rows it keeps (hdb_scan.hip, the list
+ * flavour of the VALU scan).  dev_mask: n bytes as for hdb_index_set_row_mask.  dev_rows: the m local row ids with
+ * dev_mask[r] != 0, strictly ascending, int64, device, borrowed like the mask (m >= 1; NULL = a plain mask).  The caller
+ * guarantees that list and mask describe the same rows; the library does not check it on the device.  Eligible calls score
+ * only the listed rows, every other call uses the mask.  Both NULL clears.  hdb_index_set_row_mask drops the list;
+ * hdb_index_extend, hdb_index_update and hdb_index_gather drop it with mask and bias; hdb_index_rebase keeps it.
+ *
+ * Dispatch.  A hdb_topk / hdb_topk_exact / hdb_topk_host call takes the list when use_subset is on (default 1), the metric is
+ * dot, cosine, euclidean, manhattan or pearson (hamming and jaccard read the packed sign bits and keep the mask), the matrix has
+ * at least subset_min_n rows (-1: the rule of hdb_plan.h, never below 32 768), m * ceil(nq / 4) * subset_ratio <= n (-1: the
+ * rule of hdb_plan.h; else an integer >= 1) and the same call on a matrix of m rows is the multi-kernel pipeline: k > 2048 on
+ * more than 8192 listed rows keeps the mask.  Every dtype is served.  The call then runs the plan of that m-row matrix with
+ * use_mfma = 0, use_fused = 0, use_quant = 0, use_l1_tile = 0 -- small (m <= 8192), sampled or exact -- over the listed rows:
+ * ceil(m / 16) tiles of list positions, position j in the place of row j, 1/||v||, the pearson scale and the bias taken from the
+ * true row, the true row in every candidate.  hdb_topk_host re-runs a failed sampled list call exactly over the list.
+ *
+ * Contract.  Indices, float32 score bits and status words equal those of the same call on a fresh index registered over
+ * V[rows] with bias[rows] and those four options off, indices mapped through rows and row_base added; with fewer than k listed
+ * rows the tail is -1 / -inf.  Against the masked call of the same handle the result is the same modulo ties within the
+ * dtype's tolerance (1e-3 float16, 1e-5 otherwise); the bits may differ because a default float16 index rounds float32 queries
+ * to float16 for the matrix cores and the list path does not, and because a row's slot in the reduction tree is j & 3 instead
+ * of row & 3.  A call that does not take the list is the masked call, bit for bit.
+ * Stats: subset (the last call scored from the list), subset_rows (m of the list currently set, 0 = none); path, chunks,
+ * sample_rows and sample_m are those of the plan that ran, mfma = fused = quant = 0. */
+int hdb_index_set_row_subset(hdb_index* ix, const uint8_t* dev_mask, const int64_t* dev_rows, int64_t m);
+
 /* Full score vector of one query: the per-metric functions dot_product / cosine_similarity /
  * euclidean_metric / hamming_distance (... :24,:32,:44,:128).  dev_q: d elements, float32 for
  * F16/F32/BF16 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */

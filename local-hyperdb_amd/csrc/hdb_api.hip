@@ -69,6 +69,9 @@ struct hdb_index {
     // borrowed
     const float* bias = nullptr;
     const uint8_t* mask = nullptr;
+    // ... and, beside the mask, the ascending list of the rows it keeps (hdb_index_set_row_subset): subset_m > 0 only with both set
+    const int64_t* rows = nullptr;
+    int64_t subset_m = 0;
     // mask folded into a bias vector for the MFMA scan (owned, rebuilt per call: the mask and bias are borrowed)
     float* mbias = nullptr;
     int64_t mbias_rows = 0;
@@ -325,7 +328,7 @@ extern "C" int hdb_index_update(hdb_index* ix, const void* dev_V, int64_t n, voi
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_update: at most 2^32-2 rows per shard");
     HIP_TRY(hipSetDevice(ix->device));
     ix->V = dev_V; ix->n = n;
-    ix->bias = nullptr; ix->mask = nullptr;
+    ix->bias = nullptr; ix->mask = nullptr; ix->rows = nullptr; ix->subset_m = 0;
     ix->qauto_declined = false;                        // a new matrix: the memory question is asked again
     ix->plane_declined = false;
     int rc = build_caches(ix, (hipStream_t)stream);
@@ -385,6 +388,7 @@ extern "C" int hdb_index_extend(hdb_index* ix, int64_t new_n, void* stream) {
     ix->bits_valid = false;                            // (bits_done / pscale_done stay: the next hamming / pearson call packs the appended rows only)
     ix->pscale_valid = false;
     ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old length no longer apply
+    ix->rows = nullptr; ix->subset_m = 0;
     ix->build_stream = st;
     return HDB_OK;
 }
@@ -428,7 +432,7 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     }
     ix->flags_host = -1;
     ix->bits_valid = false; ix->pscale_valid = false; ix->bits_done = 0; ix->pscale_done = 0;
-    ix->bias = nullptr; ix->mask = nullptr;
+    ix->bias = nullptr; ix->mask = nullptr; ix->rows = nullptr; ix->subset_m = 0;
     ix->build_stream = st;
     return HDB_OK;
 }
@@ -479,6 +483,16 @@ extern "C" int hdb_index_set_bias(hdb_index* ix, const float* dev_bias) {
 extern "C" int hdb_index_set_row_mask(hdb_index* ix, const uint8_t* dev_mask) {
     if (!ix) return fail(HDB_ERR_ARG, "hdb_index_set_row_mask: null index");
     ix->mask = dev_mask;
+    ix->rows = nullptr; ix->subset_m = 0;               // a stale list never sits beside a new mask
+    return HDB_OK;
+}
+
+extern "C" int hdb_index_set_row_subset(hdb_index* ix, const uint8_t* dev_mask, const int64_t* dev_rows, int64_t m) {
+    if (!ix) return fail(HDB_ERR_ARG, "hdb_index_set_row_subset: null index");
+    if (dev_rows && !dev_mask) return fail(HDB_ERR_ARG, "hdb_index_set_row_subset: a row list needs its mask");
+    if (dev_rows && (m < 1 || m > ix->n)) return fail(HDB_ERR_ARG, "hdb_index_set_row_subset: m must be in [1, n]");
+    ix->mask = dev_mask;
+    ix->rows = dev_rows; ix->subset_m = dev_rows ? m : 0;
     return HDB_OK;
 }
 
@@ -524,6 +538,9 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "use_plane")) ix->opt.use_plane = value;
     else if (!strcmp(name, "plane_min_n")) ix->opt.plane_min_n = value;
     else if (!strcmp(name, "plane_cap_rows")) ix->opt.plane_cap_rows = std::max<int64_t>(0, value);
+    else if (!strcmp(name, "use_subset")) ix->opt.use_subset = value;
+    else if (!strcmp(name, "subset_min_n")) ix->opt.subset_min_n = value < 0 ? -1 : value;
+    else if (!strcmp(name, "subset_ratio")) ix->opt.subset_ratio = value < 0 ? -1 : std::max<int64_t>(1, value);
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -546,6 +563,8 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
     else if (!strcmp(name, "plane")) *value = ix->st.plane;
+    else if (!strcmp(name, "subset")) *value = ix->st.subset;
+    else if (!strcmp(name, "subset_rows")) *value = ix->subset_m;
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
@@ -728,7 +747,7 @@ extern "C" int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* d
 struct TopkArgs { const void* Q; int32_t nq, k; int metric; int64_t* idx; float* score; int32_t* status; hipStream_t st; };
 static TopkFacts topk_facts(const hdb_index* ix) {
     return {ix->n, ix->d, ix->dtype, ix->qmode, ix->qauto, ix->qauto_declined, ix->pnib != nullptr, ix->plane_declined,
-            ix->mask != nullptr, ix->bias != nullptr, hdb_cu_count()};
+            ix->mask != nullptr, ix->bias != nullptr, hdb_cu_count(), ix->subset_m};
 }
 
 // The workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h): the memory guard of the automatic build sizes with these extents,
@@ -1105,6 +1124,9 @@ static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
 
 // The multi-kernel pipeline, cq_max queries at a time.  small: thr = -inf -> scan(filter) -> finalize; sampled: scan(scores) over the
 // row sample -> threshold -> scan(filter) over all rows -> finalize; exact: scan(scores) over all rows -> radix passes -> collect.
+// p.subset: the same three shapes over the m rows of the index's list (ScanArgs::rows / m) -- the plan is that of a matrix of m
+// rows, "all rows" are the listed ones, no mask (every listed row is kept), the bias unfolded and indexed by the true row; the
+// exact shape collects list positions and rewrites them to rows before finalize.
 static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     TopkEnv e;
     int rc = topk_begin(ix, c, p, e); if (rc) return rc;
@@ -1117,7 +1139,7 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
     const void* Qeff = e.Qeff; const int metric_eff = e.metric_eff; const float* bias_eff = e.bias_eff; const uint8_t* mask_eff = e.mask_eff;
     const bool small = p.small, exact = p.exact, mfma = p.mfma, f32s = p.f32s, fold_small = p.fold_small, f16_queries = p.f16_queries, is_pearson = p.pearson, q16_in_prep = p.q16_in_prep;
-    const int64_t n = ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
+    const int64_t n = p.subset ? ix->subset_m : ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
     const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, tile_rows = p.tile_rows, npass = p.npass;
     bool q16_ready = q16_in_prep;
     for (int q0 = 0; q0 < nq; q0 += cq_max) {
@@ -1129,6 +1151,7 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         a.q0 = q0; a.bias = bias_eff; a.mask = mask_eff; a.f32_split = f32s ? 1 : 0;
         a.thr = thr; a.cnt = cnt; a.cand = cand;
         a.ntiles = (n + tile_rows - 1) / tile_rows;
+        if (p.subset) { a.rows = ix->rows; a.m = ix->subset_m; a.mask = nullptr; a.bias = ix->bias; }
         a.ks_partial_out = kbuf; a.ks_ld = ld_n;         // (K slices only; sample and exact passes index it by their own tile sequence)
 
         if (small) {
@@ -1162,6 +1185,7 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
             HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)((char*)hist - (char*)cnt) + (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
             for (int ps = 0; ps < npass; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, n, ld_n, cq, hist, ps, kk, st));
             LAUNCH_TRY(hdb_launch_collect(sbuf, n, ld_n, cq, hist, npass, kk, cnt, cand, HDB_CAND_CAP, tie_info, st));
+            if (p.subset) LAUNCH_TRY(hdb_launch_list_rows(cand, cnt, HDB_CAND_CAP, cq, ix->rows, ix->subset_m, st));
         }
         if (mfma && metric == HDB_EUCLIDEAN)     // the MFMA path scores through ||v||^2+||q||^2-2v.q: redo near-duplicates directly
             LAUNCH_TRY(hdb_launch_rescore_euclid(cand, cnt, HDB_CAND_CAP, cq, ix->V, ix->dtype, ix->d, (const float*)dev_Q, qsq, q0, ix->bias, st));

@@ -65,6 +65,9 @@ struct ScanArgs {
                             // geometry of the next multiple of 256 bytes (hdb_mfma_anyd_*.hip): chunks past the end of a row are not fetched
                             // (the staging re-reads chunk 0 instead) and the query fragments are zero there, so they add nothing
     const float* ks_partial_in; float* ks_partial_out; int64_t ks_ld;
+    // Row-list scan (hdb_scan.hip, the LIST flavour; nullptr / 0 = dense): the tiles walk the m positions of an ascending list of
+    // row ids instead of the matrix -- position j reads row rows[min(j, m - 1)] -- and ntiles / tile_stride count list tiles
+    const int64_t* rows; int64_t m;
 };
 
 // Extra arguments of the single-launch top-k (hdb_mfma_fused.h): sample plan, exchange block, outputs.

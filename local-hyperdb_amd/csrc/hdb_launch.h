@@ -25,6 +25,7 @@ struct QuantArgs;       // hdb_quant.h
 extern "C" {
 // ---- hdb_scan.hip: the VALU row scan, per-row caches, query prep ----
 int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream);
+int hdb_launch_list_rows(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, const int64_t* rows, int64_t m, void* stream);
 int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, float* inv_norm, float* sqnorm, int* nan_flag, void* stream);
 int hdb_launch_qprep(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl, void* stream);
 int hdb_launch_qprep2(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,

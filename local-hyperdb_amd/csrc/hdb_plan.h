@@ -53,6 +53,9 @@ struct hdb_options {
     int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
     int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
     int64_t plane_cap_rows = 0;       // ... survivor list capacity in rows (0: n / 8; tests)
+    int64_t use_subset = 1;           // a row list beside the mask (hdb_index_set_row_subset): score only the listed rows where the rule says so (0: never -- the mask)
+    int64_t subset_min_n = -1;        // ... on matrices of at least this many rows (-1: the measured rule, HDB_SUBSET_MIN_ROWS)
+    int64_t subset_ratio = -1;        // ... while m * ceil(nq / 4) * subset_ratio <= n (-1: the measured rule, HDB_SUBSET_RATIO; else an integer >= 1)
 };
 
 // ---- what the planner is told ---------------------------------------------------------------------------------------------------
@@ -64,6 +67,7 @@ struct TopkFacts {
     bool plane_present, plane_declined;
     bool has_mask, has_bias;
     int cus;                          // compute units of the device
+    int64_t subset_m;                 // rows of the list set beside the mask (hdb_index_set_row_subset), 0 = none
 };
 struct TopkCall { int32_t nq, k; int metric; bool has_status, exact; };
 
@@ -79,12 +83,13 @@ enum TopkPath {
     HDB_PATH_PIPELINE                 // the multi-kernel pipeline: small, sampled or exact
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
-struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0; };
+struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0; };
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
     bool bits = false, pearson = false;                 // the metric's family
     bool exact = false, small = false, mfma = false, f32s = false, ksplit = false, l1tile = false, local = false;
+    bool subset = false;                                // the pipeline scores the rows of the index's list: every extent below is that of a matrix of subset_m rows
     // prologue of the paths that prepare their queries with launches of their own (full sort, pipeline)
     bool prep = false, fold_small = false, q16_in_prep = false, f16_queries = false, mask_fold = false;
     int tile_rows = 16;
@@ -205,9 +210,67 @@ static inline void plan_quant_batch(TopkPlan& p, const TopkFacts& ix, const hdb_
     p.stats.sample_rows = p.qs.s_rows; p.stats.sample_m = HDB_QB_SAMPLE_M; p.stats.chunks = (c.nq + p.cq_max - 1) / p.cq_max;
 }
 
+// ---- the row list (hdb_index_set_row_subset): when a filtered call scores only the rows it keeps ---------------------------------
+// A list call is the VALU scan, four queries per pass, over m gathered rows plus the launches of the multi-kernel pipeline; the
+// masked call streams all n rows on whatever path it has.  The two knobs of the rule, subset_ratio = -1 / subset_min_n = -1:
+// (profiles/subset_time.txt, one box, the same handle with use_subset = 0 and with the list, alternating call by call, p50 of 200 calls
+// in us, cosine top-100, masked -> list; share = m / n exactly, random ascending rows):
+//   10M x 384 fp16, 1 / 4 / 16 queries:
+//     share 1/2: 521 -> 688 (0.76), 799 -> 1171 (0.68), 1301 -> not eligible
+//     share 1/4: 516 -> 369 (1.40), 795 -> 617 (1.29), 1325 -> 1595 (0.83)
+//     share 1/8: 507 -> 211 (2.40), 778 -> 339 (2.30), 1296 -> 834 (1.55)
+//     share 1/16: 507 -> 130 (3.89), 748 -> 196 (3.81), 1295 -> 457 (2.83)
+//     share 1/64: 495 -> 69 (7.18), 716 -> 92 (7.78), 1289 -> 170 (7.58)
+//     share 1/1024: 489 -> 46 (10.53), 708 -> 60 (11.90), 1283 -> 74 (17.27)
+//   2M x 384 fp32, 1 / 4 / 16 queries:
+//     share 1/2: 471 -> 288 (1.64), 523 -> 392 (1.33), 528 -> not eligible
+//     share 1/4: 465 -> 167 (2.78), 522 -> 219 (2.38), 516 -> 574 (0.90)
+//     share 1/8: 465 -> 111 (4.20), 521 -> 140 (3.73), 515 -> 320 (1.61)
+//     share 1/16: 465 -> 79 (5.89), 522 -> 98 (5.31), 530 -> 200 (2.65)
+//     share 1/64: 465 -> 54 (8.57), 523 -> 71 (7.41), 516 -> 110 (4.67)
+//     share 1/1024: 467 -> 37 (12.75), 523 -> 46 (11.27), 534 -> 60 (8.89)
+//   1M x 768 bf16, 1 / 4 / 16 queries:
+//     share 1/2: 287 -> 177 (1.62), 400 -> 236 (1.69), 606 -> not eligible
+//     share 1/4: 278 -> 116 (2.38), 400 -> 155 (2.58), 603 -> 324 (1.86)
+//     share 1/8: 277 -> 88 (3.16), 400 -> 112 (3.58), 602 -> 208 (2.90)
+//     share 1/16: 276 -> 72 (3.82), 397 -> 89 (4.48), 602 -> 147 (4.09)
+//     share 1/64: 274 -> 60 (4.61), 389 -> 74 (5.23), 594 -> 95 (6.27)
+//     share 1/1024: 274 -> 44 (6.18), 379 -> 54 (6.99), 622 -> 63 (9.91)
+//   ladder, rows x 384 fp16, share 1/64, one query: 50k 43 -> 33 (1.30), 100k 56 -> 35 (1.58), 250k 64 -> 35 (1.82), 500k 91 -> 36 (2.53), 1000k 145 -> 46 (3.12)
+//   HDB_SUBSET_RATIO: the smallest power of two R such that every measured cell with m * ceil(nq / 4) * R <= n is at least 1.10x
+//   faster through the list.  R = 1 and R = 2 admit share 1/2 of the 10M x 384 fp16 index, where the masked call streams the int8
+//   shadow (4 GB) and the list gathers 3.84 GB of fp16 rows through the VALU: it loses.  R = 4 admits share 1/4 with up to four
+//   queries and share 1/16 with sixteen, every cell of which wins by 1.29x or more.
+//   HDB_SUBSET_MIN_ROWS: the smallest ladder size from which the list wins by 1.10x at that size and every larger one: 50 000, the
+//   smallest size measured (below it: not measured).  It is never below 32 768 rows whatever a measurement says: under a few tens of
+//   thousands of rows every call is launch-bound and there is nothing to win.
+#define HDB_SUBSET_RATIO 4
+#define HDB_SUBSET_MIN_ROWS 50000
+static inline bool subset_metric(int metric) {
+    return metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN || metric == HDB_MANHATTAN || metric == HDB_PEARSON;
+}
+// the call's side of the rule: m * ceil(nq / 4) * ratio <= n on a matrix of at least min_n rows
+static inline bool subset_rule(const TopkFacts& ix, const hdb_options& o, const TopkCall& c) {
+    if (ix.subset_m <= 0 || !o.use_subset || !subset_metric(c.metric) || c.nq < 1) return false;
+    if (ix.n < (o.subset_min_n >= 0 ? o.subset_min_n : (int64_t)HDB_SUBSET_MIN_ROWS)) return false;
+    const int64_t ratio = o.subset_ratio >= 1 ? std::min<int64_t>(o.subset_ratio, (int64_t)1 << 30) : (int64_t)HDB_SUBSET_RATIO;
+    return ix.subset_m <= ix.n / (((int64_t)c.nq + 3) / 4 * ratio);
+}
+
 // finite(): "are all rows of the matrix finite with a finite sum of squares?"
 template <typename Finite>
 static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite) {
+    // A list call is the same call on a matrix of the m listed rows with the matrix cores and the single launches off: the plan of
+    // those facts, taken while it is the multi-kernel pipeline (k > HDB_MAX_K on more than HDB_CAND_CAP listed rows keeps the mask).
+    // Its extents, sample plan and statistics are the inner plan's; the executor reads the rows through the list.
+    if (subset_rule(ix, o, c)) {
+        TopkFacts in{};
+        in.n = ix.subset_m; in.d = ix.d; in.dtype = ix.dtype; in.qmode = HDB_QUANT_NONE; in.has_bias = ix.has_bias; in.cus = ix.cus;
+        hdb_options oin = o;
+        oin.use_mfma = 0; oin.use_fused = 0; oin.use_quant = 0; oin.use_l1_tile = 0;
+        TopkPlan pin = plan_topk(in, oin, c, finite);
+        if (pin.path == HDB_PATH_PIPELINE) { pin.subset = true; pin.stats.subset = 1; return pin; }
+    }
     TopkPlan p;
     const int64_t n = ix.n;
     const int nq = c.nq, k = c.k, metric = c.metric;

@@ -112,8 +112,13 @@ __device__ __forceinline__ void hdb_emit(const ScanArgs& a, int q, int64_t row, 
 // grid = (blocks, ceil(nq_launch / QT)); block = 256 threads = 4 waves; LDS = QT*d*sizeof(Acc).
 // NJ > 0: compile-time number of 16-chunk steps per row (d*sizeof(T) == NJ*256), fully unrolled so
 // that all 4*NJ loads of a tile are in flight together; NJ == 0: runtime loop, any nchunks.
+// LIST: the row-list flavour (ScanArgs::rows / m).  The tiles walk the m positions of an ascending list of row ids: position j
+// stands where the dense kernel has row j -- lane split, chunk order, `live`, the reduction tree and the owned slot (j & 3) are
+// the dense kernel's on a compact matrix of the listed rows -- and only the row address, the per-row inputs of the epilogue
+// (1/||v||, bias) and the row packed into a candidate come from rows[j].  A 16-lane group still reads one row as contiguous
+// 256-byte pieces, the shape that gathers whole rows at the streaming rate.  The dense instantiations compile to what they were.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int QT, int MODE, int ACC, int NJ>
+template <typename T, int QT, int MODE, int ACC, int NJ, bool LIST>
 __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
     using Acc = typename Elem<T>::Acc;
     constexpr int EPC = Elem<T>::EPC;
@@ -136,11 +141,13 @@ __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
     const char* Vb = reinterpret_cast<const char*>(a.V);
 
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < a.ntiles; t += (int64_t)gridDim.x * 4) {
-        const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
+        const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;       // (LIST: a list position)
         const char* p[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int64_t r = min(r0 + u, a.n - 1);
+            int64_t r;
+            if constexpr (LIST) r = a.rows[min(r0 + u, a.m - 1)];
+            else r = min(r0 + u, a.n - 1);
             p[u] = Vb + r * (int64_t)a.row_bytes;
         }
         Acc acc[4][QT];
@@ -215,8 +222,13 @@ __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
             const Acc mine = hdb_rows4_sum(acc[0][qt], acc[1][qt], acc[2][qt], acc[3][qt], l16);
             const int64_t row = r0 + u_own;
             const int q = qbase + qt;
-            if ((l16 & 3) == 0 && row < a.n && q < nq_end)
-                hdb_emit<MODE>(a, q, row, t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, qt);
+            if constexpr (LIST) {        // positions below m only; the epilogue and the candidate entry take the true row
+                if ((l16 & 3) == 0 && row < a.m && q < nq_end)
+                    hdb_emit<MODE>(a, q, a.rows[row], t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, qt);
+            } else {
+                if ((l16 & 3) == 0 && row < a.n && q < nq_end)
+                    hdb_emit<MODE>(a, q, row, t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, qt);
+            }
         }
     }
     if (MODE == 1) hdb_stage_flush(a, stage, (int)blockIdx.y * QT, min(QT, nq_end - qbase));
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
 // ------------------------------------------------------------------------------------------------
 // Generic scan: any d / alignment (element-wise loads).  Same tiling, one query per launch row.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int MODE, int ACC>
+template <typename T, int MODE, int ACC, bool LIST>
 __global__ __launch_bounds__(256) void hdb_scan_generic_kernel(ScanArgs a, int nq_end) {
     using Acc = typename Elem<T>::Acc;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -239,13 +251,20 @@ __global__ __launch_bounds__(256) void hdb_scan_generic_kernel(ScanArgs a, int n
     const int g = lane >> 4, l16 = lane & 15;
     const T* Vt = reinterpret_cast<const T*>(a.V);
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < a.ntiles; t += (int64_t)gridDim.x * 4) {
-        const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
+        const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;       // (LIST: a list position)
+        int64_t lr[LIST ? 4 : 1];                                               // LIST: the four rows of the group, read once per tile
+        if constexpr (LIST) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) lr[u] = a.rows[min(r0 + u, a.m - 1)];
+        }
         Acc acc[4] = {Acc(0), Acc(0), Acc(0), Acc(0)};
         for (int e = l16; e < a.d; e += 16) {
             const Acc qv = qs[e];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int64_t r = min(r0 + u, a.n - 1);
+                int64_t r;
+                if constexpr (LIST) r = lr[u];
+                else r = min(r0 + u, a.n - 1);
                 const Acc x = (Acc)hdb_to_f(Vt[r * (int64_t)a.d + e]);
                 if (ACC == 1) { const Acc df = x - qv; acc[u] += df * df; }
                 else if (ACC == 2) { const Acc df = x - qv; acc[u] += df < Acc(0) ? -df : df; }
@@ -255,13 +274,21 @@ __global__ __launch_bounds__(256) void hdb_scan_generic_kernel(ScanArgs a, int n
         const int u_own = hdb_owned_row(l16);
         const Acc mine = hdb_rows4_sum(acc[0], acc[1], acc[2], acc[3], l16);
         const int64_t row = r0 + u_own;
-        if ((l16 & 3) == 0 && row < a.n && q < nq_end) hdb_emit<MODE>(a, q, row, t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, 0);
+        if constexpr (LIST) {
+            if ((l16 & 3) == 0 && row < a.m && q < nq_end) hdb_emit<MODE>(a, q, a.rows[row], t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, 0);
+        } else {
+            if ((l16 & 3) == 0 && row < a.n && q < nq_end) hdb_emit<MODE>(a, q, row, t * 16 + 4 * g + u_own, mine, MODE == 1 ? &stage : nullptr, 0);
+        }
     }
     if (MODE == 1) hdb_stage_flush(a, stage, (int)blockIdx.y, q < nq_end ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Row caches: 1/||v|| (norm 0 -> 1, ranking_algorithm.py:11-15), ||v||^2, NaN flag (:150).
+// The squares are accumulated with explicit fma: left to the compiler, some of a group's four row slots were contracted and
+// others multiplied and added (float32 / float64 rows, whose squares are inexact), so a row's cached norm depended on row & 3 and
+// a fresh index over a subset of the rows could differ from this one in the last bit of 1/||v||.  (float16 / bfloat16 squares
+// are exact in float32: their bits are the same either way.)
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n, int d, float* inv_norm,
@@ -285,7 +312,7 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
                     Acc x[EPC];
                     hdb_unpack(raw, x, (T*)nullptr);
 #pragma unroll
-                    for (int e = 0; e < EPC; ++e) acc[u] += x[e] * x[e];
+                    for (int e = 0; e < EPC; ++e) acc[u] = fma(x[e], x[e], acc[u]);
                 }
             }
         } else {
@@ -294,7 +321,7 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
                 for (int u = 0; u < 4; ++u) {
                     const int64_t r = min(r0 + u, n - 1);
                     const Acc x = (Acc)hdb_to_f(V[r * (int64_t)d + e]);
-                    acc[u] += x * x;
+                    acc[u] = fma(x, x, acc[u]);
                 }
             }
         }
@@ -494,7 +521,7 @@ __global__ __launch_bounds__(256) void hdb_hamming_kernel(ScanArgs a, const uint
 // ------------------------------------------------------------------------------------------------
 // host-side launchers
 // ------------------------------------------------------------------------------------------------
-template <typename T, int QT, int MODE, int ACC>
+template <typename T, int QT, int MODE, int ACC, bool LIST>
 static void launch_vec(const ScanArgs& a, int nq_launch, int blocks, hipStream_t st) {
     using Acc = typename Elem<T>::Acc;
     const dim3 grid(blocks, (nq_launch + QT - 1) / QT);
@@ -502,13 +529,13 @@ static void launch_vec(const ScanArgs& a, int nq_launch, int blocks, hipStream_t
     const int nq_end = a.q0 + nq_launch;
     if constexpr (QT == 1) {   // fully unrolled variants only for one query: with QT=4 they spill
         const int nj = (a.nchunks % 16 == 0) ? a.nchunks / 16 : 0;
-        if (nj == 3) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 3>), grid, dim3(256), lds, st, a, nq_end); return; }
-        if (nj == 6) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 6>), grid, dim3(256), lds, st, a, nq_end); return; }
+        if (nj == 3) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 3, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
+        if (nj == 6) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 6, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
     }
-    hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 0>), grid, dim3(256), lds, st, a, nq_end);
+    hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 0, LIST>), grid, dim3(256), lds, st, a, nq_end);
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool LIST>
 static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec, hipStream_t st) {
     using Acc = typename Elem<T>::Acc;
     const int accm = (a.metric == HDB_EUCLIDEAN || a.metric == HDB_EUCLIDEAN_DIST) ? 1 : (a.metric == HDB_MANHATTAN ? 2 : 0);
@@ -517,9 +544,9 @@ static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec
         const dim3 grid(blocks, nq_launch);
         const size_t lds = (size_t)a.d * sizeof(Acc);
         const int nq_end = a.q0 + nq_launch;
-        if (accm == 1) hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 1>), grid, dim3(256), lds, st, a, nq_end);
-        else if (accm == 2) hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 2>), grid, dim3(256), lds, st, a, nq_end);
-        else hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 0>), grid, dim3(256), lds, st, a, nq_end);
+        if (accm == 1) hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 1, LIST>), grid, dim3(256), lds, st, a, nq_end);
+        else if (accm == 2) hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 2, LIST>), grid, dim3(256), lds, st, a, nq_end);
+        else hipLaunchKernelGGL((hdb_scan_generic_kernel<T, MODE, 0, LIST>), grid, dim3(256), lds, st, a, nq_end);
         return;
     }
     // two queries already pay for the four-query kernel: one pass over V instead of two (float32 d=768, N=1M: 1 098 -> ~530 us)
@@ -527,13 +554,13 @@ static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec
     // queries stay with two passes there)
     const bool qt4 = (nq_launch >= 3 || (nq_launch == 2 && !(accm == 2 && sizeof(T) == 2))) && lds4 <= 60 * 1024;
     if (qt4) {
-        if (accm == 1) launch_vec<T, 4, MODE, 1>(a, nq_launch, blocks, st);
-        else if (accm == 2) launch_vec<T, 4, MODE, 2>(a, nq_launch, blocks, st);
-        else launch_vec<T, 4, MODE, 0>(a, nq_launch, blocks, st);
+        if (accm == 1) launch_vec<T, 4, MODE, 1, LIST>(a, nq_launch, blocks, st);
+        else if (accm == 2) launch_vec<T, 4, MODE, 2, LIST>(a, nq_launch, blocks, st);
+        else launch_vec<T, 4, MODE, 0, LIST>(a, nq_launch, blocks, st);
     } else {
-        if (accm == 1) launch_vec<T, 1, MODE, 1>(a, nq_launch, blocks, st);
-        else if (accm == 2) launch_vec<T, 1, MODE, 2>(a, nq_launch, blocks, st);
-        else launch_vec<T, 1, MODE, 0>(a, nq_launch, blocks, st);
+        if (accm == 1) launch_vec<T, 1, MODE, 1, LIST>(a, nq_launch, blocks, st);
+        else if (accm == 2) launch_vec<T, 1, MODE, 2, LIST>(a, nq_launch, blocks, st);
+        else launch_vec<T, 1, MODE, 0, LIST>(a, nq_launch, blocks, st);
     }
 }
 
@@ -554,10 +581,35 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
     // n = 200k x 100 float32, 16 queries 143 -> 120 us, but 1M rows 418 -> 566 us: the groups drift apart and stop sharing V in L2)
     const int auto_blocks = wide_rows ? 256 : 512;
     const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : auto_blocks);
-    if (dtype == HDB_F16) { if (mode == 0) launch_scan_t<__half, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<__half, 1>(a, nq_launch, blocks, vec, st); }
-    else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1>(a, nq_launch, blocks, vec, st); }
-    else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1>(a, nq_launch, blocks, vec, st); }
-    else { if (mode == 0) launch_scan_t<double, 0>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1>(a, nq_launch, blocks, vec, st); }
+    // (a.rows: the row-list flavour, a compile-time sibling of every kernel -- the dense ones carry no test for it)
+#define HDB_SCAN_DISPATCH(LIST_)                                                                                                   \
+    do {                                                                                                                           \
+        if (dtype == HDB_F16) { if (mode == 0) launch_scan_t<__half, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<__half, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else { if (mode == 0) launch_scan_t<double, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+    } while (0)
+    if (a.rows) HDB_SCAN_DISPATCH(true); else HDB_SCAN_DISPATCH(false);
+#undef HDB_SCAN_DISPATCH
+    return (int)hipGetLastError();
+}
+
+// Exact path of a row-list call: hdb_launch_collect left entries that carry list POSITIONS (the score buffer's index); rewrite
+// position j to rows[j] in the collected entries, at most `cap` per query, before finalize.  The list is ascending, so the order
+// of the entries (score descending, row ascending) is the order of their positions.  grid = (blocks, nq).
+__global__ __launch_bounds__(256) void hdb_list_rows_kernel(unsigned long long* cand, const uint32_t* cnt, uint32_t cap,
+                                                            const int64_t* rows, int64_t m) {
+    const int q = blockIdx.y;
+    const uint32_t have = min(cnt[q * HDB_CNT_STRIDE], cap);
+    for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < have; e += gridDim.x * 256) {
+        const unsigned long long ent = cand[(int64_t)q * cap + e];
+        const uint32_t pos = 0xFFFFFFFFu - (uint32_t)ent;
+        if ((int64_t)pos < m) cand[(int64_t)q * cap + e] = (ent & 0xFFFFFFFF00000000ull) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)rows[pos]);
+    }
+}
+extern "C" int hdb_launch_list_rows(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, const int64_t* rows, int64_t m,
+                                    void* stream) {
+    hipLaunchKernelGGL(hdb_list_rows_kernel, dim3(hdb_grid_for(cap, 256, 32), nq), dim3(256), 0, (hipStream_t)stream, cand, cnt, cap, rows, m);
     return (int)hipGetLastError();
 }
 
@@ -698,7 +750,7 @@ __global__ __launch_bounds__(256) void hdb_rowstats_kernel(const T* V, int64_t n
         Acc var[4] = {Acc(0), Acc(0), Acc(0), Acc(0)};
         for (int e = l16; e < d; e += 16)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const Acc df = (Acc)hdb_to_f(V[min(r0 + u, n - 1) * (int64_t)d + e]) - mu[u]; var[u] += df * df; }
+            for (int u = 0; u < 4; ++u) { const Acc df = (Acc)hdb_to_f(V[min(r0 + u, n - 1) * (int64_t)d + e]) - mu[u]; var[u] = fma(df, df, var[u]); }   // (explicit: the same for every row slot)
         const Acc ss = hdb_rows4_sum(var[0], var[1], var[2], var[3], l16);
         const int64_t row = r0 + uo;
         if ((l16 & 3) == 0 && row < n) {

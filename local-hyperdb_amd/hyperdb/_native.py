@@ -42,7 +42,7 @@ EXPORTS = (
     "hdb_index_has_nan", "hdb_index_set_bias", "hdb_index_set_row_mask", "hdb_scores", "hdb_topk",
     "hdb_topk_exact", "hdb_merge_topk", "hdb_set_option", "hdb_get_stat", "hdb_recency_bias", "hdb_recency_bias_twice",
     "hdb_packed_bytes", "hdb_merge_topk_packed", "hdb_merge_topk_host", "hdb_host_exchange_merge", "hdb_topk_host",
-    "hdb_index_quantize", "hdb_debug_quant_bounds",
+    "hdb_index_quantize", "hdb_debug_quant_bounds", "hdb_index_set_row_subset",
 )
 
 
@@ -77,6 +77,7 @@ def _load():
     lib.hdb_index_has_nan.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
     lib.hdb_index_set_bias.argtypes = [vp, vp]
     lib.hdb_index_set_row_mask.argtypes = [vp, vp]
+    lib.hdb_index_set_row_subset.argtypes = [vp, vp, vp, i64]
     lib.hdb_scores.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     lib.hdb_topk.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp, vp, vp]
     lib.hdb_topk_exact.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp, vp, vp]
@@ -184,6 +185,8 @@ class GpuIndex:
         self._h = ctypes.c_void_p()
         self._bias = None
         self._mask = None
+        self._rows = None                      # the row list set beside the mask (set_row_subset)
+        self._rows_ok = OrderedDict()          # id(device list) -> the list: validated once, kept alive so the id stays its own
         self._nan = None
         self._buf = None
         self.quant = HDB_QUANT_NONE             # int8 shadow (quantize)
@@ -239,6 +242,7 @@ class GpuIndex:
         self.n += m
         self.V = buf[:self.n]
         self._bias = self._mask = None
+        self._forget_rows()
         self._nan = None
         _check(_lib.hdb_index_extend(self._h, self.n, _stream_ptr(self.device)), "hdb_index_extend")
 
@@ -251,6 +255,7 @@ class GpuIndex:
             raise ValueError("update: matrix must keep d and dtype")
         self.V, self.n = t, int(t.shape[0])
         self._bias = self._mask = self._nan = None
+        self._forget_rows()
         self._buf = None                                    # the old capacity buffer is released with the old matrix
         _check(_lib.hdb_index_update(self._h, ctypes.c_void_p(t.data_ptr()), self.n, _stream_ptr(self.device)),
                "hdb_index_update")
@@ -304,6 +309,7 @@ class GpuIndex:
         self._buf = out
         self.V, self.n = out[:m], m
         self._bias = self._mask = self._nan = None
+        self._forget_rows()
 
     @property
     def has_nan(self):
@@ -372,12 +378,12 @@ class GpuIndex:
                                            self.device.index or 0, _stream_ptr(self.device)), "hdb_recency_bias_twice")
         return out
 
-    def set_row_mask(self, mask):
-        if mask is None:
-            if self._mask is not None:
-                self._mask = None
-                _check(_lib.hdb_index_set_row_mask(self._h, None), "hdb_index_set_row_mask")
-            return
+    def _forget_rows(self):
+        """The matrix changed: the library dropped the list with mask and bias, and no validated list describes the new rows."""
+        self._rows = None
+        self._rows_ok.clear()
+
+    def _mask_tensor(self, mask):
         if isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8 and mask.device == self.device and mask.is_contiguous():
             m = mask                                       # a resident 0/1 mask (HyperDB caches them per filter): borrowed as it is
         elif isinstance(mask, torch.Tensor):
@@ -386,8 +392,60 @@ class GpuIndex:
             m = torch.from_numpy(np.ascontiguousarray((np.asarray(mask) != 0).astype(np.uint8))).to(self.device)
         if m.numel() != self.n:
             raise ValueError("mask must have one entry per row")
-        self._mask = m
+        return m
+
+    def set_row_mask(self, mask):
+        """mask: None, or one entry per row (non-zero = the row takes part).  Drops a row list set by set_row_subset."""
+        if mask is None:
+            if self._mask is not None:
+                self._mask = self._rows = None
+                _check(_lib.hdb_index_set_row_mask(self._h, None), "hdb_index_set_row_mask")
+            return
+        m = self._mask_tensor(mask)
+        self._mask, self._rows = m, None
         _check(_lib.hdb_index_set_row_mask(self._h, ctypes.c_void_p(m.data_ptr())), "hdb_index_set_row_mask")
+
+    def _row_list(self, rows):
+        """numpy / torch -> the validated int64 device list.  One check per list: a resident list that passed before (the facade
+        caches its lists per filter) is taken as it is."""
+        if isinstance(rows, torch.Tensor) and id(rows) in self._rows_ok:
+            self._rows_ok.move_to_end(id(rows))
+            return rows
+        if isinstance(rows, torch.Tensor):
+            h = rows.detach().cpu().numpy()
+        else:
+            h = np.asarray(rows)
+        if h.ndim != 1 or h.size == 0:
+            raise ValueError("row list must be a non-empty 1-D array of row ids")
+        if h.dtype.kind not in "iu":
+            raise ValueError("row list must hold integers")
+        h = np.ascontiguousarray(h, dtype=np.int64)
+        if int(h[0]) < 0 or int(h[-1]) >= self.n or (h.size > 1 and bool((h[1:] <= h[:-1]).any())):
+            raise ValueError(f"row list must be strictly ascending row ids in [0, {self.n})")
+        if isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.device == self.device and rows.is_contiguous():
+            r = rows
+        else:
+            r = torch.from_numpy(h).to(self.device)
+        self._rows_ok[id(r)] = r
+        while len(self._rows_ok) > HOST_RECORD_SLOTS:
+            self._rows_ok.popitem(last=False)
+        return r
+
+    def set_row_subset(self, mask, rows):
+        """Row mask plus the strictly ascending list of the rows it keeps (hdb_index_set_row_subset): selective filters then read
+        only the listed rows where the library's rule says so, every other call uses the mask.  rows: numpy or torch, validated
+        here before anything is launched (non-empty, strictly ascending, inside [0, n)): ValueError otherwise.  The caller
+        guarantees that list and mask describe the same rows.  rows = None is set_row_mask(mask)."""
+        if mask is None or rows is None:
+            if mask is None and rows is not None:
+                raise ValueError("a row list needs its mask")
+            self.set_row_mask(mask)
+            return
+        r = self._row_list(rows)
+        m = self._mask_tensor(mask)
+        self._mask, self._rows = m, r
+        _check(_lib.hdb_index_set_row_subset(self._h, ctypes.c_void_p(m.data_ptr()), ctypes.c_void_p(r.data_ptr()), int(r.numel())),
+               "hdb_index_set_row_subset")
 
     # -- options / stats -----------------------------------------------------------------------
     def set_option(self, name, value):

@@ -90,7 +90,7 @@ class HyperDB:
         self._dead = np.zeros(0, dtype=np.int64)     # tombstoned device rows (ascending); see remove_document
         self._ts_cache = {}                           # timestamp_key -> float64 array over documents (NaN = missing)
         # resident per-row inputs of the ranking call, rebuilt only when the document list changes (_invalidate_rows):
-        self._mask_cache = OrderedDict()              # filter key -> (per-shard uint8 device masks | None, documents kept, bool array over documents | None)
+        self._mask_cache = OrderedDict()              # filter key -> (per-shard uint8 device masks | None, documents kept, bool array over documents | None, per-shard int64 device row lists | None)
         self._ts_dev = {}                             # timestamp_key -> per-shard float64 device columns over the device rows
         self._bias_cache = OrderedDict()              # (timestamp_key, filter key, recency_bias) -> per-shard float32 device bias
         self._str_tokens = None                       # per document: token sets of the strings inside it (sentence filter)
@@ -536,7 +536,10 @@ class HyperDB:
     _ROW_CACHE_SLOTS = 4
 
     def _mask_for(self, filters):
-        """-> (per-shard device masks or None, number of documents kept, bool array over documents or None)."""
+        """-> (per-shard device masks or None, number of documents kept, bool array over documents or None, per-shard
+        ascending local row lists or None).  A shard gets a list only when the filter keeps at least one and at most half of
+        its rows (8 bytes per kept row, in the same cache entry as the mask); whether a call reads through it is the library's
+        rule, not the facade's."""
         fkey = self._filter_key(filters)
         hit = self._mask_cache.get(fkey)
         if hit is not None:
@@ -544,15 +547,22 @@ class HyperDB:
             return hit
         keep = self._row_mask(filters)                          # over documents (host predicates, once per filter key)
         if keep is None and self._dead.size == 0:
-            hit = (None, len(self.documents), None)
+            hit = (None, len(self.documents), None, None)
         else:
             self.host_row_passes += 1
             live = self._live_rows()
             rows_kept = live if keep is None else live[keep]
             row_mask = np.zeros(self._index.n, dtype=np.uint8)
             row_mask[rows_kept] = 1
-            parts = [torch.from_numpy(row_mask[lo:hi]).to(sh.device) for sh, lo, hi in self._shards()]
-            hit = (parts, int(rows_kept.size), keep)
+            parts, lists = [], []
+            for sh, lo, hi in self._shards():
+                parts.append(torch.from_numpy(row_mask[lo:hi]).to(sh.device))
+                a, b = np.searchsorted(rows_kept, [lo, hi])           # rows_kept is ascending: the shard's rows are one slice
+                if 1 <= b - a and 2 * (b - a) <= hi - lo:
+                    lists.append(torch.from_numpy(np.ascontiguousarray(rows_kept[a:b] - lo, dtype=np.int64)).to(sh.device))
+                else:
+                    lists.append(None)
+            hit = (parts, int(rows_kept.size), keep, lists)
         self._mask_cache[fkey] = hit
         while len(self._mask_cache) > self._ROW_CACHE_SLOTS:
             self._mask_cache.popitem(last=False)
@@ -604,7 +614,7 @@ class HyperDB:
         # (one query: a NaN anywhere makes q.q a NaN -- a dot product instead of an isnan pass and a reduction)
         if ix.has_nan or (math.isnan(float(np.dot(Q[0], Q[0]))) if len(Q) == 1 and Q.dtype.kind == "f" else bool(np.isnan(Q).any())):
             raise ValueError(ranking.NAN_MESSAGE)
-        masks, n_avail, keep = self._mask_for(filters)
+        masks, n_avail, keep, lists = self._mask_for(filters)
         if n_avail == 0:
             print("INFO: No document matches your query with the brute-force method and the current filters.")
             return [[] for _ in range(len(Q))]
@@ -616,7 +626,7 @@ class HyperDB:
         try:
             for p, (sh, lo, hi) in enumerate(shards):
                 if sh.n:
-                    sh.set_row_mask(None if masks is None else masks[p])
+                    sh.set_row_subset(None if masks is None else masks[p], None if lists is None else lists[p])
                     sh.set_bias(None if bias is None else bias[p])
             idx, sc = ix.topk(Q, int(top_k), METRIC_IDS[metric])
         finally:
