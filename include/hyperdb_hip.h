@@ -167,14 +167,15 @@ void hdb_index_destroy(hdb_index* ix);
  * The 5-bit plane (one dot / cosine query; hdb_quant.hip, "The 5-bit plane").  Beside the codes the index keeps their high five
  * bits -- a nibble plane, a bit plane and a 16-byte record per row, 20 bytes per 32 elements + 16 (10M x 384: 2.56 GB) -- derived
  * from the codes wherever the shadow's rows are written (build, extend, update, gather) for rows of up to 512 elements.  A
- * one-query call of at least plane_min_n rows (-1: the measured rule, 2 000 000) with use_plane on first streams the plane
- * (pass 1) and keeps the rows whose coarse upper bound hi5 reaches T_s in a list of n / 8 row numbers (plane_cap_rows overrides
- * the capacity), then runs the int8 pass over those rows only (pass 2).  hi5 >= the int8 pass's own upper bound for every row, so
- * the candidate list, and the answer, are those of the call without the plane.  A list that overflows makes pass 2 scan all rows
- * instead (correct, one wasted pass; there is no automatic switch-off: use_plane = 0 is the manual one).  Euclidean calls, 2-4
- * queries and batches never take the plane.  The plane is under the automatic build's memory guard: when the shadow fits and
- * the plane does not, the shadow is built alone.  Stats: plane (the last call took it), plane_bytes, plane_survivors (rows pass 1
- * kept in the last call) and plane_overflows (calls of this index whose list overflowed); the last two synchronise. */
+ * one-query call of at least plane_min_n rows (-1: the measured rule, 2 000 000) with use_plane on streams the plane and, in the
+ * same launch, runs the int8 evaluation on the rows whose coarse upper bound hi5 reaches T_s, 16 at a time.  hi5 >= the int8
+ * pass's own upper bound for every row, so the candidate list, and the answer, are those of the call without the plane.
+ * plane_cap_rows (0: n / 8) is a mark, not a capacity: a call that keeps more rows than that is counted in plane_overflows -- the
+ * plane let more through than it is worth, the call read the plane AND the codes of those rows -- and its answer is complete all
+ * the same (there is no automatic switch-off: use_plane = 0 is the manual one).  Euclidean calls, 2-4 queries and batches never
+ * take the plane.  The plane is under the automatic build's memory guard: when the shadow fits and the plane does not, the shadow
+ * is built alone.  Stats: plane (the last call took it), plane_bytes, plane_survivors (rows the plane kept in the last call) and
+ * plane_overflows (calls of this index that kept more than plane_cap_rows); the last two synchronise. */
 enum hdb_quant { HDB_QUANT_NONE = 0, HDB_QUANT_I8 = 1 };
 int hdb_index_quantize(hdb_index* ix, int mode, void* stream);
 /* Test entry: the upper bound of every row for ONE float32 query (dot or cosine) as the int8 pass computes it (dev_hi, n floats)
@@ -366,7 +367,8 @@ void hdb_group_destroy(hdb_group* g);
  *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never), quant_batch_min_n (batches
  *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
  *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane),
- *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; the survivor list's capacity, for tests).
+ *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; kept rows beyond which a call counts in plane_overflows -- a
+ *   statistic: no call is answered differently for it).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,

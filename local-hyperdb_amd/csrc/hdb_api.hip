@@ -90,7 +90,7 @@ struct hdb_index {
     int64_t q_rows = 0;               // capacity in rows
     int32_t qP = 0;                   // code pitch: d rounded up to 16 bytes
     int* qstat = nullptr;             // device words (HDB_QSTAT_WORDS): [0] largest candidate count of the last quantized call,
-                                      // [1] survivors of its pass over the 5-bit plane, [2] calls whose survivor list overflowed
+                                      // [1] survivors of its pass over the 5-bit plane, [2] calls with more survivors than plane_cap_rows
     // the 5-bit plane beside the shadow (hdb_quant.hip): nibbles [rows][pU][16], bits [rows][pU], records [rows][4]; q_rows rows each
     uint8_t* pnib = nullptr;
     uint32_t* pbit = nullptr;
@@ -568,7 +568,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
-        // of this index so far whose survivor list overflowed (they scanned all rows in pass 2)
+        // of this index so far that kept more than plane_cap_rows of them (the plane let more through than it is worth)
         int h[HDB_QSTAT_WORDS] = {0, 0, 0, 0};
         if (ix->qstat) {
             HIP_TRY(hipSetDevice(ix->device));
@@ -753,7 +753,7 @@ static TopkFacts topk_facts(const hdb_index* ix) {
 // The workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h): the memory guard of the automatic build sizes with these extents,
 // the call lays out with them.  The score buffer takes the extent of the largest sample any k takes (quant_ld_max) -- the call's own
 // ld_s is only its leading dimension -- so calls that differ in k never regrow the workspace.  (P from d: the automatic build asks
-// before the index has a pitch.)  pl_cap: entries of the plane's survivor list (one query on an index that holds a plane).
+// before the index has a pitch.)  pl_cap: entries of a row list beside the score buffer (0 from every caller: hdb_ws.h).
 static int quant_pitch(const hdb_index* ix) { return (int)align_up((size_t)ix->d, 16); }
 static size_t quant_ws_bytes(const hdb_index* ix, int nq, uint32_t pl_cap, bool mflavour) {
     return ws_bytes_for<QuantWs>(nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
@@ -809,8 +809,10 @@ static int shadow_prepare(hdb_index* ix, const TopkPlan& p, int nq, hipStream_t 
 // those from the matrix, finalize with the floor T_s.  The sample aims at ~512 rows of the whole matrix with a lower bound above
 // T_s (the upper bounds let several times that many through; a sample of 16 keeps P(fewer than k = 128 such rows) near 1e-5).
 // mflavour (the automatic shadow of an fp16 index): the scores are the matrix cores' -- one launch prepares the queries (1/||q||,
-// the scaled fp16 copy, codes of the rounded query), the candidates are gathered into a compact matrix and scored by the MODE 0
-// launch of the matrix-core scan, the finalize packs those scores into the list before it selects.  Seven launches either way.
+// the scaled fp16 copy, codes of the rounded query), the filter pass copies every candidate's row into a compact matrix as it emits
+// it, the MODE 0 launch of the matrix-core scan scores that, the finalize packs those scores into the list before it selects.
+// Launches: query prep, sample pass, filter pass, MODE 0, finalize -- five with the threshold folded into the passes (nsub), six
+// with hdb_sample_thr_kernel; the explicit shadow has two query prep launches and hdb_quant_rescore_kernel in MODE 0's place.
 static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
     int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
@@ -819,11 +821,10 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     const uint32_t m = 16;
     const QuantSample sp = p.qs;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, nq, (nq == 1 && ix->pnib) ? p.pl_cap : 0, mflavour);
+    int rc = quant_ws_lay(ix, w, nq, 0, mflavour);
     if (rc) return rc;
-    // one dot / cosine query: pass 1 over the 5-bit plane, pass 2 (MODE 1 itself) over the rows it keeps (hdb_quant.hip)
-    const uint32_t pl_cap = p.pl_cap;
-    uint32_t* pl_cnt = use_pl ? reinterpret_cast<uint32_t*>(ix->qstat) + 1 : nullptr;
+    uint32_t* qstat = reinterpret_cast<uint32_t*>(ix->qstat);
+    uint32_t* pl_cnt = use_pl ? qstat + 1 : nullptr;
     const size_t crow = (size_t)nq * HDB_CAND_CAP;
     const int nsub = p.nsub;
     rc = quant_query_prep(ix, (const float*)dev_Q, nq, w, mflavour, ix->qstat, nsub ? w.cnt : nullptr, pl_cnt, st);
@@ -835,22 +836,23 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(w.sbuf, sp.s_rows, sp.ld_s, nq, m, w.thr, w.cnt, nullptr, st));
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
     a.thr = w.thr; a.cnt = w.cnt; a.cand = w.cand; a.cap = HDB_CAND_CAP;
+    const bool has_bias = ix->bias != nullptr || ix->mask != nullptr;
+    if (mflavour) {                                  // the filter pass fills the compact matrix as it emits
+        a.V = (const char*)ix->V; a.row_bytes = ix->d * 2; a.G = w.G;
+        a.ginv = metric == HDB_COSINE ? w.ginv : nullptr; a.gbias = has_bias ? w.gbias : nullptr;
+    }
     prof_begin(ix, st);
     if (use_pl) {
-        // pass 1 takes the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for pass 2 and the finalize
+        // one dot / cosine query: the pass over the 5-bit plane, which finishes the rows it keeps itself (hdb_quant.hip); it takes
+        // the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for the finalize
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
-        a.pl_list = w.pl_list; a.pl_cnt = pl_cnt; a.pl_cap = pl_cap;
+        a.pl_cnt = pl_cnt; a.pl_cap = p.pl_cap;
         LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->opt.max_blocks, st));
-        a.nsub = 0; a.wmax = nullptr;
-        LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 1, (int)ix->opt.max_blocks, st));
     } else {
         LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->opt.max_blocks, st));
     }
     prof_end(ix, st);
     if (mflavour) {
-        const bool has_bias = ix->bias != nullptr || ix->mask != nullptr;
-        LAUNCH_TRY(hdb_launch_quant_cgather(ix->V, ix->d * 2, ix->inv_norm, ix->bias, ix->mask, w.cand, w.cnt, HDB_CAND_CAP, nq, w.G,
-                                            metric == HDB_COSINE ? w.ginv : nullptr, has_bias ? w.gbias : nullptr, st));
         ScanArgs s; memset(&s, 0, sizeof(s));
         s.V = w.G; s.n = (int64_t)crow; s.d = ix->d; s.Q = dev_Q; s.metric = metric; s.inv_norm = w.ginv; s.qinv = w.qinv;
         s.bias = has_bias ? w.gbias : nullptr; s.mask = nullptr; s.nq = nq;
@@ -875,7 +877,7 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, 1, plane_list_cap(ix->opt, ix->n), true);
+    int rc = quant_ws_lay(ix, w, 1, 0, true);
     if (rc) return rc;
     rc = quant_query_prep(ix, dev_q, 1, w, ix->qauto, nullptr, nullptr, nullptr, st);
     if (rc) return rc;

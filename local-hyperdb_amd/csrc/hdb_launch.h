@@ -124,9 +124,6 @@ int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, v
 int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
                              const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
                              const uint32_t* cnt, uint32_t cap, void* stream);
-int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
-                             const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv, float* gbias,
-                             void* stream);
 int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
                               int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
                               const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,

@@ -52,7 +52,7 @@ struct hdb_options {
     int64_t quant_batch_kernel = 1;   // ... their filter pass: 1 = int8 matrix cores (hdb_quant_mfma.hip), 0 = the v_dot4 scan, four queries per pass
     int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
     int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
-    int64_t plane_cap_rows = 0;       // ... survivor list capacity in rows (0: n / 8; tests)
+    int64_t plane_cap_rows = 0;       // ... kept rows beyond which a call counts in the stat plane_overflows (0: n / 8); changes no answer
     int64_t use_subset = 1;           // a row list beside the mask (hdb_index_set_row_subset): score only the listed rows where the rule says so (0: never -- the mask)
     int64_t subset_min_n = -1;        // ... on matrices of at least this many rows (-1: the measured rule, HDB_SUBSET_MIN_ROWS)
     int64_t subset_ratio = -1;        // ... while m * ceil(nq / 4) * subset_ratio <= n (-1: the measured rule, HDB_SUBSET_RATIO; else an integer >= 1)
@@ -102,7 +102,7 @@ struct TopkPlan {
     // shadow paths
     bool mflavour = false, build_needed = false, plane_wanted = false;
     bool qb_int8 = false;                               // batches: the int8 matrix-core filter (0: the v_dot4 scan, four queries per pass)
-    int P = 0, nsub = 0; uint32_t pl_cap = 0;           // pl_cap: capacity of the plane's survivor list
+    int P = 0, nsub = 0; uint32_t pl_cap = 0;           // pl_cap: rows the plane may keep before the call counts in plane_overflows
     QuantSample qs = {0, 1, 0, 0};
     TopkStats stats;
     bool shadow() const { return path == HDB_PATH_QUANT || path == HDB_PATH_QUANT_BATCH; }
@@ -145,7 +145,8 @@ static inline int64_t quant_min_rows(int dtype) {
 // plane column of profiles/quant_plane_time.txt beats the plane-off column by at least 5 % in both runs, at that size and every
 // larger one (2M: 1.10x / 1.09x, 10M: 1.29x / 1.30x).  It is also the smallest size that has an automatic shadow.
 #define HDB_PLANE_MIN_ROWS 2000000
-// capacity of the survivor list in rows: an eighth of the matrix (the plane keeps under 5 % of Gaussian rows), or what the tests ask for
+// rows the plane may keep before a call counts in plane_overflows: an eighth of the matrix (the plane keeps under 5 % of Gaussian
+// rows), or what the option asks for
 static inline uint32_t plane_list_cap(const hdb_options& o, int64_t n) {
     return (uint32_t)(o.plane_cap_rows > 0 ? std::min<int64_t>(o.plane_cap_rows, n) : std::max<int64_t>(n / 8, 16));
 }

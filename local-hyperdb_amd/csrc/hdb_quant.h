@@ -38,16 +38,21 @@ struct QuantArgs {
     const float* thr; uint32_t* cnt; unsigned long long* cand; uint32_t cap;   // MODE 1: candidate lists
     // Threshold folded into the two passes (nsub > 0; matrix-core flavour): MODE 0 leaves, instead of the scores, the largest lower
     // bound every WAVE of its grid saw -- wmax[q][nsub], nsub = 4 x workgroups, as orderable keys (0: nothing seen) -- and every
-    // workgroup of MODE 1 starts by taking the 16th largest of those (a lower bound of the 16th largest sampled lower bound, equal to
-    // it unless two of the top 16 fell to one wave: hdb_sample_thr_kernel's argument with 4x the subsets) and workgroup 0 stores it
-    // to thr_out for the finalize.  No launch in between, nothing to wait for.
+    // workgroup of the filter pass starts by taking the 16th largest of those (a lower bound of the 16th largest sampled lower bound,
+    // equal to it unless two of the top 16 fell to one wave: hdb_sample_thr_kernel's argument with 4x the subsets) and workgroup 0
+    // stores it to thr_out for the finalize.  No launch in between, nothing to wait for.  (Selecting once, by the workgroup of the
+    // sample pass that arrives last on a ticket, was measured and made the call longer: DESIGN.md.)
     uint32_t* wmax; int32_t nsub; float* thr_out;
-    // The 5-bit plane (hdb_quant.hip, "The 5-bit plane"): pass 1 (hdb_quant_plane_scan_kernel) streams the plane and appends the rows
-    // whose coarse upper bound reaches T_s to pl_list (pl_cap entries; pl_cnt[0] counts past the capacity, those writes are dropped);
-    // the LIST flavour of MODE 1 then visits those rows only -- or all rows when the counter passed the capacity (pl_cnt[1] counts
-    // such calls).  dbg: test-only output of one upper bound per row (hdb_debug_quant_bounds).
+    // Matrix-core flavour (G non-null): the workgroup that stores a candidate to cand[slot] also copies its row of the matrix V
+    // (row_bytes each, a multiple of 16) to row `slot` of the compact matrix G and leaves 1/||v|| and the bias (row mask folded in, as
+    // hdb_maskbias_kernel does) in ginv[slot] / gbias[slot] (either may be null) for the MODE 0 launch of hdb_mfma_kernel.h.
+    const char* V; int32_t row_bytes; char* G; float* ginv; float* gbias;
+    // The 5-bit plane (hdb_quant.hip, "The 5-bit plane"): pass 1 (hdb_quant_plane_scan_kernel) streams the plane, and the rows whose
+    // coarse upper bound reaches T_s go through MODE 1's evaluation in the same kernel, 16 at a time, into the candidate lists.
+    // pl_cnt[0] counts those rows; a call that kept more than pl_cap of them adds one to pl_cnt[1] (the plane let more through than it
+    // is worth; the answer is complete either way).  dbg: test-only output of one upper bound per row (hdb_debug_quant_bounds).
     const uint8_t* pl_nib; const uint32_t* pl_bit; const float* pl_rec; int32_t pl_units;
-    uint32_t* pl_list; uint32_t* pl_cnt; uint32_t pl_cap;
+    uint32_t* pl_cnt; uint32_t pl_cap;
     float* dbg;
 };
 #define HDB_QUANT_NSUB_MAX 4096      // (MODE 1 holds nsub / 256 keys per thread)

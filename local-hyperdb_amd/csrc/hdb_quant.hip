@@ -59,7 +59,8 @@
 //   -> int8 scan over all rows (MODE 1: row r is a candidate of q when its upper bound >= T_s)
 //   -> exact rescoring of the candidates from the original matrix -> finalize with the floor T_s.
 // (matrix-core flavour: ONE query prep launch; the threshold rides in the two passes -- QuantArgs::nsub, hdb_quant.h -- when the
-//  sample is large enough; rescoring = hdb_quant_cgather_kernel + the MODE 0 launch of hdb_mfma_kernel.h.)
+//  sample is large enough; the kernel that emits a candidate copies its row into the compact matrix, so rescoring = the MODE 0
+//  launch of hdb_mfma_kernel.h.)
 // Completeness: every row that was not emitted has exact score <= its upper bound < T_s.  The finalize checks that the kk-th
 // best rescored candidate scores ABOVE T_s (hdb_finalize_fast's floor); then every row missing from the list scores strictly
 // below the kk-th best, so the top kk, ties at the kk-th score included, are all in the list.  If the check fails (HDB_Q_UNDERFLOW)
@@ -89,7 +90,8 @@
 // the sum of all of that (< Z 2^-20 x 1.5 + 1e-30) is covered: hi5 >= hi for every row, hi as MODE 1 computes it.  A row pass 1
 // drops (hi5 < T_s; a NaN never drops) would have been dropped by MODE 1: the candidate set, and every later stage, is unchanged.
 // Z 2^-18 is relative to magnitudes that do not cancel, at most 2^-8 of the bound's own width B: pass 1 loses nothing by it.
-// Pass 2 is MODE 1 itself (LIST flavour) over the survivor list; when the list overflowed it scans all rows densely instead.
+// The rows pass 1 keeps are finished by pass 1 itself: 16 at a time they go through MODE 1's own evaluation (hq_rows4_bounds, compiled
+// with contraction off: the uncontracted form is one of the evaluations F(A) above, and both kernels get the same bits from it).
 #include "hdb_common.h"
 #include "hdb_quant.h"
 #include "hdb_finalize.h"
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_kernel(const float* Q, int
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= nq) return;
     if (q == 0 && lane == 0 && stat) stat[0] = 0;
-    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // an empty survivor list (5-bit plane)
+    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // no survivor of the 5-bit plane yet
     const float* qr = Q + (int64_t)q * d;
     float amax = 0.f;
     bool bad = false;
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(64) void hdb_quant_qprep_m_kernel(const float* Q, i
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= nq) return;
     if (q == 0 && lane == 0 && stat) stat[0] = 0;
-    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // an empty survivor list (5-bit plane)
+    if (q == 0 && lane == 0 && pl_cnt) pl_cnt[0] = 0u;     // no survivor of the 5-bit plane yet
     if (lane == 0 && cnt_init) cnt_init[q * HDB_CNT_STRIDE] = 0u;     // an empty candidate list (the folded threshold has no kernel that would do it)
     const float* qr = Q + (int64_t)q * d;
     float s = 0.f, amax = 0.f;
@@ -410,160 +412,235 @@ __device__ __forceinline__ void hq_fold_thr(const QuantArgs& a, float (&q_thr)[N
     for (int q = 0; q < NQ; ++q) q_thr[q] = s_thr[q];
 }
 
-// MODE 2 (tests): MODE 1's upper bound of every row -> dbg[row], nothing emitted.
-// LIST (MODE 1, one query; pass 2 behind the 5-bit plane): a tile's 16 rows are 16 consecutive entries of the survivor list, the tile
-// count comes from the device counter (fixed grid, no host sync); a counter past the list's capacity means entries were dropped,
-// and the launch scans all rows densely instead.
-template <int MODE, int NQ, int NJ, bool LIST = false>
+// What the scan needs of its NQ queries (the quantized query prep's record, 1/||q|| for cosine).
+template <int NQ>
+struct HqQuery {
+    float s[NQ], n[NQ], d[NQ], sq[NQ], inv[NQ];
+    bool bad[NQ];
+};
+template <int NQ>
+__device__ __forceinline__ void hq_query_load(const QuantArgs& a, HqQuery<NQ>& qc) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const float* o = a.qaux + (int64_t)q * HDB_QQ_WORDS;
+        qc.s[q] = o[HDB_QQ_S]; qc.n[q] = o[HDB_QQ_N]; qc.d[q] = o[HDB_QQ_D]; qc.sq[q] = o[HDB_QQ_SQ]; qc.bad[q] = o[HDB_QQ_BAD] != 0.f;
+        qc.inv[q] = a.metric == HDB_COSINE ? a.qinv[q] : 1.f;
+    }
+}
+
+// One group of four rows rr[0..3] (a.n or more: no row) through the int8 evaluation, called by the 16 lanes of the group: the code
+// loads, the v_dot4 sums against the NQ queries in LDS (qs[q * nch + piece]), hq_rows4_sum, and in the lane that then owns a row
+// (`row` = rr[hdb_owned_row(l16)]; the function returns whether that is a row of the matrix) the row terms and the bounds lo <= score <= hi
+// of the header -- -inf both for a masked row or a query the prep declined -- handed to sink(q, lo, hi, masked) query by query, so that
+// no caller holds NQ pairs of bounds at once (the dense kernels keep the parent's registers that way).  The dense passes (hdb_quant_scan_kernel) and the pass over
+// the 5-bit plane (hdb_quant_plane_scan_kernel, for the rows it keeps) both call it, and the candidate set must not depend on which:
+// the float arithmetic is compiled with contraction OFF, so both instantiations round after every multiply and every add and give
+// the same bits (G, the 16-byte pieces of a row in flight per lane, only orders exact int32 sums).  That is one of the evaluations F(A) the plane's derivation (header, "The 5-bit plane") covers -- it holds for
+// whatever the compiler contracts, the uncontracted form included -- so hi5 >= hi stands as derived there.
+template <int NQ, int NJ, int G, typename Sink>
+__device__ __forceinline__ bool hq_rows4_bounds(const QuantArgs& a, const int4* qs, const HqQuery<NQ>& qc, const int64_t (&rr)[4], int l16,
+                                                int64_t row, Sink&& sink) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const int nch = a.P >> 4;
+    const int nj = NJ > 0 ? NJ : (nch + 15) >> 4;
+    const int8_t* p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) p[u] = a.codes + min(rr[u], a.n - 1) * (int64_t)a.P;
+    int acc[4][NQ];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[u][q] = 0;
+    for (int j0 = 0; j0 < nj; j0 += G) {
+        uint4 raw[G][4];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int c = l16 + 16 * (j0 + j);
+            const bool live = (j0 + j) < nj && c < nch;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (live) {
+                    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p[u] + (int64_t)c * 16));
+                    raw[j][u] = make_uint4(v.x, v.y, v.z, v.w);
+                } else {
+                    raw[j][u] = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);           // loads ahead of every use
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int c = l16 + 16 * (j0 + j);
+            const int cc = c < nch ? c : 0;          // (dead pieces are zero: any query piece gives 0)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int4 qv = qs[q * nch + cc];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    int s = acc[u][q];
+                    s = __builtin_amdgcn_sdot4((int)raw[j][u].x, qv.x, s, false);
+                    s = __builtin_amdgcn_sdot4((int)raw[j][u].y, qv.y, s, false);
+                    s = __builtin_amdgcn_sdot4((int)raw[j][u].z, qv.z, s, false);
+                    s = __builtin_amdgcn_sdot4((int)raw[j][u].w, qv.w, s, false);
+                    acc[u][q] = s;
+                }
+            }
+        }
+    }
+    int C[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) C[q] = hq_rows4_sum(acc[0][q], acc[1][q], acc[2][q], acc[3][q], l16);
+    if ((l16 & 3) != 0 || row >= a.n) return false;
+    const float s_r = a.aux[3 * row + HDB_QROW_S], e_r = a.aux[3 * row + HDB_QROW_E], t_r = a.aux[3 * row + HDB_QROW_T];
+    const bool masked = a.mask && !a.mask[row];
+    const float bias = a.bias ? a.bias[row] : 0.f;
+    const float invn = a.metric == HDB_COSINE ? a.inv_norm[row] : 1.f;
+    const float sqv = a.metric == HDB_EUCLIDEAN ? a.sqnorm[row] : 0.f;
+    {
+#pragma clang fp contract(off)
+        const float absmin = 0x1p-100f * (float)(a.d + 8);
+        const float g2 = 2.f * a.gamma;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            float lo = -INFINITY, hi = -INFINITY;
+            if (!qc.bad[q] && !masked) {
+                const float A = (qc.s[q] * s_r) * (float)C[q];
+                const float aA = fabsf(A);
+                const float B = (qc.n[q] * e_r + qc.d[q] * t_r) * (1.f + 0x1p-10f) + aA * 0x1p-10f + absmin;
+                float l, h;
+                if (a.metric == HDB_EUCLIDEAN) {
+                    const float ctr = sqv + qc.sq[q] - 2.f * A;
+                    const float err = g2 * sqv + 2.f * B + 0x1p-10f * (sqv + qc.sq[q] + 2.f * aA) + absmin;
+                    const float elo = fmaxf(ctr - err, 0.f) * (1.f - g2 - 0x1p-10f);
+                    const float ehi = (ctr + err) * (1.f + g2 + 0x1p-10f);
+                    h = (float)(1.f / (1.f + sqrt(elo)));
+                    l = (float)(1.f / (1.f + sqrt(ehi)));
+                } else {
+                    l = A - B; h = A + B;
+                    if (a.metric == HDB_COSINE) { l = l * invn * qc.inv[q]; h = h * invn * qc.inv[q]; }
+                }
+                if (a.bias) { l += bias; h += bias; }
+                l = l - fabsf(l) * 0x1p-20f - 1e-30f;
+                h = h + fabsf(h) * 0x1p-20f + 1e-30f;
+                if (l != l) l = -INFINITY;
+                if (h != h) h = INFINITY;
+                lo = l; hi = h;
+            }
+            sink(q, lo, hi, masked);
+        }
+    }
+    return true;
+}
+
+// The argument block where the launch left it, in the kernarg segment.  QuantArgs MUST stay the first (and only) parameter of every
+// kernel that reaches this function -- hdb_quant_scan_kernel and hdb_quant_plane_scan_kernel -- so that it lies at offset 0: a
+// parameter put in front of it would make this read something else without a compiler error.  Code that runs rarely -- a stage that is full, a drain of the plane pass, the flush -- reads its fields through this
+// reference when it gets there, so that the streaming loop around it does not hold two dozen pointers in registers for it.  The
+// empty asm keeps the loads from being moved back in front of the loop.
+__device__ __forceinline__ const QuantArgs& hq_args_in_memory() {
+    typedef const __attribute__((address_space(4))) QuantArgs* ArgPtr;
+    const uint64_t v = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    asm volatile("" : "+v"(lo), "+v"(hi));
+    lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo); hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi);      // (scalar again: scalar loads)
+    return *(const QuantArgs*)(ArgPtr)(((uint64_t)hi << 32) | lo);
+}
+
+// Matrix-core flavour (a.G non-null): candidate `row` of list slot `slot` goes to row `slot` of the compact matrix, its 1/||v|| and
+// bias beside it -- the bias as the matrix-core scan takes it, the row mask folded in (hdb_maskbias_kernel).  The lanes `l` of `nl`
+// share the row's 16-byte pieces.  Slots past a query's count are left as they are: the MODE 0 launch scores them too (its grid is
+// set by the host, which does not know the counts) and nobody reads those scores.
+__device__ __forceinline__ void hq_copy_row(const QuantArgs& a, int64_t slot, uint32_t row, int l, int nl) {
+    const char* src = a.V + (int64_t)row * a.row_bytes;
+    char* dst = a.G + slot * a.row_bytes;
+    for (int c = l * 16; c < a.row_bytes; c += nl * 16) *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(src + c);
+    if (l == 0) {
+        if (a.ginv) a.ginv[slot] = a.inv_norm[row];
+        if (a.gbias) a.gbias[slot] = a.mask ? (a.mask[row] ? (a.bias ? a.bias[row] : 0.f) : -INFINITY) : a.bias[row];
+    }
+}
+// A row whose upper bound reaches the threshold of query q: into the workgroup's stage, or straight to the list when that is full.
+__device__ __forceinline__ void hq_emit(HqStage& stage, int q, float hi, int64_t row) {
+    const unsigned long long ent = hdb_pack(hi, (uint32_t)row);
+    const unsigned int lp = atomicAdd(&stage.cnt[q], 1u);                    // LDS
+    if (lp < HQ_STAGE_CAP) stage.buf[q][lp] = ent;
+    else {
+        const QuantArgs& a = hq_args_in_memory();
+        const uint32_t pos = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], 1u);      // the stage is full: straight to the list
+        if (pos < a.cap) {
+            a.cand[(int64_t)q * a.cap + pos] = ent;
+            if (a.G) hq_copy_row(a, (int64_t)q * a.cap + pos, (uint32_t)row, 0, 1);
+        }
+    }
+}
+// The stage to the lists: one atomic per workgroup and query (hdb_stage_flush), then one wave per entry for the row copies.
+template <int NQ>
+__device__ __forceinline__ void hq_stage_flush(HqStage& stage) {
+    __syncthreads();
+    const QuantArgs& a = hq_args_in_memory();
+    for (int q = 0; q < NQ; ++q) {
+        const unsigned int have = min(stage.cnt[q], (unsigned int)HQ_STAGE_CAP);
+        if (have == 0u) continue;
+        if (threadIdx.x == 0) stage.base = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], have);
+        __syncthreads();
+        const unsigned int base = stage.base;
+        for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
+            if (base + e < a.cap) a.cand[(int64_t)q * a.cap + base + e] = stage.buf[q][e];
+        if (a.G)
+            for (unsigned int e = threadIdx.x >> 6; e < have; e += blockDim.x >> 6)
+                if (base + e < a.cap)
+                    hq_copy_row(a, (int64_t)q * a.cap + base + e, 0xFFFFFFFFu - (uint32_t)(stage.buf[q][e] & 0xFFFFFFFFull), threadIdx.x & 63, 64);
+        __syncthreads();
+    }
+}
+
+// MODE 0: lower bounds of the sampled rows -> scores[q][ld], or (nsub > 0) the per-wave maxima -> wmax;  MODE 1: rows whose upper bound
+// reaches the threshold (thr[q], or nsub > 0: folded, hq_fold_thr) -> candidate lists;  MODE 2 (tests): MODE 1's upper bound of every
+// row -> dbg[row], nothing emitted.
+// (QuantArgs stays the first parameter: hq_args_in_memory.)
+template <int MODE, int NQ, int NJ>
 __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
+    static_assert(sizeof(QuantArgs) % 8 == 0, "the argument block is read back from the kernarg segment as laid out here");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int4* qs = reinterpret_cast<int4*>(smem);                       // [NQ][nch]
     __shared__ HqStage stage;
     const int nch = a.P >> 4;
-    static_assert(!LIST || (MODE == 1 && NQ == 1), "the list flavour is pass 2 of a one-query call");
     if (MODE == 1 && threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
     for (int i = threadIdx.x; i < NQ * nch; i += 256) qs[i] = reinterpret_cast<const int4*>(a.qcodes)[i];
-    float q_s[NQ], q_n[NQ], q_d[NQ], q_sq[NQ], q_inv[NQ], q_thr[NQ];
-    bool q_bad[NQ];
+    HqQuery<NQ> qc;
+    hq_query_load<NQ>(a, qc);
+    float q_thr[NQ];
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const float* o = a.qaux + (int64_t)q * HDB_QQ_WORDS;
-        q_s[q] = o[HDB_QQ_S]; q_n[q] = o[HDB_QQ_N]; q_d[q] = o[HDB_QQ_D]; q_sq[q] = o[HDB_QQ_SQ]; q_bad[q] = o[HDB_QQ_BAD] != 0.f;
-        q_inv[q] = a.metric == HDB_COSINE ? a.qinv[q] : 1.f;
-        q_thr[q] = (MODE == 1 && a.nsub == 0) ? a.thr[q] : 0.f;
-    }
+    for (int q = 0; q < NQ; ++q) q_thr[q] = (MODE == 1 && a.nsub == 0) ? a.thr[q] : 0.f;
     __syncthreads();
     if (MODE == 1 && a.nsub > 0) hq_fold_thr<NQ>(a, q_thr);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, l16 = lane & 15;
-    const int nj = NJ > 0 ? NJ : (nch + 15) >> 4;
-    constexpr int G = NJ > 0 ? NJ : 2;
-    const float absmin = 0x1p-100f * (float)(a.d + 8);
-    const float g2 = 2.f * a.gamma;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     uint32_t wbest[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) wbest[q] = 0u;
 
-    int64_t ntiles = a.ntiles;
-    uint32_t pl_n = 0u;
-    bool pl_list = false;
-    if (LIST) {
-        pl_n = a.pl_cnt[0];
-        pl_list = pl_n <= a.pl_cap;
-        if (pl_list) ntiles = ((int64_t)pl_n + 15) >> 4;
-        else if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.pl_cnt[1], 1u);      // (stat plane_overflows)
-    }
+    const int64_t ntiles = a.ntiles;
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
         const int64_t r0 = hdb_tile_index(t, a.tile_stride) * 16 + 4 * g;
-        int64_t rr[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            rr[u] = r0 + u;
-            if (LIST && pl_list) rr[u] = (uint64_t)(r0 + u) < (uint64_t)pl_n ? (int64_t)a.pl_list[r0 + u] : a.n;      // (a.n: no row)
-        }
-        const int8_t* p[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = a.codes + min(rr[u], a.n - 1) * (int64_t)a.P;
-        int acc[4][NQ];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) acc[u][q] = 0;
-        for (int j0 = 0; j0 < nj; j0 += G) {
-            uint4 raw[G][4];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const int c = l16 + 16 * (j0 + j);
-                const bool live = (j0 + j) < nj && c < nch;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (live) {
-                        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p[u] + (int64_t)c * 16));
-                        raw[j][u] = make_uint4(v.x, v.y, v.z, v.w);
-                    } else {
-                        raw[j][u] = make_uint4(0u, 0u, 0u, 0u);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);           // loads ahead of every use
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const int c = l16 + 16 * (j0 + j);
-                const int cc = c < nch ? c : 0;          // (dead pieces are zero: any query piece gives 0)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const int4 qv = qs[q * nch + cc];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        int s = acc[u][q];
-                        s = __builtin_amdgcn_sdot4((int)raw[j][u].x, qv.x, s, false);
-                        s = __builtin_amdgcn_sdot4((int)raw[j][u].y, qv.y, s, false);
-                        s = __builtin_amdgcn_sdot4((int)raw[j][u].z, qv.z, s, false);
-                        s = __builtin_amdgcn_sdot4((int)raw[j][u].w, qv.w, s, false);
-                        acc[u][q] = s;
-                    }
-                }
-            }
-        }
+        const int64_t rr[4] = {r0, r0 + 1, r0 + 2, r0 + 3};
         const int u_own = hdb_owned_row(l16);
-        const int64_t row = LIST ? (u_own == 0 ? rr[0] : u_own == 1 ? rr[1] : u_own == 2 ? rr[2] : rr[3]) : r0 + u_own;
-        int C[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) C[q] = hq_rows4_sum(acc[0][q], acc[1][q], acc[2][q], acc[3][q], l16);
-        if ((l16 & 3) != 0) continue;
+        const int64_t row = r0 + u_own;
         const int64_t out_i = t * 16 + 4 * g + u_own;
-        if (row >= a.n) {
-            if (MODE == 0 && a.nsub == 0)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) a.scores[(int64_t)q * a.ld + out_i] = -INFINITY;
-            continue;
-        }
-        const float s_r = a.aux[3 * row + HDB_QROW_S], e_r = a.aux[3 * row + HDB_QROW_E], t_r = a.aux[3 * row + HDB_QROW_T];
-        const bool masked = a.mask && !a.mask[row];
-        const float bias = a.bias ? a.bias[row] : 0.f;
-        const float invn = a.metric == HDB_COSINE ? a.inv_norm[row] : 1.f;
-        const float sqv = a.metric == HDB_EUCLIDEAN ? a.sqnorm[row] : 0.f;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            float lo = -INFINITY, hi = -INFINITY;
-            if (!q_bad[q] && !masked) {
-                const float A = (q_s[q] * s_r) * (float)C[q];
-                const float aA = fabsf(A);
-                const float B = (q_n[q] * e_r + q_d[q] * t_r) * (1.f + 0x1p-10f) + aA * 0x1p-10f + absmin;
-                if (a.metric == HDB_EUCLIDEAN) {
-                    const float ctr = sqv + q_sq[q] - 2.f * A;
-                    const float err = g2 * sqv + 2.f * B + 0x1p-10f * (sqv + q_sq[q] + 2.f * aA) + absmin;
-                    const float elo = fmaxf(ctr - err, 0.f) * (1.f - g2 - 0x1p-10f);
-                    const float ehi = (ctr + err) * (1.f + g2 + 0x1p-10f);
-                    hi = (float)(1.f / (1.f + sqrt(elo)));
-                    lo = (float)(1.f / (1.f + sqrt(ehi)));
-                } else {
-                    lo = A - B; hi = A + B;
-                    if (a.metric == HDB_COSINE) { lo = lo * invn * q_inv[q]; hi = hi * invn * q_inv[q]; }
-                }
-                if (a.bias) { lo += bias; hi += bias; }
-                lo = lo - fabsf(lo) * 0x1p-20f - 1e-30f;
-                hi = hi + fabsf(hi) * 0x1p-20f + 1e-30f;
-                if (lo != lo) lo = -INFINITY;
-                if (hi != hi) hi = INFINITY;
-            }
+        const bool live = hq_rows4_bounds<NQ, NJ, (NJ > 0 ? NJ : 2)>(a, qs, qc, rr, l16, row, [&](int q, float lo, float hi, bool masked) {
             if (MODE == 2) {
                 a.dbg[row] = hi;
             } else if (MODE == 0) {
                 if (a.nsub > 0) wbest[q] = max(wbest[q], hdb_f2key(lo));
                 else a.scores[(int64_t)q * a.ld + out_i] = lo;
-            } else if (!masked && !q_bad[q] && hi >= q_thr[q]) {
-                const unsigned long long ent = hdb_pack(hi, (uint32_t)row);
-                const unsigned int lp = atomicAdd(&stage.cnt[q], 1u);                    // LDS
-                if (lp < HQ_STAGE_CAP) stage.buf[q][lp] = ent;
-                else {
-                    const uint32_t pos = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], 1u);      // the slot is full: straight to the list
-                    if (pos < a.cap) a.cand[(int64_t)q * a.cap + pos] = ent;
-                }
+            } else if (!masked && !qc.bad[q] && hi >= q_thr[q]) {
+                hq_emit(stage, q, hi, row);
             }
-        }
+        });
+        if (MODE == 0 && a.nsub == 0 && !live && (l16 & 3) == 0)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) a.scores[(int64_t)q * a.ld + out_i] = -INFINITY;
     }
     if (MODE == 0 && a.nsub > 0) {                       // (every wave of the grid writes its slot: a wave without tiles writes 0)
 #pragma unroll
@@ -574,19 +651,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
             if (lane == 0) a.wmax[(int64_t)q * a.nsub + blockIdx.x * 4 + wave] = wm;
         }
     }
-    if (MODE == 1) {                                     // one atomic per block and query (hdb_stage_flush)
-        __syncthreads();
-        for (int q = 0; q < NQ; ++q) {
-            const unsigned int have = min(stage.cnt[q], (unsigned int)HQ_STAGE_CAP);
-            if (have == 0u) continue;
-            if (threadIdx.x == 0) stage.base = atomicAdd(&a.cnt[q * HDB_CNT_STRIDE], have);
-            __syncthreads();
-            const unsigned int base = stage.base;
-            for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
-                if (base + e < a.cap) a.cand[(int64_t)q * a.cap + base + e] = stage.buf[q][e];
-            __syncthreads();
-        }
-    }
+    if (MODE == 1) hq_stage_flush<NQ>(stage);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -634,21 +699,33 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
     }
 }
 
-// Pass 1: the coarse upper bound hi5 (header, "The 5-bit plane") of every row; rows with hi5 >= T_s go to the survivor list.
+// Pass 1: the coarse upper bound hi5 (header, "The 5-bit plane") of every row; a row with hi5 >= T_s is finished here, by the wave
+// that found it.
 // A wave takes two 16-row tiles per step.  A tile of the nibble plane is 16 U contiguous 16-byte pieces and lane l takes pieces
 // l + 64 j, j < J = ceil(U / 4), i.e. whole-wave contiguous loads with every lane busy (U = 12 at d = 384: exactly 3 per lane); piece
 // f belongs to row f / U, unit f % U -- the same for every tile, so a lane keeps the query words of its J units in registers.
 // The per-piece sums meet in LDS (wave-private), lanes 0-31 add the U pieces of one row each and evaluate the bound.
-#define HQ_PL_STAGE 1024
+// Survivors wait in a wave-private queue of row numbers (LDS; appended by ballot and popcount, no atomics).  Once it holds 16 the wave
+// takes 16 of them as one MODE 1 tile -- 16 lanes per 4 rows, hq_rows4_bounds with the row numbers from the queue -- and emits the
+// candidates through the workgroup's stage exactly as MODE 1 does; what is left after the last step goes as a ragged tile (empty
+// slots: "no row" = a.n).  The gather's latency chain (row number -> code row -> row terms) hides behind the other waves' streams.
+// A step appends at most 32 rows to fewer than 16, and a drain leaves fewer than 16: 48 entries per wave.
+// (96 scalar registers: the drain's nest of branches and its argument loads would otherwise take the kernel past 96, which costs the
+//  narrow widths a wave per SIMD; with the cap the allocator keeps a handful of scalars in vector lanes around the drain instead.
+//  QuantArgs stays the first parameter: hq_args_in_memory.  The empty asm statements here and in the drain only steer the register
+//  allocator; the figures they buy are in profiles/quant_inpass_kernel_resources.txt with the compiler they were taken with.)
+#define HQ_PL_QUEUE 48
 template <int J, bool DBG>
-__global__ __launch_bounds__(256) void hdb_quant_plane_scan_kernel(QuantArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_quant_plane_scan_kernel(QuantArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int4* qs = reinterpret_cast<int4*>(smem);                       // [2 U] query codes, zero past P
+    int4* qs = reinterpret_cast<int4*>(smem);                       // [2 U] query codes, zero past P: MODE 1's layout for one query
     __shared__ int part[4][2][64 * J];
-    __shared__ uint32_t st_buf[HQ_PL_STAGE];
-    __shared__ uint32_t st_cnt, st_base;
+    __shared__ HqStage stage;
+    __shared__ uint32_t queue[4][HQ_PL_QUEUE];
+    __shared__ uint32_t surv_cnt;
     const int U = a.pl_units, nch = a.P >> 4;
-    if (threadIdx.x == 0) st_cnt = 0u;
+    if (threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) surv_cnt = 0u;
     for (int i = threadIdx.x; i < 2 * U; i += 256) qs[i] = i < nch ? reinterpret_cast<const int4*>(a.qcodes)[i] : make_int4(0, 0, 0, 0);
     const float* qo = a.qaux;
     const float q_s = qo[HDB_QQ_S], q_n = qo[HDB_QQ_N], q_d = qo[HDB_QQ_D], q_cn = qo[HDB_QQ_CN];
@@ -661,39 +738,61 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_scan_kernel(QuantArgs a) 
     if (!DBG && a.nsub > 0) hq_fold_thr<1>(a, thr1);
     const float q_thr = thr1[0];
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (the tile number stays scalar)
     const int npieces = 16 * U;
     int qw[J][8];
-    int prow[J];                                                    // row of piece j within its tile (16: no such piece)
+    auto load_qw = [&]() {
 #pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int f = lane + 64 * j;
-        const int unit = f < npieces ? f % U : 0;
-        prow[j] = f < npieces ? f / U : 16;
-        const int4 x = qs[2 * unit], y = qs[2 * unit + 1];
-        qw[j][0] = x.x; qw[j][1] = x.y; qw[j][2] = x.z; qw[j][3] = x.w;
-        qw[j][4] = y.x; qw[j][5] = y.y; qw[j][6] = y.z; qw[j][7] = y.w;
-    }
+        for (int j = 0; j < J; ++j) {
+            const int f = lane + 64 * j;
+            const int unit = f < npieces ? f % U : 0;
+            const int4 x = qs[2 * unit], y = qs[2 * unit + 1];
+            qw[j][0] = x.x; qw[j][1] = x.y; qw[j][2] = x.z; qw[j][3] = x.w;
+            qw[j][4] = y.x; qw[j][5] = y.y; qw[j][6] = y.z; qw[j][7] = y.w;
+        }
+    };
+    load_qw();
     const float absmin = 0x1p-100f * (float)(a.d + 8);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int64_t ntiles = a.ntiles;
     const int et = lane >> 4, er = lane & 15;                       // epilogue lanes 0-31: tile et of the pair, row er
+    int qn = 0;                                                     // rows in this wave's queue (wave-uniform)
+    uint32_t nsurv = 0u;                                            // rows this wave kept (wave-uniform)
+    // `m` queued rows from entry `base` on as one MODE 1 tile (m <= 16)
+    auto drain = [&](int base, int m) {
+        const QuantArgs& a = hq_args_in_memory();
+        HqQuery<1> qc;
+        qc.s[0] = q_s; qc.n[0] = q_n; qc.d[0] = q_d; qc.sq[0] = 0.f; qc.inv[0] = q_inv; qc.bad[0] = q_bad;      // (dot / cosine: no ||q||^2)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                     // (nothing of the tile is computed ahead of the loop and held through the stream)
+        const int g = ln >> 4, l16 = ln & 15;
+        int64_t rr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) rr[u] = 4 * g + u < m ? (int64_t)queue[wave][base + 4 * g + u] : a.n;
+        const int own = 4 * g + hdb_owned_row(l16);
+        const int64_t row = own < m ? (int64_t)queue[wave][base + own] : a.n;
+        hq_rows4_bounds<1, 0, 1>(a, qs, qc, rr, l16, row, [&](int, float, float hi, bool masked) {     // (one piece in flight: few registers)
+            if (!masked && !q_bad && hi >= q_thr) hq_emit(stage, 0, hi, row);
+        });
+    };
 
     for (int64_t t = ((int64_t)blockIdx.x * 4 + wave) * 2; t < ntiles; t += (int64_t)gridDim.x * 8) {
         u32x4 nv[2][J];
         uint32_t bv[2][J];
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                     // (piece numbers and lane offsets are formed per step, from one register held across steps)
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-            const int64_t rows_left = a.n - (t + tt) * 16;          // (<= 0 past the last tile; the ragged tile loads its own rows only)
+            // pieces of this tile's own rows: 0 past the last tile, the ragged tile loads its rows only (piece f is of row f / U)
+            const int pieces_left = (int)min((int64_t)16, max((int64_t)0, a.n - (t + tt) * 16)) * U;
             const uint8_t* nb = a.pl_nib + (t + tt) * (int64_t)npieces * 16;
             const uint32_t* bb = a.pl_bit + (t + tt) * (int64_t)npieces;
 #pragma unroll
             for (int j = 0; j < J; ++j) {
-                const int f = lane + 64 * j;
-                if ((int64_t)prow[j] < rows_left && prow[j] < 16) {
-                    nv[tt][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(nb + (int64_t)f * 16));
-                    bv[tt][j] = __builtin_nontemporal_load(bb + f);
+                if (ln < pieces_left - 64 * j) {
+                    nv[tt][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(nb + (uint32_t)ln * 16u) + 64 * j);     // (piece ln + 64 j: scalar base, 32-bit lane offset)
+                    bv[tt][j] = __builtin_nontemporal_load(bb + (uint32_t)ln + 64 * j);
                 } else {
                     nv[tt][j] = u32x4{0u, 0u, 0u, 0u};
                     bv[tt][j] = 0u;
@@ -738,9 +837,8 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_scan_kernel(QuantArgs a) 
             for (int i = 0; i < U; ++i) S += part[wave][et][er * U + i];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();                 // (the next step's stores stay behind these loads)
-        if (!rvalid) continue;
         float hi5 = -INFINITY;
-        const bool dead = masked || q_bad;
+        const bool dead = !rvalid || masked || q_bad;
         if (!dead) {
             const float fc = (float)(8 * S - 124 * q_cs);
             const float Uf = q_cn * rc.w;
@@ -764,25 +862,36 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_scan_kernel(QuantArgs a) 
             if (hi5 != hi5) hi5 = INFINITY;
         }
         if (DBG) {
-            a.dbg[row] = hi5;
-        } else if (!dead && !(hi5 < q_thr)) {
-            const unsigned int lp = atomicAdd(&st_cnt, 1u);                              // LDS
-            if (lp < HQ_PL_STAGE) st_buf[lp] = (uint32_t)row;
-            else {
-                const uint32_t pos = atomicAdd(&a.pl_cnt[0], 1u);                        // the stage is full: straight to the list
-                if (pos < a.pl_cap) a.pl_list[pos] = (uint32_t)row;
-            }
+            if (rvalid) a.dbg[row] = hi5;
+            continue;
+        }
+        const bool keep = !dead && !(hi5 < q_thr);
+        const unsigned long long km = __ballot(keep);
+        if (km == 0ull) continue;                        // (wave-uniform)
+        if (keep) queue[wave][qn + __popcll(km & ((1ull << lane) - 1ull))] = (uint32_t)row;
+        const int nk = __popcll(km);
+        qn += nk; nsurv += (uint32_t)nk;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (qn >= 16) {
+            do { qn -= 16; drain(qn, 16); } while (qn >= 16);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();             // (the next append stays behind the drain's loads)
+            // the query words are not held through a drain (its tile needs the registers): read them again
+            asm volatile("" ::: "memory");
+            load_qw();
         }
     }
-    if (!DBG) {                                          // one atomic per block
-        __syncthreads();
-        const unsigned int have = min(st_cnt, (unsigned int)HQ_PL_STAGE);
-        if (have != 0u) {
-            if (threadIdx.x == 0) st_base = atomicAdd(&a.pl_cnt[0], have);
-            __syncthreads();
-            const unsigned int base = st_base;
-            for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
-                if (base + e < a.pl_cap) a.pl_list[base + e] = st_buf[e];
+    if (!DBG) {
+        if (qn > 0) drain(0, qn);
+        if (lane == 0 && nsurv != 0u) atomicAdd(&surv_cnt, nsurv);                       // LDS
+        hq_stage_flush<1>(stage);
+        if (threadIdx.x == 0 && surv_cnt != 0u) {                                        // one atomic per workgroup (stat plane_survivors)
+            const QuantArgs& a = hq_args_in_memory();
+            const uint32_t before = atomicAdd(&a.pl_cnt[0], surv_cnt);
+            // the count passes plane_cap_rows in exactly one workgroup's add (stat plane_overflows: the plane kept more than it is worth)
+            if (before <= a.pl_cap && before + surv_cnt > a.pl_cap) atomicAdd(&a.pl_cnt[1], 1u);
         }
     }
 }
@@ -867,29 +976,6 @@ __global__ __launch_bounds__(256) void hdb_quant_rescore_kernel(RescoreArgs a) {
     }
 }
 
-// Matrix-core flavour of the rescoring, first half: the candidate rows of query q go to rows [q cap, q cap + count) of a compact
-// matrix G (row_bytes a multiple of 256, as every MFMA geometry has it), their 1/||v|| and bias beside them -- the bias as the
-// matrix-core scan takes it, the row mask folded in (hdb_maskbias_kernel).  One wave per candidate.  Rows past a query's count
-// are left as they are: the MODE 0 launch scores them too (its grid is set by the host, which does not know the counts) and
-// nobody reads those scores.
-__global__ __launch_bounds__(256) void hdb_quant_cgather_kernel(const char* V, int row_bytes, const float* inv_norm, const float* bias,
-                                                                const uint8_t* mask, const unsigned long long* cand, const uint32_t* cnt,
-                                                                uint32_t cap, char* G, float* ginv, float* gbias) {
-    const int q = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t total = min(cnt[q * HDB_CNT_STRIDE], cap);
-    for (uint32_t i = blockIdx.x * 4 + wave; i < total; i += gridDim.x * 4) {
-        const int64_t slot = (int64_t)q * cap + i;
-        const uint32_t row = 0xFFFFFFFFu - (uint32_t)(cand[slot] & 0xFFFFFFFFull);
-        const char* src = V + (int64_t)row * row_bytes;
-        char* dst = G + slot * row_bytes;
-        for (int c = lane * 16; c < row_bytes; c += 64 * 16) *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(src + c);
-        if (lane == 0) {
-            if (ginv) ginv[slot] = inv_norm[row];
-            if (gbias) gbias[slot] = mask ? (mask[row] ? (bias ? bias[row] : 0.f) : -INFINITY) : bias[row];
-        }
-    }
-}
-
 // Finalize: hdb_finalize_fast over the rescored list with the floor T_s (see "Completeness" above).  A query with an infinite
 // element, or one the quantized prep could not take, is reported as HDB_Q_UNDERFLOW: hdb_topk_host re-runs it exactly.
 __global__ __launch_bounds__(1024) void hdb_quant_finalize_kernel(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, uint32_t k,
@@ -950,15 +1036,6 @@ extern "C" int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, fl
     return (int)hipGetLastError();
 }
 
-extern "C" int hdb_launch_quant_cgather(const void* V, int row_bytes, const float* inv_norm, const float* bias, const uint8_t* mask,
-                                        const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, void* G, float* ginv,
-                                        float* gbias, void* stream) {
-    if (row_bytes % 16 != 0 || (reinterpret_cast<uintptr_t>(V) & 15) != 0) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(hdb_quant_cgather_kernel, dim3(256, nq), dim3(256), 0, (hipStream_t)stream, (const char*)V, row_bytes, inv_norm, bias,
-                       mask, cand, cnt, cap, (char*)G, ginv, gbias);
-    return (int)hipGetLastError();
-}
-
 template <int MODE, int NQ>
 static void hq_launch_scan_nq(const QuantArgs& a, int blocks, size_t lds, hipStream_t st) {
     const int nch = a.P >> 4;
@@ -977,6 +1054,10 @@ static void hq_launch_scan_mode(const QuantArgs& a, int blocks, size_t lds, hipS
     default: hq_launch_scan_nq<MODE, 4>(a, blocks, lds, st); break;
     }
 }
+// the row copies of the matrix-core flavour move 16-byte pieces
+static bool hq_copy_args_ok(const QuantArgs& a) {
+    return !a.G || (a.V && a.row_bytes > 0 && a.row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(a.V) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.G) & 15) == 0);
+}
 // mode 0: lower bounds of the sampled tiles; mode 1: candidate emission over a.ntiles dense tiles.  1 <= a.nq <= 4.
 extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream) {
     const QuantArgs& a = *args;
@@ -985,11 +1066,14 @@ extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_bl
     const int blocks = hdb_quant_scan_blocks(a.ntiles, max_blocks);
     if (a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || (mode == 0 ? a.nsub != 4 * blocks : !a.thr_out))) return (int)hipErrorInvalidValue;
     if (mode == 0) hq_launch_scan_mode<0>(a, blocks, lds, (hipStream_t)stream);
-    else hq_launch_scan_mode<1>(a, blocks, lds, (hipStream_t)stream);
+    else {
+        if (!hq_copy_args_ok(a)) return (int)hipErrorInvalidValue;
+        hq_launch_scan_mode<1>(a, blocks, lds, (hipStream_t)stream);
+    }
     return (int)hipGetLastError();
 }
 
-// The 5-bit plane: derivation, pass 1 and pass 2 (one query; dot / cosine).
+// The 5-bit plane: derivation and pass 1 (one query; dot / cosine).
 extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib,
                                            uint32_t* bitw, float* rec, void* stream) {
     if (m <= 0) return 0;
@@ -999,12 +1083,13 @@ extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux
                        P, U, nib, bitw, rec);
     return (int)hipGetLastError();
 }
-// dbg = false: pass 1 (survivor list); dbg = true: hi5 of every row -> a.dbg (tests)
+// dbg = false: pass 1 (candidates of the rows the plane keeps; the threshold as MODE 1 takes it, folded or a.thr); dbg = true: hi5 of every row -> a.dbg (tests)
 extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream) {
     const QuantArgs& a = *args;
     const int U = a.pl_units;
     if (a.nq != 1 || U < 1 || U > 16 || U != hdb_quant_plane_units(a.P) || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
     if (!dbg && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
+    if (!dbg && (!a.cnt || !a.cand || !a.pl_cnt || !hq_copy_args_ok(a))) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)U * 32;
     const int blocks = hdb_grid_for((a.ntiles + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024);
     hipStream_t st = (hipStream_t)stream;
@@ -1015,17 +1100,15 @@ extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int m
 #undef HQ_PLANE
     return (int)hipGetLastError();
 }
-// mode 1: pass 2 (MODE 1 over the survivor list, a.ntiles = the dense tile count for the overflow case); mode 2: MODE 1's upper
-// bound of every row -> a.dbg (tests)
+// MODE 1's upper bound of every row of a.ntiles dense tiles for one query -> a.dbg (tests)
 extern "C" int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream) {
     const QuantArgs& a = *args;
-    if (a.nq != 1 || (a.P & 15) != 0 || a.nsub != 0 || (mode != 1 && mode != 2)) return (int)hipErrorInvalidValue;
+    if (a.nq != 1 || (a.P & 15) != 0 || a.nsub != 0 || mode != 2 || !a.dbg) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)a.P;
     const int blocks = hdb_quant_scan_blocks(a.ntiles, max_blocks);
     const int nj = ((a.P >> 4) + 15) >> 4;
     hipStream_t st = (hipStream_t)stream;
-#define HQ_ONE(NJ_) do { if (mode == 1) hipLaunchKernelGGL((hdb_quant_scan_kernel<1, 1, NJ_, true>), dim3(blocks), dim3(256), lds, st, a); \
-                         else hipLaunchKernelGGL((hdb_quant_scan_kernel<2, 1, NJ_, false>), dim3(blocks), dim3(256), lds, st, a); } while (0)
+#define HQ_ONE(NJ_) hipLaunchKernelGGL((hdb_quant_scan_kernel<2, 1, NJ_>), dim3(blocks), dim3(256), lds, st, a)
     if (nj == 1) HQ_ONE(1); else if (nj == 2) HQ_ONE(2); else if (nj == 3) HQ_ONE(3); else HQ_ONE(0);
 #undef HQ_ONE
     return (int)hipGetLastError();
