@@ -29,8 +29,10 @@ extern "C" {
 typedef struct hdb_index hdb_index;
 
 /* dtype of the stored matrix: HyperDB(fp_precision=...) accepts float16/32/64 (hyperdb.py:65-66); bfloat16 (the upper 16 bits of
- * a float32, 2 bytes per element) is this library's addition for embedding models that emit it. */
-enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3 };
+ * a float32, 2 bytes per element) is this library's addition for embedding models that emit it, and so is OCP float8 e4m3
+ * (torch.float8_e4m3fn: 1 sign, 4 exponent, 3 mantissa bits, bias 7, no infinities, 0x7F / 0xFF = NaN; one byte per element).
+ * Code 4 is unassigned and refused by hdb_index_create, like every other value not listed here. */
+enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5 };
 
 /* metric strings of hyperDB_ranking_algorithm_sort's dispatch table (ranking_algorithm.py:155-163). */
 enum hdb_metric {
@@ -105,7 +107,7 @@ void hdb_index_destroy(hdb_index* ix);
 /* Opt-in int8 shadow of the matrix: quantized row scan with exact rescoring (local-hyperdb_amd/csrc/hdb_quant.hip).
  * HDB_QUANT_I8 builds, next to the float16 / float32 matrix, an owned int8 copy -- one code per element at a row pitch
  * P = round_up(d, 16) bytes -- and 12 bytes of per-row caches: N x (P + 12) bytes of device memory.  HDB_QUANT_NONE frees it.
- * float64 and bfloat16 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
+ * float64, bfloat16 and float8 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
  * hdb_index_gather moves codes and caches with the kept rows, hdb_index_update rebuilds it, hdb_index_rebase leaves it alone.
  *
  * The bound.  Row r: s_r = max_j |v_rj| / 127, c_rj = rne(v_rj / s_r), eps_r = v_r - s_r c_r; the query likewise (s_q, c_q,
@@ -235,7 +237,7 @@ int hdb_index_set_row_subset(hdb_index* ix, const uint8_t* dev_mask, const int64
 
 /* Full score vector of one query: the per-metric functions dot_product / cosine_similarity /
  * euclidean_metric / hamming_distance (... :24,:32,:44,:128).  dev_q: d elements, float32 for
- * F16/F32/BF16 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
+ * F16/F32/BF16/F8E4M3 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
 int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, void* stream);
 
 /* Top-k of nq independent queries: metric scoring + NaN->-inf + bias + argpartition/argsort of
@@ -276,7 +278,28 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     bf16_ks_min_q: -1 = that rule, else a fixed number of queries, never fewer than 5).  Other widths stay on the VALU scan.
  *   - never: the single launches of the matrix-core paths (fused = 0 always), the int8 shadow (hdb_index_quantize returns
  *     HDB_ERR_UNSUPPORTED, auto_quant does not apply).
- * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch), path as for the other dtypes. */
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch), path as for the other dtypes.
+ * float8 e4m3 matrices (HDB_F8E4M3).  Queries are float32.  Each of the 254 finite codes (largest magnitude 448, smallest 2^-9)
+ * widens to float32 exactly (v_cvt_pk_f32_fp8), and the contract is the float32 one: scores within 1e-5 of the reference's
+ * arithmetic on the widened matrix (hamming exact, jaccard 1e-6).  No approximate filter, no rescoring, no second copy.
+ *   - 1-4 queries, every metric, any d, any k, bias, row mask and row list, and every batch no other path takes: the VALU scan
+ *     (float32 arithmetic on the widened values, unrounded float32 queries), four queries per pass, through the small, sampled,
+ *     exact and full-sort pipelines, as separate launches.  Rows of 256, 384 and 512 bytes have a fully unrolled ONE-query kernel on
+ *     a grid sized by bytes (hdb_scan.hip); the four-query kernel keeps the runtime loop on that grid -- an unrolled four-query
+ *     flavour that keeps ~100 KiB in flight per CU is not built (it needs all 256 registers), and four queries reach 1.2-1.4x over
+ *     bfloat16 instead of the 2x the bytes allow.  hamming / jaccard calls of 1-4 queries may take their single launch (it reads
+ *     the packed sign bits only).  Manhattan batches stay on the 4-queries-per-pass scan.
+ *   - 5+ dot / cosine / euclidean / pearson queries on a matrix without a NaN code, d = 128, 256, 384 or 512, use_mfma on: the matrix
+ *     cores (hdb_mfma_f8.hip), multi-kernel pipeline.  The rows are converted to bf16 per fragment in registers (exact: a code has
+ *     four significant bits), a float32 query travels as three bf16 parts that add up to it exactly: three v_mfma_f32_16x16x32_bf16
+ *     per k-step, every product exact, float32 accumulation, the bfloat16 flavour's K walk and epilogue -- the scores are those of
+ *     a bfloat16 index over the widened matrix bit for bit.  A query element that is not finite keeps its first part only (status
+ *     words stay 0).  A matrix holding a NaN code stays on the VALU scan.  Other widths stay on the VALU scan.
+ *   - a matrix holding a NaN code raises the NaN flag (hdb_index_has_nan) like a NaN of any other dtype.
+ *   - never: the single launches of the matrix-core paths (fused = 0 always), the LDS tile kernel of manhattan batches, the int8 shadow
+ *     and its 5-bit plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED, auto_quant does not apply: one byte per element already
+ *     is the shadow's stream), K slices for wider rows.
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch). */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 

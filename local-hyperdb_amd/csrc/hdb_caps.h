@@ -7,6 +7,22 @@
 #pragma once
 #include "../../include/hyperdb_hip.h"
 
+// ---- hdb_scan.hip: the VALU row scan ----
+// Workgroups of a scan launch when the caller sets no limit.  A wave keeps one 16-row tile in flight, so the bytes in flight per CU
+// are workgroups per CU x 4 x 16 x row bytes: 2 workgroups per CU (512) with the 12-KiB tiles of 768-byte rows, 1 (256) with the
+// unrolled 1536-byte-row kernel -- ~100 KiB either way, the measured optimum of the fp16 / float32 scans.  The float8 kernels of
+// 256- / 384- / 512-byte rows have 4- / 6- / 8-KiB tiles: their grid grows by 768 / row bytes, up to the 4 workgroups per CU that
+// the registers of the ONE-query kernels allow (88-124 per lane: 4 waves per SIMD) -- 1024 / 1024 / 768 workgroups, 64 / 96 / 96 KiB
+// in flight per CU.  The four-query kernel takes the same grid; its dot flavour (116-118 registers) is resident four times per CU as
+// well, its euclidean / manhattan flavours (154-162: 3 waves per SIMD) three times -- the fourth workgroup of a CU waits its turn.
+static inline int hdb_scan_auto_blocks(int dtype, int row_bytes, bool vec, bool wide_rows) {
+    if (dtype == HDB_F8E4M3 && vec && (row_bytes == 256 || row_bytes == 384 || row_bytes == 512)) {
+        const int b = 512 * 768 / row_bytes;
+        return b < 1024 ? b : 1024;
+    }
+    return wide_rows ? 256 : 512;
+}
+
 // ---- hdb_mfma_ksplit.hip: K slices of rows too wide for one wave's query fragments ----
 // The slice list of a width: slice s covers `width[s]` elements of every row from byte `off[s]` of the stored row on; the widths
 // add up to d and every one of them is a slice geometry that is instantiated for the dtype (float32 512 / 768, fp16 1024 / 1536,
@@ -75,6 +91,12 @@ static inline int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtyp
 // row tiles a wave keeps in flight beside them -- 64 rows up to d = 256, 32 at d = 384, 16 at d = 512
 static inline int hdb_mfma_bf16_tile_rows(int d) { return (d == 128 || d == 256) ? 64 : d == 384 ? 32 : d == 512 ? 16 : 0; }
 
+// ---- hdb_mfma_f8.hip ----
+// float8 e4m3 rows (hdb_mfma_f8.h): d = 128, 256, 384 and 512, the bfloat16 flavour's widths (three bf16 query parts: 3 d / 8
+// registers per 16 queries).  A wave takes one 16-row tile at a time and reads its fragments from global memory, so the tile height
+// is the VALU scan's 16 rows at every width
+static inline int hdb_mfma_f8_tile_rows(int d) { return (d == 128 || d == 256 || d == 384 || d == 512) ? 16 : 0; }
+
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
 
@@ -93,6 +115,7 @@ static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 ||
 static inline int mfma_exact_tile_rows(int dtype, int d) {
     if (dtype == HDB_BF16 && d > 0 && hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;     // 640 .. 4096: K slices of 16-row stages (hdb_mfma_bf16_ks.hip)
     if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
+    if (dtype == HDB_F8E4M3) return d > 0 ? hdb_mfma_f8_tile_rows(d) : 0;
     const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
     if (!elem || d <= 0) return 0;
     if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
@@ -123,7 +146,7 @@ static inline int hdb_mfma_tile_rows(int dtype, int d) {
 // queries ONE launch of the MFMA scan covers (grid.y == 1): what a single-launch (mode 2) call can take
 static inline int hdb_mfma_batch_capacity(int dtype, int d) {
     if (hdb_mfma_tile_rows(dtype, d) <= 0 || hdb_mfma_ksplit_slices(dtype, d) > 0 || hdb_mfma_anyd_pad(dtype, d) > 0) return 0;      // (K slices, odd widths: the multi-kernel pipeline)
-    if (dtype == HDB_BF16) return 0;                                     // (bfloat16 rows likewise: no single launch is built)
+    if (dtype == HDB_BF16 || dtype == HDB_F8E4M3) return 0;             // (bfloat16 and float8 rows likewise: no single launch is built)
     if (dtype == HDB_F32) return (d == 512 || d == 768) ? 64 : 128;      // (d = 512 / 768: the bf16-part flavour pairs its waves over K, hdb_mfma_kernel.h KP)
     return (d == 384 || d == 128 || d == 256 || d == 512 || d == 640) ? 256 : 128;      // two query tiles per wave (hdb_mfma_qt2.hip)
 }

@@ -7,16 +7,31 @@
 #define HDB_WAVE 64
 
 // ---- element types -------------------------------------------------------------------------------
-// Bytes of one stored matrix element per hdb_dtype (include/hyperdb_hip.h: 0 float16, 1 float32, 2 float64, 3 bfloat16); 0 = no such
-// dtype.  Every row pitch in the library comes from here.
+// Bytes of one stored matrix element per hdb_dtype (include/hyperdb_hip.h: 0 float16, 1 float32, 2 float64, 3 bfloat16, 5 float8
+// e4m3; 4 is unassigned); 0 = no such dtype.  Every row pitch in the library comes from here.
 __host__ __device__ __forceinline__ int hdb_elem_bytes(int dtype) {
-    return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : 0;
+    return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : dtype == 5 ? 1 : 0;
 }
 // A bfloat16 as it lies in memory: the upper 16 bits of the float32 of the same value, so widening is a shift and exact.
 struct hdb_bf16 { unsigned short bits; };
 __host__ __device__ __forceinline__ float hdb_bf16_to_f(hdb_bf16 v) {
     const unsigned int u = (unsigned int)v.bits << 16;
     return __builtin_bit_cast(float, u);
+}
+
+// An OCP float8 e4m3 as it lies in memory (torch.float8_e4m3fn): sign, 4 exponent bits (bias 7), 3 mantissa bits; exponent 0 =
+// subnormal (m x 2^-9), 0x7F / 0xFF = NaN, no infinities.  Every finite code is a float32 number, so widening is exact: the
+// magnitude bits land in the float32 fields with the exponent 120 too low (normals: one multiplication by 2^120, exact) and the
+// subnormals are the integers 0 .. 7 scaled by 2^-9.  Plain arithmetic, so host code (tests) computes the same values; the
+// device scans convert sixteen at a time with v_cvt_pk_f32_fp8 (hdb_scan.hip).
+struct hdb_f8 { unsigned char bits; };
+__host__ __device__ __forceinline__ float hdb_f8_to_f(hdb_f8 v) {
+    const unsigned int b = v.bits, mag = b & 0x7Fu, sgn = (b & 0x80u) << 24;
+    float r;
+    if (mag == 0x7Fu) r = __builtin_bit_cast(float, 0x7FC00000u);
+    else if (mag < 8u) r = (float)mag * 0.001953125f;                                       // 2^-9
+    else r = __builtin_bit_cast(float, mag << 20) * __builtin_bit_cast(float, 0x7B800000u);  // x 2^120
+    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned int, r) | sgn);
 }
 
 // ---- candidate / selection geometry -------------------------------------------------------

@@ -271,6 +271,7 @@ extern "C" int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int
     const ScanArgs& a = *args;
     hipStream_t st = (hipStream_t)stream;
     if (a.mask || a.tile_stride != 1) return (int)hipErrorNotSupported;
+    if (dtype != HDB_F16 && dtype != HDB_F32) return (int)hipErrorNotSupported;      // (bfloat16 / float8 / float64 rows: the 4-query scan)
     const int cus = hdb_cu_count();
     const int rowb = a.d * hdb_elem_bytes(dtype);
     const int R = rowb <= 768 ? 64 : rowb <= 1536 ? 32 : 16;

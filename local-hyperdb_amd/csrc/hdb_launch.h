@@ -89,6 +89,10 @@ int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, con
                               const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_scan_bf16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                    const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_f8(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                            const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_f8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                 const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                            const float* qsq, const float* qscl, int blocks, void* stream);
 int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,

@@ -47,6 +47,7 @@ __global__ __launch_bounds__(64) void hdb_q_to_f16_kernel(const float* Q, int nq
 __device__ __forceinline__ float hdb_row_f(_Float16 v) { return (float)v; }
 __device__ __forceinline__ float hdb_row_f(float v) { return v; }
 __device__ __forceinline__ float hdb_row_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
+__device__ __forceinline__ float hdb_row_f(hdb_f8 v) { return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0); }
 template <typename T, bool HAS_BIAS>
 __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long long* cand, const uint32_t* cnt, uint32_t cap,
                                                                  const T* V, int d, const float* Q, const float* qsq, int q0,
@@ -111,6 +112,11 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
     }
     if (dtype == HDB_F32) return (a.f32_split > 0 && hdb_mfma_f32_split_min_q(a.d) > 0) ? hdb_launch_mfma_scan_f32s(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f)
                                                                                    : hdb_launch_mfma_scan_f32(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f);
+    if (dtype == HDB_F8E4M3) {          // float8 rows (hdb_mfma_f8.h): no LDS ring and 16-row tiles, a wave per tile -- up to four workgroups per CU
+        if (mode == 2) return (int)hipErrorNotSupported;
+        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
+        return hdb_launch_mfma_scan_f8(args, mode, nq_launch, q16, sqnorm, qsq, (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8), stream);
+    }
     if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);
     if (dtype != HDB_F16) return (int)hipErrorNotSupported;
     // (mode 2 promises hdb_mfma_batch_capacity() queries in ONE launch: only the two-tile launcher holds more than 128, whatever the variant)
@@ -135,6 +141,12 @@ extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_
                                          int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
     const dim3 grid(64, nq_launch);
     hipStream_t st = (hipStream_t)stream;
+    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
+    if (dtype == HDB_F8E4M3) {
+        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);
+        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);
+        return (int)hipGetLastError();
+    }
     if (dtype == HDB_F16) {
         if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);
         else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);

@@ -1,0 +1,152 @@
+// hdb_mfma_f8.h -- float8 e4m3 rows (HDB_F8E4M3) on the bf16 matrix pipe: the kernel behind hdb_mfma_f8.hip / hdb_mfma_f8_b.hip.
+//
+// The arithmetic is the bfloat16 flavour's (MfmaShape<16, hdb_bf16>, hdb_mfma_kernel.h): a float32 query travels as three bf16 parts that
+// add up to it exactly (hdb_split3_finite, built once per launch), a row element is ONE bf16 -- a float8 code has four significant
+// bits, so the upper half of its float32 widening is the value itself -- and a k-step of 32 elements is three
+// v_mfma_f32_16x16x32_bf16, v p2 + v p1 + v p0, every product exact, float32 accumulation.  Fragment map, K walk (k-steps in order,
+// smallest part first) and epilogue are that flavour's, so the scores equal those of a bfloat16 index over the widened matrix bit
+// for bit.
+//
+// What differs is how the rows reach the A fragments: CONVERTED PER FRAGMENT IN REGISTERS, and read straight from global memory.
+// Lane (rl = lane & 15, h = lane >> 4) of a wave owns the k slots 32 s + 8 h .. + 7 of row rl of its 16-row tile: eight bytes, one
+// 8-byte load per k-step (the four lanes of a row read 32 contiguous bytes, the wave's D / 32 loads cover whole rows), four
+// v_cvt_pk_f32_fp8 and four v_perm to pack the upper halves.  All D / 32 loads of a tile are issued before the first conversion.
+// There is no LDS ring: a 256-thread workgroup is `wq` query groups of 16 queries x 4 / wq tile lanes, the waves that share a tile
+// issue the same addresses together and meet in L1 / L2.  A one-byte row of 128 or 384 bytes is no multiple of the 256 bytes the
+// ring's XOR swizzle works on, which is why the bfloat16 kernel's staging was not instantiated for it.
+// MODE 0 = store the scores (row sample, exact path), MODE 1 = filter against a.thr into the candidate lists (one returning atomic per
+// survivor: ~2 k survivors per query and pass).  METRIC: 0 dot, 1 cosine (aux0 = 1/||v|| or pearson's row scale), 2 euclidean
+// similarity through ||v||^2 + ||q||^2 - 2 v.q (aux0 = ||v||^2; near-duplicates are re-scored by hdb_rescore_euclid_kernel).
+// Tiles are 16 rows (hdb_mfma_tile_rows): a.ntiles / a.tile_stride count 16-row tiles, as for the VALU scan.
+#pragma once
+#include "hdb_mfma_kernel.h"
+
+__device__ __forceinline__ u32x4 hdb_f8x8_to_bf16x8(const uint2& raw) {
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw.x, true);
+    const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw.y, false), e = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw.y, true);
+    u32x4 o;        // element 2 j in the low half of word j (the order hdb_split3_finite packs the query parts in)
+    o[0] = __builtin_amdgcn_perm(hdb_fbits(a[1]), hdb_fbits(a[0]), 0x07060302u);
+    o[1] = __builtin_amdgcn_perm(hdb_fbits(b[1]), hdb_fbits(b[0]), 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(hdb_fbits(c[1]), hdb_fbits(c[0]), 0x07060302u);
+    o[3] = __builtin_amdgcn_perm(hdb_fbits(e[1]), hdb_fbits(e[0]), 0x07060302u);
+    return o;
+}
+
+template <int D, int MODE, int METRIC, bool HAS_BIAS>
+__global__ __launch_bounds__(256) void hdb_mfma_f8_kernel(ScanArgs a, const float* __restrict__ Qf, const float* __restrict__ aux0,
+                                                          const float* __restrict__ qsq, int nq_end, int wq) {
+    static_assert(D % 32 == 0 && (MODE == 0 || MODE == 1), "whole k-steps; MODE 0 / 1");
+    constexpr int KS = D / 32;
+    constexpr bool FILT = MODE == 1;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int rl = lane & 15, h = lane >> 4;
+    const int qg = w % wq, tl = w / wq, ntl = 4 / wq;
+    const int qw0 = a.q0 + ((int)blockIdx.y * wq + qg) * 16;
+    if (qw0 >= nq_end) return;                       // (wave-uniform; the kernel has no barrier)
+    const int q = qw0 + rl;
+    const bool q_ok = q < nq_end;
+    const int ql = q - a.q0;
+    const int qq = q_ok ? q : nq_end - 1;
+    HdbParts3 Bq[KS];
+    {
+        const float4* qf = reinterpret_cast<const float4*>(Qf + (int64_t)qq * D) + 2 * h;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            float4 x0 = qf[8 * s], x1 = qf[8 * s + 1];
+            if (!q_ok) { x0 = make_float4(0.f, 0.f, 0.f, 0.f); x1 = x0; }
+            Bq[s] = hdb_split3_finite(HdbRaw8{f32x4{x0.x, x0.y, x0.z, x0.w}, f32x4{x1.x, x1.y, x1.z, x1.w}});
+        }
+    }
+    float qinv_l = 1.f, qsq_l = 0.f, thr_cmp = INFINITY;
+    if (q_ok) {
+        if (METRIC == 1) qinv_l = a.qinv[q];
+        if (METRIC == 2) qsq_l = qsq[q];
+        if (FILT) {
+            const float thr = a.thr[ql];
+            if (METRIC != 2 && !HAS_BIAS) { const float tc = thr / qinv_l; thr_cmp = tc - fabsf(tc) * 1e-6f; }
+            else thr_cmp = thr;
+        }
+    }
+    const char* const Vb = reinterpret_cast<const char*>(a.V);
+    const int64_t n_rows = a.n;
+    for (int64_t t = (int64_t)blockIdx.x * ntl + tl; t < a.ntiles; t += (int64_t)gridDim.x * ntl) {
+        const int64_t row0 = hdb_tile_index(t, a.tile_stride) * 16;
+        const int64_t ra = min(row0 + rl, n_rows - 1);                         // (a ragged last tile re-reads the last row)
+        const uint2* src = reinterpret_cast<const uint2*>(Vb + ra * (int64_t)D) + h;
+        uint2 raw[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) raw[s] = src[4 * s];            // (cached: the waves that share the tile find it in L1 / L2)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const u32x4 av = hdb_f8x8_to_bf16x8(raw[s]);
+#define HDB_BF(x) __builtin_bit_cast(hdb_bf16x8, x)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p2), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p0), acc, 0, 0, 0);
+#undef HDB_BF
+        }
+        // epilogue: C register j of lane (rl, h) = row 4 h + j of the tile x query rl -- the bfloat16 flavour's arithmetic, term by term
+        const int64_t rowg = row0 + 4 * h;
+        float x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t rr = min(rowg + j, n_rows - 1);
+            const float aj = METRIC != 0 ? aux0[rr] : 1.f;
+            const float bj = HAS_BIAS ? a.bias[rr] : 0.f;
+            const float dot = acc[j];
+            if (METRIC != 0 || HAS_BIAS || MODE == 0) {
+                if (METRIC == 0) x[j] = HAS_BIAS ? fmaf(dot, qinv_l, bj) : dot * qinv_l;
+                else if (METRIC == 1) {
+                    if (FILT && !HAS_BIAS) x[j] = dot * aj;
+                    else x[j] = HAS_BIAS ? fmaf(dot * aj, qinv_l, bj) : dot * aj * qinv_l;
+                } else {
+                    const float d2 = fmaxf(fmaf(-2.f * qinv_l, dot, aj + qsq_l), 0.f);
+                    x[j] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_sqrtf(d2)) + (HAS_BIAS ? bj : 0.f);
+                }
+            } else x[j] = dot;
+        }
+        if (MODE == 0) {
+            if (q_ok) {
+                float* dst = a.scores + (int64_t)ql * a.ld + (t * 16 + 4 * h);          // sample passes store compactly
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) dst[j] = hdb_canon(x[j]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool hit = x[j] >= thr_cmp && rowg + j < n_rows && !(HAS_BIAS && x[j] == -INFINITY);      // bias -inf = masked row
+                if (hit) {
+                    const float sc = hdb_canon((METRIC != 2 && !HAS_BIAS) ? x[j] * qinv_l : x[j]);
+                    const uint32_t pos = atomicAdd(&a.cnt[ql * HDB_CNT_STRIDE], 1u);
+                    if (pos < a.cap) a.cand[(int64_t)ql * a.cap + pos] = hdb_pack(sc, (uint32_t)(rowg + j));
+                }
+            }
+        }
+    }
+}
+
+template <int D, int MODE>
+static int launch_f8_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+    const int tq = (nq_launch + 15) / 16;
+    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;                              // query groups per workgroup; the other waves take further tiles
+    const dim3 grid(blocks, (tq + wq - 1) / wq);
+    const int nq_end = a.q0 + nq_launch;
+    const bool b = a.bias != nullptr;
+#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
+    if (a.metric == HDB_DOT) { if (b) HDB_F8_GO(0, true, nullptr); else HDB_F8_GO(0, false, nullptr); }
+    else if (a.metric == HDB_COSINE) { if (b) HDB_F8_GO(1, true, a.inv_norm); else HDB_F8_GO(1, false, a.inv_norm); }
+    else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_F8_GO(2, true, sqnorm); else HDB_F8_GO(2, false, sqnorm); }
+    else return (int)hipErrorNotSupported;
+#undef HDB_F8_GO
+    return (int)hipGetLastError();
+}
+template <int D>
+static int launch_f8(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+    if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || a.d != D || a.mask) return (int)hipErrorNotSupported;      // 8-byte fragment loads; a mask arrives folded into the bias
+    if (mode == 0) return launch_f8_metric<D, 0>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    if (mode == 1) return launch_f8_metric<D, 1>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    return (int)hipErrorNotSupported;
+}

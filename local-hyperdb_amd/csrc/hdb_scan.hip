@@ -18,6 +18,7 @@
 template <typename T> struct Elem;
 template <> struct Elem<__half> { using Acc = float;  static constexpr int EPC = 8; };
 template <> struct Elem<hdb_bf16> { using Acc = float; static constexpr int EPC = 8; };
+template <> struct Elem<hdb_f8> { using Acc = float; static constexpr int EPC = 16; };
 template <> struct Elem<float>  { using Acc = float;  static constexpr int EPC = 4; };
 template <> struct Elem<double> { using Acc = double; static constexpr int EPC = 2; };
 
@@ -32,6 +33,17 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[8], hdb_
 #pragma unroll
     for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(w[i] << 16); x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
 }
+// float8 e4m3 (OCP): v_cvt_pk_f32_fp8 widens the two bytes of one half of a word (word select: false = bytes 0-1, true = bytes
+// 2-3), exactly -- element 4 i + b of the chunk is byte b of word i
+__device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[16], hdb_f8*) {
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const int w[4] = {(int)raw.x, (int)raw.y, (int)raw.z, (int)raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+        x[4 * i] = lo[0]; x[4 * i + 1] = lo[1]; x[4 * i + 2] = hi[0]; x[4 * i + 3] = hi[1];
+    }
+}
 __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[4], float*) {
     x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
     x[2] = __uint_as_float(raw.z); x[3] = __uint_as_float(raw.w);
@@ -43,6 +55,7 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, double (&x)[2], dou
 
 __device__ __forceinline__ float hdb_to_f(__half v) { return __half2float(v); }
 __device__ __forceinline__ float hdb_to_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
+__device__ __forceinline__ float hdb_to_f(hdb_f8 v) { return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0); }
 __device__ __forceinline__ float hdb_to_f(float v) { return v; }
 __device__ __forceinline__ double hdb_to_f(double v) { return v; }
 
@@ -118,8 +131,12 @@ __device__ __forceinline__ void hdb_emit(const ScanArgs& a, int q, int64_t row, 
 // (1/||v||, bias) and the row packed into a candidate come from rows[j].  A 16-lane group still reads one row as contiguous
 // 256-byte pieces, the shape that gathers whole rows at the streaming rate.  The dense instantiations compile to what they were.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int QT, int MODE, int ACC, int NJ, bool LIST>
+// NC: compile-time number of chunks of an unrolled variant whose last step is ragged (one-byte elements: a 384-byte row is 24
+// chunks = one full step and one whose upper eight lanes are idle); NC == 16 NJ for every other instantiation, which compiles to
+// what it was.  The chunk order of a row's sum is that of the runtime loop either way.
+template <typename T, int QT, int MODE, int ACC, int NJ, bool LIST, int NC = 16 * NJ>
 __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
+    static_assert(NJ == 0 || (NC > 16 * (NJ - 1) && NC <= 16 * NJ), "NC chunks in NJ steps");
     using Acc = typename Elem<T>::Acc;
     constexpr int EPC = Elem<T>::EPC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -200,10 +217,16 @@ __global__ __launch_bounds__(256) void hdb_scan_kernel(ScanArgs a, int nq_end) {
             for (int j0 = 0; j0 < NJ; j0 += G) {
                 uint4 raw[G][4];
 #pragma unroll
-                for (int j = 0; j < G; ++j) load4(l16 + 16 * (j0 + j), raw[j]);
+                for (int j = 0; j < G; ++j) {
+                    if constexpr (NC == 16 * NJ) load4(l16 + 16 * (j0 + j), raw[j]);
+                    else load4(min(l16 + 16 * (j0 + j), NC - 1), raw[j]);       // (idle lanes of the ragged step re-read the last chunk)
+                }
                 __builtin_amdgcn_sched_barrier(0);       // keep the loads ahead of every use (hipcc otherwise re-serialises them)
 #pragma unroll
-                for (int j = 0; j < G; ++j) fma4(l16 + 16 * (j0 + j), true, raw[j]);
+                for (int j = 0; j < G; ++j) {
+                    if constexpr (NC == 16 * NJ) fma4(l16 + 16 * (j0 + j), true, raw[j]);
+                    else fma4(min(l16 + 16 * (j0 + j), NC - 1), l16 + 16 * (j0 + j) < NC, raw[j]);
+                }
             }
         } else {
             for (int j = 0; j < nj; ++j) {
@@ -303,6 +326,33 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
         const int64_t r0 = t * 16 + 4 * g;
         Acc acc[4] = {Acc(0), Acc(0), Acc(0), Acc(0)};
+        if constexpr (sizeof(T) == 1) {
+            // one-byte elements: a lane takes EIGHT elements per step -- the element order of a 16-byte chunk of 2-byte elements -- so
+            // that the sum of squares, and with it 1/||v||, has the bits a bfloat16 index over the same (exactly widened) values
+            // computes: the matrix-core scores of the two are then equal bit for bit (hdb_mfma_f8.h)
+            if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(V) & 7) == 0) {
+                for (int c = l16; c < d / 8; c += 16) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int64_t r = min(r0 + u, n - 1);
+                        const uint2 raw = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(V) + r * (int64_t)d + (int64_t)c * 8);
+                        float x[16];
+                        hdb_unpack(make_uint4(raw.x, raw.y, 0u, 0u), x, (hdb_f8*)nullptr);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) acc[u] = fma(x[e], x[e], acc[u]);
+                    }
+                }
+            } else {
+                for (int e = l16; e < d; e += 16) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int64_t r = min(r0 + u, n - 1);
+                        const Acc x = (Acc)hdb_to_f(V[r * (int64_t)d + e]);
+                        acc[u] = fma(x, x, acc[u]);
+                    }
+                }
+            }
+        } else
         if (vec) {
             for (int c = l16; c < nchunks; c += 16) {
 #pragma unroll
@@ -532,6 +582,16 @@ static void launch_vec(const ScanArgs& a, int nq_launch, int blocks, hipStream_t
         if (nj == 3) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 3, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
         if (nj == 6) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 6, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
     }
+    // one-byte rows of 256 / 384 / 512 bytes (float8, d = 256 / 384 / 512): a tile is 4-8 KiB, so the one-query kernel is unrolled
+    // over its 16 / 24 / 32 chunks (4-8 loads of 16 bytes per lane ahead of the first use, 88-124 registers) and the grid grows
+    // with the shorter tile (hdb_scan_auto_blocks).  The four-query kernel keeps the runtime loop on that grid: unrolled over two
+    // steps it holds 2 x 4 x 16 widened elements beside 16 sums and takes all 256 registers (one workgroup per CU) against
+    // 116-162 (three to four) for the loop.
+    if constexpr (sizeof(T) == 1 && QT == 1) {
+        if (a.nchunks == 16) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 1, LIST, 16>), grid, dim3(256), lds, st, a, nq_end); return; }
+        if (a.nchunks == 24) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 2, LIST, 24>), grid, dim3(256), lds, st, a, nq_end); return; }
+        if (a.nchunks == 32) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 2, LIST, 32>), grid, dim3(256), lds, st, a, nq_end); return; }
+    }
     hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 0, LIST>), grid, dim3(256), lds, st, a, nq_end);
 }
 
@@ -579,7 +639,7 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
     const bool wide_rows = vec && a.row_bytes == 6 * 256 && nq_launch < 2;      // (the one-query kernel; two or more queries take the four-query one)
     // (several query groups, grid.y > 1: fewer blocks along x -- to cut the flush atomics, one per block and query -- was measured:
     // n = 200k x 100 float32, 16 queries 143 -> 120 us, but 1M rows 418 -> 566 us: the groups drift apart and stop sharing V in L2)
-    const int auto_blocks = wide_rows ? 256 : 512;
+    const int auto_blocks = hdb_scan_auto_blocks(dtype, a.row_bytes, vec, wide_rows);
     const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : auto_blocks);
     // (a.rows: the row-list flavour, a compile-time sibling of every kernel -- the dense ones carry no test for it)
 #define HDB_SCAN_DISPATCH(LIST_)                                                                                                   \
@@ -587,6 +647,8 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
         if (dtype == HDB_F16) { if (mode == 0) launch_scan_t<__half, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<__half, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
         else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
         else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else if (dtype == HDB_F8E4M3) { if (mode == 0) launch_scan_t<hdb_f8, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_f8, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;                                                                \
         else { if (mode == 0) launch_scan_t<double, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
     } while (0)
     if (a.rows) HDB_SCAN_DISPATCH(true); else HDB_SCAN_DISPATCH(false);
@@ -620,6 +682,8 @@ extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, fl
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rownorm_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rownorm_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, inv_norm, sqnorm, nan_flag);
+    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, inv_norm, sqnorm, nan_flag);
+    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_rownorm_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, inv_norm, sqnorm, nan_flag);
     return (int)hipGetLastError();
 }
@@ -643,6 +707,8 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
         if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
         else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_wide_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
         else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
+        else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
+        else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
         else hipLaunchKernelGGL(hdb_signpack_wide_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
         return (int)hipGetLastError();
     }
@@ -650,6 +716,8 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
+    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
+    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_signpack_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
     return (int)hipGetLastError();
 }
@@ -781,6 +849,8 @@ extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, f
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rowstats_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, pscale);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rowstats_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, pscale);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, pscale);
+    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, pscale);
+    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_rowstats_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, pscale);
     return (int)hipGetLastError();
 }

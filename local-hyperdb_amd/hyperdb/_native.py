@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HYPERDB_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libhyperdb_hip.so")
 
 HDB_F16, HDB_F32, HDB_F64, HDB_BF16 = 0, 1, 2, 3
+HDB_F8E4M3 = 5                          # OCP float8 e4m3 (torch.float8_e4m3fn); 4 is unassigned and refused by the library
 METRIC_IDS = {
     "dot_product": 0,
     "cosine_similarity": 1,
@@ -125,7 +126,28 @@ def require_gpu():
 
 _NP2HDB = {np.dtype(np.float16): HDB_F16, np.dtype(np.float32): HDB_F32, np.dtype(np.float64): HDB_F64}
 # (numpy has no bfloat16: a bf16 matrix arrives as a torch tensor and leaves as its exact float32 widening)
-_TORCH2HDB = {torch.float16: HDB_F16, torch.float32: HDB_F32, torch.float64: HDB_F64, torch.bfloat16: HDB_BF16}
+# (... nor float8: an e4m3 matrix arrives as a torch.float8_e4m3fn tensor, one byte per element, and leaves the same way)
+_F8 = torch.float8_e4m3fn
+_TORCH2HDB = {torch.float16: HDB_F16, torch.float32: HDB_F32, torch.float64: HDB_F64, torch.bfloat16: HDB_BF16, _F8: HDB_F8E4M3}
+F8_MAX = 448.0                          # largest finite e4m3 magnitude
+
+
+def _as_bytes(t):
+    """A float8 tensor as its uint8 view (same storage): copies, indexing and allocation of one-byte rows go through uint8, for
+    which every torch build has device kernels; any other tensor as it is."""
+    return t.view(torch.uint8) if t.dtype == _F8 else t
+
+
+def to_f8(data):
+    """Float data -> host torch.float8_e4m3fn tensor with torch's own conversion: round to nearest even, magnitudes up to 464
+    round to 448 and anything beyond becomes NaN (torch does not saturate).  Done on the host, before upload."""
+    if isinstance(data, torch.Tensor):
+        if data.dtype == _F8:
+            return data                                 # already float8, wherever it lives
+        t = data.detach().cpu()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(data)))
+    return t.to(torch.float32).to(_F8)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)      # the current stream's handle without building a Stream object (0.3 vs 1.5 us)
@@ -145,11 +167,13 @@ def to_device_matrix(vectors, device):
     """numpy / list / torch -> C-contiguous 2-D torch tensor on `device` in a supported dtype.
 
     Dtype policy mirrors HyperDB.fp_precision (hyperdb.py:65-66): float16/32/64 stay as they are (and so does a
-    torch.bfloat16 tensor: 2 bytes per element on the device), anything else numeric (ints, bools) is widened to float64 like numpy would promote it."""
+    torch.bfloat16 tensor: 2 bytes per element on the device; and a torch.float8_e4m3fn tensor: 1 byte), anything else numeric (ints, bools) is widened to float64 like numpy would promote it."""
     if isinstance(vectors, torch.Tensor):
         t = vectors
         if t.dtype not in _TORCH2HDB:
             t = t.to(torch.float64)
+        if t.dtype == _F8:                  # the bytes travel as uint8
+            return t.contiguous().view(torch.uint8).to(device).view(_F8)
         return t.to(device).contiguous()
     arr = np.asarray(vectors)
     if arr.dtype not in _NP2HDB:
@@ -217,6 +241,8 @@ class GpuIndex:
     def append(self, rows):
         """Append rows behind the stored ones (HyperDB.add): amortised O(new rows).  The device allocation grows
         by doubling; the library re-points (hdb_index_rebase) and extends its row caches (hdb_index_extend)."""
+        if self.dtype == HDB_F8E4M3:
+            rows = to_f8(rows)                              # float data into a float8 index: torch's conversion, on the host
         t = to_device_matrix(rows, self.device)
         if t.dim() == 1:
             t = t.reshape(1, -1)
@@ -233,11 +259,11 @@ class GpuIndex:
         cap = int(buf.shape[0])
         if self.n + m > cap:
             new_cap = max(self.n + m, 2 * cap, 1024)
-            nbuf = torch.empty((new_cap, self.d), dtype=self.V.dtype, device=self.device)
-            nbuf[:self.n].copy_(self.V)
+            nbuf = torch.empty((new_cap, self.d), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
+            _as_bytes(nbuf)[:self.n].copy_(_as_bytes(self.V))
             buf = nbuf
             _check(_lib.hdb_index_rebase(self._h, ctypes.c_void_p(buf.data_ptr())), "hdb_index_rebase")
-        buf[self.n:self.n + m].copy_(t)
+        _as_bytes(buf)[self.n:self.n + m].copy_(_as_bytes(t))
         self._buf = buf
         self.n += m
         self.V = buf[:self.n]
@@ -248,6 +274,8 @@ class GpuIndex:
 
     def update(self, vectors):
         """Point the handle at a new matrix (after add/remove) and rebuild the row caches."""
+        if self.dtype == HDB_F8E4M3:
+            vectors = to_f8(vectors)                        # ... into a float8 index: torch's conversion, on the host, as append does
         t = to_device_matrix(vectors, self.device)
         if self.dtype == HDB_BF16 and t.dtype != torch.bfloat16:
             t = t.to(torch.bfloat16)                        # float data into a bf16 index: round to nearest even, as append does
@@ -292,9 +320,11 @@ class GpuIndex:
 
     def host_matrix(self):
         """The stored rows as a host array (one D2H copy; the resident copy stays the only one kept).  A bfloat16 index returns
-        the exact float32 widening (numpy has no bfloat16)."""
+        the exact float32 widening (numpy has no bfloat16), and so does a float8 index (widened on the host)."""
         if self.V.dtype == torch.bfloat16:
             return self.V.float().cpu().numpy()
+        if self.V.dtype == _F8:
+            return self.V.view(torch.uint8).cpu().view(_F8).float().numpy()
         return self.V.cpu().numpy()
 
     def compact(self, keep_rows):
@@ -303,7 +333,7 @@ class GpuIndex:
         (hyperdb.py:691-766) without a host round trip or a cache rebuild."""
         rows = torch.from_numpy(np.ascontiguousarray(np.asarray(keep_rows, dtype=np.int64))).to(self.device)
         m = int(rows.numel())
-        out = torch.empty((max(m, 1), self.d), dtype=self.V.dtype, device=self.device)
+        out = torch.empty((max(m, 1), self.d), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
         _check(_lib.hdb_index_gather(self._h, ctypes.c_void_p(rows.data_ptr()), m, ctypes.c_void_p(out.data_ptr()),
                                      _stream_ptr(self.device)), "hdb_index_gather")
         self._buf = out

@@ -66,14 +66,16 @@ class HyperDB:
     def __init__(self, documents=None, vectors=None, select_keys=None, embedding_function=None, fp_precision="float32",
                  add_timestamp=False, metadata_keys=None, ann_metric="cosine", n_trees=10, cache_size=256, device=None,
                  devices=None, quantize=None):
-        # ("bfloat16" is this build's addition: host arrays stay float32, the resident matrix is torch.bfloat16)
-        if fp_precision not in ["float16", "float32", "float64", "bfloat16"]:
+        # ("bfloat16" and "float8_e4m3fn" are this build's additions: host arrays stay float32, the resident matrix is
+        #  torch.bfloat16 / torch.float8_e4m3fn)
+        if fp_precision not in ["float16", "float32", "float64", "bfloat16", "float8_e4m3fn"]:
             raise ValueError("Unsupported floating-point precision.")                       # hyperdb.py:65-66
         accepted = ["angular", "euclidean", "manhattan", "hamming", "dot", "cosine"]
         if ann_metric not in accepted:
             raise ValueError(f"Unsupported ANN metric. Accepted values are: {', '.join(accepted)}")  # :69-71
         self.bf16 = fp_precision == "bfloat16"
-        self.fp_precision = np.float32 if self.bf16 else getattr(np, fp_precision)
+        self.f8 = fp_precision == "float8_e4m3fn"
+        self.fp_precision = np.float32 if (self.bf16 or self.f8) else getattr(np, fp_precision)
         self.embedding_function = embedding_function
         self.select_keys = [select_keys] if isinstance(select_keys, str) else select_keys
         self.metadata_keys = [metadata_keys] if isinstance(metadata_keys, str) else (metadata_keys or [])
@@ -128,6 +130,13 @@ class HyperDB:
         if self._index is not None and vectors.shape[1] != self._index.d:
             raise ValueError("All vectors must have the same dimension, one per document.")
         vectors = vectors.astype(self.fp_precision, copy=False)
+        if self.f8:
+            # torch's float8 conversion does not saturate: a finite value beyond the format's range would be stored as NaN, and a NaN
+            # row makes every later query raise -- refuse it here, where the caller can still act
+            big = np.abs(np.where(np.isfinite(vectors), vectors, 0))
+            if big.size and float(big.max()) > _native.F8_MAX:
+                raise ValueError(f"float8_e4m3fn holds magnitudes up to {_native.F8_MAX:g}; got {float(big.max()):g}. "
+                                 "Scale the embeddings down before adding them (cosine and pearson rankings do not depend on the scale).")
         if add_timestamp:                                   # hyperdb.py:582-588: dict documents get metadata.timestamp
             now = float(datetime.datetime.now().timestamp())
             for doc in documents:
@@ -140,6 +149,8 @@ class HyperDB:
         if self._index is None:
             if self.bf16:                             # round to nearest even at upload; later appends convert the same way (GpuIndex.append)
                 vectors = torch.from_numpy(np.ascontiguousarray(vectors)).to(torch.bfloat16)
+            if self.f8:                               # torch's conversion on the host (round to nearest even); appends convert the same way
+                vectors = _native.to_f8(vectors)
             self._index = GpuGroup(vectors, self.devices) if self.devices else GpuIndex(vectors, device=self.device)
             if self.quantize is not None:             # (append / compact / update keep the shadow current from here on)
                 self._index.quantize(self.quantize)
@@ -257,7 +268,13 @@ class HyperDB:
         rows = np.asarray(rows, dtype=np.int64)
         for sh, lo, hi in self._shards():
             mine = rows[(rows >= lo) & (rows < hi)] - lo
-            if mine.size and bool(torch.isnan(sh.V[torch.from_numpy(mine).to(sh.device)]).any().item()):
+            if not mine.size:
+                continue
+            rows_d = torch.from_numpy(mine).to(sh.device)
+            if sh.V.dtype == torch.float8_e4m3fn:            # the two NaN codes, 0x7F and 0xFF, looked for in the bytes
+                if bool(((sh.V.view(torch.uint8)[rows_d] & 0x7F) == 0x7F).any().item()):
+                    return True
+            elif bool(torch.isnan(sh.V[rows_d]).any().item()):
                 return True
         return False
 

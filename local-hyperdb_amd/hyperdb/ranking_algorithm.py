@@ -71,7 +71,9 @@ def register_vectors(vectors, device=None, devices=None, quantize=None):
 
 
 # (bfloat16 has no numpy dtype: score vectors of a bf16 matrix come back as float32, the type its values widen to exactly)
-_TORCH2NP = {torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64, torch.bfloat16: np.float32}
+# (float8 e4m3 likewise)
+_TORCH2NP = {torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64, torch.bfloat16: np.float32,
+             torch.float8_e4m3fn: np.float32}
 
 
 def _np_dtype_of(dt, index):
