@@ -295,10 +295,20 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     per k-step, every product exact, float32 accumulation, the bfloat16 flavour's K walk and epilogue -- the scores are those of
  *     a bfloat16 index over the widened matrix bit for bit.  A query element that is not finite keeps its first part only (status
  *     words stay 0).  A matrix holding a NaN code stays on the VALU scan.  Other widths stay on the VALU scan.
+ *   - on request (option f8_ks_min_q, 0 = never by default): the same calls on wider rows -- d = 640, 768, 896, 1024, 1152, 1280,
+ *     1408, 1536, 2048, 3072 or 4096 -- take the matrix cores through K slices (hdb_mfma_f8_ks.hip), multi-kernel pipeline.  The
+ *     slice list is bfloat16's (the fewest slices of 512 / 384 / 256 elements, the widest first), one launch per slice and pass, at
+ *     most 128 queries per chunk, partial sums in a [query][rows] float32 workspace (+8 bytes per row, query and extra slice); rows
+ *     are still converted per fragment in registers.  Same K walk, same epilogue: the scores are those of a bfloat16 index over the
+ *     widened matrix going through ITS K slices, bit for bit.  f8_ks_min_q = n >= 1: from max(n, 5, mfma_min_q) queries on; -1: from
+ *     hdb_mfma_f8_ks_min_q(d) queries on (hdb_caps.h).  A matrix holding a NaN code, manhattan batches, matrices of up to 8192 rows
+ *     and row-list calls stay on the VALU scan; k > 2048 is the full sort as for every dtype.  Off by default: the default dispatch
+ *     of float8 rows beyond 512 elements is pinned as "VALU scan" (tests/f8_plan_check.hip), and every 16 queries of a batch convert
+ *     a tile's fragments again, so large batches lose to a bfloat16 index -- turning a measured rule on is a change of its own.
  *   - a matrix holding a NaN code raises the NaN flag (hdb_index_has_nan) like a NaN of any other dtype.
  *   - never: the single launches of the matrix-core paths (fused = 0 always), the LDS tile kernel of manhattan batches, the int8 shadow
  *     and its 5-bit plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED, auto_quant does not apply: one byte per element already
- *     is the shadow's stream), K slices for wider rows.
+ *     is the shadow's stream); K slices for wider rows unless f8_ks_min_q asks for them.
  * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch). */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
@@ -383,7 +393,9 @@ void hdb_group_destroy(hdb_group* g);
  *   dyn_tiles (0: the batched MFMA filter pass always splits its tiles statically; default 1 = tiles from a counter for
  *   long passes over rows of >= 768 bytes with up to 64 queries).
  *   Dispatch of few-query calls (-1 = the measured rule): fused_max_q (the 1-4-query single launch takes
- *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bits_max_q
+ *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bf16_ks_min_q
+ *   (bfloat16 rows wider than 512 elements: K slices from this many queries on, never fewer than 5), f8_ks_min_q (float8 rows wider
+ *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),

@@ -529,6 +529,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "f32_split")) ix->opt.f32_split = value;
     else if (!strcmp(name, "f32_split_min_q")) ix->opt.f32_split_min_q = value;
     else if (!strcmp(name, "bf16_ks_min_q")) ix->opt.bf16_ks_min_q = value;
+    else if (!strcmp(name, "f8_ks_min_q")) ix->opt.f8_ks_min_q = value < 0 ? -1 : value;
     else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
     else if (!strcmp(name, "use_quant")) ix->opt.use_quant = value;
     else if (!strcmp(name, "quant_min_n")) ix->opt.quant_min_n = value;

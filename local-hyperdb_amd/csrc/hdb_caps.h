@@ -85,6 +85,26 @@ static inline KsGeom ks_geom(int dtype, int d) {
     return ks_list(1, 0, 0);
 }
 static inline int hdb_mfma_ksplit_slices(int dtype, int d) { return ks_geom(dtype, d).slices; }
+// float8 e4m3 (hdb_mfma_f8_ks.hip): OPT-IN slices (the planner's f8_ks_min_q, 0 = never by default), so they are no part of
+// ks_geom / hdb_mfma_ksplit_slices / hdb_mfma_tile_rows / hdb_mfma_supported, which describe the default dispatch.  The query
+// fragments are bfloat16's (three bf16 parts, 3/8 of a register per element), so the widths and the slices of a width are
+// ks_geom_bf16's; an element is one byte, so off[s] is the byte offset into the stored row and the element offset into the query.
+static inline KsGeom ks_geom_f8(int d) {
+    const KsGeom b = ks_geom_bf16(d);
+    KsGeom g = {};
+    g.slices = b.slices;
+    for (int s = 0; s < b.slices && s < HDB_KS_MAX_SLICES; ++s) { g.width[s] = b.width[s]; g.off[s] = b.off[s] / 2; }
+    return g;
+}
+static inline int hdb_mfma_f8_ks_slices(int d) { return ks_geom_f8(d).slices; }
+// ... and the number of queries of a call from which the float8 slices are used when f8_ks_min_q = -1.  Measured, one box, the
+// contenders alternating call by call, cosine top-100, p50 in us, slices vs VALU scan at 5 / 8 / 16 queries on ~1.5 GB of rows, the
+// two p50s of the repeated slice contender at most 1.9 % apart (tools/time_f8_wide.py -> profiles/f8_wide_time.txt):
+//   768: 483 vs 1149, 501 vs 1187, 526 vs 2251    1024: 513 vs 1160, 517 vs 1181, 535 vs 2242
+//  1536: 553 vs 1177, 560 vs 1186, 580 vs 2238    4096: 732 vs 1239, 750 vs 1956, 771 vs 3815
+// The slices win 1.7-2.4x at 5 queries at every measured width (two VALU passes of one-byte rows run at ~2.7 TB/s, far from HBM
+// speed), so the rule is 5, the first batch size the matrix cores are offered; the widths between were not measured.
+static inline int hdb_mfma_f8_ks_min_q(int d) { (void)d; return 5; }
 
 // ---- hdb_mfma_bf16.hip ----
 // rows per LDS stage (hdb_mfma_tile_rows): the query fragments of 16 queries take 3 d / 8 registers, so the wider the row the fewer

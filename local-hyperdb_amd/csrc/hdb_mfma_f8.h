@@ -18,6 +18,12 @@
 // survivor: ~2 k survivors per query and pass).  METRIC: 0 dot, 1 cosine (aux0 = 1/||v|| or pearson's row scale), 2 euclidean
 // similarity through ||v||^2 + ||q||^2 - 2 v.q (aux0 = ||v||^2; near-duplicates are re-scored by hdb_rescore_euclid_kernel).
 // Tiles are 16 rows (hdb_mfma_tile_rows): a.ntiles / a.tile_stride count 16-row tiles, as for the VALU scan.
+// KSL: the launch covers ONE K slice of D elements of rows that are wider (hdb_mfma_ksplit.hip, ks_geom_f8; opt-in, f8_ks_min_q): rows
+// at pitch a.ks_pitch from byte a.ks_off, the query at pitch a.ks_dfull from element a.ks_off (one byte per element: the same number),
+// accumulators started from a.ks_partial_in (nullptr = zero) and, MODE 3, stored raw to a.ks_partial_out for the next slice; the last
+// slice runs the epilogue, MODE 0 / 1.  The sums are indexed like MODE 0's scores -- [query][compact tile sequence x 16 + row], pitch
+// a.ks_ld -- which is the bfloat16 slice kernel's layout (hdb_mfma_kernel.h); a lane reads the four elements it later writes, so the
+// two buffers and MODE 0's scores may alias.  With ks_geom_bf16's slice list the K walk is that kernel's, partial sum by partial sum.
 #pragma once
 #include "hdb_mfma_kernel.h"
 
@@ -33,10 +39,13 @@ __device__ __forceinline__ u32x4 hdb_f8x8_to_bf16x8(const uint2& raw) {
     return o;
 }
 
-template <int D, int MODE, int METRIC, bool HAS_BIAS>
-__global__ __launch_bounds__(256) void hdb_mfma_f8_kernel(ScanArgs a, const float* __restrict__ Qf, const float* __restrict__ aux0,
+// (the filter flavour of a 512-element slice holds 192 registers of query parts, 32 of raw row bytes, the partial sums and the slice
+//  addressing: left alone it takes 254-256 VGPRs plus 4 AGPRs for the accumulator -- 264 allocated, one wave per SIMD.  Asked for two
+//  workgroups per CU it keeps the accumulator in the 256 VGPRs, without scratch: two waves per SIMD like the other 512-element kernels)
+template <int D, int MODE, int METRIC, bool HAS_BIAS, bool KSL = false>
+__global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void hdb_mfma_f8_kernel(ScanArgs a, const float* __restrict__ Qf, const float* __restrict__ aux0,
                                                           const float* __restrict__ qsq, int nq_end, int wq) {
-    static_assert(D % 32 == 0 && (MODE == 0 || MODE == 1), "whole k-steps; MODE 0 / 1");
+    static_assert(D % 32 == 0 && (MODE == 0 || MODE == 1 || (KSL && MODE == 3 && METRIC == 0 && !HAS_BIAS)), "whole k-steps; MODE 0 / 1, a K slice also 3");
     constexpr int KS = D / 32;
     constexpr bool FILT = MODE == 1;
     const int lane = threadIdx.x & 63;
@@ -51,7 +60,7 @@ __global__ __launch_bounds__(256) void hdb_mfma_f8_kernel(ScanArgs a, const floa
     const int qq = q_ok ? q : nq_end - 1;
     HdbParts3 Bq[KS];
     {
-        const float4* qf = reinterpret_cast<const float4*>(Qf + (int64_t)qq * D) + 2 * h;
+        const float4* qf = reinterpret_cast<const float4*>(KSL ? Qf + (int64_t)qq * a.ks_dfull + a.ks_off : Qf + (int64_t)qq * D) + 2 * h;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             float4 x0 = qf[8 * s], x1 = qf[8 * s + 1];
@@ -71,14 +80,28 @@ __global__ __launch_bounds__(256) void hdb_mfma_f8_kernel(ScanArgs a, const floa
     }
     const char* const Vb = reinterpret_cast<const char*>(a.V);
     const int64_t n_rows = a.n;
+    const int64_t pitch = KSL ? a.ks_pitch : (int64_t)D;
     for (int64_t t = (int64_t)blockIdx.x * ntl + tl; t < a.ntiles; t += (int64_t)gridDim.x * ntl) {
         const int64_t row0 = hdb_tile_index(t, a.tile_stride) * 16;
         const int64_t ra = min(row0 + rl, n_rows - 1);                         // (a ragged last tile re-reads the last row)
-        const uint2* src = reinterpret_cast<const uint2*>(Vb + ra * (int64_t)D) + h;
+        const uint2* src = reinterpret_cast<const uint2*>(Vb + ra * pitch + (KSL ? a.ks_off : 0)) + h;
         uint2 raw[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) raw[s] = src[4 * s];            // (cached: the waves that share the tile find it in L1 / L2)
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int64_t rowg = row0 + 4 * h;
+        // C register j of lane (rl, h) = row 4 h + j of the tile x query rl; a K slice keeps it at [query][t * 16 + 4 h + j]
+        const int64_t ks_at = KSL ? (int64_t)(q_ok ? ql : 0) * a.ks_ld + (t * 16 + 4 * h) : 0;
+        if constexpr (KSL) {
+            if (a.ks_partial_in && q_ok) {           // the sums of the slices before this one
+                const float* pin = a.ks_partial_in + ks_at;
+                if (rowg + 3 < n_rows) { const float4 pv = *reinterpret_cast<const float4*>(pin); acc[0] = pv.x; acc[1] = pv.y; acc[2] = pv.z; acc[3] = pv.w; }
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) acc[j] = pin[j];
+                }
+            }
+        }
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             const u32x4 av = hdb_f8x8_to_bf16x8(raw[s]);
@@ -88,8 +111,18 @@ __global__ __launch_bounds__(256) void hdb_mfma_f8_kernel(ScanArgs a, const floa
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p0), acc, 0, 0, 0);
 #undef HDB_BF
         }
-        // epilogue: C register j of lane (rl, h) = row 4 h + j of the tile x query rl -- the bfloat16 flavour's arithmetic, term by term
-        const int64_t rowg = row0 + 4 * h;
+        if constexpr (MODE == 3) {                   // raw partial sums for the next K slice
+            if (q_ok) {
+                float* pout = a.ks_partial_out + ks_at;
+                if (rowg + 3 < n_rows) *reinterpret_cast<float4*>(pout) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) pout[j] = acc[j];
+                }
+            }
+            continue;
+        }
+        // epilogue: the bfloat16 flavour's arithmetic, term by term
         float x[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -148,5 +181,36 @@ static int launch_f8(const ScanArgs& a, int mode, const void* q, const float* sq
     if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || a.d != D || a.mask) return (int)hipErrorNotSupported;      // 8-byte fragment loads; a mask arrives folded into the bias
     if (mode == 0) return launch_f8_metric<D, 0>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
     if (mode == 1) return launch_f8_metric<D, 1>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    return (int)hipErrorNotSupported;
+}
+
+// One K slice of a wide float8 row (hdb_mfma_ksplit.hip): mode 3 = raw partial sums out, 0 / 1 = the last slice with the metric's epilogue
+template <int D, int MODE>
+static int launch_f8_kslice_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+    const int tq = (nq_launch + 15) / 16;
+    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;
+    const dim3 grid(blocks, (tq + wq - 1) / wq);
+    const int nq_end = a.q0 + nq_launch;
+    const bool b = a.bias != nullptr;
+#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_, true>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
+    if constexpr (MODE == 3) HDB_F8_GO(0, false, nullptr);
+    else {
+        if (a.metric == HDB_DOT) { if (b) HDB_F8_GO(0, true, nullptr); else HDB_F8_GO(0, false, nullptr); }
+        else if (a.metric == HDB_COSINE) { if (b) HDB_F8_GO(1, true, a.inv_norm); else HDB_F8_GO(1, false, a.inv_norm); }
+        else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_F8_GO(2, true, sqnorm); else HDB_F8_GO(2, false, sqnorm); }
+        else return (int)hipErrorNotSupported;
+    }
+#undef HDB_F8_GO
+    return (int)hipGetLastError();
+}
+template <int D>
+static int launch_f8_kslice(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+    // 8-byte fragment loads: base, pitch and slice offset; float4 query and partial-sum accesses; the slice lies inside the row
+    if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || (a.ks_pitch & 7) != 0 || (a.ks_off & 7) != 0 || a.ks_off < 0 || a.ks_off + D > a.ks_pitch ||
+        a.ks_dfull != a.ks_pitch || (a.ks_ld & 3) != 0 || a.mask) return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
+    if (mode == 3) return launch_f8_kslice_metric<D, 3>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    if (mode == 0) return launch_f8_kslice_metric<D, 0>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    if (mode == 1) return launch_f8_kslice_metric<D, 1>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
     return (int)hipErrorNotSupported;
 }

@@ -26,6 +26,7 @@ struct hdb_options {
     int64_t f32_split = 1;            // ... as bf16 parts (hdb_mfma_f32s.hip) where that flavour exists, the matrix is finite and the call has at least
     int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
+    int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
     int64_t host_direct = 1;          // hdb_topk_host: kernels write a pinned host record themselves (no D2H copy)
     int64_t dyn_tiles = 1;            // MFMA filter pass: hand tiles out from a counter (0: static split)
@@ -323,8 +324,13 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // float32 (VALU flavour, two queries): the single launch wins at every size.
     const int64_t fused_max_q = o.fused_max_q >= 0 ? o.fused_max_q
                               : ix.dtype == HDB_F32 ? HDB_FUSED_MAXQ_RULE : (n >= 1500000 ? 3 : 1);
-    bool mfma = o.use_mfma && !is_ham && !small && nq >= min_q &&
-                hdb_mfma_supported(ix.dtype, ix.d, is_pearson ? (int)HDB_COSINE : metric);
+    // (float8 rows wider than 512 elements reach the matrix cores through K slices on request only, f8_ks_min_q != 0: the caps above
+    //  answer for the default dispatch, where such rows keep the VALU scan, so the slices have a rule of their own here)
+    const int64_t f8_ks_first = (ix.dtype == HDB_F8E4M3 && o.f8_ks_min_q != 0 && hdb_mfma_f8_ks_slices(ix.d) > 0)
+                                    ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), o.f8_ks_min_q > 0 ? o.f8_ks_min_q : (int64_t)hdb_mfma_f8_ks_min_q(ix.d)) : 0;
+    const int metric_mm = is_pearson ? (int)HDB_COSINE : metric;
+    const bool f8ks_call = f8_ks_first > 0 && nq >= f8_ks_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
+    bool mfma = o.use_mfma && !is_ham && !small && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call);
     // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
@@ -332,6 +338,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call (build_needed); an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
+    const bool f8ks = mfma && f8ks_call;
     const bool auto_q = auto_quant_call(ix, o, c, mfma, exact, small);
     if (auto_q && nq >= 1 && nq <= 4 &&
         // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
@@ -367,7 +374,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
                              // fp16 d = 1024 (32-KiB tiles, 32 k-steps in one wave): 189 vs 195 us at 0.5 M rows, 619 vs 627 at 2 M,
                              // but 1 491 vs 1 466 at 5 M -- the single launch up to 4 M rows
                              !(ix.dtype == HDB_F16 && ix.d == 1024 && n > 4000000);
-    const int tile_rows = (mfma || fused_shape) ? hdb_mfma_tile_rows(ix.dtype, ix.d) : 16;
+    const int tile_rows = f8ks ? 16 : (mfma || fused_shape) ? hdb_mfma_tile_rows(ix.dtype, ix.d) : 16;      // (float8 slices: the 16-row tiles of every float8 kernel)
     // float32 rows on the matrix cores multiply in three bf16 parts (hdb_mfma_f32s.hip: 2.7x the rate of the float32 MFMAs, same
     // 1e-5 contract) -- on finite matrices: the parts of an infinite element would cancel to NaN where np.dot keeps the infinity
     bool f32s = false;
@@ -389,7 +396,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     int cq_max = batch1 ? bcap : 256;
     if (exact && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(256, o.exact_bytes / (ld_n * 4)));
     // wide rows on the matrix cores go through K slices with a [query][rows] buffer of partial sums (hdb_mfma_ksplit.hip)
-    const bool ksplit = mfma && hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0;
+    const bool ksplit = mfma && (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || f8ks);
     if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), o.exact_bytes / (ld_n * 4)));
     cq_max = std::min(cq_max, (int)nq);
     const bool fused = fused_shape && !full_sort && (m == 8 || local_ok);           // (no prep kernel either)
