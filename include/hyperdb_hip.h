@@ -305,11 +305,19 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     and row-list calls stay on the VALU scan; k > 2048 is the full sort as for every dtype.  Off by default: the default dispatch
  *     of float8 rows beyond 512 elements is pinned as "VALU scan" (tests/f8_plan_check.hip), and every 16 queries of a batch convert
  *     a tile's fragments again, so large batches lose to a bfloat16 index -- turning a measured rule on is a change of its own.
+ *   - on request (option f8_lds_min_q, 0 = never by default): every matrix-core launch of such a call -- whole rows of 128 .. 512
+ *     elements or, under f8_ks_min_q, the K slices; sample, filter and exact pass -- expands its rows to bf16 in LDS once per workgroup
+ *     of 4 waves (launches of more than 64 queries: 8; f8_lds_waves fixes it) instead of once per wave (hdb_mfma_f8_lds.h): a stage of rows is loaded with 16-byte loads,
+ *     converted and stored to a swizzled, double-buffered image that every wave reads its fragments from.  Same query parts, K walk
+ *     and epilogue, same plan otherwise: indices, score bits and status words are those of the call with the option off.
+ *     f8_lds_min_q = n >= 1: from max(n, 5, mfma_min_q) queries on; -1: from hdb_mfma_f8_lds_min_q(d) queries on (hdb_caps.h: 32 at
+ *     d = 384 / 768, 64 at d = 128 / 256 / 512 / 4096, 0 = never at the widths not measured; profiles/f8_lds_time.txt).  Whatever stays off the float8 matrix cores stays off this flavour.
  *   - a matrix holding a NaN code raises the NaN flag (hdb_index_has_nan) like a NaN of any other dtype.
  *   - never: the single launches of the matrix-core paths (fused = 0 always), the LDS tile kernel of manhattan batches, the int8 shadow
  *     and its 5-bit plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED, auto_quant does not apply: one byte per element already
  *     is the shadow's stream); K slices for wider rows unless f8_ks_min_q asks for them.
- * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch). */
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch); f8_lds = 1 when the last call's
+ * matrix-core launches expanded the rows in LDS; f8_lds_min_q = the threshold in force for this index, 0 = never. */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 
@@ -395,7 +403,9 @@ void hdb_group_destroy(hdb_group* g);
  *   Dispatch of few-query calls (-1 = the measured rule): fused_max_q (the 1-4-query single launch takes
  *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bf16_ks_min_q
  *   (bfloat16 rows wider than 512 elements: K slices from this many queries on, never fewer than 5), f8_ks_min_q (float8 rows wider
- *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), bits_max_q
+ *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), f8_lds_min_q
+ *   (float8 batches with the rows expanded to bf16 in LDS once per workgroup: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q)
+ *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),

@@ -530,6 +530,8 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "f32_split_min_q")) ix->opt.f32_split_min_q = value;
     else if (!strcmp(name, "bf16_ks_min_q")) ix->opt.bf16_ks_min_q = value;
     else if (!strcmp(name, "f8_ks_min_q")) ix->opt.f8_ks_min_q = value < 0 ? -1 : value;
+    else if (!strcmp(name, "f8_lds_min_q")) ix->opt.f8_lds_min_q = value < 0 ? -1 : value;
+    else if (!strcmp(name, "f8_lds_waves")) { if (value == 0 || value == 4 || value == 8) ix->opt.f8_lds_waves = value; }
     else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
     else if (!strcmp(name, "use_quant")) ix->opt.use_quant = value;
     else if (!strcmp(name, "quant_min_n")) ix->opt.quant_min_n = value;
@@ -557,6 +559,8 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "chunks")) *value = ix->st.chunks;
     else if (!strcmp(name, "mfma")) *value = ix->st.mfma;
     else if (!strcmp(name, "f32_split")) *value = ix->st.f32s;
+    else if (!strcmp(name, "f8_lds")) *value = ix->st.f8_lds;
+    else if (!strcmp(name, "f8_lds_min_q")) *value = f8_lds_first_q(ix->opt, ix->dtype, ix->d);      // the threshold in force for this index, 0 = never
     else if (!strcmp(name, "host_direct")) *value = ix->st_host_direct;
     else if (!strcmp(name, "fused")) *value = ix->st.fused;
     else if (!strcmp(name, "local")) *value = ix->st.local;
@@ -1153,6 +1157,7 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         ScanArgs a; base_args(ix, a, Qeff, metric_eff);
         if (is_pearson) a.inv_norm = ix->pscale;
         a.q0 = q0; a.bias = bias_eff; a.mask = mask_eff; a.f32_split = f32s ? 1 : 0;
+        a.f8_lds = !p.f8_lds ? 0 : ix->opt.f8_lds_waves ? (int)ix->opt.f8_lds_waves : hdb_mfma_f8_lds_auto_waves(cq);
         a.thr = thr; a.cnt = cnt; a.cand = cand;
         a.ntiles = (n + tile_rows - 1) / tile_rows;
         if (p.subset) { a.rows = ix->rows; a.m = ix->subset_m; a.mask = nullptr; a.bias = ix->bias; }

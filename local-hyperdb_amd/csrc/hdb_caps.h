@@ -117,6 +117,54 @@ static inline int hdb_mfma_bf16_tile_rows(int d) { return (d == 128 || d == 256)
 // is the VALU scan's 16 rows at every width
 static inline int hdb_mfma_f8_tile_rows(int d) { return (d == 128 || d == 256 || d == 384 || d == 512) ? 16 : 0; }
 
+// ---- hdb_mfma_f8_lds*.hip: float8 rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h; opt-in, f8_lds_min_q) ----
+// Whole rows of 128 / 256 / 384 / 512 elements and the K slices of 256 / 384 / 512.  A workgroup of `waves` waves (4 or 8, 16
+// queries each) takes a STAGE of rows at a time: every thread loads hdb_mfma_f8_lds_chunks(d) 16-byte pieces of it, so a stage is
+// chunks x 64 x waves x 16 bytes of float8 -- 8 / 8 / 12 / 16 KiB with four waves, twice that with eight -- and twice as many
+// bytes of bf16 in LDS, in two buffers:
+//   d        128    256    384    512
+//   rows      64     32     32     32     (four waves; eight: 128 / 64 / 64 / --)
+//   LDS    32 KiB 32 KiB 48 KiB 64 KiB    (four waves; eight: 64 / 64 / 96 KiB / --, dynamic LDS beyond 64 KiB)
+// Four waves leave room for two workgroups per CU (128 KiB at most, 256 registers per lane), eight for one.  d = 512 is built for four
+// waves and one workgroup per CU only: 192 registers of query parts, the stage's pieces and the A fragments in flight do not fit the
+// 256 registers that two waves per SIMD leave a lane (the build spilled 44-124 bytes), so those kernels take what they need.
+static constexpr int hdb_mfma_f8_lds_supported(int d) { return d == 128 || d == 256 || d == 384 || d == 512; }
+// waves per workgroup: ScanArgs::f8_lds carries 4 or 8.  Measured at 10M x 384, cosine top-100, p50 in us, LDS flavour with four waves
+// (profiles/f8_lds_time.txt) vs eight (profiles/f8_lds_time_w8.txt; runs of their own, the repeated contender 4-12 % apart at this
+// shape): 64 queries 1 855 vs 2 310, 128 queries 3 566 vs 2 800, 256 queries 6 994 vs 5 453 -- four waves (two workgroups per CU: one
+// converts while the other multiplies) win while one workgroup holds the launch's queries, eight win 1.27x once four would read the
+// matrix twice.  So a launch of up to 64 queries takes four waves and a larger one eight (the option f8_lds_waves = 4 | 8 fixes it).
+#define HDB_F8_LDS_WAVES 4
+static constexpr int hdb_mfma_f8_lds_waves(int waves, int d = 0) { return d == 512 ? 4 : waves == 8 ? 8 : waves == 4 ? 4 : HDB_F8_LDS_WAVES; }
+static constexpr int hdb_mfma_f8_lds_auto_waves(int nq_launch) { return nq_launch > 64 ? 8 : 4; }
+static constexpr int hdb_mfma_f8_lds_chunks(int d) { return d == 128 || d == 256 ? 2 : d == 384 ? 3 : d == 512 ? 4 : 0; }
+static constexpr int hdb_mfma_f8_lds_stage_rows(int d, int waves = HDB_F8_LDS_WAVES) {
+    return hdb_mfma_f8_lds_supported(d) ? hdb_mfma_f8_lds_chunks(d) * 64 * hdb_mfma_f8_lds_waves(waves, d) * 16 / d : 0;
+}
+static constexpr int hdb_mfma_f8_lds_bytes(int d, int waves = HDB_F8_LDS_WAVES) { return 2 * hdb_mfma_f8_lds_stage_rows(d, waves) * 2 * d; }
+static constexpr int hdb_mfma_f8_lds_wg_per_cu(int d, int waves) { return (d == 512 || hdb_mfma_f8_lds_waves(waves, d) == 8) ? 1 : 2; }
+// workgroups of a launch over `ntiles` 16-row tiles: one per stage, at most `limit` (max_blocks, or workgroups per CU x CUs)
+static inline int hdb_mfma_f8_lds_blocks(int64_t ntiles, int d, int waves, int limit) {
+    const int tps = hdb_mfma_f8_lds_stage_rows(d, waves) / 16;
+    const int64_t stages = tps > 0 ? (ntiles + tps - 1) / tps : 0;
+    const int64_t b = stages < limit ? stages : limit;
+    return b < 1 ? 1 : (int)b;
+}
+// ... and the number of queries of a call from which the LDS flavour is used when f8_lds_min_q = -1; 0 = never.  d: the stored row
+// width -- a whole row or, under f8_ks_min_q, a sliced one.  The rule is the smallest measured batch size from which the LDS flavour
+// beats the register flavour by more than the repeated contender's spread at every larger measured size.  Measured, one box, the
+// contenders alternating call by call, cosine top-100, p50 in us, LDS (four waves) vs registers at 16 / 32 / 64 / 128 / 256 queries,
+// the two p50s of the repeated LDS contender at most 1.6 % apart (10M x 384: 0.2 / 2.3 / 3.7 / 9.5 / 5.6 %)
+// (tools/time_f8_lds.py -> profiles/f8_lds_time.txt):
+//   10M x 384: 1 480 vs 1 095, 1 575 vs 2 061, 1 855 vs 4 138, 3 566 vs 8 155, 6 994 vs 15 830     -> 32 (1.31x; 16 queries 0.74x)
+//    2M x 128:   223 vs   118,   231 vs   177,   260 vs   308,   431 vs   558,   701 vs  1 055     -> 64 (1.18x; 32 queries 0.77x)
+//    2M x 256:   367 vs   242,   387 vs   384,   421 vs   665,   772 vs 1 117, 1 191 vs  2 078     -> 64 (1.58x; 32 queries 0.99x)
+//    2M x 512:   799 vs   334,   801 vs   563,   845 vs 1 001, 1 616 vs 1 947, 3 185 vs  3 812     -> 64 (1.19x; 32 queries 0.70x)
+//    2M x 768:   808 vs   554,   859 vs   932,   964 vs 1 689, 1 831 vs 3 286, 3 611 vs  6 541     -> 32 (1.08x; 16 queries 0.69x)
+//  375k x 4096: 1 455 vs   801, 1 520 vs 1 242, 1 663 vs 2 068, 3 199 vs 3 812, 6 268 vs  7 510     -> 64 (1.24x; 32 queries 0.82x)
+// The other sliced widths were not measured: 0.  (The option is 0 by default: the rule is used only where a caller sets -1.)
+static inline int hdb_mfma_f8_lds_min_q(int d) { return (d == 384 || d == 768) ? 32 : (d == 128 || d == 256 || d == 512 || d == 4096) ? 64 : 0; }
+
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
 

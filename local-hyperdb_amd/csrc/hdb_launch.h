@@ -105,6 +105,15 @@ int hdb_launch_mfma_kslice_f8(const ScanArgs* a, int dslice, int mode, int nq_la
                               const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_kslice_f8_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
                                    const float* qsq, int blocks, void* stream);
+// float8 rows expanded to bf16 in LDS (hdb_mfma_f8_lds.h; ScanArgs::f8_lds = waves per workgroup); blocks: the most workgroups the launch may take
+int hdb_launch_mfma_scan_f8_lds(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_f8_lds_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                     const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_kslice_f8_lds(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                  const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_kslice_f8_lds_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                       const float* qsq, int blocks, void* stream);
 HDB_ANYD_DECL(hdb_launch_mfma_anyd_a); HDB_ANYD_DECL(hdb_launch_mfma_anyd_b);       // fp16 rows
 HDB_ANYD_DECL(hdb_launch_mfma_anyd_c); HDB_ANYD_DECL(hdb_launch_mfma_anyd_d);       // float32 rows
 HDB_ANYD_DECL(hdb_launch_mfma_anyd_e); HDB_ANYD_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts

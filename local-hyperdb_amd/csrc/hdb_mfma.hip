@@ -114,10 +114,17 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
                                                                                    : hdb_launch_mfma_scan_f32(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f);
     if (dtype == HDB_F8E4M3) {          // float8 rows (hdb_mfma_f8.h): no LDS ring and 16-row tiles, a wave per tile -- up to four workgroups per CU
         if (mode == 2) return (int)hipErrorNotSupported;
+        const bool ks8 = a.ks_partial_out && hdb_mfma_f8_ks_slices(a.d) > 0;
+        if (a.f8_lds) {                  // the plan asked for the rows to be expanded in LDS once per workgroup (f8_lds_min_q, hdb_mfma_f8_lds.h):
+            // a grid of stages, one or two workgroups per CU at most; every launcher takes min(its stages, this limit)
+            const int lim = max_blocks > 0 ? max_blocks : hdb_mfma_f8_lds_wg_per_cu(a.d, a.f8_lds) * cus;
+            if (ks8) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, lim, stream);
+            return hdb_launch_mfma_scan_f8_lds(args, mode, nq_launch, q16, sqnorm, qsq, lim, stream);
+        }
         const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
         const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
         // rows wider than 512 elements: the plan asked for K slices (f8_ks_min_q) -- it alone hands such a call a partial-sum buffer
-        if (a.ks_partial_out && hdb_mfma_f8_ks_slices(a.d) > 0) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
+        if (ks8) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
         return hdb_launch_mfma_scan_f8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
     }
     if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);

@@ -39,6 +39,78 @@ __device__ __forceinline__ u32x4 hdb_f8x8_to_bf16x8(const uint2& raw) {
     return o;
 }
 
+// What the register kernel below and the LDS kernel (hdb_mfma_f8_lds.h) do with a tile's accumulator, in ONE place so that the two
+// cannot drift: lane (rl, h) holds rows rowg = row0 + 4 h .. + 3 of tile sequence number t against query rl.
+// ... its start: zero, or the sums of the K slices before this one
+template <bool KSL>
+__device__ __forceinline__ f32x4 hdb_f8_acc_start(const ScanArgs& a, bool q_ok, int64_t ks_at, int64_t rowg, int64_t n_rows) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (KSL) {
+        if (a.ks_partial_in && q_ok) {           // the sums of the slices before this one
+            const float* pin = a.ks_partial_in + ks_at;
+            if (rowg + 3 < n_rows) { const float4 pv = *reinterpret_cast<const float4*>(pin); acc[0] = pv.x; acc[1] = pv.y; acc[2] = pv.z; acc[3] = pv.w; }
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) acc[j] = pin[j];
+            }
+        }
+    }
+    return acc;
+}
+// ... and its end: MODE 3 stores the raw sums for the next slice, MODE 0 / 1 run the metric's epilogue and store or filter
+template <int MODE, int METRIC, bool HAS_BIAS, bool KSL>
+__device__ __forceinline__ void hdb_f8_tile_finish(const ScanArgs& a, const f32x4& acc, const float* __restrict__ aux0, int64_t t, int h, int64_t rowg,
+                                                   int64_t n_rows, bool q_ok, int ql, float qinv_l, float qsq_l, float thr_cmp, int64_t ks_at) {
+    constexpr bool FILT = MODE == 1;
+    if constexpr (MODE == 3) {                   // raw partial sums for the next K slice
+        if (q_ok) {
+            float* pout = a.ks_partial_out + ks_at;
+            if (rowg + 3 < n_rows) *reinterpret_cast<float4*>(pout) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) pout[j] = acc[j];
+            }
+        }
+        return;
+    }
+    // epilogue: the bfloat16 flavour's arithmetic, term by term
+    float x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t rr = min(rowg + j, n_rows - 1);
+        const float aj = METRIC != 0 ? aux0[rr] : 1.f;
+        const float bj = HAS_BIAS ? a.bias[rr] : 0.f;
+        const float dot = acc[j];
+        if (METRIC != 0 || HAS_BIAS || MODE == 0) {
+            if (METRIC == 0) x[j] = HAS_BIAS ? fmaf(dot, qinv_l, bj) : dot * qinv_l;
+            else if (METRIC == 1) {
+                if (FILT && !HAS_BIAS) x[j] = dot * aj;
+                else x[j] = HAS_BIAS ? fmaf(dot * aj, qinv_l, bj) : dot * aj * qinv_l;
+            } else {
+                const float d2 = fmaxf(fmaf(-2.f * qinv_l, dot, aj + qsq_l), 0.f);
+                x[j] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_sqrtf(d2)) + (HAS_BIAS ? bj : 0.f);
+            }
+        } else x[j] = dot;
+    }
+    if (MODE == 0) {
+        if (q_ok) {
+            float* dst = a.scores + (int64_t)ql * a.ld + (t * 16 + 4 * h);          // sample passes store compactly
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) dst[j] = hdb_canon(x[j]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool hit = x[j] >= thr_cmp && rowg + j < n_rows && !(HAS_BIAS && x[j] == -INFINITY);      // bias -inf = masked row
+            if (hit) {
+                const float sc = hdb_canon((METRIC != 2 && !HAS_BIAS) ? x[j] * qinv_l : x[j]);
+                const uint32_t pos = atomicAdd(&a.cnt[ql * HDB_CNT_STRIDE], 1u);
+                if (pos < a.cap) a.cand[(int64_t)ql * a.cap + pos] = hdb_pack(sc, (uint32_t)(rowg + j));
+            }
+        }
+    }
+}
+
 // (the filter flavour of a 512-element slice holds 192 registers of query parts, 32 of raw row bytes, the partial sums and the slice
 //  addressing: left alone it takes 254-256 VGPRs plus 4 AGPRs for the accumulator -- 264 allocated, one wave per SIMD.  Asked for two
 //  workgroups per CU it keeps the accumulator in the 256 VGPRs, without scratch: two waves per SIMD like the other 512-element kernels)
@@ -88,20 +160,10 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
         uint2 raw[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) raw[s] = src[4 * s];            // (cached: the waves that share the tile find it in L1 / L2)
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         const int64_t rowg = row0 + 4 * h;
         // C register j of lane (rl, h) = row 4 h + j of the tile x query rl; a K slice keeps it at [query][t * 16 + 4 h + j]
         const int64_t ks_at = KSL ? (int64_t)(q_ok ? ql : 0) * a.ks_ld + (t * 16 + 4 * h) : 0;
-        if constexpr (KSL) {
-            if (a.ks_partial_in && q_ok) {           // the sums of the slices before this one
-                const float* pin = a.ks_partial_in + ks_at;
-                if (rowg + 3 < n_rows) { const float4 pv = *reinterpret_cast<const float4*>(pin); acc[0] = pv.x; acc[1] = pv.y; acc[2] = pv.z; acc[3] = pv.w; }
-                else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) acc[j] = pin[j];
-                }
-            }
-        }
+        f32x4 acc = hdb_f8_acc_start<KSL>(a, q_ok, ks_at, rowg, n_rows);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             const u32x4 av = hdb_f8x8_to_bf16x8(raw[s]);
@@ -111,53 +173,7 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p0), acc, 0, 0, 0);
 #undef HDB_BF
         }
-        if constexpr (MODE == 3) {                   // raw partial sums for the next K slice
-            if (q_ok) {
-                float* pout = a.ks_partial_out + ks_at;
-                if (rowg + 3 < n_rows) *reinterpret_cast<float4*>(pout) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-                else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) pout[j] = acc[j];
-                }
-            }
-            continue;
-        }
-        // epilogue: the bfloat16 flavour's arithmetic, term by term
-        float x[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t rr = min(rowg + j, n_rows - 1);
-            const float aj = METRIC != 0 ? aux0[rr] : 1.f;
-            const float bj = HAS_BIAS ? a.bias[rr] : 0.f;
-            const float dot = acc[j];
-            if (METRIC != 0 || HAS_BIAS || MODE == 0) {
-                if (METRIC == 0) x[j] = HAS_BIAS ? fmaf(dot, qinv_l, bj) : dot * qinv_l;
-                else if (METRIC == 1) {
-                    if (FILT && !HAS_BIAS) x[j] = dot * aj;
-                    else x[j] = HAS_BIAS ? fmaf(dot * aj, qinv_l, bj) : dot * aj * qinv_l;
-                } else {
-                    const float d2 = fmaxf(fmaf(-2.f * qinv_l, dot, aj + qsq_l), 0.f);
-                    x[j] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_sqrtf(d2)) + (HAS_BIAS ? bj : 0.f);
-                }
-            } else x[j] = dot;
-        }
-        if (MODE == 0) {
-            if (q_ok) {
-                float* dst = a.scores + (int64_t)ql * a.ld + (t * 16 + 4 * h);          // sample passes store compactly
-#pragma unroll
-                for (int j = 0; j < 4; ++j) if (rowg + j < n_rows) dst[j] = hdb_canon(x[j]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool hit = x[j] >= thr_cmp && rowg + j < n_rows && !(HAS_BIAS && x[j] == -INFINITY);      // bias -inf = masked row
-                if (hit) {
-                    const float sc = hdb_canon((METRIC != 2 && !HAS_BIAS) ? x[j] * qinv_l : x[j]);
-                    const uint32_t pos = atomicAdd(&a.cnt[ql * HDB_CNT_STRIDE], 1u);
-                    if (pos < a.cap) a.cand[(int64_t)ql * a.cap + pos] = hdb_pack(sc, (uint32_t)(rowg + j));
-                }
-            }
-        }
+        hdb_f8_tile_finish<MODE, METRIC, HAS_BIAS, KSL>(a, acc, aux0, t, h, rowg, n_rows, q_ok, ql, qinv_l, qsq_l, thr_cmp, ks_at);
     }
 }
 

@@ -28,7 +28,8 @@ extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode,
         const int m = s + 1 < g.slices ? 3 : mode;
         const int w = g.width[s];
         int rc;
-        if (dtype == HDB_F8E4M3) rc = hdb_launch_mfma_kslice_f8(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
+        if (dtype == HDB_F8E4M3 && args->f8_lds) rc = hdb_launch_mfma_kslice_f8_lds(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (blocks: a limit, each slice sizes its own grid)
+        else if (dtype == HDB_F8E4M3) rc = hdb_launch_mfma_kslice_f8(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
         else if (dtype == HDB_BF16) rc = hdb_launch_mfma_kslice_bf16(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (float32 queries as they are: no qscl)
         else if (dtype == HDB_F32 && args->f32_split) rc = hdb_launch_mfma_kslice_f32s(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
         else if (dtype == HDB_F32) rc = w == 512 ? launch_kslice<float, 512, 16>(a, m, q, sqnorm, qsq, nullptr, nq_launch, blocks, st)

@@ -27,6 +27,8 @@ struct hdb_options {
     int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
+    int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
+    int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
     int64_t host_direct = 1;          // hdb_topk_host: kernels write a pinned host record themselves (no D2H copy)
     int64_t dyn_tiles = 1;            // MFMA filter pass: hand tiles out from a counter (0: static split)
@@ -84,12 +86,13 @@ enum TopkPath {
     HDB_PATH_PIPELINE                 // the multi-kernel pipeline: small, sampled or exact
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
-struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0; };
+struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0; };
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
     bool bits = false, pearson = false;                 // the metric's family
     bool exact = false, small = false, mfma = false, f32s = false, ksplit = false, l1tile = false, local = false;
+    bool f8_lds = false;                                // float8 rows: every matrix-core launch of the call expands its rows in LDS (hdb_mfma_f8_lds.h)
     bool subset = false;                                // the pipeline scores the rows of the index's list: every extent below is that of a matrix of subset_m rows
     // prologue of the paths that prepare their queries with launches of their own (full sort, pipeline)
     bool prep = false, fold_small = false, q16_in_prep = false, f16_queries = false, mask_fold = false;
@@ -259,6 +262,14 @@ static inline bool subset_rule(const TopkFacts& ix, const hdb_options& o, const 
     return ix.subset_m <= ix.n / (((int64_t)c.nq + 3) / 4 * ratio);
 }
 
+// The number of queries of a call from which a float8 index expands its rows in LDS (f8_lds_min_q; the stat of the same name): the
+// option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never
+static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
+    if (dtype != HDB_F8E4M3) return 0;
+    const int64_t rule = o.f8_lds_min_q > 0 ? o.f8_lds_min_q : o.f8_lds_min_q < 0 ? (int64_t)hdb_mfma_f8_lds_min_q(d) : 0;
+    return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
+}
+
 // finite(): "are all rows of the matrix finite with a finite sum of squares?"
 template <typename Finite>
 static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite) {
@@ -408,6 +419,12 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
                        // (more than four queries: the six launches take them all in one go, grid.y = query groups -- 16 queries on
                        // 100k rows 50 vs 148 us for four single launches in a row, 64 queries 67 vs 642; 10M rows 464 vs 524)
                        nq <= (o.bits_max_q >= 0 ? o.bits_max_q : 4);
+    // float8 batches with the rows expanded in LDS once per workgroup (f8_lds_min_q, opt-in): whatever the float8 matrix cores take --
+    // a whole row or the K slices -- from the threshold's number of queries on; sample, filter and exact pass alike.  Nothing else of
+    // the plan changes: the tiles stay 16 rows, so the sample rows, the thresholds and with them the answers are the register flavour's
+    const int64_t f8_lds_first = f8_lds_first_q(o, ix.dtype, ix.d);
+    p.f8_lds = mfma && ix.dtype == HDB_F8E4M3 && !full_sort && (f8ks || hdb_mfma_f8_lds_supported(ix.d)) && f8_lds_first > 0 && nq >= f8_lds_first;
+    p.stats.f8_lds = p.f8_lds ? 1 : 0;
     p.exact = exact; p.small = small; p.mfma = mfma; p.f32s = f32s; p.ksplit = ksplit; p.local = local_ok;
     p.tile_rows = tile_rows; p.s_tiles = s_tiles; p.s_stride = s_stride; p.m = m; p.s_rows = s_rows; p.ld_s = ld_s; p.ld_n = ld_n;
     p.cq_max = cq_max;
