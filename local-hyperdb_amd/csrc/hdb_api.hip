@@ -759,8 +759,13 @@ static TopkFacts topk_facts(const hdb_index* ix) {
 // The workspace of a 1-4-query shadow call (QuantWs, hdb_ws.h): the memory guard of the automatic build sizes with these extents,
 // the call lays out with them.  The score buffer takes the extent of the largest sample any k takes (quant_ld_max) -- the call's own
 // ld_s is only its leading dimension -- so calls that differ in k never regrow the workspace.  (P from d: the automatic build asks
-// before the index has a pitch.)  pl_cap: entries of a row list beside the score buffer (0 from every caller: hdb_ws.h).
+// before the index has a pitch.)  pl_cap: entries of the list beside the score buffer (hdb_ws.h): quant_hi_cap from every caller.
 static int quant_pitch(const hdb_index* ix) { return (int)align_up((size_t)ix->d, 16); }
+// The list of the sampled rows' upper bounds (QuantArgs::pl_hi): one query, a width the plane takes; like the score buffer it has
+// the extent of the largest sample any k takes.  The memory guard, the call and the test entry all size with it.
+static uint32_t quant_hi_cap(const hdb_index* ix, int nq) {
+    return nq == 1 && plane_possible((int)ix->d) ? (uint32_t)quant_ld_max(ix->n, ix->d) : 0u;
+}
 static size_t quant_ws_bytes(const hdb_index* ix, int nq, uint32_t pl_cap, bool mflavour) {
     return ws_bytes_for<QuantWs>(nq, quant_pitch(ix), (int)ix->d, quant_ld_max(ix->n, ix->d), pl_cap, mflavour);
 }
@@ -799,7 +804,7 @@ static int quant_query_prep(hdb_index* ix, const float* Q, int nq, const QuantWs
 // Either may be declined for memory: the index remembers that, *declined is set and topk_impl plans once more on the new facts.
 static int shadow_prepare(hdb_index* ix, const TopkPlan& p, int nq, hipStream_t st, bool* declined) {
     if (p.build_needed) {
-        const size_t ws_need = p.path == HDB_PATH_QUANT ? quant_ws_bytes(ix, nq, 0, true) : quant_batch_ws_bytes(ix, p.cq_max);
+        const size_t ws_need = p.path == HDB_PATH_QUANT ? quant_ws_bytes(ix, nq, quant_hi_cap(ix, nq), true) : quant_batch_ws_bytes(ix, p.cq_max);
         if (!quant_auto_build(ix, ws_need, st)) { *declined = true; return HDB_OK; }
     }
     if (p.plane_wanted && !ix->pnib) {
@@ -827,7 +832,7 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     const uint32_t m = 16;
     const QuantSample sp = p.qs;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, nq, 0, mflavour);
+    int rc = quant_ws_lay(ix, w, nq, quant_hi_cap(ix, nq), mflavour);
     if (rc) return rc;
     uint32_t* qstat = reinterpret_cast<uint32_t*>(ix->qstat);
     uint32_t* pl_cnt = use_pl ? qstat + 1 : nullptr;
@@ -838,6 +843,8 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     QuantArgs a; quant_base_args(ix, a, w.qcodes, w.qaux, w.qinv, metric, nq);
     a.ntiles = sp.s_tiles; a.tile_stride = sp.s_stride; a.scores = w.sbuf; a.ld = sp.ld_s;
     a.wmax = w.wmax; a.nsub = nsub; a.thr_out = w.thr;
+    a.pl_hi = use_pl ? reinterpret_cast<float*>(w.pl_list) : nullptr;      // the plane pass takes the sampled rows from this list
+    if (use_pl && (!a.pl_hi || sp.s_rows > (int64_t)quant_hi_cap(ix, nq))) return fail(HDB_ERR_ARG, "quant_topk: no list for the sampled rows");
     LAUNCH_TRY(hdb_launch_quant_scan(&a, 0, (int)ix->opt.max_blocks, st));
     if (!nsub) LAUNCH_TRY(hdb_launch_sample_thr(w.sbuf, sp.s_rows, sp.ld_s, nq, m, w.thr, w.cnt, nullptr, st));
     a.ntiles = (n + 15) / 16; a.tile_stride = 1; a.scores = nullptr; a.ld = 0;
@@ -850,9 +857,11 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     prof_begin(ix, st);
     if (use_pl) {
         // one dot / cosine query: the pass over the 5-bit plane, which finishes the rows it keeps itself (hdb_quant.hip); it takes
-        // the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for the finalize
+        // the threshold the way MODE 1 would (folded or from thr) and leaves it in thr for the finalize.  It does not stream the
+        // sample's tiles: their rows come from the list of upper bounds the sample pass left (pl_hi)
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
         a.pl_cnt = pl_cnt; a.pl_cap = p.pl_cap;
+        a.pl_s_tiles = (uint32_t)sp.s_tiles; a.pl_s_stride = (uint32_t)sp.s_stride;      // ... and walks the other tiles
         LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->opt.max_blocks, st));
     } else {
         LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->opt.max_blocks, st));
@@ -883,7 +892,7 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     QuantWs w;
-    int rc = quant_ws_lay(ix, w, 1, 0, true);
+    int rc = quant_ws_lay(ix, w, 1, quant_hi_cap(ix, 1), true);
     if (rc) return rc;
     rc = quant_query_prep(ix, dev_q, 1, w, ix->qauto, nullptr, nullptr, nullptr, st);
     if (rc) return rc;

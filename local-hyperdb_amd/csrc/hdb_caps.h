@@ -318,6 +318,45 @@ static inline int hdb_l1_tile_supported(int dtype, int d) {
 static inline int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for(ntiles, 4, max_blocks > 0 ? max_blocks : 1024); }
 // The 5-bit plane: units of a row
 static inline int hdb_quant_plane_units(int P) { return (P + 31) / 32; }
+// The plane pass of a one-query call does not stream the tiles the sample pass evaluated (it takes their upper bounds from the
+// list that pass left, QuantArgs::pl_hi): it walks a dense index t' over the OTHER tiles.  The sample takes one tile of each
+// window w < s_tiles of `stride` tiles, hdb_tile_index(w, stride); the tiles from s_tiles x stride on (the ragged last one among
+// them) are in no window.  A position is (w, o): w < s_tiles and o < stride - 1 counts the window's tiles with the sampled one
+// left out, or w == s_tiles and o counts the tiles behind the last window.  s_tiles == 0: no sample, every tile is walked.
+// One division where a walk starts; a step of `step` positions adds (step / (stride - 1), step % (stride - 1)), which the walker
+// forms once, so that nothing divides per step but hdb_tile_index itself.  (stride == 1: the sample is a dense prefix, no window
+// has a tile of its own and every position is in the tail.)  Tile numbers fit 32 bits: a row number does (hdb_pack).
+// (__host__ __device__: the kernel walks with these very functions, tests/plane_skip_check.hip walks them on the host.)
+struct HdbSkipPos { uint32_t w, o; };
+struct HdbSkipStep { uint32_t dw, dn, step; };        // (windows, positions inside a window, positions) of one step
+__host__ __device__ __forceinline__ uint32_t hdb_plane_skip_count(uint32_t ntiles, uint32_t s_tiles) { return ntiles - s_tiles; }
+__host__ __device__ __forceinline__ HdbSkipStep hdb_plane_skip_step(uint32_t step, uint32_t stride) {
+    const uint32_t m = stride - 1u;
+    HdbSkipStep s;
+    s.dw = m ? step / m : 0u; s.dn = m ? step % m : 0u; s.step = step;
+    return s;
+}
+__host__ __device__ __forceinline__ HdbSkipPos hdb_plane_skip_start(uint32_t tp, uint32_t s_tiles, uint32_t stride) {
+    const uint32_t m = stride - 1u;
+    HdbSkipPos p;
+    const uint32_t w = m ? tp / m : s_tiles;
+    if (w < s_tiles) { p.w = w; p.o = tp - w * m; }
+    else { p.w = s_tiles; p.o = tp - s_tiles * m; }
+    return p;
+}
+// (the step must come from hdb_plane_skip_step with the same stride, or be {0, 1, 1}: the next position)
+__host__ __device__ __forceinline__ void hdb_plane_skip_advance(HdbSkipPos& p, const HdbSkipStep& s, uint32_t s_tiles, uint32_t stride) {
+    if (p.w >= s_tiles) { p.o += s.step; return; }
+    const uint32_t m = stride - 1u;
+    p.w += s.dw; p.o += s.dn;
+    if (p.o >= m) { p.o -= m; ++p.w; }
+    if (p.w >= s_tiles) { p.o += (p.w - s_tiles) * m; p.w = s_tiles; }
+}
+__host__ __device__ __forceinline__ int64_t hdb_plane_skip_tile(const HdbSkipPos& p, uint32_t s_tiles, uint32_t stride) {
+    if (p.w >= s_tiles) return (int64_t)s_tiles * stride + p.o;
+    const uint32_t jit = (uint32_t)(hdb_tile_index((int64_t)p.w, (int64_t)stride) - (int64_t)p.w * stride);
+    return (int64_t)p.w * stride + p.o + (p.o >= jit ? 1u : 0u);
+}
 
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 // widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan

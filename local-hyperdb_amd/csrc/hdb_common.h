@@ -196,7 +196,7 @@ __device__ __forceinline__ float hdb_q16_scale(float amax) {
 // Sample tile t of a strided sample sits at tile index t*stride + jitter(t), jitter in [0, stride): a fixed
 // pseudo-random offset inside each stride window, so that a matrix with periodic structure (rows inserted
 // round-robin by class, ...) cannot alias with the sampling period.  stride == 1 (dense scan) gives jitter 0.
-__device__ __forceinline__ int64_t hdb_tile_index(int64_t t, int64_t stride) {
+__host__ __device__ __forceinline__ int64_t hdb_tile_index(int64_t t, int64_t stride) {
     if (stride == 1) return t;                       // dense pass: keep the division off the load path
     const uint32_t h = (uint32_t)t * 2654435761u;
     return t * stride + (int64_t)((h >> 8) % (uint32_t)stride);

@@ -53,6 +53,11 @@ struct QuantArgs {
     // is worth; the answer is complete either way).  dbg: test-only output of one upper bound per row (hdb_debug_quant_bounds).
     const uint8_t* pl_nib; const uint32_t* pl_bit; const float* pl_rec; int32_t pl_units;
     uint32_t* pl_cnt; uint32_t pl_cap;
+    // The sampled tiles are evaluated once: the sample pass of a one-query call that takes the plane (MODE 0, pl_hi non-null) stores
+    // MODE 1's upper bound of every sampled row to pl_hi[sample slot] (-inf: masked row, declined query), and pass 1 walks the
+    // tiles the sample did not take (pl_s_tiles windows of pl_s_stride tiles, hdb_plane_skip_tile; 0 windows: every tile) and
+    // queues the sampled rows with !(pl_hi < T_s) for the evaluation it gives the rows its own bound keeps.
+    float* pl_hi; uint32_t pl_s_tiles; uint32_t pl_s_stride;
     float* dbg;
 };
 #define HDB_QUANT_NSUB_MAX 4096      // (MODE 1 holds nsub / 256 keys per thread)

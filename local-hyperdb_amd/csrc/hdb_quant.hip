@@ -92,6 +92,11 @@
 // Z 2^-18 is relative to magnitudes that do not cancel, at most 2^-8 of the bound's own width B: pass 1 loses nothing by it.
 // The rows pass 1 keeps are finished by pass 1 itself: 16 at a time they go through MODE 1's own evaluation (hq_rows4_bounds, compiled
 // with contraction off: the uncontracted form is one of the evaluations F(A) above, and both kernels get the same bits from it).
+// The sampled tiles are not streamed a second time.  The sample pass has already put their rows through that evaluation, so it stores
+// hi beside the lower bound it is after (QuantArgs::pl_hi, one float per sample slot), and pass 1 walks the other tiles only
+// (hdb_plane_skip_*, hdb_caps.h) and queues the sampled rows with !(hi < T_s) from the list.  Streamed, such a row was queued because
+// hi5 >= hi; a sampled row with hi < T_s that hi5 let through was queued for nothing (the drain drops it).  The drain evaluates and
+// emits on the same condition either way: the candidate set is unchanged, plane_survivors counts at most what it counted.
 #include "hdb_common.h"
 #include "hdb_quant.h"
 #include "hdb_finalize.h"
@@ -357,7 +362,9 @@ __device__ __forceinline__ int hq_rows4_sum(int a0, int a1, int a2, int a3, int 
     return w;
 }
 
-// The threshold folded into the passes (QuantArgs::nsub > 0), every thread of a 256-thread workgroup calls it:
+// The threshold folded into the passes (QuantArgs::nsub > 0), every thread of a 256-thread workgroup calls it.  Every workgroup of
+// the filter pass runs it at its head with no load of the stream in flight, so the 32 wave maxima are DPP reductions
+// (hdb_wave_max_dpp: a scalar, no LDS crossbar) and the owner of a maximum is found by comparing with that scalar:
 template <int NQ>
 __device__ __forceinline__ void hq_fold_thr(const QuantArgs& a, float (&q_thr)[NQ]) {
     // T_s = 16th largest of the per-wave maxima of the sample pass: every wave extracts the 16 largest of its quarter, wave 0
@@ -376,9 +383,7 @@ __device__ __forceinline__ void hq_fold_thr(const QuantArgs& a, float (&q_thr)[N
             uint32_t lm = 0u;
 #pragma unroll
             for (int j = 0; j < HDB_QUANT_NSUB_MAX / 256; ++j) lm = max(lm, c[j]);
-            uint32_t wm = lm;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+            const uint32_t wm = hdb_wave_max_dpp(lm);        // (scalar: DPP inside the rows, v_readlane across them -- no LDS crossbar)
             const unsigned long long who = __ballot(lm == wm);
             if (ln == (int)__ffsll((long long)who) - 1) {
                 bool gone = false;
@@ -393,9 +398,7 @@ __device__ __forceinline__ void hq_fold_thr(const QuantArgs& a, float (&q_thr)[N
             uint32_t v = s_top[ln];
             uint32_t kth = 0u;
             for (int r = 0; r < 16; ++r) {
-                uint32_t wm = v;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o, 64));
+                const uint32_t wm = hdb_wave_max_dpp(v);
                 const unsigned long long who = __ballot(v == wm);
                 if (ln == (int)__ffsll((long long)who) - 1) v = 0u;
                 kth = wm;
@@ -594,7 +597,8 @@ __device__ __forceinline__ void hq_stage_flush(HqStage& stage) {
     }
 }
 
-// MODE 0: lower bounds of the sampled rows -> scores[q][ld], or (nsub > 0) the per-wave maxima -> wmax;  MODE 1: rows whose upper bound
+// MODE 0: lower bounds of the sampled rows -> scores[q][ld], or (nsub > 0) the per-wave maxima -> wmax, and for one query ahead of the
+// plane pass (pl_hi non-null) their upper bounds -> pl_hi[sample slot];  MODE 1: rows whose upper bound
 // reaches the threshold (thr[q], or nsub > 0: folded, hq_fold_thr) -> candidate lists;  MODE 2 (tests): MODE 1's upper bound of every
 // row -> dbg[row], nothing emitted.
 // (QuantArgs stays the first parameter: hq_args_in_memory.)
@@ -634,6 +638,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
             } else if (MODE == 0) {
                 if (a.nsub > 0) wbest[q] = max(wbest[q], hdb_f2key(lo));
                 else a.scores[(int64_t)q * a.ld + out_i] = lo;
+                if (NQ == 1 && a.pl_hi) a.pl_hi[out_i] = hi;          // (pass 1 over the plane takes the sampled rows from here)
             } else if (!masked && !qc.bad[q] && hi >= q_thr[q]) {
                 hq_emit(stage, q, hi, row);
             }
@@ -641,6 +646,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
         if (MODE == 0 && a.nsub == 0 && !live && (l16 & 3) == 0)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) a.scores[(int64_t)q * a.ld + out_i] = -INFINITY;
+        if (MODE == 0 && NQ == 1 && a.pl_hi && !live && (l16 & 3) == 0) a.pl_hi[out_i] = -INFINITY;
     }
     if (MODE == 0 && a.nsub > 0) {                       // (every wave of the grid writes its slot: a wave without tiles writes 0)
 #pragma unroll
@@ -710,6 +716,7 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
 // candidates through the workgroup's stage exactly as MODE 1 does; what is left after the last step goes as a ragged tile (empty
 // slots: "no row" = a.n).  The gather's latency chain (row number -> code row -> row terms) hides behind the other waves' streams.
 // A step appends at most 32 rows to fewer than 16, and a drain leaves fewer than 16: 48 entries per wave.
+// Behind the stream the wave takes its share of the sampled rows from the list of the sample pass, 32 at a time into the same queue.
 // (96 scalar registers: the drain's nest of branches and its argument loads would otherwise take the kernel past 96, which costs the
 //  narrow widths a wave per SIMD; with the cap the allocator keeps a handful of scalars in vector lanes around the drain instead.
 //  QuantArgs stays the first parameter: hq_args_in_memory.  The empty asm statements here and in the drain only steer the register
@@ -777,7 +784,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         });
     };
 
-    for (int64_t t = ((int64_t)blockIdx.x * 4 + wave) * 2; t < ntiles; t += (int64_t)gridDim.x * 8) {
+    // The walk: position tp of the tiles the sample pass did not take (hdb_caps.h; DBG, or no list: every tile), two positions per
+    // step.  The two tiles of a step need not be adjacent -- a sampled tile may lie between them -- so every address and every
+    // epilogue row comes from the mapped tile number tl[tt] (scalar; ntiles: no tile).
+    const uint32_t s_tiles = DBG ? 0u : a.pl_s_tiles, s_stride = DBG ? 1u : a.pl_s_stride;
+    const uint32_t nwalk = hdb_plane_skip_count((uint32_t)ntiles, s_tiles);
+    const uint32_t tp0 = ((uint32_t)blockIdx.x * 4u + (uint32_t)wave) * 2u;
+    const HdbSkipStep sk_step = hdb_plane_skip_step((uint32_t)gridDim.x * 8u, s_stride), sk_next = {0u, 1u, 1u};
+    HdbSkipPos pos = hdb_plane_skip_start(tp0 < nwalk ? tp0 : 0u, s_tiles, s_stride);
+    for (uint32_t tp = tp0; tp < nwalk; tp += (uint32_t)gridDim.x * 8u, hdb_plane_skip_advance(pos, sk_step, s_tiles, s_stride)) {
+        int64_t tl[2];
+        {
+            HdbSkipPos p1 = pos;
+            hdb_plane_skip_advance(p1, sk_next, s_tiles, s_stride);
+            tl[0] = hdb_plane_skip_tile(pos, s_tiles, s_stride);
+            tl[1] = tp + 1u < nwalk ? hdb_plane_skip_tile(p1, s_tiles, s_stride) : ntiles;
+        }
         u32x4 nv[2][J];
         uint32_t bv[2][J];
         int ln = lane;
@@ -785,9 +807,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             // pieces of this tile's own rows: 0 past the last tile, the ragged tile loads its rows only (piece f is of row f / U)
-            const int pieces_left = (int)min((int64_t)16, max((int64_t)0, a.n - (t + tt) * 16)) * U;
-            const uint8_t* nb = a.pl_nib + (t + tt) * (int64_t)npieces * 16;
-            const uint32_t* bb = a.pl_bit + (t + tt) * (int64_t)npieces;
+            const int pieces_left = (int)min((int64_t)16, max((int64_t)0, a.n - tl[tt] * 16)) * U;
+            const uint8_t* nb = a.pl_nib + tl[tt] * (int64_t)npieces * 16;
+            const uint32_t* bb = a.pl_bit + tl[tt] * (int64_t)npieces;
 #pragma unroll
             for (int j = 0; j < J; ++j) {
                 if (ln < pieces_left - 64 * j) {
@@ -800,8 +822,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             }
         }
         // the row terms of the epilogue lanes, issued with the plane loads
-        const int64_t row = (t + et) * 16 + er;
-        const bool rvalid = lane < 32 && t + et < ntiles && row < a.n;
+        const int64_t row = (et ? tl[1] : tl[0]) * 16 + er;
+        const bool rvalid = lane < 32 && row < a.n;      // (no tile: row = 16 ntiles >= n)
         f32x4 rc = f32x4{0.f, 0.f, 0.f, 0.f};
         float invn = 1.f, bias = 0.f;
         bool masked = false;
@@ -884,6 +906,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         }
     }
     if (!DBG) {
+        // The sampled rows: their upper bounds are in the list the sample pass left, slot 16 w + r for row r of window w's tile.  A wave
+        // loads 64 slots at a time (the next 64 in flight behind them) and appends the rows with !(hi < T_s) half by half -- at most 32 to
+        // fewer than 16, as a step of the stream does -- and drains as the stream does.  hi is MODE 1's own (hq_rows4_bounds, same
+        // bits), and hi5 >= hi had every such row queued when the tile was streamed: the drain emits what it emitted then.
+        if (s_tiles != 0u) {
+            const QuantArgs& am = hq_args_in_memory();
+            const uint32_t nslots = s_tiles * 16u, dslot = (uint32_t)gridDim.x * 256u;
+            uint32_t cbase = ((uint32_t)blockIdx.x * 4u + (uint32_t)wave) * 64u;             // (scalar)
+            float hnext = cbase + lane < nslots ? am.pl_hi[cbase + lane] : 0.f;
+#pragma unroll 1
+            for (; cbase < nslots; cbase += dslot) {
+                const uint32_t slot = cbase + lane;
+                const float hi = hnext;
+                hnext = slot + dslot < nslots ? am.pl_hi[slot + dslot] : 0.f;
+                const int64_t row = hdb_tile_index((int64_t)(slot >> 4), (int64_t)s_stride) * 16 + (slot & 15u);
+                bool keep = slot < nslots && !q_bad && !(hi < q_thr);
+                if (keep && am.mask) keep = am.mask[row] != 0;                               // (a masked row is in no queue, as in the stream)
+                const unsigned long long km = __ballot(keep);
+#pragma unroll 1
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t kh = (uint32_t)(km >> (32 * h));
+                    if (kh == 0u) continue;                                                  // (wave-uniform)
+                    if (keep && (lane >> 5) == h) queue[wave][qn + __popc(kh & ((1u << (lane & 31)) - 1u))] = (uint32_t)row;
+                    const int nk = __popc(kh);
+                    qn += nk; nsurv += (uint32_t)nk;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    while (qn >= 16) { qn -= 16; drain(qn, 16); }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();                                         // (the next append stays behind the drain's loads)
+                }
+            }
+        }
         if (qn > 0) drain(0, qn);
         if (lane == 0 && nsurv != 0u) atomicAdd(&surv_cnt, nsurv);                       // LDS
         hq_stage_flush<1>(stage);
@@ -1090,8 +1146,12 @@ extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int m
     if (a.nq != 1 || U < 1 || U > 16 || U != hdb_quant_plane_units(a.P) || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
     if (!dbg && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
     if (!dbg && (!a.cnt || !a.cand || !a.pl_cnt || !hq_copy_args_ok(a))) return (int)hipErrorInvalidValue;
+    // the tiles the sample pass took are not walked (dbg: every tile is): its windows lie inside the matrix and its list is there
+    if (a.ntiles < 0 || a.ntiles > 0x10000000) return (int)hipErrorInvalidValue;      // (a row number has 32 bits: hdb_pack)
+    if (!dbg && a.pl_s_tiles != 0u && (!a.pl_hi || a.pl_s_stride < 1u || (uint64_t)a.pl_s_tiles * a.pl_s_stride > (uint64_t)a.ntiles)) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)U * 32;
-    const int blocks = hdb_grid_for((a.ntiles + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024);
+    const int64_t nwalk = a.ntiles - (dbg ? 0 : (int64_t)a.pl_s_tiles);
+    const int blocks = hdb_grid_for((nwalk + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024);
     hipStream_t st = (hipStream_t)stream;
     const int J = (U + 3) / 4;
 #define HQ_PLANE(J_) do { if (dbg) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, true>), dim3(blocks), dim3(256), lds, st, a); \

@@ -113,9 +113,10 @@ static inline QuantSample quant_batch_sample(int64_t n) {
 }
 
 // 1-4 queries through the int8 shadow (quant_topk, hdb_debug_quant_bounds).  ld_s: the score buffer's extent per query -- the
-// largest sample any k takes, so that calls that differ in k never regrow the workspace; pl_cap: entries of a list of row numbers
-// beside the score buffer (0: none -- what every caller passes since the pass over the 5-bit plane finishes the rows it keeps
-// itself; tests/ws_layout_check.hip still lays one, and the member goes when that check does); mflavour: the compact matrix and the score block of the matrix-core rescoring.
+// largest sample any k takes, so that calls that differ in k never regrow the workspace; pl_cap: 4-byte entries of a list beside
+// the score buffer (0: none) -- the upper bounds of the sampled rows, which the sample pass of a one-query call leaves for the pass
+// over the 5-bit plane (QuantArgs::pl_hi; one per sample slot, so the same extent as ld_s); mflavour: the compact matrix and the
+// score block of the matrix-core rescoring.
 struct QuantWs {
     float* qinv; float* qsq; int* qnan; int8_t* qcodes; float* qaux; float* thr; uint32_t* cnt; unsigned long long* cand; float* sbuf;
     uint32_t* pl_list;
