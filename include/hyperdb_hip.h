@@ -107,7 +107,10 @@ void hdb_index_destroy(hdb_index* ix);
 /* Opt-in int8 shadow of the matrix: quantized row scan with exact rescoring (local-hyperdb_amd/csrc/hdb_quant.hip).
  * HDB_QUANT_I8 builds, next to the float16 / float32 matrix, an owned int8 copy -- one code per element at a row pitch
  * P = round_up(d, 16) bytes -- and 12 bytes of per-row caches: N x (P + 12) bytes of device memory.  HDB_QUANT_NONE frees it.
- * float64, bfloat16 and float8 matrices return HDB_ERR_UNSUPPORTED.  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
+ * float64 and float8 matrices return HDB_ERR_UNSUPPORTED, and so does a bfloat16 matrix unless the option bf16_quant is set on the
+ * index (opt-in: then the call builds the same explicit shadow, codes, caches and 5-bit plane, from the two-byte rows; the calls it
+ * serves return the bits of the VALU scan, which is the default path of a bfloat16 index for 1-4 queries; a bfloat16 index never
+ * builds a shadow for itself, with or without the option).  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
  * hdb_index_gather moves codes and caches with the kept rows, hdb_index_update rebuilds it, hdb_index_rebase leaves it alone.
  *
  * The bound.  Row r: s_r = max_j |v_rj| / 127, c_rj = rne(v_rj / s_r), eps_r = v_r - s_r c_r; the query likewise (s_q, c_q,
@@ -263,6 +266,9 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     float32 queries), through the small, sampled, exact and full-sort pipelines, as separate launches.  hamming / jaccard calls
  *     of 1-4 queries may take their single launch (it reads the packed sign bits only).  Manhattan batches stay on the
  *     4-queries-per-pass scan (no LDS tile kernel).
+ *     On request (option bf16_quant = 1, then hdb_index_quantize(HDB_QUANT_I8)): 1-4 dot / cosine / euclidean queries with k <= 128
+ *     on a finite matrix of at least quant_min_n rows (-1: 1 000 000, measured) filter on the int8 shadow and rescore the candidates
+ *     from the bfloat16 rows with this scan's arithmetic -- the same indices and float32 score bits.
  *   - 5+ dot / cosine / euclidean / pearson queries on a FINITE matrix of d = 128, 256, 384 or 512 with use_mfma on: the matrix
  *     cores (hdb_mfma_bf16.hip), multi-kernel pipeline.  A float32 query travels as three bf16 parts that add up to it exactly,
  *     a row is one bf16: three v_mfma_f32_16x16x32_bf16 per k-step, every product exact, float32 accumulation.  A query element
@@ -409,6 +415,8 @@ void hdb_group_destroy(hdb_group* g);
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),
+ *   bf16_quant (0, the default: hdb_index_quantize(HDB_QUANT_I8) refuses a bfloat16 matrix; 1: it builds an explicit shadow; means
+ *   nothing on other dtypes),
  *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never), quant_batch_min_n (batches
  *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
  *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane),

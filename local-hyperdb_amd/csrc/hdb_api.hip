@@ -139,7 +139,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 104; }
+extern "C" int hdb_version(void) { return 105; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -260,9 +260,10 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
         ix->opt.auto_quant = 0;                            // dropped on request: the index does not build one for itself again
         return HDB_OK;
     }
-    if (ix->dtype == HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
+    // (bfloat16: on request only, option bf16_quant -- an explicit shadow with the VALU scan's bits, never an automatic one)
+    if (ix->dtype == HDB_BF16 && !ix->opt.bf16_quant) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype == HDB_F8E4M3) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: float8 (e4m3) matrices have no int8 shadow: one byte per element already");
-    if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
+    if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32 && ix->dtype != HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     HIP_TRY(qstat_alloc(ix, st));
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
     ix->plane_declined = false;
@@ -531,6 +532,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "bf16_ks_min_q")) ix->opt.bf16_ks_min_q = value;
     else if (!strcmp(name, "f8_ks_min_q")) ix->opt.f8_ks_min_q = value < 0 ? -1 : value;
     else if (!strcmp(name, "f8_lds_min_q")) ix->opt.f8_lds_min_q = value < 0 ? -1 : value;
+    else if (!strcmp(name, "bf16_quant")) ix->opt.bf16_quant = value ? 1 : 0;
     else if (!strcmp(name, "f8_lds_waves")) { if (value == 0 || value == 4 || value == 8) ix->opt.f8_lds_waves = value; }
     else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
     else if (!strcmp(name, "use_quant")) ix->opt.use_quant = value;

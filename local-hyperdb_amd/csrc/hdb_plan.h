@@ -28,6 +28,7 @@ struct hdb_options {
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
     int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
+    int64_t bf16_quant = 0;           // bfloat16 matrices: hdb_index_quantize(HDB_QUANT_I8) builds an explicit int8 shadow (0, the default: the call is refused; opt-in).  Means nothing on other types; the plan does not read it
     int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
     int64_t host_direct = 1;          // hdb_topk_host: kernels write a pinned host record themselves (no D2H copy)
@@ -138,8 +139,14 @@ static inline void sample_plan(int64_t n, int64_t sample_target, uint32_t kk, in
 
 // Smallest matrix that takes the int8 shadow when quant_min_n is -1 (measured): below it the extra launches
 // of the quantized pipeline cost more than the bytes it saves.
+// bfloat16 (the opt-in shadow, bf16_quant): the smallest measured n at d = 384 from which the shadow beats the same handle with
+// use_quant = 0 (the VALU scan) by at least 5 % in both of two runs, at that size and every larger one, for 1 and for 4 queries --
+// the criterion of HDB_PLANE_MIN_ROWS (profiles/bf16_quant_time.txt, tools/time_bf16_quant.py; cosine top-100, p50 in us, VALU scan
+// -> shadow, both runs): one query 500k 107 -> 108 / 105 -> 106 (0.99: no), 1M 165 -> 136 / 164 -> 133 (1.22x / 1.23x), 1.25M 1.31x /
+// 1.34x, 2M (plane) 1.69x / 1.67x, 10M 1 222 -> 541 / 1 223 -> 527 (2.26x / 2.32x); four queries 500k 1.33x / 1.37x, 1M 1.69x / 1.77x,
+// 10M 2 058 -> 738 / 2 028 -> 736 (2.79x / 2.75x).  It lies below fp16's because the bf16 default is the VALU scan, not the matrix cores.
 static inline int64_t quant_min_rows(int dtype) {
-    return dtype == HDB_F16 ? 1250000 : 500000;
+    return dtype == HDB_F16 ? 1250000 : dtype == HDB_BF16 ? 1000000 : 500000;
 }
 
 // ... and the smallest fp16 matrix that builds a shadow for itself (auto_quant; measured, profiles/auto_quant_time.txt, DESIGN.md
@@ -304,9 +311,11 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     if (o.force_exact && !small) exact = true;
     if (!small && (int64_t)kk * 32 > n) exact = true;        // k is a large share of the rows: a sampled threshold cannot help
     // the int8 shadow (hdb_index_quantize): 1-4 dot / cosine / euclidean queries on a finite float16 / float32 matrix; same answer
+    // (bfloat16 likewise: such an index holds a shadow only where its caller set bf16_quant and asked for one.  A bfloat16 call of
+    //  1-4 queries never reaches the matrix cores below, so a matrix that is not finite is still asked about once per plan.)
     if (ix.qmode == HDB_QUANT_I8 && !ix.qauto && o.use_quant && !exact && !small && c.has_status && nq >= 1 && nq <= 4 &&
         k <= o.quant_max_k && k <= 128 && (metric == HDB_DOT || metric == HDB_COSINE || metric == HDB_EUCLIDEAN) &&
-        (ix.dtype == HDB_F16 || ix.dtype == HDB_F32) && n >= (o.quant_min_n >= 0 ? o.quant_min_n : quant_min_rows(ix.dtype))) {
+        (ix.dtype == HDB_F16 || ix.dtype == HDB_F32 || ix.dtype == HDB_BF16) && n >= (o.quant_min_n >= 0 ? o.quant_min_n : quant_min_rows(ix.dtype))) {
         if (finite()) { plan_quant(p, ix, o, c, false); return p; }
     }
     // fp32 matrices: the VALU scan serves up to 4 queries in one pass at HBM speed; the fp32 MFMA scan (matrix-pipe

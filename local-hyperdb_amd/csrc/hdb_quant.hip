@@ -35,6 +35,17 @@
 // bounds are pushed outward by |s| 2^-20 + 1e-30 (many ulps) to cover that.  NaN never reaches a bound (finite matrix, finite
 // query; a NaN upper bound would count as +inf).
 //
+// ---- bfloat16 rows (opt-in: bf16_quant) ------------------------------------------------------------------------------------------
+// Nothing above depends on the element type of the matrix.  A bfloat16 element widens to float32 exactly (a shift), so v_rj is a
+// float32 number as for the other types; the row quantizer forms s_r, eps_r, ||v_r|| from the widened values in float64, and E_r
+// takes max(gamma, gamma_m) like every shadow.  The target is the float32 sum of the VALU scan, bound (2): hdb_scan_kernel /
+// hdb_scan_generic_kernel instantiated for hdb_bf16 run the same fma chain per lane and the same tree on the widened values (the
+// products of an 8-bit and a 24-bit significand are not exact in float32, as for float32 rows; (2) counts every rounding).  The
+// euclidean interval reads the float32 sqnorm cache, which hdb_rownorm_kernel<hdb_bf16> fills with the same chain and tree as for
+// the other types (squares of bfloat16 numbers are exact in float32: within gamma a fortiori).  The rescoring kernel's bfloat16
+// instantiation unpacks a 16-byte piece as hdb_scan.hip's hdb_unpack does -- even element the low half of its word, odd element the
+// high half -- so the lanes' partial sums are the scan's.  A default bfloat16 index answers 1-4 queries on that scan: the shadow
+// returns the default path's bits.
 //
 // ---- The matrix-core flavour (automatic shadow of an fp16 index, hdb_api.hip) --------------------------------------------
 // A default fp16 index answers 1-4-query calls on the matrix cores, so the shadow it builds for itself must return THOSE bits.
@@ -111,16 +122,24 @@ __device__ __forceinline__ float hq_up(double x) {
 }
 
 __device__ __forceinline__ float hq_f(__half v) { return __half2float(v); }
+__device__ __forceinline__ float hq_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 __device__ __forceinline__ float hq_f(float v) { return v; }
 
 template <typename T> struct HqElem;
 template <> struct HqElem<__half> { static constexpr int EPC = 8; };
+template <> struct HqElem<hdb_bf16> { static constexpr int EPC = 8; };
 template <> struct HqElem<float> { static constexpr int EPC = 4; };
 
 __device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[8], __half*) {
     const __half2* h = reinterpret_cast<const __half2*>(&raw);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { float2 f = __half22float2(h[i]); x[2 * i] = f.x; x[2 * i + 1] = f.y; }
+}
+// bfloat16 pairs in the order of hdb_scan.hip's hdb_unpack: the even element is the low half of its word, the odd one the high half
+__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[8], hdb_bf16*) {
+    const unsigned int w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(w[i] << 16); x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
 }
 __device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[4], float*) {
     x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
@@ -1066,8 +1085,11 @@ extern "C" int hdb_launch_quant_rows(const void* V, int64_t n, int d, int dtype,
     if (n <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = hdb_grid_for(n, 4, 8192);
+    // (every element type has an instantiation of its own: a type that is not built is an error, never another type's kernel)
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_quant_rows_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, P, codes, aux, nan_flag, gamma);
-    else hipLaunchKernelGGL(hdb_quant_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, P, codes, aux, nan_flag, gamma);
+    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_quant_rows_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, P, codes, aux, nan_flag, gamma);
+    else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_quant_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, P, codes, aux, nan_flag, gamma);
+    else return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
@@ -1192,9 +1214,14 @@ extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const f
     if (dtype == HDB_F16) {
         if (vec) { if (euc) HQ_RESCORE(__half, 1, true); else HQ_RESCORE(__half, 0, true); }
         else { if (euc) HQ_RESCORE(__half, 1, false); else HQ_RESCORE(__half, 0, false); }
-    } else {
+    } else if (dtype == HDB_BF16) {
+        if (vec) { if (euc) HQ_RESCORE(hdb_bf16, 1, true); else HQ_RESCORE(hdb_bf16, 0, true); }
+        else { if (euc) HQ_RESCORE(hdb_bf16, 1, false); else HQ_RESCORE(hdb_bf16, 0, false); }
+    } else if (dtype == HDB_F32) {
         if (vec) { if (euc) HQ_RESCORE(float, 1, true); else HQ_RESCORE(float, 0, true); }
         else { if (euc) HQ_RESCORE(float, 1, false); else HQ_RESCORE(float, 0, false); }
+    } else {
+        return (int)hipErrorInvalidValue;
     }
 #undef HQ_RESCORE
     return (int)hipGetLastError();

@@ -295,7 +295,12 @@ class GpuIndex:
         + 12) bytes of device memory.  A large fp16 index also builds a shadow for itself on its first 1-4-query dot / cosine
         call (option ``auto_quant``; that flavour returns the matrix cores' bits, i.e. exactly what the call returned before);
         ``quantize(None)`` drops either kind and switches the automatic build off for this handle, ``quantize("int8")`` keeps
-        the explicit meaning."""
+        the explicit meaning.
+
+        bfloat16: opt-in.  ``quantize("int8")`` raises NotImplementedError on a bf16 index unless ``set_option("bf16_quant", 1)``
+        came first; with it the shadow is built as for fp16 / fp32 (explicit only, never automatic) and the 1-4-query calls it
+        serves return the bits of the VALU scan -- the path a bf16 index takes for such calls by default.  ``register_vectors``
+        and ``HyperDB`` set the option themselves when they are given ``quantize="int8"``.  float8 and float64 raise."""
         mode = quant_mode(mode)
         with torch.cuda.device(self.device):
             _check(_lib.hdb_index_quantize(self._h, mode, _stream_ptr(self.device)), "hdb_index_quantize")
@@ -628,6 +633,15 @@ def quant_mode(mode):
     if mode not in QUANT_MODES:
         raise ValueError(f"quantize must be None or 'int8', got {mode!r}")
     return QUANT_MODES[mode]
+
+
+def request_shadow(index, mode):
+    """What a ``quantize=`` argument of an entry point (register_vectors, HyperDB) does with its GpuIndex or GpuGroup: the
+    caller asked for a shadow by name, so a bfloat16 index -- every shard of a group -- gets the option ``bf16_quant`` first
+    (without it hdb_index_quantize refuses bfloat16 matrices: GpuIndex.quantize).  Other dtypes: quantize(mode) and nothing else."""
+    if quant_mode(mode) != HDB_QUANT_NONE and index.dtype == HDB_BF16:
+        index.set_option("bf16_quant", 1)
+    index.quantize(mode)
 
 
 def packed_bytes(nq, k):

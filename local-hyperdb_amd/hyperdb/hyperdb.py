@@ -153,7 +153,7 @@ class HyperDB:
                 vectors = _native.to_f8(vectors)
             self._index = GpuGroup(vectors, self.devices) if self.devices else GpuIndex(vectors, device=self.device)
             if self.quantize is not None:             # (append / compact / update keep the shadow current from here on)
-                self._index.quantize(self.quantize)
+                _native.request_shadow(self._index, self.quantize)      # (fp_precision="bfloat16": sets bf16_quant first)
         else:
             self._index.append(vectors)
 

@@ -47,7 +47,7 @@ class ResidentVectors:
         _native.quant_mode(quantize)                     # (ValueError before anything is uploaded)
         self.index = GpuGroup(vectors, devices) if devices else GpuIndex(vectors, device=device)
         if quantize is not None:
-            self.index.quantize(quantize)
+            _native.request_shadow(self.index, quantize)     # (a bfloat16 matrix: sets bf16_quant first)
         arr_dtype = vectors.dtype if hasattr(vectors, "dtype") else None
         self.np_dtype = _np_dtype_of(arr_dtype, self.index)
 
