@@ -421,12 +421,14 @@ void hdb_group_destroy(hdb_group* g);
  *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
  *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane),
  *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; kept rows beyond which a call counts in plane_overflows -- a
- *   statistic: no call is answered differently for it).
+ *   statistic: no call is answered differently for it), plane_wg_per_cu (workgroups per CU of the pass over the plane: 0 the
+ *   measured table, 1 .. 8 that many -- for A/B runs, no call is answered differently for it).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
  *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
- *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows. */
+ *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows, plane_blocks (workgroups of the last call's
+ *   pass over the plane, 0 when it did not take it). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

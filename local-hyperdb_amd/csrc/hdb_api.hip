@@ -139,7 +139,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 105; }
+extern "C" int hdb_version(void) { return 106; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -544,6 +544,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "use_plane")) ix->opt.use_plane = value;
     else if (!strcmp(name, "plane_min_n")) ix->opt.plane_min_n = value;
     else if (!strcmp(name, "plane_cap_rows")) ix->opt.plane_cap_rows = std::max<int64_t>(0, value);
+    else if (!strcmp(name, "plane_wg_per_cu")) ix->opt.plane_wg_per_cu = std::max<int64_t>(0, std::min<int64_t>(value, 8));
     else if (!strcmp(name, "use_subset")) ix->opt.use_subset = value;
     else if (!strcmp(name, "subset_min_n")) ix->opt.subset_min_n = value < 0 ? -1 : value;
     else if (!strcmp(name, "subset_ratio")) ix->opt.subset_ratio = value < 0 ? -1 : std::max<int64_t>(1, value);
@@ -571,6 +572,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
     else if (!strcmp(name, "plane")) *value = ix->st.plane;
+    else if (!strcmp(name, "plane_blocks")) *value = ix->st.plane_blocks;      // workgroups of the last call's plane pass (0: it did not take the plane)
     else if (!strcmp(name, "subset")) *value = ix->st.subset;
     else if (!strcmp(name, "subset_rows")) *value = ix->subset_m;
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
@@ -864,7 +866,7 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
         a.pl_cnt = pl_cnt; a.pl_cap = p.pl_cap;
         a.pl_s_tiles = (uint32_t)sp.s_tiles; a.pl_s_stride = (uint32_t)sp.s_stride;      // ... and walks the other tiles
-        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, (int)ix->opt.max_blocks, st));
+        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, p.pl_blocks, st));      // (the grid is the plan's: stat plane_blocks)
     } else {
         LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->opt.max_blocks, st));
     }
@@ -904,7 +906,7 @@ extern "C" int hdb_debug_quant_bounds(hdb_index* ix, const float* dev_q, int met
     a.dbg = dev_hi;
     LAUNCH_TRY(hdb_launch_quant_scan_one(&a, 2, (int)ix->opt.max_blocks, st));
     a.dbg = dev_hi5;
-    LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 1, (int)ix->opt.max_blocks, st));
+    LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 1, hdb_quant_plane_dbg_blocks(a.ntiles, (int)ix->opt.max_blocks), st));
     return HDB_OK;
 }
 

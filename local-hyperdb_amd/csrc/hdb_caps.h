@@ -318,6 +318,43 @@ static inline int hdb_l1_tile_supported(int dtype, int d) {
 static inline int hdb_quant_scan_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for(ntiles, 4, max_blocks > 0 ? max_blocks : 1024); }
 // The 5-bit plane: units of a row
 static inline int hdb_quant_plane_units(int P) { return (P + 31) / 32; }
+// ... and 16-byte pieces a lane takes of a tile: the J of hdb_quant_plane_scan_kernel<J, DBG> (1 .. 4 for rows of up to 512 elements)
+static constexpr int hdb_quant_plane_j(int U) { return (U + 3) / 4; }
+// The grid of the plane pass (hdb_quant_plane_scan_kernel<J, false>): workgroups of four waves, a wave takes two tiles per step, so
+// one workgroup per four step-pairs of the `nwalk` tiles it walks, at most wg_per_cu per CU.  Every workgroup of the grid is resident
+// while wg_per_cu does not exceed the waves per SIMD the kernel is compiled for (four waves of a workgroup: one per SIMD), and the
+// static split of the walk is balanced only then.  HDB_PLANE_WAVES: what the compiler gives <J, false>, J = 1 .. 4
+// (profiles/plane_occupancy_kernel_resources.txt; the figures move with the compiler, and so must this line).
+// HDB_PLANE_WG_PER_CU: the default per J.  An entry moves off 4 (the grid the pass had on 256 CUs) only where another grid won in
+// both of two runs at every measured size from 2M rows up (profiles/plane_occupancy_time.txt, DESIGN.md section 4, "The 5-bit
+// plane"; tools/time_quant.py --auto --plane-grid, one handle, the settings alternating call by call, p50 of a call in us, run 1 /
+// run 2).  More waves than four per SIMD bought nothing at any width; FEWER win where a wave has three or four pieces in flight:
+//   J = 3 (d = 384), 3 against 4: 2M 141.6 / 141.3 vs 143.1 / 143.2, 2.5M 167.6 / 168.3 vs 170.8 / 170.3, 3M 189.4 / 188.5 vs 191.4 /
+//     190.7, 5M 274.7 / 274.6 vs 279.5 / 279.0, 10M 464.1 / 481.8 vs 481.3 / 493.5 (2 loses: 487.7 / 496.9; 5 .. 7: 482.6 .. 505.6)   -> 3
+//   J = 4 (d = 512), 2 against 4: 2M 181.3 / 181.2 vs 184.4 / 184.5, 3M 239.7 / 239.2 vs 245.5 / 245.9, 10M 597.9 / 596.7 vs 622.2 /
+//     621.9 (3: 614.4 / 615.9; 5: 626.4 / 618.9; 1 was not measured)                                                            -> 2
+//   J = 2 (d = 256): 3 wins at 10M (344.0 / 343.4 vs 347.8 / 349.0) and loses at 2M (115.3 / 115.6 vs 114.4 / 114.8); 6 and 8 lose  -> 4
+//   J = 1 (d = 128): 5 .. 7 win at 5M and 10M (10M: 223.8 / 223.3 vs 235.5 / 236.1) and do not at 2M (90.2 / 90.3 vs 89.8 / 90.0)      -> 4
+// The option plane_wg_per_cu (1 .. 8) puts any value in the table's place for A/B runs -- more than the compiled waves only queues
+// workgroups behind the resident ones.
+#define HDB_PLANE_WAVES {8, 8, 7, 5}
+#define HDB_PLANE_WG_PER_CU {4, 4, 3, 2}
+static constexpr int hdb_quant_plane_waves(int J) { constexpr int t[4] = HDB_PLANE_WAVES; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
+static constexpr int hdb_quant_plane_wg_per_cu(int J) { constexpr int t[4] = HDB_PLANE_WG_PER_CU; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
+static_assert(hdb_quant_plane_wg_per_cu(1) >= 1 && hdb_quant_plane_wg_per_cu(1) <= hdb_quant_plane_waves(1) &&
+              hdb_quant_plane_wg_per_cu(2) >= 1 && hdb_quant_plane_wg_per_cu(2) <= hdb_quant_plane_waves(2) &&
+              hdb_quant_plane_wg_per_cu(3) >= 1 && hdb_quant_plane_wg_per_cu(3) <= hdb_quant_plane_waves(3) &&
+              hdb_quant_plane_wg_per_cu(4) >= 1 && hdb_quant_plane_wg_per_cu(4) <= hdb_quant_plane_waves(4),
+              "a default grid of the plane pass asks for more waves per SIMD than its kernel is compiled for");
+// wg_per_cu: 0 = the table, 1 .. 8 = that many; max_blocks > 0 caps the result as it caps every grid
+static inline int hdb_quant_plane_blocks(int64_t nwalk, int J, int cus, int wg_per_cu, int max_blocks) {
+    const int per_cu = wg_per_cu >= 1 ? (wg_per_cu < 8 ? wg_per_cu : 8) : hdb_quant_plane_wg_per_cu(J);
+    int64_t limit = (int64_t)per_cu * (cus > 0 ? cus : 1);
+    if (max_blocks > 0 && max_blocks < limit) limit = max_blocks;
+    return hdb_grid_for((nwalk + 1) / 2, 4, (int)limit);
+}
+// ... and of the test entry (DBG: every tile, no list): the 1024 workgroups the pass had before its grid followed the device
+static inline int hdb_quant_plane_dbg_blocks(int64_t ntiles, int max_blocks) { return hdb_grid_for((ntiles + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024); }
 // The plane pass of a one-query call does not stream the tiles the sample pass evaluated (it takes their upper bounds from the
 // list that pass left, QuantArgs::pl_hi): it walks a dense index t' over the OTHER tiles.  The sample takes one tile of each
 // window w < s_tiles of `stride` tiles, hdb_tile_index(w, stride); the tiles from s_tiles x stride on (the ragged last one among

@@ -135,7 +135,7 @@ int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, 
                              int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
 int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
                                 float* rec, void* stream);
-int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream);
+int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int blocks, void* stream);
 int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,

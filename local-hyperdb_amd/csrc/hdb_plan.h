@@ -57,6 +57,7 @@ struct hdb_options {
     int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
     int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
     int64_t plane_cap_rows = 0;       // ... kept rows beyond which a call counts in the stat plane_overflows (0: n / 8); changes no answer
+    int64_t plane_wg_per_cu = 0;      // ... workgroups per CU of its pass: 0 = the measured table (HDB_PLANE_WG_PER_CU, hdb_caps.h), 1 .. 8 = fixed (A/B runs); changes no answer
     int64_t use_subset = 1;           // a row list beside the mask (hdb_index_set_row_subset): score only the listed rows where the rule says so (0: never -- the mask)
     int64_t subset_min_n = -1;        // ... on matrices of at least this many rows (-1: the measured rule, HDB_SUBSET_MIN_ROWS)
     int64_t subset_ratio = -1;        // ... while m * ceil(nq / 4) * subset_ratio <= n (-1: the measured rule, HDB_SUBSET_RATIO; else an integer >= 1)
@@ -87,7 +88,7 @@ enum TopkPath {
     HDB_PATH_PIPELINE                 // the multi-kernel pipeline: small, sampled or exact
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
-struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0; };
+struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0; };
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
@@ -108,6 +109,7 @@ struct TopkPlan {
     bool mflavour = false, build_needed = false, plane_wanted = false;
     bool qb_int8 = false;                               // batches: the int8 matrix-core filter (0: the v_dot4 scan, four queries per pass)
     int P = 0, nsub = 0; uint32_t pl_cap = 0;           // pl_cap: rows the plane may keep before the call counts in plane_overflows
+    int pl_blocks = 0;                                  // workgroups of the plane pass (hdb_quant_plane_blocks), 0: the call does not take the plane
     QuantSample qs = {0, 1, 0, 0};
     TopkStats stats;
     bool shadow() const { return path == HDB_PATH_QUANT || path == HDB_PATH_QUANT_BATCH; }
@@ -202,6 +204,10 @@ static inline void plan_quant(TopkPlan& p, const TopkFacts& ix, const hdb_option
     p.plane_wanted = c.nq == 1 && (c.metric == HDB_DOT || c.metric == HDB_COSINE) && plane_wanted(ix.d, o) && !ix.plane_declined &&
                      ix.n >= (o.plane_min_n >= 0 ? o.plane_min_n : (int64_t)HDB_PLANE_MIN_ROWS);
     p.pl_cap = plane_list_cap(o, ix.n);
+    // the plane pass walks the tiles the sample did not take; its grid follows the device and the measured table (hdb_caps.h)
+    if (p.plane_wanted)
+        p.pl_blocks = hdb_quant_plane_blocks((ix.n + 15) / 16 - p.qs.s_tiles, hdb_quant_plane_j(hdb_quant_plane_units(p.P)), ix.cus,
+                                             (int)o.plane_wg_per_cu, (int)o.max_blocks);
     if (mflavour) {
         // the threshold folded into the two passes (QuantArgs::nsub) while the sample's grid has at least the 1024 subsets
         // hdb_sample_thr_kernel works with; smaller samples keep that kernel
@@ -209,6 +215,7 @@ static inline void plan_quant(TopkPlan& p, const TopkFacts& ix, const hdb_option
         if (p.nsub < 1024 || p.nsub > HDB_QUANT_NSUB_MAX) p.nsub = 0;
     }
     p.stats.quant = 1; p.stats.path = 1; p.stats.mfma = mflavour ? 1 : 0; p.stats.plane = p.plane_wanted ? 1 : 0;
+    p.stats.plane_blocks = p.pl_blocks;
     p.stats.sample_rows = p.qs.s_rows; p.stats.sample_m = 16; p.stats.chunks = 1;
 }
 // batches of 5+ queries through the automatic shadow (quant_batch_topk): chunks of up to 256 queries

@@ -728,7 +728,10 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
 // that found it.
 // A wave takes two 16-row tiles per step.  A tile of the nibble plane is 16 U contiguous 16-byte pieces and lane l takes pieces
 // l + 64 j, j < J = ceil(U / 4), i.e. whole-wave contiguous loads with every lane busy (U = 12 at d = 384: exactly 3 per lane); piece
-// f belongs to row f / U, unit f % U -- the same for every tile, so a lane keeps the query words of its J units in registers.
+// f belongs to row f / U, unit f % U -- the same for every tile, so a lane keeps one LDS offset per j and reads the eight query words
+// of a unit from qs as it decodes that piece (the words themselves, 8 J registers held through the loop, cost J = 3 two waves per
+// SIMD and J = 2, 4 one: profiles/plane_occupancy_kernel_resources.txt; the pass is no slower for the LDS reads at any grid and needs
+// no reload after a drain: profiles/plane_occupancy_time.txt, "Attribution").
 // The per-piece sums meet in LDS (wave-private), lanes 0-31 add the U pieces of one row each and evaluate the bound.
 // Survivors wait in a wave-private queue of row numbers (LDS; appended by ballot and popcount, no atomics).  Once it holds 16 the wave
 // takes 16 of them as one MODE 1 tile -- 16 lanes per 4 rows, hq_rows4_bounds with the row numbers from the queue -- and emits the
@@ -766,18 +769,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (the tile number stays scalar)
     const int npieces = 16 * U;
-    int qw[J][8];
-    auto load_qw = [&]() {
+    // where the query words of piece lane + 64 j lie in qs: the decode reads them there, piece by piece, and holds one offset per j
+    int qoff[J];
 #pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int f = lane + 64 * j;
-            const int unit = f < npieces ? f % U : 0;
-            const int4 x = qs[2 * unit], y = qs[2 * unit + 1];
-            qw[j][0] = x.x; qw[j][1] = x.y; qw[j][2] = x.z; qw[j][3] = x.w;
-            qw[j][4] = y.x; qw[j][5] = y.y; qw[j][6] = y.z; qw[j][7] = y.w;
-        }
-    };
-    load_qw();
+    for (int j = 0; j < J; ++j) {
+        const int f = lane + 64 * j;
+        qoff[j] = f < npieces ? 2 * (f % U) : 0;
+    }
     const float absmin = 0x1p-100f * (float)(a.d + 8);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -853,10 +851,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             if (a.mask) masked = !a.mask[row];
         }
         __builtin_amdgcn_sched_barrier(0);               // loads ahead of every use
+        // piece j of both tiles against the eight query words of its unit, read from qs (two 16-byte LDS reads per j, in flight with
+        // nothing but themselves: the barrier keeps the words of the next j from being read, and held, ahead of their piece)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
+        for (int j = 0; j < J; ++j) {
+            const int4 x = qs[qoff[j]], y = qs[qoff[j] + 1];
+            const int qw[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
 #pragma unroll
-            for (int j = 0; j < J; ++j) {
+            for (int tt = 0; tt < 2; ++tt) {
                 const uint32_t bw = bv[tt][j];
                 const uint32_t w4[4] = {nv[tt][j].x, nv[tt][j].y, nv[tt][j].z, nv[tt][j].w};
                 int s = 0;
@@ -864,11 +866,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t lo = ((w4[i] << 1) & 0x1E1E1E1Eu) | ((bw >> (2 * i)) & 0x01010101u);
                     const uint32_t hi = ((w4[i] >> 3) & 0x1E1E1E1Eu) | ((bw >> (2 * i + 1)) & 0x01010101u);
-                    s = __builtin_amdgcn_sdot4((int)lo, qw[j][2 * i], s, false);
-                    s = __builtin_amdgcn_sdot4((int)hi, qw[j][2 * i + 1], s, false);
+                    s = __builtin_amdgcn_sdot4((int)lo, qw[2 * i], s, false);
+                    s = __builtin_amdgcn_sdot4((int)hi, qw[2 * i + 1], s, false);
                 }
                 part[wave][tt][lane + 64 * j] = s;
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -919,9 +922,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             do { qn -= 16; drain(qn, 16); } while (qn >= 16);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();             // (the next append stays behind the drain's loads)
-            // the query words are not held through a drain (its tile needs the registers): read them again
-            asm volatile("" ::: "memory");
-            load_qw();
         }
     }
     if (!DBG) {
@@ -1162,9 +1162,12 @@ extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux
     return (int)hipGetLastError();
 }
 // dbg = false: pass 1 (candidates of the rows the plane keeps; the threshold as MODE 1 takes it, folded or a.thr); dbg = true: hi5 of every row -> a.dbg (tests)
-extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int max_blocks, void* stream) {
+// blocks: the grid, from the plan (hdb_quant_plane_blocks; dbg: hdb_quant_plane_dbg_blocks).  Any count gives the same candidates --
+// only gridDim.x enters the kernel, as the walk's step and the list phase's stride.
+extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int blocks, void* stream) {
     const QuantArgs& a = *args;
     const int U = a.pl_units;
+    if (blocks < 1 || blocks > (1 << 22)) return (int)hipErrorInvalidValue;           // (blocks x 256 list slots per round fit 32 bits)
     if (a.nq != 1 || U < 1 || U > 16 || U != hdb_quant_plane_units(a.P) || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
     if (!dbg && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
     if (!dbg && (!a.cnt || !a.cand || !a.pl_cnt || !hq_copy_args_ok(a))) return (int)hipErrorInvalidValue;
@@ -1172,10 +1175,8 @@ extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int m
     if (a.ntiles < 0 || a.ntiles > 0x10000000) return (int)hipErrorInvalidValue;      // (a row number has 32 bits: hdb_pack)
     if (!dbg && a.pl_s_tiles != 0u && (!a.pl_hi || a.pl_s_stride < 1u || (uint64_t)a.pl_s_tiles * a.pl_s_stride > (uint64_t)a.ntiles)) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)U * 32;
-    const int64_t nwalk = a.ntiles - (dbg ? 0 : (int64_t)a.pl_s_tiles);
-    const int blocks = hdb_grid_for((nwalk + 1) / 2, 4, max_blocks > 0 ? max_blocks : 1024);
     hipStream_t st = (hipStream_t)stream;
-    const int J = (U + 3) / 4;
+    const int J = hdb_quant_plane_j(U);
 #define HQ_PLANE(J_) do { if (dbg) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, true>), dim3(blocks), dim3(256), lds, st, a); \
                           else hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, false>), dim3(blocks), dim3(256), lds, st, a); } while (0)
     if (J == 1) HQ_PLANE(1); else if (J == 2) HQ_PLANE(2); else if (J == 3) HQ_PLANE(3); else HQ_PLANE(4);

@@ -1,0 +1,51 @@
+"""The grid of the plane pass (hdb_quant_plane_blocks and its table, csrc/hdb_caps.h) on the host.
+
+tests/plane_grid_check.hip, a stand-alone program with its own main built under AddressSanitizer and UBSan, checks the rule over
+n in {16, 17, 8193, 70001, 2 000 000, 10 000 000}, J = 1 .. 4, 1 / 64 / 256 CUs, plane_wg_per_cu = 0 .. 8 and max_blocks in {0, 1, 3, 5000}:
+1 <= workgroups <= the cap, never more than the work, the max_blocks cap, the default equal to the table, no table entry above the
+waves per SIMD its kernel is compiled for, and -- with hdb_plane_skip_* -- that the walk at every such grid still visits the complement
+of the sample exactly once.  This file restates the rule in Python (plane_blocks; tests/test_plane_occupancy.py compares the stat
+plane_blocks with it) and pins the restatement's table against the one the program prints.
+No GPU call, nothing loaded into Python."""
+import os
+import re
+import subprocess
+
+from test_plane_skip_plan import CSRC, ROOT, _hipcc
+
+
+def wg_table():
+    """HDB_PLANE_WG_PER_CU as the header states it: the default workgroups per CU for J = 1 .. 4"""
+    text = open(os.path.join(CSRC, "hdb_caps.h")).read()
+    m = re.search(r"^#define HDB_PLANE_WG_PER_CU \{(\d+), (\d+), (\d+), (\d+)\}$", text, re.M)
+    assert m, "hdb_caps.h: HDB_PLANE_WG_PER_CU not found"
+    return [int(x) for x in m.groups()]
+
+
+def plane_blocks(nwalk, wg_per_cu, cus, max_blocks):
+    """hdb_quant_plane_blocks with the workgroups per CU already chosen (1 .. 8)"""
+    limit = wg_per_cu * max(cus, 1)
+    if 0 < max_blocks < limit:
+        limit = max_blocks
+    return max(1, min(((nwalk + 1) // 2 + 3) // 4, limit))
+
+
+def test_the_rule_and_the_walk_at_its_grids(tmp_path):
+    exe = str(tmp_path / "plane_grid_check")
+    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
+                            os.path.join(ROOT, "tests", "plane_grid_check.hip"), "-o", exe],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stdout + build.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    run = subprocess.run([exe], capture_output=True, text=True, env=env)
+    print(run.stdout)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    assert "rules 2592\n" in run.stdout, "6 sizes, 4 widths, 3 devices, 9 settings of plane_wg_per_cu, 4 of max_blocks"
+    table = [tuple(int(x) for x in line.split()[1:]) for line in run.stdout.splitlines() if line.startswith("table ")]
+    assert [j for j, _, _ in table] == [1, 2, 3, 4] and [wg for _, wg, _ in table] == wg_table()
+    for j, wg, waves in table:
+        assert 1 <= wg <= waves <= 8, f"J = {j}: {wg} workgroups per CU, {waves} waves per SIMD compiled"
+    walks = int(next(line.split()[1] for line in run.stdout.splitlines() if line.startswith("walks ")))
+    assert walks >= 6 * 4 * 3, "every size and width is walked at several grids"

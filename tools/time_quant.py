@@ -14,6 +14,9 @@ shadow WITHOUT the 5-bit plane (use_plane = 0); one-query shapes get two more co
 0) and the rows its first pass kept (plane_survivors), all columns interleaved in one process on one index.  The plane's row rule
 (HDB_PLANE_MIN_ROWS, hdb_api.hip) cites that table, profiles/quant_plane_time.txt.
 
+--auto --plane-grid [--rows ...] [--dims ...] [--wg 4 5 6 7] times the one-query call behind the plane at several grids of its pass
+(option plane_wg_per_cu; plane_grid_table below); the table HDB_PLANE_WG_PER_CU (hdb_caps.h) cites it, profiles/plane_occupancy_time.txt.
+
 --auto --batch [--rows ...] [--dims ...] [--queries ...] times batches of 5+ queries through the automatic shadow (batch_table
 below); the row rule of batches (quant_batch_rule, hdb_api.hip) cites that table, profiles/quant_batch_time.txt.
 """
@@ -112,8 +115,64 @@ def batch_table(args):
             torch.cuda.empty_cache()
 
 
+def plane_grid_table(args):
+    """--auto --plane-grid [--rows ...] [--dims ...] [--wg 4 5 6 7]: the one-query call behind the 5-bit plane at several grids of its
+    pass (option plane_wg_per_cu, workgroups per CU; 0 = the table of hdb_caps.h).  Per (rows, d): one matrix, one index, one
+    process; the settings alternate call by call.  Per setting: p50 of --reps calls (wall, us) and p50 of the plane pass alone (us,
+    HIP events around its launch: option profile, stat scan_time_ns -- taken in calls of their own, the events cost the call a few
+    us), the workgroups of the pass (plane_blocks).  same: every setting returned the indices and score bits of the first and kept
+    the same rows (plane_survivors, quant_cands).  HDB_PLANE_WG_PER_CU (hdb_caps.h) cites this table,
+    profiles/plane_occupancy_time.txt."""
+    g = torch.Generator(device="cuda").manual_seed(5)
+    print(f"{'rows':>10s} {'d':>4s} " + " ".join(f"{'wg ' + str(w) + ': call / pass us (blocks)':>34s}" for w in args.wg) + "  same", flush=True)
+    for d in args.dims:
+        for n in args.rows:
+            V = torch.randn((n, d), generator=g, device="cuda", dtype=torch.float32).to(torch.float16)
+            h = ranking.register_vectors(V)
+            ix = h.index
+            ix.set_option("quant_min_n", 0)
+            ix.set_option("plane_min_n", 0)
+            Q = np.random.default_rng(n + 1).standard_normal((1, d)).astype(np.float32)
+            k = 100
+
+            def run(w):
+                ix.set_option("plane_wg_per_cu", w)
+                return call(h, Q, k)
+
+            first, same, blocks = None, True, {}
+            for w in args.wg:
+                r = flat(run(w))
+                same = same and ix.stat("quant") == 1 and ix.stat("plane") == 1
+                blocks[w] = ix.stat("plane_blocks")
+                kept = (ix.stat("plane_survivors"), ix.stat("quant_cands"))
+                if first is None:
+                    first = (r, kept)
+                same = same and kept == first[1] and all(np.array_equal(x, y) for x, y in zip(r, first[0]))
+            for _ in range(5):
+                for w in args.wg:
+                    run(w)
+            tc = {w: [] for w in args.wg}
+            tp = {w: [] for w in args.wg}
+            for _ in range(args.reps):
+                for w in args.wg:
+                    t0 = time.perf_counter(); run(w); tc[w].append(time.perf_counter() - t0)
+            for _ in range(args.reps):
+                for w in args.wg:
+                    ix.set_option("profile", 1)
+                    run(w)
+                    tp[w].append(ix.stat("scan_time_ns") * 1e-3)
+            ix.set_option("profile", 0)
+            print(f"{n:10d} {d:4d} " + " ".join(f"{np.median(tc[w]) * 1e6:15.1f} / {np.median(tp[w]):7.1f} ({blocks[w]:5d})" for w in args.wg)
+                  + f"  {same}", flush=True)
+            h.close()
+            del V, h, ix
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--plane-grid", action="store_true", help="with --auto: the plane pass at several grids (plane_wg_per_cu)")
+    ap.add_argument("--wg", type=int, nargs="+", default=[4, 5, 6, 7], help="with --plane-grid: the workgroups per CU to compare")
     ap.add_argument("--batch", action="store_true", help="with --auto: batches of 5+ queries (parent path, int8 matrix cores, v_dot4 scan)")
     ap.add_argument("--rows", type=int, nargs="+", default=[2_000_000, 5_000_000, 10_000_000])
     ap.add_argument("--dims", type=int, nargs="+", default=[128, 384, 512])
@@ -125,6 +184,8 @@ def main():
     args = ap.parse_args()
     if args.batch:
         return batch_table(args)
+    if args.plane_grid:
+        return plane_grid_table(args)
     g = torch.Generator(device="cuda").manual_seed(5)
     print(f"{'dtype':8s} {'rows':>10s} {'d':>4s} {'nq':>3s} {'plain us':>9s} {'int8 us':>9s} {'speed-up':>8s} {'cands':>6s} same"
           + ("  first call ms  plane us  vs int8  survivors" if args.auto else ""), flush=True)
