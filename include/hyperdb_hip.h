@@ -31,8 +31,10 @@ typedef struct hdb_index hdb_index;
 /* dtype of the stored matrix: HyperDB(fp_precision=...) accepts float16/32/64 (hyperdb.py:65-66); bfloat16 (the upper 16 bits of
  * a float32, 2 bytes per element) is this library's addition for embedding models that emit it, and so is OCP float8 e4m3
  * (torch.float8_e4m3fn: 1 sign, 4 exponent, 3 mantissa bits, bias 7, no infinities, 0x7F / 0xFF = NaN; one byte per element).
- * Code 4 is unassigned and refused by hdb_index_create, like every other value not listed here. */
-enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5 };
+ * HDB_I8 = 7 is a matrix of signed 8-bit integers (np.int8 / torch.int8, two's complement, one byte per element): the integers ARE
+ * the matrix -- no scale, no zero point, no NaN code, every value in [-128, 127] widens to float32 exactly.
+ * Codes 4 and 6 are unassigned and refused by hdb_index_create, like every other value not listed here. */
+enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5, HDB_I8 = 7 };
 
 /* metric strings of hyperDB_ranking_algorithm_sort's dispatch table (ranking_algorithm.py:155-163). */
 enum hdb_metric {
@@ -107,7 +109,7 @@ void hdb_index_destroy(hdb_index* ix);
 /* Opt-in int8 shadow of the matrix: quantized row scan with exact rescoring (local-hyperdb_amd/csrc/hdb_quant.hip).
  * HDB_QUANT_I8 builds, next to the float16 / float32 matrix, an owned int8 copy -- one code per element at a row pitch
  * P = round_up(d, 16) bytes -- and 12 bytes of per-row caches: N x (P + 12) bytes of device memory.  HDB_QUANT_NONE frees it.
- * float64 and float8 matrices return HDB_ERR_UNSUPPORTED, and so does a bfloat16 matrix unless the option bf16_quant is set on the
+ * float64, float8 and int8 matrices return HDB_ERR_UNSUPPORTED, and so does a bfloat16 matrix unless the option bf16_quant is set on the
  * index (opt-in: then the call builds the same explicit shadow, codes, caches and 5-bit plane, from the two-byte rows; the calls it
  * serves return the bits of the VALU scan, which is the default path of a bfloat16 index for 1-4 queries; a bfloat16 index never
  * builds a shadow for itself, with or without the option).  The shadow follows the matrix: hdb_index_extend quantizes the appended rows,
@@ -240,7 +242,7 @@ int hdb_index_set_row_subset(hdb_index* ix, const uint8_t* dev_mask, const int64
 
 /* Full score vector of one query: the per-metric functions dot_product / cosine_similarity /
  * euclidean_metric / hamming_distance (... :24,:32,:44,:128).  dev_q: d elements, float32 for
- * F16/F32/BF16/F8E4M3 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
+ * F16/F32/BF16/F8E4M3/I8 matrices, float64 for F64 matrices.  dev_out: n floats.  The bias is NOT added. */
 int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, void* stream);
 
 /* Top-k of nq independent queries: metric scoring + NaN->-inf + bias + argpartition/argsort of
@@ -323,7 +325,22 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     and its 5-bit plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED, auto_quant does not apply: one byte per element already
  *     is the shadow's stream); K slices for wider rows unless f8_ks_min_q asks for them.
  * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch); f8_lds = 1 when the last call's
- * matrix-core launches expanded the rows in LDS; f8_lds_min_q = the threshold in force for this index, 0 = never. */
+ * matrix-core launches expanded the rows in LDS; f8_lds_min_q = the threshold in force for this index, 0 = never.
+ * int8 matrices (HDB_I8).  Queries are float32.  Every stored integer widens to float32 exactly (one v_cvt_f32_i32 with a
+ * sign-extending byte select per element), all arithmetic is float32 on unrounded float32 queries, and the contract is the float32
+ * one: scores within 1e-5 of the reference's arithmetic on the widened matrix (hamming exact with the sign bit x > 0, jaccard 1e-6).
+ * The matrix is always finite: hdb_index_has_nan is 0.  An int8 index plans exactly like a float8 index of the same shape with
+ * f8_ks_min_q = 0 and f8_lds_min_q = 0:
+ *   - 1-4 queries, every metric, any d, any k, bias, row mask and row list, and every batch no other path takes: the VALU scan, four
+ *     queries per pass, through the small, sampled, exact and full-sort pipelines.  Rows of 256, 384 and 512 bytes take the float8
+ *     flavour's unrolled ONE-query kernels on its grid sized by bytes.  Manhattan batches stay on the 4-queries-per-pass scan.
+ *   - 5+ dot / cosine / euclidean / pearson queries, d = 128, 256, 384 or 512, use_mfma on: the matrix cores (hdb_mfma_i8.hip), the
+ *     float8 flavour's kernel with another row converter: eight signed bytes become eight bf16 in registers (exact: |x| <= 128 has
+ *     at most 8 significant bits), the query travels as three exact bf16 parts, same K walk and epilogue -- indices, score bits and
+ *     status words are those of a bfloat16 index over the widened matrix.  Other widths stay on the VALU scan.
+ *   - never: the single launches of the matrix-core paths, the manhattan tile kernel, K slices, the LDS flavour, the int8 shadow and
+ *     its plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED: one byte per element already).
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch). */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 

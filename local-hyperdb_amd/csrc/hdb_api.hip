@@ -139,7 +139,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 106; }
+extern "C" int hdb_version(void) { return 107; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -263,6 +263,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     // (bfloat16: on request only, option bf16_quant -- an explicit shadow with the VALU scan's bits, never an automatic one)
     if (ix->dtype == HDB_BF16 && !ix->opt.bf16_quant) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype == HDB_F8E4M3) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: float8 (e4m3) matrices have no int8 shadow: one byte per element already");
+    if (ix->dtype == HDB_I8) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: int8 matrices have no int8 shadow: one byte per element already");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32 && ix->dtype != HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     HIP_TRY(qstat_alloc(ix, st));
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
@@ -310,7 +311,7 @@ extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, i
     if (!out) return fail(HDB_ERR_ARG, "hdb_index_create: out is null");
     if (n < 0 || d <= 0) return fail(HDB_ERR_ARG, "hdb_index_create: need n >= 0 and d > 0");
     if (n > 0 && !dev_V) return fail(HDB_ERR_ARG, "hdb_index_create: matrix pointer is null");
-    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3");
+    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3 && dtype != HDB_I8) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3/i8");
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_create: at most 2^32-2 rows per shard");
     if ((int64_t)d * 8 > 60 * 1024) return fail(HDB_ERR_ARG, "hdb_index_create: d too large for the query LDS tile");
     HIP_TRY(hipSetDevice(device));

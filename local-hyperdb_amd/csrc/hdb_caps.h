@@ -15,8 +15,9 @@
 // the registers of the ONE-query kernels allow (88-124 per lane: 4 waves per SIMD) -- 1024 / 1024 / 768 workgroups, 64 / 96 / 96 KiB
 // in flight per CU.  The four-query kernel takes the same grid; its dot flavour (116-118 registers) is resident four times per CU as
 // well, its euclidean / manhattan flavours (154-162: 3 waves per SIMD) three times -- the fourth workgroup of a CU waits its turn.
+// int8 rows (HDB_I8) are the same bytes and take the same kernels' unrolled flavours, so the same grid.
 static inline int hdb_scan_auto_blocks(int dtype, int row_bytes, bool vec, bool wide_rows) {
-    if (dtype == HDB_F8E4M3 && vec && (row_bytes == 256 || row_bytes == 384 || row_bytes == 512)) {
+    if ((dtype == HDB_F8E4M3 || dtype == HDB_I8) && vec && (row_bytes == 256 || row_bytes == 384 || row_bytes == 512)) {
         const int b = 512 * 768 / row_bytes;
         return b < 1024 ? b : 1024;
     }
@@ -183,7 +184,7 @@ static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 ||
 static inline int mfma_exact_tile_rows(int dtype, int d) {
     if (dtype == HDB_BF16 && d > 0 && hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;     // 640 .. 4096: K slices of 16-row stages (hdb_mfma_bf16_ks.hip)
     if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
-    if (dtype == HDB_F8E4M3) return d > 0 ? hdb_mfma_f8_tile_rows(d) : 0;
+    if (dtype == HDB_F8E4M3 || dtype == HDB_I8) return d > 0 ? hdb_mfma_f8_tile_rows(d) : 0;      // (int8: the float8 kernel with another row converter, hdb_mfma_i8.hip)
     const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
     if (!elem || d <= 0) return 0;
     if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
@@ -214,7 +215,7 @@ static inline int hdb_mfma_tile_rows(int dtype, int d) {
 // queries ONE launch of the MFMA scan covers (grid.y == 1): what a single-launch (mode 2) call can take
 static inline int hdb_mfma_batch_capacity(int dtype, int d) {
     if (hdb_mfma_tile_rows(dtype, d) <= 0 || hdb_mfma_ksplit_slices(dtype, d) > 0 || hdb_mfma_anyd_pad(dtype, d) > 0) return 0;      // (K slices, odd widths: the multi-kernel pipeline)
-    if (dtype == HDB_BF16 || dtype == HDB_F8E4M3) return 0;             // (bfloat16 and float8 rows likewise: no single launch is built)
+    if (dtype == HDB_BF16 || dtype == HDB_F8E4M3 || dtype == HDB_I8) return 0;      // (bfloat16, float8 and int8 rows likewise: no single launch is built)
     if (dtype == HDB_F32) return (d == 512 || d == 768) ? 64 : 128;      // (d = 512 / 768: the bf16-part flavour pairs its waves over K, hdb_mfma_kernel.h KP)
     return (d == 384 || d == 128 || d == 256 || d == 512 || d == 640) ? 256 : 128;      // two query tiles per wave (hdb_mfma_qt2.hip)
 }

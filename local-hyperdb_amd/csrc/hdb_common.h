@@ -8,9 +8,9 @@
 
 // ---- element types -------------------------------------------------------------------------------
 // Bytes of one stored matrix element per hdb_dtype (include/hyperdb_hip.h: 0 float16, 1 float32, 2 float64, 3 bfloat16, 5 float8
-// e4m3; 4 is unassigned); 0 = no such dtype.  Every row pitch in the library comes from here.
+// e4m3, 7 int8; 4 and 6 are unassigned); 0 = no such dtype.  Every row pitch in the library comes from here.
 __host__ __device__ __forceinline__ int hdb_elem_bytes(int dtype) {
-    return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : dtype == 5 ? 1 : 0;
+    return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : (dtype == 5 || dtype == 7) ? 1 : 0;
 }
 // A bfloat16 as it lies in memory: the upper 16 bits of the float32 of the same value, so widening is a shift and exact.
 struct hdb_bf16 { unsigned short bits; };
@@ -32,6 +32,21 @@ __host__ __device__ __forceinline__ float hdb_f8_to_f(hdb_f8 v) {
     else if (mag < 8u) r = (float)mag * 0.001953125f;                                       // 2^-9
     else r = __builtin_bit_cast(float, mag << 20) * __builtin_bit_cast(float, 0x7B800000u);  // x 2^120
     return __builtin_bit_cast(float, __builtin_bit_cast(unsigned int, r) | sgn);
+}
+
+// A signed 8-bit integer as it lies in memory (np.int8 / torch.int8, two's complement): the integers are the matrix, no scale and
+// no NaN code.  |x| <= 128 has at most 8 significant bits, so the float32 widening is exact AND its upper 16 bits -- a bfloat16 --
+// carry the whole value (the low 16 are zero).  Plain arithmetic, so host code (tests) computes the same values; the device scans
+// convert with one v_cvt_f32_i32 per element, the byte picked and sign-extended by the instruction's operand select (hdb_i8_cvt).
+struct hdb_i8 { signed char v; };
+__host__ __device__ __forceinline__ float hdb_i8_to_f(hdb_i8 x) { return (float)(int)x.v; }
+// byte B of word w, sign-extended and converted.  Written as a shift, a narrowing and a conversion: hipcc folds the three into ONE
+// instruction, v_cvt_f32_i32_sdwa v, sext(w) src0_sel:BYTE_B (the scan kernels' disassembly shows 16 of them per 16-byte load and
+// no v_bfe_i32 / v_ashrrev; DESIGN.md, "int8 matrices") -- float8 pays half an instruction per element with v_cvt_pk_f32_fp8
+template <int B>
+__host__ __device__ __forceinline__ float hdb_i8_cvt(int w) {
+    static_assert(B >= 0 && B < 4, "byte of a word");
+    return (float)(int)(signed char)((unsigned int)w >> (8 * B));
 }
 
 // ---- candidate / selection geometry -------------------------------------------------------

@@ -93,6 +93,11 @@ int hdb_launch_mfma_scan_f8(const ScanArgs* args, int mode, int nq_launch, const
                             const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_scan_f8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                  const float* qsq, int blocks, void* stream);
+// int8 rows: the float8 kernel with the int8 row converter (hdb_mfma_i8.hip)
+int hdb_launch_mfma_scan_i8(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                            const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_i8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                 const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                            const float* qsq, const float* qscl, int blocks, void* stream);
 int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,

@@ -48,6 +48,7 @@ __device__ __forceinline__ float hdb_row_f(_Float16 v) { return (float)v; }
 __device__ __forceinline__ float hdb_row_f(float v) { return v; }
 __device__ __forceinline__ float hdb_row_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 __device__ __forceinline__ float hdb_row_f(hdb_f8 v) { return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0); }
+__device__ __forceinline__ float hdb_row_f(hdb_i8 v) { return hdb_i8_to_f(v); }
 template <typename T, bool HAS_BIAS>
 __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long long* cand, const uint32_t* cnt, uint32_t cap,
                                                                  const T* V, int d, const float* Q, const float* qsq, int q0,
@@ -127,6 +128,12 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
         if (ks8) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
         return hdb_launch_mfma_scan_f8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
     }
+    if (dtype == HDB_I8) {              // int8 rows (hdb_mfma_i8.hip): the float8 register kernel with another row converter, and its grid
+        if (mode == 2) return (int)hipErrorNotSupported;
+        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
+        const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
+        return hdb_launch_mfma_scan_i8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
+    }
     if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);
     if (dtype != HDB_F16) return (int)hipErrorNotSupported;
     // (mode 2 promises hdb_mfma_batch_capacity() queries in ONE launch: only the two-tile launcher holds more than 128, whatever the variant)
@@ -151,7 +158,12 @@ extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_
                                          int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
     const dim3 grid(64, nq_launch);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
+    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3 && dtype != HDB_I8) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
+    if (dtype == HDB_I8) {
+        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);
+        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);
+        return (int)hipGetLastError();
+    }
     if (dtype == HDB_F8E4M3) {
         if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);
         else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);

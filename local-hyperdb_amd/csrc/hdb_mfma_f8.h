@@ -39,6 +39,25 @@ __device__ __forceinline__ u32x4 hdb_f8x8_to_bf16x8(const uint2& raw) {
     return o;
 }
 
+// int8 rows (HDB_I8, hdb_mfma_i8.hip): eight signed bytes -> eight bf16, element 2 j in the low half of word j.  |x| <= 128 has at
+// most 8 significant bits, so the upper half of the float32 widening is the value itself: one v_cvt_f32_i32 with a sign-extending
+// byte select per element (hdb_i8_cvt) and one v_perm per pair -- 12 instructions per 8 bytes against float8's 8, and fewer than
+// the 2 v_xor + 8 v_cvt_f32_ubyteN + 8 v_sub_f32 + 4 v_perm of the unsigned recipe.
+__device__ __forceinline__ u32x4 hdb_i8x8_to_bf16x8(const uint2& raw) {
+    const int lo = (int)raw.x, hi = (int)raw.y;
+    u32x4 o;
+    o[0] = __builtin_amdgcn_perm(hdb_fbits(hdb_i8_cvt<1>(lo)), hdb_fbits(hdb_i8_cvt<0>(lo)), 0x07060302u);
+    o[1] = __builtin_amdgcn_perm(hdb_fbits(hdb_i8_cvt<3>(lo)), hdb_fbits(hdb_i8_cvt<2>(lo)), 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(hdb_fbits(hdb_i8_cvt<1>(hi)), hdb_fbits(hdb_i8_cvt<0>(hi)), 0x07060302u);
+    o[3] = __builtin_amdgcn_perm(hdb_fbits(hdb_i8_cvt<3>(hi)), hdb_fbits(hdb_i8_cvt<2>(hi)), 0x07060302u);
+    return o;
+}
+// The row converter of hdb_mfma_f8_kernel, a compile-time parameter: eight stored bytes -> the A fragment's eight bf16.  Everything
+// else of the kernel -- fragment map, K walk, epilogue, grid, the wq rule -- is shared; the float8 instantiations take the default
+// and compile to what they were.
+struct HdbRowCvtF8 { static __device__ __forceinline__ u32x4 to_bf16x8(const uint2& raw) { return hdb_f8x8_to_bf16x8(raw); } };
+struct HdbRowCvtI8 { static __device__ __forceinline__ u32x4 to_bf16x8(const uint2& raw) { return hdb_i8x8_to_bf16x8(raw); } };
+
 // What the register kernel below and the LDS kernel (hdb_mfma_f8_lds.h) do with a tile's accumulator, in ONE place so that the two
 // cannot drift: lane (rl, h) holds rows rowg = row0 + 4 h .. + 3 of tile sequence number t against query rl.
 // ... its start: zero, or the sums of the K slices before this one
@@ -114,7 +133,7 @@ __device__ __forceinline__ void hdb_f8_tile_finish(const ScanArgs& a, const f32x
 // (the filter flavour of a 512-element slice holds 192 registers of query parts, 32 of raw row bytes, the partial sums and the slice
 //  addressing: left alone it takes 254-256 VGPRs plus 4 AGPRs for the accumulator -- 264 allocated, one wave per SIMD.  Asked for two
 //  workgroups per CU it keeps the accumulator in the 256 VGPRs, without scratch: two waves per SIMD like the other 512-element kernels)
-template <int D, int MODE, int METRIC, bool HAS_BIAS, bool KSL = false>
+template <int D, int MODE, int METRIC, bool HAS_BIAS, bool KSL = false, typename CVT = HdbRowCvtF8>
 __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void hdb_mfma_f8_kernel(ScanArgs a, const float* __restrict__ Qf, const float* __restrict__ aux0,
                                                           const float* __restrict__ qsq, int nq_end, int wq) {
     static_assert(D % 32 == 0 && (MODE == 0 || MODE == 1 || (KSL && MODE == 3 && METRIC == 0 && !HAS_BIAS)), "whole k-steps; MODE 0 / 1, a K slice also 3");
@@ -166,7 +185,7 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
         f32x4 acc = hdb_f8_acc_start<KSL>(a, q_ok, ks_at, rowg, n_rows);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            const u32x4 av = hdb_f8x8_to_bf16x8(raw[s]);
+            const u32x4 av = CVT::to_bf16x8(raw[s]);
 #define HDB_BF(x) __builtin_bit_cast(hdb_bf16x8, x)
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p2), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HDB_BF(av), HDB_BF(Bq[s].p1), acc, 0, 0, 0);
@@ -177,14 +196,14 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
     }
 }
 
-template <int D, int MODE>
+template <int D, int MODE, typename CVT = HdbRowCvtF8>
 static int launch_f8_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
     const int tq = (nq_launch + 15) / 16;
     const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;                              // query groups per workgroup; the other waves take further tiles
     const dim3 grid(blocks, (tq + wq - 1) / wq);
     const int nq_end = a.q0 + nq_launch;
     const bool b = a.bias != nullptr;
-#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
+#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_, false, CVT>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
     if (a.metric == HDB_DOT) { if (b) HDB_F8_GO(0, true, nullptr); else HDB_F8_GO(0, false, nullptr); }
     else if (a.metric == HDB_COSINE) { if (b) HDB_F8_GO(1, true, a.inv_norm); else HDB_F8_GO(1, false, a.inv_norm); }
     else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_F8_GO(2, true, sqnorm); else HDB_F8_GO(2, false, sqnorm); }
@@ -192,11 +211,11 @@ static int launch_f8_metric(const ScanArgs& a, const float* Qf, const float* sqn
 #undef HDB_F8_GO
     return (int)hipGetLastError();
 }
-template <int D>
+template <int D, typename CVT = HdbRowCvtF8>
 static int launch_f8(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
     if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || a.d != D || a.mask) return (int)hipErrorNotSupported;      // 8-byte fragment loads; a mask arrives folded into the bias
-    if (mode == 0) return launch_f8_metric<D, 0>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_f8_metric<D, 1>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    if (mode == 0) return launch_f8_metric<D, 0, CVT>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
+    if (mode == 1) return launch_f8_metric<D, 1, CVT>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
     return (int)hipErrorNotSupported;
 }
 

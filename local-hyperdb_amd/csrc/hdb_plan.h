@@ -343,7 +343,9 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     //  cores vs use_mfma = 0 on the same tensor, alternating, p50 in us, spread <= 5 % (profiles/f8_time.txt): 5 queries 10M x 384 1 070
     //  vs 2 902, 2M x 384 260 vs 616, 2M x 128 121 vs 285, 2M x 256 231 vs 421, 2M x 512 307 vs 772; 8 queries 1 073 vs 2 992, 264 vs 637,
     //  123 vs 331, 234 vs 439, 312 vs 793 -- the matrix cores win 1.8-2.8x from the first batch size they are offered)
-    const int64_t min_q = (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || hdb_mfma_anyd_pad(ix.dtype, ix.d) > 0 || ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3) ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), bf16_ks_min_q)
+    // (int8 rows, hdb_mfma_i8.hip: the same bytes through the same kernel with another row converter -- float8's rule; an int8 index
+    //  plans like a float8 index whose two opt-ins, f8_ks_min_q and f8_lds_min_q, are 0)
+    const int64_t min_q = (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || hdb_mfma_anyd_pad(ix.dtype, ix.d) > 0 || ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3 || ix.dtype == HDB_I8) ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), bf16_ks_min_q)
                         : ix.dtype == HDB_F32 ? std::max<int64_t>(o.mfma_min_q, f32_min_q) : o.mfma_min_q;
     // hdb_mfma_fused_kernel is built around ONE multiplying wave and two selector waves: with 2-4 fp16 queries its sample phase and
     // epilogue cost more than the batched single launch (eight multiplying waves) until the pass itself dominates -- n = 100k x 384,
@@ -361,7 +363,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
-    if (mfma && (ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3)) mfma = finite();
+    // (int8 rows are always finite -- 512 x 128^2 is far from overflow -- and the flag their row norms leave says so: the same question, always yes)
+    if (mfma && (ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3 || ix.dtype == HDB_I8)) mfma = finite();
     // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call (build_needed); an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.

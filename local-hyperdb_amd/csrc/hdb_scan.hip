@@ -19,6 +19,7 @@ template <typename T> struct Elem;
 template <> struct Elem<__half> { using Acc = float;  static constexpr int EPC = 8; };
 template <> struct Elem<hdb_bf16> { using Acc = float; static constexpr int EPC = 8; };
 template <> struct Elem<hdb_f8> { using Acc = float; static constexpr int EPC = 16; };
+template <> struct Elem<hdb_i8> { using Acc = float; static constexpr int EPC = 16; };
 template <> struct Elem<float>  { using Acc = float;  static constexpr int EPC = 4; };
 template <> struct Elem<double> { using Acc = double; static constexpr int EPC = 2; };
 
@@ -44,6 +45,15 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[16], hdb
         x[4 * i] = lo[0]; x[4 * i + 1] = lo[1]; x[4 * i + 2] = hi[0]; x[4 * i + 3] = hi[1];
     }
 }
+// int8: element 4 i + b of the chunk is byte b of word i, sign-extended and converted by one v_cvt_f32_i32 with a byte select
+// (hdb_i8_cvt): 16 instructions per 16-byte load against float8's 8
+__device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[16], hdb_i8*) {
+    const int w[4] = {(int)raw.x, (int)raw.y, (int)raw.z, (int)raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[4 * i] = hdb_i8_cvt<0>(w[i]); x[4 * i + 1] = hdb_i8_cvt<1>(w[i]); x[4 * i + 2] = hdb_i8_cvt<2>(w[i]); x[4 * i + 3] = hdb_i8_cvt<3>(w[i]);
+    }
+}
 __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[4], float*) {
     x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
     x[2] = __uint_as_float(raw.z); x[3] = __uint_as_float(raw.w);
@@ -56,6 +66,7 @@ __device__ __forceinline__ void hdb_unpack(const uint4& raw, double (&x)[2], dou
 __device__ __forceinline__ float hdb_to_f(__half v) { return __half2float(v); }
 __device__ __forceinline__ float hdb_to_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 __device__ __forceinline__ float hdb_to_f(hdb_f8 v) { return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0); }
+__device__ __forceinline__ float hdb_to_f(hdb_i8 v) { return hdb_i8_to_f(v); }
 __device__ __forceinline__ float hdb_to_f(float v) { return v; }
 __device__ __forceinline__ double hdb_to_f(double v) { return v; }
 
@@ -329,7 +340,7 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
         if constexpr (sizeof(T) == 1) {
             // one-byte elements: a lane takes EIGHT elements per step -- the element order of a 16-byte chunk of 2-byte elements -- so
             // that the sum of squares, and with it 1/||v||, has the bits a bfloat16 index over the same (exactly widened) values
-            // computes: the matrix-core scores of the two are then equal bit for bit (hdb_mfma_f8.h)
+            // computes: the matrix-core scores of the two are then equal bit for bit (hdb_mfma_f8.h; float8 and int8 alike)
             if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(V) & 7) == 0) {
                 for (int c = l16; c < d / 8; c += 16) {
 #pragma unroll
@@ -337,7 +348,7 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
                         const int64_t r = min(r0 + u, n - 1);
                         const uint2 raw = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(V) + r * (int64_t)d + (int64_t)c * 8);
                         float x[16];
-                        hdb_unpack(make_uint4(raw.x, raw.y, 0u, 0u), x, (hdb_f8*)nullptr);
+                        hdb_unpack(make_uint4(raw.x, raw.y, 0u, 0u), x, (T*)nullptr);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[u] = fma(x[e], x[e], acc[u]);
                     }
@@ -582,7 +593,7 @@ static void launch_vec(const ScanArgs& a, int nq_launch, int blocks, hipStream_t
         if (nj == 3) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 3, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
         if (nj == 6) { hipLaunchKernelGGL((hdb_scan_kernel<T, QT, MODE, ACC, 6, LIST>), grid, dim3(256), lds, st, a, nq_end); return; }
     }
-    // one-byte rows of 256 / 384 / 512 bytes (float8, d = 256 / 384 / 512): a tile is 4-8 KiB, so the one-query kernel is unrolled
+    // one-byte rows of 256 / 384 / 512 bytes (float8 and int8, d = 256 / 384 / 512): a tile is 4-8 KiB, so the one-query kernel is unrolled
     // over its 16 / 24 / 32 chunks (4-8 loads of 16 bytes per lane ahead of the first use, 88-124 registers) and the grid grows
     // with the shorter tile (hdb_scan_auto_blocks).  The four-query kernel keeps the runtime loop on that grid: unrolled over two
     // steps it holds 2 x 4 x 16 widened elements beside 16 sums and takes all 256 registers (one workgroup per CU) against
@@ -648,6 +659,7 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
         else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
         else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
         else if (dtype == HDB_F8E4M3) { if (mode == 0) launch_scan_t<hdb_f8, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_f8, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
+        else if (dtype == HDB_I8) { if (mode == 0) launch_scan_t<hdb_i8, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_i8, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
         else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;                                                                \
         else { if (mode == 0) launch_scan_t<double, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
     } while (0)
@@ -683,6 +695,7 @@ extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, fl
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rownorm_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, inv_norm, sqnorm, nan_flag);
+    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_rownorm_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, inv_norm, sqnorm, nan_flag);
     return (int)hipGetLastError();
@@ -708,6 +721,7 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
         else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_wide_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
         else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
         else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
+        else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, row0, bits);
         else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
         else hipLaunchKernelGGL(hdb_signpack_wide_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
         return (int)hipGetLastError();
@@ -717,6 +731,7 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
     else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
+    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, row0, bits);
     else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_signpack_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
     return (int)hipGetLastError();
@@ -850,6 +865,7 @@ extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, f
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rowstats_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, pscale);
     else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, pscale);
     else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, pscale);
+    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, pscale);
     else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
     else hipLaunchKernelGGL(hdb_rowstats_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, pscale);
     return (int)hipGetLastError();

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("HYPERDB_HIP_LIB") or os.path.join(os.path.dirname(_HE
 
 HDB_F16, HDB_F32, HDB_F64, HDB_BF16 = 0, 1, 2, 3
 HDB_F8E4M3 = 5                          # OCP float8 e4m3 (torch.float8_e4m3fn); 4 is unassigned and refused by the library
+HDB_I8 = 7                              # signed 8-bit integers (np.int8 / torch.int8), on request: storage="int8"; 6 is unassigned
 METRIC_IDS = {
     "dot_product": 0,
     "cosine_similarity": 1,
@@ -130,6 +131,50 @@ _NP2HDB = {np.dtype(np.float16): HDB_F16, np.dtype(np.float32): HDB_F32, np.dtyp
 _F8 = torch.float8_e4m3fn
 _TORCH2HDB = {torch.float16: HDB_F16, torch.float32: HDB_F32, torch.float64: HDB_F64, torch.bfloat16: HDB_BF16, _F8: HDB_F8E4M3}
 F8_MAX = 448.0                          # largest finite e4m3 magnitude
+# what a STORED tensor's dtype is to the library.  torch.int8 is in here and not in _TORCH2HDB: without storage="int8" an int8
+# tensor is widened to float64 like every other integer input (to_device_matrix), with it the bytes are the matrix
+_STORED2HDB = dict(_TORCH2HDB)
+_STORED2HDB[torch.int8] = HDB_I8
+STORAGE_MODES = (None, "int8")
+
+
+def storage_mode(storage):
+    """A ``storage=`` argument: None (the input's own dtype policy) or "int8"; anything else raises ValueError."""
+    if storage is not None and not isinstance(storage, str) or storage not in STORAGE_MODES:
+        raise ValueError(f"storage must be None or 'int8', got {storage!r}")
+    return storage
+
+
+def to_i8(data):
+    """Numeric data -> torch.int8 tensor for an int8 index (storage="int8"), on the host.  An int8 tensor or array goes in as it
+    is (``to_i8(t) is t`` for a torch.int8 tensor, wherever it lives).  Anything else numeric is accepted only if every element is
+    an integer in [-128, 127]; otherwise ValueError names the first offending value -- no rounding, no scaling, no saturation."""
+    if isinstance(data, torch.Tensor):
+        if data.dtype == torch.int8:
+            return data
+        t = data.detach().cpu()
+        if t.dtype in (torch.bfloat16, torch.float16, _F8):
+            t = t.to(torch.float32)                     # (exact; numpy has no bfloat16 / float8)
+        a = t.numpy()
+    else:
+        a = np.asarray(data)
+    if a.dtype == np.int8:
+        return torch.from_numpy(np.ascontiguousarray(a))
+    if a.dtype == np.bool_:
+        a = a.astype(np.int8)
+    elif not np.issubdtype(a.dtype, np.number) or np.issubdtype(a.dtype, np.complexfloating):
+        raise ValueError("vectors must be numeric")
+    else:
+        ok = (a >= -128) & (a <= 127)                   # (NaN compares false; inf is out of range)
+        if a.dtype.kind == "f":
+            with np.errstate(invalid="ignore"):
+                ok &= a == np.floor(a)
+        if not ok.all():
+            bad = a[~ok].reshape(-1)[0]
+            raise ValueError(f"storage='int8' takes integers in [-128, 127] and stores them as they are; got {bad!r} "
+                             "(quantise float embeddings before handing them over)")
+        a = a.astype(np.int8)
+    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 def _as_bytes(t):
@@ -163,11 +208,17 @@ def _stream_ptr(device):
     return ctypes.c_void_p(_stream_int(device))
 
 
-def to_device_matrix(vectors, device):
+def to_device_matrix(vectors, device, storage=None):
     """numpy / list / torch -> C-contiguous 2-D torch tensor on `device` in a supported dtype.
+
+    storage="int8": the input is converted with to_i8 (int8 stays, integers in [-128, 127] of any numeric dtype are taken,
+    anything else raises ValueError) and travels as torch.int8.  Without it nothing below changes: integer inputs, torch.int8
+    included, are widened to float64.
 
     Dtype policy mirrors HyperDB.fp_precision (hyperdb.py:65-66): float16/32/64 stay as they are (and so does a
     torch.bfloat16 tensor: 2 bytes per element on the device; and a torch.float8_e4m3fn tensor: 1 byte), anything else numeric (ints, bools) is widened to float64 like numpy would promote it."""
+    if storage_mode(storage) == "int8":
+        return to_i8(vectors).to(device).contiguous()
     if isinstance(vectors, torch.Tensor):
         t = vectors
         if t.dtype not in _TORCH2HDB:
@@ -191,12 +242,13 @@ class GpuIndex:
     :37 (re-normalising every row): those happen once here, at registration.
     """
 
-    def __init__(self, vectors, device=None, row_base=0):
+    def __init__(self, vectors, device=None, row_base=0, storage=None):
+        storage_mode(storage)
         require_gpu()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
-        t = to_device_matrix(vectors, self.device)
+        t = to_device_matrix(vectors, self.device, storage)
         if t.dim() != 2:
             # reference: non-2-D vectors make the metric functions raise (tests/test_ranking_algorithm.py:107-114)
             raise ValueError(f"vectors must be 2-D (N x d), got shape {tuple(t.shape)}")
@@ -204,7 +256,8 @@ class GpuIndex:
         self.n, self.d = int(t.shape[0]), int(t.shape[1])
         if self.d == 0:
             raise ValueError("vectors must have d > 0")
-        self.dtype = _TORCH2HDB[t.dtype]
+        self.dtype = _STORED2HDB[t.dtype]
+        self.storage = storage                 # "int8": append / update convert with to_i8
         self.row_base = int(row_base)
         self._h = ctypes.c_void_p()
         self._bias = None
@@ -243,7 +296,7 @@ class GpuIndex:
         by doubling; the library re-points (hdb_index_rebase) and extends its row caches (hdb_index_extend)."""
         if self.dtype == HDB_F8E4M3:
             rows = to_f8(rows)                              # float data into a float8 index: torch's conversion, on the host
-        t = to_device_matrix(rows, self.device)
+        t = to_device_matrix(rows, self.device, self.storage)      # (an int8 index: to_i8 -- ValueError before anything is stored)
         if t.dim() == 1:
             t = t.reshape(1, -1)
         if t.dim() != 2 or int(t.shape[1]) != self.d:
@@ -276,10 +329,10 @@ class GpuIndex:
         """Point the handle at a new matrix (after add/remove) and rebuild the row caches."""
         if self.dtype == HDB_F8E4M3:
             vectors = to_f8(vectors)                        # ... into a float8 index: torch's conversion, on the host, as append does
-        t = to_device_matrix(vectors, self.device)
+        t = to_device_matrix(vectors, self.device, self.storage)   # (an int8 index: to_i8, as append does)
         if self.dtype == HDB_BF16 and t.dtype != torch.bfloat16:
             t = t.to(torch.bfloat16)                        # float data into a bf16 index: round to nearest even, as append does
-        if t.dim() != 2 or int(t.shape[1]) != self.d or _TORCH2HDB[t.dtype] != self.dtype:
+        if t.dim() != 2 or int(t.shape[1]) != self.d or _STORED2HDB[t.dtype] != self.dtype:
             raise ValueError("update: matrix must keep d and dtype")
         self.V, self.n = t, int(t.shape[0])
         self._bias = self._mask = self._nan = None
@@ -300,7 +353,8 @@ class GpuIndex:
         bfloat16: opt-in.  ``quantize("int8")`` raises NotImplementedError on a bf16 index unless ``set_option("bf16_quant", 1)``
         came first; with it the shadow is built as for fp16 / fp32 (explicit only, never automatic) and the 1-4-query calls it
         serves return the bits of the VALU scan -- the path a bf16 index takes for such calls by default.  ``register_vectors``
-        and ``HyperDB`` set the option themselves when they are given ``quantize="int8"``.  float8 and float64 raise."""
+        and ``HyperDB`` set the option themselves when they are given ``quantize="int8"``.  float8, int8 (``storage="int8"``: one
+        byte per element already) and float64 raise."""
         mode = quant_mode(mode)
         with torch.cuda.device(self.device):
             _check(_lib.hdb_index_quantize(self._h, mode, _stream_ptr(self.device)), "hdb_index_quantize")
@@ -325,7 +379,9 @@ class GpuIndex:
 
     def host_matrix(self):
         """The stored rows as a host array (one D2H copy; the resident copy stays the only one kept).  A bfloat16 index returns
-        the exact float32 widening (numpy has no bfloat16), and so does a float8 index (widened on the host)."""
+        the exact float32 widening (numpy has no bfloat16), and so do a float8 index (widened on the host) and an int8 index."""
+        if self.V.dtype == torch.int8:
+            return self.V.cpu().numpy().astype(np.float32)
         if self.V.dtype == torch.bfloat16:
             return self.V.float().cpu().numpy()
         if self.V.dtype == _F8:

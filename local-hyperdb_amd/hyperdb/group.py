@@ -29,12 +29,15 @@ def _bounds(n, parts):
 
 
 class GpuGroup:
-    def __init__(self, vectors, devices):
+    def __init__(self, vectors, devices, storage=None):
+        _native.storage_mode(storage)
         _native.require_gpu()
         devices = [torch.device("cuda", d) if isinstance(d, int) else torch.device(d) for d in devices]
         if not devices:
             raise ValueError("devices must name at least one GPU")
-        if isinstance(vectors, torch.Tensor):
+        if storage == "int8":
+            mat = _native.to_i8(vectors)              # the whole matrix is checked before any shard is uploaded
+        elif isinstance(vectors, torch.Tensor):
             mat = vectors
         else:
             mat = np.asarray(vectors)
@@ -48,7 +51,7 @@ class GpuGroup:
         self.shards = []
         try:
             for (lo, hi), dev in zip(_bounds(n, parts), self.devices):
-                self.shards.append(GpuIndex(mat[lo:hi], device=dev, row_base=lo))
+                self.shards.append(GpuIndex(mat[lo:hi], device=dev, row_base=lo, storage=storage))
         except Exception:
             self.close()
             raise

@@ -65,7 +65,7 @@ _METRICS = ['dot_product', 'cosine_similarity', 'euclidean_metric', 'manhattan_d
 class HyperDB:
     def __init__(self, documents=None, vectors=None, select_keys=None, embedding_function=None, fp_precision="float32",
                  add_timestamp=False, metadata_keys=None, ann_metric="cosine", n_trees=10, cache_size=256, device=None,
-                 devices=None, quantize=None):
+                 devices=None, quantize=None, storage=None):
         # ("bfloat16" and "float8_e4m3fn" are this build's additions: host arrays stay float32, the resident matrix is
         #  torch.bfloat16 / torch.float8_e4m3fn)
         if fp_precision not in ["float16", "float32", "float64", "bfloat16", "float8_e4m3fn"]:
@@ -87,6 +87,15 @@ class HyperDB:
         self.devices = list(devices) if devices else None      # several GPUs: the matrix is row-sharded over them (GpuGroup)
         _native.quant_mode(quantize)                  # None | "int8": keep an int8 shadow of the matrix (GpuIndex.quantize; not saved)
         self.quantize = quantize
+        # storage="int8": the resident matrix is torch.int8, one byte per element -- the integers are the matrix.  Host arrays
+        # (.vectors, save / load) stay in fp_precision, as for bfloat16 / float8; fp_precision="int8" is still refused above
+        self.storage = _native.storage_mode(storage)
+        self.i8 = storage == "int8"
+        if self.i8:
+            if fp_precision != "float32":
+                raise ValueError("storage='int8' keeps float32 host arrays: leave fp_precision at 'float32'")
+            if quantize is not None:
+                raise NotImplementedError("storage='int8' has no int8 shadow: one byte per element already")
         self.documents, self.source_indices = [], []
         self._index = None
         self._dead = np.zeros(0, dtype=np.int64)     # tombstoned device rows (ascending); see remove_document
@@ -129,6 +138,8 @@ class HyperDB:
             raise ValueError("All vectors must have the same dimension, one per document.")   # hyperdb.py:139-164
         if self._index is not None and vectors.shape[1] != self._index.d:
             raise ValueError("All vectors must have the same dimension, one per document.")
+        # (an int8 store: integers in [-128, 127] or ValueError -- here, before anything of the call is stored)
+        vectors_i8 = _native.to_i8(vectors) if self.i8 else None
         vectors = vectors.astype(self.fp_precision, copy=False)
         if self.f8:
             # torch's float8 conversion does not saturate: a finite value beyond the format's range would be stored as NaN, and a NaN
@@ -151,11 +162,14 @@ class HyperDB:
                 vectors = torch.from_numpy(np.ascontiguousarray(vectors)).to(torch.bfloat16)
             if self.f8:                               # torch's conversion on the host (round to nearest even); appends convert the same way
                 vectors = _native.to_f8(vectors)
-            self._index = GpuGroup(vectors, self.devices) if self.devices else GpuIndex(vectors, device=self.device)
+            if self.i8:
+                vectors = vectors_i8
+            self._index = (GpuGroup(vectors, self.devices, storage=self.storage) if self.devices
+                           else GpuIndex(vectors, device=self.device, storage=self.storage))
             if self.quantize is not None:             # (append / compact / update keep the shadow current from here on)
                 _native.request_shadow(self._index, self.quantize)      # (fp_precision="bfloat16": sets bf16_quant first)
         else:
-            self._index.append(vectors)
+            self._index.append(vectors_i8 if self.i8 else vectors)
 
     def add_document(self, document, vectors=None, count=1, add_timestamp=False):
         """One document and its vector (hyperdb.py:568-626); the chunked-text form (count > 1) belongs to the
@@ -269,6 +283,8 @@ class HyperDB:
         for sh, lo, hi in self._shards():
             mine = rows[(rows >= lo) & (rows < hi)] - lo
             if not mine.size:
+                continue
+            if sh.V.dtype == torch.int8:                     # integers: no NaN code
                 continue
             rows_d = torch.from_numpy(mine).to(sh.device)
             if sh.V.dtype == torch.float8_e4m3fn:            # the two NaN codes, 0x7F and 0xFF, looked for in the bytes

@@ -43,12 +43,15 @@ _ALL_METRICS = tuple(METRIC_IDS)
 class ResidentVectors:
     """Handle for a matrix registered on the GPU; pass it wherever ``vectors`` is expected."""
 
-    def __init__(self, vectors, device=None, devices=None, quantize=None):
+    def __init__(self, vectors, device=None, devices=None, quantize=None, storage=None):
         _native.quant_mode(quantize)                     # (ValueError before anything is uploaded)
-        self.index = GpuGroup(vectors, devices) if devices else GpuIndex(vectors, device=device)
+        _native.storage_mode(storage)
+        self.index = GpuGroup(vectors, devices, storage=storage) if devices else GpuIndex(vectors, device=device, storage=storage)
         if quantize is not None:
             _native.request_shadow(self.index, quantize)     # (a bfloat16 matrix: sets bf16_quant first)
         arr_dtype = vectors.dtype if hasattr(vectors, "dtype") else None
+        if storage == "int8":
+            arr_dtype = None                             # the STORED dtype decides: an int8 index answers in float32
         self.np_dtype = _np_dtype_of(arr_dtype, self.index)
 
     @property
@@ -62,18 +65,24 @@ class ResidentVectors:
         self.index.close()
 
 
-def register_vectors(vectors, device=None, devices=None, quantize=None):
+def register_vectors(vectors, device=None, devices=None, quantize=None, storage=None):
     """Upload ``vectors`` once; returns a handle usable in place of ``vectors``.  ``devices=[...]`` row-shards the matrix
     over several GPUs behind the same handle (single process, see hyperdb/group.py).  ``quantize="int8"`` also keeps an int8
     shadow of the matrix that 1-4-query dot / cosine / euclidean calls scan first, rescoring the surviving rows exactly (same
-    answer, fewer bytes read; see GpuIndex.quantize)."""
-    return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize)
+    answer, fewer bytes read; see GpuIndex.quantize).  ``storage="int8"`` keeps the matrix as signed 8-bit integers, one byte per
+    element: np.int8 / torch.int8 go in as they are, any other numeric input only if every element is an integer in
+    [-128, 127] (ValueError otherwise); queries and scores are float32.  Without it integer inputs are widened to float64."""
+    return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize, storage=storage)
 
 
 # (bfloat16 has no numpy dtype: score vectors of a bf16 matrix come back as float32, the type its values widen to exactly)
 # (float8 e4m3 likewise)
 _TORCH2NP = {torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64, torch.bfloat16: np.float32,
              torch.float8_e4m3fn: np.float32}
+# ... of a STORED matrix: an int8 index (storage="int8") answers in float32.  Not part of _TORCH2NP, which also reads the dtype of
+# raw inputs: a raw torch.int8 tensor handed to a metric function becomes a float64 index and answers in float64
+_STORED2NP = dict(_TORCH2NP)
+_STORED2NP[torch.int8] = np.float32
 
 
 def _np_dtype_of(dt, index):
@@ -82,7 +91,7 @@ def _np_dtype_of(dt, index):
     if dt is not None:
         d = np.dtype(dt)
         return d
-    return np.dtype(_TORCH2NP[(index.shards[0] if isinstance(index, GpuGroup) else index).V.dtype])
+    return np.dtype(_STORED2NP[(index.shards[0] if isinstance(index, GpuGroup) else index).V.dtype])
 
 
 def _resolve(vectors):
@@ -90,9 +99,9 @@ def _resolve(vectors):
     if isinstance(vectors, ResidentVectors):
         return vectors.index, vectors.np_dtype, False
     if isinstance(vectors, GpuIndex):
-        return vectors, np.dtype(_TORCH2NP[vectors.V.dtype]), False
+        return vectors, np.dtype(_STORED2NP[vectors.V.dtype]), False
     if isinstance(vectors, GpuGroup):
-        return vectors, np.dtype(_TORCH2NP[vectors.shards[0].V.dtype]), False
+        return vectors, np.dtype(_STORED2NP[vectors.shards[0].V.dtype]), False
     if isinstance(vectors, torch.Tensor):
         ix = GpuIndex(vectors)
         return ix, np.dtype(_TORCH2NP.get(vectors.dtype, np.float64)), True
