@@ -258,6 +258,14 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  * float32 query is rounded to 11 significant bits per element (score error ~1e-4 relative, inside the 1e-3
  * contract for fp16 data).  hdb_set_option(ix, "use_mfma", 0) keeps float32 queries unrounded (VALU scan).
  * float32 matrices (d in {128,256,384,512,768}) take batches of 5+ queries through fp32 MFMAs: exact fp32 products.
+ * Larger cosine / euclidean / pearson batches on a finite float32 matrix multiply the rows as two bf16 parts instead (option
+ * f32_split, default 1; stat f32_split): 16 mantissa bits of a row value, a product error of up to 2^-17 |v| |q| that those
+ * metrics divide by |v| |q| or bury under |v|^2 + |q|^2 -- inside 1e-5 * max(1, |s|) for every row.  dot_product never does:
+ * nothing scales its error down, and a row whose score is small against |v| |q| would miss the band (|v| = 20, |q| = 2,
+ * |s| < 1: up to 2.3e-5), so dot_product batches run on the fp32 MFMAs at every size.  The parts of an infinite query element
+ * cancel to NaN: such a query gets HDB_Q_UNDERFLOW from hdb_topk and its answer from hdb_topk_exact.
+ * fp16 / float32 rows of a width without a geometry of its own (any multiple of 16 bytes) ride the next wider one on the matrix
+ * cores while the matrix is finite; a matrix with an infinite or NaN element keeps the VALU scan at those widths.
  * Calls of 1-4 dot / cosine queries with k <= 128 on an fp16 matrix (d = 256 .. 768; 1-2 queries for d = 1024 .. 1536), or of 1-2 on a float32 matrix
  * (d in {128,256,384}; one query at d = 768 and, from 1.5 M rows on, at d = 512), run as ONE kernel launch (query preparation, row sample, threshold exchange between the
  * workgroups, filter pass, final sort: hdb_mfma_fused.h); everything else is the same pipeline as separate launches.
@@ -351,7 +359,10 @@ int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric
 int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, void* host_record, void* stream);
 
 /* Same contract, but by materialising all n scores per query and radix-selecting them:
- * always exact, any tie pattern, any k <= HDB_MAX_K; dev_status is written as 0. */
+ * always exact, any tie pattern, any k <= HDB_MAX_K; dev_status is written as 0 (HDB_Q_NAN apart) whatever the queries hold --
+ * an infinite query element included.  The scores are hdb_topk's own bits; where hdb_topk would multiply float32 rows as bf16
+ * parts, this call does so only while no query of the call holds an infinity (it reads the query flags back: one stream
+ * synchronisation, on float32 cosine / euclidean / pearson batches only) and uses the fp32 MFMAs otherwise. */
 int hdb_topk_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
                    int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 
@@ -430,7 +441,10 @@ void hdb_group_destroy(hdb_group* g);
  *   (float8 batches with the rows expanded to bf16 in LDS once per workgroup: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q)
  *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
- *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan).
+ *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan),
+ *   l1_packed (0: that tile kernel always subtracts in float32; default 1 = packed fp16 differences on fp16 rows while every query
+ *   element is an fp16 number and every element of the matrix and of the queries is within 32752 = 65504 / 2 in magnitude, so that
+ *   no difference leaves fp16 range), f32_split (0: float32 batches never multiply as bf16 parts), f32_split_min_q.
  *   Int8 shadow (hdb_index_quantize): use_quant (0: never), quant_min_n (-1: the measured rule), quant_max_k (<= 128),
  *   bf16_quant (0, the default: hdb_index_quantize(HDB_QUANT_I8) refuses a bfloat16 matrix; 1: it builds an explicit shadow; means
  *   nothing on other dtypes),

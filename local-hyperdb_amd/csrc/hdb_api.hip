@@ -103,7 +103,7 @@ struct hdb_index {
     char* ws = nullptr;
     size_t ws_bytes = 0;
     hdb_options opt;                  // hdb_set_option (hdb_plan.h)
-    int flags_host = -1;              // host copy of *nan_flag (1 = a NaN row, 2 = a row with an infinite sum of squares); -1 = not fetched since the last build
+    int flags_host = -1;              // host copy of *nan_flag (HDB_FLAG_*, hdb_caps.h: 1 = a NaN row, 2 = a row with an infinite sum of squares, 4 = a row that may hold an element beyond half of fp16 range); -1 = not fetched since the last build
     // stats of the last hdb_topk call: the plan's (topk_impl), and whether hdb_topk_host wrote the caller's record directly
     TopkStats st;
     int64_t st_host_direct = 0;
@@ -473,7 +473,15 @@ extern "C" int hdb_index_has_nan(hdb_index* ix, int* out_flag) {
 // Are all rows of the matrix finite with a finite sum of squares?  One 4-byte copy after each build, cached.
 static int matrix_is_finite(hdb_index* ix, bool* out) {
     if (ix->flags_host < 0) { int f = 0; int rc = hdb_index_has_nan(ix, &f); if (rc != HDB_OK) return rc; }
-    *out = ix->flags_host == 0;
+    *out = (ix->flags_host & (HDB_FLAG_NAN | HDB_FLAG_INF)) == 0;
+    return HDB_OK;
+}
+// May a manhattan pass over this fp16 matrix take its differences in packed fp16 (hdb_l1_packed_ok, hdb_caps.h)?  The same cached word.
+static int matrix_l1_packed_ok(hdb_index* ix, bool* out) {
+    *out = false;
+    if (ix->dtype != HDB_F16 || !ix->opt.l1_packed) return HDB_OK;      // (nothing to ask)
+    if (ix->flags_host < 0) { int f = 0; int rc = hdb_index_has_nan(ix, &f); if (rc != HDB_OK) return rc; }
+    *out = hdb_l1_packed_ok(ix->dtype, ix->opt.l1_packed, ix->flags_host);
     return HDB_OK;
 }
 
@@ -714,7 +722,10 @@ static int run_scan(hdb_index* ix, ScanArgs& a, int mode, int cq, const QueryBuf
         // dense manhattan passes of a call the plan gave to the tile kernel (TopkPlan::l1tile; the mask is folded into the bias):
         // tiles staged once in LDS, queries in registers, 8-16 queries per pass (hdb_l1_tile.hip)
         // (the tile kernel has no use for ScanArgs::dyn_heavy: 77 there = "keep the float32 arithmetic", set_option l1_packed 0)
-        ScanArgs al = a; al.dyn_heavy = ix->opt.l1_packed ? 0 : 77;
+        // ... and also where an element of the matrix may lie beyond half of fp16 range: a packed difference could round to inf
+        bool pk_ok = false;
+        const int prc = matrix_l1_packed_ok(ix, &pk_ok); if (prc) return prc;
+        ScanArgs al = a; al.dyn_heavy = pk_ok ? 0 : 77;
         LAUNCH_TRY(hdb_launch_l1_tile(&al, ix->dtype, mode, cq, (int)ix->opt.max_blocks, st));
     } else if (mfma) {
         LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, mode, cq, qb.q16, ix->sqnorm, qb.qsq, qb.qscl, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, st, nullptr));
@@ -1160,7 +1171,19 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
     uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
     const void* Qeff = e.Qeff; const int metric_eff = e.metric_eff; const float* bias_eff = e.bias_eff; const uint8_t* mask_eff = e.mask_eff;
-    const bool small = p.small, exact = p.exact, mfma = p.mfma, f32s = p.f32s, fold_small = p.fold_small, f16_queries = p.f16_queries, is_pearson = p.pearson, q16_in_prep = p.q16_in_prep;
+    const bool small = p.small, exact = p.exact, mfma = p.mfma, fold_small = p.fold_small, f16_queries = p.f16_queries, is_pearson = p.pearson, q16_in_prep = p.q16_in_prep;
+    // float32 rows as bf16 parts in a call that ASKED for the exact selection (hdb_topk_exact: the last resort, status 0 whatever the
+    // queries hold): the parts of an infinite query element cancel to NaN, so the call keeps them -- and the default call's bits --
+    // only while no query holds an infinity.  The preparation above left that per query (qnan & 2); reading it is a stream
+    // synchronisation, paid by exact calls of float32 batches and by no other call.
+    bool f32s = p.f32s;
+    if (f32s && p.exact_req) {
+        std::vector<int> h_qnan((size_t)nq);
+        HIP_TRY(hipMemcpyAsync(h_qnan.data(), qnan, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int q = 0; q < nq; ++q) f32s = f32s && !(h_qnan[q] & 2);
+        if (!f32s) ix->st.f32s = 0;
+    }
     const int64_t n = p.subset ? ix->subset_m : ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
     const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, tile_rows = p.tile_rows, npass = p.npass;
     bool q16_ready = q16_in_prep;

@@ -313,6 +313,20 @@ static inline int hdb_l1_tile_supported(int dtype, int d) {
     if (dtype == HDB_F32) return d == 128 || d == 256 || d == 384 || d == 512 || d == 768;      // (512: two queries per wave, 16-row tiles; 768: one)
     return 0;
 }
+// The packed-fp16 flavour of that kernel (fp16 rows, queries that are fp16 numbers) rounds v - q to fp16: a difference beyond 65504
+// becomes inf, the row's sum inf and its score 0 where the float32 flavour and the reference stay finite.  It is taken only where no
+// difference can leave fp16 range: every stored element and every query element within HDB_L1_PK_MAX = 65504 / 2 in magnitude.
+//   the matrix: bit HDB_FLAG_L1_WIDE of the index's flag word, set by the row-norm kernels for a row whose sum of squares exceeds
+//     HDB_L1_PK_MAX^2 -- no element of a row below that can exceed HDB_L1_PK_MAX (a sufficient test that costs the build nothing;
+//     a matrix of many moderately large elements loses the packed flavour with it and keeps the float32 one);
+//   the queries: the kernel's own wave-uniform test beside "is an fp16 number".
+#define HDB_L1_PK_MAX 32752.0f
+#define HDB_FLAG_NAN 1            // bits of hdb_index::nan_flag: a NaN row,
+#define HDB_FLAG_INF 2            // a row with an infinite sum of squares,
+#define HDB_FLAG_L1_WIDE 4        // a row that may hold an element beyond HDB_L1_PK_MAX
+static inline bool hdb_l1_packed_ok(int dtype, int64_t l1_packed_opt, int flags) {
+    return dtype == HDB_F16 && l1_packed_opt != 0 && flags >= 0 && (flags & HDB_FLAG_L1_WIDE) == 0;      // (flags < 0: not fetched)
+}
 
 // ---- hdb_quant.hip: the int8 shadow and its 5-bit plane ----
 // workgroups a launch over `ntiles` tiles takes (the folded threshold keeps 4 x that many per-wave maxima of the sample pass)

@@ -55,7 +55,10 @@ __global__ __launch_bounds__(512) void hdb_l1_tile_kernel(ScanArgs a, int nq_end
     // Sterbenz, and off by at most 2^-11 of itself elsewhere; an error of the SUM of ~2^-11 / sqrt(d), far inside the 1e-3 contract),
     // sign bits masked off, v_dot2c_f32_f16 against (1, 1) for the float32 sum: 3 instructions per TWO elements and query instead of
     // 2 per element plus the conversions, and half the registers per query.  A query that is not an fp16 number keeps the float32
-    // path (its rounding would be a large share of a small |v - q|, see the header).  The choice is wave-uniform, made once, and
+    // path (its rounding would be a large share of a small |v - q|, see the header), and so does a difference that could leave fp16
+    // range: |v - q| > 65504 rounds to inf, the row's sum to inf and its score to 0 -- the flavour is taken only while every element
+    // of the matrix (the launcher's word, dyn_heavy = 77 otherwise) and of the wave's queries is within HDB_L1_PK_MAX = 65504 / 2
+    // in magnitude (hdb_caps.h).  The choice is wave-uniform, made once, and
     // selects one of two copies of the tile loop (the query registers of the other flavour never exist).
     constexpr int EPC = 16 / ES;                    // elements per 16-byte chunk of V
     float thr[NQH];
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(512) void hdb_l1_tile_kernel(ScanArgs a, int nq_end
     };
     bool pk = false;
     if constexpr (ES == 2) {
-        bool exact = wave_active && a.dyn_heavy != 77;        // (ScanArgs::dyn_heavy = 77: keep the float32 arithmetic -- set_option l1_packed 0, A/B runs)
+        bool exact = wave_active && a.dyn_heavy != 77;        // (ScanArgs::dyn_heavy = 77: keep the float32 arithmetic -- set_option l1_packed 0, or a matrix with elements beyond HDB_L1_PK_MAX)
         for (int q = 0; q < nqw; ++q) {
             const float* src = query_src(q);
 #pragma unroll
@@ -76,6 +79,9 @@ __global__ __launch_bounds__(512) void hdb_l1_tile_kernel(ScanArgs a, int nq_end
                 for (int e = 0; e < EPC; e += 4) {
                     const float4 x = *reinterpret_cast<const float4*>(src + (l16 + 16 * j) * EPC + e);
                     exact = exact && (float)(_Float16)x.x == x.x && (float)(_Float16)x.y == x.y && (float)(_Float16)x.z == x.z && (float)(_Float16)x.w == x.w;
+                    // ... and lies within half of fp16 range, like every element of the matrix (the launcher's side of the rule:
+                    // hdb_l1_packed_ok), so that no v - q rounds to inf
+                    exact = exact && fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))) <= HDB_L1_PK_MAX;
                 }
         }
         pk = __builtin_amdgcn_readfirstlane((int)__all(exact)) != 0;

@@ -94,6 +94,7 @@ struct TopkPlan {
     uint32_t kk = 0; int W = 0;
     bool bits = false, pearson = false;                 // the metric's family
     bool exact = false, small = false, mfma = false, f32s = false, ksplit = false, l1tile = false, local = false;
+    bool exact_req = false;                             // the caller asked for the exact selection (f32s: only while no query holds an infinity, run_pipeline)
     bool f8_lds = false;                                // float8 rows: every matrix-core launch of the call expands its rows in LDS (hdb_mfma_f8_lds.h)
     bool subset = false;                                // the pipeline scores the rows of the index's list: every extent below is that of a matrix of subset_m rows
     // prologue of the paths that prepare their queries with launches of their own (full sort, pipeline)
@@ -286,7 +287,9 @@ static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
 
 // finite(): "are all rows of the matrix finite with a finite sum of squares?"
 template <typename Finite>
-static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite) {
+static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite_fn) {
+    int fin_known = -1;                                      // several rules below read the answer: the question is asked once
+    auto finite = [&]() -> bool { if (fin_known < 0) fin_known = finite_fn() ? 1 : 0; return fin_known == 1; };
     // A list call is the same call on a matrix of the m listed rows with the matrix cores and the single launches off: the plan of
     // those facts, taken while it is the multi-kernel pipeline (k > HDB_MAX_K on more than HDB_CAND_CAP listed rows keeps the mask).
     // Its extents, sample plan and statistics are the inner plan's; the executor reads the rows through the list.
@@ -295,7 +298,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
         in.n = ix.subset_m; in.d = ix.d; in.dtype = ix.dtype; in.qmode = HDB_QUANT_NONE; in.has_bias = ix.has_bias; in.cus = ix.cus;
         hdb_options oin = o;
         oin.use_mfma = 0; oin.use_fused = 0; oin.use_quant = 0; oin.use_l1_tile = 0;
-        TopkPlan pin = plan_topk(in, oin, c, finite);
+        TopkPlan pin = plan_topk(in, oin, c, finite_fn);     // (the caller's callable, not the lambda: one instantiation)
         if (pin.path == HDB_PATH_PIPELINE) { pin.subset = true; pin.stats.subset = 1; return pin; }
     }
     TopkPlan p;
@@ -365,6 +368,10 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
     // (int8 rows are always finite -- 512 x 128^2 is far from overflow -- and the flag their row norms leave says so: the same question, always yes)
     if (mfma && (ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3 || ix.dtype == HDB_I8)) mfma = finite();
+    // fp16 / float32 rows narrower than the geometry they ride (hdb_mfma_anyd.h): the chunks past the end of a row are chunk 0 of
+    // the row again and meet zero query fragments -- an infinite element in a row's first 16 bytes gives inf x 0 = NaN there where
+    // np.dot gives the infinity.  Same rule: a matrix that is not finite stays on the VALU scan.
+    if (mfma && hdb_mfma_anyd_pad(ix.dtype, ix.d) > 0) mfma = finite();
     // The automatic int8 shadow (auto_quant): a call of 1-4 dot / cosine queries that the matrix cores would answer on a large finite
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call (build_needed); an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
@@ -407,10 +414,20 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int tile_rows = f8ks ? 16 : (mfma || fused_shape) ? hdb_mfma_tile_rows(ix.dtype, ix.d) : 16;      // (float8 slices: the 16-row tiles of every float8 kernel)
     // float32 rows on the matrix cores multiply in three bf16 parts (hdb_mfma_f32s.hip: 2.7x the rate of the float32 MFMAs, same
     // 1e-5 contract) -- on finite matrices: the parts of an infinite element would cancel to NaN where np.dot keeps the infinity
+    // Two parts keep 16 mantissa bits of a row value, so the product's error is up to 2^-17 |v| |q| whatever the score:
+    //   cosine / pearson divide it by |v| |q| (2^-17 = 7.6e-6 at the very worst, measured 3e-7: inside 1e-5 for every row);
+    //   euclidean adds |v|^2 + |q|^2 before the root and 1 / (1 + .): a score error below 2^-17 as well;
+    //   dot_product keeps it as it is: a row whose score is small against |v| |q| (a selective filter, a large k, data that share a
+    //   dominant direction) misses 1e-5 * max(1, |s|) -- |v| = 20, |q| = 2, |s| < 1: up to 2.3 bands (tests/test_low_score_contract.py).
+    // So dot_product runs on the float32 MFMAs, which exist for every shape the parts have.
+    // The parts of an infinite QUERY element cancel to NaN too, which the parts flavour reports as HDB_Q_UNDERFLOW -- to the exact
+    // re-run.  A call that asks for the exact selection (hdb_topk_exact, exact_req) is that last resort and keeps the parts, and with
+    // them the default call's bits, only while no query of the call holds an infinity: a fact of the queries, so the executor looks
+    // (run_pipeline reads the flags its query preparation left) and multiplies in float32 otherwise.
     bool f32s = false;
     const int f32s_auto = hdb_mfma_f32_split_min_q(ix.d);
     const int f32s_min = f32s_auto > 0 ? (int)(o.f32_split_min_q > 0 ? o.f32_split_min_q : f32s_auto) : 0;       // queries of the CALL (every launch of a call multiplies the same way)
-    if (mfma && ix.dtype == HDB_F32 && o.f32_split && f32s_min > 0 && nq >= f32s_min && nq <= hdb_mfma_f32_split_max_q(ix.d)) f32s = finite();
+    if (mfma && ix.dtype == HDB_F32 && o.f32_split && metric != HDB_DOT && f32s_min > 0 && nq >= f32s_min && nq <= hdb_mfma_f32_split_max_q(ix.d)) f32s = finite();
     // anything else the matrix-core scan takes (5-256 dot / cosine queries, 1-256 euclidean ones), k <= 128: one launch per
     // <= bcap queries does preparation, sample, thresholds, the pass and every query's final sort (hdb_mfma_kernel.h, MODE 2)
     const int bcap = mfma ? hdb_mfma_batch_capacity(ix.dtype, ix.d) : 0;
@@ -444,7 +461,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int64_t f8_lds_first = f8_lds_first_q(o, ix.dtype, ix.d);
     p.f8_lds = mfma && ix.dtype == HDB_F8E4M3 && !full_sort && (f8ks || hdb_mfma_f8_lds_supported(ix.d)) && f8_lds_first > 0 && nq >= f8_lds_first;
     p.stats.f8_lds = p.f8_lds ? 1 : 0;
-    p.exact = exact; p.small = small; p.mfma = mfma; p.f32s = f32s; p.ksplit = ksplit; p.local = local_ok;
+    p.exact = exact; p.exact_req = exact_req; p.small = small; p.mfma = mfma; p.f32s = f32s; p.ksplit = ksplit; p.local = local_ok;
     p.tile_rows = tile_rows; p.s_tiles = s_tiles; p.s_stride = s_stride; p.m = m; p.s_rows = s_rows; p.ld_s = ld_s; p.ld_n = ld_n;
     p.cq_max = cq_max;
     // full sort (k > HDB_MAX_K): all scores of one query, the sort's work array and its scratch live in the same layout

@@ -391,7 +391,8 @@ __global__ __launch_bounds__(256) void hdb_rownorm_kernel(const T* V, int64_t n,
         if ((l16 & 3) == 0 && row < n) {
             const float ss = (float)mine;
             if (ss != ss) atomicOr(nan_flag, 1);
-            else if (ss - ss != 0.f) atomicOr(nan_flag, 2);      // an infinite sum: infinite or huge elements (no bf16-part arithmetic on this matrix)
+            else if (ss - ss != 0.f) atomicOr(nan_flag, HDB_FLAG_INF | HDB_FLAG_L1_WIDE);      // an infinite sum: infinite or huge elements (no bf16-part arithmetic on this matrix)
+            else if (ss > HDB_L1_PK_MAX * HDB_L1_PK_MAX) atomicOr(nan_flag, HDB_FLAG_L1_WIDE);      // an element may exceed half of fp16 range (no packed manhattan differences, hdb_caps.h)
             sqnorm[row] = ss;
             inv_norm[row] = (mine == Acc(0)) ? 1.0f : (float)(Acc(1) / sqrt(mine));
         }

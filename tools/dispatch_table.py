@@ -139,6 +139,22 @@ def rows():
             add("f32", d, 20000, nq, 100, "cosine")
     add("f32", 384, 20000, 16, 100, "cosine", finite=False)
     add("f32", 384, 20000, 2, 100, "cosine", finite=False)
+    # float32 batches as bf16 parts: cosine / euclidean / pearson, never dot_product, never a call that asks for the exact selection
+    for nq in (16, 64):
+        for metric in ("dot", "euclidean", "pearson"):
+            add("f32", 384, 70001, nq, 100, metric)
+    add("f32", 384, 70001, 16, 100, "cosine", exact=True)
+    add("f32", 384, 70001, 16, 100, "dot", exact=True)
+    add("f32", 384, 70001, 16, 100, "dot", opts={"f32_split": 0})
+    for d, nq in ((768, 8), (1024, 16)):
+        for metric in ("dot", "cosine"):
+            add("f32", d, 20000, nq, 100, metric)
+    # widths that ride a wider geometry (fp16 d = 96 -> 128, float32 d = 100 -> 128, d = 300 -> 384): the matrix cores on a finite matrix only
+    for dtype, d in (("f16", 96), ("f32", 100), ("f32", 300)):
+        for nq in (6, 40):
+            for metric in ("dot", "cosine"):
+                add(dtype, d, 20000, nq, 100, metric)
+                add(dtype, d, 20000, nq, 100, metric, finite=False)
     # ---- bfloat16, float64 ----
     for d in (40, 384, 512):
         for nq in (1, 5, 129):
