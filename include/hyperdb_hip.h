@@ -210,8 +210,8 @@ int hdb_recency_bias_twice(const double* dev_ts, const uint8_t* dev_mask, int64_
                            double ts_min, float* dev_out, int device, void* stream);
 
 /* Optional row subset (filters / skip_doc, hyperdb.py:1119-1134,:1258-1308): dev_mask is n bytes,
- * non-zero = row takes part; NULL clears.  Excluded rows score -inf and are never returned
- * while at least k rows are included. */
+ * non-zero = row takes part; NULL clears.  Excluded rows score -inf and are never returned:
+ * with fewer than k rows included the tail is -1 / -inf on every path. */
 int hdb_index_set_row_mask(hdb_index* ix, const uint8_t* dev_mask);
 
 /* Row mask plus the ascending list of the rows it keeps: a selective filter reads only the rows it keeps (hdb_scan.hip, the list

@@ -1059,7 +1059,7 @@ static int run_full_sort(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         if (p.pearson) s2.inv_norm = ix->pscale;
         s2.q0 = q0; s2.bias = ix->bias; s2.scores = e.w.sc1; s2.ld = p.ld_n;
         rc = run_scan(ix, s2, 0, 1, qb, false, false, c.st); if (rc) return rc;
-        LAUNCH_TRY(hdb_launch_full_sort(e.w.sc1, ix->n, c.k, ix->row_base, e.w.work, e.w.temp, e.sort_temp, c.idx + (int64_t)q0 * c.k,
+        LAUNCH_TRY(hdb_launch_full_sort(e.w.sc1, s2.mask, ix->n, c.k, ix->row_base, e.w.work, e.w.temp, e.sort_temp, c.idx + (int64_t)q0 * c.k,
                                         c.score + (int64_t)q0 * c.k, c.st));
     }
     if (c.status) LAUNCH_TRY(hdb_launch_status_nan(e.w.qnan, c.nq, c.status, c.st));     // HDB_Q_NAN survives on this path too

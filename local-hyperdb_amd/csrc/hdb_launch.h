@@ -56,7 +56,7 @@ int hdb_launch_merge(const void* idx_base, int64_t idx_stride, const void* score
 
 // ---- hdb_sort.hip, hdb_rows.hip ----
 int hdb_sort_temp_bytes(int64_t n, size_t* bytes);
-int hdb_launch_full_sort(const float* scores, int64_t n, int64_t k, int64_t row_base, uint32_t* work, void* temp, size_t temp_bytes,
+int hdb_launch_full_sort(const float* scores, const uint8_t* mask, int64_t n, int64_t k, int64_t row_base, uint32_t* work, void* temp, size_t temp_bytes,
                          int64_t* idx_out, float* score_out, void* stream);
 int hdb_launch_gather_rows(const void* V, const int64_t* rows, int64_t m, int row_bytes, void* out, const float* inv_in,
                            const float* sq_in, float* inv_out, float* sq_out, int* nan_flag, void* stream);

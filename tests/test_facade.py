@@ -24,6 +24,15 @@ def _docs(n):
              "timestamp": 1.7e9 + 3600.0 * i} for i in range(n)]
 
 
+def expected_with_recency(orc, V, docs, keep, q, top_k, recency_bias, metric, timestamp_key="timestamp"):
+    """The brute-force tail of reference _execute_query over the documents `keep` selects (hyperdb.py:1555-1575): the first decay
+    is normalised by the newest KEPT document (:1344), oracle.rank applies the second -> (document positions, float64 scores)."""
+    ts = np.array([dd[timestamp_key] for dd in np.array(docs, dtype=object)[keep]])
+    first = recency_bias * np.exp(ts - ts.max())
+    oi, osc = orc.rank(V[keep], q, top_k=top_k, metric=metric, timestamps=first, recency_bias=recency_bias)
+    return np.nonzero(keep)[0][oi], osc
+
+
 # ------------------------------------------------------------------------------------------------ CPU
 def test_constructor_validation_and_cache_key():
     from hyperdb import HyperDB
@@ -305,10 +314,8 @@ def test_filters_with_recency_use_the_filtered_maximum():
     keep = np.array([i < 300 and i % 2 == 1 for i in range(n)])
     res = db.query(q, top_k=6, recency_bias=0.8, timestamp_key="timestamp", metric="cosine_similarity",
                    filters=[("skip_doc", -100), ("metadata", {"info.type": "odd"})])
-    ts = np.array([dd["timestamp"] for dd in np.array(docs, dtype=object)[keep]])
-    first = 0.8 * np.exp(ts - ts.max())
-    oi, osc = orc.rank(V[keep], q, top_k=6, metric="cosine_similarity", timestamps=first, recency_bias=0.8)
-    assert [r[2] for r in res] == list(np.nonzero(keep)[0][oi])
+    oi, osc = expected_with_recency(orc, V, docs, keep, q, top_k=6, recency_bias=0.8, metric="cosine_similarity")
+    assert [r[2] for r in res] == list(oi)
     assert np.allclose([r[1] for r in res], osc, atol=1e-5)
     assert max(r[1] for r in res) > 0.5                         # the recency term acts (it would be ~0 with the global max)
     with pytest.raises(ValueError, match="All timestamps must be populated"):
