@@ -33,8 +33,11 @@ typedef struct hdb_index hdb_index;
  * (torch.float8_e4m3fn: 1 sign, 4 exponent, 3 mantissa bits, bias 7, no infinities, 0x7F / 0xFF = NaN; one byte per element).
  * HDB_I8 = 7 is a matrix of signed 8-bit integers (np.int8 / torch.int8, two's complement, one byte per element): the integers ARE
  * the matrix -- no scale, no zero point, no NaN code, every value in [-128, 127] widens to float32 exactly.
- * Codes 4 and 6 are unassigned and refused by hdb_index_create, like every other value not listed here. */
-enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5, HDB_I8 = 7 };
+ * HDB_B1 = 10 is a matrix of packed bits, one bit per element: `d` counts bits and is a multiple of 32, a row is d / 32 uint32 words
+ * (row-major, 4-byte aligned) and element e of a row is bit e & 31 of word e >> 5 -- np.packbits(.., bitorder="little") read as
+ * little-endian words, the bit order of the sign cache.  The matrix is the 0/1 matrix the bits stand for: 1.0 where the bit is set.
+ * Codes 4, 6, 8 and 9 are unassigned and refused by hdb_index_create, like every other value not listed here. */
+enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5, HDB_I8 = 7, HDB_B1 = 10 };
 
 /* metric strings of hyperDB_ranking_algorithm_sort's dispatch table (ranking_algorithm.py:155-163). */
 enum hdb_metric {
@@ -348,7 +351,21 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     status words are those of a bfloat16 index over the widened matrix.  Other widths stay on the VALU scan.
  *   - never: the single launches of the matrix-core paths, the manhattan tile kernel, K slices, the LDS flavour, the int8 shadow and
  *     its plane (hdb_index_quantize returns HDB_ERR_UNSUPPORTED: one byte per element already).
- * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch). */
+ * Stats: mfma = 1 on the matrix-core path, fused = 0 (3 for the bit metrics' single launch).
+ * packed-bit matrices (HDB_B1).  Layout: n x d / 32 uint32 words, element e of a row = bit e & 31 of word e >> 5; d % 32 == 0
+ * (HDB_ERR_ARG otherwise) and d <= 7680.  Queries are float32 x d.  Contract: every metric is the reference's arithmetic on the 0/1
+ * float32 matrix the bits stand for -- scores within 1e-5 * max(1, |s|), hamming exact (x > 0 is the bit itself), jaccard 1e-6; no
+ * scale, no +-1 reading, no centring; hdb_index_has_nan is 0.  Row caches: ||v||^2 is the row's popcount, 1/||v|| = 1/sqrt(pop)
+ * (0 -> 1), the pearson scale comes from pop and d (an all-0 or all-1 row is a constant row: NaN), the sign cache is a re-layout
+ * of the words.
+ *   - dot / cosine / pearson / euclidean / manhattan: hdb_bscan.hip, one thread per row, through the small, sampled, exact and
+ *     full-sort pipelines.  The score of a row is sum_j (b_j ? A_j : B_j) over the per-element terms themselves (A = q, B = 0 q;
+ *     (1 - q)^2, q^2; |1 - q|, |q|), four elements at a time from a per-query table in LDS, in ONE summation order per row: the
+ *     sample pass, the filter pass, hdb_topk_exact and hdb_scores return the same float32 bits for a row, whatever the grid.
+ *   - hamming / jaccard: the bit kernels that every dtype uses, on the sign cache; such calls plan exactly as on an int8 index.
+ *   - never: the matrix cores, the 1-4-query and batched single launches, the manhattan tile kernel, the int8 shadow and its plane
+ *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit).
+ * Stats: mfma = 0, quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics' single launch). */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 

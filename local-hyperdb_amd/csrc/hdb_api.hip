@@ -139,7 +139,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 107; }
+extern "C" int hdb_version(void) { return 108; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -168,7 +168,8 @@ static double quant_gamma(int d) {
 // gamma_m of the matrix-core sum (hdb_quant.hip, bound (2m)); the per-row cache E_r takes the larger of the two
 static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -22); }
 static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
-static size_t quant_elem(const hdb_index* ix) { return (size_t)hdb_elem_bytes(ix->dtype); }
+// bytes of one stored row (hdb_row_bytes, hdb_common.h: the one source of every row pitch)
+static size_t row_pitch(const hdb_index* ix) { return (size_t)hdb_row_bytes(ix->dtype, ix->d); }
 #define HDB_QSTAT_WORDS 4
 // the device words of hdb_index::qstat, zeroed on `st`; qstat stays null when the allocation itself fails
 static hipError_t qstat_alloc(hdb_index* ix, hipStream_t st) {
@@ -241,7 +242,7 @@ static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t 
 // quantize rows [row0, row0 + m) of the current matrix into the shadow, and derive their part of the plane
 static int quant_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
     if (m <= 0) return HDB_OK;
-    const char* src = (const char*)ix->V + (size_t)row0 * ix->d * quant_elem(ix);
+    const char* src = (const char*)ix->V + (size_t)row0 * row_pitch(ix);
     LAUNCH_TRY(hdb_launch_quant_rows(src, m, ix->d, ix->dtype, ix->qP, ix->qcodes + (size_t)row0 * ix->qP, ix->qaux + (size_t)row0 * 3,
                                      ix->nan_flag, quant_gamma_rows(ix->d), st));
     return plane_rows(ix, row0, m, st);
@@ -264,6 +265,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     if (ix->dtype == HDB_BF16 && !ix->opt.bf16_quant) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: bfloat16 (bf16) matrices have no int8 shadow");
     if (ix->dtype == HDB_F8E4M3) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: float8 (e4m3) matrices have no int8 shadow: one byte per element already");
     if (ix->dtype == HDB_I8) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: int8 matrices have no int8 shadow: one byte per element already");
+    if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: packed-bit matrices have no int8 shadow: one bit per element already");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32 && ix->dtype != HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     HIP_TRY(qstat_alloc(ix, st));
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
@@ -311,9 +313,11 @@ extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, i
     if (!out) return fail(HDB_ERR_ARG, "hdb_index_create: out is null");
     if (n < 0 || d <= 0) return fail(HDB_ERR_ARG, "hdb_index_create: need n >= 0 and d > 0");
     if (n > 0 && !dev_V) return fail(HDB_ERR_ARG, "hdb_index_create: matrix pointer is null");
-    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3 && dtype != HDB_I8) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3/i8");
+    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3 && dtype != HDB_I8 && dtype != HDB_B1) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3/i8/b1");
+    if (dtype == HDB_B1 && d % 32 != 0) return fail(HDB_ERR_ARG, "hdb_index_create: a packed-bit matrix needs d (bits per row) to be a multiple of 32");
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_create: at most 2^32-2 rows per shard");
     if ((int64_t)d * 8 > 60 * 1024) return fail(HDB_ERR_ARG, "hdb_index_create: d too large for the query LDS tile");
+    if (dtype == HDB_B1 && n > 0 && (reinterpret_cast<uintptr_t>(dev_V) & 3) != 0) return fail(HDB_ERR_ARG, "hdb_index_create: a packed-bit matrix must be 4-byte aligned");
     HIP_TRY(hipSetDevice(device));
     hdb_index* ix = new hdb_index();
     ix->V = dev_V; ix->n = n; ix->d = d; ix->dtype = dtype; ix->device = device; ix->row_base = row_base;
@@ -378,8 +382,7 @@ extern "C" int hdb_index_extend(hdb_index* ix, int64_t new_n, void* stream) {
         if (ix->inv_norm) { HIP_TRY(hipFree(ix->inv_norm)); HIP_TRY(hipFree(ix->sqnorm)); }
         ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
     }
-    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
-    const char* tail = (const char*)ix->V + (size_t)old_n * ix->d * elem;
+    const char* tail = (const char*)ix->V + (size_t)old_n * row_pitch(ix);
     LAUNCH_TRY(hdb_launch_rownorm(tail, new_n - old_n, ix->d, ix->dtype, ix->inv_norm + old_n, ix->sqnorm + old_n, ix->nan_flag, st));
     ix->n = new_n;
     if (ix->qmode == HDB_QUANT_I8) {                   // the shadow: the appended rows only
@@ -403,13 +406,12 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     if (m > 0 && dev_V_out == ix->V) return fail(HDB_ERR_ARG, "hdb_index_gather: the gather is out of place");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     float *inv2 = nullptr, *sq2 = nullptr;
     const int64_t rows = m + m / 4 + 64;
     HIP_TRY(hipMalloc((void**)&inv2, rows * sizeof(float)));
     HIP_TRY(hipMalloc((void**)&sq2, rows * sizeof(float)));
     HIP_TRY(hipMemsetAsync(ix->nan_flag, 0, sizeof(int), st));
-    int rc = hdb_launch_gather_rows(ix->V, dev_rows, m, (int)(ix->d * elem), dev_V_out, ix->inv_norm, ix->sqnorm, inv2, sq2,
+    int rc = hdb_launch_gather_rows(ix->V, dev_rows, m, (int)row_pitch(ix), dev_V_out, ix->inv_norm, ix->sqnorm, inv2, sq2,
                                     ix->nan_flag, st);
     // the shadow travels with its rows too
     int8_t* qc2 = nullptr; float* qa2 = nullptr;
@@ -659,7 +661,6 @@ static bool metric_ok(int metric) { return metric >= HDB_DOT && metric <= HDB_EU
 
 static int ensure_pscale(hdb_index* ix, hipStream_t st) {
     if (ix->pscale_valid) return HDB_OK;
-    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     int64_t keep = ix->pscale ? std::min(ix->pscale_done, ix->n) : 0;          // rows whose scale is still good (appended matrix)
     if (ix->n > ix->pscale_rows) {
         const int64_t rows = ix->n + ix->n / 4 + 64;
@@ -670,7 +671,7 @@ static int ensure_pscale(hdb_index* ix, hipStream_t st) {
         ix->pscale = p2; ix->pscale_rows = rows;
     }
     if (ix->n > keep)
-        LAUNCH_TRY(hdb_launch_rowstats((const char*)ix->V + (size_t)keep * ix->d * elem, ix->n - keep, ix->d, ix->dtype, ix->pscale + keep, st));
+        LAUNCH_TRY(hdb_launch_rowstats((const char*)ix->V + (size_t)keep * row_pitch(ix), ix->n - keep, ix->d, ix->dtype, ix->pscale + keep, st));
     ix->pscale_done = ix->n;
     ix->pscale_valid = true;
     return HDB_OK;
@@ -680,7 +681,6 @@ static int ensure_bits(hdb_index* ix, hipStream_t st) {
     if (ix->bits_valid) return HDB_OK;
     const int W = (ix->d + 31) / 32;
     if (W > 512) return fail(HDB_ERR_UNSUPPORTED, "hamming: d > 16384 not supported");
-    const size_t elem = (size_t)hdb_elem_bytes(ix->dtype);
     const int64_t npad = align_up((size_t)std::max<int64_t>(ix->n, 4), 256);      // whole 256-row blocks (hdb_bits_word)
     // rows packed before the matrix grew stay where they are: the layout is a sequence of 256-row blocks, so a bigger buffer takes
     // the old blocks as a prefix (hdb_index_extend / HyperDB.add: the next bit-metric call packs the appended rows only)
@@ -697,7 +697,7 @@ static int ensure_bits(hdb_index* ix, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(ix->bits, 0, (size_t)ix->bits_npad * W * sizeof(uint32_t), st));
     }
     if (ix->n > keep)
-        LAUNCH_TRY(hdb_launch_signpack((const char*)ix->V + (size_t)keep * ix->d * elem, ix->n - keep, ix->d, ix->dtype, keep, ix->bits, st));
+        LAUNCH_TRY(hdb_launch_signpack((const char*)ix->V + (size_t)keep * row_pitch(ix), ix->n - keep, ix->d, ix->dtype, keep, ix->bits, st));
     ix->bits_done = ix->n;
     ix->bits_valid = true;
     return HDB_OK;

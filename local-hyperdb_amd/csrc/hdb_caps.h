@@ -24,6 +24,31 @@ static inline int hdb_scan_auto_blocks(int dtype, int row_bytes, bool vec, bool 
     return wide_rows ? 256 : 512;
 }
 
+// ---- hdb_bscan.hip: float32 queries against packed-bit rows (HDB_B1) ----
+// One thread per row.  A query lives in LDS as a NIBBLE TABLE, T[d / 4][16] floats = 16 d bytes: entry [j][m] is the sum of the four
+// per-element terms of elements 4 j .. 4 j + 3 for the bit pattern m, so a row costs d / 4 reads.  QT queries per pass have all
+// their tables resident; the rule below takes the largest QT of 4 / 2 / 1 whose tables fit HDB_BSCAN_TABLE_BYTES, the 60 KiB every
+// scan kernel allows its queries -- with the 4-KiB survivor stage beside them two workgroups fit the 160 KiB of a CU:
+//   d <= 960: 4 queries per pass, d <= 1920: 2, d <= 3840: 1.
+// Wider rows (up to the 7680 hdb_index_create admits) keep the two terms of every element in LDS instead, 8 d bytes <= 60 KiB, one
+// query per pass, and select per bit in registers (QT = 0 here: the fallback; it forms the same nibble sums in the same order).
+#define HDB_BSCAN_TABLE_BYTES (60 * 1024)
+static inline int hdb_bscan_qt(int d) {
+    if (d <= 0 || d % 32 != 0) return -1;                                 // no such row
+    for (int qt = 4; qt >= 1; qt >>= 1)
+        if ((int64_t)qt * 16 * d <= HDB_BSCAN_TABLE_BYTES) return qt;
+    return (int64_t)8 * d <= HDB_BSCAN_TABLE_BYTES ? 0 : -1;
+}
+// dynamic LDS of a launch: the tables of the queries of one pass, or the fallback's pairs of terms
+static inline int hdb_bscan_lds_bytes(int d, int qt) { return qt > 0 ? qt * 16 * d : 8 * d; }
+// workgroups (256 threads, one row each) of a launch when the caller sets no limit: as many per CU as the LDS holds beside the
+// 4-KiB stage, eight at most (the waves a SIMD takes)
+static inline int hdb_bscan_auto_blocks(int d, int qt, int cus) {
+    int per_cu = (160 * 1024) / (hdb_bscan_lds_bytes(d, qt) + 5 * 1024);
+    per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
+    return per_cu * (cus > 0 ? cus : 1);
+}
+
 // ---- hdb_mfma_ksplit.hip: K slices of rows too wide for one wave's query fragments ----
 // The slice list of a width: slice s covers `width[s]` elements of every row from byte `off[s]` of the stored row on; the widths
 // add up to d and every one of them is a slice geometry that is instantiated for the dtype (float32 512 / 768, fp16 1024 / 1536,
@@ -185,10 +210,9 @@ static inline int mfma_exact_tile_rows(int dtype, int d) {
     if (dtype == HDB_BF16 && d > 0 && hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;     // 640 .. 4096: K slices of 16-row stages (hdb_mfma_bf16_ks.hip)
     if (dtype == HDB_BF16) return d > 0 ? hdb_mfma_bf16_tile_rows(d) : 0;
     if (dtype == HDB_F8E4M3 || dtype == HDB_I8) return d > 0 ? hdb_mfma_f8_tile_rows(d) : 0;      // (int8: the float8 kernel with another row converter, hdb_mfma_i8.hip)
-    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;
-    if (!elem || d <= 0) return 0;
+    if ((dtype != HDB_F16 && dtype != HDB_F32) || d <= 0) return 0;       // (packed bits, float64: no matrix cores)
     if (hdb_mfma_ksplit_slices(dtype, d) > 0) return 16;                  // wide rows: K slices of 16-row stages (hdb_mfma_ksplit.hip)
-    const int row_bytes = d * elem;
+    const int row_bytes = (int)hdb_row_bytes(dtype, d);
     if (row_bytes % 256 != 0 || row_bytes > 3072) return 0;          // d <= 1536 (fp16) / 768 (fp32)
     if (dtype == HDB_F32 && d != 128 && d != 256 && d != 384 && d != 512 && d != 768) return 0;     // instantiated fp32 widths
     for (int r = 64; r >= 16; r >>= 1)
@@ -199,8 +223,8 @@ static inline int mfma_exact_tile_rows(int dtype, int d) {
 // Rows of any width that is a multiple of 16 bytes and has no geometry of its own ride the next wider one as a single K slice
 // (hdb_mfma_anyd.h): -> that width, or 0.  fp16 d % 8 == 0 up to 1024, float32 d % 4 == 0 up to 768.
 static inline int hdb_mfma_anyd_pad(int dtype, int d) {
-    const int elem = dtype == HDB_F16 || dtype == HDB_F32 ? hdb_elem_bytes(dtype) : 0;      // (bfloat16: its own widths only)
-    if (!elem || d <= 0 || (d * elem) % 16 != 0 || mfma_exact_tile_rows(dtype, d) > 0) return 0;
+    if (dtype != HDB_F16 && dtype != HDB_F32) return 0;      // (bfloat16: its own widths only)
+    if (d <= 0 || hdb_row_bytes(dtype, d) % 16 != 0 || mfma_exact_tile_rows(dtype, d) > 0) return 0;
     static const int w16[] = {128, 256, 384, 512, 768, 1024}, w32[] = {128, 256, 384, 512, 768};
     if (dtype == HDB_F16) { for (int w : w16) if (w >= d) return w; }
     else { for (int w : w32) if (w >= d) return w; }

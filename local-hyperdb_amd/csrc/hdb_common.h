@@ -8,9 +8,16 @@
 
 // ---- element types -------------------------------------------------------------------------------
 // Bytes of one stored matrix element per hdb_dtype (include/hyperdb_hip.h: 0 float16, 1 float32, 2 float64, 3 bfloat16, 5 float8
-// e4m3, 7 int8; 4 and 6 are unassigned); 0 = no such dtype.  Every row pitch in the library comes from here.
+// e4m3, 7 int8; 4, 6, 8 and 9 are unassigned); 0 = no such dtype -- and 0 for 10, packed bits: a bit has no whole-byte size.
 __host__ __device__ __forceinline__ int hdb_elem_bytes(int dtype) {
     return dtype == 0 ? 2 : dtype == 1 ? 4 : dtype == 2 ? 8 : dtype == 3 ? 2 : (dtype == 5 || dtype == 7) ? 1 : 0;
+}
+// Bytes of one stored row of d elements: every row pitch in the library comes from here.  Packed bits (10): d / 8, for whole 32-bit
+// words only; 0 = no such dtype, or a width the dtype does not take.
+__host__ __device__ __forceinline__ int64_t hdb_row_bytes(int dtype, int d) {
+    if (d <= 0) return 0;
+    if (dtype == 10) return d % 32 == 0 ? (int64_t)(d / 8) : 0;
+    return (int64_t)d * hdb_elem_bytes(dtype);
 }
 // A bfloat16 as it lies in memory: the upper 16 bits of the float32 of the same value, so widening is a shift and exact.
 struct hdb_bf16 { unsigned short bits; };

@@ -279,7 +279,7 @@ extern "C" int hdb_launch_l1_tile(const ScanArgs* args, int dtype, int mode, int
     if (a.mask || a.tile_stride != 1) return (int)hipErrorNotSupported;
     if (dtype != HDB_F16 && dtype != HDB_F32) return (int)hipErrorNotSupported;      // (bfloat16 / float8 / float64 rows: the 4-query scan)
     const int cus = hdb_cu_count();
-    const int rowb = a.d * hdb_elem_bytes(dtype);
+    const int rowb = (int)hdb_row_bytes(dtype, a.d);
     const int R = rowb <= 768 ? 64 : rowb <= 1536 ? 32 : 16;
     const int64_t tiles = (a.n + R - 1) / R;
     int blocks = (int)(tiles < cus ? tiles : cus);

@@ -40,6 +40,9 @@ int hdb_launch_recency2(const double* ts, const uint8_t* mask, int64_t n, double
 int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, float* pscale, void* stream);
 int hdb_launch_qcentre(const void* Q, int nq, int d, bool f64, void* Qc, float* qscale, void* stream);
 
+// ---- hdb_bscan.hip: float32 queries against packed-bit rows (HDB_B1); reached from hdb_launch_scan ----
+int hdb_launch_bscan(const ScanArgs* args, int mode, int nq_launch, int max_blocks, void* stream);
+
 // ---- hdb_select.hip: thresholds, collection, finalize, merge ----
 int hdb_launch_hist(const float* scores, int64_t n, int64_t ld, int nq, uint32_t* hist, int pass, uint32_t k, void* stream);
 int hdb_launch_thr(const uint32_t* hist, int nq, int npass, uint32_t m, uint32_t sample_n, float* thr, uint32_t* cnt, void* stream);

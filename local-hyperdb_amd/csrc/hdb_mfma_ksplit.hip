@@ -20,10 +20,9 @@ extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode,
     const KsGeom g = dtype == HDB_F8E4M3 ? ks_geom_f8(args->d) : ks_geom(dtype, args->d);       // (float8: the opt-in list, no part of ks_geom)
     if (!g.slices || !args->ks_partial_out) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
-    const int es = hdb_elem_bytes(dtype);
     for (int s = 0; s < g.slices; ++s) {
         ScanArgs a = *args;
-        a.ks_pitch = (int64_t)args->d * es; a.ks_off = g.off[s]; a.ks_dfull = args->d;
+        a.ks_pitch = hdb_row_bytes(dtype, args->d); a.ks_off = g.off[s]; a.ks_dfull = args->d;
         a.ks_partial_in = s == 0 ? nullptr : args->ks_partial_out;
         const int m = s + 1 < g.slices ? 3 : mode;
         const int w = g.width[s];

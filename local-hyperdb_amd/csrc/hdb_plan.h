@@ -272,6 +272,7 @@ static inline bool subset_metric(int metric) {
 // the call's side of the rule: m * ceil(nq / 4) * ratio <= n on a matrix of at least min_n rows
 static inline bool subset_rule(const TopkFacts& ix, const hdb_options& o, const TopkCall& c) {
     if (ix.subset_m <= 0 || !o.use_subset || !subset_metric(c.metric) || c.nq < 1) return false;
+    if (ix.dtype == HDB_B1) return false;       // packed-bit rows have no list flavour (hdb_bscan.hip): the mask serves, bit for bit
     if (ix.n < (o.subset_min_n >= 0 ? o.subset_min_n : (int64_t)HDB_SUBSET_MIN_ROWS)) return false;
     const int64_t ratio = o.subset_ratio >= 1 ? std::min<int64_t>(o.subset_ratio, (int64_t)1 << 30) : (int64_t)HDB_SUBSET_RATIO;
     return ix.subset_m <= ix.n / (((int64_t)c.nq + 3) / 4 * ratio);

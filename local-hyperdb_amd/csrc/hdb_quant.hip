@@ -1204,8 +1204,8 @@ extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const f
     RescoreArgs a;
     a.V = V; a.d = d; a.Q = Q; a.metric = metric; a.inv_norm = inv_norm; a.qinv = qinv; a.bias = bias; a.mask = mask;
     a.cand = cand; a.cnt = cnt; a.cap = cap;
-    const int elem = hdb_elem_bytes(dtype);
-    a.row_bytes = d * elem;
+    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_BF16) return (int)hipErrorInvalidValue;      // (the dtypes that have a shadow)
+    a.row_bytes = (int32_t)hdb_row_bytes(dtype, d);
     a.nchunks = a.row_bytes / 16;
     // the same choice as hdb_launch_scan: 16-byte pieces when rows are whole pieces of an aligned matrix
     const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(V) & 15) == 0) && ((size_t)d * 4 <= 60 * 1024);

@@ -13,6 +13,7 @@
 // type; per-row sums are finished with four DPP row rotations (no LDS, no shuffles).
 // Algorithmic bytes per row = row_bytes (+4 for the cached 1/||v||, +4 bias when set).
 #include "hdb_common.h"
+#include "hdb_emit.h"
 #include "../../include/hyperdb_hip.h"
 
 template <typename T> struct Elem;
@@ -70,66 +71,7 @@ __device__ __forceinline__ float hdb_to_f(hdb_i8 v) { return hdb_i8_to_f(v); }
 __device__ __forceinline__ float hdb_to_f(float v) { return v; }
 __device__ __forceinline__ double hdb_to_f(double v) { return v; }
 
-// Survivors of a filter pass (MODE 1) wait in LDS, per block and query slot, and reach the global candidate lists with ONE atomic
-// per block and query at the end of the block's tiles.  A returning atomic per survivor on the per-query counters (one cache line:
-// ~88 per us) was what small matrices spent their time in: n = 200k x 100 float32, 16 queries, ~2 k survivors each -- 374 us of
-// filter pass for 11 us of matrix; the N <= 8192 path, where every row survives, likewise (tools/diag_small_valu.py).
-#define HDB_STAGE_CAP 128
-struct HdbStage {
-    unsigned long long buf[4][HDB_STAGE_CAP];      // up to four query slots per block (QT, QH <= 4)
-    unsigned int cnt[4];
-    unsigned int base;
-};
-__device__ __forceinline__ void hdb_stage_init(HdbStage& st) { if (threadIdx.x < 4) st.cnt[threadIdx.x] = 0u; }   // (before a block barrier)
-// every thread of the block, after its last tile; slot s holds the survivors of local query ql0 + s
-__device__ __forceinline__ void hdb_stage_flush(const ScanArgs& a, HdbStage& st, int ql0, int nslots) {
-    __syncthreads();
-    for (int s = 0; s < nslots; ++s) {
-        const unsigned int have = min(st.cnt[s], (unsigned int)HDB_STAGE_CAP);        // (block-uniform)
-        if (have == 0u) continue;
-        if (threadIdx.x == 0) st.base = atomicAdd(&a.cnt[(ql0 + s) * HDB_CNT_STRIDE], have);
-        __syncthreads();
-        const unsigned int base = st.base;
-        for (unsigned int e = threadIdx.x; e < have; e += blockDim.x)
-            if (base + e < a.cap) a.cand[(int64_t)(ql0 + s) * a.cap + base + e] = st.buf[s][e];
-        __syncthreads();
-    }
-}
-
-// Shared epilogue: raw row sum -> final score of hyperDB_ranking_algorithm_sort, then store / filter.
-template <int MODE, typename Acc>
-__device__ __forceinline__ void hdb_emit(const ScanArgs& a, int q, int64_t row, int64_t out_i, Acc sum, HdbStage* stg = nullptr, int slot = 0) {
-    float s;
-    if (a.metric == HDB_EUCLIDEAN) {
-        s = (float)(Acc(1) / (Acc(1) + sqrt(sum)));                       // 1/(1+||v-q||), :49-51
-    } else if (a.metric == HDB_MANHATTAN) {
-        s = (float)(Acc(1) / (Acc(1) + sum));                             // 1/(1+sum|v-q|), :59-60
-    } else if (a.metric == HDB_EUCLIDEAN_DIST) {
-        s = (float)sqrt(sum);
-    } else if (a.metric == HDB_COSINE) {
-        s = (float)sum * a.inv_norm[row] * a.qinv[q];                      // :37-41 with cached norms
-    } else {
-        s = (float)sum;                                                    // dot / hamming
-    }
-    if (a.bias) s += a.bias[row];                                          // recency, :186
-    const bool masked = a.mask && !a.mask[row];                            // filtered-out row
-    if (masked) s = -INFINITY;
-    if (!a.raw) s = hdb_canon(s);                                          // NaN -> -inf, :174
-    if (MODE == 0) {
-        a.scores[(int64_t)(q - a.q0) * a.ld + out_i] = s;
-    } else {
-        const int ql = q - a.q0;
-        if (!masked && s >= a.thr[ql]) {
-            const unsigned long long ent = hdb_pack(s, (uint32_t)row);
-            if (stg) {
-                const unsigned int lp = atomicAdd(&stg->cnt[slot], 1u);              // LDS
-                if (lp < HDB_STAGE_CAP) { stg->buf[slot][lp] = ent; return; }
-            }
-            const uint32_t pos = atomicAdd(&a.cnt[ql * HDB_CNT_STRIDE], 1u);         // the slot is full: straight to the global list
-            if (pos < a.cap) a.cand[(int64_t)ql * a.cap + pos] = ent;
-        }
-    }
-}
+// The survivor stage of a filter pass (HdbStage) and the shared epilogue (hdb_emit): hdb_emit.h, shared with hdb_bscan.hip.
 
 // ------------------------------------------------------------------------------------------------
 // Vector scan: rows are multiples of 16 bytes and V is 16-byte aligned.
@@ -638,10 +580,11 @@ static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec
 
 // Entry used by hdb_api.hip.  mode: 0 = write scores, 1 = threshold filter.
 extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream) {
+    if (dtype == HDB_B1) return hdb_launch_bscan(args, mode, nq_launch, max_blocks, stream);      // packed-bit rows: hdb_bscan.hip
     ScanArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     const int elem = hdb_elem_bytes(dtype);
-    a.row_bytes = a.d * elem;
+    a.row_bytes = (int32_t)hdb_row_bytes(dtype, a.d);
     a.nchunks = a.row_bytes / 16;
     const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(a.V) & 15) == 0) &&
                      ((size_t)a.d * (elem == 8 ? 8 : 4) <= 60 * 1024);
@@ -688,9 +631,52 @@ extern "C" int hdb_launch_list_rows(unsigned long long* cand, const uint32_t* cn
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Packed-bit rows (HDB_B1: d / 32 words per row, element e = bit e & 31 of word e >> 5; the matrix is the 0/1 matrix the bits stand
+// for).  One thread per row.  ||v||^2 is the popcount -- the integer an int8 index over the same 0/1 values sums to, so 1/||v||
+// has that index's bits; the matrix is always finite: the flag word is not touched.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int hdb_b1_row_pop(const uint32_t* p, int W) {
+    int pop = 0;
+    for (int w = 0; w < W; ++w) pop += __popc(p[w]);
+    return pop;
+}
+__global__ __launch_bounds__(256) void hdb_b1_rownorm_kernel(const uint32_t* V, int64_t n, int W, float* inv_norm, float* sqnorm) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const float ss = (float)hdb_b1_row_pop(V + r * W, W);
+        sqnorm[r] = ss;
+        inv_norm[r] = (ss == 0.f) ? 1.0f : (float)(1.f / sqrt(ss));
+    }
+}
+// pearson row scale 1/(sd d) from the popcount: mean = pop / d, sum of centred squares = pop (1 - mean)^2 + (d - pop) mean^2, in
+// float64; an all-0 or all-1 row is a constant row: NaN, the reference's rule (hdb_rowstats_kernel)
+__global__ __launch_bounds__(256) void hdb_b1_rowstats_kernel(const uint32_t* V, int64_t n, int W, int d, float* pscale) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const int pop = hdb_b1_row_pop(V + r * W, W);
+        const double mean = (double)pop / (double)d, up = 1.0 - mean;
+        const double ss = (double)pop * up * up + (double)(d - pop) * mean * mean;
+        const double sd = sqrt(ss / (double)d);
+        pscale[r] = (pop == 0 || pop == d || sd == 0.0) ? NAN : (float)(1.0 / (sd * (double)d));
+    }
+}
+// the sign cache of a packed-bit matrix is a re-layout: x > 0 is the bit itself
+__global__ __launch_bounds__(256) void hdb_b1_signpack_kernel(const uint32_t* V, int64_t n, int W, int64_t row0, uint32_t* bits) {
+    const int64_t total = n * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / W;
+        const int w = (int)(i - r * W);
+        bits[hdb_bits_word(row0 + r, w, W)] = V[i];
+    }
+}
+
 extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, float* inv_norm, float* sqnorm,
                                   int* nan_flag, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (dtype == HDB_B1) {
+        if (d % 32 != 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_b1_rownorm_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, inv_norm, sqnorm);
+        return (int)hipGetLastError();
+    }
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rownorm_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, inv_norm, sqnorm, nan_flag);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rownorm_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, inv_norm, sqnorm, nan_flag);
@@ -716,6 +702,11 @@ extern "C" int hdb_launch_qprep(const void* Q, int nq, int d, bool f64, float* q
 
 extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, int64_t row0, uint32_t* bits, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (dtype == HDB_B1) {
+        if (d % 32 != 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_b1_signpack_kernel, dim3(hdb_grid_for(n * (d / 32), 256, 4096)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, row0, bits);
+        return (int)hipGetLastError();
+    }
     if (d % 32 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0) {
         const int blocks = hdb_grid_for((n + 7) / 8, 4, 4096);      // a wave per eight rows
         if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
@@ -861,6 +852,11 @@ __global__ __launch_bounds__(64) void hdb_qcentre_kernel(const Acc* Q, int nq, i
 
 extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, float* pscale, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (dtype == HDB_B1) {
+        if (d % 32 != 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_b1_rowstats_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, d, pscale);
+        return (int)hipGetLastError();
+    }
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
     if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rowstats_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, pscale);
     else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rowstats_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, pscale);

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("HYPERDB_HIP_LIB") or os.path.join(os.path.dirname(_HE
 HDB_F16, HDB_F32, HDB_F64, HDB_BF16 = 0, 1, 2, 3
 HDB_F8E4M3 = 5                          # OCP float8 e4m3 (torch.float8_e4m3fn); 4 is unassigned and refused by the library
 HDB_I8 = 7                              # signed 8-bit integers (np.int8 / torch.int8), on request: storage="int8"; 6 is unassigned
+HDB_B1 = 10                             # packed bits, one bit per element, on request: storage="bits"; 8 and 9 are unassigned
 METRIC_IDS = {
     "dot_product": 0,
     "cosine_similarity": 1,
@@ -135,14 +136,96 @@ F8_MAX = 448.0                          # largest finite e4m3 magnitude
 # tensor is widened to float64 like every other integer input (to_device_matrix), with it the bytes are the matrix
 _STORED2HDB = dict(_TORCH2HDB)
 _STORED2HDB[torch.int8] = HDB_I8
-STORAGE_MODES = (None, "int8")
+# ... and torch.uint8: the packed rows of a bits index (storage="bits"); without the keyword a uint8 input is widened to float64
+_STORED2HDB[torch.uint8] = HDB_B1
+STORAGE_MODES = (None, "int8", "bits")
+BITORDERS = ("big", "little")
+BITS_SINGLE_INDEX = ("storage='bits' is built for a single index on one device only (GpuIndex, register_vectors without "
+                     "devices=): no GpuGroup, no sharded index, no HyperDB facade")
 
 
 def storage_mode(storage):
-    """A ``storage=`` argument: None (the input's own dtype policy) or "int8"; anything else raises ValueError."""
+    """A ``storage=`` argument: None (the input's own dtype policy), "int8" or "bits"; anything else raises ValueError."""
     if storage is not None and not isinstance(storage, str) or storage not in STORAGE_MODES:
-        raise ValueError(f"storage must be None or 'int8', got {storage!r}")
+        raise ValueError(f"storage must be None, 'int8' or 'bits', got {storage!r}")
     return storage
+
+
+def bit_order(bitorder):
+    """A ``bitorder=`` argument: "big" (np.packbits' default, what embedding exports use) or "little"."""
+    if bitorder not in BITORDERS:
+        raise ValueError(f"bitorder must be 'big' or 'little', got {bitorder!r}")
+    return bitorder
+
+
+def pack_bits(X, bitorder="big"):
+    """Any numeric or bool ``[n, d]`` -> packed uint8 ``[n, d/8]`` by ``X > 0``, the reference's own binarisation
+    (check_and_binarize_vectors): what storage="bits" takes.  d must be a multiple of 32 (ValueError otherwise)."""
+    bit_order(bitorder)
+    if isinstance(X, torch.Tensor):
+        t = X.detach().cpu()
+        if t.dtype in (torch.bfloat16, torch.float16, _F8):
+            t = t.to(torch.float32)
+        X = t.numpy()
+    a = np.asarray(X)
+    if a.dtype != np.bool_ and (not np.issubdtype(a.dtype, np.number) or np.issubdtype(a.dtype, np.complexfloating)):
+        raise ValueError("pack_bits: vectors must be numeric or bool")
+    if a.ndim != 2:
+        raise ValueError(f"pack_bits: vectors must be 2-D (N x d), got shape {tuple(a.shape)}")
+    if a.shape[1] == 0 or a.shape[1] % 32 != 0:
+        raise ValueError(f"pack_bits: d must be a multiple of 32, got {a.shape[1]}")
+    bits = a if a.dtype == np.bool_ else a > 0
+    return np.packbits(bits, axis=1, bitorder=bitorder)
+
+
+def reverse_bits8(t):
+    """Every byte of a torch.uint8 tensor with its bits reversed (big <-> little bit order), on the tensor's own device: three
+    swap steps of byte-wise masks and shifts, no table."""
+    t = ((t & 0xF0) >> 4) | ((t & 0x0F) << 4)
+    t = ((t & 0xCC) >> 2) | ((t & 0x33) << 2)
+    return ((t & 0xAA) >> 1) | ((t & 0x55) << 1)
+
+
+_BITS_POLICY = ("storage='bits' takes packed rows (2-D uint8, [n, d/8]) or unpacked bits (2-D bool, [n, d]) with d a multiple of "
+                "32 and binarises nothing itself: pack other data with hyperdb._native.pack_bits(X) (x > 0) first")
+
+
+def _bits_check(data):
+    """The input policy of storage="bits" -> ("bool" | "packed", the 2-D tensor or array); ValueError naming pack_bits otherwise."""
+    if isinstance(data, torch.Tensor):
+        x, dt, shape = data.detach(), data.dtype, tuple(data.shape)
+        kind = "bool" if dt == torch.bool else "packed" if dt == torch.uint8 else None
+    else:
+        x = data if isinstance(data, np.ndarray) else np.asarray(data)
+        dt, shape = x.dtype, tuple(x.shape)
+        kind = "bool" if dt == np.bool_ else "packed" if dt == np.uint8 else None
+    if kind is None or len(shape) != 2:
+        raise ValueError(f"{_BITS_POLICY}; got {dt} data of shape {shape}")
+    bits = shape[1] * (8 if kind == "packed" else 1)
+    if bits == 0 or bits % 32 != 0:
+        raise ValueError(f"{_BITS_POLICY}; got {bits} bits per row")
+    return kind, x
+
+
+def to_bits(data, device, bitorder="big"):
+    """The input of a bits index -> contiguous torch.uint8 ``[n, d/8]`` on `device` in the LITTLE bit order the library reads
+    (element e of a row = bit e & 7 of byte e >> 3).  Takes only a 2-D uint8 array / tensor of packed rows in `bitorder` (host or
+    device) and a 2-D bool array / tensor of unpacked bits (packed on the host); anything else raises ValueError naming pack_bits.
+    Big-order bytes are bit-reversed once, on `device`."""
+    bit_order(bitorder)
+    kind, x = _bits_check(data)
+    if kind == "bool":
+        h = x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+        return torch.from_numpy(pack_bits(h, "little")).to(device).contiguous()
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    t = t.to(device)
+    t = reverse_bits8(t) if bitorder == "big" else t
+    return t.contiguous()
+
+
+def unpack_bits_host(packed, bitorder):
+    """Packed uint8 ``[..., d/8]`` (numpy) -> the float32 0/1 array ``[..., d]``."""
+    return np.unpackbits(np.ascontiguousarray(packed), axis=-1, bitorder=bitorder).astype(np.float32)
 
 
 def to_i8(data):
@@ -242,22 +325,28 @@ class GpuIndex:
     :37 (re-normalising every row): those happen once here, at registration.
     """
 
-    def __init__(self, vectors, device=None, row_base=0, storage=None):
+    def __init__(self, vectors, device=None, row_base=0, storage=None, bitorder="big"):
         storage_mode(storage)
+        self.bitorder = bit_order(bitorder)    # storage="bits": the order of the caller's packed bytes (the device holds "little")
+        if storage == "bits":
+            _bits_check(vectors)               # (the input policy: ValueError before a GPU is asked for)
         require_gpu()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
-        t = to_device_matrix(vectors, self.device, storage)
+        t = to_bits(vectors, self.device, bitorder) if storage == "bits" else to_device_matrix(vectors, self.device, storage)
         if t.dim() != 2:
             # reference: non-2-D vectors make the metric functions raise (tests/test_ranking_algorithm.py:107-114)
             raise ValueError(f"vectors must be 2-D (N x d), got shape {tuple(t.shape)}")
         self.V = t
         self.n, self.d = int(t.shape[0]), int(t.shape[1])
+        if storage == "bits":
+            self.d *= 8                        # d counts bits; V is the uint8 tensor [n, d / 8]
         if self.d == 0:
             raise ValueError("vectors must have d > 0")
+        self._cols = int(t.shape[1])           # columns of the stored tensor: d, or d / 8 bytes of a bits index
         self.dtype = _STORED2HDB[t.dtype]
-        self.storage = storage                 # "int8": append / update convert with to_i8
+        self.storage = storage                 # "int8": append / update convert with to_i8; "bits": with to_bits
         self.row_base = int(row_base)
         self._h = ctypes.c_void_p()
         self._bias = None
@@ -296,10 +385,13 @@ class GpuIndex:
         by doubling; the library re-points (hdb_index_rebase) and extends its row caches (hdb_index_extend)."""
         if self.dtype == HDB_F8E4M3:
             rows = to_f8(rows)                              # float data into a float8 index: torch's conversion, on the host
-        t = to_device_matrix(rows, self.device, self.storage)      # (an int8 index: to_i8 -- ValueError before anything is stored)
+        if self.dtype == HDB_B1:
+            t = to_bits(rows, self.device, self.bitorder)          # (packed uint8 or bool rows only -- ValueError before anything is stored)
+        else:
+            t = to_device_matrix(rows, self.device, self.storage)      # (an int8 index: to_i8 -- ValueError before anything is stored)
         if t.dim() == 1:
             t = t.reshape(1, -1)
-        if t.dim() != 2 or int(t.shape[1]) != self.d:
+        if t.dim() != 2 or int(t.shape[1]) != self._cols:
             raise ValueError(f"append: rows must have {self.d} columns")
         if t.dtype != self.V.dtype:
             t = t.to(self.V.dtype)
@@ -312,7 +404,7 @@ class GpuIndex:
         cap = int(buf.shape[0])
         if self.n + m > cap:
             new_cap = max(self.n + m, 2 * cap, 1024)
-            nbuf = torch.empty((new_cap, self.d), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
+            nbuf = torch.empty((new_cap, self._cols), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
             _as_bytes(nbuf)[:self.n].copy_(_as_bytes(self.V))
             buf = nbuf
             _check(_lib.hdb_index_rebase(self._h, ctypes.c_void_p(buf.data_ptr())), "hdb_index_rebase")
@@ -329,10 +421,13 @@ class GpuIndex:
         """Point the handle at a new matrix (after add/remove) and rebuild the row caches."""
         if self.dtype == HDB_F8E4M3:
             vectors = to_f8(vectors)                        # ... into a float8 index: torch's conversion, on the host, as append does
-        t = to_device_matrix(vectors, self.device, self.storage)   # (an int8 index: to_i8, as append does)
+        if self.dtype == HDB_B1:
+            t = to_bits(vectors, self.device, self.bitorder)       # (a bits index: packed uint8 or bool rows, as append does)
+        else:
+            t = to_device_matrix(vectors, self.device, self.storage)   # (an int8 index: to_i8, as append does)
         if self.dtype == HDB_BF16 and t.dtype != torch.bfloat16:
             t = t.to(torch.bfloat16)                        # float data into a bf16 index: round to nearest even, as append does
-        if t.dim() != 2 or int(t.shape[1]) != self.d or _STORED2HDB[t.dtype] != self.dtype:
+        if t.dim() != 2 or int(t.shape[1]) != self._cols or _STORED2HDB.get(t.dtype) != self.dtype:
             raise ValueError("update: matrix must keep d and dtype")
         self.V, self.n = t, int(t.shape[0])
         self._bias = self._mask = self._nan = None
@@ -380,6 +475,8 @@ class GpuIndex:
     def host_matrix(self):
         """The stored rows as a host array (one D2H copy; the resident copy stays the only one kept).  A bfloat16 index returns
         the exact float32 widening (numpy has no bfloat16), and so do a float8 index (widened on the host) and an int8 index."""
+        if self.dtype == HDB_B1:
+            return unpack_bits_host(self.V.cpu().numpy(), "little")
         if self.V.dtype == torch.int8:
             return self.V.cpu().numpy().astype(np.float32)
         if self.V.dtype == torch.bfloat16:
@@ -388,13 +485,33 @@ class GpuIndex:
             return self.V.view(torch.uint8).cpu().view(_F8).float().numpy()
         return self.V.cpu().numpy()
 
+    def host_bits(self):
+        """A bits index (storage="bits"): the stored rows as packed uint8 ``[n, d/8]`` in the index's ``bitorder`` -- what went in."""
+        if self.dtype != HDB_B1:
+            raise ValueError("host_bits: only a storage='bits' index holds packed rows")
+        v = reverse_bits8(self.V) if self.bitorder == "big" else self.V
+        return v.cpu().numpy()
+
+    def _bits_query(self, q):
+        """A bits index: a uint8 query of d/8 bytes (or [nq, d/8]) is packed in the index's bitorder -> its 0/1 float32 form (binary
+        query against binary rows); anything else is a query of d elements and passes through."""
+        if isinstance(q, torch.Tensor):
+            if q.dtype == torch.uint8 and q.dim() in (1, 2) and int(q.shape[-1]) == self._cols:
+                sh = torch.arange(7, -1, -1, device=q.device) if self.bitorder == "big" else torch.arange(8, device=q.device)
+                return ((q.unsqueeze(-1).to(torch.int32) >> sh.to(torch.int32)) & 1).reshape(*q.shape[:-1], self.d).to(torch.float32)
+            return q
+        a = q if isinstance(q, np.ndarray) else np.asarray(q)
+        if a.dtype == np.uint8 and a.ndim in (1, 2) and a.shape[-1] == self._cols:
+            return unpack_bits_host(a, self.bitorder)
+        return q
+
     def compact(self, keep_rows):
         """Keep only the rows `keep_rows` (ascending local row ids): device-side gather into a fresh allocation, the
         row caches travel with their rows (hdb_index_gather) -- the matrix part of HyperDB.remove_document
         (hyperdb.py:691-766) without a host round trip or a cache rebuild."""
         rows = torch.from_numpy(np.ascontiguousarray(np.asarray(keep_rows, dtype=np.int64))).to(self.device)
         m = int(rows.numel())
-        out = torch.empty((max(m, 1), self.d), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
+        out = torch.empty((max(m, 1), self._cols), dtype=_as_bytes(self.V).dtype, device=self.device).view(self.V.dtype)
         _check(_lib.hdb_index_gather(self._h, ctypes.c_void_p(rows.data_ptr()), m, ctypes.c_void_p(out.data_ptr()),
                                      _stream_ptr(self.device)), "hdb_index_gather")
         self._buf = out
@@ -582,6 +699,8 @@ class GpuIndex:
 
     def _query_tensor(self, q, batched, staged=False):
         qdt = torch.float64 if self.dtype == HDB_F64 else torch.float32
+        if self.dtype == HDB_B1:
+            q = self._bits_query(q)
         if staged and batched and not isinstance(q, torch.Tensor):
             return self._stage_host_query(q)
         if isinstance(q, torch.Tensor):
@@ -640,6 +759,8 @@ class GpuIndex:
         rare exact re-run.  Returns numpy VIEWS (idx int64 [nq,k], score float32 [nq,k], status int32 [nq]) that are
         overwritten by the next call of THIS index with the same (nq, k); the record belongs to the index (two
         indices, devices or shard groups never share one) and at most HOST_RECORD_SLOTS shapes are kept."""
+        if self.dtype == HDB_B1:
+            Q = self._bits_query(Q)
         if type(Q) is np.ndarray and Q.ndim <= 2 and Q.shape[-1] == self.d and Q.size <= 4 * self.d and Q.size:
             # the per-query path of the drop-in entry points (a host query of 1-4 rows): straight into the cached pinned staging
             # buffer the kernels read, no tensor objects, no per-call ctypes wrappers (tools/time_host_path.py)

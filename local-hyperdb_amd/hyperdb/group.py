@@ -30,7 +30,8 @@ def _bounds(n, parts):
 
 class GpuGroup:
     def __init__(self, vectors, devices, storage=None):
-        _native.storage_mode(storage)
+        if _native.storage_mode(storage) == "bits":
+            raise NotImplementedError(_native.BITS_SINGLE_INDEX)
         _native.require_gpu()
         devices = [torch.device("cuda", d) if isinstance(d, int) else torch.device(d) for d in devices]
         if not devices:

@@ -90,6 +90,8 @@ class HyperDB:
         # storage="int8": the resident matrix is torch.int8, one byte per element -- the integers are the matrix.  Host arrays
         # (.vectors, save / load) stay in fp_precision, as for bfloat16 / float8; fp_precision="int8" is still refused above
         self.storage = _native.storage_mode(storage)
+        if self.storage == "bits":
+            raise NotImplementedError(_native.BITS_SINGLE_INDEX)
         self.i8 = storage == "int8"
         if self.i8:
             if fp_precision != "float32":

@@ -43,15 +43,17 @@ _ALL_METRICS = tuple(METRIC_IDS)
 class ResidentVectors:
     """Handle for a matrix registered on the GPU; pass it wherever ``vectors`` is expected."""
 
-    def __init__(self, vectors, device=None, devices=None, quantize=None, storage=None):
+    def __init__(self, vectors, device=None, devices=None, quantize=None, storage=None, bitorder="big"):
         _native.quant_mode(quantize)                     # (ValueError before anything is uploaded)
-        _native.storage_mode(storage)
-        self.index = GpuGroup(vectors, devices, storage=storage) if devices else GpuIndex(vectors, device=device, storage=storage)
+        if _native.storage_mode(storage) == "bits" and devices:
+            raise NotImplementedError(_native.BITS_SINGLE_INDEX)
+        self.index = (GpuGroup(vectors, devices, storage=storage) if devices
+                      else GpuIndex(vectors, device=device, storage=storage, bitorder=bitorder))
         if quantize is not None:
             _native.request_shadow(self.index, quantize)     # (a bfloat16 matrix: sets bf16_quant first)
         arr_dtype = vectors.dtype if hasattr(vectors, "dtype") else None
-        if storage == "int8":
-            arr_dtype = None                             # the STORED dtype decides: an int8 index answers in float32
+        if storage in ("int8", "bits"):
+            arr_dtype = None                             # the STORED dtype decides: an int8 / packed-bit index answers in float32
         self.np_dtype = _np_dtype_of(arr_dtype, self.index)
 
     @property
@@ -65,14 +67,19 @@ class ResidentVectors:
         self.index.close()
 
 
-def register_vectors(vectors, device=None, devices=None, quantize=None, storage=None):
+def register_vectors(vectors, device=None, devices=None, quantize=None, storage=None, bitorder="big"):
     """Upload ``vectors`` once; returns a handle usable in place of ``vectors``.  ``devices=[...]`` row-shards the matrix
     over several GPUs behind the same handle (single process, see hyperdb/group.py).  ``quantize="int8"`` also keeps an int8
     shadow of the matrix that 1-4-query dot / cosine / euclidean calls scan first, rescoring the surviving rows exactly (same
     answer, fewer bytes read; see GpuIndex.quantize).  ``storage="int8"`` keeps the matrix as signed 8-bit integers, one byte per
     element: np.int8 / torch.int8 go in as they are, any other numeric input only if every element is an integer in
-    [-128, 127] (ValueError otherwise); queries and scores are float32.  Without it integer inputs are widened to float64."""
-    return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize, storage=storage)
+    [-128, 127] (ValueError otherwise); queries and scores are float32.  Without it integer inputs are widened to float64.
+    ``storage="bits"`` (one device only) keeps a packed-bit matrix, one bit per element: a 2-D uint8 array of packed rows
+    ``[n, d/8]`` (``np.packbits`` order; see ``_native.pack_bits``) or a 2-D bool array ``[n, d]``; every metric is the reference's
+    arithmetic on the 0/1 matrix the bits stand for, with float32 queries of d elements and float32 scores.  ``bitorder``
+    ("big", np.packbits' default, or "little") names the order of the packed bytes; a uint8 query of d/8 bytes is taken as packed
+    in the same order."""
+    return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize, storage=storage, bitorder=bitorder)
 
 
 # (bfloat16 has no numpy dtype: score vectors of a bf16 matrix come back as float32, the type its values widen to exactly)
@@ -83,6 +90,7 @@ _TORCH2NP = {torch.float16: np.float16, torch.float32: np.float32, torch.float64
 # raw inputs: a raw torch.int8 tensor handed to a metric function becomes a float64 index and answers in float64
 _STORED2NP = dict(_TORCH2NP)
 _STORED2NP[torch.int8] = np.float32
+_STORED2NP[torch.uint8] = np.float32                 # a packed-bit index (storage="bits"): the 0/1 matrix answers in float32
 
 
 def _np_dtype_of(dt, index):
@@ -108,6 +116,13 @@ def _resolve(vectors):
     arr = np.asarray(vectors)
     ix = GpuIndex(arr)
     return ix, arr.dtype, True
+
+
+def _packed_query(vectors, query_vector):
+    """Is this a packed uint8 query of a bits index (storage="bits")?  Such a query is bytes, not elements: never binarised in place."""
+    ix = vectors.index if isinstance(vectors, ResidentVectors) else vectors
+    return (isinstance(ix, GpuIndex) and ix.dtype == _native.HDB_B1 and isinstance(query_vector, np.ndarray)
+            and query_vector.dtype == np.uint8 and query_vector.shape[-1] == ix.d // 8)
 
 
 def _query_host(query_vector):
@@ -196,7 +211,7 @@ def hamming_distance(vectors, query_vector):
 
     Like the reference, a numpy ``query_vector`` is binarised in place."""
     out = _scores(vectors, query_vector, METRIC_IDS["hamming_distance"], out_dtype=np.uint64)
-    if isinstance(query_vector, np.ndarray) and query_vector.flags.writeable:
+    if isinstance(query_vector, np.ndarray) and query_vector.flags.writeable and not _packed_query(vectors, query_vector):
         check_and_binarize_vectors(query_vector)
     return out
 
@@ -210,7 +225,7 @@ def jaccard_similarity(vectors, query_vector):
     """|v AND q| / |v OR q| on the x>0 bits, NaN where both are empty (reference :63-75); float64 like numpy's
     true division.  A numpy ``query_vector`` is binarised in place, as in the reference."""
     out = _scores(vectors, query_vector, METRIC_IDS["jaccard_similarity"], out_dtype=np.float64)
-    if isinstance(query_vector, np.ndarray) and query_vector.flags.writeable:
+    if isinstance(query_vector, np.ndarray) and query_vector.flags.writeable and not _packed_query(vectors, query_vector):
         check_and_binarize_vectors(query_vector)
     return out
 
@@ -282,7 +297,7 @@ def hyperDB_ranking_algorithm_sort(vectors, query_vector, top_k=5, metric='cosin
             if had_bias:
                 ix.set_bias(None)
         if metric in ("hamming_distance", "jaccard_similarity") and isinstance(query_vector, np.ndarray) \
-                and query_vector.flags.writeable:
+                and query_vector.flags.writeable and not _packed_query(ix, query_vector):
             check_and_binarize_vectors(query_vector)
         return idx, sc
     finally:
