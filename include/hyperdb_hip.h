@@ -363,9 +363,20 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     (1 - q)^2, q^2; |1 - q|, |q|), four elements at a time from a per-query table in LDS, in ONE summation order per row: the
  *     sample pass, the filter pass, hdb_topk_exact and hdb_scores return the same float32 bits for a row, whatever the grid.
  *   - hamming / jaccard: the bit kernels that every dtype uses, on the sign cache; such calls plan exactly as on an int8 index.
- *   - never: the matrix cores, the 1-4-query and batched single launches, the manhattan tile kernel, the int8 shadow and its plane
- *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit).
- * Stats: mfma = 0, quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics' single launch). */
+ *   - on request (option b1_mfma_min_q, 0 = never by default): batches of 5+ dot / cosine / euclidean / pearson queries on rows of
+ *     d = 128, 256, 384 or 512 bits, and in K slices (bfloat16's slice list) on d = 640 .. 1536 in steps of 128, 2048, 3072 and 4096,
+ *     run on the bf16 matrix cores (hdb_mfma_b1.h), multi-kernel pipeline: a bit is exactly one bf16 number, expanded per fragment in
+ *     registers; float32 queries as three exact bf16 parts, the bfloat16 flavour's K walk and epilogue.  Dot, cosine and euclidean
+ *     return the indices, score bits and status words of a bfloat16 index over the unpacked 0/1 matrix (wider rows: going through
+ *     ITS K slices); pearson takes the cosine epilogue with its own row scale and keeps the 1e-5 contract.  b1_mfma_min_q = n >= 1:
+ *     from max(n, 5, mfma_min_q) queries on; -1: from hdb_mfma_b1_min_q(d) queries on (hdb_caps.h, 0 there = never).  Manhattan, the
+ *     bit metrics, 1-4 queries, other widths, matrices of up to 8192 rows and use_mfma = 0 stay on the bit scan; a base that is only
+ *     4-byte aligned is served.  Off by default: the default dispatch of packed-bit rows is pinned (tests/b1_plan_check.hip).
+ *   - never: the 1-4-query and batched single launches, the manhattan tile kernel, the int8 shadow and its plane
+ *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit); the
+ *     matrix cores unless b1_mfma_min_q asks for them.
+ * Stats: mfma = 0 (1 on the matrix-core path of b1_mfma_min_q), quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics'
+ * single launch); b1_mfma_min_q = the threshold in force for this index, 0 = never. */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 
@@ -456,7 +467,9 @@ void hdb_group_destroy(hdb_group* g);
  *   (bfloat16 rows wider than 512 elements: K slices from this many queries on, never fewer than 5), f8_ks_min_q (float8 rows wider
  *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), f8_lds_min_q
  *   (float8 batches with the rows expanded to bf16 in LDS once per workgroup: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q)
- *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), bits_max_q
+ *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), b1_mfma_min_q
+ *   (packed-bit batches on the bf16 matrix cores: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q) queries on; -1 =
+ *   hdb_mfma_b1_min_q(d), 0 there = never), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan),
  *   l1_packed (0: that tile kernel always subtracts in float32; default 1 = packed fp16 differences on fp16 rows while every query

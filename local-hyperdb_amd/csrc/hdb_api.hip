@@ -543,6 +543,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "bf16_ks_min_q")) ix->opt.bf16_ks_min_q = value;
     else if (!strcmp(name, "f8_ks_min_q")) ix->opt.f8_ks_min_q = value < 0 ? -1 : value;
     else if (!strcmp(name, "f8_lds_min_q")) ix->opt.f8_lds_min_q = value < 0 ? -1 : value;
+    else if (!strcmp(name, "b1_mfma_min_q")) ix->opt.b1_mfma_min_q = value < 0 ? -1 : value;
     else if (!strcmp(name, "bf16_quant")) ix->opt.bf16_quant = value ? 1 : 0;
     else if (!strcmp(name, "f8_lds_waves")) { if (value == 0 || value == 4 || value == 8) ix->opt.f8_lds_waves = value; }
     else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
@@ -575,6 +576,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "f32_split")) *value = ix->st.f32s;
     else if (!strcmp(name, "f8_lds")) *value = ix->st.f8_lds;
     else if (!strcmp(name, "f8_lds_min_q")) *value = f8_lds_first_q(ix->opt, ix->dtype, ix->d);      // the threshold in force for this index, 0 = never
+    else if (!strcmp(name, "b1_mfma_min_q")) *value = b1_mfma_first_q(ix->opt, ix->dtype, ix->d);      // likewise, for a packed-bit index
     else if (!strcmp(name, "host_direct")) *value = ix->st_host_direct;
     else if (!strcmp(name, "fused")) *value = ix->st.fused;
     else if (!strcmp(name, "local")) *value = ix->st.local;

@@ -191,6 +191,43 @@ static inline int hdb_mfma_f8_lds_blocks(int64_t ntiles, int d, int waves, int l
 // The other sliced widths were not measured: 0.  (The option is 0 by default: the rule is used only where a caller sets -1.)
 static inline int hdb_mfma_f8_lds_min_q(int d) { return (d == 384 || d == 768) ? 32 : (d == 128 || d == 256 || d == 512 || d == 4096) ? 64 : 0; }
 
+// ---- hdb_mfma_b1*.hip: packed-bit rows on the bf16 matrix pipe (hdb_mfma_b1.h; OPT-IN, the planner's b1_mfma_min_q, 0 = never by default) ----
+// Like the float8 slices these rules are no part of hdb_mfma_supported / hdb_mfma_tile_rows / hdb_mfma_ksplit_slices /
+// hdb_mfma_batch_capacity / hdb_mfma_fused_supported, which describe the default dispatch and keep answering "no" for HDB_B1.
+// Whole rows of 128 / 256 / 384 / 512 elements (the query fragments are bfloat16's: three bf16 parts, 3 d / 8 registers per 16
+// queries), 16-row tiles read straight from global memory, as in the float8 register kernel.
+static inline int hdb_mfma_b1_tile_rows(int d) { return (d == 128 || d == 256 || d == 384 || d == 512) ? 16 : 0; }
+// Wider rows in K slices: the widths and the slices of a width are ks_geom_bf16's; off[s] is the BYTE offset into the stored row
+// (an eighth of the element offset into the query: a slice starts on a whole 32-bit word, in fact on a multiple of 16 bytes).
+static inline KsGeom ks_geom_b1(int d) {
+    const KsGeom b = ks_geom_bf16(d);
+    KsGeom g = {};
+    g.slices = b.slices;
+    for (int s = 0; s < b.slices && s < HDB_KS_MAX_SLICES; ++s) { g.width[s] = b.width[s]; g.off[s] = b.off[s] / 16; }
+    return g;
+}
+static inline int hdb_mfma_b1_ks_slices(int d) { return ks_geom_b1(d).slices; }
+// ... and the number of queries of a call from which a packed-bit index takes the matrix cores when b1_mfma_min_q = -1; 0 = never
+// (a width nobody measured).  The rule is the smallest measured batch size from which the matrix cores beat the bit scan
+// (hdb_bscan.hip: four queries per pass) by more than the repeated contender's spread, for cosine AND euclidean, at every larger
+// measured size and at every measured row count of the width.  Measured, one box, the contenders alternating call by call, top-100
+// through rank_batch, p50 of 60 calls in us, matrix cores vs bit scan on the same handle at 5 / 8 / 16 / 64 / 128 queries, cosine
+// (euclidean in brackets where it decides); spread = the two p50s of the repeated matrix-core contender, up to 14 % at 2M rows, where
+// its second turn of a round is the slower one throughout (tools/time_b1_mfma.py -> profiles/b1_mfma_time.txt):
+//   10M x 384:  475 vs 472 (517 vs 474), 480 vs 533 (522 vs 533), 504 vs 963, 1 710 vs 3 689, 3 355 vs 7 466      -> 8 (5 queries: 0.99 / 0.92)
+//    2M x 384:  139 vs 158, 142 vs 173, 165 vs 287, 396 vs 902, 719 vs 1 724                                      -> 5; the width takes 8
+//    2M x 128:  109 vs 113 (94 vs 103, spread 5.9 %), 90 vs 119, 97 vs 191, 219 vs 574, 353 vs 1 085               -> 5 (1.03, spread 1.5 % / 1.09)
+//    2M x 256:  114 vs 139 (121 vs 134, spread 8.8 %), 116 vs 149, 123 vs 237, 305 vs 750, 503 vs 1 429           -> 5 (1.21 / 1.10)
+//    2M x 512:  161 vs 180 (165 vs 178, spread 6.8 %), 164 vs 188, 187 vs 328, 469 vs 1 077, 863 vs 2 109         -> 5 (1.12 / 1.07)
+//    2M x 768:  268 vs 280 (284 vs 275), 305 vs 307 (315 vs 309), 361 vs 542, 1 134 vs 1 944, 2 170 vs 3 862      -> 16 (5 and 8 queries: 0.97-1.04, inside the spread)
+//   10M x 1024: 1 633 vs 2 043, 1 633 vs 2 709, 1 695 vs 5 355, 7 573 vs 21 170, 14 834 vs 41 861                 -> 5 (1.25 / 1.21)
+//    2M x 1024: 405 vs 481 (410 vs 447), 416 vs 616, 439 vs 1 150, 1 317 vs 4 498, 2 528 vs 8 937                 -> 5 (1.19 / 1.09)
+//  375k x 4096: 510 vs 881, 527 vs 1 317, 559 vs 2 481, 1 304 vs 9 336, 2 485 vs 18 219                           -> 5 (1.73)
+// The other sliced widths were not measured: 0.  (The option is 0 by default: the rule is used only where a caller sets -1.)
+static inline int hdb_mfma_b1_min_q(int d) {
+    return d == 384 ? 8 : (d == 128 || d == 256 || d == 512 || d == 1024 || d == 4096) ? 5 : d == 768 ? 16 : 0;
+}
+
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
 

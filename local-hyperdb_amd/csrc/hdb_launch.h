@@ -101,6 +101,15 @@ int hdb_launch_mfma_scan_i8(const ScanArgs* args, int mode, int nq_launch, const
                             const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_scan_i8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
                                  const float* qsq, int blocks, void* stream);
+// packed-bit rows: bits expanded to bf16 0.0 / 1.0 per fragment in registers (hdb_mfma_b1.h; opt-in, b1_mfma_min_q)
+int hdb_launch_mfma_scan_b1(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                            const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_scan_b1_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                 const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_kslice_b1(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
+                              const float* qsq, int blocks, void* stream);
+int hdb_launch_mfma_kslice_b1_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                   const float* qsq, int blocks, void* stream);
 int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                            const float* qsq, const float* qscl, int blocks, void* stream);
 int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,

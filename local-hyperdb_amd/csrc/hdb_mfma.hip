@@ -49,6 +49,13 @@ __device__ __forceinline__ float hdb_row_f(float v) { return v; }
 __device__ __forceinline__ float hdb_row_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
 __device__ __forceinline__ float hdb_row_f(hdb_f8 v) { return __builtin_amdgcn_cvt_f32_fp8((int)v.bits, 0); }
 __device__ __forceinline__ float hdb_row_f(hdb_i8 v) { return hdb_i8_to_f(v); }
+// element k of a stored row; packed bits (HdbB1Word rows of d / 32 words, element e = bit e & 31 of word e >> 5) yield 0.f / 1.f
+struct HdbB1Word { uint32_t w; };
+template <typename T>
+__device__ __forceinline__ float hdb_row_at(const T* V, uint32_t row, int d, int k) { return hdb_row_f(V[(int64_t)row * d + k]); }
+__device__ __forceinline__ float hdb_row_at(const HdbB1Word* V, uint32_t row, int d, int k) {
+    return (float)((V[(int64_t)row * (d >> 5) + (k >> 5)].w >> (k & 31)) & 1u);
+}
 template <typename T, bool HAS_BIAS>
 __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long long* cand, const uint32_t* cnt, uint32_t cap,
                                                                  const T* V, int d, const float* Q, const float* qsq, int q0,
@@ -66,7 +73,7 @@ __global__ __launch_bounds__(256) void hdb_rescore_euclid_kernel(unsigned long l
         const float dist = 1.f / sim - 1.f;
         if (sim > 0.f && dist * dist < close2) {                   // wave-uniform: one entry per wave
             float acc = 0.f;
-            for (int k = lane; k < d; k += 64) { const float df = hdb_row_f(V[(int64_t)row * d + k]) - qv[k]; acc += df * df; }
+            for (int k = lane; k < d; k += 64) { const float df = hdb_row_at(V, row, d, k) - qv[k]; acc += df * df; }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
             s = hdb_canon(1.f / (1.f + sqrtf(acc)) + b);
@@ -134,6 +141,13 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
         const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
         return hdb_launch_mfma_scan_i8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
     }
+    if (dtype == HDB_B1) {              // packed-bit rows (hdb_mfma_b1.h; the plan asked, b1_mfma_min_q): the float8 register kernel's grid rule
+        if (mode == 2) return (int)hipErrorNotSupported;
+        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
+        const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
+        if (hdb_mfma_b1_ks_slices(a.d) > 0) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
+        return hdb_launch_mfma_scan_b1(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
+    }
     if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);
     if (dtype != HDB_F16) return (int)hipErrorNotSupported;
     // (mode 2 promises hdb_mfma_batch_capacity() queries in ONE launch: only the two-tile launcher holds more than 128, whatever the variant)
@@ -158,7 +172,12 @@ extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_
                                          int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
     const dim3 grid(64, nq_launch);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3 && dtype != HDB_I8) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
+    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3 && dtype != HDB_I8 && dtype != HDB_B1) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
+    if (dtype == HDB_B1) {
+        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<HdbB1Word, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const HdbB1Word*)V, d, Q, qsq, q0, bias);
+        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<HdbB1Word, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const HdbB1Word*)V, d, Q, qsq, q0, bias);
+        return (int)hipGetLastError();
+    }
     if (dtype == HDB_I8) {
         if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);
         else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);

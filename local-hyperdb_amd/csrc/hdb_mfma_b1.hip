@@ -1,0 +1,15 @@
+// hdb_mfma_b1.hip -- the row scan of packed-bit matrices (HDB_B1) on the bf16 matrix pipe (hdb_mfma_b1.h; opt-in, b1_mfma_min_q):
+// bits expanded to bf16 0.0 / 1.0 per fragment in registers, float32 queries as three exact bf16 parts, the bfloat16 flavour's K walk
+// and epilogue.  Multi-kernel pipeline only: MODE 0 (scores) and MODE 1 (filter).  d = 128 / 256 here, 384 / 512 in hdb_mfma_b1_b.hip.
+#include "hdb_mfma_b1.h"
+
+extern "C" int hdb_launch_mfma_scan_b1(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
+                                       const float* qsq, int blocks, void* stream) {
+    const ScanArgs& a = *args;
+    hipStream_t st = (hipStream_t)stream;
+    switch (a.d) {
+        case 128: return launch_b1<128>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
+        case 256: return launch_b1<256>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
+        default: return hdb_launch_mfma_scan_b1_wide(args, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+    }
+}

@@ -1,6 +1,6 @@
 // hdb_mfma_ksplit.hip -- the MFMA row scan for rows too wide for one wave's query fragments: float32 d = 1024 / 1536 (the
 // reference's default precision at its demo width, hyperdb.py:51), fp16 d = 2048 / 3072 / 4096, bfloat16 d = 640 .. 4096 and, on
-// request (f8_ks_min_q), float8 e4m3 d = 640 .. 4096.
+// request (f8_ks_min_q, b1_mfma_min_q), float8 e4m3 and packed-bit rows d = 640 .. 4096.
 //
 // A wave holds the B fragments of 16 queries for at most 3072 bytes of row (192 registers; bfloat16 rows, whose float32 queries
 // travel as three bf16 parts: 1024 bytes), and a 16-row LDS stage of wider rows does not fit the 3-deep ring.  So the K dimension
@@ -17,18 +17,20 @@
 // slice overwrites the sums with the scores, element by element, by the lane that read them)
 extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
                                       const float* qsq, const float* qscl, int blocks, void* stream) {
-    const KsGeom g = dtype == HDB_F8E4M3 ? ks_geom_f8(args->d) : ks_geom(dtype, args->d);       // (float8: the opt-in list, no part of ks_geom)
+    const KsGeom g = dtype == HDB_F8E4M3 ? ks_geom_f8(args->d) : dtype == HDB_B1 ? ks_geom_b1(args->d) : ks_geom(dtype, args->d);       // (float8, packed bits: the opt-in lists, no part of ks_geom)
     if (!g.slices || !args->ks_partial_out) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     for (int s = 0; s < g.slices; ++s) {
         ScanArgs a = *args;
         a.ks_pitch = hdb_row_bytes(dtype, args->d); a.ks_off = g.off[s]; a.ks_dfull = args->d;
+        if (dtype == HDB_B1) a.ks_off = g.off[s] * 8;         // (packed bits: the kernel takes the ELEMENT offset -- into the query as it is, an eighth of it into the row)
         a.ks_partial_in = s == 0 ? nullptr : args->ks_partial_out;
         const int m = s + 1 < g.slices ? 3 : mode;
         const int w = g.width[s];
         int rc;
         if (dtype == HDB_F8E4M3 && args->f8_lds) rc = hdb_launch_mfma_kslice_f8_lds(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (blocks: a limit, each slice sizes its own grid)
         else if (dtype == HDB_F8E4M3) rc = hdb_launch_mfma_kslice_f8(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
+        else if (dtype == HDB_B1) rc = hdb_launch_mfma_kslice_b1(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
         else if (dtype == HDB_BF16) rc = hdb_launch_mfma_kslice_bf16(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (float32 queries as they are: no qscl)
         else if (dtype == HDB_F32 && args->f32_split) rc = hdb_launch_mfma_kslice_f32s(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
         else if (dtype == HDB_F32) rc = w == 512 ? launch_kslice<float, 512, 16>(a, m, q, sqnorm, qsq, nullptr, nq_launch, blocks, st)

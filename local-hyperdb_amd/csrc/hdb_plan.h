@@ -28,6 +28,7 @@ struct hdb_options {
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
     int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
+    int64_t b1_mfma_min_q = 0;        // packed-bit batches on the bf16 matrix cores (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never)
     int64_t bf16_quant = 0;           // bfloat16 matrices: hdb_index_quantize(HDB_QUANT_I8) builds an explicit int8 shadow (0, the default: the call is refused; opt-in).  Means nothing on other types; the plan does not read it
     int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
@@ -286,6 +287,14 @@ static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
     return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
 }
 
+// The number of queries of a call from which a packed-bit index takes the matrix cores (b1_mfma_min_q; the stat of the same name):
+// the option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never (the default, and every width without a kernel)
+static inline int64_t b1_mfma_first_q(const hdb_options& o, int dtype, int d) {
+    if (dtype != HDB_B1 || (hdb_mfma_b1_tile_rows(d) <= 0 && hdb_mfma_b1_ks_slices(d) <= 0)) return 0;
+    const int64_t rule = o.b1_mfma_min_q > 0 ? o.b1_mfma_min_q : o.b1_mfma_min_q < 0 ? (int64_t)hdb_mfma_b1_min_q(d) : 0;
+    return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
+}
+
 // finite(): "are all rows of the matrix finite with a finite sum of squares?"
 template <typename Finite>
 static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite_fn) {
@@ -363,7 +372,11 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
                                     ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), o.f8_ks_min_q > 0 ? o.f8_ks_min_q : (int64_t)hdb_mfma_f8_ks_min_q(ix.d)) : 0;
     const int metric_mm = is_pearson ? (int)HDB_COSINE : metric;
     const bool f8ks_call = f8_ks_first > 0 && nq >= f8_ks_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
-    bool mfma = o.use_mfma && !is_ham && !small && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call);
+    // (packed-bit rows reach the matrix cores on request only as well, b1_mfma_min_q != 0 -- whole rows of up to 512 elements and the
+    //  K slices of wider ones, hdb_mfma_b1.h.  The matrix is always finite -- its flag word is never written -- so nothing is asked.)
+    const int64_t b1_first = b1_mfma_first_q(o, ix.dtype, ix.d);
+    const bool b1_call = b1_first > 0 && nq >= b1_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
+    bool mfma = o.use_mfma && !is_ham && !small && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
     // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
@@ -377,6 +390,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call (build_needed); an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
     const bool f8ks = mfma && f8ks_call;
+    const bool b1mm = mfma && b1_call, b1ks = b1mm && hdb_mfma_b1_ks_slices(ix.d) > 0;
     const bool auto_q = auto_quant_call(ix, o, c, mfma, exact, small);
     if (auto_q && nq >= 1 && nq <= 4 &&
         // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
@@ -412,7 +426,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
                              // fp16 d = 1024 (32-KiB tiles, 32 k-steps in one wave): 189 vs 195 us at 0.5 M rows, 619 vs 627 at 2 M,
                              // but 1 491 vs 1 466 at 5 M -- the single launch up to 4 M rows
                              !(ix.dtype == HDB_F16 && ix.d == 1024 && n > 4000000);
-    const int tile_rows = f8ks ? 16 : (mfma || fused_shape) ? hdb_mfma_tile_rows(ix.dtype, ix.d) : 16;      // (float8 slices: the 16-row tiles of every float8 kernel)
+    const int tile_rows = (f8ks || b1mm) ? 16 : (mfma || fused_shape) ? hdb_mfma_tile_rows(ix.dtype, ix.d) : 16;      // (float8 slices, packed bits: the 16-row tiles of the register kernels)
     // float32 rows on the matrix cores multiply in three bf16 parts (hdb_mfma_f32s.hip: 2.7x the rate of the float32 MFMAs, same
     // 1e-5 contract) -- on finite matrices: the parts of an infinite element would cancel to NaN where np.dot keeps the infinity
     // Two parts keep 16 mantissa bits of a row value, so the product's error is up to 2^-17 |v| |q| whatever the score:
@@ -444,7 +458,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     int cq_max = batch1 ? bcap : 256;
     if (exact && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(256, o.exact_bytes / (ld_n * 4)));
     // wide rows on the matrix cores go through K slices with a [query][rows] buffer of partial sums (hdb_mfma_ksplit.hip)
-    const bool ksplit = mfma && (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || f8ks);
+    const bool ksplit = mfma && (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || f8ks || b1ks);
     if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), o.exact_bytes / (ld_n * 4)));
     cq_max = std::min(cq_max, (int)nq);
     const bool fused = fused_shape && !full_sort && (m == 8 || local_ok);           // (no prep kernel either)

@@ -657,6 +657,9 @@ class GpuIndex:
 
     # -- options / stats -----------------------------------------------------------------------
     def set_option(self, name, value):
+        """An option of the index by its C name (include/hyperdb_hip.h lists them), e.g. ``set_option("b1_mfma_min_q", 5)``: a
+        storage="bits" index sends dot / cosine / euclidean / pearson batches of 5+ queries to the bf16 matrix cores (d = 128 .. 512,
+        and 640 .. 4096 in K slices; 0 = never, the default; ``stat("b1_mfma_min_q")`` is the threshold in force)."""
         _check(_lib.hdb_set_option(self._h, name.encode(), int(value)), "hdb_set_option")
 
     def stat(self, name):
