@@ -64,7 +64,8 @@ enum hdb_query_status {
     HDB_Q_OK = 0,
     HDB_Q_UNDERFLOW = 1,  /* sampled threshold too high: fewer than k candidates passed */
     HDB_Q_OVERFLOW = 2,   /* candidate buffer overflowed (massive ties or skewed sample) */
-    HDB_Q_NAN = 4         /* the query vector contains a NaN (ValueError of ranking_algorithm.py:150-151) */
+    HDB_Q_NAN = 4,        /* the query vector contains a NaN (ValueError of ranking_algorithm.py:150-151) */
+    HDB_Q_BADROW = 8      /* hdb_rerank: a candidate id outside [row_base, row_base + n) other than a negative one: skipped, never read */
 };
 
 /* Library/ABI version (major*100+minor). */
@@ -394,6 +395,49 @@ int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int m
 int hdb_topk_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
                    int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 
+/* Rerank: the exact top-k of every query among ITS OWN list of rows (local-hyperdb_amd/csrc/hdb_rerank.hip) -- the second half of
+ * a two-stage search (candidates from a cheap index, rescored against this one), of hybrid search and of per-query filters.
+ * dev_cand: [nq][m] int64, row-major, device; ids as hdb_topk returns them (row_base added), so the output of one index feeds
+ * another with the same base.  1 <= m <= HDB_CAND_CAP (8192) and 1 <= k <= m, anything else is HDB_ERR_ARG.
+ * The list of query q:
+ *   - a negative id is padding (the -1 tail of a short first stage) and is skipped silently;
+ *   - an id outside [row_base, row_base + n) is skipped and sets HDB_Q_BADROW in the query's status word.  The id is compared
+ *     against the bounds before any address is formed from it: no row, cache or mask byte of such an id is read;
+ *   - an id listed twice counts once;
+ *   - the rest are scored with the handle's bias added and its row mask applied (a masked row is never returned; a row list set
+ *     with hdb_index_set_row_subset is ignored);
+ *   - the result is ordered by (score descending, id ascending); where fewer than k rows remain the tail is -1 / -inf.
+ * Status: 0, HDB_Q_NAN, HDB_Q_BADROW.  Nothing is sampled, so nothing is ever re-run.
+ * Served: HDB_F16, HDB_F32, HDB_F64 (float64 queries), HDB_BF16, HDB_F8E4M3, HDB_I8 matrices; dot, cosine, euclidean, manhattan,
+ * pearson; any d.  Rows that are whole 16-byte pieces of a 16-byte aligned matrix are read with 16-byte loads, everything else
+ * element by element.  HDB_B1 matrices, hamming and jaccard return HDB_ERR_UNSUPPORTED: a bits index is a FIRST stage.
+ * Scores: a returned row carries the float32 bits the VALU scan gives that row on this handle -- the indices and score bits of
+ * hdb_topk_exact with use_mfma = use_fused = use_quant = use_l1_tile = 0 under a row mask that keeps exactly the query's valid
+ * candidates.  The score of a (query, row) pair does not depend on the row's place in the list, on the other candidates or on
+ * the other queries.  The 1e-5 band (1e-3 float16) against the reference's arithmetic on V[cand[q]] follows.
+ * Launches per chunk of queries: query preparation (pearson: and centring), list preparation (one workgroup per query sorts the
+ * list in LDS, drops padding, out-of-range, masked and repeated ids and writes the status word), the scoring pass (a 16-lane
+ * group per candidate, the query in LDS) and the finalize of the multi-kernel pipeline.  Option rerank_chunk: queries per chunk
+ * (0: up to 256).  Stats: rerank = 1, chunks; hdb_topk sets rerank = 0.
+ * hdb_rerank_host: the same, then the packed record (hdb_packed_bytes(nq, k)) in host memory and one stream synchronisation.
+ * Not built: rerank onto an HDB_B1 index and the bit metrics, lists longer than 8192, groups and sharded indexes (ids would need
+ * routing to shards), one launch that scores and selects a short list, the matrix cores (a gather of a few hundred rows per
+ * query is bound by latency). */
+int hdb_rerank(hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
+               int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
+int hdb_rerank_host(hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
+                    void* host_record, void* stream);
+
+/* Two-stage search in one call: hdb_topk of k1 on `first` (any dtype and metric, HDB_B1 and hamming included; dev_Q1 are ITS
+ * queries), kept on the device, then hdb_rerank of those [nq][k1] ids on `second` with dev_Q2 and metric2, top k, as one packed
+ * record in host memory.  Stage one's status words are read back (one small copy and a synchronisation) and its failed queries
+ * re-run exactly, as hdb_topk_host does, before their ids are used; the record's status words are the rerank's.
+ * `first` and `second` must be on the same device with the same n and row_base, 1 <= k1 <= min(8192, n) and 1 <= k <= k1;
+ * otherwise HDB_ERR_ARG.  They may be the same handle. */
+int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metric1, int32_t k1,
+                       hdb_index* second, const void* dev_Q2, int metric2, int32_t k,
+                       int32_t nq, void* host_record, void* stream);
+
 /* Merge `parts` per-shard top-k lists (the all-gathered [parts][nq][k] buffers of the row-sharded
  * index) into the global top-k per query, same ordering rule.  Every part list must be ordered as hdb_topk writes
  * it: score descending, row ascending, unused slots (index -1) at the end. */
@@ -484,12 +528,14 @@ void hdb_group_destroy(hdb_group* g);
  *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; kept rows beyond which a call counts in plane_overflows -- a
  *   statistic: no call is answered differently for it), plane_wg_per_cu (workgroups per CU of the pass over the plane: 0 the
  *   measured table, 1 .. 8 that many -- for A/B runs, no call is answered differently for it).
+ *   rerank_chunk (hdb_rerank: queries per chunk, 0 = automatic, up to 256; at most 256).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
  *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
  *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows, plane_blocks (workgroups of the last call's
- *   pass over the plane, 0 when it did not take it). */
+ *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second
+ *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

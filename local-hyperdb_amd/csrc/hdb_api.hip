@@ -83,6 +83,9 @@ struct hdb_index {
     // device copy of the result record of hdb_topk_host (owned)
     char* rec = nullptr;
     size_t rec_bytes = 0;
+    // ... and of stage one of hdb_two_stage_host (owned): its ids feed the rerank, which may use `rec` of the same handle
+    char* rec1 = nullptr;
+    size_t rec1_bytes = 0;
     // int8 shadow of the matrix (owned, hdb_index_quantize; hdb_quant.hip): codes [rows][qP], caches [rows][3]
     int qmode = HDB_QUANT_NONE;
     int8_t* qcodes = nullptr;
@@ -139,7 +142,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 108; }
+extern "C" int hdb_version(void) { return 109; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 static int build_caches(hdb_index* ix, hipStream_t st) {
@@ -456,6 +459,7 @@ extern "C" void hdb_index_destroy(hdb_index* ix) {
     if (ix->bctl) (void)hipFree(ix->bctl);
     if (ix->ws) (void)hipFree(ix->ws);
     if (ix->rec) (void)hipFree(ix->rec);
+    if (ix->rec1) (void)hipFree(ix->rec1);
     quant_free(ix);
     if (ix->qstat) (void)hipFree(ix->qstat);
     for (hipEvent_t e : ix->ev_pool) (void)hipEventDestroy(e);
@@ -560,6 +564,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "use_subset")) ix->opt.use_subset = value;
     else if (!strcmp(name, "subset_min_n")) ix->opt.subset_min_n = value < 0 ? -1 : value;
     else if (!strcmp(name, "subset_ratio")) ix->opt.subset_ratio = value < 0 ? -1 : std::max<int64_t>(1, value);
+    else if (!strcmp(name, "rerank_chunk")) ix->opt.rerank_chunk = std::max<int64_t>(0, std::min<int64_t>(value, HDB_RERANK_MAXQ));
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -588,6 +593,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "plane_blocks")) *value = ix->st.plane_blocks;      // workgroups of the last call's plane pass (0: it did not take the plane)
     else if (!strcmp(name, "subset")) *value = ix->st.subset;
     else if (!strcmp(name, "subset_rows")) *value = ix->subset_m;
+    else if (!strcmp(name, "rerank")) *value = ix->st.rerank;
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
@@ -1437,6 +1443,130 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
 extern "C" int hdb_topk_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
                               float* dev_score, int32_t* dev_status, void* stream) {
     return topk_impl(ix, dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, stream, true);
+}
+
+// ---- hdb_rerank: exact top-k of every query among its own list of rows (hdb_rerank.hip) ---------------------------------------------
+// What is decided from the numbers alone comes first, before the handle is looked at and before any HIP call.
+static int rerank_sizes(const char* who, int32_t nq, int32_t m, int32_t k, bool host) {
+    if (m < 1 || m > HDB_CAND_CAP) return fail(HDB_ERR_ARG, std::string(who) + ": m (candidates per query) must be in [1, 8192]");
+    if (k < 1 || k > m) return fail(HDB_ERR_ARG, std::string(who) + ": k must be in [1, m]");
+    if (host ? nq <= 0 : nq < 0) return fail(HDB_ERR_ARG, std::string(who) + (host ? ": nq must be positive" : ": nq must be >= 0"));
+    return HDB_OK;
+}
+// Per chunk of queries: list preparation (valid, ascending, unique rows; the status words), the scoring pass, the finalize of the
+// multi-kernel pipeline over lists of at most m <= HDB_CAND_CAP entries.  The finalize gets no status pointer: a list shorter than k
+// is no underflow here, the tail is -1 / -inf and the status word is the preparation's (HDB_Q_NAN, HDB_Q_BADROW).
+static int rerank_impl(const char* who, hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
+                       int64_t* dev_idx, float* dev_score, int32_t* dev_status, hipStream_t st) {
+    if (!ix) return fail(HDB_ERR_ARG, std::string(who) + ": null index");
+    if (nq == 0) return HDB_OK;
+    if (!dev_Q || !dev_cand || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, std::string(who) + ": null argument");
+    if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": a packed-bit index is a first stage: rerank onto packed bits is not built");
+    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": hamming / jaccard rerank is not built");
+    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
+        return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": metric not built");
+    HIP_TRY(hipSetDevice(ix->device));
+    const bool f64 = ix->dtype == HDB_F64, pearson = metric == HDB_PEARSON;
+    const int cq_max = (int)std::min<int64_t>(nq, ix->opt.rerank_chunk > 0 ? ix->opt.rerank_chunk : HDB_RERANK_MAXQ);
+    ix->st = TopkStats();
+    ix->st.rerank = 1;
+    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    RerankWs w;
+    int rc = ws_lay(ix, w, (int)nq, (int)ix->d, cq_max, (int)m, pearson);
+    if (rc) return rc;
+    LAUNCH_TRY(hdb_launch_qprep2(dev_Q, nq, ix->d, f64, w.qinv, w.qsq, w.qnan, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st));
+    const void* Qeff = dev_Q; int metric_eff = metric;
+    if (pearson) {                      // cosine on the centred queries with 1/(sd d) row scales, as topk_begin / run_pipeline prepare them
+        rc = ensure_pscale(ix, st); if (rc) return rc;
+        LAUNCH_TRY(hdb_launch_qcentre(dev_Q, nq, ix->d, f64, w.qc, w.qinv, st));
+        Qeff = w.qc; metric_eff = HDB_COSINE;
+    }
+    for (int q0 = 0; q0 < nq; q0 += cq_max) {
+        const int cq = std::min(cq_max, nq - q0);
+        LAUNCH_TRY(hdb_launch_rerank_prep(dev_cand + (int64_t)q0 * m, m, cq, ix->n, ix->row_base, ix->mask, w.qnan + q0, w.rows, w.cnt,
+                                          dev_status ? dev_status + q0 : nullptr, st));
+        ScanArgs a; base_args(ix, a, Qeff, metric_eff);
+        if (pearson) a.inv_norm = ix->pscale;
+        a.q0 = q0; a.qinv = w.qinv; a.bias = ix->bias; a.mask = nullptr;      // (the preparation dropped the masked rows)
+        a.rows = w.rows; a.m = m; a.cnt = w.cnt; a.cand = w.cand; a.nq = nq;
+        LAUNCH_TRY(hdb_launch_rerank_score(&a, ix->dtype, cq, st));
+        LAUNCH_TRY(hdb_launch_finalize(w.cand, w.cnt, HDB_CAND_CAP, cq, (uint32_t)k, (uint32_t)k, ix->row_base, dev_idx + (int64_t)q0 * k,
+                                       dev_score + (int64_t)q0 * k, nullptr, nullptr, (int)ix->opt.finalize_threads, 0, st));
+        ix->st.chunks++;
+    }
+    return HDB_OK;
+}
+
+extern "C" int hdb_rerank(hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
+                          int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream) {
+    const int rc = rerank_sizes("hdb_rerank", nq, m, k, false);
+    if (rc) return rc;
+    return rerank_impl("hdb_rerank", ix, dev_Q, nq, dev_cand, m, k, metric, dev_idx, dev_score, dev_status, (hipStream_t)stream);
+}
+
+// a device record of at least `bytes` (hdb_packed_bytes) in *rec, grown by doubling
+static int ensure_record(char** rec, size_t* have, size_t bytes) {
+    if (bytes <= *have) return HDB_OK;
+    if (*rec) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*rec)); *rec = nullptr; *have = 0; }
+    HIP_TRY(hipMalloc((void**)rec, bytes * 2));
+    *have = bytes * 2;
+    return HDB_OK;
+}
+
+extern "C" int hdb_rerank_host(hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
+                               void* host_record, void* stream) {
+    int rc = rerank_sizes("hdb_rerank_host", nq, m, k, true);
+    if (rc) return rc;
+    if (!ix || !host_record) return fail(HDB_ERR_ARG, "hdb_rerank_host: null argument");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
+    rc = ensure_record(&ix->rec, &ix->rec_bytes, bytes);
+    if (rc) return rc;
+    char* rec = ix->rec;
+    rc = rerank_impl("hdb_rerank_host", ix, dev_Q, nq, dev_cand, m, k, metric, reinterpret_cast<int64_t*>(rec),
+                     reinterpret_cast<float*>(rec + (size_t)nq * k * 8), reinterpret_cast<int32_t*>(rec + (size_t)nq * k * 12), st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HDB_OK;
+}
+
+// Stage one on `first` into a device record of its own, its status words read back and the failed queries re-run exactly (as
+// hdb_topk_host does); the [nq][k1] ids then go straight into the rerank on `second`.
+extern "C" int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metric1, int32_t k1, hdb_index* second, const void* dev_Q2,
+                                  int metric2, int32_t k, int32_t nq, void* host_record, void* stream) {
+    int rc = rerank_sizes("hdb_two_stage_host", nq, k1, k, true);      // (k1 is the rerank's m)
+    if (rc) return rc;
+    if (!first || !second || !dev_Q1 || !dev_Q2 || !host_record) return fail(HDB_ERR_ARG, "hdb_two_stage_host: null argument");
+    if (first->device != second->device || first->n != second->n || first->row_base != second->row_base)
+        return fail(HDB_ERR_ARG, "hdb_two_stage_host: the two indexes must be on the same device and have the same n and row_base");
+    if ((int64_t)k1 > first->n) return fail(HDB_ERR_ARG, "hdb_two_stage_host: k1 must be at most min(8192, n)");
+    HIP_TRY(hipSetDevice(first->device));
+    hipStream_t st = (hipStream_t)stream;
+    rc = ensure_record(&first->rec1, &first->rec1_bytes, (size_t)hdb_packed_bytes(nq, k1));
+    if (rc) return rc;
+    char* rec = first->rec1;
+    int64_t* d_idx = reinterpret_cast<int64_t*>(rec);
+    float* d_sc = reinterpret_cast<float*>(rec + (size_t)nq * k1 * 8);
+    int32_t* d_st = reinterpret_cast<int32_t*>(rec + (size_t)nq * k1 * 12);
+    rc = topk_impl(first, dev_Q1, nq, k1, metric1, d_idx, d_sc, d_st, stream, false);
+    if (rc) return rc;
+    std::vector<int32_t> h_st((size_t)nq);
+    HIP_TRY(hipMemcpyAsync(h_st.data(), d_st, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t qbytes = (size_t)first->d * (first->dtype == HDB_F64 ? 8 : 4);
+    const TopkStats first_stats = first->st;          // (the statistics report the call's first attempt)
+    bool rerun = false;
+    for (int q = 0; q < nq; ++q) {
+        if (!(h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW))) continue;
+        rc = topk_impl(first, static_cast<const char*>(dev_Q1) + (size_t)q * qbytes, 1, k1, metric1, d_idx + (size_t)q * k1, d_sc + (size_t)q * k1,
+                       d_st + q, stream, true);
+        if (rc) return rc;
+        rerun = true;
+    }
+    if (rerun) first->st = first_stats;
+    return hdb_rerank_host(second, dev_Q2, nq, d_idx, k1, k, metric2, host_record, stream);
 }
 
 extern "C" int hdb_merge_topk(const int64_t* dev_idx_parts, const float* dev_score_parts, int32_t parts, int32_t nq,

@@ -163,6 +163,13 @@ int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cn
                               const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
                               void* stream);
 
+// ---- hdb_rerank.hip: exact scores of per-query candidate lists ----
+// prep: cand [nq][m] caller ids -> rows [nq][m] valid, ascending, unique local rows, cnt[q * HDB_CNT_STRIDE] of them, status[q]
+// score: ScanArgs as for the VALU scan, with rows = those lists, m = their leading dimension, cnt / cand / cap the packed lists out
+int hdb_launch_rerank_prep(const int64_t* cand, int m, int nq, int64_t n, int64_t row_base, const uint8_t* mask, const int* qnan,
+                           int64_t* rows, uint32_t* cnt, int32_t* status, void* stream);
+int hdb_launch_rerank_score(const ScanArgs* args, int dtype, int nq_launch, void* stream);
+
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);

@@ -62,7 +62,9 @@ struct hdb_options {
     int64_t use_subset = 1;           // a row list beside the mask (hdb_index_set_row_subset): score only the listed rows where the rule says so (0: never -- the mask)
     int64_t subset_min_n = -1;        // ... on matrices of at least this many rows (-1: the measured rule, HDB_SUBSET_MIN_ROWS)
     int64_t subset_ratio = -1;        // ... while m * ceil(nq / 4) * subset_ratio <= n (-1: the measured rule, HDB_SUBSET_RATIO; else an integer >= 1)
+    int64_t rerank_chunk = 0;         // hdb_rerank: queries per chunk (0: up to HDB_RERANK_MAXQ); the plan of hdb_topk does not read it
 };
+#define HDB_RERANK_MAXQ 256
 
 // ---- what the planner is told ---------------------------------------------------------------------------------------------------
 struct TopkFacts {
@@ -89,7 +91,7 @@ enum TopkPath {
     HDB_PATH_PIPELINE                 // the multi-kernel pipeline: small, sampled or exact
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
-struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0; };
+struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0; };
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;

@@ -72,6 +72,20 @@ struct TopkWs {
     }
 };
 
+// hdb_rerank: per-query words of the whole call, then the buffers of one chunk of cq queries.  m: the caller's list length -- the
+// prepared lists (valid, ascending, unique local rows) have that leading dimension; the packed entries keep the leading dimension
+// HDB_CAND_CAP the finalize kernel is launched with.  pearson: the centred queries.
+struct RerankWs {
+    float* qinv; float* qsq; int* qnan; void* qc; uint32_t* cnt; int64_t* rows; unsigned long long* cand;
+    void lay(Bump& b, int nq, int d, int cq, int m, bool pearson) {
+        qinv = b.take<float>(nq); qsq = b.take<float>(nq); qnan = b.take<int>(nq);
+        qc = pearson ? b.take<double>((size_t)nq * d) : nullptr;
+        cnt = b.take<uint32_t>((size_t)cq * HDB_CNT_STRIDE);
+        rows = b.take<int64_t>((size_t)cq * m);
+        cand = b.take<unsigned long long>((size_t)cq * HDB_CAND_CAP);
+    }
+};
+
 // ---- sample plans of the shadow paths -----------------------------------------------------------------------------------------
 // The strided row sample: s_tiles 16-row tiles spread evenly over the matrix, one score per sampled row and query in a buffer of
 // leading dimension ld_s.

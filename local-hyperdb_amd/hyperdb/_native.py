@@ -31,6 +31,8 @@ METRIC_IDS = {
 }
 EUCLIDEAN_DIST = 7
 Q_UNDERFLOW, Q_OVERFLOW, Q_NAN = 1, 2, 4
+Q_BADROW = 8                            # hdb_rerank: a candidate id outside the index (skipped, never read)
+CAND_CAP = 8192                         # longest candidate list of a rerank call (HDB_CAND_CAP)
 HDB_QUANT_NONE, HDB_QUANT_I8 = 0, 1
 QUANT_MODES = {None: HDB_QUANT_NONE, "int8": HDB_QUANT_I8}
 HDB_MAX_K = 2048
@@ -46,6 +48,7 @@ EXPORTS = (
     "hdb_topk_exact", "hdb_merge_topk", "hdb_set_option", "hdb_get_stat", "hdb_recency_bias", "hdb_recency_bias_twice",
     "hdb_packed_bytes", "hdb_merge_topk_packed", "hdb_merge_topk_host", "hdb_host_exchange_merge", "hdb_topk_host",
     "hdb_index_quantize", "hdb_debug_quant_bounds", "hdb_index_set_row_subset",
+    "hdb_rerank", "hdb_rerank_host", "hdb_two_stage_host",
 )
 
 
@@ -91,6 +94,9 @@ def _load():
     lib.hdb_recency_bias_twice.argtypes = [vp, vp, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]
     lib.hdb_topk_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_packed_bytes.argtypes = [i32, i32]
+    lib.hdb_rerank.argtypes = [vp, vp, i32, vp, i32, i32, ctypes.c_int, vp, vp, vp, vp]
+    lib.hdb_rerank_host.argtypes = [vp, vp, i32, vp, i32, i32, ctypes.c_int, vp, vp]
+    lib.hdb_two_stage_host.argtypes = [vp, vp, ctypes.c_int, i32, vp, vp, ctypes.c_int, i32, i32, vp, vp]
     lib.hdb_merge_topk_packed.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_host.argtypes = [vp, i32, i32, i32, vp]
     lib.hdb_host_exchange_merge.argtypes = [vp, i64, i32, i32, ctypes.c_uint64, vp, i32, i32, vp, ctypes.c_double]
@@ -798,12 +804,136 @@ class GpuIndex:
         self.topk_views(qt, k, metric_id)
         return self._host_records[(nq, int(k))][5]
 
+    # -- rerank: every query against its own list of rows -----------------------------------------
+    def _candidates(self, cand, nq):
+        """The lists of a rerank call -> (contiguous int64 tensor [nq, m] on the index's device, m); host arrays are range-checked."""
+        m = check_candidates(cand, nq, self.n, self.row_base)
+        if isinstance(cand, torch.Tensor):
+            if cand.device.type != "cpu" and cand.device != self.device:
+                raise ValueError(f"candidates live on {cand.device}, the index on {self.device}")
+            t = cand.detach().to(self.device, torch.int64)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(cand), dtype=np.int64)).to(self.device)
+        return t.contiguous(), m
+
+    def rerank_device(self, Q, cand, k, metric_id):
+        """Enqueue the exact top-k of every query among ITS OWN candidates (hdb_rerank): ``cand`` is ``[nq, m]`` global row ids, a
+        host array or an int64 CUDA tensor on the index's device; negative ids are padding.  Returns CUDA tensors (idx, score,
+        status); the status word of a query is 0, Q_NAN or Q_BADROW (an id outside the index: skipped)."""
+        qt = self._query_tensor(Q, batched=True)
+        nq = int(qt.shape[0])
+        ct, m = self._candidates(cand, nq)
+        k = int(k)
+        idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=self.device)
+        sc = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=self.device)
+        st = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_rerank(self._h, ctypes.c_void_p(qt.data_ptr()), nq, ctypes.c_void_p(ct.data_ptr()), m, k, int(metric_id),
+                                   ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(sc.data_ptr()), ctypes.c_void_p(st.data_ptr()),
+                                   _stream_ptr(self.device)), "hdb_rerank")
+        return idx, sc, st
+
+    def _record_slot(self, nq, k):
+        """The pinned result record of (nq, k) and its numpy views (topk_views keeps the same cache)."""
+        slot = self._host_records.get((nq, k))
+        if slot is None:
+            host = torch.empty(packed_bytes(nq, k), dtype=torch.uint8, pin_memory=True)
+            h = host.numpy()
+            slot = (host, host.data_ptr(), h[:nq * k * 8].view(np.int64).reshape(nq, k),
+                    h[nq * k * 8:nq * k * 12].view(np.float32).reshape(nq, k), h[nq * k * 12:nq * k * 12 + nq * 4].view(np.int32), h)
+            self._host_records[(nq, k)] = slot
+            while len(self._host_records) > HOST_RECORD_SLOTS:
+                self._host_records.popitem(last=False)
+        else:
+            self._host_records.move_to_end((nq, k))
+        return slot
+
+    @staticmethod
+    def _raise_rerank_status(st):
+        if (st & Q_NAN).any():
+            raise ValueError(NAN_MESSAGE)
+        if (st & Q_BADROW).any():
+            raise IndexError(f"{BADROW_MESSAGE}: the lists of queries {np.flatnonzero(st & Q_BADROW)[:8].tolist()} hold one")
+
+    def rerank(self, Q, cand, k, metric_id):
+        """rerank_device through one C call (hdb_rerank_host) -> numpy (int64 [nq,k], float32 [nq,k]) (copies).  Raises ValueError
+        on a NaN query and IndexError on a candidate id outside the index."""
+        qt = self._query_tensor(Q, batched=True)
+        nq = int(qt.shape[0])
+        ct, m = self._candidates(cand, nq)
+        k = int(k)
+        if nq == 0 or k < 1:
+            raise ValueError("rerank: need at least one query and k >= 1")
+        slot = self._record_slot(nq, k)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_rerank_host(self._h, ctypes.c_void_p(qt.data_ptr()), nq, ctypes.c_void_p(ct.data_ptr()), m, k, int(metric_id),
+                                        ctypes.c_void_p(slot[1]), _stream_ptr(self.device)), "hdb_rerank_host")
+        self._raise_rerank_status(slot[4])
+        return slot[2].copy(), slot[3].copy()
+
+    def two_stage(self, first, Q1, metric1_id, k1, Q2, metric2_id, k):
+        """One hdb_two_stage_host call: top-k1 of ``Q1`` on the index ``first``, those ids reranked on THIS index with ``Q2`` ->
+        numpy (int64 [nq,k], float32 [nq,k]) (copies).  ValueError when the two handles differ in n, row_base or device."""
+        if not isinstance(first, GpuIndex):
+            raise NotImplementedError("two_stage: the first stage must be a single GpuIndex")
+        if first.n != self.n or first.row_base != self.row_base or first.device != self.device:
+            raise ValueError("two_stage: the two indexes must hold the same rows (n, row_base) on the same device")
+        q1 = first._query_tensor(Q1, batched=True)
+        q2 = self._query_tensor(Q2, batched=True)
+        nq = int(q2.shape[0])
+        if int(q1.shape[0]) != nq:
+            raise ValueError(f"two_stage: {q1.shape[0]} first-stage queries for {nq} queries")
+        k, k1 = int(k), int(k1)
+        if nq == 0 or k < 1:
+            raise ValueError("two_stage: need at least one query and k >= 1")
+        slot = self._record_slot(nq, k)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_two_stage_host(first._h, ctypes.c_void_p(q1.data_ptr()), int(metric1_id), k1, self._h,
+                                           ctypes.c_void_p(q2.data_ptr()), int(metric2_id), k, nq, ctypes.c_void_p(slot[1]),
+                                           _stream_ptr(self.device)), "hdb_two_stage_host")
+        self._raise_rerank_status(slot[4])
+        return slot[2].copy(), slot[3].copy()
+
     def topk(self, Q, k, metric_id):
         """Top-k of a query batch on the host: (int64 [nq,k], float32 [nq,k]) (copies)."""
         idx, sc, st = self.topk_views(Q, k, metric_id)
         if (st[0] & Q_NAN) if len(st) == 1 else (st & Q_NAN).any():      # (one query: a scalar test instead of two array operations)
             raise ValueError(NAN_MESSAGE)
         return idx.copy(), sc.copy()
+
+
+BADROW_MESSAGE = "candidate id outside the index"
+
+
+def check_candidates(cand, nq, n, row_base):
+    """The candidate lists of a rerank call, checked on the host before any GPU call -> m, the list length.
+
+    ``cand`` is a 2-D integer array or tensor ``[nq, m]`` with ``1 <= m <= 8192`` (ValueError otherwise).  Ids are global (row_base
+    added, as top-k calls return them); a negative id is padding.  A HOST array is also range-checked: an id ``>= row_base + n``,
+    or a non-negative id below ``row_base``, raises IndexError naming the value.  A device tensor is not read here: the kernels
+    skip such an id and say so in the query's status word (Q_BADROW)."""
+    if isinstance(cand, torch.Tensor):
+        shape, integer, host = tuple(cand.shape), not (cand.dtype.is_floating_point or cand.dtype.is_complex or cand.dtype == torch.bool), None
+        if cand.device.type == "cpu":
+            host = cand.detach().numpy()
+    else:
+        host = cand if isinstance(cand, np.ndarray) else np.asarray(cand)
+        shape, integer = tuple(host.shape), host.dtype.kind in "iu"
+    if len(shape) != 2:
+        raise ValueError(f"candidates must be a 2-D array [nq, m], got shape {shape}")
+    if not integer:
+        raise ValueError("candidates must hold integer row ids")
+    if shape[0] != int(nq):
+        raise ValueError(f"candidates must have one list per query: {nq} queries, {shape[0]} lists")
+    m = int(shape[1])
+    if m < 1 or m > CAND_CAP:
+        raise ValueError(f"candidates per query must be in [1, {CAND_CAP}], got {m}")
+    if host is not None and host.size:
+        lo, hi = int(row_base), int(row_base) + int(n)
+        bad = (host >= hi) | ((host >= 0) & (host < lo))
+        if bad.any():
+            raise IndexError(f"{BADROW_MESSAGE}: {int(host[bad].reshape(-1)[0])} is not in [{lo}, {hi})")
+    return m
 
 
 def quant_mode(mode):

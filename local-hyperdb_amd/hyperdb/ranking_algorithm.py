@@ -14,7 +14,8 @@ reference's return types (int64 indices, float64 scores, ValueError on NaN / unk
   * a :class:`ResidentVectors`    - registered once with :func:`register_vectors`; the N x d
     matrix and its 1/||v|| cache stay in HBM between calls (what ``HyperDB`` uses).
 
-Additive surface (the reference has no batched call): :func:`rank_batch`.
+Additive surface (the reference has no batched call): :func:`rank_batch`; every query against its own list of rows:
+:func:`rerank_batch`; a cheap index in front of an exact one in one call: :func:`rank_two_stage`.
 
 There is NO CPU fallback: without the HIP library importing this module fails, and without a GPU every
 call raises ``HyperDBNativeError`` instead of silently computing on the host.
@@ -34,6 +35,7 @@ __all__ = [
     "get_norm_vector", "dot_product", "cosine_similarity", "euclidean_metric", "manhattan_distance",
     "jaccard_similarity", "pearson_correlation", "check_and_binarize_vectors", "hamming_distance",
     "hyperDB_ranking_algorithm_sort", "rank_batch", "register_vectors", "ResidentVectors",
+    "rerank_batch", "rank_two_stage",
 ]
 
 _GPU_METRICS = tuple(METRIC_IDS)      # all seven metrics of the reference's dispatch table have kernels
@@ -333,3 +335,80 @@ def rank_batch(vectors, query_vectors, top_k=5, metric='cosine_similarity', time
     finally:
         if owned:
             ix.close()
+
+
+def _single_index(vectors, what):
+    """The GpuIndex behind a handle of the rerank entry points; sharded and group handles are not served (ids would need routing)."""
+    ix = vectors.index if isinstance(vectors, ResidentVectors) else vectors
+    if not isinstance(ix, GpuIndex):
+        raise NotImplementedError(f"{what}: needs an index on one device (register_vectors without devices=, or a GpuIndex); "
+                                  "sharded and group handles are not served")
+    return ix
+
+
+def rerank_batch(vectors, query_vectors, candidates, top_k=5, metric='cosine_similarity', timestamps=None, recency_bias=0):
+    """Additive: the exact top-k of every query among ITS OWN candidate rows -- the second half of a two-stage search, of hybrid
+    search (candidates from a keyword index) and of per-query filters.
+
+    ``candidates`` is ``[Q, m]`` row ids (``1 <= m <= 8192``), a host array or an int64 CUDA tensor; ``-1`` is padding, an id
+    listed twice counts once, an id outside the index raises IndexError.  Returns ``(int64 (Q, k), float64 (Q, k))`` with
+    ``k = min(top_k, m)``, ordered by (score descending, id ascending); where a list holds fewer than k valid rows the tail is
+    ``-1`` / ``-inf``.  The scores are those a full ranking gives the same rows; recency is applied as in :func:`rank_batch`.
+    Not served: ``storage="bits"`` indexes, hamming and jaccard (NotImplementedError), sharded handles."""
+    ix, _, owned = _resolve(vectors)
+    try:
+        if not isinstance(ix, GpuIndex):
+            raise NotImplementedError("rerank_batch: sharded and group handles are not served")
+        qh = _query_host(query_vectors)
+        if qh.ndim == 1:
+            qh = qh.reshape(1, -1)
+        if ix.has_nan or np.isnan(qh).any():
+            raise ValueError(NAN_MESSAGE)
+        _validate_metric(metric)
+        m = _native.check_candidates(candidates, qh.shape[0], ix.n, ix.row_base)
+        k = max(0, min(int(top_k), m))
+        if k == 0:
+            return np.zeros((qh.shape[0], 0), np.int64), np.zeros((qh.shape[0], 0), np.float64)
+        had_bias = _apply_recency(ix, timestamps, recency_bias)
+        try:
+            idx, sc = ix.rerank(qh, candidates, k, METRIC_IDS[metric])
+        finally:
+            if had_bias:
+                ix.set_bias(None)
+        return idx.astype(np.int64), sc.astype(np.float64)
+    finally:
+        if owned:
+            ix.close()
+
+
+def rank_two_stage(first, second, query_vectors, top_k=5, oversample=4, metric='cosine_similarity', first_metric=None,
+                   first_queries=None):
+    """Additive: two-stage search in ONE library call.  The index ``first`` (typically ``storage="bits"``) retrieves
+    ``k1 = min(top_k * oversample, 8192, n)`` candidates per query, the index ``second`` over the same rows (int8 or float)
+    rescores them exactly with ``metric`` and the best ``min(top_k, k1)`` come back as ``(int64 (Q, k), float64 (Q, k))``.
+
+    ``first_metric`` defaults to ``metric``; ``first_queries`` defaults to ``query_vectors`` -- pass packed ``uint8`` queries for
+    a hamming first stage over a bits index.  Both handles are registered indexes on one device with the same rows: ValueError
+    when they differ in n, row_base or device, NotImplementedError for sharded or group handles."""
+    ix1, ix2 = _single_index(first, "rank_two_stage"), _single_index(second, "rank_two_stage")
+    if ix1.n != ix2.n or ix1.row_base != ix2.row_base or ix1.device != ix2.device:
+        raise ValueError("rank_two_stage: the two indexes must hold the same rows (n, row_base) on the same device")
+    fm = metric if first_metric is None else first_metric
+    _validate_metric(metric)
+    _validate_metric(fm)
+    qh = _query_host(query_vectors)
+    if qh.ndim == 1:
+        qh = qh.reshape(1, -1)
+    q1 = qh if first_queries is None else _query_host(first_queries)
+    if q1.ndim == 1:
+        q1 = q1.reshape(1, -1)
+    if ix1.has_nan or ix2.has_nan or np.isnan(qh).any() or np.isnan(q1).any():
+        raise ValueError(NAN_MESSAGE)
+    if ix2.n == 0:
+        raise ValueError("vectors is empty")
+    k1 = max(0, min(int(top_k) * int(oversample), _native.CAND_CAP, ix2.n))
+    k = max(0, min(int(top_k), k1))
+    if k == 0:
+        return np.zeros((qh.shape[0], 0), np.int64), np.zeros((qh.shape[0], 0), np.float64)
+    idx, sc = ix2.two_stage(ix1, q1, METRIC_IDS[fm], k1, qh, METRIC_IDS[metric], k)
+    return idx.astype(np.int64), sc.astype(np.float64)
