@@ -18,6 +18,7 @@
 #include "hdb_quant.h"
 #include "hdb_ws.h"
 #include "hdb_plan.h"
+#include "hdb_devbuf.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
 #include <cmath>
@@ -49,21 +50,19 @@ struct hdb_index {
     int dtype = HDB_F32;
     int device = 0;
     int64_t row_base = 0;
-    // per-row caches (owned)
-    float* inv_norm = nullptr;
-    float* sqnorm = nullptr;
-    int64_t cache_rows = 0;
-    int* nan_flag = nullptr;          // device int
+    // Device memory is owned through DevBuf (hdb_devbuf.h); a buffer's capacity is its `cap`, and a field beside it says more than that.
+    // per-row caches (owned; the two change together, inv_norm.cap is the capacity in rows of both)
+    DevBuf<float> inv_norm, sqnorm;
+    DevBuf<int> nan_flag;             // device int
     hipStream_t build_stream = nullptr;
     // hamming sign bits (owned, lazy)
-    uint32_t* bits = nullptr;
-    int64_t bits_npad = 0;
+    DevBuf<uint32_t> bits;
+    int64_t bits_npad = 0;            // its capacity in rows (bits.cap = bits_npad * W words), and a kernel argument
     int W = 0;
     bool bits_valid = false;
     int64_t bits_done = 0;            // rows [0, bits_done) are packed for the CURRENT matrix (hdb_index_extend keeps them: only the appended rows are packed)
     // pearson per-row scale 1/(sd*d) (owned, lazy)
-    float* pscale = nullptr;
-    int64_t pscale_rows = 0;
+    DevBuf<float> pscale;
     bool pscale_valid = false;
     int64_t pscale_done = 0;          // likewise
     // borrowed
@@ -73,38 +72,34 @@ struct hdb_index {
     const int64_t* rows = nullptr;
     int64_t subset_m = 0;
     // mask folded into a bias vector for the MFMA scan (owned, rebuilt per call: the mask and bias are borrowed)
-    float* mbias = nullptr;
-    int64_t mbias_rows = 0;
+    DevBuf<float> mbias;
     // control block of the single-launch pipeline (owned): counters + exchange granules, zero between calls
-    char* fctl = nullptr;
+    DevBuf<char> fctl;
     uint32_t fused_epoch = 0;
     // ... and of the single-launch BATCHED pipeline (hdb_mfma_kernel.h, MODE 2): counters, threshold words, sample granules
-    char* bctl = nullptr;
+    DevBuf<char> bctl;
     // device copy of the result record of hdb_topk_host (owned)
-    char* rec = nullptr;
-    size_t rec_bytes = 0;
+    DevBuf<char> rec;
     // ... and of stage one of hdb_two_stage_host (owned): its ids feed the rerank, which may use `rec` of the same handle
-    char* rec1 = nullptr;
-    size_t rec1_bytes = 0;
+    DevBuf<char> rec1;
     // int8 shadow of the matrix (owned, hdb_index_quantize; hdb_quant.hip): codes [rows][qP], caches [rows][3]
     int qmode = HDB_QUANT_NONE;
-    int8_t* qcodes = nullptr;
-    float* qaux = nullptr;
-    int64_t q_rows = 0;               // capacity in rows
+    DevBuf<int8_t> qcodes;
+    DevBuf<float> qaux;
+    int64_t q_rows = 0;               // capacity in rows of the shadow AND its plane: five arrays of different pitch share it
     int32_t qP = 0;                   // code pitch: d rounded up to 16 bytes
-    int* qstat = nullptr;             // device words (HDB_QSTAT_WORDS): [0] largest candidate count of the last quantized call,
+    DevBuf<int> qstat;                // device words (HDB_QSTAT_WORDS): [0] largest candidate count of the last quantized call,
                                       // [1] survivors of its pass over the 5-bit plane, [2] calls with more survivors than plane_cap_rows
     // the 5-bit plane beside the shadow (hdb_quant.hip): nibbles [rows][pU][16], bits [rows][pU], records [rows][4]; q_rows rows each
-    uint8_t* pnib = nullptr;
-    uint32_t* pbit = nullptr;
-    float* prec = nullptr;
+    DevBuf<uint8_t> pnib;
+    DevBuf<uint32_t> pbit;
+    DevBuf<float> prec;
     int32_t pU = 0;                   // 32-element units per row
     bool plane_declined = false;      // no memory for it (the shadow alone serves): stands until hdb_index_update / hdb_index_quantize
     bool qauto = false;               // the shadow was built by the index itself (auto_quant): its calls return the matrix cores' bits
     bool qauto_declined = false;      // ... or could not be (memory): the decision stands until the matrix changes
     // scratch (owned)
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<char> ws;
     hdb_options opt;                  // hdb_set_option (hdb_plan.h)
     int flags_host = -1;              // host copy of *nan_flag (HDB_FLAG_*, hdb_caps.h: 1 = a NaN row, 2 = a row with an infinite sum of squares, 4 = a row that may hold an element beyond half of fp16 range); -1 = not fetched since the last build
     // stats of the last hdb_topk call: the plan's (topk_impl), and whether hdb_topk_host wrote the caller's record directly
@@ -124,11 +119,8 @@ struct hdb_index {
 };
 
 static int ensure_ws(hdb_index* ix, size_t bytes) {
-    if (bytes <= ix->ws_bytes) return HDB_OK;
-    if (ix->ws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->ws)); ix->ws = nullptr; ix->ws_bytes = 0; }
-    bytes = align_up(bytes + (bytes >> 2), 1 << 20);
-    HIP_TRY(hipMalloc((void**)&ix->ws, bytes));
-    ix->ws_bytes = bytes;
+    if (bytes <= ix->ws.cap) return HDB_OK;
+    HIP_TRY(ix->ws.alloc(align_up(bytes + (bytes >> 2), 1 << 20)));      // (free first: a failure leaves no workspace, capacity 0)
     return HDB_OK;
 }
 // Lay a workspace out (hdb_ws.h): a dry run of the layout gives the size, the second run places the pointers.
@@ -136,7 +128,7 @@ template <typename WS, typename... Ext>
 static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     const int rc = ensure_ws(ix, ws_bytes_for<WS>(ext...));
     if (rc) return rc;
-    Bump b(ix->ws, ix->ws_bytes);
+    Bump b(ix->ws, ix->ws.cap);
     w.lay(b, ext...);
     if (b.off > b.cap) return fail(HDB_ERR_NOMEM, "workspace: a layout ran past the size it reported");
     return HDB_OK;
@@ -145,21 +137,40 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
 extern "C" int hdb_version(void) { return 109; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
-static int build_caches(hdb_index* ix, hipStream_t st) {
-    if (ix->n > ix->cache_rows) {
-        if (ix->inv_norm) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->inv_norm)); HIP_TRY(hipFree(ix->sqnorm)); }
-        const int64_t rows = ix->n + ix->n / 4 + 64;
-        HIP_TRY(hipMalloc((void**)&ix->inv_norm, rows * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&ix->sqnorm, rows * sizeof(float)));
-        ix->cache_rows = rows;
-    }
-    HIP_TRY(hipMemsetAsync(ix->nan_flag, 0, sizeof(int), st));
-    if (ix->n > 0) LAUNCH_TRY(hdb_launch_rownorm(ix->V, ix->n, ix->d, ix->dtype, ix->inv_norm, ix->sqnorm, ix->nan_flag, st));
-    ix->flags_host = -1;
-    ix->bits_valid = false; ix->bits_done = 0;         // a new matrix: nothing of the lazy caches survives
-    ix->pscale_valid = false; ix->pscale_done = 0;
-    ix->build_stream = st;
+// The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
+struct PackedRec { int64_t* idx; float* score; int32_t* status; };
+static PackedRec packed_view(const void* base, int32_t nq, int32_t k) {
+    char* b = static_cast<char*>(const_cast<void*>(base));
+    return {reinterpret_cast<int64_t*>(b), reinterpret_cast<float*>(b + (size_t)nq * k * 8), reinterpret_cast<int32_t*>(b + (size_t)nq * k * 12)};
+}
+// a device record of at least `bytes` (hdb_packed_bytes), grown by doubling
+static int ensure_record(DevBuf<char>& rec, size_t bytes) {
+    if (bytes <= rec.cap) return HDB_OK;
+    HIP_TRY(rec.alloc(bytes * 2));
     return HDB_OK;
+}
+
+// What a change of the matrix invalidates, stated once (create, update, extend, gather).  kept_rows: the rows that are the old
+// matrix's still -- 0, or the old n of an append, where the next hamming / pearson call packs the appended rows only.
+static void matrix_changed(hdb_index* ix, int64_t kept_rows, hipStream_t st) {
+    ix->flags_host = -1;
+    ix->bits_valid = false; ix->bits_done = std::min(ix->bits_done, kept_rows);
+    ix->pscale_valid = false; ix->pscale_done = std::min(ix->pscale_done, kept_rows);
+    ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old matrix no longer apply
+    ix->rows = nullptr; ix->subset_m = 0;
+    ix->build_stream = st;
+}
+// New blocks for the per-row caches.  The two change together: they are built beside the index and swapped in (caches_commit) after
+// the last step that can fail; the old blocks go when the CacheBufs does.
+struct CacheBufs { DevBuf<float> inv, sq; };
+static int caches_alloc(int64_t rows, CacheBufs& c) {
+    HIP_TRY(c.inv.alloc((size_t)rows));
+    HIP_TRY(c.sq.alloc((size_t)rows));
+    return HDB_OK;
+}
+static void caches_commit(hdb_index* ix, CacheBufs& c) {
+    if (!c.inv) return;                                // (the index had the room)
+    ix->inv_norm.swap(c.inv); ix->sqnorm.swap(c.sq);
 }
 
 // ---- int8 shadow (hdb_quant.hip) --------------------------------------------------------------
@@ -177,39 +188,30 @@ static size_t row_pitch(const hdb_index* ix) { return (size_t)hdb_row_bytes(ix->
 // the device words of hdb_index::qstat, zeroed on `st`; qstat stays null when the allocation itself fails
 static hipError_t qstat_alloc(hdb_index* ix, hipStream_t st) {
     if (ix->qstat) return hipSuccess;
-    const hipError_t e = hipMalloc((void**)&ix->qstat, HDB_QSTAT_WORDS * sizeof(int));
-    if (e != hipSuccess) { ix->qstat = nullptr; return e; }
-    return hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st);
+    const hipError_t e = ix->qstat.alloc(HDB_QSTAT_WORDS);
+    return e != hipSuccess ? e : hipMemsetAsync(ix->qstat, 0, HDB_QSTAT_WORDS * sizeof(int), st);
 }
-static void plane_free(hdb_index* ix) {
-    if (ix->pnib) (void)hipFree(ix->pnib);
-    if (ix->pbit) (void)hipFree(ix->pbit);
-    if (ix->prec) (void)hipFree(ix->prec);
-    ix->pnib = nullptr; ix->pbit = nullptr; ix->prec = nullptr;
-}
+static void plane_free(hdb_index* ix) { ix->pnib.reset(); ix->pbit.reset(); ix->prec.reset(); }
 static void quant_free(hdb_index* ix) {
-    if (ix->qcodes) (void)hipFree(ix->qcodes);
-    if (ix->qaux) (void)hipFree(ix->qaux);
-    ix->qcodes = nullptr; ix->qaux = nullptr; ix->q_rows = 0;
+    ix->qcodes.reset(); ix->qaux.reset(); ix->q_rows = 0;
     plane_free(ix);
 }
 // bytes of the 5-bit plane per row: 20 per 32-element unit and a 16-byte record (plane_possible, hdb_plan.h: rows of up to 512 elements)
 static size_t plane_row_bytes(int P) { return (size_t)hdb_quant_plane_units(P) * 20 + 16; }
-static bool plane_alloc(hdb_index* ix, int64_t rows, uint8_t** nib, uint32_t** bit, float** rec) {
+// the plane's three arrays for `rows` rows: all of them, or none and the index as it was
+static bool plane_alloc(hdb_index* ix, int64_t rows) {
     const size_t U = (size_t)hdb_quant_plane_units(ix->qP);
-    *nib = nullptr; *bit = nullptr; *rec = nullptr;
-    if (hipMalloc((void**)nib, (size_t)rows * U * 16) == hipSuccess && hipMalloc((void**)bit, (size_t)rows * U * 4) == hipSuccess &&
-        hipMalloc((void**)rec, (size_t)rows * 16) == hipSuccess) return true;
-    (void)hipGetLastError();
-    if (*nib) (void)hipFree(*nib);
-    if (*bit) (void)hipFree(*bit);
-    if (*rec) (void)hipFree(*rec);
-    *nib = nullptr; *bit = nullptr; *rec = nullptr;
-    return false;
+    DevBuf<uint8_t> nib; DevBuf<uint32_t> bit; DevBuf<float> rec;
+    if (nib.alloc((size_t)rows * U * 16) != hipSuccess || bit.alloc((size_t)rows * U) != hipSuccess || rec.alloc((size_t)rows * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    ix->pnib.swap(nib); ix->pbit.swap(bit); ix->prec.swap(rec);
+    return true;
 }
 // Derive the plane of rows [row0, row0 + m) from their codes; called wherever the shadow's rows are written.  The plane's arrays
 // have the shadow's capacity (q_rows >= n rows; pass 1 loads the rows below n only); a reallocated shadow has dropped
-// them (quant_free), and every row is derived again.  No memory: the index goes on without a plane.
+// them (quant_commit), and every row is derived again.  No memory: the index goes on without a plane.
 static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
     if (!plane_possible(ix->d) || ix->plane_declined) return HDB_OK;
     if (!ix->pnib && !plane_wanted(ix->d, ix->opt)) return HDB_OK;
@@ -218,28 +220,43 @@ static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->plane_declined = true; return HDB_OK; }
         if (free_b < (size_t)ix->q_rows * plane_row_bytes(ix->qP) + ((size_t)1 << 30)) { ix->plane_declined = true; return HDB_OK; }
-        if (!plane_alloc(ix, ix->q_rows, &ix->pnib, &ix->pbit, &ix->prec)) { ix->plane_declined = true; return HDB_OK; }
+        if (!plane_alloc(ix, ix->q_rows)) { ix->plane_declined = true; return HDB_OK; }
         ix->pU = hdb_quant_plane_units(ix->qP);
         m = row0 + m; row0 = 0;
     }
     LAUNCH_TRY(hdb_launch_quant_plane_rows(ix->qcodes, ix->qaux, row0, m, ix->d, ix->qP, ix->pnib, ix->pbit, ix->prec, st));
     return HDB_OK;
 }
+// New blocks for the shadow's codes and caches.  The two change together: built beside the index and swapped in (quant_commit) after
+// the last step that can fail; the old blocks go when the ShadowBufs does.
+struct ShadowBufs { DevBuf<int8_t> codes; DevBuf<float> aux; int64_t rows = 0; };
+static int quant_alloc(const hdb_index* ix, int64_t rows, ShadowBufs& s) {
+    hipError_t e = s.codes.alloc((size_t)rows * ix->qP);
+    if (e == hipSuccess) e = s.aux.alloc((size_t)rows * 3);
+    if (e != hipSuccess) return fail(HDB_ERR_NOMEM, std::string("the int8 shadow: ") + hipGetErrorString(e));
+    s.rows = rows;
+    return HDB_OK;
+}
+// ... for `need` rows where the shadow lacks the room (s stays empty where it has it)
+static int quant_room(const hdb_index* ix, int64_t need, bool tight, ShadowBufs& s) {
+    if (need <= ix->q_rows && ix->qcodes) return HDB_OK;
+    return quant_alloc(ix, tight ? need + 64 : need + need / 2 + 64, s);      // (tight: the automatic build -- no room for appends until one comes)
+}
+static void quant_commit(hdb_index* ix, ShadowBufs& s) {
+    if (!s.rows) return;
+    ix->qcodes.swap(s.codes); ix->qaux.swap(s.aux); ix->q_rows = s.rows;
+    plane_free(ix);                                    // the plane has the shadow's capacity: plane_rows derives all of it again
+}
 // room for `need` rows; the first `keep` rows of codes and caches survive a reallocation
 static int quant_reserve(hdb_index* ix, int64_t need, int64_t keep, hipStream_t st, bool tight = false) {
-    if (need <= ix->q_rows && ix->qcodes) return HDB_OK;
-    const int64_t rows = tight ? need + 64 : need + need / 2 + 64;      // (tight: the automatic build -- no room for appends until one comes)
-    int8_t* c2 = nullptr; float* a2 = nullptr;
-    HIP_TRY(hipMalloc((void**)&c2, (size_t)rows * ix->qP));
-    hipError_t e = hipMalloc((void**)&a2, (size_t)rows * 3 * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(c2); return fail(HDB_ERR_NOMEM, std::string("hdb_index_quantize: ") + hipGetErrorString(e)); }
+    ShadowBufs s;
+    const int rc = quant_room(ix, need, tight, s);
+    if (rc || !s.rows) return rc;
     if (keep > 0 && ix->qcodes) {
-        HIP_TRY(hipMemcpyAsync(c2, ix->qcodes, (size_t)keep * ix->qP, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(a2, ix->qaux, (size_t)keep * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s.codes, ix->qcodes, (size_t)keep * ix->qP, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s.aux, ix->qaux, (size_t)keep * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));
-    quant_free(ix);
-    ix->qcodes = c2; ix->qaux = a2; ix->q_rows = rows;          // (quant_free dropped the plane: plane_rows derives all of it again)
+    quant_commit(ix, s);
     return HDB_OK;
 }
 // quantize rows [row0, row0 + m) of the current matrix into the shadow, and derive their part of the plane
@@ -293,7 +310,7 @@ static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     const size_t shadow = (size_t)(ix->n + 64) * ((size_t)P + 12);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); ix->qauto_declined = true; return false; }
-    const size_t ws_grow = ws_need > ix->ws_bytes ? ws_need + (ws_need >> 2) + ((size_t)1 << 20) : 0;
+    const size_t ws_grow = ws_need > ix->ws.cap ? ws_need + (ws_need >> 2) + ((size_t)1 << 20) : 0;
     if (free_b < shadow + ws_grow + ((size_t)1 << 30)) { ix->qauto_declined = true; return false; }
     const size_t plane = plane_possible(ix->d) ? (size_t)(ix->n + 64) * plane_row_bytes(P) : 0;
     ix->plane_declined = plane_wanted(ix->d, ix->opt) && free_b < shadow + plane + ws_grow + ((size_t)1 << 30);
@@ -311,6 +328,21 @@ static bool quant_auto_build(hdb_index* ix, size_t ws_need, hipStream_t st) {
     return true;
 }
 
+// A new matrix (create, update): allocate first, then commit V, n and the buffers together, then fill the caches and the shadow.
+// An allocation that fails leaves the index on its old matrix, with its old buffers.
+static int build_caches(hdb_index* ix, const void* V, int64_t n, hipStream_t st) {
+    CacheBufs c; ShadowBufs s;
+    int rc = n > (int64_t)ix->inv_norm.cap ? caches_alloc(n + n / 4 + 64, c) : HDB_OK;
+    if (rc == HDB_OK && ix->qmode == HDB_QUANT_I8) rc = quant_room(ix, std::max<int64_t>(n, 1), false, s);      // the whole shadow is rebuilt
+    if (rc) return rc;
+    ix->V = V; ix->n = n;
+    caches_commit(ix, c); quant_commit(ix, s);
+    matrix_changed(ix, 0, st);                         // nothing of the lazy caches survives
+    HIP_TRY(hipMemsetAsync(ix->nan_flag, 0, sizeof(int), st));
+    if (n > 0) LAUNCH_TRY(hdb_launch_rownorm(V, n, ix->d, ix->dtype, ix->inv_norm, ix->sqnorm, ix->nan_flag, st));
+    return ix->qmode == HDB_QUANT_I8 ? quant_rows(ix, 0, n, st) : HDB_OK;
+}
+
 extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, int32_t d, int dtype, int device,
                                 int64_t row_base, void* stream) {
     if (!out) return fail(HDB_ERR_ARG, "hdb_index_create: out is null");
@@ -323,10 +355,9 @@ extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, i
     if (dtype == HDB_B1 && n > 0 && (reinterpret_cast<uintptr_t>(dev_V) & 3) != 0) return fail(HDB_ERR_ARG, "hdb_index_create: a packed-bit matrix must be 4-byte aligned");
     HIP_TRY(hipSetDevice(device));
     hdb_index* ix = new hdb_index();
-    ix->V = dev_V; ix->n = n; ix->d = d; ix->dtype = dtype; ix->device = device; ix->row_base = row_base;
-    hipError_t e = hipMalloc((void**)&ix->nan_flag, sizeof(int));
-    if (e != hipSuccess) { delete ix; return fail(HDB_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    int rc = build_caches(ix, (hipStream_t)stream);
+    ix->d = d; ix->dtype = dtype; ix->device = device; ix->row_base = row_base;
+    const hipError_t e = ix->nan_flag.alloc(1);
+    int rc = e == hipSuccess ? build_caches(ix, dev_V, n, (hipStream_t)stream) : fail(HDB_ERR_HIP, std::string("hdb_index_create: ") + hipGetErrorString(e));
     if (rc != HDB_OK) { hdb_index_destroy(ix); return rc; }
     *out = ix;
     return HDB_OK;
@@ -337,16 +368,11 @@ extern "C" int hdb_index_update(hdb_index* ix, const void* dev_V, int64_t n, voi
     if (n < 0 || (n > 0 && !dev_V)) return fail(HDB_ERR_ARG, "hdb_index_update: bad matrix");
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_update: at most 2^32-2 rows per shard");
     HIP_TRY(hipSetDevice(ix->device));
-    ix->V = dev_V; ix->n = n;
-    ix->bias = nullptr; ix->mask = nullptr; ix->rows = nullptr; ix->subset_m = 0;
-    ix->qauto_declined = false;                        // a new matrix: the memory question is asked again
+    // a new matrix: the memory question is asked again.  Only this call resets the two flags -- an append or a compaction changes
+    // no answer (matrix_changed leaves them alone)
+    ix->qauto_declined = false;
     ix->plane_declined = false;
-    int rc = build_caches(ix, (hipStream_t)stream);
-    if (rc == HDB_OK && ix->qmode == HDB_QUANT_I8) {          // a new matrix: the whole shadow is rebuilt
-        rc = quant_reserve(ix, std::max<int64_t>(n, 1), 0, (hipStream_t)stream);
-        if (rc == HDB_OK) rc = quant_rows(ix, 0, n, (hipStream_t)stream);
-    }
-    return rc;
+    return build_caches(ix, dev_V, n, (hipStream_t)stream);
 }
 
 extern "C" int hdb_index_rebase(hdb_index* ix, const void* dev_V) {
@@ -372,33 +398,30 @@ extern "C" int hdb_index_extend(hdb_index* ix, int64_t new_n, void* stream) {
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t old_n = ix->n;
-    if (new_n > ix->cache_rows) {                      // grow the per-row caches, keeping the old values
-        const int64_t rows = new_n + new_n / 2 + 64;
-        float *inv2 = nullptr, *sq2 = nullptr;
-        HIP_TRY(hipMalloc((void**)&inv2, rows * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&sq2, rows * sizeof(float)));
+    // Room first, for the caches and for the shadow, each keeping its first old_n rows: until n is committed below, a step that
+    // fails leaves the index on its old n rows, whose values every buffer still holds.
+    if (new_n > (int64_t)ix->inv_norm.cap) {
+        CacheBufs c;
+        const int rc = caches_alloc(new_n + new_n / 2 + 64, c);
+        if (rc) return rc;
         if (old_n > 0) {
-            HIP_TRY(hipMemcpyAsync(inv2, ix->inv_norm, old_n * sizeof(float), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(sq2, ix->sqnorm, old_n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c.inv, ix->inv_norm, old_n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(c.sq, ix->sqnorm, old_n * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
-        HIP_TRY(hipStreamSynchronize(st));
-        if (ix->inv_norm) { HIP_TRY(hipFree(ix->inv_norm)); HIP_TRY(hipFree(ix->sqnorm)); }
-        ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
+        caches_commit(ix, c);
+    }
+    if (ix->qmode == HDB_QUANT_I8) {
+        const int rc = quant_reserve(ix, new_n, old_n, st);
+        if (rc) return rc;
     }
     const char* tail = (const char*)ix->V + (size_t)old_n * row_pitch(ix);
     LAUNCH_TRY(hdb_launch_rownorm(tail, new_n - old_n, ix->d, ix->dtype, ix->inv_norm + old_n, ix->sqnorm + old_n, ix->nan_flag, st));
-    ix->n = new_n;
     if (ix->qmode == HDB_QUANT_I8) {                   // the shadow: the appended rows only
-        int rc = quant_reserve(ix, new_n, old_n, st);
-        if (rc == HDB_OK) rc = quant_rows(ix, old_n, new_n - old_n, st);
+        const int rc = quant_rows(ix, old_n, new_n - old_n, st);
         if (rc) return rc;
     }
-    ix->flags_host = -1;
-    ix->bits_valid = false;                            // (bits_done / pscale_done stay: the next hamming / pearson call packs the appended rows only)
-    ix->pscale_valid = false;
-    ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old length no longer apply
-    ix->rows = nullptr; ix->subset_m = 0;
-    ix->build_stream = st;
+    ix->n = new_n;
+    matrix_changed(ix, old_n, st);                     // (the next hamming / pearson call packs the appended rows only)
     return HDB_OK;
 }
 
@@ -409,61 +432,29 @@ extern "C" int hdb_index_gather(hdb_index* ix, const int64_t* dev_rows, int64_t 
     if (m > 0 && dev_V_out == ix->V) return fail(HDB_ERR_ARG, "hdb_index_gather: the gather is out of place");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    float *inv2 = nullptr, *sq2 = nullptr;
+    const bool shadow = ix->qmode == HDB_QUANT_I8;     // the shadow travels with its rows too
+    // new blocks always (the gather is out of place); the index keeps the old ones until the gathered ones are complete
+    CacheBufs c; ShadowBufs s;
     const int64_t rows = m + m / 4 + 64;
-    HIP_TRY(hipMalloc((void**)&inv2, rows * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&sq2, rows * sizeof(float)));
+    int rc = caches_alloc(rows, c);
+    if (rc == HDB_OK && shadow) rc = quant_alloc(ix, rows, s);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ix->nan_flag, 0, sizeof(int), st));
-    int rc = hdb_launch_gather_rows(ix->V, dev_rows, m, (int)row_pitch(ix), dev_V_out, ix->inv_norm, ix->sqnorm, inv2, sq2,
-                                    ix->nan_flag, st);
-    // the shadow travels with its rows too
-    int8_t* qc2 = nullptr; float* qa2 = nullptr;
-    if (rc == 0 && ix->qmode == HDB_QUANT_I8) {
-        rc = (int)hipMalloc((void**)&qc2, (size_t)rows * ix->qP);
-        if (rc == 0) rc = (int)hipMalloc((void**)&qa2, (size_t)rows * 3 * sizeof(float));
-        if (rc == 0) rc = hdb_launch_quant_gather(ix->qcodes, ix->qaux, dev_rows, m, ix->qP, qc2, qa2, st);
-    }
-    if (rc == 0) rc = (int)hipStreamSynchronize(st);          // the old caches (and the caller's old matrix) are free after this
-    if (rc != 0) {
-        (void)hipFree(inv2); (void)hipFree(sq2);
-        if (qc2) (void)hipFree(qc2);
-        if (qa2) (void)hipFree(qa2);
-        return fail(HDB_ERR_HIP, std::string("hdb_index_gather: ") + hipGetErrorString((hipError_t)rc));
-    }
-    if (ix->qmode == HDB_QUANT_I8) { quant_free(ix); ix->qcodes = qc2; ix->qaux = qa2; ix->q_rows = rows; }
-    if (ix->inv_norm) { (void)hipFree(ix->inv_norm); (void)hipFree(ix->sqnorm); }
-    ix->inv_norm = inv2; ix->sqnorm = sq2; ix->cache_rows = rows;
+    LAUNCH_TRY(hdb_launch_gather_rows(ix->V, dev_rows, m, (int)row_pitch(ix), dev_V_out, ix->inv_norm, ix->sqnorm, c.inv, c.sq, ix->nan_flag, st));
+    if (shadow) LAUNCH_TRY(hdb_launch_quant_gather(ix->qcodes, ix->qaux, dev_rows, m, ix->qP, s.codes, s.aux, st));
+    HIP_TRY(hipStreamSynchronize(st));                 // the caller's old matrix is free after this
     ix->V = dev_V_out; ix->n = m;
-    if (ix->qmode == HDB_QUANT_I8) {                   // the plane is derived again from the gathered codes
-        const int rcp = plane_rows(ix, 0, m, st);
-        if (rcp != HDB_OK) return rcp;
-    }
-    ix->flags_host = -1;
-    ix->bits_valid = false; ix->pscale_valid = false; ix->bits_done = 0; ix->pscale_done = 0;
-    ix->bias = nullptr; ix->mask = nullptr; ix->rows = nullptr; ix->subset_m = 0;
-    ix->build_stream = st;
-    return HDB_OK;
+    caches_commit(ix, c); quant_commit(ix, s);
+    matrix_changed(ix, 0, st);
+    return shadow ? plane_rows(ix, 0, m, st) : HDB_OK; // the plane is derived again from the gathered codes
 }
 
 extern "C" void hdb_index_destroy(hdb_index* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
-    if (ix->inv_norm) (void)hipFree(ix->inv_norm);
-    if (ix->sqnorm) (void)hipFree(ix->sqnorm);
-    if (ix->nan_flag) (void)hipFree(ix->nan_flag);
-    if (ix->bits) (void)hipFree(ix->bits);
-    if (ix->pscale) (void)hipFree(ix->pscale);
-    if (ix->mbias) (void)hipFree(ix->mbias);
-    if (ix->fctl) (void)hipFree(ix->fctl);
-    if (ix->bctl) (void)hipFree(ix->bctl);
-    if (ix->ws) (void)hipFree(ix->ws);
-    if (ix->rec) (void)hipFree(ix->rec);
-    if (ix->rec1) (void)hipFree(ix->rec1);
-    quant_free(ix);
-    if (ix->qstat) (void)hipFree(ix->qstat);
     for (hipEvent_t e : ix->ev_pool) (void)hipEventDestroy(e);
-    delete ix;
+    delete ix;                                         // every DevBuf frees its block
 }
 
 extern "C" int hdb_index_has_nan(hdb_index* ix, int* out_flag) {
@@ -629,7 +620,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
         *value = v;
     }
     else if (!strcmp(name, "n")) *value = ix->n;
-    else if (!strcmp(name, "ws_bytes")) *value = (int64_t)ix->ws_bytes;
+    else if (!strcmp(name, "ws_bytes")) *value = (int64_t)ix->ws.cap;
     else if (!strcmp(name, "scan_launches")) *value = (int64_t)(ix->ev_used / 2);
     else if (!strcmp(name, "host_pre_ns")) *value = ix->ht_pre_ns;
     else if (!strcmp(name, "host_launch_ns")) *value = ix->ht_launch_ns;
@@ -670,14 +661,7 @@ static bool metric_ok(int metric) { return metric >= HDB_DOT && metric <= HDB_EU
 static int ensure_pscale(hdb_index* ix, hipStream_t st) {
     if (ix->pscale_valid) return HDB_OK;
     int64_t keep = ix->pscale ? std::min(ix->pscale_done, ix->n) : 0;          // rows whose scale is still good (appended matrix)
-    if (ix->n > ix->pscale_rows) {
-        const int64_t rows = ix->n + ix->n / 4 + 64;
-        float* p2 = nullptr;
-        HIP_TRY(hipMalloc((void**)&p2, rows * sizeof(float)));
-        if (keep > 0) HIP_TRY(hipMemcpyAsync(p2, ix->pscale, keep * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (ix->pscale) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->pscale)); }
-        ix->pscale = p2; ix->pscale_rows = rows;
-    }
+    if (ix->n > (int64_t)ix->pscale.cap) HIP_TRY(ix->pscale.grow_keep((size_t)(ix->n + ix->n / 4 + 64), (size_t)keep, st));
     if (ix->n > keep)
         LAUNCH_TRY(hdb_launch_rowstats((const char*)ix->V + (size_t)keep * row_pitch(ix), ix->n - keep, ix->d, ix->dtype, ix->pscale + keep, st));
     ix->pscale_done = ix->n;
@@ -695,12 +679,11 @@ static int ensure_bits(hdb_index* ix, hipStream_t st) {
     int64_t keep = (ix->bits && ix->W == W) ? std::min(ix->bits_done, ix->n) : 0;
     if (!ix->bits || ix->bits_npad < npad || ix->W != W) {
         const int64_t cap = align_up((size_t)(npad + npad / 4), 256);
-        uint32_t* b2 = nullptr;
-        HIP_TRY(hipMalloc((void**)&b2, (size_t)cap * W * sizeof(uint32_t)));
+        DevBuf<uint32_t> b2;                               // zero-filled, then the kept blocks: swapped in when both are queued
+        HIP_TRY(b2.alloc((size_t)cap * W));
         HIP_TRY(hipMemsetAsync(b2, 0, (size_t)cap * W * sizeof(uint32_t), st));
         if (keep > 0) HIP_TRY(hipMemcpyAsync(b2, ix->bits, (size_t)align_up((size_t)keep, 256) * W * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        if (ix->bits) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->bits)); }
-        ix->bits = b2; ix->bits_npad = cap; ix->W = W;
+        ix->bits.swap(b2); ix->bits_npad = cap; ix->W = W;
     } else if (keep == 0) {
         HIP_TRY(hipMemsetAsync(ix->bits, 0, (size_t)ix->bits_npad * W * sizeof(uint32_t), st));
     }
@@ -858,7 +841,7 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     QuantWs w;
     int rc = quant_ws_lay(ix, w, nq, quant_hi_cap(ix, nq), mflavour);
     if (rc) return rc;
-    uint32_t* qstat = reinterpret_cast<uint32_t*>(ix->qstat);
+    uint32_t* qstat = reinterpret_cast<uint32_t*>(ix->qstat.p);
     uint32_t* pl_cnt = use_pl ? qstat + 1 : nullptr;
     const size_t crow = (size_t)nq * HDB_CAND_CAP;
     const int nsub = p.nsub;
@@ -999,10 +982,12 @@ static uint32_t next_epoch(hdb_index* ix) {
     return ix->fused_epoch;
 }
 static uint32_t timeout_ticks(const hdb_index* ix) { return (uint32_t)std::min<int64_t>(ix->opt.fused_timeout_us * 100, 0x7FFFFFFF); }
-static int ensure_ctl(char** ctl, size_t bytes) {
-    if (*ctl) return HDB_OK;
-    HIP_TRY(hipMalloc((void**)ctl, bytes));
-    HIP_TRY(hipMemset(*ctl, 0, bytes));
+static int ensure_ctl(DevBuf<char>& ctl, size_t bytes) {
+    if (ctl) return HDB_OK;
+    DevBuf<char> c2;                                   // (the index takes the block once it is zero)
+    HIP_TRY(c2.alloc(bytes));
+    HIP_TRY(hipMemset(c2, 0, bytes));
+    ctl.swap(c2);
     return HDB_OK;
 }
 
@@ -1045,12 +1030,7 @@ static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkE
     }
     e.bias_eff = ix->bias; e.mask_eff = ix->mask;
     if (p.mask_fold) {
-        if (n > ix->mbias_rows) {
-            if (ix->mbias) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->mbias)); ix->mbias = nullptr; }
-            const int64_t rows = n + n / 4 + 64;
-            HIP_TRY(hipMalloc((void**)&ix->mbias, rows * sizeof(float)));
-            ix->mbias_rows = rows;
-        }
+        if (n > (int64_t)ix->mbias.cap) HIP_TRY(ix->mbias.alloc((size_t)(n + n / 4 + 64)));
         LAUNCH_TRY(hdb_launch_maskbias(ix->mask, ix->bias, n, ix->mbias, st));
         e.bias_eff = ix->mbias; e.mask_eff = nullptr;
     }
@@ -1079,7 +1059,7 @@ static int run_full_sort(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
 static int run_fused(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     TopkEnv e;
     int rc = topk_begin(ix, c, p, e); if (rc) return rc;
-    rc = ensure_ctl(&ix->fctl, hdb_mfma_fused_ctl_bytes()); if (rc) return rc;
+    rc = ensure_ctl(ix->fctl, hdb_mfma_fused_ctl_bytes()); if (rc) return rc;
     ScanArgs a; base_args(ix, a, c.Q, c.metric);
     a.bias = e.bias_eff; a.mask = nullptr;
     if (c.metric == HDB_EUCLIDEAN) a.inv_norm = ix->sqnorm;        // the per-row aux value of the euclidean expansion
@@ -1091,7 +1071,7 @@ static int run_fused(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     fa.s_tiles = p.s_tiles; fa.s_stride = p.s_stride;
     fa.epoch = next_epoch(ix);
     fa.timeout_ticks = timeout_ticks(ix);
-    fa.ctl = reinterpret_cast<uint32_t*>(ix->fctl);
+    fa.ctl = reinterpret_cast<uint32_t*>(ix->fctl.p);
     fa.cand = e.w.cand; fa.cap = HDB_CAND_CAP; fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
     fa.idx_out = c.idx; fa.score_out = c.score; fa.status = c.status; fa.thr_out = e.w.thr;
     fa.local = p.local ? 1 : 0; fa.local_slot = p.local_slot; fa.local_m = p.local_m;
@@ -1108,7 +1088,7 @@ static int run_fused(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
 static int run_bits1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     TopkEnv e;
     int rc = topk_begin(ix, c, p, e); if (rc) return rc;
-    rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
+    rc = ensure_ctl(ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
     for (int q0 = 0; q0 < c.nq; q0 += 4) {
         const int cq = std::min(4, c.nq - q0);
         BitsArgs ba; memset(&ba, 0, sizeof(ba));
@@ -1119,7 +1099,7 @@ static int run_bits1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         ba.local = p.bits_local;
         ba.epoch = next_epoch(ix);
         ba.timeout_ticks = timeout_ticks(ix);
-        ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
+        ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl.p);
         ba.cand = e.w.cand; ba.cap = HDB_CAND_CAP; ba.k = (uint32_t)c.k; ba.kk = p.kk; ba.row_base = ix->row_base;
         ba.idx_out = c.idx + (int64_t)q0 * c.k; ba.score_out = c.score + (int64_t)q0 * c.k; ba.status = c.status + q0;
         prof_begin(ix, c.st);
@@ -1136,7 +1116,7 @@ static int run_bits1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
 static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     TopkEnv e;
     int rc = topk_begin(ix, c, p, e); if (rc) return rc;
-    rc = ensure_ctl(&ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
+    rc = ensure_ctl(ix->bctl, hdb_mfma_batch_ctl_bytes(hdb_cu_count())); if (rc) return rc;
     const size_t qrow = (size_t)ix->d * 4;
     for (int q0 = 0; q0 < c.nq; q0 += p.cq_max) {
         const int cq = std::min(p.cq_max, c.nq - q0);
@@ -1145,13 +1125,13 @@ static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         a.bias = e.bias_eff; a.mask = nullptr; a.q0 = 0; a.nq = cq; a.f32_split = p.f32s ? 1 : 0;
         a.ntiles = (ix->n + p.tile_rows - 1) / p.tile_rows;
         a.cand = e.w.cand;
-        a.tile_ctr = ix->opt.dyn_tiles ? reinterpret_cast<uint32_t*>(ix->bctl) + HDB_BATCH_CTL_TILE : nullptr;
+        a.tile_ctr = ix->opt.dyn_tiles ? reinterpret_cast<uint32_t*>(ix->bctl.p) + HDB_BATCH_CTL_TILE : nullptr;
         BatchArgs fa; memset(&fa, 0, sizeof(fa));
         fa.Qraw = static_cast<const char*>(c.Q) + (size_t)q0 * qrow;
         fa.s_tiles = p.s_tiles; fa.s_stride = p.s_stride; fa.centre = p.pearson ? 1 : 0;
         fa.epoch = next_epoch(ix);
         fa.timeout_ticks = timeout_ticks(ix);
-        fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl);
+        fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl.p);
         fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
         fa.idx_out = c.idx + (int64_t)q0 * c.k; fa.score_out = c.score + (int64_t)q0 * c.k; fa.status = c.status + q0;
         prof_begin(ix, c.st);
@@ -1296,23 +1276,23 @@ extern "C" int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k,
 
 // k-way merge of `parts` packed records in host memory (recs[p] = record of shard p) into out_record
 static void merge_host_records(const char* const* recs, int32_t parts, int32_t nq, int32_t k, void* out_record) {
-    int64_t* oi = reinterpret_cast<int64_t*>(out_record);
-    float* os = reinterpret_cast<float*>(static_cast<char*>(out_record) + (int64_t)nq * k * 8);
-    int32_t* ost = reinterpret_cast<int32_t*>(static_cast<char*>(out_record) + (int64_t)nq * k * 12);
+    const PackedRec out = packed_view(out_record, nq, k);
+    int64_t* oi = out.idx; float* os = out.score; int32_t* ost = out.status;
+    auto in = [&](int32_t p) { return packed_view(recs[p], nq, k); };
     std::vector<int32_t> pos((size_t)parts);
     for (int32_t q = 0; q < nq; ++q) {
         int32_t st = 0;
         for (int32_t p = 0; p < parts; ++p) {
-            st |= reinterpret_cast<const int32_t*>(recs[p] + (int64_t)nq * k * 12)[q];
+            st |= in(p).status[q];
             pos[p] = 0;
         }
         for (int32_t i = 0; i < k; ++i) {                // lists sorted by (score descending, row ascending)
             int32_t best = -1; int64_t bi = -1; float bs = 0.f;
             for (int32_t p = 0; p < parts; ++p) {
                 if (pos[p] >= k) continue;
-                const int64_t ci = reinterpret_cast<const int64_t*>(recs[p])[(int64_t)q * k + pos[p]];
+                const int64_t ci = in(p).idx[(int64_t)q * k + pos[p]];
                 if (ci < 0) { pos[p] = k; continue; }    // padding: this shard has no more rows
-                const float cs = reinterpret_cast<const float*>(recs[p] + (int64_t)nq * k * 8)[(int64_t)q * k + pos[p]];
+                const float cs = in(p).score[(int64_t)q * k + pos[p]];
                 if (best < 0 || cs > bs || (cs == bs && ci < bi)) { best = p; bi = ci; bs = cs; }
             }
             if (best < 0) { oi[(int64_t)q * k + i] = -1; os[(int64_t)q * k + i] = -INFINITY; }
@@ -1377,22 +1357,18 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     ix->st_host_direct = direct ? 1 : 0;
     char* rec = static_cast<char*>(host_record);
     if (!direct) {
-        if (bytes > ix->rec_bytes) {
-            if (ix->rec) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ix->rec)); ix->rec = nullptr; }
-            HIP_TRY(hipMalloc((void**)&ix->rec, bytes * 2));
-            ix->rec_bytes = bytes * 2;
-        }
+        const int rc = ensure_record(ix->rec, bytes);
+        if (rc) return rc;
         rec = ix->rec;
     }
-    int64_t* d_idx = reinterpret_cast<int64_t*>(rec);
-    float* d_sc = reinterpret_cast<float*>(rec + (size_t)nq * k * 8);
-    int32_t* d_st = reinterpret_cast<int32_t*>(rec + (size_t)nq * k * 12);
+    const PackedRec dr = packed_view(rec, nq, k);
+    int64_t* d_idx = dr.idx; float* d_sc = dr.score; int32_t* d_st = dr.status;
     // Pinned record: the status words are stored last (by the single-launch kernel's final workgroup, or by each query's
     // finalize workgroup), behind a system-scope release, so the host can poll them instead of waiting for the completion
     // signal of the last kernel (end-of-kernel drain, cache write-back, signal, wake-up: ~5-10 us).  The stream stays
     // ordered: the next launch queues behind the kernels.
     constexpr int32_t SENTINEL = 0x7FFFFFFF;
-    volatile int32_t* poll = reinterpret_cast<volatile int32_t*>(static_cast<char*>(host_record) + (size_t)nq * k * 12);
+    volatile int32_t* poll = packed_view(host_record, nq, k).status;
     if (direct && ix->opt.host_poll) for (int q = 0; q < nq; ++q) poll[q] = SENTINEL;
     ix->ht_l0 = ix->ht_l1 = std::chrono::steady_clock::now();      // (pipelines of several launches: everything counts as "pre")
     int rc = topk_impl(ix, dev_Q, nq, k, metric, d_idx, d_sc, d_st, stream, false);
@@ -1419,7 +1395,7 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
         ix->ht_wait_ns += std::chrono::duration_cast<ns>(ht3 - ix->ht_l1).count();
         ix->ht_calls++;
     }
-    const int32_t* h_st = reinterpret_cast<const int32_t*>(static_cast<const char*>(host_record) + (size_t)nq * k * 12);
+    const int32_t* h_st = packed_view(host_record, nq, k).status;
     bool any_bad = false;
     for (int q = 0; q < nq; ++q) any_bad |= (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) != 0;
     if (!any_bad) return HDB_OK;
@@ -1504,15 +1480,6 @@ extern "C" int hdb_rerank(hdb_index* ix, const void* dev_Q, int32_t nq, const in
     return rerank_impl("hdb_rerank", ix, dev_Q, nq, dev_cand, m, k, metric, dev_idx, dev_score, dev_status, (hipStream_t)stream);
 }
 
-// a device record of at least `bytes` (hdb_packed_bytes) in *rec, grown by doubling
-static int ensure_record(char** rec, size_t* have, size_t bytes) {
-    if (bytes <= *have) return HDB_OK;
-    if (*rec) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*rec)); *rec = nullptr; *have = 0; }
-    HIP_TRY(hipMalloc((void**)rec, bytes * 2));
-    *have = bytes * 2;
-    return HDB_OK;
-}
-
 extern "C" int hdb_rerank_host(hdb_index* ix, const void* dev_Q, int32_t nq, const int64_t* dev_cand, int32_t m, int32_t k, int metric,
                                void* host_record, void* stream) {
     int rc = rerank_sizes("hdb_rerank_host", nq, m, k, true);
@@ -1521,13 +1488,12 @@ extern "C" int hdb_rerank_host(hdb_index* ix, const void* dev_Q, int32_t nq, con
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
-    rc = ensure_record(&ix->rec, &ix->rec_bytes, bytes);
+    rc = ensure_record(ix->rec, bytes);
     if (rc) return rc;
-    char* rec = ix->rec;
-    rc = rerank_impl("hdb_rerank_host", ix, dev_Q, nq, dev_cand, m, k, metric, reinterpret_cast<int64_t*>(rec),
-                     reinterpret_cast<float*>(rec + (size_t)nq * k * 8), reinterpret_cast<int32_t*>(rec + (size_t)nq * k * 12), st);
+    const PackedRec r = packed_view(ix->rec, nq, k);
+    rc = rerank_impl("hdb_rerank_host", ix, dev_Q, nq, dev_cand, m, k, metric, r.idx, r.score, r.status, st);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HDB_OK;
 }
@@ -1544,12 +1510,10 @@ extern "C" int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metr
     if ((int64_t)k1 > first->n) return fail(HDB_ERR_ARG, "hdb_two_stage_host: k1 must be at most min(8192, n)");
     HIP_TRY(hipSetDevice(first->device));
     hipStream_t st = (hipStream_t)stream;
-    rc = ensure_record(&first->rec1, &first->rec1_bytes, (size_t)hdb_packed_bytes(nq, k1));
+    rc = ensure_record(first->rec1, (size_t)hdb_packed_bytes(nq, k1));
     if (rc) return rc;
-    char* rec = first->rec1;
-    int64_t* d_idx = reinterpret_cast<int64_t*>(rec);
-    float* d_sc = reinterpret_cast<float*>(rec + (size_t)nq * k1 * 8);
-    int32_t* d_st = reinterpret_cast<int32_t*>(rec + (size_t)nq * k1 * 12);
+    const PackedRec r1 = packed_view(first->rec1, nq, k1);
+    int64_t* d_idx = r1.idx; float* d_sc = r1.score; int32_t* d_st = r1.status;
     rc = topk_impl(first, dev_Q1, nq, k1, metric1, d_idx, d_sc, d_st, stream, false);
     if (rc) return rc;
     std::vector<int32_t> h_st((size_t)nq);
@@ -1594,9 +1558,8 @@ extern "C" int hdb_merge_topk_packed(const void* dev_gathered, int32_t parts, in
     if ((int64_t)parts * k > HDB_CAND_CAP) return fail(HDB_ERR_UNSUPPORTED, "hdb_merge_topk_packed: parts*k exceeds 8192");
     HIP_TRY(hipSetDevice(device));
     const int64_t stride = hdb_packed_bytes(nq, k);
-    const char* base = (const char*)dev_gathered;
-    LAUNCH_TRY(hdb_launch_merge(base, stride, base + (int64_t)nq * k * 8, stride, base + (int64_t)nq * k * 12, stride, parts, nq,
-                                (uint32_t)k, dev_idx, dev_score, dev_status, stream));
+    const PackedRec r = packed_view(dev_gathered, nq, k);      // the first shard's; the others follow at `stride`
+    LAUNCH_TRY(hdb_launch_merge(r.idx, stride, r.score, stride, r.status, stride, parts, nq, (uint32_t)k, dev_idx, dev_score, dev_status, stream));
     return HDB_OK;
 }
 
@@ -1647,8 +1610,7 @@ struct hdb_group {
     int parts = 0;
     std::vector<hdb_index*> ix;
     std::vector<hipStream_t> st;
-    std::vector<void*> qdev;
-    std::vector<size_t> qcap;
+    std::vector<DevBuf<char>> qdev;                       // per shard: the device copy of a batch of more than four queries
     std::vector<char> shared_dev;                         // shard p shares its device with another shard of the group
     char* gather = nullptr; size_t gather_bytes = 0;     // pinned + portable host memory: parts records
     char* qpin = nullptr; size_t qpin_bytes = 0;         // pinned + portable host memory: the queries of the current call
@@ -1695,11 +1657,7 @@ static void group_worker(hdb_group* g, int p) {
             const void* dq = g->qpin;                                // up to four queries: the kernels read the pinned staging buffer
             if (g->nq > 4) {
                 hipError_t e = hipSuccess;
-                if (g->q_bytes > g->qcap[p]) {
-                    if (g->qdev[p]) { (void)hipStreamSynchronize(st); (void)hipFree(g->qdev[p]); g->qdev[p] = nullptr; g->qcap[p] = 0; }
-                    e = hipMalloc(&g->qdev[p], g->q_bytes * 2);
-                    if (e == hipSuccess) g->qcap[p] = g->q_bytes * 2;
-                }
+                if (g->q_bytes > g->qdev[p].cap) e = g->qdev[p].alloc(g->q_bytes * 2);
                 if (e == hipSuccess) e = hipMemcpyAsync(g->qdev[p], g->qpin, g->q_bytes, hipMemcpyHostToDevice, st);
                 if (e != hipSuccess) { rc = HDB_ERR_HIP; msg = std::string("hdb_group: query upload: ") + hipGetErrorString(e); }
                 dq = g->qdev[p];
@@ -1712,12 +1670,9 @@ static void group_worker(hdb_group* g, int p) {
                 if (rc != HDB_OK) msg = hdb_last_error();
             }
         } else {                                                     // an empty shard contributes padding
-            char* rec = g->gather + (size_t)p * g->stride;
-            int64_t* ri = reinterpret_cast<int64_t*>(rec);
-            float* rs = reinterpret_cast<float*>(rec + (size_t)g->nq * g->k * 8);
-            int32_t* rst = reinterpret_cast<int32_t*>(rec + (size_t)g->nq * g->k * 12);
-            for (size_t i = 0; i < (size_t)g->nq * g->k; ++i) { ri[i] = -1; rs[i] = -INFINITY; }
-            for (int q = 0; q < g->nq; ++q) rst[q] = 0;
+            const PackedRec r = packed_view(g->gather + (size_t)p * g->stride, g->nq, g->k);
+            for (size_t i = 0; i < (size_t)g->nq * g->k; ++i) { r.idx[i] = -1; r.score[i] = -INFINITY; }
+            for (int q = 0; q < g->nq; ++q) r.status[q] = 0;
         }
         g->rc[p] = rc; g->err[p] = msg;
         if (g->pending.fetch_sub(1, std::memory_order_acq_rel) == 1) {
@@ -1736,7 +1691,7 @@ extern "C" void hdb_group_destroy(hdb_group* g) {
     for (int p = 0; p < (int)g->st.size(); ++p) {
         (void)hipSetDevice(g->ix[p]->device);
         if (g->st[p]) { (void)hipStreamSynchronize(g->st[p]); (void)hipStreamDestroy(g->st[p]); }
-        if (p < (int)g->qdev.size() && g->qdev[p]) (void)hipFree(g->qdev[p]);
+        if (p < (int)g->qdev.size()) g->qdev[p].reset();      // (on its own device)
     }
     if (g->gather) (void)hipHostFree(g->gather);
     if (g->qpin) (void)hipHostFree(g->qpin);
@@ -1754,7 +1709,7 @@ extern "C" int hdb_group_create(hdb_group** out, hdb_index* const* shards, int32
     hdb_group* g = new hdb_group();
     g->parts = parts;
     g->ix.assign(shards, shards + parts);
-    g->st.assign(parts, nullptr); g->qdev.assign(parts, nullptr); g->qcap.assign(parts, 0);
+    g->st.assign(parts, nullptr); g->qdev = std::vector<DevBuf<char>>((size_t)parts);
     g->rc.assign(parts, 0); g->err.assign(parts, std::string());
     g->shared_dev.assign(parts, 0);
     for (int p = 0; p < parts; ++p)

@@ -64,11 +64,11 @@ def _align(x, a):
 
 # ---- the library's capacities as functions of the row counts it has seen (hdb_api.hip) ---------------------------------------------
 class Caps:
-    """Row counts only.  cache_rows: build_caches n + n/4 + 64 (kept when the new matrix fits), hdb_index_extend n + n/2 + 64 when it
-    grows, hdb_index_gather m + m/4 + 64.  bits_cap: ensure_bits, align_up(npad + npad/4, 256) over npad = align_up(max(n, 4), 256),
-    reallocated by the bit-metric call that finds it short, never shrunk.  q_rows: quant_reserve need + need/2 + 64 (the automatic
-    build need + 64), the gather's m + m/4 + 64; an automatic shadow is built by the first 1-4-query dot / cosine top-k on more than
-    CAND_CAP finite rows."""
+    """Row counts only.  cache_rows (inv_norm.cap): build_caches n + n/4 + 64 (kept when the new matrix fits), hdb_index_extend
+    n + n/2 + 64 when it grows, hdb_index_gather m + m/4 + 64.  bits_cap: ensure_bits, align_up(npad + npad/4, 256) over
+    npad = align_up(max(n, 4), 256), reallocated by the bit-metric call that finds it short, never shrunk.  q_rows: quant_room
+    need + need/2 + 64 (the automatic build need + 64), the gather's m + m/4 + 64; an automatic shadow is built by the first
+    1-4-query dot / cosine top-k on more than CAND_CAP finite rows."""
 
     def __init__(self, n, shadow):
         self.n, self.kind = n, shadow
