@@ -65,7 +65,9 @@ enum hdb_query_status {
     HDB_Q_UNDERFLOW = 1,  /* sampled threshold too high: fewer than k candidates passed */
     HDB_Q_OVERFLOW = 2,   /* candidate buffer overflowed (massive ties or skewed sample) */
     HDB_Q_NAN = 4,        /* the query vector contains a NaN (ValueError of ranking_algorithm.py:150-151) */
-    HDB_Q_BADROW = 8      /* hdb_rerank: a candidate id outside [row_base, row_base + n) other than a negative one: skipped, never read */
+    HDB_Q_BADROW = 8,     /* hdb_rerank: a candidate id outside [row_base, row_base + n) other than a negative one: skipped, never read;
+                             grouped calls: also a row whose group id is outside [0, n_groups): treated as masked, never used as an index */
+    HDB_Q_GROUPS_SHORT = 16 /* hdb_collapse_groups: fewer than k groups were found and the list was not exhaustive */
 };
 
 /* Library/ABI version (major*100+minor). */
@@ -438,6 +440,60 @@ int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metric1, int32_
                        hdb_index* second, const void* dev_Q2, int metric2, int32_t k,
                        int32_t nq, void* host_record, void* stream);
 
+/* Grouped top-k: the best row of each group, k distinct groups per query ("group by" / "collapse": the rows are chunks, a group is
+ * the document they were cut from -- source_indices of the reference's data model).
+ * Semantics.  Order the eligible rows of a query -- not masked; bias added; NaN -> -inf -- by (score descending, row ascending), the
+ * order of hdb_topk.  A group's representative is its first row in that order; the grouped top-k is the first k representatives, in
+ * that order: no group twice, and with fewer than k groups among the eligible rows the tail is -1 / -inf.  A group whose rows are all
+ * excluded (or all at -inf) is not returned.  Walking the ungrouped ranking from the top and keeping each group's first occurrence
+ * gives exactly this answer as soon as k groups have been seen.
+ *
+ * hdb_index_set_groups: dev_groups = n int32 ids in [0, n_groups), one per row, device memory, borrowed like bias and mask until
+ * replaced or cleared (NULL clears; 1 <= n_groups <= 2^31 - 1).  hdb_index_extend, hdb_index_update and hdb_index_gather drop the
+ * ids with mask and bias; hdb_index_rebase keeps them.  The library does not trust them: every kernel compares an id against
+ * [0, n_groups) before it forms an address from it; a row whose id is outside counts as masked for that call and sets HDB_Q_BADROW
+ * in the status words of the call.
+ *
+ * hdb_topk_grouped_host: the grouped top-k of nq queries as the packed record of hdb_topk_host (hdb_packed_bytes(nq, k)) in host
+ * memory; indices are the representatives' rows (row_base added), scores theirs; the call synchronises `stream`.
+ * 1 <= k <= HDB_MAX_K (0 or less: HDB_ERR_ARG; more: HDB_ERR_UNSUPPORTED); no groups set: HDB_ERR_ARG.  The sizes are judged before
+ * the handle, the handle before any HIP call.  Served: every dtype (HDB_B1 included) with dot, cosine, euclidean, manhattan and
+ * pearson; hamming and jaccard return HDB_ERR_UNSUPPORTED.  Status words on return: 0, HDB_Q_NAN, HDB_Q_BADROW -- never
+ * HDB_Q_GROUPS_SHORT, HDB_Q_UNDERFLOW or HDB_Q_OVERFLOW.
+ * How it runs (local-hyperdb_amd/csrc/hdb_group_plan.h, hdb_group.hip).  Fast rounds: hdb_topk of k1 = min(n, HDB_MAX_K,
+ * k * group_oversample) into a device record -- on whatever path that call takes: single launch, shadow, matrix cores, row list --,
+ * one collapse launch, and the nq status words read back (one small copy, one synchronisation).  The queries flagged
+ * HDB_Q_GROUPS_SHORT run a second round at k2 = min(n, HDB_MAX_K, 4 * k1) where k2 > k1, one by one.  A query whose sampled call failed
+ * (HDB_Q_UNDERFLOW / HDB_Q_OVERFLOW) or that is still short after the last round goes to the exact grouped pass: the exact shape of
+ * the multi-kernel pipeline -- all scores of a chunk of queries in the workspace -- with two launches before the radix selection:
+ * best[q][g] = max over the group's rows of the packed (score, row) key (64-bit atomicMax, adjacent rows of one group combined in
+ * the wave first), then every row that is not its group's best is set to -inf, the state a masked row is in.  best is
+ * cq x n_groups x 8 bytes of the call's workspace and counts against exact_bytes when the chunk size cq is chosen.
+ * Scores: a fast round returns the float32 bits hdb_topk returns for the row; the exact pass those of hdb_topk_exact.  Where the
+ * two differ (a default float16 index rounds float32 queries for the matrix cores) the representative of a group may differ between
+ * the two within the dtype's tolerance, as it may between hdb_topk and hdb_topk_exact.
+ * Options: group_oversample (1 .. 64, default 4), group_fast_rounds (0 .. 2, default 2; 0 = always the exact pass).
+ * Stats: grouped (1 after a grouped call; hdb_topk and hdb_rerank set it to 0), group_k (rows per query of the last fast round
+ * run, 0 = none), group_rounds (fast rounds run), group_exact (queries answered by the exact pass); the other stats are those of
+ * the last inner call.
+ *
+ * hdb_collapse_groups: the primitive on its own.  dev_idx / dev_score: any ranked list [nq][m], 1 <= k <= m <= HDB_MAX_K (anything else:
+ * HDB_ERR_ARG), ids as hdb_topk, hdb_rerank and hdb_two_stage_host return them (row_base added), so grouping composes with those
+ * calls; dev_groups / n_groups / n / row_base describe the rows as for hdb_index_set_groups.  Output [nq][k]: each group's first
+ * occurrence in list order, then -1 / -inf.  A negative id, or an entry at -inf, is padding.  An id outside [row_base, row_base + n)
+ * is skipped and sets HDB_Q_BADROW -- nothing is read for it --, and so does an id whose group id is outside [0, n_groups).
+ * dev_status (nq words, may be NULL) is read and written: HDB_Q_NAN is carried over from the call that ranked the list, every
+ * other bit is replaced by HDB_Q_BADROW and HDB_Q_GROUPS_SHORT: fewer than k groups were found and the list was not exhaustive.  A
+ * list is exhaustive when it holds padding or when m >= n.  The outputs must not overlap the inputs.
+ * Not built: hamming / jaccard grouped calls, k > HDB_MAX_K, several GPUs (a group can span shards: a second collapse after the
+ * merge), more than one hit per group, per-group hit counts, a grouped stage inside hdb_two_stage_host (compose it with
+ * hdb_collapse_groups), threshold estimation that knows about groups. */
+int hdb_index_set_groups(hdb_index* ix, const int32_t* dev_groups, int64_t n_groups);
+int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, void* host_record, void* stream);
+int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, const int32_t* dev_groups,
+                        int64_t n_groups, int64_t n, int64_t row_base, int64_t* dev_idx_out, float* dev_score_out, int32_t* dev_status,
+                        int device, void* stream);
+
 /* Merge `parts` per-shard top-k lists (the all-gathered [parts][nq][k] buffers of the row-sharded
  * index) into the global top-k per query, same ordering rule.  Every part list must be ordered as hdb_topk writes
  * it: score descending, row ascending, unused slots (index -1) at the end. */
@@ -529,13 +585,16 @@ void hdb_group_destroy(hdb_group* g);
  *   statistic: no call is answered differently for it), plane_wg_per_cu (workgroups per CU of the pass over the plane: 0 the
  *   measured table, 1 .. 8 that many -- for A/B runs, no call is answered differently for it).
  *   rerank_chunk (hdb_rerank: queries per chunk, 0 = automatic, up to 256; at most 256).
+ *   group_oversample (hdb_topk_grouped_host: rows per wanted group in the first fast round, 1 .. 64, default 4), group_fast_rounds
+ *   (0 .. 2, default 2; 0: every query through the exact grouped pass).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
  *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
  *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows, plane_blocks (workgroups of the last call's
  *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second
- *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0). */
+ *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0), grouped, group_k,
+ *   group_rounds, group_exact (hdb_topk_grouped_host, above). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

@@ -18,6 +18,7 @@
 #include "hdb_quant.h"
 #include "hdb_ws.h"
 #include "hdb_plan.h"
+#include "hdb_group_plan.h"
 #include "hdb_devbuf.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
@@ -71,6 +72,9 @@ struct hdb_index {
     // ... and, beside the mask, the ascending list of the rows it keeps (hdb_index_set_row_subset): subset_m > 0 only with both set
     const int64_t* rows = nullptr;
     int64_t subset_m = 0;
+    // ... and a group id per row (hdb_index_set_groups): n ids in [0, n_groups), checked by every kernel that reads one
+    const int32_t* groups = nullptr;
+    int64_t n_groups = 0;
     // mask folded into a bias vector for the MFMA scan (owned, rebuilt per call: the mask and bias are borrowed)
     DevBuf<float> mbias;
     // control block of the single-launch pipeline (owned): counters + exchange granules, zero between calls
@@ -134,7 +138,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 109; }
+extern "C" int hdb_version(void) { return 110; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 // The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
@@ -158,6 +162,7 @@ static void matrix_changed(hdb_index* ix, int64_t kept_rows, hipStream_t st) {
     ix->pscale_valid = false; ix->pscale_done = std::min(ix->pscale_done, kept_rows);
     ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old matrix no longer apply
     ix->rows = nullptr; ix->subset_m = 0;
+    ix->groups = nullptr; ix->n_groups = 0;
     ix->build_stream = st;
 }
 // New blocks for the per-row caches.  The two change together: they are built beside the index and swapped in (caches_commit) after
@@ -504,6 +509,13 @@ extern "C" int hdb_index_set_row_subset(hdb_index* ix, const uint8_t* dev_mask, 
     return HDB_OK;
 }
 
+extern "C" int hdb_index_set_groups(hdb_index* ix, const int32_t* dev_groups, int64_t n_groups) {
+    if (!ix) return fail(HDB_ERR_ARG, "hdb_index_set_groups: null index");
+    if (dev_groups && (n_groups < 1 || n_groups > 0x7FFFFFFFll)) return fail(HDB_ERR_ARG, "hdb_index_set_groups: n_groups must be in [1, 2^31 - 1]");
+    ix->groups = dev_groups; ix->n_groups = dev_groups ? n_groups : 0;
+    return HDB_OK;
+}
+
 extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(HDB_ERR_ARG, "hdb_set_option: null argument");
     if (!strcmp(name, "max_blocks")) ix->opt.max_blocks = value;
@@ -556,6 +568,8 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "subset_min_n")) ix->opt.subset_min_n = value < 0 ? -1 : value;
     else if (!strcmp(name, "subset_ratio")) ix->opt.subset_ratio = value < 0 ? -1 : std::max<int64_t>(1, value);
     else if (!strcmp(name, "rerank_chunk")) ix->opt.rerank_chunk = std::max<int64_t>(0, std::min<int64_t>(value, HDB_RERANK_MAXQ));
+    else if (!strcmp(name, "group_oversample")) ix->opt.group_oversample = std::max<int64_t>(1, std::min<int64_t>(value, HDB_GROUP_OVERSAMPLE_MAX));
+    else if (!strcmp(name, "group_fast_rounds")) ix->opt.group_fast_rounds = std::max<int64_t>(0, std::min<int64_t>(value, HDB_GROUP_ROUNDS_MAX));
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -585,6 +599,10 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "subset")) *value = ix->st.subset;
     else if (!strcmp(name, "subset_rows")) *value = ix->subset_m;
     else if (!strcmp(name, "rerank")) *value = ix->st.rerank;
+    else if (!strcmp(name, "grouped")) *value = ix->st.grouped;
+    else if (!strcmp(name, "group_k")) *value = ix->st.group_k;
+    else if (!strcmp(name, "group_rounds")) *value = ix->st.group_rounds;
+    else if (!strcmp(name, "group_exact")) *value = ix->st.group_exact;
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
@@ -1013,7 +1031,7 @@ static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkE
     e.sort_temp = 0;
     if (p.sort_n > 0) LAUNCH_TRY(hdb_sort_temp_bytes(p.sort_n, &e.sort_temp));
     TopkWs& w = e.w;
-    int rc = ws_lay(ix, w, (int)c.nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, p.sort_n, e.sort_temp);
+    int rc = ws_lay(ix, w, (int)c.nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, p.sort_n, e.sort_temp, p.n_best);
     if (rc) return rc;
     if (p.prep)
         LAUNCH_TRY(hdb_launch_qprep2(c.Q, c.nq, ix->d, f64, w.qinv, w.qsq, w.qnan, p.q16_in_prep ? w.q16 : nullptr, w.qscl, p.fold_small ? w.thr : nullptr,
@@ -1215,6 +1233,13 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
             prof_begin(ix, st);
             rc = run_scan(ix, s, 0, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
             prof_end(ix, st);
+            if (p.n_best > 0) {
+                // the exact grouped pass: each group's best row keeps its score, every other row joins the masked ones at -inf
+                HIP_TRY(hipMemsetAsync(w.best, 0, (size_t)cq * (size_t)p.n_best * sizeof(unsigned long long), st));      // key 0 is below every real key
+                if (q0 == 0) HIP_TRY(hipMemsetAsync(w.gbad, 0, sizeof(int), st));
+                LAUNCH_TRY(hdb_launch_group_best(sbuf, n, ld_n, cq, ix->groups, p.n_best, w.best, st));
+                LAUNCH_TRY(hdb_launch_group_demote(sbuf, n, ld_n, cq, ix->groups, p.n_best, w.best, w.gbad, st));
+            }
             // cnt and hist are neighbours in the workspace: one memset clears both
             HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)((char*)hist - (char*)cnt) + (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
             for (int ps = 0; ps < npass; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, n, ld_n, cq, hist, ps, kk, st));
@@ -1227,6 +1252,8 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
                                        dev_idx + (int64_t)q0 * k, dev_score + (int64_t)q0 * k,
                                        dev_status ? dev_status + q0 : nullptr, qnan + q0, (int)ix->opt.finalize_threads,
                                        a.f32_split ? HDB_Q_UNDERFLOW : 0, st));      // (parts of an infinite query element cancel to NaN: exact re-run)
+        if (p.n_best > 0)       // (entries the selection handed out at -inf are padding; a bad group id marks the chunk's queries)
+            LAUNCH_TRY(hdb_launch_group_finish(dev_idx + (int64_t)q0 * k, dev_score + (int64_t)q0 * k, cq, k, dev_status ? dev_status + q0 : nullptr, w.gbad, st));
     }
     return HDB_OK;
 }
@@ -1531,6 +1558,115 @@ extern "C" int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metr
     }
     if (rerun) first->st = first_stats;
     return hdb_rerank_host(second, dev_Q2, nq, d_idx, k1, k, metric2, host_record, stream);
+}
+
+// ---- grouped top-k: one row per group (hdb_group.hip, hdb_group_plan.h) -----------------------------------------------------------
+// The exact grouped pass over nq queries: the exact shape of run_pipeline with the per-group maxima in its workspace.
+static int grouped_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx, float* dev_score,
+                         int32_t* dev_status, hipStream_t st) {
+    const TopkArgs c{dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, st};
+    int frc = HDB_OK;
+    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
+    const TopkPlan p = plan_topk(topk_facts(ix), ix->opt, group_exact_call(nq, k, metric, ix->n_groups), finite);
+    if (frc != HDB_OK) return frc;
+    if (!group_exact_shape(p)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: this call has no exact grouped pass");
+    ix->st = p.stats;
+    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    return run_pipeline(ix, c, p);
+}
+
+extern "C" int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, void* host_record, void* stream) {
+    // what the numbers alone decide, then the handle, then the device
+    if (nq <= 0) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: nq must be positive");
+    if (k < 1) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: k must be at least 1");
+    if (k > HDB_MAX_K) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: k beyond HDB_MAX_K (2048) is not built");
+    if (!ix || !dev_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: null argument");
+    if (!ix->groups) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: no groups set (hdb_index_set_groups)");
+    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: hamming / jaccard grouped calls are not built");
+    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
+        return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: metric not built");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
+    int rc = ensure_record(ix->rec, bytes);
+    if (rc) return rc;
+    const PackedRec out = packed_view(ix->rec, nq, k);
+    const size_t qbytes = (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4);
+    const GroupRounds gr = group_rounds(ix->n, k, ix->opt.group_oversample, ix->opt.group_fast_rounds);
+    int64_t st_k = 0, st_rounds = 0, st_exact = 0;
+    std::vector<int32_t> h_st((size_t)nq, 0);
+    std::vector<char> todo((size_t)nq, 1);             // queries the exact pass still has to answer
+    if (ix->n == 0) {
+        rc = run_empty(TopkArgs{dev_Q, nq, k, metric, out.idx, out.score, out.status, st});
+        if (rc) return rc;
+        std::fill(todo.begin(), todo.end(), 0);
+    }
+    const int32_t carry = HDB_Q_NAN | HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW;
+    for (int r = 0; r < gr.rounds && ix->n > 0; ++r) {
+        const int32_t kr = gr.kr[r];
+        // round 1: the whole batch in one call; round 2: the flagged queries, one by one, each into the head of the round's record
+        rc = ensure_record(ix->rec1, (size_t)hdb_packed_bytes(r == 0 ? nq : 1, kr));
+        if (rc) return rc;
+        bool ran = false;
+        if (r == 0) {
+            const PackedRec r1 = packed_view(ix->rec1, nq, kr);
+            rc = topk_impl(ix, dev_Q, nq, kr, metric, r1.idx, r1.score, r1.status, stream, false);
+            if (rc) return rc;
+            LAUNCH_TRY(hdb_launch_group_collapse(r1.idx, r1.score, nq, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx, out.score,
+                                                 r1.status, out.status, carry, st));
+            ran = true;
+        } else {
+            const PackedRec r2 = packed_view(ix->rec1, 1, kr);
+            for (int q = 0; q < nq; ++q) {
+                if (!todo[q] || (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW))) continue;      // (a failed sampled call: straight to the exact pass)
+                rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, kr, metric, r2.idx, r2.score, r2.status, stream, false);
+                if (rc) return rc;
+                LAUNCH_TRY(hdb_launch_group_collapse(r2.idx, r2.score, 1, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx + (size_t)q * k,
+                                                     out.score + (size_t)q * k, r2.status, out.status + q, carry, st));
+                ran = true;
+            }
+        }
+        if (!ran) break;
+        st_k = kr; ++st_rounds;
+        HIP_TRY(hipMemcpyAsync(h_st.data(), out.status, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        bool any = false;
+        for (int q = 0; q < nq; ++q) {
+            todo[q] = (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW | HDB_Q_GROUPS_SHORT)) != 0;
+            any |= todo[q] != 0;
+        }
+        if (!any) break;
+    }
+    // the exact grouped pass: runs of consecutive queries in one call each
+    for (int q = 0; q < nq;) {
+        if (!todo[q]) { ++q; continue; }
+        int e = q + 1;
+        while (e < nq && todo[e]) ++e;
+        rc = grouped_exact(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, e - q, k, metric, out.idx + (size_t)q * k, out.score + (size_t)q * k,
+                           out.status + q, st);
+        if (rc) return rc;
+        st_exact += e - q;
+        q = e;
+    }
+    ix->st.grouped = 1; ix->st.group_k = st_k; ix->st.group_rounds = st_rounds; ix->st.group_exact = st_exact;
+    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HDB_OK;
+}
+
+extern "C" int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, const int32_t* dev_groups,
+                                   int64_t n_groups, int64_t n, int64_t row_base, int64_t* dev_idx_out, float* dev_score_out, int32_t* dev_status,
+                                   int device, void* stream) {
+    if (m < 1 || m > HDB_MAX_K) return fail(HDB_ERR_ARG, "hdb_collapse_groups: m (entries per query) must be in [1, 2048]");
+    if (k < 1 || k > m) return fail(HDB_ERR_ARG, "hdb_collapse_groups: k must be in [1, m]");
+    if (nq < 0) return fail(HDB_ERR_ARG, "hdb_collapse_groups: nq must be >= 0");
+    if (n_groups < 1 || n_groups > 0x7FFFFFFFll || n < 0 || row_base < 0) return fail(HDB_ERR_ARG, "hdb_collapse_groups: need n_groups in [1, 2^31 - 1], n >= 0 and row_base >= 0");
+    if (nq == 0) return HDB_OK;
+    if (!dev_idx || !dev_score || !dev_groups || !dev_idx_out || !dev_score_out) return fail(HDB_ERR_ARG, "hdb_collapse_groups: null argument");
+    HIP_TRY(hipSetDevice(device));
+    LAUNCH_TRY(hdb_launch_group_collapse(dev_idx, dev_score, nq, m, k, dev_groups, n_groups, n, row_base, dev_idx_out, dev_score_out, dev_status,
+                                         dev_status, HDB_Q_NAN, stream));
+    return HDB_OK;
 }
 
 extern "C" int hdb_merge_topk(const int64_t* dev_idx_parts, const float* dev_score_parts, int32_t parts, int32_t nq,

@@ -170,6 +170,20 @@ int hdb_launch_rerank_prep(const int64_t* cand, int m, int nq, int64_t n, int64_
                            int64_t* rows, uint32_t* cnt, int32_t* status, void* stream);
 int hdb_launch_rerank_score(const ScanArgs* args, int dtype, int nq_launch, void* stream);
 
+// ---- hdb_group.hip: grouped top-k (one row per group) ----
+// collapse: a ranked list [nq][m <= 2048] -> the first k first occurrences of a group per query; status_in / status_out may be the
+// same array, `carry` = the bits of status_in that survive.  best / demote: the two launches of the exact grouped pass over the
+// score buffer [nq][ld] (best: [nq][n_groups], zero on entry; *bad is raised by an id outside [0, n_groups)).  finish: behind the
+// finalize of that pass, nq <= 256.
+int hdb_launch_group_collapse(const int64_t* idx, const float* score, int nq, int m, int k, const int32_t* groups, int64_t n_groups,
+                              int64_t n, int64_t row_base, int64_t* idx_out, float* score_out, const int32_t* status_in,
+                              int32_t* status_out, int carry, void* stream);
+int hdb_launch_group_best(const float* scores, int64_t n, int64_t ld, int nq, const int32_t* groups, int64_t n_groups,
+                          unsigned long long* best, void* stream);
+int hdb_launch_group_demote(float* scores, int64_t n, int64_t ld, int nq, const int32_t* groups, int64_t n_groups,
+                            const unsigned long long* best, int* bad, void* stream);
+int hdb_launch_group_finish(int64_t* idx, const float* score, int nq, int k, int32_t* status, const int* bad, void* stream);
+
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);

@@ -63,6 +63,8 @@ struct hdb_options {
     int64_t subset_min_n = -1;        // ... on matrices of at least this many rows (-1: the measured rule, HDB_SUBSET_MIN_ROWS)
     int64_t subset_ratio = -1;        // ... while m * ceil(nq / 4) * subset_ratio <= n (-1: the measured rule, HDB_SUBSET_RATIO; else an integer >= 1)
     int64_t rerank_chunk = 0;         // hdb_rerank: queries per chunk (0: up to HDB_RERANK_MAXQ); the plan of hdb_topk does not read it
+    int64_t group_oversample = 4;     // hdb_topk_grouped_host: the first fast round collapses the top k * group_oversample (1 .. 64; rank_two_stage's default, not measured)
+    int64_t group_fast_rounds = 2;    // ... fast rounds at most (0 .. 2); 0: always the exact grouped pass.  The plan of hdb_topk reads neither (hdb_group_plan.h)
 };
 #define HDB_RERANK_MAXQ 256
 
@@ -77,7 +79,8 @@ struct TopkFacts {
     int cus;                          // compute units of the device
     int64_t subset_m;                 // rows of the list set beside the mask (hdb_index_set_row_subset), 0 = none
 };
-struct TopkCall { int32_t nq, k; int metric; bool has_status, exact; };
+// n_groups > 0: the exact grouped pass of hdb_topk_grouped_host (exact is set as well); 0 for every other call
+struct TopkCall { int32_t nq, k; int metric; bool has_status, exact; int64_t n_groups; };
 
 // ---- what it answers ------------------------------------------------------------------------------------------------------------
 enum TopkPath {
@@ -91,7 +94,8 @@ enum TopkPath {
     HDB_PATH_PIPELINE                 // the multi-kernel pipeline: small, sampled or exact
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
-struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0; };
+struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0;
+                   int64_t grouped = 0, group_k = 0, group_rounds = 0, group_exact = 0; };      // hdb_topk_grouped_host writes these four behind its last inner call
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
@@ -106,6 +110,7 @@ struct TopkPlan {
     int64_t s_tiles = 0, s_stride = 1, s_rows = 0, ld_s = 0, ld_n = 0; uint32_t m = 0;      // the row sample
     int cq_max = 1;
     int64_t ld_scores = 0, ld_ks = 0, sort_n = 0;      // extents of TopkWs beside (nq, d, W, cq_max)
+    int64_t n_best = 0;                                 // ... and its per-group maxima: the exact grouped pass (TopkCall::n_groups), 0 otherwise
     uint32_t local_slot = 0, local_m = 0;               // single launch, local flavour
     int bits_local = 0;                                 // bits single launch: the local flavour is allowed
     int npass = 4;                                      // radix passes of the exact selection
@@ -305,7 +310,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // A list call is the same call on a matrix of the m listed rows with the matrix cores and the single launches off: the plan of
     // those facts, taken while it is the multi-kernel pipeline (k > HDB_MAX_K on more than HDB_CAND_CAP listed rows keeps the mask).
     // Its extents, sample plan and statistics are the inner plan's; the executor reads the rows through the list.
-    if (subset_rule(ix, o, c)) {
+    // (the exact grouped pass indexes its score buffer by row: it keeps the mask)
+    if (c.n_groups <= 0 && subset_rule(ix, o, c)) {
         TopkFacts in{};
         in.n = ix.subset_m; in.d = ix.d; in.dtype = ix.dtype; in.qmode = HDB_QUANT_NONE; in.has_bias = ix.has_bias; in.cus = ix.cus;
         hdb_options oin = o;
@@ -324,7 +330,10 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     if (n == 0) return p;            // nothing stored: all -1 / -inf
     const bool full_sort = k > HDB_MAX_K && n > HDB_CAND_CAP;
     const bool f64 = ix.dtype == HDB_F64;
-    const bool small = n <= HDB_CAND_CAP;
+    // The exact grouped pass needs every score in a buffer, so a matrix of up to HDB_CAND_CAP rows takes the exact shape too -- on
+    // the VALU scan, which is what such a matrix runs on in every other call (`tiny`).  small == tiny wherever n_groups is 0.
+    const bool tiny = n <= HDB_CAND_CAP;
+    const bool small = tiny && c.n_groups <= 0;
     // bit metrics tie massively by construction; the sampled threshold still works while the rows at and above its
     // level fit the candidate list (random data: yes), and the status word sends the rest through the exact path
     const bool exact_req = c.exact;                          // the caller asked for the exact selection (tests; the re-run of a failed call)
@@ -378,7 +387,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     //  K slices of wider ones, hdb_mfma_b1.h.  The matrix is always finite -- its flag word is never written -- so nothing is asked.)
     const int64_t b1_first = b1_mfma_first_q(o, ix.dtype, ix.d);
     const bool b1_call = b1_first > 0 && nq >= b1_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
-    bool mfma = o.use_mfma && !is_ham && !small && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
+    bool mfma = o.use_mfma && !is_ham && !small && !tiny && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
     // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
@@ -458,10 +467,12 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int64_t ld_s = align_up((size_t)std::max<int64_t>(s_rows, 4), 4);
     const int64_t ld_n = align_up((size_t)n, 4);
     int cq_max = batch1 ? bcap : 256;
-    if (exact && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(256, o.exact_bytes / (ld_n * 4)));
+    // (the per-group maxima of the exact grouped pass, 8 bytes per query and group, count against exact_bytes beside the scores)
+    const int64_t n_best = c.n_groups > 0 ? c.n_groups : 0;
+    if (exact && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(256, o.exact_bytes / (ld_n * 4 + n_best * 8)));
     // wide rows on the matrix cores go through K slices with a [query][rows] buffer of partial sums (hdb_mfma_ksplit.hip)
     const bool ksplit = mfma && (hdb_mfma_ksplit_slices(ix.dtype, ix.d) > 0 || f8ks || b1ks);
-    if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), o.exact_bytes / (ld_n * 4)));
+    if (ksplit && !small) cq_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(cq_max, 128), o.exact_bytes / (ld_n * 4 + n_best * 8)));
     cq_max = std::min(cq_max, (int)nq);
     const bool fused = fused_shape && !full_sort && (m == 8 || local_ok);           // (no prep kernel either)
     // hamming / jaccard: the single launch for every call (with the two-level hand-out of the pass: one query 120-124 vs 125-132 us
@@ -480,7 +491,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     p.stats.f8_lds = p.f8_lds ? 1 : 0;
     p.exact = exact; p.exact_req = exact_req; p.small = small; p.mfma = mfma; p.f32s = f32s; p.ksplit = ksplit; p.local = local_ok;
     p.tile_rows = tile_rows; p.s_tiles = s_tiles; p.s_stride = s_stride; p.m = m; p.s_rows = s_rows; p.ld_s = ld_s; p.ld_n = ld_n;
-    p.cq_max = cq_max;
+    p.cq_max = cq_max; p.n_best = n_best;
     // full sort (k > HDB_MAX_K): all scores of one query, the sort's work array and its scratch live in the same layout
     p.ld_scores = exact && !small ? ld_n : ld_s; p.ld_ks = ksplit ? ld_n : 0; p.sort_n = full_sort ? n : 0;
     p.path = fused ? HDB_PATH_FUSED : bits1 ? HDB_PATH_BITS1 : batch1 ? HDB_PATH_BATCH1 : full_sort ? HDB_PATH_FULL_SORT : HDB_PATH_PIPELINE;
@@ -494,7 +505,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     p.fold_small = small && p.path == HDB_PATH_PIPELINE && nq <= cq_max;
     // the MFMA scan has no mask input: excluded rows get a bias of -inf instead (never appended, like the VALU scan)
     // (run_scan hands manhattan calls of two or more queries to the tile kernel; a single query keeps the VALU scan and its mask input)
-    p.l1tile = metric == HDB_MANHATTAN && o.use_l1_tile && !small && nq >= 2 && hdb_l1_tile_supported(ix.dtype, ix.d);
+    p.l1tile = metric == HDB_MANHATTAN && o.use_l1_tile && !small && !tiny && nq >= 2 && hdb_l1_tile_supported(ix.dtype, ix.d);
     p.mask_fold = (mfma || fused || p.l1tile) && ix.has_mask && !full_sort;
     p.stats.f32s = f32s ? 1 : 0; p.stats.sample_rows = s_rows; p.stats.sample_m = m; p.stats.path = 1;
     switch (p.path) {

@@ -45,12 +45,15 @@ struct ScoresWs {
 // The main pipeline (topk_impl): per-query words of the whole call, then the buffers of one chunk of cq queries.
 // ld_scores: leading dimension of the score buffer (the sample's, or all rows on the exact path); ld_ks: of the partial sums of
 // the K slices (0: none); sort_n > 0: the three buffers of the full sort (k > HDB_MAX_K), sort_temp bytes of radix-sort scratch.
+// n_best > 0 (the exact grouped pass, hdb_topk_grouped_host): the per-group maxima of a chunk, [cq][n_best] 64-bit keys, and the
+// word its demote launch raises on a bad group id; every other call passes 0 and gets neither.
 struct TopkWs {
     float* qinv; float* qsq; int* qnan; float* qscl; uint32_t* qbits; void* q16; void* qc;
     float* thr; uint32_t* cnt; uint32_t* tile_ctr; uint32_t* hist; uint32_t* tie_info; unsigned long long* cand;
     float* sbuf; float* kbuf;
     float* sc1; uint32_t* work; void* temp;
-    void lay(Bump& b, int nq, int d, int W, int cq, int64_t ld_scores, int64_t ld_ks, int64_t sort_n, size_t sort_temp) {
+    unsigned long long* best; int* gbad;
+    void lay(Bump& b, int nq, int d, int W, int cq, int64_t ld_scores, int64_t ld_ks, int64_t sort_n, size_t sort_temp, int64_t n_best = 0) {
         qinv = b.take<float>(nq); qsq = b.take<float>(nq); qnan = b.take<int>(nq); qscl = b.take<float>(nq);
         qbits = b.take<uint32_t>((size_t)nq * W);
         q16 = b.take<uint16_t>((size_t)nq * d);                         // fp16 queries (MFMA)
@@ -68,6 +71,11 @@ struct TopkWs {
             sc1 = b.take<float>(align_up((size_t)sort_n, 4));
             work = b.take<uint32_t>((size_t)sort_n * 4);
             temp = b.take<char>(sort_temp);
+        }
+        best = nullptr; gbad = nullptr;
+        if (n_best > 0) {
+            best = b.take<unsigned long long>((size_t)cq * (size_t)n_best);
+            gbad = b.take<int>(1);
         }
     }
 };

@@ -32,6 +32,7 @@ METRIC_IDS = {
 EUCLIDEAN_DIST = 7
 Q_UNDERFLOW, Q_OVERFLOW, Q_NAN = 1, 2, 4
 Q_BADROW = 8                            # hdb_rerank: a candidate id outside the index (skipped, never read)
+Q_GROUPS_SHORT = 16                     # hdb_collapse_groups: fewer than k groups in a list that was not exhaustive
 CAND_CAP = 8192                         # longest candidate list of a rerank call (HDB_CAND_CAP)
 HDB_QUANT_NONE, HDB_QUANT_I8 = 0, 1
 QUANT_MODES = {None: HDB_QUANT_NONE, "int8": HDB_QUANT_I8}
@@ -49,6 +50,7 @@ EXPORTS = (
     "hdb_packed_bytes", "hdb_merge_topk_packed", "hdb_merge_topk_host", "hdb_host_exchange_merge", "hdb_topk_host",
     "hdb_index_quantize", "hdb_debug_quant_bounds", "hdb_index_set_row_subset",
     "hdb_rerank", "hdb_rerank_host", "hdb_two_stage_host",
+    "hdb_index_set_groups", "hdb_topk_grouped_host", "hdb_collapse_groups",
 )
 
 
@@ -97,6 +99,9 @@ def _load():
     lib.hdb_rerank.argtypes = [vp, vp, i32, vp, i32, i32, ctypes.c_int, vp, vp, vp, vp]
     lib.hdb_rerank_host.argtypes = [vp, vp, i32, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_two_stage_host.argtypes = [vp, vp, ctypes.c_int, i32, vp, vp, ctypes.c_int, i32, i32, vp, vp]
+    lib.hdb_index_set_groups.argtypes = [vp, vp, i64]
+    lib.hdb_topk_grouped_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp]
+    lib.hdb_collapse_groups.argtypes = [vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_packed.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_host.argtypes = [vp, i32, i32, i32, vp]
     lib.hdb_host_exchange_merge.argtypes = [vp, i64, i32, i32, ctypes.c_uint64, vp, i32, i32, vp, ctypes.c_double]
@@ -359,6 +364,9 @@ class GpuIndex:
         self._mask = None
         self._rows = None                      # the row list set beside the mask (set_row_subset)
         self._rows_ok = OrderedDict()          # id(device list) -> the list: validated once, kept alive so the id stays its own
+        self._groups = None                    # the group id per row (set_groups), int32 on the device
+        self.n_groups = 0
+        self._groups_ok = OrderedDict()        # id(device ids) -> (the ids, their maximum + 1): validated once, as _rows_ok
         self._nan = None
         self._buf = None
         self.quant = HDB_QUANT_NONE             # int8 shadow (quantize)
@@ -593,9 +601,12 @@ class GpuIndex:
         return out
 
     def _forget_rows(self):
-        """The matrix changed: the library dropped the list with mask and bias, and no validated list describes the new rows."""
+        """The matrix changed: the library dropped the list and the group ids with mask and bias, and nothing validated describes
+        the new rows."""
         self._rows = None
         self._rows_ok.clear()
+        self._groups, self.n_groups = None, 0
+        self._groups_ok.clear()
 
     def _mask_tensor(self, mask):
         if isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8 and mask.device == self.device and mask.is_contiguous():
@@ -660,6 +671,43 @@ class GpuIndex:
         self._mask, self._rows = m, r
         _check(_lib.hdb_index_set_row_subset(self._h, ctypes.c_void_p(m.data_ptr()), ctypes.c_void_p(r.data_ptr()), int(r.numel())),
                "hdb_index_set_row_subset")
+
+    # -- groups: one id per row, one hit per group ----------------------------------------------
+    def set_groups(self, groups, n_groups=None):
+        """A group id per row (hdb_index_set_groups) for topk_grouped: numpy or torch, any integer dtype, one entry per row, every
+        id in ``[0, n_groups)``; ``n_groups`` defaults to the largest id + 1.  Checked here on the host, once per array and before
+        anything is launched: a wrong length, a negative id or an id >= n_groups raises ValueError naming the value.  ``None``
+        clears.  append / update / compact drop the ids with mask and bias."""
+        if groups is None:
+            if self._groups is not None:
+                self._groups, self.n_groups = None, 0
+                _check(_lib.hdb_index_set_groups(self._h, None, 0), "hdb_index_set_groups")
+            return
+        g, top = check_groups(groups, self.n, self._groups_ok, self.device)
+        ng = top if n_groups is None else int(n_groups)
+        if ng < top or ng < 1:
+            raise ValueError(f"set_groups: group id {top - 1} is not in [0, {ng}): n_groups is too small")
+        self._groups_ok[id(g)] = (g, top)
+        while len(self._groups_ok) > HOST_RECORD_SLOTS:
+            self._groups_ok.popitem(last=False)
+        self._groups, self.n_groups = g, ng
+        _check(_lib.hdb_index_set_groups(self._h, ctypes.c_void_p(g.data_ptr()), ng), "hdb_index_set_groups")
+
+    def topk_grouped(self, Q, k, metric_id):
+        """One row per group, k distinct groups per query (hdb_topk_grouped_host) -> numpy (int64 [nq,k], float32 [nq,k])
+        (copies): each group's best row by (score descending, row ascending), the first k of them; -1 / -inf where fewer than k
+        groups can be returned.  Needs set_groups (ValueError otherwise); hamming / jaccard and k > 2048: NotImplementedError."""
+        qt = self._query_tensor(Q, batched=True)
+        nq, k = int(qt.shape[0]), int(k)
+        if nq == 0 or k < 1:
+            raise ValueError("topk_grouped: need at least one query and k >= 1")
+        slot = self._record_slot(nq, k) if k <= HDB_MAX_K else (None, None)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_topk_grouped_host(self._h, ctypes.c_void_p(qt.data_ptr()), nq, k, int(metric_id), ctypes.c_void_p(slot[1]),
+                                              _stream_ptr(self.device)), "hdb_topk_grouped_host")
+        if (slot[4] & Q_NAN).any():
+            raise ValueError(NAN_MESSAGE)
+        return slot[2].copy(), slot[3].copy()
 
     # -- options / stats -----------------------------------------------------------------------
     def set_option(self, name, value):
@@ -934,6 +982,115 @@ def check_candidates(cand, nq, n, row_base):
         if bad.any():
             raise IndexError(f"{BADROW_MESSAGE}: {int(host[bad].reshape(-1)[0])} is not in [{lo}, {hi})")
     return m
+
+
+def check_groups(groups, n, seen=None, device=None):
+    """The group ids of a set_groups / collapse_groups call, checked on the host -> (int32 tensor, largest id + 1).
+
+    ``groups``: numpy or torch, any integer dtype, 1-D with ``n`` entries, no negative id (ValueError naming the length or the
+    offending value otherwise).  ``seen``: the cache of arrays that passed before (id -> (tensor, top)); ``device``: where the
+    int32 copy goes (None: it stays on the host)."""
+    if seen is not None and isinstance(groups, torch.Tensor) and id(groups) in seen:
+        seen.move_to_end(id(groups))
+        return seen[id(groups)]
+    if isinstance(groups, torch.Tensor):
+        if groups.dtype.is_floating_point or groups.dtype.is_complex or groups.dtype == torch.bool:
+            raise ValueError(f"group ids must be integers, got {groups.dtype}")
+        h = groups.detach().cpu().numpy()
+    else:
+        h = np.asarray(groups)
+        if h.dtype.kind not in "iu":
+            raise ValueError(f"group ids must be integers, got dtype {h.dtype}")
+    if h.ndim != 1 or h.size != int(n):
+        raise ValueError(f"group ids must be 1-D with one entry per row ({int(n)}), got shape {tuple(h.shape)}")
+    if h.size == 0:
+        raise ValueError("group ids of an empty index")
+    lo, hi = int(h.min()), int(h.max())
+    if lo < 0:
+        raise ValueError(f"group id {lo} is negative: ids must be in [0, n_groups)")
+    if hi >= 2 ** 31 - 1:
+        raise ValueError(f"group id {hi} does not fit: at most 2^31 - 1 groups")
+    if isinstance(groups, torch.Tensor) and groups.dtype == torch.int32 and groups.is_contiguous() and (device is None or groups.device == device):
+        g = groups
+    else:
+        g = torch.from_numpy(np.ascontiguousarray(h, dtype=np.int32))
+        if device is not None:
+            g = g.to(device)
+    return g, hi + 1
+
+
+def collapse_groups_host(idx, scores, groups, k, row_base=0):
+    """The model of hdb_collapse_groups in numpy: ranked lists ``idx`` / ``scores`` ``[nq, m]`` -> ``(idx [nq, k], scores [nq, k],
+    status [nq])``: each group's first occurrence in list order, then ``-1`` / ``-inf``.  A negative id or an entry at ``-inf`` is
+    padding; an id outside the rows of ``groups`` is skipped and sets Q_BADROW; Q_GROUPS_SHORT: fewer than k groups in a list
+    without padding that is shorter than the index."""
+    idx = np.asarray(idx, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float32)
+    groups = np.asarray(groups)
+    nq, m = idx.shape
+    n, k = int(groups.shape[0]), int(k)
+    out_i = np.full((nq, k), -1, np.int64)
+    out_s = np.full((nq, k), -np.inf, np.float32)
+    status = np.zeros(nq, np.int32)
+    for q in range(nq):
+        seen, found, pad = set(), 0, False
+        for j in range(m):
+            r = int(idx[q, j])
+            if r < 0 or scores[q, j] == -np.inf:
+                pad = True
+                continue
+            if r < row_base or r - row_base >= n:
+                status[q] |= Q_BADROW
+                continue
+            g = int(groups[r - row_base])
+            if g in seen:
+                continue
+            seen.add(g)
+            if found < k:
+                out_i[q, found], out_s[q, found] = r, scores[q, j]
+            found += 1
+        if found < k and not pad and m < n:
+            status[q] |= Q_GROUPS_SHORT
+    return out_i, out_s, status
+
+
+def collapse_groups(idx, scores, groups, k, n_groups=None, row_base=0):
+    """hdb_collapse_groups on the device: ranked lists ``idx`` (int64) / ``scores`` (float32) ``[nq, m]``, ``1 <= k <= m <= 2048``,
+    as CUDA tensors or host arrays, and one group id per row of the index they name (``row_base`` = the id of its row 0) ->
+    CUDA tensors ``(idx [nq, k], scores [nq, k], status int32 [nq])``.  The output of topk_device, rerank_device or a two-stage
+    call goes in as it is, so grouping composes with those.  Host ``groups`` are checked here (ValueError); a device tensor is
+    taken as it is, and the kernel compares every id against ``[0, n_groups)`` before it uses one (Q_BADROW otherwise)."""
+    require_gpu()
+    if isinstance(idx, torch.Tensor) and idx.is_cuda:
+        device = idx.device
+    elif isinstance(groups, torch.Tensor) and groups.is_cuda:
+        device = groups.device
+    else:
+        device = torch.device("cuda", torch.cuda.current_device())
+    it = torch.as_tensor(idx).to(device, torch.int64).contiguous()
+    st_ = torch.as_tensor(scores).to(device, torch.float32).contiguous()
+    if it.dim() != 2 or st_.shape != it.shape:
+        raise ValueError(f"collapse_groups: idx and scores must be 2-D [nq, m] of one shape, got {tuple(it.shape)} and {tuple(st_.shape)}")
+    nq, m, k = int(it.shape[0]), int(it.shape[1]), int(k)
+    if isinstance(groups, torch.Tensor) and groups.is_cuda:
+        if groups.dtype != torch.int32 or groups.dim() != 1 or not groups.is_contiguous() or groups.device != device:
+            raise ValueError("collapse_groups: device group ids must be a contiguous 1-D int32 tensor on the lists' device")
+        if n_groups is None:
+            raise ValueError("collapse_groups: device group ids need n_groups")
+        g, ng = groups, int(n_groups)
+    else:
+        g, top = check_groups(groups, len(groups), None, device)
+        ng = top if n_groups is None else int(n_groups)
+        if ng < top:
+            raise ValueError(f"collapse_groups: group id {top - 1} is not in [0, {ng}): n_groups is too small")
+    out_i = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=device)
+    out_s = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=device)
+    status = torch.zeros((nq,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(_lib.hdb_collapse_groups(ctypes.c_void_p(it.data_ptr()), ctypes.c_void_p(st_.data_ptr()), nq, m, k, ctypes.c_void_p(g.data_ptr()),
+                                        ng, int(g.numel()), int(row_base), ctypes.c_void_p(out_i.data_ptr()), ctypes.c_void_p(out_s.data_ptr()),
+                                        ctypes.c_void_p(status.data_ptr()), device.index or 0, _stream_ptr(device)), "hdb_collapse_groups")
+    return out_i, out_s, status
 
 
 def quant_mode(mode):

@@ -106,6 +106,7 @@ class HyperDB:
         self._mask_cache = OrderedDict()              # filter key -> (per-shard uint8 device masks | None, documents kept, bool array over documents | None, per-shard int64 device row lists | None)
         self._ts_dev = {}                             # timestamp_key -> per-shard float64 device columns over the device rows
         self._bias_cache = OrderedDict()              # (timestamp_key, filter key, recency_bias) -> per-shard float32 device bias
+        self._group_cache = OrderedDict()             # group_by -> (int32 device codes over the device rows, number of groups)
         self._str_tokens = None                       # per document: token sets of the strings inside it (sentence filter)
         self.host_row_passes = 0                      # O(N) host arrays built so far (cache misses only; tests watch it)
         self._cache = OrderedDict()
@@ -216,6 +217,7 @@ class HyperDB:
         self._mask_cache.clear()
         self._ts_dev.clear()
         self._bias_cache.clear()
+        self._group_cache.clear()
         self._str_tokens = None
         self.clear_cache()
 
@@ -329,12 +331,13 @@ class HyperDB:
                                'currsize': len(self._cache)}}
 
     @staticmethod
-    def _hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent):
+    def _hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by=None):
         if isinstance(query_input, np.ndarray):               # the array's bytes (1 us) instead of a tuple of its values (8 us at d=384)
             query_input = (query_input.tobytes(), query_input.dtype.str, query_input.shape)
         elif isinstance(query_input, list):
             query_input = tuple(np.asarray(query_input).ravel().tolist())
-        return (query_input, top_k, return_similarities, HyperDB._filter_key(filters), recency_bias, timestamp_key, metric, ann_percent)
+        key = (query_input, top_k, return_similarities, HyperDB._filter_key(filters), recency_bias, timestamp_key, metric, ann_percent)
+        return key if group_by is None else key + (("group_by", group_by),)
 
     @staticmethod
     def _filter_key(filters):
@@ -639,13 +642,63 @@ class HyperDB:
             self._bias_cache.popitem(last=False)
         return hit
 
-    def _execute(self, Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric):
+    def _group_codes(self, group_by):
+        """One int32 code per DEVICE row for ``group_by`` -> (codes, number of groups).  Host only.
+
+        ``"source"``: documents with the same ``source_indices`` entry share a group (the chunks of one source document).  A name in
+        ``metadata_keys``: documents with the same value under that key (dotted names walk nested dicts) share a group; a document
+        without the key -- or one that is no dict -- is a group of its own.  Tombstoned rows get code 0, a valid one: they are
+        masked in every call."""
+        n_docs = len(self.documents)
+        if group_by == "source":
+            if len(self.source_indices) != n_docs:
+                raise ValueError("group_by='source' needs one source_indices entry per document")
+            _, codes = np.unique(np.asarray(self.source_indices), return_inverse=True)
+            codes = codes.reshape(-1)
+        elif isinstance(group_by, str) and group_by in self.metadata_keys:
+            nested = group_by.split('.')
+            seen, codes = {}, np.empty(n_docs, dtype=np.int64)
+            for i, doc in enumerate(self.documents):
+                v = self.get_nested_value(doc, nested) if isinstance(doc, dict) else None
+                if v is None:
+                    codes[i] = len(seen)
+                    seen[("doc", i)] = codes[i]              # a group of its own
+                    continue
+                try:
+                    key = ("val", v)
+                    hash(key)
+                except TypeError:
+                    key = ("repr", repr(v))
+                codes[i] = seen.setdefault(key, len(seen))
+        else:
+            raise ValueError(f"group_by must be None, 'source' or one of metadata_keys {self.metadata_keys}, got {group_by!r}")
+        n_groups = int(codes.max()) + 1 if n_docs else 1
+        rows = np.zeros(self._index.n, dtype=np.int32)
+        rows[self._live_rows()] = codes
+        return rows, n_groups
+
+    def _groups_for(self, group_by):
+        """The device array of _group_codes, cached per key until the document list changes."""
+        hit = self._group_cache.get(group_by)
+        if hit is None:
+            self.host_row_passes += 1
+            rows, n_groups = self._group_codes(group_by)
+            hit = self._group_cache[group_by] = (torch.from_numpy(rows).to(self._index.device), n_groups)
+            while len(self._group_cache) > self._ROW_CACHE_SLOTS:
+                self._group_cache.popitem(last=False)
+        else:
+            self._group_cache.move_to_end(group_by)
+        return hit
+
+    def _execute(self, Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, group_by=None):
         if self._index is None or not self.documents:
             raise Exception("The database is empty. Cannot proceed with the query.")
         if metric not in _METRICS:
             raise ValueError(f"Invalid metric '{metric}'. Supported: " + ", ".join(f"'{m}'" for m in _METRICS))
         ranking._validate_metric(metric)
         ix = self._index
+        if group_by is not None and isinstance(ix, GpuGroup):
+            raise NotImplementedError("group_by on several devices is not built: a group can span shards")
         # (one query: a NaN anywhere makes q.q a NaN -- a dot product instead of an isnan pass and a reduction)
         if ix.has_nan or (math.isnan(float(np.dot(Q[0], Q[0]))) if len(Q) == 1 and Q.dtype.kind == "f" else bool(np.isnan(Q).any())):
             raise ValueError(ranking.NAN_MESSAGE)
@@ -663,11 +716,18 @@ class HyperDB:
                 if sh.n:
                     sh.set_row_subset(None if masks is None else masks[p], None if lists is None else lists[p])
                     sh.set_bias(None if bias is None else bias[p])
-            idx, sc = ix.topk(Q, int(top_k), METRIC_IDS[metric])
+            if group_by is None:
+                idx, sc = ix.topk(Q, int(top_k), METRIC_IDS[metric])
+            else:                                     # one hit per group: the best row of each, top_k groups (GpuIndex.topk_grouped)
+                codes, n_groups = self._groups_for(group_by)
+                ix.set_groups(codes, n_groups)
+                idx, sc = ix.topk_grouped(Q, int(top_k), METRIC_IDS[metric])
         finally:
             for sh, lo, hi in shards:
                 sh.set_row_mask(None)
                 sh.set_bias(None)
+                if group_by is not None:
+                    sh.set_groups(None)
         if n_avail == 1:
             print("Info: Only one document left.")                               # ranking_algorithm.py:189-191
         out = []
@@ -692,7 +752,20 @@ class HyperDB:
               metric='cosine_similarity', ann_percent=5):
         """Same signature and return shape as reference HyperDB.query (hyperdb.py:1584): a list of
         ``(document, score, source_index)`` tuples (or documents) for ONE query."""
-        key = self._hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent)
+        return self._query_one(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, None)
+
+    def query_grouped(self, query_input, group_by, top_k=5, return_similarities=True, filters=None, recency_bias=0, timestamp_key=None,
+                      metric='cosine_similarity', ann_percent=5):
+        """Additive: :meth:`query` with one hit per group.  ``group_by="source"`` groups the documents by their ``source_indices``
+        entry (the chunks of one source document), a name in ``metadata_keys`` by that metadata value (documents without it are
+        each their own group).  The best document of each group comes back, ``top_k`` groups at most (fewer when fewer exist), in
+        the ``(document, score, source_index)`` shape of :meth:`query`; results are cached like its own, ``group_by`` being part of
+        the key.  ``group_by=None`` is :meth:`query` exactly.  One device only (NotImplementedError with ``devices=[...]``).
+        (:meth:`query` itself keeps the reference's parameter list; :meth:`query_batch` takes ``group_by`` as its last keyword.)"""
+        return self._query_one(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)
+
+    def _query_one(self, query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by):
+        key = self._hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)
         if key in self._cache:
             self.cache_hits += 1
             self._cache.move_to_end(key)
@@ -704,7 +777,7 @@ class HyperDB:
             Q = self._query_vectors(query_input)
             if len(Q) != 1:
                 raise ValueError("query() takes one query; use query_batch() for a (Q, d) batch.")
-            result = self._execute(Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric)[0]
+            result = self._execute(Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, group_by)[0]
         except (ValueError, TypeError) as e:
             print(f"An exception occurred due to invalid input: {e}")
             raise
@@ -714,7 +787,8 @@ class HyperDB:
         return result
 
     def query_batch(self, query_inputs, top_k=5, return_similarities=True, filters=None, recency_bias=0, timestamp_key=None,
-                    metric='cosine_similarity'):
-        """Additive: one list of results per row of a (Q, d) batch, computed in a single pass over the matrix."""
+                    metric='cosine_similarity', group_by=None):
+        """Additive: one list of results per row of a (Q, d) batch, computed in a single pass over the matrix.  ``group_by``: as
+        in :meth:`query_grouped`."""
         Q = self._query_vectors(query_inputs)
-        return self._execute(Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric)
+        return self._execute(Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, group_by)

@@ -15,7 +15,8 @@ reference's return types (int64 indices, float64 scores, ValueError on NaN / unk
     matrix and its 1/||v|| cache stay in HBM between calls (what ``HyperDB`` uses).
 
 Additive surface (the reference has no batched call): :func:`rank_batch`; every query against its own list of rows:
-:func:`rerank_batch`; a cheap index in front of an exact one in one call: :func:`rank_two_stage`.
+:func:`rerank_batch`; a cheap index in front of an exact one in one call: :func:`rank_two_stage`; one hit per group of rows (a
+document's chunks): :func:`rank_grouped`.
 
 There is NO CPU fallback: without the HIP library importing this module fails, and without a GPU every
 call raises ``HyperDBNativeError`` instead of silently computing on the host.
@@ -35,7 +36,7 @@ __all__ = [
     "get_norm_vector", "dot_product", "cosine_similarity", "euclidean_metric", "manhattan_distance",
     "jaccard_similarity", "pearson_correlation", "check_and_binarize_vectors", "hamming_distance",
     "hyperDB_ranking_algorithm_sort", "rank_batch", "register_vectors", "ResidentVectors",
-    "rerank_batch", "rank_two_stage",
+    "rerank_batch", "rank_two_stage", "rank_grouped",
 ]
 
 _GPU_METRICS = tuple(METRIC_IDS)      # all seven metrics of the reference's dispatch table have kernels
@@ -412,3 +413,48 @@ def rank_two_stage(first, second, query_vectors, top_k=5, oversample=4, metric='
         return np.zeros((qh.shape[0], 0), np.int64), np.zeros((qh.shape[0], 0), np.float64)
     idx, sc = ix2.two_stage(ix1, q1, METRIC_IDS[fm], k1, qh, METRIC_IDS[metric], k)
     return idx.astype(np.int64), sc.astype(np.float64)
+
+
+def rank_grouped(vectors, query_vectors, groups, top_k=5, metric='cosine_similarity', timestamps=None, recency_bias=0):
+    """Additive: one hit per group -- the best row of each group, ``top_k`` distinct groups per query ("group by" / "collapse" of
+    a store whose rows are chunks of documents).
+
+    ``groups`` is one integer id per row (numpy or torch).  The rows of a query are ordered as :func:`rank_batch` orders them
+    (score descending, row ascending, recency applied); a group is represented by its first row in that order, and the first
+    ``k = min(top_k, n)`` representatives come back as ``(int64 (Q, k) rows, float64 (Q, k) scores, int64 (Q, k) group ids)``;
+    where fewer than k groups exist the tail is ``-1`` / ``-inf`` / ``-1``.  ``vectors`` is a registered handle on one device or a
+    raw matrix registered for the call; sharded and group handles raise NotImplementedError (a group can span shards), and so do
+    hamming and jaccard and ``top_k`` beyond 2048."""
+    if isinstance(vectors, ResidentVectors) and not isinstance(vectors.index, GpuIndex) or isinstance(vectors, GpuGroup):
+        raise NotImplementedError("rank_grouped: needs an index on one device; a group of rows can span the shards of a sharded handle")
+    ix, _, owned = _resolve(vectors)
+    try:
+        if not isinstance(ix, GpuIndex):
+            raise NotImplementedError("rank_grouped: needs an index on one device; a group of rows can span the shards of a sharded handle")
+        qh = _query_host(query_vectors)
+        if qh.ndim == 1:
+            qh = qh.reshape(1, -1)
+        if ix.has_nan or np.isnan(qh).any():
+            raise ValueError(NAN_MESSAGE)
+        _validate_metric(metric)
+        if ix.n == 0:
+            raise ValueError("vectors is empty")
+        k = max(0, min(int(top_k), ix.n))
+        if k == 0:
+            z = np.zeros((qh.shape[0], 0), np.int64)
+            return z, np.zeros((qh.shape[0], 0), np.float64), z.copy()
+        ix.set_groups(groups)
+        had_bias = _apply_recency(ix, timestamps, recency_bias)
+        try:
+            idx, sc = ix.topk_grouped(qh, k, METRIC_IDS[metric])
+            gh = ix._groups.cpu().numpy().astype(np.int64)
+        finally:
+            ix.set_groups(None)
+            if had_bias:
+                ix.set_bias(None)
+        idx = idx.astype(np.int64)
+        gid = np.where(idx >= 0, gh[np.clip(idx - ix.row_base, 0, ix.n - 1)], -1)
+        return idx, sc.astype(np.float64), gid
+    finally:
+        if owned:
+            ix.close()
