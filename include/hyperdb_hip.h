@@ -178,8 +178,12 @@ void hdb_index_destroy(hdb_index* ix);
  * the one that builds the shadow and pays for it.
  *
  * The 5-bit plane (one dot / cosine query; hdb_quant.hip, "The 5-bit plane").  Beside the codes the index keeps their high five
- * bits -- a nibble plane, a bit plane and a 16-byte record per row, 20 bytes per 32 elements + 16 (10M x 384: 2.56 GB) -- derived
- * from the codes wherever the shadow's rows are written (build, extend, update, gather) for rows of up to 512 elements.  A
+ * bits -- a nibble plane, a bit plane and 16 bytes of row terms per row, 20 bytes per 32 elements + 16 (10M x 384: 2.56 GB) --
+ * derived from the codes wherever the shadow's rows are written (build, extend, update, gather) for rows of up to 512 elements.
+ * The row terms are laid out per 16-row tile: 256 bytes = a 64-byte hot block for dot-product calls, one for cosine calls, and 128
+ * reserved bytes (zero).  A hot block holds 16 bfloat16 row scales rounded up (cosine: divided by the row's norm), 16 bytes
+ * ceil(2 ||residual||) and the tile's largest error terms {E*, T*, F*, 0} as float32; a call reads the one block of its metric,
+ * 4 bytes per row.  The maxima are tile state: whatever writes a row derives its whole tile again, from all of the tile's rows.  A
  * one-query call of at least plane_min_n rows (-1: the measured rule, 2 000 000) with use_plane on streams the plane and, in the
  * same launch, runs the int8 evaluation on the rows whose coarse upper bound hi5 reaches T_s, 16 at a time.  hi5 >= the int8
  * pass's own upper bound for every row, so the candidate list, and the answer, are those of the call without the plane.

@@ -201,13 +201,17 @@ static void quant_free(hdb_index* ix) {
     ix->qcodes.reset(); ix->qaux.reset(); ix->q_rows = 0;
     plane_free(ix);
 }
-// bytes of the 5-bit plane per row: 20 per 32-element unit and a 16-byte record (plane_possible, hdb_plan.h: rows of up to 512 elements)
+// bytes of the 5-bit plane per row: 20 per 32-element unit and 16 of row terms (plane_possible, hdb_plan.h: rows of up to 512 elements).
+// The row terms are laid out per 16-row tile (hdb_plane_rec_bytes, hdb_caps.h), so their array is rounded up to a whole tile: up to 240
+// bytes more than rows x this figure, which the memory guards below and the stat plane_bytes leave out (the guards keep 1 GiB free).
 static size_t plane_row_bytes(int P) { return (size_t)hdb_quant_plane_units(P) * 20 + 16; }
 // the plane's three arrays for `rows` rows: all of them, or none and the index as it was
 static bool plane_alloc(hdb_index* ix, int64_t rows) {
     const size_t U = (size_t)hdb_quant_plane_units(ix->qP);
     DevBuf<uint8_t> nib; DevBuf<uint32_t> bit; DevBuf<float> rec;
-    if (nib.alloc((size_t)rows * U * 16) != hipSuccess || bit.alloc((size_t)rows * U) != hipSuccess || rec.alloc((size_t)rows * 4) != hipSuccess) {
+    // (the records are laid out per 16-row tile, hdb_caps.h: whole tiles)
+    if (nib.alloc((size_t)rows * U * 16) != hipSuccess || bit.alloc((size_t)rows * U) != hipSuccess ||
+        rec.alloc((size_t)hdb_plane_rec_bytes(rows) / sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
@@ -217,6 +221,10 @@ static bool plane_alloc(hdb_index* ix, int64_t rows) {
 // Derive the plane of rows [row0, row0 + m) from their codes; called wherever the shadow's rows are written.  The plane's arrays
 // have the shadow's capacity (q_rows >= n rows; pass 1 loads the rows below n only); a reallocated shadow has dropped
 // them (quant_commit), and every row is derived again.  No memory: the index goes on without a plane.
+// A tile's hot blocks hold maxima over its rows (hdb_caps.h), so the plane is derived tile by tile: every tile that [row0, row0 + m)
+// touches, from all of its rows below the row count -- ix->n, or row0 + m where an extend has not committed its rows yet -- with
+// the neighbours' codes, caches and 1/||v|| as they stand.  inv_norm of the rows must be current: every caller fills it first, on
+// the same stream (build_caches and extend: hdb_launch_rownorm; gather: hdb_launch_gather_rows, committed before the call).
 static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
     if (!plane_possible(ix->d) || ix->plane_declined) return HDB_OK;
     if (!ix->pnib && !plane_wanted(ix->d, ix->opt)) return HDB_OK;
@@ -229,7 +237,10 @@ static int plane_rows(hdb_index* ix, int64_t row0, int64_t m, hipStream_t st) {
         ix->pU = hdb_quant_plane_units(ix->qP);
         m = row0 + m; row0 = 0;
     }
-    LAUNCH_TRY(hdb_launch_quant_plane_rows(ix->qcodes, ix->qaux, row0, m, ix->d, ix->qP, ix->pnib, ix->pbit, ix->prec, st));
+    if (m <= 0) return HDB_OK;
+    const int64_t rows = std::max(ix->n, row0 + m);
+    LAUNCH_TRY(hdb_launch_quant_plane_rows(ix->qcodes, ix->qaux, ix->inv_norm, row0 / 16, (row0 + m + 15) / 16, rows, ix->d, ix->qP, ix->pnib,
+                                           ix->pbit, ix->prec, st));
     return HDB_OK;
 }
 // New blocks for the shadow's codes and caches.  The two change together: built beside the index and swapped in (quant_commit) after

@@ -470,6 +470,63 @@ __host__ __device__ __forceinline__ int64_t hdb_plane_skip_tile(const HdbSkipPos
     const uint32_t jit = (uint32_t)(hdb_tile_index((int64_t)p.w, (int64_t)stride) - (int64_t)p.w * stride);
     return (int64_t)p.w * stride + p.o + (p.o >= jit ? 1u : 0u);
 }
+// The row terms of the plane pass (hdb_quant.hip, "The 5-bit plane": the hot block).  The record array keeps 16 bytes per row, laid
+// out per 16-row tile: 256 bytes = [0, 64) the hot block of dot-product calls, [64, 128) that of cosine calls, [128, 256) reserved
+// (zero).  A hot block: 16 bfloat16 k_hi (row r's scale -- s_r, cosine: s_r / ||v_r|| -- rounded UP), 16 bytes rc = ceil(2 R_r),
+// then four float32 words of the tile: E*, T* (the maxima of E_r and T_r over the tile's rows, cosine: of E_r / ||v_r|| and
+// T_r / ||v_r||, rounded up), F* (the bound's absolute floor 2^-100 (d + 8), cosine: times the largest 1 / ||v_r||, rounded up)
+// and a zero.  Pass 1 reads one block per tile; the numbers only ever widen its bound, and no bit of them reaches an answer.
+// (__host__ __device__: hdb_quant_plane_rows_kernel writes with these functions, hdb_quant_plane_scan_kernel reads with them and
+// tests/plane_block_check.hip runs them on the host.)
+#define HDB_PLANE_TILE_BYTES 256
+#define HDB_PLANE_BLOCK_BYTES 64
+#define HDB_PLANE_BLOCK_DOT 0
+#define HDB_PLANE_BLOCK_COSINE 1
+#define HDB_PLANE_BLOCK_K 0           // byte offsets inside a hot block: 16 x bf16 k_hi,
+#define HDB_PLANE_BLOCK_RC 32         // 16 x u8 rc,
+#define HDB_PLANE_BLOCK_TILE 48       // {E*, T*, F*, 0} float32
+// bytes of the record array for `rows` rows: whole tiles (16 bytes per row all the same)
+__host__ __device__ __forceinline__ int64_t hdb_plane_rec_bytes(int64_t rows) { return (rows + 15) / 16 * HDB_PLANE_TILE_BYTES; }
+__host__ __device__ __forceinline__ int64_t hdb_plane_block_off(int64_t tile, int flavour) {
+    return tile * HDB_PLANE_TILE_BYTES + (int64_t)flavour * HDB_PLANE_BLOCK_BYTES;
+}
+__host__ __device__ __forceinline__ float hdb_plane_bits_f(uint32_t u) { union { uint32_t u; float f; } c; c.u = u; return c.f; }
+__host__ __device__ __forceinline__ uint32_t hdb_plane_f_bits(float f) { union { uint32_t u; float f; } c; c.f = f; return c.u; }
+// The smallest bfloat16 at or above the non-negative float64 k (the high half of a float32; infinity where k is beyond the largest
+// finite bfloat16, which no scale of a finite row reaches; a NaN stays one).  Exact: a bfloat16 is a float32 is a float64.
+__host__ __device__ __forceinline__ uint16_t hdb_plane_k_encode(double k) {
+    if (!(k > 0.0)) return k == k ? (uint16_t)0 : (uint16_t)0x7FC0;
+    float f = (float)k;                                   // (rne: at most half a float32 ulp below k, then the truncation is at or below k)
+    if (f != f || f - f != 0.f) return (uint16_t)0x7F80;
+    uint32_t h = hdb_plane_f_bits(f) >> 16;               // truncated: at or below f
+    if ((double)hdb_plane_bits_f(h << 16) < k) ++h;       // next bfloat16 (carries into the exponent, up to infinity, as the bits do)
+    return (uint16_t)h;
+}
+__host__ __device__ __forceinline__ float hdb_plane_k_hi(uint32_t code) { return hdb_plane_bits_f(code << 16); }
+// The lower side is derived: bfloat16 numbers from 2^-126 on are at most a factor 1 + 2^-7 apart, so the k that rounded up to k_hi
+// is above k_hi (1 - 2^-7) (an exact float32 product: 8 x 7 bits); below that the spacing is absolute and the lower side is 0, as
+// it is for an infinite k_hi.
+__host__ __device__ __forceinline__ float hdb_plane_k_lo(float k_hi) {
+    return k_hi >= 0x1p-126f && k_hi <= 0x1.fep127f ? k_hi * (1.f - 0x1p-7f) : 0.f;
+}
+// rc = ceil(2 R) for R = sqrt(ss), ss the integer sum of squared residuals of a row (at most 16 x 512, so rc <= 182): the smallest
+// integer with rc^2 >= 4 ss, in integers.  It decodes as 0.5 rc >= R, exactly.
+__host__ __device__ __forceinline__ uint32_t hdb_plane_rc_encode(uint32_t ss) {
+    const uint32_t t = 4u * ss;
+    uint32_t rc = (uint32_t)sqrtf((float)t);
+    while (rc * rc < t) ++rc;
+    while (rc > 0u && (rc - 1u) * (rc - 1u) >= t) --rc;
+    return rc < 255u ? rc : 255u;
+}
+__host__ __device__ __forceinline__ float hdb_plane_rc_decode(uint32_t rc) { return 0.5f * (float)rc; }
+// float32 at or above the non-negative float64 x (a NaN or an overflow: infinity, which keeps every row of the tile)
+__host__ __device__ __forceinline__ float hdb_plane_up(double x) {
+    if (!(x > 0.0)) return x == x ? 0.f : hdb_plane_bits_f(0x7F800000u);
+    float f = (float)x;
+    if (f != f || f - f != 0.f) return hdb_plane_bits_f(0x7F800000u);
+    if ((double)f < x) f = hdb_plane_bits_f(hdb_plane_f_bits(f) + 1u);
+    return f;
+}
 
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 // widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan

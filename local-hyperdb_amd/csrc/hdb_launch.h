@@ -150,8 +150,8 @@ int hdb_launch_quant_gather(const int8_t* codes, const float* aux, const int64_t
 int hdb_launch_quant_qprep(const float* Q, int nq, int d, int P, int8_t* qcodes, float* qaux, int* stat, uint32_t* pl_cnt, void* stream);
 int hdb_launch_quant_qprep_m(const float* Q, int nq, int d, int P, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
                              int8_t* qcodes, float* qaux, int* stat, uint32_t* cnt_init, uint32_t* pl_cnt, void* stream);
-int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib, uint32_t* bitw,
-                                float* rec, void* stream);
+int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, const float* inv_norm, int64_t t0, int64_t t1, int64_t n, int d, int P,
+                                uint8_t* nib, uint32_t* bitw, float* rec, void* stream);
 int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int blocks, void* stream);
 int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);

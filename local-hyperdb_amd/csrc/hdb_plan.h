@@ -172,7 +172,7 @@ static inline int64_t quant_min_rows(int dtype) {
 static inline uint32_t plane_list_cap(const hdb_options& o, int64_t n) {
     return (uint32_t)(o.plane_cap_rows > 0 ? std::min<int64_t>(o.plane_cap_rows, n) : std::max<int64_t>(n / 8, 16));
 }
-// The 5-bit plane of the shadow (hdb_quant.hip): 20 bytes per 32-element unit and a 16-byte record per row, for rows of up to 512
+// The 5-bit plane of the shadow (hdb_quant.hip): 20 bytes per 32-element unit and 16 bytes of row terms per row (hot blocks per 16-row tile, hdb_caps.h), for rows of up to 512
 // elements (the widths the plane path takes).
 static inline bool plane_possible(int d) { return d <= 512; }
 // an index whose caller switched the path off (use_plane = 0) before the shadow was built does not pay for a plane

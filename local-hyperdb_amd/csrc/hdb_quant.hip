@@ -83,24 +83,53 @@
 // units of 32 elements (U = ceil(P / 32) units): a 16-byte piece of nibbles u >> 1 (byte b of word i = elements 8i + b | 8i + 4 + b
 // << 4, so w & 0x0F0F0F0F and (w >> 4) & 0x0F0F0F0F pair with consecutive query-code words), one word of bits u & 1 (element
 // 4g + b at bit 8b + g, so (w >> g) & 0x01010101 pairs with query word g), both as arrays of their own (a 16-row tile is
-// contiguous), and one record {s_r, E_r, T_r, R_r}, R_r = ||rho_r||_2 over j < d rounded up (an integer sum of at most 16 d).
+// contiguous), and 16 bytes of row terms, laid out per 16-row tile as two 64-byte HOT BLOCKS (one for dot-product calls, one for
+// cosine calls; hdb_caps.h) and 128 reserved bytes.  Pass 1 reads one block: 4 bytes per row, where the float32 terms
+// {s_r, E_r, T_r, R_r} and 1 / ||v_r|| took 20.  With w_r = 1 (dot) or 1 / ||v_r|| (cosine: the cached float32 inv_norm[r]) a block holds
+//     k_hi[16]   bfloat16: the smallest bfloat16 >= s_r w_r (the float64 product of two float32 numbers is exact);
+//                the lower side is derived, k_lo = k_hi (1 - 2^-7) <= s_r w_r (bfloat16 spacing; 0 below 2^-126);
+//     rc[16]     bytes: ceil(2 R_r), R_r = ||rho_r||_2 over j < d (an integer sum of squares of at most 16 d <= 8192, so rc <= 182);
+//                R = 0.5 rc >= R_r exactly;
+//     E*, T*, F* float32, the maxima over the tile's rows (rows < n) of E_r w_r, T_r w_r and absmin w_r, each rounded up,
+//                absmin = 2^-100 (d + 8) the absolute floor of (3).  For cosine E_r w_r and T_r w_r are scale-free (about 7e-3 for every
+//                row), so the maxima are tight; a dot-product call on a tile whose norms differ widely passes more of its rows.
+// Pass 1 only filters: every row it keeps is evaluated again with MODE 1's own bits, so these terms need to be conservative and
+// nothing else -- no bit of them reaches an answer.
 // The bound.  c = 8u - 124 + rho, so with C5 = sum_j c_qj (8 u_rj - 124) = 8 sum_j c_qj u_rj - 124 sum_j c_qj (exact in int32)
-//     |C - C5| = |sum_j c_qj rho_rj| <= ||c_q|| ||rho_r|| <= N_c R_r =: U                                            (4)
+//     |C - C5| = |sum_j c_qj rho_rj| <= ||c_q|| ||rho_r|| <= N_c R =: U                                              (4)
 // (Cauchy-Schwarz on integers; the query prep leaves N_c = ||c_q|| rounded up and sum_j c_qj in qaux).  In float32:
-//     ch = fl(fl(C5) + fl(N_c R_r)) + (|.| 2^-20 + 1) >= C5 + U >= C, and ch is a float, so ch >= fl(C);  cl likewise <= fl(C)
+//     ch = fl(fl(C5) + fl(N_c R)) + (|.| 2^-20 + 1) >= C5 + U >= C, and ch is a float, so ch >= fl(C);  cl likewise <= fl(C)
 // (fl(C5) errs by 2^-24 |C5|, the product and the sum by 2^-24 (|C5| + 2U), U <= 508 d: the absolute 1 covers what the relative term
-// does not).  MODE 1 forms A = fl(k fl(C)), k = fl(s_q s_r) >= 0: two multiplies, nothing to contract, monotone in fl(C).  So
-// A5 = fl(k ch) >= A >= Al = fl(k cl), and |A| <= Amax = max(|A5|, |Al|).  The raw upper bound of (3) is, in real numbers,
-// g(A) = A + c0 + |A| 2^-10 + absmin with c0 = (N_q E_r + D_q T_r)(1 + 2^-10): non-decreasing in A.  ANY float32 evaluation F(A) of it
-// (whatever the compiler contracts) errs by at most 8u (|A| + B(A)) <= 8u Mx, Mx = Amax + Bmax, Bmax = B at |A| = Amax.  Hence
-//     X = F5(A5) + Mx 2^-18 >= g(A5) - 8u Mx + 64u Mx - (own roundings, < 4u Mx) >= g(A) + 8u Mx >= F(A).
-// The cosine scalings are two multiplies by positive numbers in both kernels: y5 = m(X) >= m(F(A)) = y8, and both magnitudes are at
-// most mM = m(Mx (1 + 2^-17)).  The bias add may be contracted into the last multiply in either kernel: each side errs by at most
-// 2u (|y| + |bias|) <= 2u Z, Z = mM + |bias|; MODE 1 then pushes its value by |hi| 2^-20 + 1e-30 <= Z 2^-20 (1 + 4u) + 1e-30.  With
+// does not).  MODE 1 forms A = fl(k8 fl(C)), k8 = fl(s_q s_r) >= 0, and, for cosine, multiplies by w_r after the sum A + B; pass 1
+// works in the scaled domain from the start, A' = A w_r (a real number), k' = s_q s_r w_r.  |A - s_q s_r fl(C)| <= 2.1u |A|, so
+// A' lies within 2.1u |A'| of k' fl(C).  The two sides of k':
+//     k_up = fl(s_q k_hi) pushed up by 2^-20   >= k' (1 + 2^-21),        k_dn = fl(s_q k_lo) pushed down by 2^-20   <= k' (1 - 2^-21)
+// (the pushes, 16u, cover the three roundings of each WHILE THE PRODUCTS ARE NORMAL NUMBERS.  A product s_q k below 2^-126 errs by an
+// absolute 2^-150 instead -- by up to 2^-126 if denormals were flushed -- which |ch| < 2^23 turns into at most 2^-103 of A5; MODE 1's
+// own k8 = fl(s_q s_r) errs by 2^-150 likewise, 2^-127 of A, and its multiply by w_r scales that.  Neither is relative to anything,
+// so the cover is the absolute 1e-30 > 2^-100 in X below, ahead of the multiply by 1 / ||q|| in both kernels.  It holds for
+// w_r <= 2^24, i.e. rows of norm 2^-24 or more: every non-zero float16 row.  The assumption is therefore about float32 rows of
+// smaller norm: for those s_q s_r must be a normal number, at least 2^-126.  A dot-product call needs none, see "monotone" below.)
+// The upper side of k' fl(C) takes k_up where ch >= 0 and k_dn where ch < 0:
+//     ch >= 0:  A5 = fl(k_up ch) >= k' (1 + 2^-22) ch >= k' (1 + 2^-22) fl(C) >= A' for fl(C) >= 0, and A5 >= 0 > A' for fl(C) < 0;
+//     ch <  0:  fl(C) <= ch < 0 and A5 = fl(k_dn ch) >= k' (1 - 2^-22) ch >= k' (1 - 2^-22) fl(C) = k' fl(C) + 4u |k' fl(C)| >= A'.
+// Al = fl(k_dn cl) for cl >= 0, fl(k_up cl) for cl < 0, is <= A' in the same way, and |A'| <= Amax = max(|A5|, |Al|).  (For dot, where
+// w_r = 1, fl(s_q k_hi) >= k8 >= fl(s_q k_lo) already by monotone rounding.)  The raw upper bound of (3), times w_r, is at most
+//     g(A') = A' + c0 + |A'| 2^-10 + F*,   c0 = (N_q E* + D_q T*)(1 + 2^-10) >= (N_q E_r + D_q T_r)(1 + 2^-10) w_r,   F* >= absmin w_r
+// in real numbers: non-decreasing in A'.  MODE 1's float32 evaluation F(A) of (3), whatever the compiler contracts, errs by at most
+// 8u (|A| + B(A)), and its multiply by w_r by one more u: y = fl(F(A) w_r) <= g(A') + 9.1u (|A'| + B'(A')) <= g(A5) + 9.1u Mx,
+// Mx = Amax + Bmax, Bmax = c0 + Amax 2^-10 + F*.  ANY float32 evaluation F5 of g errs by at most 8u Mx.  Hence
+//     X = F5(A5) + Mx 2^-18 >= g(A5) - 8u Mx + 64u Mx - (own roundings, < 4u Mx) >= g(A5) + 52u Mx >= y.
+// What is left of the cosine scaling is one multiply by 1 / ||q|| > 0 in both kernels: y5 = fl(X / ||q||) >= fl(y / ||q||) = y8, and
+// both magnitudes are at most mM = fl(Mx (1 + 2^-17) / ||q||).  (MODE 1 associates (F w_r) / ||q||, pass 1 folds w_r into k', c0 and
+// F*: a few ulps, inside the 52u above.)  The bias add may be contracted into the last multiply in either kernel: each side errs by at
+// most 2u (|y| + |bias|) <= 2u Z, Z = mM + |bias|; MODE 1 then pushes its value by |hi| 2^-20 + 1e-30 <= Z 2^-20 (1 + 4u) + 1e-30.  With
 //     hi5 = fl(y5 + bias) + Z 2^-18 + 4e-30
-// the sum of all of that (< Z 2^-20 x 1.5 + 1e-30) is covered: hi5 >= hi for every row, hi as MODE 1 computes it.  A row pass 1
-// drops (hi5 < T_s; a NaN never drops) would have been dropped by MODE 1: the candidate set, and every later stage, is unchanged.
-// Z 2^-18 is relative to magnitudes that do not cancel, at most 2^-8 of the bound's own width B: pass 1 loses nothing by it.
+// the sum of all of that (< Z 2^-20 x 1.5 + 1e-30) is covered: hi5 >= hi for every row, hi as MODE 1 computes it, and hi5 is finite
+// where the terms are.  A row pass 1 drops (hi5 < T_s; a NaN never drops) would have been dropped by MODE 1: the candidate set, and
+// every later stage, is unchanged.  The pushes are relative to magnitudes that do not cancel.  What the block costs in width: k_up
+// and k_dn are 2^-7 |A'| apart -- about 0.03 of a score's standard deviation at d = 384, against a width B of about 1.15 -- R grows by
+// at most 0.5 in about 45, and E*, T* are the tile's largest instead of the row's own.
 // The rows pass 1 keeps are finished by pass 1 itself: 16 at a time they go through MODE 1's own evaluation (hq_rows4_bounds, compiled
 // with contraction off: the uncontracted form is one of the evaluations F(A) above, and both kernels get the same bits from it).
 // The sampled tiles are not streamed a second time.  The sample pass has already put their rows through that evaluation, so it stores
@@ -680,46 +709,89 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// The 5-bit plane.  Derivation from the codes of rows [row0, row0 + m): 16 lanes per row, lane l16 packs unit l16 (32 elements:
-// one 16-byte piece of nibbles, one word of bits), the group sums the squared residuals of the elements below d.
+// The 5-bit plane.  Derivation from the codes of the 16-row tiles [t0, t1), rows below n: a wave per tile, four rows at a time, 16
+// lanes per row; lane l16 packs unit l16 (32 elements: one 16-byte piece of nibbles, one word of bits), the group sums the squared
+// residuals of the elements below d.  Lanes 0-15 then hold one row of the tile each and write its two hot blocks (hdb_caps.h): the
+// maxima E*, T*, F* are tile state, so a tile is always derived whole, from all of its rows (plane_rows, hdb_api.hip, rounds to
+// tiles), and the rows at or beyond n take no part in them.  inv_norm must hold the tile's rows already.
 // ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P,
-                                                                   int U, uint8_t* nib, uint32_t* bitw, float* rec) {
+__global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t* codes, const float* aux, const float* inv_norm, int64_t t0,
+                                                                   int64_t t1, int64_t n, int d, int P, int U, uint8_t* nib,
+                                                                   uint32_t* bitw, float* rec) {
     const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
-    for (int64_t base = wave * 4; base < m; base += nwaves * 4) {            // (wave-uniform)
-        const int64_t r = row0 + base + g;
-        const bool valid = base + g < m;
-        int ss = 0;
-        if (valid && l16 < U) {
-            const int8_t* src = codes + r * (int64_t)P + 32 * l16;
-            uint4 raw[2];
-            raw[0] = *reinterpret_cast<const uint4*>(src);
-            raw[1] = (32 * l16 + 16 < P) ? *reinterpret_cast<const uint4*>(src + 16) : make_uint4(0u, 0u, 0u, 0u);
-            const uint32_t* cw = reinterpret_cast<const uint32_t*>(raw);      // query-aligned words: word w holds elements 4w .. 4w + 3
-            uint32_t nw[4] = {0u, 0u, 0u, 0u}, bw = 0u;
+    for (int64_t t = t0 + wave; t < t1; t += nwaves) {                       // (wave-uniform)
+        int ssr[4];
 #pragma unroll
-            for (int w = 0; w < 8; ++w) {
+        for (int it = 0; it < 4; ++it) {
+            const int64_t r = t * 16 + 4 * it + g;
+            int ss = 0;
+            if (r < n && l16 < U) {
+                const int8_t* src = codes + r * (int64_t)P + 32 * l16;
+                uint4 raw[2];
+                raw[0] = *reinterpret_cast<const uint4*>(src);
+                raw[1] = (32 * l16 + 16 < P) ? *reinterpret_cast<const uint4*>(src + 16) : make_uint4(0u, 0u, 0u, 0u);
+                const uint32_t* cw = reinterpret_cast<const uint32_t*>(raw);      // query-aligned words: word w holds elements 4w .. 4w + 3
+                uint32_t nw[4] = {0u, 0u, 0u, 0u}, bw = 0u;
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int c = (int)(int8_t)((cw[w] >> (8 * b)) & 0xFFu);
-                    const int h = c >> 3;
-                    const uint32_t u5 = (uint32_t)(h + 16);
-                    const int rho = c - (8 * h + 4);
-                    if (32 * l16 + 4 * w + b < d) ss += rho * rho;
-                    nw[w >> 1] |= (u5 >> 1) << (8 * b + 4 * (w & 1));
-                    bw |= (u5 & 1u) << (8 * b + w);
+                for (int w = 0; w < 8; ++w) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const int c = (int)(int8_t)((cw[w] >> (8 * b)) & 0xFFu);
+                        const int h = c >> 3;
+                        const uint32_t u5 = (uint32_t)(h + 16);
+                        const int rho = c - (8 * h + 4);
+                        if (32 * l16 + 4 * w + b < d) ss += rho * rho;
+                        nw[w >> 1] |= (u5 >> 1) << (8 * b + 4 * (w & 1));
+                        bw |= (u5 & 1u) << (8 * b + w);
+                    }
                 }
+                *reinterpret_cast<uint4*>(nib + (r * (int64_t)U + l16) * 16) = make_uint4(nw[0], nw[1], nw[2], nw[3]);
+                bitw[r * (int64_t)U + l16] = bw;
             }
-            *reinterpret_cast<uint4*>(nib + (r * (int64_t)U + l16) * 16) = make_uint4(nw[0], nw[1], nw[2], nw[3]);
-            bitw[r * (int64_t)U + l16] = bw;
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+            ssr[it] = ss;                                                    // (every lane of group g: row 4 it + g; at most 16 d, exact)
+        }
+        // lane e < 16 takes row e = 4 it + g of the tile from group g = e & 3, pass it = e >> 2
+        int ss = 0;
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int v = __shfl(ssr[it], 16 * (lane & 3), 64);
+            if (((lane >> 2) & 3) == it) ss = v;
+        }
+        const int64_t r = t * 16 + l16;
+        const bool valid = lane < 16 && r < n;
+        const double absmin = 0x1p-100 * (double)(d + 8);
+        double kd = 0.0, kc = 0.0;
+        float ed = 0.f, td = 0.f, fd = 0.f, ec = 0.f, tc = 0.f, fc = 0.f;
+        uint32_t rcode = 0u;
+        if (valid) {
+            const float s = aux[3 * r + HDB_QROW_S], e = aux[3 * r + HDB_QROW_E], tt = aux[3 * r + HDB_QROW_T];
+            const double inv = (double)inv_norm[r];
+            kd = (double)s; kc = (double)s * inv;                            // (products of two float32 numbers: exact in float64)
+            ed = e; td = tt; fd = hdb_plane_up(absmin);
+            ec = hdb_plane_up((double)e * inv); tc = hdb_plane_up((double)tt * inv); fc = hdb_plane_up(absmin * inv * (1.0 + 0x1p-40));
+            rcode = hdb_plane_rc_encode((uint32_t)ss);
         }
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        if (valid && l16 == 0) {
-            const float R = sqrtf((float)ss) * (1.f + 0x1p-20f);             // ss <= 16 d is exact; sqrtf errs by half an ulp
-            *reinterpret_cast<float4*>(rec + 4 * r) = make_float4(aux[3 * r + HDB_QROW_S], aux[3 * r + HDB_QROW_E], aux[3 * r + HDB_QROW_T], R);
+        for (int o = 8; o > 0; o >>= 1) {                                    // (a NaN of a non-finite row is dropped or kept: such an index takes no quantized call)
+            ed = fmaxf(ed, __shfl_xor(ed, o, 64)); td = fmaxf(td, __shfl_xor(td, o, 64)); fd = fmaxf(fd, __shfl_xor(fd, o, 64));
+            ec = fmaxf(ec, __shfl_xor(ec, o, 64)); tc = fmaxf(tc, __shfl_xor(tc, o, 64)); fc = fmaxf(fc, __shfl_xor(fc, o, 64));
+        }
+        if (lane < 16) {
+            char* tile = reinterpret_cast<char*>(rec) + hdb_plane_block_off(t, 0);
+#pragma unroll
+            for (int fl = 0; fl < 2; ++fl) {
+                char* blk = tile + fl * HDB_PLANE_BLOCK_BYTES;
+                reinterpret_cast<uint16_t*>(blk + HDB_PLANE_BLOCK_K)[l16] = hdb_plane_k_encode(fl == HDB_PLANE_BLOCK_COSINE ? kc : kd);
+                reinterpret_cast<uint8_t*>(blk + HDB_PLANE_BLOCK_RC)[l16] = (uint8_t)rcode;
+                if (l16 == 0)
+                    *reinterpret_cast<float4*>(blk + HDB_PLANE_BLOCK_TILE) =
+                        fl == HDB_PLANE_BLOCK_COSINE ? make_float4(ec, tc, fc, 0.f) : make_float4(ed, td, fd, 0.f);
+            }
+            if (l16 < 8) *reinterpret_cast<uint4*>(tile + 2 * HDB_PLANE_BLOCK_BYTES + 16 * l16) = make_uint4(0u, 0u, 0u, 0u);      // reserved
         }
     }
 }
@@ -776,9 +848,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         const int f = lane + 64 * j;
         qoff[j] = f < npieces ? 2 * (f % U) : 0;
     }
-    const float absmin = 0x1p-100f * (float)(a.d + 8);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x3 __attribute__((ext_vector_type(3)));
     const int64_t ntiles = a.ntiles;
     const int et = lane >> 4, er = lane & 15;                       // epilogue lanes 0-31: tile et of the pair, row er
     int qn = 0;                                                     // rows in this wave's queue (wave-uniform)
@@ -841,12 +912,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         // the row terms of the epilogue lanes, issued with the plane loads
         const int64_t row = (et ? tl[1] : tl[0]) * 16 + er;
         const bool rvalid = lane < 32 && row < a.n;      // (no tile: row = 16 ntiles >= n)
-        f32x4 rc = f32x4{0.f, 0.f, 0.f, 0.f};
-        float invn = 1.f, bias = 0.f;
+        // (the hot block of the lane's tile, hdb_caps.h: its own k_hi and rc, and the tile's {E*, T*, F*, 0} -- 64 bytes per tile)
+        f32x3 tm = f32x3{0.f, 0.f, 0.f};                 // (three words, not the block's four: a fourth register nobody reads is reused at once, and that write waits for every load in flight)
+        uint32_t kcode = 0u, rcode = 0u;
+        float bias = 0.f;
         bool masked = false;
         if (rvalid) {
-            rc = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.pl_rec) + row);
-            if (cosine) invn = a.inv_norm[row];
+            const char* blk = reinterpret_cast<const char*>(a.pl_rec) + hdb_plane_block_off(et ? tl[1] : tl[0], cosine ? HDB_PLANE_BLOCK_COSINE : HDB_PLANE_BLOCK_DOT);
+            // (plain loads: the three pieces of a lane, and the 16 lanes of a tile, share one 64-byte block, and the streaming hint on them
+            //  cost the headline 13 us against these -- profiles/plane_block_time.txt, "variant")
+            kcode = reinterpret_cast<const uint16_t*>(blk + HDB_PLANE_BLOCK_K)[er];
+            rcode = reinterpret_cast<const uint8_t*>(blk + HDB_PLANE_BLOCK_RC)[er];
+            tm = *reinterpret_cast<const f32x3*>(blk + HDB_PLANE_BLOCK_TILE);
             if (a.bias) bias = a.bias[row];
             if (a.mask) masked = !a.mask[row];
         }
@@ -885,20 +962,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         const bool dead = !rvalid || masked || q_bad;
         if (!dead) {
             const float fc = (float)(8 * S - 124 * q_cs);
-            const float Uf = q_cn * rc.w;
+            const float Uf = q_cn * hdb_plane_rc_decode(rcode);
             float ch = fc + Uf, cl = fc - Uf;
             ch = ch + (fabsf(ch) * 0x1p-20f + 1.f);
             cl = cl - (fabsf(cl) * 0x1p-20f + 1.f);
-            const float k = q_s * rc.x;
-            const float A5 = k * ch, Al = k * cl;
+            const float k_hi = hdb_plane_k_hi(kcode), k_lo = hdb_plane_k_lo(k_hi);
+            float k_up = q_s * k_hi, k_dn = q_s * k_lo;
+            k_up = k_up + k_up * 0x1p-20f;
+            k_dn = k_dn - k_dn * 0x1p-20f;
+            const float A5 = (ch >= 0.f ? k_up : k_dn) * ch, Al = (cl >= 0.f ? k_dn : k_up) * cl;
             const float Amax = fmaxf(fabsf(A5), fabsf(Al));
-            const float c0 = (q_n * rc.y + q_d * rc.z) * (1.f + 0x1p-10f);
-            const float B5 = c0 + fabsf(A5) * 0x1p-10f + absmin;
-            const float Bmax = c0 + Amax * 0x1p-10f + absmin;
+            const float c0 = (q_n * tm.x + q_d * tm.y) * (1.f + 0x1p-10f);
+            const float B5 = c0 + fabsf(A5) * 0x1p-10f + tm.z;
+            const float Bmax = c0 + Amax * 0x1p-10f + tm.z;
             const float Mx = Amax + Bmax;
             float X = (A5 + B5) + (Mx * 0x1p-18f + 1e-30f);
             float mM = Mx * (1.f + 0x1p-17f);
-            if (cosine) { X = X * invn * q_inv; mM = mM * invn * q_inv; }
+            if (cosine) { X = X * q_inv; mM = mM * q_inv; }            // (1 / ||v_r|| is in k_hi, E*, T*, F* already)
             const float Z = mM + fabsf(bias);
             float h = X;
             if (a.bias) h += bias;
@@ -1152,13 +1232,14 @@ extern "C" int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_bl
 }
 
 // The 5-bit plane: derivation and pass 1 (one query; dot / cosine).
-extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, int64_t row0, int64_t m, int d, int P, uint8_t* nib,
-                                           uint32_t* bitw, float* rec, void* stream) {
-    if (m <= 0) return 0;
+// the tiles [t0, t1) of the plane, whole, from the codes, caches and 1/||v|| of their rows below n
+extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, const float* inv_norm, int64_t t0, int64_t t1, int64_t n, int d,
+                                           int P, uint8_t* nib, uint32_t* bitw, float* rec, void* stream) {
+    if (t1 <= t0) return 0;
     const int U = hdb_quant_plane_units(P);
-    if (U > 16 || (P & 15) != 0) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(hdb_quant_plane_rows_kernel, dim3(hdb_grid_for(m, 16, 8192)), dim3(256), 0, (hipStream_t)stream, codes, aux, row0, m, d,
-                       P, U, nib, bitw, rec);
+    if (U > 16 || (P & 15) != 0 || t0 < 0 || (t1 - 1) * 16 >= n) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(hdb_quant_plane_rows_kernel, dim3(hdb_grid_for(t1 - t0, 4, 8192)), dim3(256), 0, (hipStream_t)stream, codes, aux, inv_norm,
+                       t0, t1, n, d, P, U, nib, bitw, rec);
     return (int)hipGetLastError();
 }
 // dbg = false: pass 1 (candidates of the rows the plane keeps; the threshold as MODE 1 takes it, folded or a.thr); dbg = true: hi5 of every row -> a.dbg (tests)
