@@ -498,6 +498,51 @@ int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_score, int32_t 
                         int64_t n_groups, int64_t n, int64_t row_base, int64_t* dev_idx_out, float* dev_score_out, int32_t* dev_status,
                         int device, void* stream);
 
+/* Multi-vector queries: a query is a SET of vectors, a document a group of rows, and groups are ranked by the sum over the set's
+ * vectors of each vector's best row in the group -- late interaction (ColBERT / ColPali style stores: token or patch vectors) and
+ * multi-query fusion (T paraphrases of one question over source_indices groups; every row its own group: the sum of the scores).
+ * Semantics.  A call carries ns sets; set s is the vectors dev_Q[host_off[s] .. host_off[s + 1]) of one flat float32 matrix
+ * (float64 for an HDB_F64 index), T_s = host_off[s + 1] - host_off[s] >= 1.  x(t, r) is the score every exact call of this handle
+ * ranks by: the metric's score with the handle's bias added, -inf where the row mask excludes the row, where the score is NaN or
+ * where the row's group id is outside [0, n_groups); its bits are those hdb_topk_exact gives that row in a call of the same vectors.
+ * (Euclidean: the score pass stays on the VALU scan, which sums the differences themselves -- the bits hdb_topk_exact gives a row it
+ * re-scores.  The matrix cores' ||v||^2 + ||q||^2 - 2 v.q cancels on a row close to a query vector, the row a group's maximum picks.)
+ *   score(s, g) = canon(((x_0 + x_1) + ...) + x_{T-1}),  x_i = max over the rows r of g of x(host_off[s] + i, r)
+ * in float32, one add per vector, in vector order; canon: NaN -> -inf.  A group without an eligible row, or with a term at -inf,
+ * scores -inf.  The answer of set s is the first k groups by (score descending, group id ascending); groups at -inf are never
+ * returned: the tail is -1 / -inf.  The bias enters every term, T times in all.  The result does not depend on how the vectors are
+ * chunked as long as the vectors' score bits do not; on integer data they never do.
+ *
+ * hdb_maxsim_host: the answer of ns sets as the packed record of hdb_topk_host (hdb_packed_bytes(ns, k)) in host memory; indices
+ * are GROUP ids, scores the group scores; the call synchronises `stream`.  ns >= 1 and 1 <= k (else HDB_ERR_ARG), k <= HDB_MAX_K
+ * (else HDB_ERR_UNSUPPORTED), host_off[0] == 0 and strictly increasing (else HDB_ERR_ARG naming the set); then the handle; no groups
+ * set: HDB_ERR_ARG.  Served: every dtype (HDB_B1 included) with dot, cosine, euclidean, manhattan and pearson; hamming and jaccard
+ * return HDB_ERR_UNSUPPORTED.  Status word of a set: HDB_Q_NAN where one of its vectors holds a NaN, HDB_Q_BADROW for every set
+ * where a row's group id is outside [0, n_groups) (such a row counts as masked; nothing is indexed with its id).
+ * How it runs (local-hyperdb_amd/csrc/hdb_maxsim_plan.h, hdb_maxsim.hip).  On the first call after hdb_index_set_groups the index
+ * builds an inverted index of the ids on the device -- grp_rows, the rows ordered by (group id, row), by a stable radix sort, and
+ * grp_off, n_groups + 1 offsets -- and keeps it until the ids are replaced, cleared or dropped (hdb_index_extend / _update / _gather
+ * drop it, hdb_index_rebase keeps it).  The index is derived from the ids as they stood at that call: a caller who rewrites the borrowed
+ * array in place must call hdb_index_set_groups again (the grouped call reads the ids afresh on every call; this one does not).
+ * Ids that are non-decreasing by row -- a document's chunks are adjacent rows -- are their own
+ * index: only the offsets are built and the reduction reads the scores contiguously (stat maxsim_sorted).  The sets are handled in
+ * blocks of sb whose running sums acc[sb][n_groups] fit the budget; inside a block the flat vector range goes through the exact
+ * score pass of the multi-kernel pipeline in chunks of cq <= 256 vectors (128 in K slices) -- VALU scan on matrices of up to 8192
+ * rows, the matrix cores where the plan of a call of that many queries says so (never for euclidean, above) -- and chunks may cut across set boundaries: one pass
+ * over V serves several sets.  After each chunk one launch reduces sbuf[cq][n] into acc: a team of 1 | 4 | 16 | 64 lanes owns a
+ * group, takes the maximum over the group's rows per vector and adds it to the set's running sum -- no atomics, one owner per
+ * element, a fixed order of adds.  Per block the radix selection of the exact pipeline runs over acc (n = n_groups, row_base 0).
+ * sbuf (4 bytes per vector and row) and acc (4 bytes per set and group) count against exact_bytes.
+ * Options: maxsim_team (0 = the rule from n / n_groups, hdb_caps.h; 1 | 4 | 16 | 64 = fixed; no call is answered differently for it).
+ * Stats: maxsim (1 after such a call; hdb_topk, hdb_rerank and the grouped call set it to 0; a multi-vector call sets grouped =
+ * rerank = 0), maxsim_chunks (score-pass launches' chunks), maxsim_team, maxsim_sorted, maxsim_bytes (the inverted index as held);
+ * mfma / path are those of the score pass.
+ * Not built: several GPUs / shards; hamming / jaccard; k > 2048; a score pass that reduces in its own epilogue without the
+ * [vectors][rows] round trip (the follow-up); per-vector weights; splitting one huge group over teams (one team walks it: correct,
+ * slow). */
+int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* host_off, int32_t ns, int32_t k, int metric,
+                    void* host_record, void* stream);   /* record: hdb_packed_bytes(ns, k); indices are GROUP ids */
+
 /* Merge `parts` per-shard top-k lists (the all-gathered [parts][nq][k] buffers of the row-sharded
  * index) into the global top-k per query, same ordering rule.  Every part list must be ordered as hdb_topk writes
  * it: score descending, row ascending, unused slots (index -1) at the end. */
@@ -591,6 +636,7 @@ void hdb_group_destroy(hdb_group* g);
  *   rerank_chunk (hdb_rerank: queries per chunk, 0 = automatic, up to 256; at most 256).
  *   group_oversample (hdb_topk_grouped_host: rows per wanted group in the first fast round, 1 .. 64, default 4), group_fast_rounds
  *   (0 .. 2, default 2; 0: every query through the exact grouped pass).
+ *   maxsim_team (hdb_maxsim_host: lanes per group of its reduction, 0 = the rule, 1 | 4 | 16 | 64).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
@@ -598,7 +644,8 @@ void hdb_group_destroy(hdb_group* g);
  *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows, plane_blocks (workgroups of the last call's
  *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second
  *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0), grouped, group_k,
- *   group_rounds, group_exact (hdb_topk_grouped_host, above). */
+ *   group_rounds, group_exact (hdb_topk_grouped_host, above), maxsim, maxsim_chunks, maxsim_team, maxsim_sorted, maxsim_bytes
+ *   (hdb_maxsim_host, above). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

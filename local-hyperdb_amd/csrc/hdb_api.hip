@@ -19,6 +19,7 @@
 #include "hdb_ws.h"
 #include "hdb_plan.h"
 #include "hdb_group_plan.h"
+#include "hdb_maxsim_plan.h"
 #include "hdb_devbuf.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
@@ -75,6 +76,12 @@ struct hdb_index {
     // ... and a group id per row (hdb_index_set_groups): n ids in [0, n_groups), checked by every kernel that reads one
     const int32_t* groups = nullptr;
     int64_t n_groups = 0;
+    // ... and their inverted index (owned, lazy: hdb_maxsim_host builds it on its first call after hdb_index_set_groups; hdb_maxsim.hip):
+    // grp_rows = the rows ordered by (group id, row) -- not built where the ids are non-decreasing by row (grp_sorted: the identity) --
+    // grp_off = n_groups + 1 offsets into it, grp_flags = two device words: [0] an id outside [0, n_groups), [1] ids that decrease
+    DevBuf<uint32_t> grp_rows, grp_off;
+    DevBuf<int> grp_flags;
+    bool grp_valid = false, grp_sorted = false;
     // mask folded into a bias vector for the MFMA scan (owned, rebuilt per call: the mask and bias are borrowed)
     DevBuf<float> mbias;
     // control block of the single-launch pipeline (owned): counters + exchange granules, zero between calls
@@ -138,7 +145,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 110; }
+extern "C" int hdb_version(void) { return 111; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 // The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
@@ -162,7 +169,7 @@ static void matrix_changed(hdb_index* ix, int64_t kept_rows, hipStream_t st) {
     ix->pscale_valid = false; ix->pscale_done = std::min(ix->pscale_done, kept_rows);
     ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old matrix no longer apply
     ix->rows = nullptr; ix->subset_m = 0;
-    ix->groups = nullptr; ix->n_groups = 0;
+    ix->groups = nullptr; ix->n_groups = 0; ix->grp_valid = false;
     ix->build_stream = st;
 }
 // New blocks for the per-row caches.  The two change together: they are built beside the index and swapped in (caches_commit) after
@@ -524,6 +531,7 @@ extern "C" int hdb_index_set_groups(hdb_index* ix, const int32_t* dev_groups, in
     if (!ix) return fail(HDB_ERR_ARG, "hdb_index_set_groups: null index");
     if (dev_groups && (n_groups < 1 || n_groups > 0x7FFFFFFFll)) return fail(HDB_ERR_ARG, "hdb_index_set_groups: n_groups must be in [1, 2^31 - 1]");
     ix->groups = dev_groups; ix->n_groups = dev_groups ? n_groups : 0;
+    ix->grp_valid = false;                              // (the inverted index of the old ids: built again by the next multi-vector call)
     return HDB_OK;
 }
 
@@ -581,6 +589,7 @@ extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     else if (!strcmp(name, "rerank_chunk")) ix->opt.rerank_chunk = std::max<int64_t>(0, std::min<int64_t>(value, HDB_RERANK_MAXQ));
     else if (!strcmp(name, "group_oversample")) ix->opt.group_oversample = std::max<int64_t>(1, std::min<int64_t>(value, HDB_GROUP_OVERSAMPLE_MAX));
     else if (!strcmp(name, "group_fast_rounds")) ix->opt.group_fast_rounds = std::max<int64_t>(0, std::min<int64_t>(value, HDB_GROUP_ROUNDS_MAX));
+    else if (!strcmp(name, "maxsim_team")) { if (value == 0 || value == 1 || value == 4 || value == 16 || value == 64) ix->opt.maxsim_team = value; }
     else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
@@ -614,6 +623,11 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     else if (!strcmp(name, "group_k")) *value = ix->st.group_k;
     else if (!strcmp(name, "group_rounds")) *value = ix->st.group_rounds;
     else if (!strcmp(name, "group_exact")) *value = ix->st.group_exact;
+    else if (!strcmp(name, "maxsim")) *value = ix->st.maxsim;
+    else if (!strcmp(name, "maxsim_chunks")) *value = ix->st.maxsim_chunks;
+    else if (!strcmp(name, "maxsim_team")) *value = ix->st.maxsim_team;
+    else if (!strcmp(name, "maxsim_sorted")) *value = ix->st.maxsim_sorted;
+    else if (!strcmp(name, "maxsim_bytes")) *value = (int64_t)((ix->grp_rows.cap + ix->grp_off.cap) * sizeof(uint32_t));      // the inverted index of the groups, as held
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
@@ -1035,15 +1049,13 @@ struct TopkEnv {
     const void* Qeff; int metric_eff;                  // pearson: the centred queries through the cosine pipeline
     const float* bias_eff; const uint8_t* mask_eff;    // the MFMA scan has no mask input: excluded rows get a bias of -inf instead
 };
-static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkEnv& e) {
+// (the prologue alone, over a workspace that is laid out already: hdb_maxsim_host lays TopkWs inside its own layout)
+static int topk_prologue(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkEnv& e) {
     hipStream_t st = c.st;
     const bool f64 = ix->dtype == HDB_F64;
     const int64_t n = ix->n;
-    e.sort_temp = 0;
-    if (p.sort_n > 0) LAUNCH_TRY(hdb_sort_temp_bytes(p.sort_n, &e.sort_temp));
     TopkWs& w = e.w;
-    int rc = ws_lay(ix, w, (int)c.nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, p.sort_n, e.sort_temp, p.n_best);
-    if (rc) return rc;
+    int rc = HDB_OK;
     if (p.prep)
         LAUNCH_TRY(hdb_launch_qprep2(c.Q, c.nq, ix->d, f64, w.qinv, w.qsq, w.qnan, p.q16_in_prep ? w.q16 : nullptr, w.qscl, p.fold_small ? w.thr : nullptr,
                                      p.fold_small ? w.cnt : nullptr, (p.fold_small && p.bits) ? w.qbits : nullptr, p.W, st));
@@ -1064,6 +1076,13 @@ static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkE
         e.bias_eff = ix->mbias; e.mask_eff = nullptr;
     }
     return HDB_OK;
+}
+static int topk_begin(hdb_index* ix, const TopkArgs& c, const TopkPlan& p, TopkEnv& e) {
+    e.sort_temp = 0;
+    if (p.sort_n > 0) LAUNCH_TRY(hdb_sort_temp_bytes(p.sort_n, &e.sort_temp));
+    const int rc = ws_lay(ix, e.w, (int)c.nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, p.sort_n, e.sort_temp, p.n_best);
+    if (rc) return rc;
+    return topk_prologue(ix, c, p, e);
 }
 
 // k > HDB_MAX_K: one query at a time, all scores -> stable radix sort (hdb_sort.hip)
@@ -1177,23 +1196,13 @@ static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
 // p.subset: the same three shapes over the m rows of the index's list (ScanArgs::rows / m) -- the plan is that of a matrix of m
 // rows, "all rows" are the listed ones, no mask (every listed row is kept), the bias unfolded and indexed by the true row; the
 // exact shape collects list positions and rewrites them to rows before finalize.
-static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
-    TopkEnv e;
-    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
-    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
-    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
-    const TopkWs& w = e.w;
-    float* const qinv = w.qinv; float* const qsq = w.qsq; int* const qnan = w.qnan; float* const qscl = w.qscl;
-    uint32_t* const qbits = w.qbits; void* const q16 = w.q16;
-    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
-    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf; float* const kbuf = w.kbuf;
-    const void* Qeff = e.Qeff; const int metric_eff = e.metric_eff; const float* bias_eff = e.bias_eff; const uint8_t* mask_eff = e.mask_eff;
-    const bool small = p.small, exact = p.exact, mfma = p.mfma, fold_small = p.fold_small, f16_queries = p.f16_queries, is_pearson = p.pearson, q16_in_prep = p.q16_in_prep;
-    // float32 rows as bf16 parts in a call that ASKED for the exact selection (hdb_topk_exact: the last resort, status 0 whatever the
-    // queries hold): the parts of an infinite query element cancel to NaN, so the call keeps them -- and the default call's bits --
-    // only while no query holds an infinity.  The preparation above left that per query (qnan & 2); reading it is a stream
-    // synchronisation, paid by exact calls of float32 batches and by no other call.
-    bool f32s = p.f32s;
+// What run_pipeline and hdb_maxsim_host share -- "prepare the queries of a chunk and score them into sbuf" -- in three steps:
+// exact_parts: float32 rows as bf16 parts in a call that ASKED for the exact selection (hdb_topk_exact: the last resort, status 0
+// whatever the queries hold): the parts of an infinite query element cancel to NaN, so the call keeps them -- and the default call's
+// bits -- only while no query holds an infinity.  The preparation left that per query (qnan & 2); reading it is a stream
+// synchronisation, paid by exact calls of float32 batches and by no other call.
+static int exact_parts(hdb_index* ix, const TopkPlan& p, const int* qnan, int32_t nq, hipStream_t st, bool& f32s) {
+    f32s = p.f32s;
     if (f32s && p.exact_req) {
         std::vector<int> h_qnan((size_t)nq);
         HIP_TRY(hipMemcpyAsync(h_qnan.data(), qnan, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1201,21 +1210,54 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         for (int q = 0; q < nq; ++q) f32s = f32s && !(h_qnan[q] & 2);
         if (!f32s) ix->st.f32s = 0;
     }
+    return HDB_OK;
+}
+// chunk_args: the query buffers and scan arguments of the chunk [q0, q0 + cq) of a call of nq queries over n rows (the fp16 copies of
+// all queries are written by the first chunk that needs them)
+static int chunk_args(hdb_index* ix, const TopkPlan& p, const TopkEnv& e, bool f32s, int32_t nq, int q0, int cq, int64_t n, bool& q16_ready,
+                      hipStream_t st, QueryBufs& qb, ScanArgs& a) {
+    const TopkWs& w = e.w;
+    if (p.f16_queries && !q16_ready) { LAUNCH_TRY(hdb_launch_q_to_f16((const float*)e.Qeff, nq, ix->d, w.q16, w.qscl, st)); q16_ready = true; }
+    qb = QueryBufs{w.qinv, w.qsq, w.qbits, p.f16_queries ? w.q16 : e.Qeff, p.f16_queries ? w.qscl : nullptr};
+    base_args(ix, a, e.Qeff, e.metric_eff);
+    if (p.pearson) a.inv_norm = ix->pscale;
+    a.q0 = q0; a.bias = e.bias_eff; a.mask = e.mask_eff; a.f32_split = f32s ? 1 : 0;
+    a.f8_lds = !p.f8_lds ? 0 : ix->opt.f8_lds_waves ? (int)ix->opt.f8_lds_waves : hdb_mfma_f8_lds_auto_waves(cq);
+    a.thr = w.thr; a.cnt = w.cnt; a.cand = w.cand;
+    a.ntiles = (n + p.tile_rows - 1) / p.tile_rows;
+    if (p.subset) { a.rows = ix->rows; a.m = ix->subset_m; a.mask = nullptr; a.bias = ix->bias; }
+    a.ks_partial_out = w.kbuf; a.ks_ld = p.ld_n;       // (K slices only; sample and exact passes index it by their own tile sequence)
+    return HDB_OK;
+}
+// score_chunk: the exact shape's score pass -- every score of the chunk's queries into sbuf[cq][ld_n]
+static int score_chunk(hdb_index* ix, const TopkPlan& p, const ScanArgs& a, const QueryBufs& qb, int cq, float* sbuf, hipStream_t st) {
+    ScanArgs s = a;
+    s.scores = sbuf; s.ld = p.ld_n;
+    prof_begin(ix, st);
+    const int rc = run_scan(ix, s, 0, cq, qb, p.l1tile, p.mfma, st); if (rc) return rc;
+    prof_end(ix, st);
+    return HDB_OK;
+}
+
+static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
+    TopkEnv e;
+    int rc = topk_begin(ix, c, p, e); if (rc) return rc;
+    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
+    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
+    const TopkWs& w = e.w;
+    float* const qsq = w.qsq; int* const qnan = w.qnan;
+    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
+    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf;
+    const bool small = p.small, exact = p.exact, mfma = p.mfma, fold_small = p.fold_small, q16_in_prep = p.q16_in_prep;
+    bool f32s = false;
+    rc = exact_parts(ix, p, qnan, nq, st, f32s); if (rc) return rc;
     const int64_t n = p.subset ? ix->subset_m : ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
-    const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, tile_rows = p.tile_rows, npass = p.npass;
+    const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, npass = p.npass;
     bool q16_ready = q16_in_prep;
     for (int q0 = 0; q0 < nq; q0 += cq_max) {
         const int cq = std::min(cq_max, nq - q0);
-        if (f16_queries && !q16_ready) { LAUNCH_TRY(hdb_launch_q_to_f16((const float*)Qeff, nq, ix->d, q16, qscl, st)); q16_ready = true; }
-        QueryBufs qb{qinv, qsq, qbits, f16_queries ? q16 : Qeff, f16_queries ? qscl : nullptr};
-        ScanArgs a; base_args(ix, a, Qeff, metric_eff);
-        if (is_pearson) a.inv_norm = ix->pscale;
-        a.q0 = q0; a.bias = bias_eff; a.mask = mask_eff; a.f32_split = f32s ? 1 : 0;
-        a.f8_lds = !p.f8_lds ? 0 : ix->opt.f8_lds_waves ? (int)ix->opt.f8_lds_waves : hdb_mfma_f8_lds_auto_waves(cq);
-        a.thr = thr; a.cnt = cnt; a.cand = cand;
-        a.ntiles = (n + tile_rows - 1) / tile_rows;
-        if (p.subset) { a.rows = ix->rows; a.m = ix->subset_m; a.mask = nullptr; a.bias = ix->bias; }
-        a.ks_partial_out = kbuf; a.ks_ld = ld_n;         // (K slices only; sample and exact passes index it by their own tile sequence)
+        QueryBufs qb; ScanArgs a;
+        rc = chunk_args(ix, p, e, f32s, nq, q0, cq, n, q16_ready, st, qb, a); if (rc) return rc;
 
         if (small) {
             if (!fold_small) LAUNCH_TRY(hdb_launch_fill_thr(thr, cnt, cq, -INFINITY, st));
@@ -1239,11 +1281,7 @@ static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
             rc = run_scan(ix, a, 1, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
             prof_end(ix, st);
         } else {
-            ScanArgs s = a;
-            s.scores = sbuf; s.ld = ld_n;
-            prof_begin(ix, st);
-            rc = run_scan(ix, s, 0, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
-            prof_end(ix, st);
+            rc = score_chunk(ix, p, a, qb, cq, sbuf, st); if (rc) return rc;
             if (p.n_best > 0) {
                 // the exact grouped pass: each group's best row keeps its score, every other row joins the masked ones at -inf
                 HIP_TRY(hipMemsetAsync(w.best, 0, (size_t)cq * (size_t)p.n_best * sizeof(unsigned long long), st));      // key 0 is below every real key
@@ -1660,6 +1698,129 @@ extern "C" int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t n
         q = e;
     }
     ix->st.grouped = 1; ix->st.group_k = st_k; ix->st.group_rounds = st_rounds; ix->st.group_exact = st_exact;
+    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HDB_OK;
+}
+
+// ---- multi-vector queries: groups ranked by the sum over a set's vectors of the per-group maxima (hdb_maxsim.hip, hdb_maxsim_plan.h) ----
+// The inverted index of the group ids, built on the first multi-vector call after hdb_index_set_groups and kept until the ids are
+// replaced, cleared or dropped with the matrix.  One synchronisation: the two flag words decide what is built.  Ids that are
+// non-decreasing by row are their own index (grp_sorted): only the offsets are built, grp_rows is not touched.
+static int maxsim_index(hdb_index* ix, hipStream_t st) {
+    if (ix->grp_valid) return HDB_OK;
+    const int64_t n = ix->n, ng = ix->n_groups;
+    if (n > 0xFFFFFFFFll) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: more than 2^32 - 1 rows are not built");
+    HIP_TRY(ix->grp_flags.alloc(2));
+    if ((size_t)ng + 1 > ix->grp_off.cap) HIP_TRY(ix->grp_off.alloc((size_t)(ng + ng / 4 + 64)));
+    DevBuf<uint32_t> keys, keys_out, rows_in;
+    DevBuf<char> temp;
+    HIP_TRY(keys.alloc((size_t)n));
+    HIP_TRY(hipMemsetAsync(ix->grp_flags, 0, 2 * sizeof(int), st));
+    LAUNCH_TRY(hdb_launch_maxsim_keys(ix->groups, n, ng, keys, ix->grp_flags, st));
+    int flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(flags, ix->grp_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const bool sorted = flags[1] == 0;
+    if (sorted) {
+        LAUNCH_TRY(hdb_launch_maxsim_offsets(keys, n, ng, ix->grp_off, st));
+    } else {
+        size_t temp_bytes = 0;
+        LAUNCH_TRY(hdb_maxsim_sort_temp_bytes(n, ng, &temp_bytes));
+        if ((size_t)n > ix->grp_rows.cap) HIP_TRY(ix->grp_rows.alloc((size_t)(n + n / 4 + 64)));
+        HIP_TRY(keys_out.alloc((size_t)n));
+        HIP_TRY(rows_in.alloc((size_t)n));
+        HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 16)));
+        LAUNCH_TRY(hdb_launch_maxsim_iota(rows_in, n, st));       // (the rows enter ascending: the stable sort keeps a group's rows in order)
+        LAUNCH_TRY(hdb_launch_maxsim_sort(temp, temp_bytes, keys, keys_out, rows_in, ix->grp_rows, n, ng, st));
+        LAUNCH_TRY(hdb_launch_maxsim_offsets(keys_out, n, ng, ix->grp_off, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                 // (the temporaries go when this function returns)
+    ix->grp_sorted = sorted; ix->grp_valid = true;
+    return HDB_OK;
+}
+
+extern "C" int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* host_off, int32_t ns, int32_t k, int metric, void* host_record,
+                               void* stream) {
+    // what the numbers alone decide, then the handle, then the device
+    if (ns < 1) return fail(HDB_ERR_ARG, "hdb_maxsim_host: ns (query sets) must be positive");
+    if (k < 1) return fail(HDB_ERR_ARG, "hdb_maxsim_host: k must be at least 1");
+    if (k > HDB_MAX_K) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: k beyond HDB_MAX_K (2048) is not built");
+    if (!host_off) return fail(HDB_ERR_ARG, "hdb_maxsim_host: null argument (host_off)");
+    if (host_off[0] != 0) return fail(HDB_ERR_ARG, "hdb_maxsim_host: host_off[0] must be 0, got " + std::to_string(host_off[0]));
+    for (int32_t s = 0; s < ns; ++s)
+        if (host_off[s + 1] <= host_off[s])
+            return fail(HDB_ERR_ARG, "hdb_maxsim_host: host_off must be strictly increasing: set " + std::to_string(s) + " is empty (host_off " +
+                                         std::to_string(host_off[s]) + " -> " + std::to_string(host_off[s + 1]) + ")");
+    if (!ix || !dev_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_maxsim_host: null argument");
+    if (!ix->groups) return fail(HDB_ERR_ARG, "hdb_maxsim_host: no groups set (hdb_index_set_groups)");
+    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: hamming / jaccard multi-vector calls are not built");
+    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
+        return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: metric not built");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t nv = host_off[ns];
+    const size_t bytes = (size_t)hdb_packed_bytes(ns, k);
+    int rc = ensure_record(ix->rec, bytes);
+    if (rc) return rc;
+    const PackedRec out = packed_view(ix->rec, ns, k);
+    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    if (ix->n == 0) {
+        ix->st = TopkStats(); ix->st.maxsim = 1;
+        rc = run_empty(TopkArgs{dev_Q, ns, k, metric, out.idx, out.score, out.status, st});
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HDB_OK;
+    }
+    rc = maxsim_index(ix, st);
+    if (rc) return rc;
+    // the score pass: the exact shape of run_pipeline for the nv flat vectors, cut by the block / chunk plan
+    int frc = HDB_OK;
+    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
+    TopkPlan p = plan_topk(topk_facts(ix), ix->opt, maxsim_call(nv, k, metric), finite);
+    if (frc != HDB_OK) return frc;
+    if (!maxsim_shape(p)) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: this call has no exact score pass");
+    const int64_t n = ix->n, ng = ix->n_groups;
+    const MaxsimPlan mp = maxsim_plan(n, ng, ns, p.ksplit ? 128 : 256, ix->opt.exact_bytes);
+    p.cq_max = std::min<int>(mp.cq, nv);
+    const int team = ix->opt.maxsim_team ? (int)ix->opt.maxsim_team : hdb_maxsim_team_rule(n, ng);
+    ix->st = p.stats;
+    ix->st.maxsim = 1; ix->st.maxsim_team = team; ix->st.maxsim_sorted = ix->grp_sorted ? 1 : 0;
+    ix->st.maxsim_chunks = maxsim_chunks(mp, host_off, ns); ix->st.chunks = ix->st.maxsim_chunks;
+    MaxsimWs w;
+    rc = ws_lay(ix, w, (int)nv, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, mp.sb, mp.ld_g, (int)ns);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(w.voff, host_off, ((size_t)ns + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TopkEnv e; e.w = w.t; e.sort_temp = 0;
+    const TopkArgs c{dev_Q, nv, k, metric, out.idx, out.score, out.status, st};
+    rc = topk_prologue(ix, c, p, e); if (rc) return rc;
+    bool f32s = false;
+    rc = exact_parts(ix, p, w.t.qnan, nv, st, f32s); if (rc) return rc;
+    LAUNCH_TRY(hdb_launch_maxsim_setnan(w.t.qnan, w.voff, ns, w.snan, st));
+    const uint32_t kk = (uint32_t)std::min<int64_t>(k, ng);
+    bool q16_ready = p.q16_in_prep;
+    for (int32_t s0 = 0; s0 < ns; s0 += mp.sb) {
+        const int32_t sbn = std::min<int32_t>(mp.sb, ns - s0), v_end = host_off[s0 + sbn];
+        int32_t s_cur = s0;
+        for (int32_t v0 = host_off[s0]; v0 < v_end; v0 += p.cq_max) {
+            const int cq = std::min<int32_t>(p.cq_max, v_end - v0);
+            QueryBufs qb; ScanArgs a;
+            rc = chunk_args(ix, p, e, f32s, nv, v0, cq, n, q16_ready, st, qb, a); if (rc) return rc;
+            rc = score_chunk(ix, p, a, qb, cq, w.t.sbuf, st); if (rc) return rc;
+            while (host_off[s_cur + 1] <= v0) ++s_cur;       // the set that holds vector v0
+            LAUNCH_TRY(hdb_launch_maxsim_reduce(w.t.sbuf, p.ld_n, cq, v0, w.voff, s_cur, s0, ix->grp_off, ix->grp_rows, ix->grp_sorted ? 1 : 0, ng,
+                                                w.acc, mp.ld_g, team, st));
+        }
+        // the block's selection: acc is a score matrix of sbn "queries" over n_groups "rows"; ids are group ids (row_base 0)
+        HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)((char*)w.hist - (char*)w.cnt) + (size_t)sbn * 4 * HDB_RADIX_BINS * 4, st));
+        for (int ps = 0; ps < 4; ++ps) LAUNCH_TRY(hdb_launch_hist(w.acc, ng, mp.ld_g, sbn, w.hist, ps, kk, st));
+        LAUNCH_TRY(hdb_launch_collect(w.acc, ng, mp.ld_g, sbn, w.hist, 4, kk, w.cnt, w.cand, HDB_CAND_CAP, w.tie_info, st));
+        LAUNCH_TRY(hdb_launch_finalize(w.cand, w.cnt, HDB_CAND_CAP, sbn, (uint32_t)k, kk, 0, out.idx + (int64_t)s0 * k, out.score + (int64_t)s0 * k,
+                                       out.status + s0, w.snan + s0, (int)ix->opt.finalize_threads, 0, st));
+        // (groups at -inf are never returned: padding; a bad group id anywhere in the index marks every set)
+        LAUNCH_TRY(hdb_launch_group_finish(out.idx + (int64_t)s0 * k, out.score + (int64_t)s0 * k, sbn, k, out.status + s0, ix->grp_flags, st));
+    }
     HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HDB_OK;

@@ -544,3 +544,20 @@ static inline int hdb_qb_scan_blocks(int64_t ntiles, int nq, int cus, int max_bl
 }
 // slots of wstat every query has after a MODE 0 launch of that many workgroups
 static inline int64_t hdb_qb_slots(int blocks, int nq) { int wq, nqt; qb_shape(nq, wq, nqt); return (int64_t)blocks * (4 / wq) * 4; }
+
+// ---- hdb_maxsim.hip: multi-vector queries ----
+// Lanes that own one group in the reduction (hdb_maxsim_reduce_kernel<TEAM>), from the mean group size n / n_groups: a team reads
+// its group's rows TEAM at a time, so a team wider than the group idles lanes and a team far narrower walks it alone.  The steps were
+// derived -- a lane takes about four rows of a mean group -- and then measured (tools/time_maxsim.py, profiles/maxsim_time.txt, one
+// device, cosine top-10, p50 of 60 calls in us, team 1 / 4 / 16 / 64; the rule's choice in brackets):
+//   10M x 128 fp16, groups of 100, 32 vectors:      2 518 / 1 798 / [1 659] / 1 874        8 sets: 16 717 / 10 743 / [9 682] / 11 283
+//   2M x 384 fp32, groups of 4, 4 vectors:          [602] / 614 / 651 / 804
+//   2M x 384 fp16, every row a group, 8 vectors:    [399] / 458 / 705 / 1 776
+//   2M x 384 fp16, groups of 4 shuffled, 4 vectors: [464] / 479 / 484 / 644
+//   200k x 384 fp16, ONE group, 4 vectors:          50 924 / 15 361 / 6 909 / [1 928]      (one team walks all rows: not split, see the header's Not-built list)
+// In every measured shape the rule's team is the fastest; sizes between the steps (mean 5 .. 50, 100 .. 200k) are
+// not measured.  The option maxsim_team fixes the team for such runs.
+static inline int hdb_maxsim_team_rule(int64_t n, int64_t n_groups) {
+    const int64_t mean = n_groups > 0 ? n / n_groups : n;
+    return mean <= 4 ? 1 : mean <= 32 ? 4 : mean <= 256 ? 16 : 64;
+}

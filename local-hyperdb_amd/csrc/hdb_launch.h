@@ -184,6 +184,22 @@ int hdb_launch_group_demote(float* scores, int64_t n, int64_t ld, int nq, const 
                             const unsigned long long* best, int* bad, void* stream);
 int hdb_launch_group_finish(int64_t* idx, const float* score, int nq, int k, int32_t* status, const int* bad, void* stream);
 
+// ---- hdb_maxsim.hip: multi-vector queries (sum over a set's vectors of the per-group maxima) ----
+// keys / sort / offsets: the inverted index of the group ids -- keys [n] (an id outside [0, n_groups) becomes n_groups and raises
+// flags[0]; keys that decrease somewhere raise flags[1]), iota: rows = 0 .. n - 1, the stable sort of the pairs, and
+// grp_off [n_groups + 1].  reduce: one launch per chunk of cq vectors (v0 = the first one, s_first = its set, s_base = the first set
+// of acc [sets][ld_g]); team = 1 | 4 | 16 | 64 lanes per group.  setnan: snan[s] = a vector of set s holds a NaN.
+int hdb_maxsim_sort_temp_bytes(int64_t n, int64_t n_groups, size_t* bytes);
+int hdb_launch_maxsim_keys(const int32_t* groups, int64_t n, int64_t n_groups, uint32_t* keys, int* flags, void* stream);
+int hdb_launch_maxsim_iota(uint32_t* rows, int64_t n, void* stream);
+int hdb_launch_maxsim_sort(void* temp, size_t temp_bytes, uint32_t* keys_in, uint32_t* keys_out, uint32_t* rows_in, uint32_t* rows_out,
+                           int64_t n, int64_t n_groups, void* stream);
+int hdb_launch_maxsim_offsets(const uint32_t* keys, int64_t n, int64_t n_groups, uint32_t* grp_off, void* stream);
+int hdb_launch_maxsim_setnan(const int* qnan, const int32_t* voff, int ns, int* snan, void* stream);
+int hdb_launch_maxsim_reduce(const float* sbuf, int64_t ld_n, int cq, int32_t v0, const int32_t* voff, int32_t s_first, int32_t s_base,
+                             const uint32_t* grp_off, const uint32_t* grp_rows, int sorted, int64_t n_groups, float* acc, int64_t ld_g,
+                             int team, void* stream);
+
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);

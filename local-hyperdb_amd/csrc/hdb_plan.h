@@ -65,6 +65,7 @@ struct hdb_options {
     int64_t rerank_chunk = 0;         // hdb_rerank: queries per chunk (0: up to HDB_RERANK_MAXQ); the plan of hdb_topk does not read it
     int64_t group_oversample = 4;     // hdb_topk_grouped_host: the first fast round collapses the top k * group_oversample (1 .. 64; rank_two_stage's default, not measured)
     int64_t group_fast_rounds = 2;    // ... fast rounds at most (0 .. 2); 0: always the exact grouped pass.  The plan of hdb_topk reads neither (hdb_group_plan.h)
+    int64_t maxsim_team = 0;          // hdb_maxsim_host: lanes that own one group in its reduction (0: the rule, hdb_maxsim_team_rule; 1 | 4 | 16 | 64 = fixed, A/B runs and tests); changes no answer
 };
 #define HDB_RERANK_MAXQ 256
 
@@ -80,7 +81,8 @@ struct TopkFacts {
     int64_t subset_m;                 // rows of the list set beside the mask (hdb_index_set_row_subset), 0 = none
 };
 // n_groups > 0: the exact grouped pass of hdb_topk_grouped_host (exact is set as well); 0 for every other call
-struct TopkCall { int32_t nq, k; int metric; bool has_status, exact; int64_t n_groups; };
+// maxsim: the score pass of hdb_maxsim_host (hdb_maxsim_plan.h; exact is set as well): the exact shape on every matrix size, all rows
+struct TopkCall { int32_t nq, k; int metric; bool has_status, exact; int64_t n_groups; bool maxsim = false; };
 
 // ---- what it answers ------------------------------------------------------------------------------------------------------------
 enum TopkPath {
@@ -95,7 +97,8 @@ enum TopkPath {
 };
 // statistics of one call (hdb_get_stat); every call writes all of them
 struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0;
-                   int64_t grouped = 0, group_k = 0, group_rounds = 0, group_exact = 0; };      // hdb_topk_grouped_host writes these four behind its last inner call
+                   int64_t grouped = 0, group_k = 0, group_rounds = 0, group_exact = 0;        // hdb_topk_grouped_host writes these four behind its last inner call
+                   int64_t maxsim = 0, maxsim_chunks = 0, maxsim_team = 0, maxsim_sorted = 0; };      // hdb_maxsim_host writes these four behind its plan's
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
@@ -310,8 +313,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // A list call is the same call on a matrix of the m listed rows with the matrix cores and the single launches off: the plan of
     // those facts, taken while it is the multi-kernel pipeline (k > HDB_MAX_K on more than HDB_CAND_CAP listed rows keeps the mask).
     // Its extents, sample plan and statistics are the inner plan's; the executor reads the rows through the list.
-    // (the exact grouped pass indexes its score buffer by row: it keeps the mask)
-    if (c.n_groups <= 0 && subset_rule(ix, o, c)) {
+    // (the exact grouped pass indexes its score buffer by row: it keeps the mask; the multi-vector reduction likewise)
+    if (c.n_groups <= 0 && !c.maxsim && subset_rule(ix, o, c)) {
         TopkFacts in{};
         in.n = ix.subset_m; in.d = ix.d; in.dtype = ix.dtype; in.qmode = HDB_QUANT_NONE; in.has_bias = ix.has_bias; in.cus = ix.cus;
         hdb_options oin = o;
@@ -333,7 +336,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // The exact grouped pass needs every score in a buffer, so a matrix of up to HDB_CAND_CAP rows takes the exact shape too -- on
     // the VALU scan, which is what such a matrix runs on in every other call (`tiny`).  small == tiny wherever n_groups is 0.
     const bool tiny = n <= HDB_CAND_CAP;
-    const bool small = tiny && c.n_groups <= 0;
+    const bool small = tiny && c.n_groups <= 0 && !c.maxsim;      // (the multi-vector score pass: the same, hdb_maxsim_plan.h)
     // bit metrics tie massively by construction; the sampled threshold still works while the rows at and above its
     // level fit the candidate list (random data: yes), and the status word sends the rest through the exact path
     const bool exact_req = c.exact;                          // the caller asked for the exact selection (tests; the re-run of a failed call)
@@ -388,6 +391,11 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int64_t b1_first = b1_mfma_first_q(o, ix.dtype, ix.d);
     const bool b1_call = b1_first > 0 && nq >= b1_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
     bool mfma = o.use_mfma && !is_ham && !small && !tiny && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
+    // The matrix cores score euclidean through ||v||^2 + ||q||^2 - 2 v.q, which cancels where v is close to q; every other call
+    // re-scores its few candidates directly (hdb_launch_rescore_euclid).  The multi-vector reduction consumes EVERY score of the pass,
+    // and the near-duplicate of a query vector is exactly the row a group's maximum picks: its euclidean score pass stays on the VALU
+    // scan, which sums the differences themselves.
+    if (c.maxsim && metric == HDB_EUCLIDEAN) mfma = false;
     // bfloat16 rows meet three query parts, two of them zero where the query is a bf16 number: a row holding inf would give
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)

@@ -80,6 +80,25 @@ struct TopkWs {
     }
 };
 
+// hdb_maxsim_host: the main pipeline's layout for the call's nq flat vectors in chunks of cq (exact shape: ld_scores = all rows), then
+// the running sums of a block of sb sets, acc [sb][ld_g], the call's set offsets and per-set NaN words on the device, and the
+// selection's buffers for sb sets (cnt and hist neighbours, as in TopkWs: one memset clears both).
+struct MaxsimWs {
+    TopkWs t;
+    float* acc; int32_t* voff; int* snan;
+    uint32_t* cnt; uint32_t* hist; uint32_t* tie_info; unsigned long long* cand;
+    void lay(Bump& b, int nq, int d, int W, int cq, int64_t ld_scores, int64_t ld_ks, int sb, int64_t ld_g, int ns) {
+        t.lay(b, nq, d, W, cq, ld_scores, ld_ks, 0, 0, 0);
+        acc = b.take<float>((size_t)sb * (size_t)ld_g);
+        voff = b.take<int32_t>((size_t)ns + 1);
+        snan = b.take<int>((size_t)ns);
+        cnt = b.take<uint32_t>((size_t)sb * HDB_CNT_STRIDE);
+        hist = b.take<uint32_t>((size_t)sb * 4 * HDB_RADIX_BINS);
+        tie_info = b.take<uint32_t>((size_t)sb * 4);
+        cand = b.take<unsigned long long>((size_t)sb * HDB_CAND_CAP);
+    }
+};
+
 // hdb_rerank: per-query words of the whole call, then the buffers of one chunk of cq queries.  m: the caller's list length -- the
 // prepared lists (valid, ascending, unique local rows) have that leading dimension; the packed entries keep the leading dimension
 // HDB_CAND_CAP the finalize kernel is launched with.  pearson: the centred queries.

@@ -51,6 +51,7 @@ EXPORTS = (
     "hdb_index_quantize", "hdb_debug_quant_bounds", "hdb_index_set_row_subset",
     "hdb_rerank", "hdb_rerank_host", "hdb_two_stage_host",
     "hdb_index_set_groups", "hdb_topk_grouped_host", "hdb_collapse_groups",
+    "hdb_maxsim_host",
 )
 
 
@@ -102,6 +103,7 @@ def _load():
     lib.hdb_index_set_groups.argtypes = [vp, vp, i64]
     lib.hdb_topk_grouped_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_collapse_groups.argtypes = [vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp, ctypes.c_int, vp]
+    lib.hdb_maxsim_host.argtypes = [vp, vp, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_merge_topk_packed.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_host.argtypes = [vp, i32, i32, i32, vp]
     lib.hdb_host_exchange_merge.argtypes = [vp, i64, i32, i32, ctypes.c_uint64, vp, i32, i32, vp, ctypes.c_double]
@@ -709,6 +711,29 @@ class GpuIndex:
             raise ValueError(NAN_MESSAGE)
         return slot[2].copy(), slot[3].copy()
 
+    def maxsim(self, Q, offsets, k, metric_id):
+        """Multi-vector queries (hdb_maxsim_host): ``Q`` the flat ``[nv, d]`` vectors of ``ns`` sets, set ``s`` = rows
+        ``offsets[s] .. offsets[s + 1]`` (``pack_query_sets`` makes both) -> numpy ``(group ids [ns, k] int64, scores [ns, k]
+        float32)`` (copies): the groups by the sum over the set's vectors of each vector's best row in the group, score descending,
+        group id ascending; ``-1`` / ``-inf`` where fewer than k groups have an eligible row for every vector.  The status words of
+        the call stay in ``maxsim_status`` (Q_BADROW: a group id outside ``[0, n_groups)``).  Needs set_groups (ValueError
+        otherwise); a NaN vector raises ValueError; hamming / jaccard and k > 2048: NotImplementedError."""
+        qt = self._query_tensor(Q, batched=True)
+        off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int32).reshape(-1)
+        ns, k = int(off.size) - 1, int(k)
+        if ns < 1 or k < 1:
+            raise ValueError("maxsim: need at least one query set and k >= 1")
+        if int(off[-1]) != int(qt.shape[0]):
+            raise ValueError(f"maxsim: offsets end at {int(off[-1])}, the flat matrix holds {int(qt.shape[0])} vectors")
+        slot = self._record_slot(ns, k) if k <= HDB_MAX_K else (None, None)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_maxsim_host(self._h, ctypes.c_void_p(qt.data_ptr()), off.ctypes.data_as(ctypes.c_void_p), ns, k, int(metric_id),
+                                        ctypes.c_void_p(slot[1]), _stream_ptr(self.device)), "hdb_maxsim_host")
+        self.maxsim_status = slot[4].copy()
+        if (slot[4] & Q_NAN).any():
+            raise ValueError(NAN_MESSAGE)
+        return slot[2].copy(), slot[3].copy()
+
     # -- options / stats -----------------------------------------------------------------------
     def set_option(self, name, value):
         """An option of the index by its C name (include/hyperdb_hip.h lists them), e.g. ``set_option("b1_mfma_min_q", 5)``: a
@@ -1052,6 +1077,96 @@ def collapse_groups_host(idx, scores, groups, k, row_base=0):
         if found < k and not pad and m < n:
             status[q] |= Q_GROUPS_SHORT
     return out_i, out_s, status
+
+
+def pack_query_sets(x, d):
+    """Query sets -> ``(flat float32 [nv, d], int32 offsets [ns + 1])`` for ``GpuIndex.maxsim``.  ``x``: a ``(T, d)`` array (one
+    set), an ``(S, T, d)`` array (S sets of T vectors) or a list of ``(T_i, d)`` arrays (ragged sets).  ValueError for an empty set, no
+    set at all or a width other than ``d``."""
+    d = int(d)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if isinstance(x, np.ndarray) and x.dtype != object:
+        if x.ndim == 2:
+            sets = [x]
+        elif x.ndim == 3:
+            sets = [x[i] for i in range(x.shape[0])]
+        else:
+            raise ValueError(f"query sets must be (T, d), (S, T, d) or a list of (T_i, d) arrays, got shape {tuple(x.shape)}")
+    else:
+        sets = [t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in x]
+    if not sets:
+        raise ValueError("query sets: need at least one set")
+    flat, off = [], [0]
+    for i, t in enumerate(sets):
+        if t.ndim != 2:
+            raise ValueError(f"query set {i} must be a (T, {d}) array, got shape {tuple(t.shape)}")
+        if t.shape[0] == 0:
+            raise ValueError(f"query set {i} is empty: a set needs at least one vector")
+        if t.shape[1] != d:
+            raise ValueError(f"query set {i} has width {t.shape[1]}, the index has {d}")
+        flat.append(np.asarray(t, dtype=np.float32))
+        off.append(off[-1] + int(t.shape[0]))
+    return np.ascontiguousarray(np.concatenate(flat, axis=0)), np.asarray(off, dtype=np.int32)
+
+
+def _host_scores(V, q, metric):
+    """float64 scores of one vector against the rows of V, by the metric's definition (the models' side of a comparison)."""
+    V = np.asarray(V, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if metric == "dot_product":
+            return V @ q
+        if metric == "cosine_similarity":
+            return (V @ q) / (np.linalg.norm(V, axis=1) * np.linalg.norm(q))
+        if metric == "euclidean_metric":
+            return 1.0 / (1.0 + np.linalg.norm(V - q, axis=1))
+        if metric == "manhattan_distance":
+            return 1.0 / (1.0 + np.abs(V - q).sum(axis=1))
+        if metric == "pearson_correlation":
+            Vc = V - V.mean(axis=1, keepdims=True)
+            qc = q - q.mean()
+            return (Vc @ qc) / (np.linalg.norm(Vc, axis=1) * np.linalg.norm(qc))
+    raise ValueError(f"maxsim_host: metric {metric!r} has no multi-vector model")
+
+
+def maxsim_host(V, query_sets, groups, k, metric, bias=None, mask=None, n_groups=None):
+    """The contract of hdb_maxsim_host in numpy, float64: ``(group ids [ns, k] int64, scores [ns, k] float64)``.  For every set the
+    group score is the sum over the set's vectors, in vector order, of the maximum over the group's eligible rows of (score + bias); a
+    row the mask excludes, a NaN score or a group id outside ``[0, n_groups)`` is ``-inf``; a group without an eligible row, or with a
+    term at ``-inf``, scores ``-inf`` and is never returned.  Order: score descending, group id ascending; tail ``-1`` / ``-inf``."""
+    V = np.asarray(V)
+    n = int(V.shape[0])
+    flat, off = pack_query_sets(query_sets, V.shape[1])
+    flat = flat.astype(np.float64)
+    g = np.asarray(groups).astype(np.int64).reshape(-1)
+    if g.size != n:
+        raise ValueError(f"maxsim_host: group ids must have one entry per row ({n}), got {g.size}")
+    ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if n else 0)
+    ok = (g >= 0) & (g < ng)
+    if mask is not None:
+        ok &= np.asarray(mask).reshape(-1) != 0
+    b = np.zeros(n) if bias is None else np.asarray(bias, dtype=np.float64).reshape(-1)
+    k = int(k)
+    ns = int(off.size) - 1
+    out_i = np.full((ns, k), -1, dtype=np.int64)
+    out_s = np.full((ns, k), -np.inf, dtype=np.float64)
+    gi = g[ok]
+    for s in range(ns):
+        total = None
+        for v in range(int(off[s]), int(off[s + 1])):
+            x = _host_scores(V, flat[v], metric) + b
+            x = np.where(np.isnan(x), -np.inf, x)[ok]
+            best = np.full(ng, -np.inf)
+            np.maximum.at(best, gi, x)
+            with np.errstate(invalid="ignore"):
+                total = best if total is None else total + best
+        total = np.where(np.isnan(total), -np.inf, total)
+        order = np.lexsort((np.arange(ng), -total))
+        order = order[total[order] > -np.inf][:k]
+        out_i[s, :order.size] = order
+        out_s[s, :order.size] = total[order]
+    return out_i, out_s
 
 
 def collapse_groups(idx, scores, groups, k, n_groups=None, row_base=0):

@@ -53,7 +53,7 @@ import torch
 
 from . import ranking_algorithm as ranking
 from . import _native
-from ._native import GpuIndex, METRIC_IDS
+from ._native import GpuIndex, METRIC_IDS, pack_query_sets
 from .group import GpuGroup
 
 __all__ = ["HyperDB"]
@@ -763,6 +763,65 @@ class HyperDB:
         the key.  ``group_by=None`` is :meth:`query` exactly.  One device only (NotImplementedError with ``devices=[...]``).
         (:meth:`query` itself keeps the reference's parameter list; :meth:`query_batch` takes ``group_by`` as its last keyword.)"""
         return self._query_one(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)
+
+    def _group_key(self, group_by, doc):
+        """What a group is called in the results of :meth:`query_multi`: the ``source_indices`` entry, or the metadata value -- ``None``
+        for a document that is a group of its own.  ``doc``: any member of the group."""
+        if group_by == "source":
+            return self.source_indices[doc]
+        d = self.documents[doc]
+        return self.get_nested_value(d, group_by.split('.')) if isinstance(d, dict) else None
+
+    def _multi_results(self, group_by, codes, gids, scores, keep, return_similarities):
+        """Group codes of one answer of GpuIndex.maxsim -> ``[(group_key, score, documents)]``.  ``codes``: one code per device row
+        (_group_codes); ``keep``: the filter's bool array over documents or None.  Host only."""
+        doc_codes = np.asarray(codes)[self._live_rows()]
+        out = []
+        for g, s_ in zip(np.asarray(gids).tolist(), np.asarray(scores).tolist()):
+            if g < 0:                                    # fewer than k groups exist: the tail is padded with -1
+                break
+            members = np.flatnonzero(doc_codes == g)
+            if keep is not None:
+                members = members[np.asarray(keep)[members]]
+            key = self._group_key(group_by, int(members[0]))
+            out.append((key, float(s_), [self.documents[i] for i in members.tolist()]) if return_similarities else key)
+        return out
+
+    def query_multi(self, query_inputs, group_by="source", top_k=5, return_similarities=True, filters=None, metric='cosine_similarity'):
+        """Additive: one question asked as a SET of vectors -- several paraphrases, the token vectors of a late-interaction model --
+        answered by groups of documents.  ``query_inputs`` is what :meth:`query_batch` takes, read as one set of T vectors;
+        ``group_by`` as in :meth:`query_grouped`.  A group's score is the sum over the T vectors of the best score any of its
+        documents that pass ``filters`` has for that vector; the ``top_k`` best groups come back as ``(group_key, score, documents)``
+        -- the ``source_indices`` entry or the metadata value (``None`` for a document that is a group of its own), and the group's
+        live documents that pass the filters, in store order -- or as ``[group_key, ...]`` with ``return_similarities=False``.
+        No recency (a bias would enter every term, T times), not cached, one device only (NotImplementedError with
+        ``devices=[...]``)."""
+        if self._index is None or not self.documents:
+            raise Exception("The database is empty. Cannot proceed with the query.")
+        if metric not in _METRICS:
+            raise ValueError(f"Invalid metric '{metric}'. Supported: " + ", ".join(f"'{m}'" for m in _METRICS))
+        ranking._validate_metric(metric)
+        ix = self._index
+        if isinstance(ix, GpuGroup):
+            raise NotImplementedError("query_multi on several devices is not built: a group can span shards")
+        Q = self._query_vectors(query_inputs)
+        if ix.has_nan or bool(np.isnan(Q).any()):
+            raise ValueError(ranking.NAN_MESSAGE)
+        masks, n_avail, keep, lists = self._mask_for(filters)
+        if n_avail == 0:
+            print("INFO: No document matches your query with the brute-force method and the current filters.")
+            return []
+        codes, n_groups = self._groups_for(group_by)
+        flat, off = pack_query_sets(np.asarray(Q), Q.shape[1])
+        try:
+            ix.set_row_mask(None if masks is None else masks[0])
+            ix.set_bias(None)
+            ix.set_groups(codes, n_groups)
+            gids, sc = ix.maxsim(flat, off, max(1, min(int(top_k), n_groups)), METRIC_IDS[metric])
+        finally:
+            ix.set_row_mask(None)
+            ix.set_groups(None)
+        return self._multi_results(group_by, codes.cpu().numpy(), gids[0], sc[0], keep, return_similarities)
 
     def _query_one(self, query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by):
         key = self._hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)

@@ -29,14 +29,14 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import GpuIndex, METRIC_IDS, NAN_MESSAGE
+from ._native import GpuIndex, METRIC_IDS, NAN_MESSAGE, pack_query_sets
 from .group import GpuGroup
 
 __all__ = [
     "get_norm_vector", "dot_product", "cosine_similarity", "euclidean_metric", "manhattan_distance",
     "jaccard_similarity", "pearson_correlation", "check_and_binarize_vectors", "hamming_distance",
     "hyperDB_ranking_algorithm_sort", "rank_batch", "register_vectors", "ResidentVectors",
-    "rerank_batch", "rank_two_stage", "rank_grouped",
+    "rerank_batch", "rank_two_stage", "rank_grouped", "rank_maxsim",
 ]
 
 _GPU_METRICS = tuple(METRIC_IDS)      # all seven metrics of the reference's dispatch table have kernels
@@ -455,6 +455,44 @@ def rank_grouped(vectors, query_vectors, groups, top_k=5, metric='cosine_similar
         idx = idx.astype(np.int64)
         gid = np.where(idx >= 0, gh[np.clip(idx - ix.row_base, 0, ix.n - 1)], -1)
         return idx, sc.astype(np.float64), gid
+    finally:
+        if owned:
+            ix.close()
+
+
+def rank_maxsim(vectors, query_sets, groups=None, top_k=5, metric='cosine_similarity'):
+    """Additive: multi-vector queries -- groups ranked by the sum over a set's vectors of each vector's best row in the group (late
+    interaction over token / patch vectors; fusion of several paraphrases of one question over the chunks of documents).
+
+    ``query_sets`` is a ``(T, d)`` array (one set), an ``(S, T, d)`` array or a list of ``(T_i, d)`` arrays; ``groups`` one integer
+    id per row, ``None`` = every row its own group (the rows ranked by their summed scores).  Returns ``(int64 (S, k) group ids,
+    float64 (S, k) scores)``, ``k = min(top_k, n_groups)``, score descending, group id ascending; where fewer than k groups have an
+    eligible row for every vector the tail is ``-1`` / ``-inf``.  A bias set on the handle enters every term, so T times in all.
+    ``vectors`` is a registered handle on one device or a raw matrix registered for the call; sharded and group handles raise
+    NotImplementedError, and so do hamming and jaccard and ``top_k`` beyond 2048."""
+    if isinstance(vectors, ResidentVectors) and not isinstance(vectors.index, GpuIndex) or isinstance(vectors, GpuGroup):
+        raise NotImplementedError("rank_maxsim: needs an index on one device; a group of rows can span the shards of a sharded handle")
+    ix, _, owned = _resolve(vectors)
+    try:
+        if not isinstance(ix, GpuIndex):
+            raise NotImplementedError("rank_maxsim: needs an index on one device; a group of rows can span the shards of a sharded handle")
+        flat, off = pack_query_sets(query_sets, ix.d)
+        if ix.has_nan or np.isnan(flat).any():
+            raise ValueError(NAN_MESSAGE)
+        _validate_metric(metric)
+        if ix.n == 0:
+            raise ValueError("vectors is empty")
+        ns = int(off.size) - 1
+        ids = np.arange(ix.n, dtype=np.int32) if groups is None else groups
+        ix.set_groups(ids)
+        try:
+            k = max(0, min(int(top_k), ix.n_groups))
+            if k == 0:
+                return np.zeros((ns, 0), np.int64), np.zeros((ns, 0), np.float64)
+            gid, sc = ix.maxsim(flat, off, k, METRIC_IDS[metric])
+        finally:
+            ix.set_groups(None)
+        return gid.astype(np.int64), sc.astype(np.float64)
     finally:
         if owned:
             ix.close()
