@@ -2,7 +2,7 @@
 //
 // hdb_topk = validate, plan, execute (topk_impl).  Which path a call takes is decided in ONE place, plan_topk (hdb_plan.h), a pure
 // function that sees plain facts and no hdb_index; its TopkPlan carries everything the executors here consume and the statistics of
-// the call (ix->st = plan.stats, the only place they are written).  One executor per path: quant_topk, quant_batch_topk,
+// the call (stats_begin stores plan.stats; nothing else starts a call's statistics).  One executor per path: quant_topk, quant_batch_topk,
 // run_fused, run_bits1, run_batch1, run_full_sort, run_pipeline -- launches, workspace layouts and ensure_* calls, no rule.
 //
 // The multi-kernel pipeline (run_pipeline) for a chunk of queries (everything enqueued on the caller's stream):
@@ -14,6 +14,9 @@
 // hdb_topk_exact: scan(scores) over all rows -> 4 histogram passes -> collect (+ordered ties)
 //                 -> finalize.  Used for hamming (integer scores, massive ties), for queries whose
 //                 sampled threshold failed, and by tests as the on-device cross-check.
+// Written once for all ranking calls (tests/test_host_calls_once.py): plan_call + stats_begin, select_exact (the radix selection),
+// single_launch (the timing bracket of a one-launch pipeline); for the *_host calls HostRec (the device record and its way back),
+// rerun_flagged (the exact re-run of queries whose sampled threshold failed), query_pitch, ranking_metric / ranking_k (argument checks).
 #include "hdb_common.h"
 #include "hdb_quant.h"
 #include "hdb_ws.h"
@@ -160,6 +163,24 @@ static int ensure_record(DevBuf<char>& rec, size_t bytes) {
     HIP_TRY(rec.alloc(bytes * 2));
     return HDB_OK;
 }
+// The record of a *_host call.  open: the device record in `buf` (rec or rec1 of an index), grown as needed, and `view`, the three
+// arrays the kernels write; direct (hdb_topk_host alone asks): the caller's record is pinned, device-visible memory and the kernels
+// write it themselves -- no device record, no copy.  close: the copy to the caller unless direct, then (wait) the stream's completion.
+struct HostRec { void* host_record; char* dev; size_t bytes; bool direct; PackedRec view; };
+static int hostrec_open(DevBuf<char>& buf, int32_t nq, int32_t k, void* host_record, bool direct, HostRec& r) {
+    r.host_record = host_record; r.dev = static_cast<char*>(host_record); r.bytes = (size_t)hdb_packed_bytes(nq, k); r.direct = direct;
+    if (!direct) {
+        const int rc = ensure_record(buf, r.bytes); if (rc) return rc;
+        r.dev = buf;
+    }
+    r.view = packed_view(r.dev, nq, k);
+    return HDB_OK;
+}
+static int hostrec_close(const HostRec& r, hipStream_t st, bool wait = true) {
+    if (!r.direct) HIP_TRY(hipMemcpyAsync(r.host_record, r.dev, r.bytes, hipMemcpyDeviceToHost, st));
+    if (wait) HIP_TRY(hipStreamSynchronize(st));
+    return HDB_OK;
+}
 
 // What a change of the matrix invalidates, stated once (create, update, extend, gather).  kept_rows: the rows that are the old
 // matrix's still -- 0, or the old n of an append, where the next hamming / pearson call packs the appended rows only.
@@ -196,6 +217,8 @@ static double quant_gamma_m(int d) { return (double)(d + 8) * std::ldexp(1.0, -2
 static double quant_gamma_rows(int d) { return std::max(quant_gamma(d), quant_gamma_m(d)); }
 // bytes of one stored row (hdb_row_bytes, hdb_common.h: the one source of every row pitch)
 static size_t row_pitch(const hdb_index* ix) { return (size_t)hdb_row_bytes(ix->dtype, ix->d); }
+// bytes of one query: float64 against a float64 matrix, float32 against every other storage
+static size_t query_pitch(const hdb_index* ix) { return (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4); }
 #define HDB_QSTAT_WORDS 4
 // the device words of hdb_index::qstat, zeroed on `st`; qstat stays null when the allocation itself fails
 static hipError_t qstat_alloc(hdb_index* ix, hipStream_t st) {
@@ -698,6 +721,17 @@ static void prof_end(hdb_index* ix, hipStream_t st) {
     (void)hipEventRecord(ix->ev_pool[ix->ev_used + 1], st);
     ix->ev_used += 2;
 }
+// The bracket round the launch of a single-launch pipeline: the profile's events outside, the two clock reads of hdb_topk_host's
+// timing tight round the launch call.  `launch` returns the launcher's code, handed on as it stands (a failed launch ends no event pair).
+template <typename Launch>
+static inline int single_launch(hdb_index* ix, hipStream_t st, Launch&& launch) {
+    prof_begin(ix, st);
+    ix->ht_l0 = std::chrono::steady_clock::now();
+    const int e = launch();
+    ix->ht_l1 = std::chrono::steady_clock::now();
+    if (e == 0) prof_end(ix, st);
+    return e;
+}
 
 static bool metric_ok(int metric) { return metric >= HDB_DOT && metric <= HDB_EUCLIDEAN_DIST; }
 
@@ -1123,11 +1157,7 @@ static int run_fused(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     fa.cand = e.w.cand; fa.cap = HDB_CAND_CAP; fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
     fa.idx_out = c.idx; fa.score_out = c.score; fa.status = c.status; fa.thr_out = e.w.thr;
     fa.local = p.local ? 1 : 0; fa.local_slot = p.local_slot; fa.local_m = p.local_m;
-    prof_begin(ix, c.st);
-    ix->ht_l0 = std::chrono::steady_clock::now();
-    LAUNCH_TRY(hdb_launch_mfma_fused(&a, ix->dtype, &fa, (int)ix->opt.max_blocks, c.st));
-    ix->ht_l1 = std::chrono::steady_clock::now();
-    prof_end(ix, c.st);
+    LAUNCH_TRY(single_launch(ix, c.st, [&] { return hdb_launch_mfma_fused(&a, ix->dtype, &fa, (int)ix->opt.max_blocks, c.st); }));
     return HDB_OK;
 }
 
@@ -1150,11 +1180,7 @@ static int run_bits1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         ba.ctl = reinterpret_cast<uint32_t*>(ix->bctl.p);
         ba.cand = e.w.cand; ba.cap = HDB_CAND_CAP; ba.k = (uint32_t)c.k; ba.kk = p.kk; ba.row_base = ix->row_base;
         ba.idx_out = c.idx + (int64_t)q0 * c.k; ba.score_out = c.score + (int64_t)q0 * c.k; ba.status = c.status + q0;
-        prof_begin(ix, c.st);
-        ix->ht_l0 = std::chrono::steady_clock::now();
-        LAUNCH_TRY(hdb_launch_bits_fused(&ba, c.metric == HDB_JACCARD ? 1 : 0, (int)ix->opt.max_blocks, c.st));
-        ix->ht_l1 = std::chrono::steady_clock::now();
-        prof_end(ix, c.st);
+        LAUNCH_TRY(single_launch(ix, c.st, [&] { return hdb_launch_bits_fused(&ba, c.metric == HDB_JACCARD ? 1 : 0, (int)ix->opt.max_blocks, c.st); }));
     }
     return HDB_OK;
 }
@@ -1182,11 +1208,9 @@ static int run_batch1(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         fa.ctl = reinterpret_cast<uint32_t*>(ix->bctl.p);
         fa.k = (uint32_t)c.k; fa.kk = p.kk; fa.row_base = ix->row_base;
         fa.idx_out = c.idx + (int64_t)q0 * c.k; fa.score_out = c.score + (int64_t)q0 * c.k; fa.status = c.status + q0;
-        prof_begin(ix, c.st);
-        ix->ht_l0 = std::chrono::steady_clock::now();
-        LAUNCH_TRY(hdb_launch_mfma_scan(&a, ix->dtype, 2, cq, nullptr, ix->sqnorm, nullptr, nullptr, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, c.st, &fa));
-        ix->ht_l1 = std::chrono::steady_clock::now();
-        prof_end(ix, c.st);
+        LAUNCH_TRY(single_launch(ix, c.st, [&] {
+            return hdb_launch_mfma_scan(&a, ix->dtype, 2, cq, nullptr, ix->sqnorm, nullptr, nullptr, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, c.st, &fa);
+        }));
     }
     return HDB_OK;
 }
@@ -1238,73 +1262,87 @@ static int score_chunk(hdb_index* ix, const TopkPlan& p, const ScanArgs& a, cons
     prof_end(ix, st);
     return HDB_OK;
 }
+// select_exact: the exact selection over a score matrix -- scores[cq][ld], n entries each -- into cand / cnt: npass radix-histogram
+// passes fix each query's kk-th largest score, collect gathers what lies above it and the ordered ties.
+// cnt and hist are neighbours in the workspace, cnt first (TopkWs, MaxsimWs; hdb_ws.h): one memset clears both.
+static int select_exact(const float* scores, int64_t n, int64_t ld, int cq, int npass, uint32_t kk, uint32_t* cnt, uint32_t* hist, uint32_t* tie_info,
+                        unsigned long long* cand, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)((char*)hist - (char*)cnt) + (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
+    for (int ps = 0; ps < npass; ++ps) LAUNCH_TRY(hdb_launch_hist(scores, n, ld, cq, hist, ps, kk, st));
+    LAUNCH_TRY(hdb_launch_collect(scores, n, ld, cq, hist, npass, kk, cnt, cand, HDB_CAND_CAP, tie_info, st));
+    return HDB_OK;
+}
 
 static int run_pipeline(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     TopkEnv e;
     int rc = topk_begin(ix, c, p, e); if (rc) return rc;
-    const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
-    int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
     const TopkWs& w = e.w;
-    float* const qsq = w.qsq; int* const qnan = w.qnan;
-    float* const thr = w.thr; uint32_t* const cnt = w.cnt; uint32_t* const tile_ctr = w.tile_ctr; uint32_t* const hist = w.hist;
-    uint32_t* const tie_info = w.tie_info; unsigned long long* const cand = w.cand; float* const sbuf = w.sbuf;
-    const bool small = p.small, exact = p.exact, mfma = p.mfma, fold_small = p.fold_small, q16_in_prep = p.q16_in_prep;
+    hipStream_t st = c.st; const int32_t k = c.k;
+    const int64_t n = p.subset ? ix->subset_m : ix->n;
     bool f32s = false;
-    rc = exact_parts(ix, p, qnan, nq, st, f32s); if (rc) return rc;
-    const int64_t n = p.subset ? ix->subset_m : ix->n, s_tiles = p.s_tiles, s_stride = p.s_stride, s_rows = p.s_rows, ld_s = p.ld_s, ld_n = p.ld_n;
-    const uint32_t kk = p.kk, m = p.m; const int cq_max = p.cq_max, npass = p.npass;
-    bool q16_ready = q16_in_prep;
-    for (int q0 = 0; q0 < nq; q0 += cq_max) {
-        const int cq = std::min(cq_max, nq - q0);
+    rc = exact_parts(ix, p, w.qnan, c.nq, st, f32s); if (rc) return rc;
+    bool q16_ready = p.q16_in_prep;
+    for (int q0 = 0; q0 < c.nq; q0 += p.cq_max) {
+        const int cq = std::min(p.cq_max, c.nq - q0);
+        int64_t* const out_idx = c.idx + (int64_t)q0 * k; float* const out_score = c.score + (int64_t)q0 * k;      // the chunk's slots of the answer
+        int32_t* const out_status = c.status ? c.status + q0 : nullptr;
         QueryBufs qb; ScanArgs a;
-        rc = chunk_args(ix, p, e, f32s, nq, q0, cq, n, q16_ready, st, qb, a); if (rc) return rc;
+        rc = chunk_args(ix, p, e, f32s, c.nq, q0, cq, n, q16_ready, st, qb, a); if (rc) return rc;
 
-        if (small) {
-            if (!fold_small) LAUNCH_TRY(hdb_launch_fill_thr(thr, cnt, cq, -INFINITY, st));
-            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
-        } else if (!exact) {
+        if (p.small) {
+            if (!p.fold_small) LAUNCH_TRY(hdb_launch_fill_thr(w.thr, w.cnt, cq, -INFINITY, st));
+            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, p.mfma, st); if (rc) return rc;
+        } else if (!p.exact) {
             // 1) strided row sample -> sample scores
             ScanArgs s = a;
-            s.ntiles = s_tiles; s.tile_stride = s_stride; s.scores = sbuf; s.ld = ld_s;
-            rc = run_scan(ix, s, 0, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
+            s.ntiles = p.s_tiles; s.tile_stride = p.s_stride; s.scores = w.sbuf; s.ld = p.ld_s;
+            rc = run_scan(ix, s, 0, cq, qb, p.l1tile, p.mfma, st); if (rc) return rc;
             // 2) m-th largest sample score per query
-            if (m <= 16) {
-                LAUNCH_TRY(hdb_launch_sample_thr(sbuf, s_rows, ld_s, cq, m, thr, cnt, tile_ctr, st));
-                if (mfma && ix->opt.dyn_tiles) a.tile_ctr = tile_ctr;       // zeroed just now: dynamic tile hand-out in the pass
+            if (p.m <= 16) {
+                LAUNCH_TRY(hdb_launch_sample_thr(w.sbuf, p.s_rows, p.ld_s, cq, p.m, w.thr, w.cnt, w.tile_ctr, st));
+                if (p.mfma && ix->opt.dyn_tiles) a.tile_ctr = w.tile_ctr;       // zeroed just now: dynamic tile hand-out in the pass
             } else {
-                HIP_TRY(hipMemsetAsync(hist, 0, (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
-                for (int ps = 0; ps < 4; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, s_rows, ld_s, cq, hist, ps, m, st));
-                LAUNCH_TRY(hdb_launch_thr(hist, cq, 4, m, (uint32_t)s_rows, thr, cnt, st));
+                HIP_TRY(hipMemsetAsync(w.hist, 0, (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
+                for (int ps = 0; ps < 4; ++ps) LAUNCH_TRY(hdb_launch_hist(w.sbuf, p.s_rows, p.ld_s, cq, w.hist, ps, p.m, st));
+                LAUNCH_TRY(hdb_launch_thr(w.hist, cq, 4, p.m, (uint32_t)p.s_rows, w.thr, w.cnt, st));
             }
             // 3) the pass over all of V
             prof_begin(ix, st);
-            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, mfma, st); if (rc) return rc;
+            rc = run_scan(ix, a, 1, cq, qb, p.l1tile, p.mfma, st); if (rc) return rc;
             prof_end(ix, st);
         } else {
-            rc = score_chunk(ix, p, a, qb, cq, sbuf, st); if (rc) return rc;
+            rc = score_chunk(ix, p, a, qb, cq, w.sbuf, st); if (rc) return rc;
             if (p.n_best > 0) {
                 // the exact grouped pass: each group's best row keeps its score, every other row joins the masked ones at -inf
                 HIP_TRY(hipMemsetAsync(w.best, 0, (size_t)cq * (size_t)p.n_best * sizeof(unsigned long long), st));      // key 0 is below every real key
                 if (q0 == 0) HIP_TRY(hipMemsetAsync(w.gbad, 0, sizeof(int), st));
-                LAUNCH_TRY(hdb_launch_group_best(sbuf, n, ld_n, cq, ix->groups, p.n_best, w.best, st));
-                LAUNCH_TRY(hdb_launch_group_demote(sbuf, n, ld_n, cq, ix->groups, p.n_best, w.best, w.gbad, st));
+                LAUNCH_TRY(hdb_launch_group_best(w.sbuf, n, p.ld_n, cq, ix->groups, p.n_best, w.best, st));
+                LAUNCH_TRY(hdb_launch_group_demote(w.sbuf, n, p.ld_n, cq, ix->groups, p.n_best, w.best, w.gbad, st));
             }
-            // cnt and hist are neighbours in the workspace: one memset clears both
-            HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)((char*)hist - (char*)cnt) + (size_t)cq * 4 * HDB_RADIX_BINS * 4, st));
-            for (int ps = 0; ps < npass; ++ps) LAUNCH_TRY(hdb_launch_hist(sbuf, n, ld_n, cq, hist, ps, kk, st));
-            LAUNCH_TRY(hdb_launch_collect(sbuf, n, ld_n, cq, hist, npass, kk, cnt, cand, HDB_CAND_CAP, tie_info, st));
-            if (p.subset) LAUNCH_TRY(hdb_launch_list_rows(cand, cnt, HDB_CAND_CAP, cq, ix->rows, ix->subset_m, st));
+            rc = select_exact(w.sbuf, n, p.ld_n, cq, p.npass, p.kk, w.cnt, w.hist, w.tie_info, w.cand, st); if (rc) return rc;
+            if (p.subset) LAUNCH_TRY(hdb_launch_list_rows(w.cand, w.cnt, HDB_CAND_CAP, cq, ix->rows, ix->subset_m, st));
         }
-        if (mfma && metric == HDB_EUCLIDEAN)     // the MFMA path scores through ||v||^2+||q||^2-2v.q: redo near-duplicates directly
-            LAUNCH_TRY(hdb_launch_rescore_euclid(cand, cnt, HDB_CAND_CAP, cq, ix->V, ix->dtype, ix->d, (const float*)dev_Q, qsq, q0, ix->bias, st));
-        LAUNCH_TRY(hdb_launch_finalize(cand, cnt, HDB_CAND_CAP, cq, (uint32_t)k, kk, ix->row_base,
-                                       dev_idx + (int64_t)q0 * k, dev_score + (int64_t)q0 * k,
-                                       dev_status ? dev_status + q0 : nullptr, qnan + q0, (int)ix->opt.finalize_threads,
-                                       a.f32_split ? HDB_Q_UNDERFLOW : 0, st));      // (parts of an infinite query element cancel to NaN: exact re-run)
+        if (p.mfma && c.metric == HDB_EUCLIDEAN)     // the MFMA path scores through ||v||^2+||q||^2-2v.q: redo near-duplicates directly
+            LAUNCH_TRY(hdb_launch_rescore_euclid(w.cand, w.cnt, HDB_CAND_CAP, cq, ix->V, ix->dtype, ix->d, (const float*)c.Q, w.qsq, q0, ix->bias, st));
+        LAUNCH_TRY(hdb_launch_finalize(w.cand, w.cnt, HDB_CAND_CAP, cq, (uint32_t)k, p.kk, ix->row_base, out_idx, out_score, out_status, w.qnan + q0,
+                                       (int)ix->opt.finalize_threads, a.f32_split ? HDB_Q_UNDERFLOW : 0, st));      // (parts of an infinite query element cancel to NaN: exact re-run)
         if (p.n_best > 0)       // (entries the selection handed out at -inf are padding; a bad group id marks the chunk's queries)
-            LAUNCH_TRY(hdb_launch_group_finish(dev_idx + (int64_t)q0 * k, dev_score + (int64_t)q0 * k, cq, k, dev_status ? dev_status + q0 : nullptr, w.gbad, st));
+            LAUNCH_TRY(hdb_launch_group_finish(out_idx, out_score, cq, k, out_status, w.gbad, st));
     }
     return HDB_OK;
+}
+
+// Plan a call (plan_topk, hdb_plan.h).  The planner's one question to the device is the cached flag word of the last build, fetched
+// where it decides something; a fetch that failed is the call's error.
+static int plan_call(hdb_index* ix, const TopkCall& call, TopkPlan& out) {
+    int frc = HDB_OK;
+    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
+    out = plan_topk(topk_facts(ix), ix->opt, call, finite);
+    return frc;
+}
+// The statistics of a call start here: the plan's (or a fresh set), and no list counters of an earlier batch through the shadow.
+static void stats_begin(hdb_index* ix, const TopkStats& stats) {
+    ix->st = stats; ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
 }
 
 static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
@@ -1318,20 +1356,14 @@ static int topk_impl(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, in
     HIP_TRY(hipSetDevice(ix->device));
     const TopkArgs c{dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, (hipStream_t)stream};
     const TopkCall call{nq, k, metric, dev_status != nullptr, exact};
-    // the planner's one question to the device: the cached flag word of the last build, fetched where it decides something
-    int frc = HDB_OK;
-    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
-    TopkPlan p = plan_topk(topk_facts(ix), ix->opt, call, finite);
-    if (frc != HDB_OK) return frc;
+    TopkPlan p;
+    int rc = plan_call(ix, call, p); if (rc) return rc;
     if (p.shadow()) {                // a declined build or plane is a new fact: plan once more, and only once
         bool declined = false;
-        const int rc = shadow_prepare(ix, p, nq, c.st, &declined);
-        if (rc) return rc;
-        if (declined) p = plan_topk(topk_facts(ix), ix->opt, call, finite);
-        if (frc != HDB_OK) return frc;
+        rc = shadow_prepare(ix, p, nq, c.st, &declined); if (rc) return rc;
+        if (declined) { rc = plan_call(ix, call, p); if (rc) return rc; }
     }
-    ix->st = p.stats;                // the statistics of the call: written here and nowhere else
-    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    stats_begin(ix, p.stats);
     switch (p.path) {
     case HDB_PATH_EMPTY: return run_empty(c);
     case HDB_PATH_QUANT: return quant_topk(ix, c, p);
@@ -1414,13 +1446,28 @@ extern "C" int hdb_host_exchange_merge(void* shm, int64_t stride, int32_t world,
     return HDB_OK;
 }
 
+// The exact re-run: every query whose status word says that its sampled threshold failed goes once more through the exact selection,
+// one by one, straight into its slots of the device view `dv`.  Which queries are flagged is read off `h_st` BEFORE the first re-run:
+// with a pinned record the host's words ARE the device's, and every re-run rewrites its own.  *ran: whether anything ran.  Each
+// re-run starts the statistics anew; what the call reports afterwards is the caller's rule.
+static int rerun_flagged(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, const PackedRec& dv, const int32_t* h_st,
+                         hipStream_t st, bool* ran) {
+    std::vector<int> bad;                  // (empty, as nearly always: no allocation)
+    for (int q = 0; q < nq; ++q) if (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) bad.push_back(q);
+    *ran = !bad.empty();
+    for (int q : bad) {
+        const int rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * query_pitch(ix), 1, k, metric, dv.idx + (size_t)q * k,
+                                 dv.score + (size_t)q * k, dv.status + q, st, true);
+        if (rc) return rc;
+    }
+    return HDB_OK;
+}
 extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, void* host_record, void* stream) {
     if (!ix || !host_record) return fail(HDB_ERR_ARG, "hdb_topk_host: null argument");
     if (nq <= 0 || k <= 0) return fail(HDB_ERR_ARG, "hdb_topk_host: nq and k must be positive");
     const auto ht0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
     // Pinned (device-visible) host memory: the last kernels of the pipeline store the record there themselves and the
     // D2H copy disappears from the critical path; anything else goes through a device record and one hipMemcpyAsync.
     bool direct = false;
@@ -1431,14 +1478,8 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
         ix->ht_attr_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ht0).count();
     }
     ix->st_host_direct = direct ? 1 : 0;
-    char* rec = static_cast<char*>(host_record);
-    if (!direct) {
-        const int rc = ensure_record(ix->rec, bytes);
-        if (rc) return rc;
-        rec = ix->rec;
-    }
-    const PackedRec dr = packed_view(rec, nq, k);
-    int64_t* d_idx = dr.idx; float* d_sc = dr.score; int32_t* d_st = dr.status;
+    HostRec rec;
+    int rc = hostrec_open(ix->rec, nq, k, host_record, direct, rec); if (rc) return rc;
     // Pinned record: the status words are stored last (by the single-launch kernel's final workgroup, or by each query's
     // finalize workgroup), behind a system-scope release, so the host can poll them instead of waiting for the completion
     // signal of the last kernel (end-of-kernel drain, cache write-back, signal, wake-up: ~5-10 us).  The stream stays
@@ -1447,9 +1488,8 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
     volatile int32_t* poll = packed_view(host_record, nq, k).status;
     if (direct && ix->opt.host_poll) for (int q = 0; q < nq; ++q) poll[q] = SENTINEL;
     ix->ht_l0 = ix->ht_l1 = std::chrono::steady_clock::now();      // (pipelines of several launches: everything counts as "pre")
-    int rc = topk_impl(ix, dev_Q, nq, k, metric, d_idx, d_sc, d_st, stream, false);
-    if (rc) return rc;
-    if (!direct) HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
+    rc = topk_impl(ix, dev_Q, nq, k, metric, rec.view.idx, rec.view.score, rec.view.status, stream, false); if (rc) return rc;
+    rc = hostrec_close(rec, st, false); if (rc) return rc;      // (the copy alone: the wait is the poll below, or the stream's where nothing was polled)
     bool polled = false;
     if (direct && ix->opt.host_poll && (ix->st.fused || ix->st.path != 3)) {      // (the k > 2048 full sort writes its status words elsewhere)
         const auto t0 = std::chrono::steady_clock::now();
@@ -1471,25 +1511,12 @@ extern "C" int hdb_topk_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32
         ix->ht_wait_ns += std::chrono::duration_cast<ns>(ht3 - ix->ht_l1).count();
         ix->ht_calls++;
     }
-    const int32_t* h_st = packed_view(host_record, nq, k).status;
-    bool any_bad = false;
-    for (int q = 0; q < nq; ++q) any_bad |= (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) != 0;
-    if (!any_bad) return HDB_OK;
-    // rare: re-run the failed queries one by one through the exact path, straight into their slots of the record
-    const size_t qbytes = (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4);
-    std::vector<char> bad(nq);
-    for (int q = 0; q < nq; ++q) bad[q] = (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW)) != 0;     // the re-run rewrites h_st
-    const int64_t quant_first = ix->st.quant;            // ("quant" reports the call's first attempt)
-    for (int q = 0; q < nq; ++q) {
-        if (!bad[q]) continue;
-        rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, k, metric, d_idx + (size_t)q * k,
-                       d_sc + (size_t)q * k, d_st + q, stream, true);
-        if (rc) return rc;
-    }
-    ix->st.quant = quant_first;
-    if (!direct) HIP_TRY(hipMemcpyAsync(host_record, rec, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HDB_OK;
+    const int64_t quant_first = ix->st.quant;      // rare: the failed queries again, straight into their slots of the record
+    bool ran = false;
+    rc = rerun_flagged(ix, dev_Q, nq, k, metric, rec.view, packed_view(host_record, nq, k).status, st, &ran);
+    if (rc || !ran) return rc;
+    ix->st.quant = quant_first;      // the rule of this call: the statistics are the last re-run's, but "quant" reports the first attempt
+    return hostrec_close(rec, st);
 }
 
 extern "C" int hdb_topk_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx,
@@ -1505,6 +1532,20 @@ static int rerank_sizes(const char* who, int32_t nq, int32_t m, int32_t k, bool 
     if (host ? nq <= 0 : nq < 0) return fail(HDB_ERR_ARG, std::string(who) + (host ? ": nq must be positive" : ": nq must be >= 0"));
     return HDB_OK;
 }
+// The metrics a ranking call beside hdb_topk takes (rerank, grouped, multi-vector): the five that score a row against a query.
+// what_is: the call's name for itself in the sentence ("rerank is", "grouped calls are").
+static int ranking_metric(const char* who, const char* what_is, int metric) {
+    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": hamming / jaccard " + what_is + " not built");
+    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
+        return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": metric not built");
+    return HDB_OK;
+}
+// ... and the k of a call that answers in groups (grouped, multi-vector)
+static int ranking_k(const char* who, int32_t k) {
+    if (k < 1) return fail(HDB_ERR_ARG, std::string(who) + ": k must be at least 1");
+    if (k > HDB_MAX_K) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": k beyond HDB_MAX_K (2048) is not built");
+    return HDB_OK;
+}
 // Per chunk of queries: list preparation (valid, ascending, unique rows; the status words), the scoring pass, the finalize of the
 // multi-kernel pipeline over lists of at most m <= HDB_CAND_CAP entries.  The finalize gets no status pointer: a list shorter than k
 // is no underflow here, the tail is -1 / -inf and the status word is the preparation's (HDB_Q_NAN, HDB_Q_BADROW).
@@ -1514,17 +1555,14 @@ static int rerank_impl(const char* who, hdb_index* ix, const void* dev_Q, int32_
     if (nq == 0) return HDB_OK;
     if (!dev_Q || !dev_cand || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, std::string(who) + ": null argument");
     if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": a packed-bit index is a first stage: rerank onto packed bits is not built");
-    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": hamming / jaccard rerank is not built");
-    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
-        return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": metric not built");
+    int rc = ranking_metric(who, "rerank is", metric); if (rc) return rc;
     HIP_TRY(hipSetDevice(ix->device));
     const bool f64 = ix->dtype == HDB_F64, pearson = metric == HDB_PEARSON;
     const int cq_max = (int)std::min<int64_t>(nq, ix->opt.rerank_chunk > 0 ? ix->opt.rerank_chunk : HDB_RERANK_MAXQ);
-    ix->st = TopkStats();
+    stats_begin(ix, TopkStats());
     ix->st.rerank = 1;
-    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
     RerankWs w;
-    int rc = ws_lay(ix, w, (int)nq, (int)ix->d, cq_max, (int)m, pearson);
+    rc = ws_lay(ix, w, (int)nq, (int)ix->d, cq_max, (int)m, pearson);
     if (rc) return rc;
     LAUNCH_TRY(hdb_launch_qprep2(dev_Q, nq, ix->d, f64, w.qinv, w.qsq, w.qnan, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st));
     const void* Qeff = dev_Q; int metric_eff = metric;
@@ -1563,15 +1601,10 @@ extern "C" int hdb_rerank_host(hdb_index* ix, const void* dev_Q, int32_t nq, con
     if (!ix || !host_record) return fail(HDB_ERR_ARG, "hdb_rerank_host: null argument");
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
-    rc = ensure_record(ix->rec, bytes);
-    if (rc) return rc;
-    const PackedRec r = packed_view(ix->rec, nq, k);
-    rc = rerank_impl("hdb_rerank_host", ix, dev_Q, nq, dev_cand, m, k, metric, r.idx, r.score, r.status, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HDB_OK;
+    HostRec rec;
+    rc = hostrec_open(ix->rec, nq, k, host_record, false, rec); if (rc) return rc;
+    rc = rerank_impl("hdb_rerank_host", ix, dev_Q, nq, dev_cand, m, k, metric, rec.view.idx, rec.view.score, rec.view.status, st); if (rc) return rc;
+    return hostrec_close(rec, st);
 }
 
 // Stage one on `first` into a device record of its own, its status words read back and the failed queries re-run exactly (as
@@ -1586,27 +1619,18 @@ extern "C" int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metr
     if ((int64_t)k1 > first->n) return fail(HDB_ERR_ARG, "hdb_two_stage_host: k1 must be at most min(8192, n)");
     HIP_TRY(hipSetDevice(first->device));
     hipStream_t st = (hipStream_t)stream;
-    rc = ensure_record(first->rec1, (size_t)hdb_packed_bytes(nq, k1));
-    if (rc) return rc;
-    const PackedRec r1 = packed_view(first->rec1, nq, k1);
-    int64_t* d_idx = r1.idx; float* d_sc = r1.score; int32_t* d_st = r1.status;
-    rc = topk_impl(first, dev_Q1, nq, k1, metric1, d_idx, d_sc, d_st, stream, false);
-    if (rc) return rc;
+    HostRec rec1;                                     // (stage one's record stays on the device: opened, never closed)
+    rc = hostrec_open(first->rec1, nq, k1, nullptr, false, rec1); if (rc) return rc;
+    const PackedRec& r1 = rec1.view;
+    rc = topk_impl(first, dev_Q1, nq, k1, metric1, r1.idx, r1.score, r1.status, stream, false); if (rc) return rc;
     std::vector<int32_t> h_st((size_t)nq);
-    HIP_TRY(hipMemcpyAsync(h_st.data(), d_st, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_st.data(), r1.status, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const size_t qbytes = (size_t)first->d * (first->dtype == HDB_F64 ? 8 : 4);
-    const TopkStats first_stats = first->st;          // (the statistics report the call's first attempt)
-    bool rerun = false;
-    for (int q = 0; q < nq; ++q) {
-        if (!(h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW))) continue;
-        rc = topk_impl(first, static_cast<const char*>(dev_Q1) + (size_t)q * qbytes, 1, k1, metric1, d_idx + (size_t)q * k1, d_sc + (size_t)q * k1,
-                       d_st + q, stream, true);
-        if (rc) return rc;
-        rerun = true;
-    }
-    if (rerun) first->st = first_stats;
-    return hdb_rerank_host(second, dev_Q2, nq, d_idx, k1, k, metric2, host_record, stream);
+    const TopkStats first_stats = first->st;
+    bool ran = false;
+    rc = rerun_flagged(first, dev_Q1, nq, k1, metric1, r1, h_st.data(), st, &ran); if (rc) return rc;
+    if (ran) first->st = first_stats;                 // the rule of this call: `first` reports its first attempt, every statistic of it
+    return hdb_rerank_host(second, dev_Q2, nq, r1.idx, k1, k, metric2, host_record, stream);
 }
 
 // ---- grouped top-k: one row per group (hdb_group.hip, hdb_group_plan.h) -----------------------------------------------------------
@@ -1614,33 +1638,26 @@ extern "C" int hdb_two_stage_host(hdb_index* first, const void* dev_Q1, int metr
 static int grouped_exact(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, int64_t* dev_idx, float* dev_score,
                          int32_t* dev_status, hipStream_t st) {
     const TopkArgs c{dev_Q, nq, k, metric, dev_idx, dev_score, dev_status, st};
-    int frc = HDB_OK;
-    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
-    const TopkPlan p = plan_topk(topk_facts(ix), ix->opt, group_exact_call(nq, k, metric, ix->n_groups), finite);
-    if (frc != HDB_OK) return frc;
+    TopkPlan p;
+    const int rc = plan_call(ix, group_exact_call(nq, k, metric, ix->n_groups), p); if (rc) return rc;
     if (!group_exact_shape(p)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: this call has no exact grouped pass");
-    ix->st = p.stats;
-    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    stats_begin(ix, p.stats);
     return run_pipeline(ix, c, p);
 }
 
 extern "C" int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric, void* host_record, void* stream) {
     // what the numbers alone decide, then the handle, then the device
     if (nq <= 0) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: nq must be positive");
-    if (k < 1) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: k must be at least 1");
-    if (k > HDB_MAX_K) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: k beyond HDB_MAX_K (2048) is not built");
+    int rc = ranking_k("hdb_topk_grouped_host", k); if (rc) return rc;
     if (!ix || !dev_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: null argument");
     if (!ix->groups) return fail(HDB_ERR_ARG, "hdb_topk_grouped_host: no groups set (hdb_index_set_groups)");
-    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: hamming / jaccard grouped calls are not built");
-    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
-        return fail(HDB_ERR_UNSUPPORTED, "hdb_topk_grouped_host: metric not built");
+    rc = ranking_metric("hdb_topk_grouped_host", "grouped calls are", metric); if (rc) return rc;
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
-    int rc = ensure_record(ix->rec, bytes);
-    if (rc) return rc;
-    const PackedRec out = packed_view(ix->rec, nq, k);
-    const size_t qbytes = (size_t)ix->d * (ix->dtype == HDB_F64 ? 8 : 4);
+    HostRec rec;
+    rc = hostrec_open(ix->rec, nq, k, host_record, false, rec); if (rc) return rc;
+    const PackedRec& out = rec.view;
+    const size_t qbytes = query_pitch(ix);
     const GroupRounds gr = group_rounds(ix->n, k, ix->opt.group_oversample, ix->opt.group_fast_rounds);
     int64_t st_k = 0, st_rounds = 0, st_exact = 0;
     std::vector<int32_t> h_st((size_t)nq, 0);
@@ -1654,24 +1671,23 @@ extern "C" int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t n
     for (int r = 0; r < gr.rounds && ix->n > 0; ++r) {
         const int32_t kr = gr.kr[r];
         // round 1: the whole batch in one call; round 2: the flagged queries, one by one, each into the head of the round's record
-        rc = ensure_record(ix->rec1, (size_t)hdb_packed_bytes(r == 0 ? nq : 1, kr));
-        if (rc) return rc;
+        HostRec round;
+        rc = hostrec_open(ix->rec1, r == 0 ? nq : 1, kr, nullptr, false, round); if (rc) return rc;
+        const PackedRec& rr = round.view;
         bool ran = false;
         if (r == 0) {
-            const PackedRec r1 = packed_view(ix->rec1, nq, kr);
-            rc = topk_impl(ix, dev_Q, nq, kr, metric, r1.idx, r1.score, r1.status, stream, false);
+            rc = topk_impl(ix, dev_Q, nq, kr, metric, rr.idx, rr.score, rr.status, stream, false);
             if (rc) return rc;
-            LAUNCH_TRY(hdb_launch_group_collapse(r1.idx, r1.score, nq, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx, out.score,
-                                                 r1.status, out.status, carry, st));
+            LAUNCH_TRY(hdb_launch_group_collapse(rr.idx, rr.score, nq, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx, out.score,
+                                                 rr.status, out.status, carry, st));
             ran = true;
         } else {
-            const PackedRec r2 = packed_view(ix->rec1, 1, kr);
             for (int q = 0; q < nq; ++q) {
                 if (!todo[q] || (h_st[q] & (HDB_Q_UNDERFLOW | HDB_Q_OVERFLOW))) continue;      // (a failed sampled call: straight to the exact pass)
-                rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, kr, metric, r2.idx, r2.score, r2.status, stream, false);
+                rc = topk_impl(ix, static_cast<const char*>(dev_Q) + (size_t)q * qbytes, 1, kr, metric, rr.idx, rr.score, rr.status, stream, false);
                 if (rc) return rc;
-                LAUNCH_TRY(hdb_launch_group_collapse(r2.idx, r2.score, 1, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx + (size_t)q * k,
-                                                     out.score + (size_t)q * k, r2.status, out.status + q, carry, st));
+                LAUNCH_TRY(hdb_launch_group_collapse(rr.idx, rr.score, 1, kr, k, ix->groups, ix->n_groups, ix->n, ix->row_base, out.idx + (size_t)q * k,
+                                                     out.score + (size_t)q * k, rr.status, out.status + q, carry, st));
                 ran = true;
             }
         }
@@ -1698,9 +1714,7 @@ extern "C" int hdb_topk_grouped_host(hdb_index* ix, const void* dev_Q, int32_t n
         q = e;
     }
     ix->st.grouped = 1; ix->st.group_k = st_k; ix->st.group_rounds = st_rounds; ix->st.group_exact = st_exact;
-    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HDB_OK;
+    return hostrec_close(rec, st);
 }
 
 // ---- multi-vector queries: groups ranked by the sum over a set's vectors of the per-group maxima (hdb_maxsim.hip, hdb_maxsim_plan.h) ----
@@ -1744,8 +1758,7 @@ extern "C" int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* 
                                void* stream) {
     // what the numbers alone decide, then the handle, then the device
     if (ns < 1) return fail(HDB_ERR_ARG, "hdb_maxsim_host: ns (query sets) must be positive");
-    if (k < 1) return fail(HDB_ERR_ARG, "hdb_maxsim_host: k must be at least 1");
-    if (k > HDB_MAX_K) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: k beyond HDB_MAX_K (2048) is not built");
+    int rc = ranking_k("hdb_maxsim_host", k); if (rc) return rc;
     if (!host_off) return fail(HDB_ERR_ARG, "hdb_maxsim_host: null argument (host_off)");
     if (host_off[0] != 0) return fail(HDB_ERR_ARG, "hdb_maxsim_host: host_off[0] must be 0, got " + std::to_string(host_off[0]));
     for (int32_t s = 0; s < ns; ++s)
@@ -1754,38 +1767,29 @@ extern "C" int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* 
                                          std::to_string(host_off[s]) + " -> " + std::to_string(host_off[s + 1]) + ")");
     if (!ix || !dev_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_maxsim_host: null argument");
     if (!ix->groups) return fail(HDB_ERR_ARG, "hdb_maxsim_host: no groups set (hdb_index_set_groups)");
-    if (is_bits_metric(metric)) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: hamming / jaccard multi-vector calls are not built");
-    if (metric != HDB_DOT && metric != HDB_COSINE && metric != HDB_EUCLIDEAN && metric != HDB_MANHATTAN && metric != HDB_PEARSON)
-        return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: metric not built");
+    rc = ranking_metric("hdb_maxsim_host", "multi-vector calls are", metric); if (rc) return rc;
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;
     const int32_t nv = host_off[ns];
-    const size_t bytes = (size_t)hdb_packed_bytes(ns, k);
-    int rc = ensure_record(ix->rec, bytes);
-    if (rc) return rc;
-    const PackedRec out = packed_view(ix->rec, ns, k);
-    ix->qb_cnt = nullptr; ix->qb_cnt_n = 0;
+    HostRec rec;
+    rc = hostrec_open(ix->rec, ns, k, host_record, false, rec); if (rc) return rc;
+    const PackedRec& out = rec.view;
     if (ix->n == 0) {
-        ix->st = TopkStats(); ix->st.maxsim = 1;
-        rc = run_empty(TopkArgs{dev_Q, ns, k, metric, out.idx, out.score, out.status, st});
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return HDB_OK;
+        stats_begin(ix, TopkStats()); ix->st.maxsim = 1;
+        rc = run_empty(TopkArgs{dev_Q, ns, k, metric, out.idx, out.score, out.status, st}); if (rc) return rc;
+        return hostrec_close(rec, st);
     }
     rc = maxsim_index(ix, st);
     if (rc) return rc;
     // the score pass: the exact shape of run_pipeline for the nv flat vectors, cut by the block / chunk plan
-    int frc = HDB_OK;
-    auto finite = [&] { bool f = false; if (frc == HDB_OK) frc = matrix_is_finite(ix, &f); return f; };
-    TopkPlan p = plan_topk(topk_facts(ix), ix->opt, maxsim_call(nv, k, metric), finite);
-    if (frc != HDB_OK) return frc;
+    TopkPlan p;
+    rc = plan_call(ix, maxsim_call(nv, k, metric), p); if (rc) return rc;
     if (!maxsim_shape(p)) return fail(HDB_ERR_UNSUPPORTED, "hdb_maxsim_host: this call has no exact score pass");
     const int64_t n = ix->n, ng = ix->n_groups;
     const MaxsimPlan mp = maxsim_plan(n, ng, ns, p.ksplit ? 128 : 256, ix->opt.exact_bytes);
     p.cq_max = std::min<int>(mp.cq, nv);
     const int team = ix->opt.maxsim_team ? (int)ix->opt.maxsim_team : hdb_maxsim_team_rule(n, ng);
-    ix->st = p.stats;
+    stats_begin(ix, p.stats);          // (here, not sooner: the statistics are those of the plan as used)
     ix->st.maxsim = 1; ix->st.maxsim_team = team; ix->st.maxsim_sorted = ix->grp_sorted ? 1 : 0;
     ix->st.maxsim_chunks = maxsim_chunks(mp, host_off, ns); ix->st.chunks = ix->st.maxsim_chunks;
     MaxsimWs w;
@@ -1813,17 +1817,13 @@ extern "C" int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* 
                                                 w.acc, mp.ld_g, team, st));
         }
         // the block's selection: acc is a score matrix of sbn "queries" over n_groups "rows"; ids are group ids (row_base 0)
-        HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)((char*)w.hist - (char*)w.cnt) + (size_t)sbn * 4 * HDB_RADIX_BINS * 4, st));
-        for (int ps = 0; ps < 4; ++ps) LAUNCH_TRY(hdb_launch_hist(w.acc, ng, mp.ld_g, sbn, w.hist, ps, kk, st));
-        LAUNCH_TRY(hdb_launch_collect(w.acc, ng, mp.ld_g, sbn, w.hist, 4, kk, w.cnt, w.cand, HDB_CAND_CAP, w.tie_info, st));
+        rc = select_exact(w.acc, ng, mp.ld_g, sbn, 4, kk, w.cnt, w.hist, w.tie_info, w.cand, st); if (rc) return rc;
         LAUNCH_TRY(hdb_launch_finalize(w.cand, w.cnt, HDB_CAND_CAP, sbn, (uint32_t)k, kk, 0, out.idx + (int64_t)s0 * k, out.score + (int64_t)s0 * k,
                                        out.status + s0, w.snan + s0, (int)ix->opt.finalize_threads, 0, st));
         // (groups at -inf are never returned: padding; a bad group id anywhere in the index marks every set)
         LAUNCH_TRY(hdb_launch_group_finish(out.idx + (int64_t)s0 * k, out.score + (int64_t)s0 * k, sbn, k, out.status + s0, ix->grp_flags, st));
     }
-    HIP_TRY(hipMemcpyAsync(host_record, ix->rec, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HDB_OK;
+    return hostrec_close(rec, st);
 }
 
 extern "C" int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, const int32_t* dev_groups,
@@ -2047,8 +2047,7 @@ extern "C" int hdb_group_topk_host(hdb_group* g, const void* host_Q, int32_t nq,
     if (!g || !host_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_group_topk_host: null argument");
     if (nq <= 0 || k <= 0) return fail(HDB_ERR_ARG, "hdb_group_topk_host: nq and k must be positive");
     const size_t bytes = (size_t)hdb_packed_bytes(nq, k);
-    const size_t qelem = g->ix[0]->dtype == HDB_F64 ? 8 : 4;
-    const size_t q_bytes = (size_t)g->ix[0]->d * qelem * nq;
+    const size_t q_bytes = query_pitch(g->ix[0]) * nq;
     if (bytes * g->parts > g->gather_bytes || q_bytes > g->qpin_bytes) {      // (no call is in flight: the previous one returned)
         HIP_TRY(hipSetDevice(g->ix[0]->device));
         int rc = group_pinned(&g->gather, &g->gather_bytes, bytes * g->parts); if (rc) return rc;

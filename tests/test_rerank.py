@@ -348,7 +348,8 @@ def test_two_stage_survives_a_failing_first_stage():
     """40 distinct first-stage rows repeated to 20 001: every score is a 500-fold tie.  With the sampled threshold aimed at 16
     survivors (sample_target, as tests/test_row_subset.py fails a sampled pass) the threshold sits on the best level, its 500 rows
     pass and k1 = 600 are wanted: the first stage reports that in its status words (asserted, so the input is what it claims).
-    The call re-runs those queries exactly and returns the composed answer."""
+    The call re-runs those queries exactly and returns the composed answer; afterwards `first` reports the statistics of its first
+    attempt, all of them, not those of the last one-query exact re-run."""
     import hyperdb.ranking_algorithm as ranking
     from hyperdb._native import METRIC_IDS
     rng = np.random.default_rng(12)
@@ -361,7 +362,10 @@ def test_two_stage_survives_a_failing_first_stage():
         st = _np(first.topk_device(Q, k1, METRIC_IDS["cosine_similarity"]))[2]
         print("first-stage status words:", st.tolist())
         assert (st != 0).any()
+        attempt = {s: first.stat(s) for s in ("path", "mfma", "fused", "chunks", "quant")}
         got = ranking.rank_two_stage(first, second, Q, top_k=K, oversample=60, metric="cosine_similarity")
+        print("first-stage statistics:", attempt)
+        assert {s: first.stat(s) for s in attempt} == attempt
         assert _same_ranked(got, _composed(first, second, Q, Q, K, k1, "cosine_similarity", "cosine_similarity"))
         assert (got[0] >= 0).all()
     finally:
