@@ -142,6 +142,12 @@ static inline int hdb_mfma_bf16_tile_rows(int d) { return (d == 128 || d == 256)
 // registers per 16 queries).  A wave takes one 16-row tile at a time and reads its fragments from global memory, so the tile height
 // is the VALU scan's 16 rows at every width
 static inline int hdb_mfma_f8_tile_rows(int d) { return (d == 128 || d == 256 || d == 384 || d == 512) ? 16 : 0; }
+// workgroups of a launch of the register kernels (float8, int8, packed bits: no LDS ring, 256 threads) over `ntiles` 16-row tiles:
+// max_blocks when the caller set one, else four workgroups per CU; never more than there are tiles, never fewer than one
+static inline int hdb_mfma_reg_blocks(int64_t ntiles, int cus, int max_blocks) {
+    const int64_t want = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
+    return (int)(ntiles < want ? (ntiles < 1 ? 1 : ntiles) : want);
+}
 
 // ---- hdb_mfma_f8_lds*.hip: float8 rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h; opt-in, f8_lds_min_q) ----
 // Whole rows of 128 / 256 / 384 / 512 elements and the K slices of 256 / 384 / 512.  A workgroup of `waves` waves (4 or 8, 16

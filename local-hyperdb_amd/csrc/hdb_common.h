@@ -157,6 +157,22 @@ struct BatchArgs {
     int32_t centre;                 // pearson: the kernel centres its queries (hdb_qcentre_kernel) and multiplies by 1/sd_q; the launch is the cosine one, aux = 1/(sd_v d)
 };
 
+// One launch of the matrix-core scan as the router (hdb_launch_mfma_scan, hdb_mfma.hip) hands it to a shard and the shard to its
+// template launchers: every shard is int name(const ScanArgs*, const MfmaLaunch*) (HDB_GEOM_DECL, hdb_launch.h) and reads what it
+// needs.  mode: 0 scores, 1 filter, 2 the whole call in one launch (f != nullptr), 3 raw partial sums of a K slice.  q: the query
+// fragments' source -- scaled fp16 copies with qscl[q] = 1 / scale for fp16 rows, the float32 queries themselves (qscl = nullptr)
+// for every other row type.  blocks: the workgroups of the launch (float8 rows in LDS: the most it may take).  variant: the
+// index's mfma_variant, 16 | 32 | 64 (fp16 d = 384 only).  width: the instantiated width a padded row rides (hdb_mfma_anyd.h) or
+// the elements of this K slice (hdb_mfma_ksplit.hip); 0 for a whole row of a geometry of its own.
+struct MfmaLaunch {
+    int mode, nq_launch;
+    const void* q;
+    const float *sqnorm, *qsq, *qscl;
+    int blocks, variant, width;
+    void* stream;
+    const BatchArgs* f;
+};
+
 // Arguments of the single-launch top-k of the bit metrics (hdb_bits_fused.hip): 1-4 hamming / jaccard queries in one launch.
 // Sign bits of the stored rows (hamming / jaccard): blocks of 256 rows, word-major inside a block -- [block][w][256 rows] -- so the
 // W x 1 KiB of a block are one contiguous piece (a wave step of the bit scans: 64 lanes x 16 B per word) and a pass streams the

@@ -13,14 +13,12 @@
 struct ScanArgs;        // hdb_common.h
 struct FusedArgs;
 struct BatchArgs;
+struct MfmaLaunch;
 struct BitsArgs;
 struct QuantArgs;       // hdb_quant.h
 
-// shards of the matrix-core scan: one launcher per geometry, all with the same arguments
-#define HDB_ANYD_DECL(name) int name(const ScanArgs* args, int dpad, int mode, int nq_launch, const void* q, const float* sqnorm, \
-                                     const float* qsq, const float* qscl, int blocks, void* stream)
-#define HDB_GEOM_DECL(name) int name(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm, \
-                                     const float* qsq, const float* qscl, int blocks, int variant, void* stream, const BatchArgs* f)
+// shards of the matrix-core scan: one launcher per geometry, all with ONE signature -- the scan and the launch record
+#define HDB_GEOM_DECL(name) int name(const ScanArgs* args, const MfmaLaunch* l)
 
 extern "C" {
 // ---- hdb_scan.hip: the VALU row scan, per-row caches, query prep ----
@@ -71,69 +69,42 @@ int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, int nq_launc
 int hdb_launch_q_to_f16(const float* Q, int nq, int d, void* q16, float* qscl, void* stream);
 int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int dtype, int d,
                               const float* Q, const float* qsq, int q0, const float* bias, void* stream);
-// ... its shards (hdb_mfma_<geometry>.hip)
-HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_d384);
+// ... its shards (hdb_mfma_<geometry>.hip): what a shard reads of the record is its own business (MfmaLaunch, hdb_common.h)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_d384);           // fp16 rows: the only shards that read qscl, d384 the only one that reads variant
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_narrow);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_mid);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_1k);
-int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                  const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                 const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_f32(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                             const float* qsq, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_f32_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                  const float* qsq, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                              const float* qsq, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_f32s_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                   const float* qsq, int blocks, void* stream, const BatchArgs* f);
-int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                              const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_bf16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                   const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_f8(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                            const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_f8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                 const float* qsq, int blocks, void* stream);
-// int8 rows: the float8 kernel with the int8 row converter (hdb_mfma_i8.hip)
-int hdb_launch_mfma_scan_i8(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                            const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_i8_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                 const float* qsq, int blocks, void* stream);
-// packed-bit rows: bits expanded to bf16 0.0 / 1.0 per fragment in registers (hdb_mfma_b1.h; opt-in, b1_mfma_min_q)
-int hdb_launch_mfma_scan_b1(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                            const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_b1_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                 const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_b1(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                              const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_b1_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                   const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
-                           const float* qsq, const float* qscl, int blocks, void* stream);
-int hdb_launch_mfma_kslice_f32s(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_bf16(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_bf16_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                     const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_f8(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                              const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_f8_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                   const float* qsq, int blocks, void* stream);
-// float8 rows expanded to bf16 in LDS (hdb_mfma_f8_lds.h; ScanArgs::f8_lds = waves per workgroup); blocks: the most workgroups the launch may take
-int hdb_launch_mfma_scan_f8_lds(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_scan_f8_lds_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                     const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_f8_lds(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                  const float* qsq, int blocks, void* stream);
-int hdb_launch_mfma_kslice_f8_lds_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                       const float* qsq, int blocks, void* stream);
-HDB_ANYD_DECL(hdb_launch_mfma_anyd_a); HDB_ANYD_DECL(hdb_launch_mfma_anyd_b);       // fp16 rows
-HDB_ANYD_DECL(hdb_launch_mfma_anyd_c); HDB_ANYD_DECL(hdb_launch_mfma_anyd_d);       // float32 rows
-HDB_ANYD_DECL(hdb_launch_mfma_anyd_e); HDB_ANYD_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f16_qt2);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f32);                // float32 rows, and as bf16 parts (f32s)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f32_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f32s);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f32s_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_bf16);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_bf16_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f8);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f8_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_i8);                 // int8 rows: the float8 kernel with the int8 row converter (hdb_mfma_i8.hip)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_i8_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_b1);                 // packed-bit rows: bits expanded to bf16 0.0 / 1.0 per fragment in registers (hdb_mfma_b1.h; opt-in, b1_mfma_min_q)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_b1_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f8_lds);             // float8 rows expanded to bf16 in LDS (hdb_mfma_f8_lds.h; ScanArgs::f8_lds = waves per workgroup); blocks: the most workgroups the launch may take
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f8_lds_wide);
+// the K-slice driver (hdb_mfma_ksplit.hip) and one slice of l->width elements (args: the slice's ks_* fields set)
+int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, const MfmaLaunch* l);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_f32s);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_bf16);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_bf16_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_f8);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_f8_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_f8_lds);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_f8_lds_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_b1);
+HDB_GEOM_DECL(hdb_launch_mfma_kslice_b1_wide);
+// a width without a geometry of its own as one slice of the next wider one, l->width (hdb_mfma_anyd.h)
+HDB_GEOM_DECL(hdb_launch_mfma_anyd_a); HDB_GEOM_DECL(hdb_launch_mfma_anyd_b);       // fp16 rows
+HDB_GEOM_DECL(hdb_launch_mfma_anyd_c); HDB_GEOM_DECL(hdb_launch_mfma_anyd_d);       // float32 rows
+HDB_GEOM_DECL(hdb_launch_mfma_anyd_e); HDB_GEOM_DECL(hdb_launch_mfma_anyd_f);       // float32 rows as bf16 parts
 
 // ---- the single launches: hdb_mfma_fused*.hip, hdb_bits_fused.hip; hdb_l1_tile.hip ----
 size_t hdb_mfma_fused_ctl_bytes(void);

@@ -90,15 +90,16 @@ extern "C" size_t hdb_mfma_batch_ctl_bytes(int wgs) { return (size_t)HDB_BATCH_G
 // for N=10M, Q=256), 32 = 32x32x16 with one query tile per wave (kept for A/B measurements).
 // (per index: hdb_set_option(ix, "mfma_variant", 16 | 32), passed down as `variant`)
 
+// The router: picks the shard and hands it the scan and ONE launch record (MfmaLaunch, hdb_common.h); every shard has the same
+// signature and reads what it needs.  The grids are rules of hdb_caps.h or the few lines below.
 // a.ntiles / a.tile_stride are in units of hdb_mfma_tile_rows(dtype, d) rows here.  q: the query fragments' source --
-// scaled fp16 copies (+ qscl) for fp16 matrices, the float32 queries themselves (qscl = nullptr) for fp32 ones.
+// scaled fp16 copies (+ qscl) for fp16 matrices, the float32 queries themselves for every other row type (the record's qscl is nullptr).
 // mode 2 = the whole call in one launch (hdb_mfma_kernel.h): f != nullptr, nq_launch <= hdb_mfma_batch_capacity(), grid = one
 // workgroup per CU at most (the in-kernel exchange needs the grid co-resident)
 extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q16, const float* sqnorm,
                                     const float* qsq, const float* qscl, int max_blocks, int variant, void* stream, const BatchArgs* f) {
     const int g_mfma_variant = variant == 32 ? 32 : variant == 64 ? 64 : 16;
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     if (a.mask) return (int)hipErrorNotSupported;
     const int cus = hdb_cu_count();                      // one persistent workgroup per CU ...
     // ... or, with max_blocks < 0, -max_blocks workgroups per CU: the hardware dispatcher then hands the next workgroup
@@ -108,58 +109,40 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
     if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
     if (blocks < 1) blocks = 1;
     if (mode == 2 && blocks > cus) blocks = cus;
-    if (hdb_mfma_ksplit_slices(dtype, a.d) > 0) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, stream);
+    MfmaLaunch l = {mode, nq_launch, q16, sqnorm, qsq, dtype == HDB_F16 ? qscl : nullptr, blocks, g_mfma_variant, 0, stream, f};
+    if (hdb_mfma_ksplit_slices(dtype, a.d) > 0) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_ksplit(args, dtype, &l);
     if (const int pad = hdb_mfma_anyd_pad(dtype, a.d)) {               // a width without a geometry of its own: one slice of the next wider one
         if (mode == 2) return (int)hipErrorNotSupported;
-        if (dtype == HDB_F16) return pad <= 384 ? hdb_launch_mfma_anyd_a(args, pad, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, stream)
-                                                : hdb_launch_mfma_anyd_b(args, pad, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, stream);
-        if (a.f32_split) return pad <= 384 ? hdb_launch_mfma_anyd_e(args, pad, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks, stream)
-                                           : hdb_launch_mfma_anyd_f(args, pad, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks, stream);
-        return pad <= 384 ? hdb_launch_mfma_anyd_c(args, pad, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks, stream)
-                          : hdb_launch_mfma_anyd_d(args, pad, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks, stream);
+        l.width = pad;
+        if (dtype == HDB_F16) return pad <= 384 ? hdb_launch_mfma_anyd_a(args, &l) : hdb_launch_mfma_anyd_b(args, &l);
+        if (a.f32_split) return pad <= 384 ? hdb_launch_mfma_anyd_e(args, &l) : hdb_launch_mfma_anyd_f(args, &l);
+        return pad <= 384 ? hdb_launch_mfma_anyd_c(args, &l) : hdb_launch_mfma_anyd_d(args, &l);
     }
-    if (dtype == HDB_F32) return (a.f32_split > 0 && hdb_mfma_f32_split_min_q(a.d) > 0) ? hdb_launch_mfma_scan_f32s(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f)
-                                                                                   : hdb_launch_mfma_scan_f32(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream, f);
-    if (dtype == HDB_F8E4M3) {          // float8 rows (hdb_mfma_f8.h): no LDS ring and 16-row tiles, a wave per tile -- up to four workgroups per CU
+    if (dtype == HDB_F32) return (a.f32_split > 0 && hdb_mfma_f32_split_min_q(a.d) > 0) ? hdb_launch_mfma_scan_f32s(args, &l) : hdb_launch_mfma_scan_f32(args, &l);
+    if (dtype == HDB_F8E4M3 || dtype == HDB_I8 || dtype == HDB_B1) {
+        // one-byte and packed-bit rows: the register kernels (hdb_mfma_f8.h; int8 with another row converter, hdb_mfma_i8.hip; packed
+        // bits when the plan asked, b1_mfma_min_q, hdb_mfma_b1.h) -- no LDS ring and 16-row tiles, a wave per tile, hdb_mfma_reg_blocks
         if (mode == 2) return (int)hipErrorNotSupported;
-        const bool ks8 = a.ks_partial_out && hdb_mfma_f8_ks_slices(a.d) > 0;
-        if (a.f8_lds) {                  // the plan asked for the rows to be expanded in LDS once per workgroup (f8_lds_min_q, hdb_mfma_f8_lds.h):
-            // a grid of stages, one or two workgroups per CU at most; every launcher takes min(its stages, this limit)
-            const int lim = max_blocks > 0 ? max_blocks : hdb_mfma_f8_lds_wg_per_cu(a.d, a.f8_lds) * cus;
-            if (ks8) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, lim, stream);
-            return hdb_launch_mfma_scan_f8_lds(args, mode, nq_launch, q16, sqnorm, qsq, lim, stream);
-        }
-        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
-        const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
+        l.blocks = hdb_mfma_reg_blocks(a.ntiles, cus, max_blocks);
+        if (dtype == HDB_I8) return hdb_launch_mfma_scan_i8(args, &l);
+        if (dtype == HDB_B1) return hdb_mfma_b1_ks_slices(a.d) > 0 ? hdb_launch_mfma_ksplit(args, dtype, &l) : hdb_launch_mfma_scan_b1(args, &l);
+        // float8 with the rows expanded in LDS once per workgroup (the plan asked, f8_lds_min_q, hdb_mfma_f8_lds.h): a grid of stages,
+        // one or two workgroups per CU at most; every launcher takes min(its stages, this limit)
+        if (a.f8_lds) l.blocks = max_blocks > 0 ? max_blocks : hdb_mfma_f8_lds_wg_per_cu(a.d, a.f8_lds) * cus;
         // rows wider than 512 elements: the plan asked for K slices (f8_ks_min_q) -- it alone hands such a call a partial-sum buffer
-        if (ks8) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
-        return hdb_launch_mfma_scan_f8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
+        if (a.ks_partial_out && hdb_mfma_f8_ks_slices(a.d) > 0) return hdb_launch_mfma_ksplit(args, dtype, &l);
+        return a.f8_lds ? hdb_launch_mfma_scan_f8_lds(args, &l) : hdb_launch_mfma_scan_f8(args, &l);
     }
-    if (dtype == HDB_I8) {              // int8 rows (hdb_mfma_i8.hip): the float8 register kernel with another row converter, and its grid
-        if (mode == 2) return (int)hipErrorNotSupported;
-        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
-        const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
-        return hdb_launch_mfma_scan_i8(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
-    }
-    if (dtype == HDB_B1) {              // packed-bit rows (hdb_mfma_b1.h; the plan asked, b1_mfma_min_q): the float8 register kernel's grid rule
-        if (mode == 2) return (int)hipErrorNotSupported;
-        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
-        const int blocks8 = (int)(a.ntiles < want8 ? (a.ntiles < 1 ? 1 : a.ntiles) : want8);
-        if (hdb_mfma_b1_ks_slices(a.d) > 0) return hdb_launch_mfma_ksplit(args, dtype, mode, nq_launch, q16, sqnorm, qsq, nullptr, blocks8, stream);
-        return hdb_launch_mfma_scan_b1(args, mode, nq_launch, q16, sqnorm, qsq, blocks8, stream);
-    }
-    if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, mode, nq_launch, q16, sqnorm, qsq, blocks, stream);
+    if (dtype == HDB_BF16) return mode == 2 ? (int)hipErrorNotSupported : hdb_launch_mfma_scan_bf16(args, &l);
     if (dtype != HDB_F16) return (int)hipErrorNotSupported;
     // (mode 2 promises hdb_mfma_batch_capacity() queries in ONE launch: only the two-tile launcher holds more than 128, whatever the variant)
-    if (nq_launch > 128 && hdb_mfma_qt2_supported(a.d) && (g_mfma_variant != 32 || (mode == 2 && a.d != 384)))
-        return hdb_launch_mfma_scan_f16_qt2(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, stream, f);
-    const int v = g_mfma_variant;
+    if (nq_launch > 128 && hdb_mfma_qt2_supported(a.d) && (g_mfma_variant != 32 || (mode == 2 && a.d != 384))) return hdb_launch_mfma_scan_f16_qt2(args, &l);
     switch (a.d) {
-        case 128: case 256: return hdb_launch_mfma_scan_f16_narrow(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, v, stream, f);
-        case 384: return hdb_launch_mfma_scan_f16_d384(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, v, stream, f);
-        case 512: case 640: case 768: return hdb_launch_mfma_scan_f16_mid(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, v, stream, f);
-        case 1024: case 1536: return hdb_launch_mfma_scan_f16_1k(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, v, stream, f);
-        default: return hdb_launch_mfma_scan_f16_wide(args, mode, nq_launch, q16, sqnorm, qsq, qscl, blocks, stream, f);     // 896, 1152, 1280, 1408
+        case 128: case 256: return hdb_launch_mfma_scan_f16_narrow(args, &l);
+        case 384: return hdb_launch_mfma_scan_f16_d384(args, &l);
+        case 512: case 640: case 768: return hdb_launch_mfma_scan_f16_mid(args, &l);
+        case 1024: case 1536: return hdb_launch_mfma_scan_f16_1k(args, &l);
+        default: return hdb_launch_mfma_scan_f16_wide(args, &l);     // 896, 1152, 1280, 1408
     }
 }
 
@@ -168,36 +151,23 @@ extern "C" int hdb_launch_q_to_f16(const float* Q, int nq, int d, void* q16, flo
     return (int)hipGetLastError();
 }
 
-extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V,
-                                         int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
-    const dim3 grid(64, nq_launch);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype != HDB_F16 && dtype != HDB_BF16 && dtype != HDB_F32 && dtype != HDB_F8E4M3 && dtype != HDB_I8 && dtype != HDB_B1) return (int)hipErrorNotSupported;      // (the dtypes of the matrix-core scan)
-    if (dtype == HDB_B1) {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<HdbB1Word, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const HdbB1Word*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<HdbB1Word, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const HdbB1Word*)V, d, Q, qsq, q0, bias);
-        return (int)hipGetLastError();
-    }
-    if (dtype == HDB_I8) {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_i8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_i8*)V, d, Q, qsq, q0, bias);
-        return (int)hipGetLastError();
-    }
-    if (dtype == HDB_F8E4M3) {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_f8, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_f8*)V, d, Q, qsq, q0, bias);
-        return (int)hipGetLastError();
-    }
-    if (dtype == HDB_F16) {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<_Float16, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const _Float16*)V, d, Q, qsq, q0, bias);
-    } else if (dtype == HDB_BF16) {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_bf16, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_bf16*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<hdb_bf16, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const hdb_bf16*)V, d, Q, qsq, q0, bias);
-    } else {
-        if (bias) hipLaunchKernelGGL((hdb_rescore_euclid_kernel<float, true>), grid, dim3(256), 0, st, cand, cnt, cap, (const float*)V, d, Q, qsq, q0, bias);
-        else hipLaunchKernelGGL((hdb_rescore_euclid_kernel<float, false>), grid, dim3(256), 0, st, cand, cnt, cap, (const float*)V, d, Q, qsq, q0, bias);
-    }
+// one row type of the re-score: the bias flavour, the launch
+template <typename T>
+static int launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int d, const float* Q,
+                                 const float* qsq, int q0, const float* bias, void* stream) {
+    auto kern = bias ? hdb_rescore_euclid_kernel<T, true> : hdb_rescore_euclid_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(64, nq_launch), dim3(256), 0, (hipStream_t)stream, cand, cnt, cap, (const T*)V, d, Q, qsq, q0, bias);
     return (int)hipGetLastError();
 }
-
+extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V,
+                                         int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
+    switch (dtype) {                    // (the dtypes of the matrix-core scan)
+        case HDB_B1: return launch_rescore_euclid<HdbB1Word>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        case HDB_I8: return launch_rescore_euclid<hdb_i8>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        case HDB_F8E4M3: return launch_rescore_euclid<hdb_f8>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        case HDB_F16: return launch_rescore_euclid<_Float16>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        case HDB_BF16: return launch_rescore_euclid<hdb_bf16>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        case HDB_F32: return launch_rescore_euclid<float>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
+        default: return (int)hipErrorNotSupported;
+    }
+}

@@ -130,42 +130,23 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
     }
 }
 
-// the grid of every launch: (workgroups, query-group rows); wq query groups per workgroup, the other waves take further tiles
-template <int D, int MODE, bool KSL>
-static int launch_b1_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
-    const int tq = (nq_launch + 15) / 16;
-    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;
-    const dim3 grid(blocks, (tq + wq - 1) / wq);
-    const int nq_end = a.q0 + nq_launch;
-    const bool b = a.bias != nullptr;
-#define HDB_B1_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_b1_kernel<D, MODE, METRIC_, BIAS_, KSL>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
-    if constexpr (MODE == 3) HDB_B1_GO(0, false, nullptr);
-    else {
-        if (a.metric == HDB_DOT) { if (b) HDB_B1_GO(0, true, nullptr); else HDB_B1_GO(0, false, nullptr); }
-        else if (a.metric == HDB_COSINE) { if (b) HDB_B1_GO(1, true, a.inv_norm); else HDB_B1_GO(1, false, a.inv_norm); }
-        else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_B1_GO(2, true, sqnorm); else HDB_B1_GO(2, false, sqnorm); }
-        else return (int)hipErrorNotSupported;
-    }
-#undef HDB_B1_GO
-    return (int)hipGetLastError();
-}
+// (the grid and the launch are the float8 register kernel's: launch_reg_kernel, hdb_mfma_f8.h)
 template <int D>
-static int launch_b1(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_b1(const ScanArgs& a, const MfmaLaunch& l) {
     // 4-byte row words (what hdb_index_create guarantees); a mask arrives folded into the bias
-    if ((reinterpret_cast<uintptr_t>(a.V) & 3) != 0 || a.d != D || a.mask || a.n < 1 || blocks < 1) return (int)hipErrorNotSupported;
-    if (mode == 0) return launch_b1_metric<D, 0, false>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_b1_metric<D, 1, false>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.V) & 3) != 0 || a.d != D || a.mask || a.n < 1 || l.blocks < 1) return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_reg_kernel(hdb_mfma_b1_kernel<D, mode.value, metric.value, bias.value != 0, false>, a, l, aux0);
+    });
 }
 // One K slice of a wide packed-bit row (hdb_mfma_ksplit.hip): mode 3 = raw partial sums out, 0 / 1 = the last slice with the metric's epilogue
 template <int D>
-static int launch_b1_kslice(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_b1_kslice(const ScanArgs& a, const MfmaLaunch& l) {
     // 4-byte row words: base, pitch (bytes) and slice offset (elements: whole words); float4 query and partial-sum accesses; the slice lies inside the row
     if ((reinterpret_cast<uintptr_t>(a.V) & 3) != 0 || (a.ks_pitch & 3) != 0 || (a.ks_off & 31) != 0 || a.ks_off < 0 ||
-        a.ks_off + D > a.ks_dfull || (int64_t)a.ks_dfull != a.ks_pitch * 8 || (a.ks_dfull & 3) != 0 || (a.ks_ld & 3) != 0 || a.mask || a.n < 1 || blocks < 1) return (int)hipErrorNotSupported;
-    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
-    if (mode == 3) return launch_b1_metric<D, 3, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 0) return launch_b1_metric<D, 0, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_b1_metric<D, 1, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+        a.ks_off + D > a.ks_dfull || (int64_t)a.ks_dfull != a.ks_pitch * 8 || (a.ks_dfull & 3) != 0 || (a.ks_ld & 3) != 0 || a.mask || a.n < 1 || l.blocks < 1) return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (l.mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0, 3>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_reg_kernel(hdb_mfma_b1_kernel<D, mode.value, metric.value, bias.value != 0, true>, a, l, aux0);
+    });
 }

@@ -4,10 +4,8 @@
 // Slices of 256 / 384 here, 512 in hdb_mfma_b1_ks_b.hip (translation units of their own so that the instantiations compile in parallel).
 #include "hdb_mfma_b1.h"
 
-extern "C" int hdb_launch_mfma_kslice_b1(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                         const float* qsq, int blocks, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (dslice == 256) return launch_b1_kslice<256>(*a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-    if (dslice == 384) return launch_b1_kslice<384>(*a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-    return hdb_launch_mfma_kslice_b1_wide(a, dslice, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+extern "C" int hdb_launch_mfma_kslice_b1(const ScanArgs* a, const MfmaLaunch* l) {
+    if (l->width == 256) return launch_b1_kslice<256>(*a, *l);
+    if (l->width == 384) return launch_b1_kslice<384>(*a, *l);
+    return hdb_launch_mfma_kslice_b1_wide(a, l);
 }

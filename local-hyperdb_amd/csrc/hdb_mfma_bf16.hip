@@ -7,13 +7,11 @@
 // wider rows go through K slices of these widths (hdb_mfma_bf16_ks.hip).
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_bf16(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                         const float* qsq, int blocks, void* stream) {
+extern "C" int hdb_launch_mfma_scan_bf16(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 128: return launch_mode01<hdb_bf16, 16, 1, 128, 64>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        case 256: return launch_mode01<hdb_bf16, 16, 1, 256, 64>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        default: return hdb_launch_mfma_scan_bf16_wide(args, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+        case 128: return launch_mode01<hdb_bf16, 16, 1, 128, 64>(a, *l);
+        case 256: return launch_mode01<hdb_bf16, 16, 1, 256, 64>(a, *l);
+        default: return hdb_launch_mfma_scan_bf16_wide(args, l);
     }
 }

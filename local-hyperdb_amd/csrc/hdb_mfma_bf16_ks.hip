@@ -6,10 +6,8 @@
 // Slices of 256 / 384 here, 512 in hdb_mfma_bf16_ks_b.hip (translation units of their own so that the instantiations compile in parallel).
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_kslice_bf16(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                           const float* qsq, int blocks, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (dslice == 256) return launch_kslice<hdb_bf16, 256, 16>(*a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st);
-    if (dslice == 384) return launch_kslice<hdb_bf16, 384, 16>(*a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st);
-    return hdb_launch_mfma_kslice_bf16_wide(a, dslice, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+extern "C" int hdb_launch_mfma_kslice_bf16(const ScanArgs* a, const MfmaLaunch* l) {
+    if (l->width == 256) return launch_kslice<hdb_bf16, 256, 16>(*a, *l);
+    if (l->width == 384) return launch_kslice<hdb_bf16, 384, 16>(*a, *l);
+    return hdb_launch_mfma_kslice_bf16_wide(a, l);
 }

@@ -7,18 +7,16 @@
 // (translation units of their own so that the instantiations compile in parallel).
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f32s(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                         const float* qsq, int blocks, void* stream, const BatchArgs* f) {
+extern "C" int hdb_launch_mfma_scan_f32s(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
         // (up to 64 queries: two waves per query group, each multiplying every other 16-row tile of the stage -- all eight waves multiply)
         case 128:
-            if (nq_launch <= 64) return launch_mode<hdb_f32s, 16, 1, 128, 64, 2>(a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, f);
-            return launch_mode<hdb_f32s, 16, 1, 128, 64>(a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, f);
+            if (l->nq_launch <= 64) return launch_mode<hdb_f32s, 16, 1, 128, 64, 2>(a, *l);
+            return launch_mode<hdb_f32s, 16, 1, 128, 64>(a, *l);
         case 256:
-            if (nq_launch <= 64) return launch_mode<hdb_f32s, 16, 1, 256, 32, 2>(a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, f);
-            return launch_mode<hdb_f32s, 16, 1, 256, 32>(a, mode, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, f);
-        default: return hdb_launch_mfma_scan_f32s_wide(args, mode, nq_launch, q, sqnorm, qsq, blocks, stream, f);
+            if (l->nq_launch <= 64) return launch_mode<hdb_f32s, 16, 1, 256, 32, 2>(a, *l);
+            return launch_mode<hdb_f32s, 16, 1, 256, 32>(a, *l);
+        default: return hdb_launch_mfma_scan_f32s_wide(args, l);
     }
 }

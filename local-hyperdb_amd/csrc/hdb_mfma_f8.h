@@ -196,56 +196,31 @@ __global__ __launch_bounds__(256, (KSL && D == 512 && MODE == 1) ? 2 : 1) void h
     }
 }
 
-template <int D, int MODE, typename CVT = HdbRowCvtF8>
-static int launch_f8_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
-    const int tq = (nq_launch + 15) / 16;
-    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;                              // query groups per workgroup; the other waves take further tiles
-    const dim3 grid(blocks, (tq + wq - 1) / wq);
-    const int nq_end = a.q0 + nq_launch;
-    const bool b = a.bias != nullptr;
-#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_, false, CVT>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
-    if (a.metric == HDB_DOT) { if (b) HDB_F8_GO(0, true, nullptr); else HDB_F8_GO(0, false, nullptr); }
-    else if (a.metric == HDB_COSINE) { if (b) HDB_F8_GO(1, true, a.inv_norm); else HDB_F8_GO(1, false, a.inv_norm); }
-    else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_F8_GO(2, true, sqnorm); else HDB_F8_GO(2, false, sqnorm); }
-    else return (int)hipErrorNotSupported;
-#undef HDB_F8_GO
+// One launch of a register kernel -- this one, its int8 flavour, the packed-bit one (hdb_mfma_b1.h): the same arguments and the
+// same grid, (workgroups, query-group rows) with wq query groups per workgroup; the other waves take further tiles
+template <typename K>
+static int launch_reg_kernel(K kern, const ScanArgs& a, const MfmaLaunch& l, const float* aux0) {
+    const int tq = (l.nq_launch + 15) / 16;
+    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;
+    const dim3 grid(l.blocks, (tq + wq - 1) / wq);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)l.stream, a, (const float*)l.q, aux0, l.qsq, a.q0 + l.nq_launch, wq);
     return (int)hipGetLastError();
 }
 template <int D, typename CVT = HdbRowCvtF8>
-static int launch_f8(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_f8(const ScanArgs& a, const MfmaLaunch& l) {
     if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || a.d != D || a.mask) return (int)hipErrorNotSupported;      // 8-byte fragment loads; a mask arrives folded into the bias
-    if (mode == 0) return launch_f8_metric<D, 0, CVT>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_f8_metric<D, 1, CVT>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_reg_kernel(hdb_mfma_f8_kernel<D, mode.value, metric.value, bias.value != 0, false, CVT>, a, l, aux0);
+    });
 }
-
 // One K slice of a wide float8 row (hdb_mfma_ksplit.hip): mode 3 = raw partial sums out, 0 / 1 = the last slice with the metric's epilogue
-template <int D, int MODE>
-static int launch_f8_kslice_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
-    const int tq = (nq_launch + 15) / 16;
-    const int wq = tq <= 1 ? 1 : tq <= 2 ? 2 : 4;
-    const dim3 grid(blocks, (tq + wq - 1) / wq);
-    const int nq_end = a.q0 + nq_launch;
-    const bool b = a.bias != nullptr;
-#define HDB_F8_GO(METRIC_, BIAS_, AUX_) hipLaunchKernelGGL((hdb_mfma_f8_kernel<D, MODE, METRIC_, BIAS_, true>), grid, dim3(256), 0, st, a, Qf, AUX_, qsq, nq_end, wq)
-    if constexpr (MODE == 3) HDB_F8_GO(0, false, nullptr);
-    else {
-        if (a.metric == HDB_DOT) { if (b) HDB_F8_GO(0, true, nullptr); else HDB_F8_GO(0, false, nullptr); }
-        else if (a.metric == HDB_COSINE) { if (b) HDB_F8_GO(1, true, a.inv_norm); else HDB_F8_GO(1, false, a.inv_norm); }
-        else if (a.metric == HDB_EUCLIDEAN) { if (b) HDB_F8_GO(2, true, sqnorm); else HDB_F8_GO(2, false, sqnorm); }
-        else return (int)hipErrorNotSupported;
-    }
-#undef HDB_F8_GO
-    return (int)hipGetLastError();
-}
 template <int D>
-static int launch_f8_kslice(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_f8_kslice(const ScanArgs& a, const MfmaLaunch& l) {
     // 8-byte fragment loads: base, pitch and slice offset; float4 query and partial-sum accesses; the slice lies inside the row
     if ((reinterpret_cast<uintptr_t>(a.V) & 7) != 0 || (a.ks_pitch & 7) != 0 || (a.ks_off & 7) != 0 || a.ks_off < 0 || a.ks_off + D > a.ks_pitch ||
         a.ks_dfull != a.ks_pitch || (a.ks_ld & 3) != 0 || a.mask) return (int)hipErrorNotSupported;
-    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
-    if (mode == 3) return launch_f8_kslice_metric<D, 3>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 0) return launch_f8_kslice_metric<D, 0>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_f8_kslice_metric<D, 1>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (l.mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0, 3>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_reg_kernel(hdb_mfma_f8_kernel<D, mode.value, metric.value, bias.value != 0, true>, a, l, aux0);
+    });
 }

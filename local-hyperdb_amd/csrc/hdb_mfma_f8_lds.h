@@ -143,48 +143,33 @@ __global__ __launch_bounds__(D == 512 ? 256 : 512) void hdb_mfma_f8_lds_kernel(S
 
 // blocks: the most workgroups the launch may take (max_blocks, or workgroups per CU x CUs); the grid is one workgroup per stage up to it
 template <int D, int MODE, int METRIC, bool HAS_BIAS, bool KSL>
-static int launch_f8_lds_one(const ScanArgs& a, const float* Qf, const float* aux0, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_f8_lds_one(const ScanArgs& a, const MfmaLaunch& l, const float* aux0) {
     auto kern = hdb_mfma_f8_lds_kernel<D, MODE, METRIC, HAS_BIAS, KSL>;
     static unsigned long long attr_done = 0;          // per instantiation, one bit per device
     const hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(kern), hdb_mfma_f8_lds_bytes(D, 8), &attr_done);      // (eight waves at d >= 384: beyond 64 KiB)
     if (e != hipSuccess) return (int)e;
     const int waves = hdb_mfma_f8_lds_waves(a.f8_lds, D);          // (d = 512: four waves whatever was asked for)
-    const int tq = (nq_launch + 15) / 16;
-    const dim3 grid(hdb_mfma_f8_lds_blocks(a.ntiles, D, waves, blocks), (tq + waves - 1) / waves);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), (size_t)hdb_mfma_f8_lds_bytes(D, waves), st, a, Qf, aux0, qsq, a.q0 + nq_launch);
+    const int tq = (l.nq_launch + 15) / 16;
+    const dim3 grid(hdb_mfma_f8_lds_blocks(a.ntiles, D, waves, l.blocks), (tq + waves - 1) / waves);
+    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), (size_t)hdb_mfma_f8_lds_bytes(D, waves), (hipStream_t)l.stream, a, (const float*)l.q, aux0, l.qsq, a.q0 + l.nq_launch);
     return (int)hipGetLastError();
 }
-template <int D, int MODE, bool KSL>
-static int launch_f8_lds_metric(const ScanArgs& a, const float* Qf, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
-    const bool b = a.bias != nullptr;
-    if constexpr (MODE == 3) return launch_f8_lds_one<D, 3, 0, false, KSL>(a, Qf, nullptr, qsq, nq_launch, blocks, st);
-    else {
-        if (a.metric == HDB_DOT) return b ? launch_f8_lds_one<D, MODE, 0, true, KSL>(a, Qf, nullptr, qsq, nq_launch, blocks, st)
-                                          : launch_f8_lds_one<D, MODE, 0, false, KSL>(a, Qf, nullptr, qsq, nq_launch, blocks, st);
-        if (a.metric == HDB_COSINE) return b ? launch_f8_lds_one<D, MODE, 1, true, KSL>(a, Qf, a.inv_norm, qsq, nq_launch, blocks, st)
-                                             : launch_f8_lds_one<D, MODE, 1, false, KSL>(a, Qf, a.inv_norm, qsq, nq_launch, blocks, st);
-        if (a.metric == HDB_EUCLIDEAN) return b ? launch_f8_lds_one<D, MODE, 2, true, KSL>(a, Qf, sqnorm, qsq, nq_launch, blocks, st)
-                                                : launch_f8_lds_one<D, MODE, 2, false, KSL>(a, Qf, sqnorm, qsq, nq_launch, blocks, st);
-        return (int)hipErrorNotSupported;
-    }
-}
 template <int D>
-static int launch_f8_lds(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_f8_lds(const ScanArgs& a, const MfmaLaunch& l) {
     // 16-byte pieces of whole rows; a mask arrives folded into the bias
-    if ((reinterpret_cast<uintptr_t>(a.V) & 15) != 0 || a.d != D || a.mask || a.ntiles < 1 || a.n < 1 || blocks < 1) return (int)hipErrorNotSupported;
-    if (mode == 0) return launch_f8_lds_metric<D, 0, false>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_f8_lds_metric<D, 1, false>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.V) & 15) != 0 || a.d != D || a.mask || a.ntiles < 1 || a.n < 1 || l.blocks < 1) return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_f8_lds_one<D, mode.value, metric.value, bias.value != 0, false>(a, l, aux0);
+    });
 }
 // One K slice of a wide float8 row (hdb_mfma_ksplit.hip): mode 3 = raw partial sums out, 0 / 1 = the last slice with the metric's epilogue
 template <int D>
-static int launch_f8_lds_kslice(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
+static int launch_f8_lds_kslice(const ScanArgs& a, const MfmaLaunch& l) {
     // 16-byte pieces: base, pitch and slice offset; float4 query and partial-sum accesses; the slice lies inside the row
     if ((reinterpret_cast<uintptr_t>(a.V) & 15) != 0 || (a.ks_pitch & 15) != 0 || (a.ks_off & 15) != 0 || a.ks_off < 0 || a.ks_off + D > a.ks_pitch ||
-        a.ks_dfull != a.ks_pitch || (a.ks_ld & 3) != 0 || a.mask || a.ntiles < 1 || a.n < 1 || blocks < 1) return (int)hipErrorNotSupported;
-    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
-    if (mode == 3) return launch_f8_lds_metric<D, 3, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 0) return launch_f8_lds_metric<D, 0, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    if (mode == 1) return launch_f8_lds_metric<D, 1, true>(a, (const float*)q, sqnorm, qsq, nq_launch, blocks, st);
-    return (int)hipErrorNotSupported;
+        a.ks_dfull != a.ks_pitch || (a.ks_ld & 3) != 0 || a.mask || a.ntiles < 1 || a.n < 1 || l.blocks < 1) return (int)hipErrorNotSupported;
+    if ((reinterpret_cast<uintptr_t>(a.ks_partial_in) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.ks_partial_out) & 15) != 0 || (l.mode == 3 && !a.ks_partial_out)) return (int)hipErrorNotSupported;
+    return hdb_mode_ladder<1, 0, 3>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_f8_lds_one<D, mode.value, metric.value, bias.value != 0, true>(a, l, aux0);
+    });
 }

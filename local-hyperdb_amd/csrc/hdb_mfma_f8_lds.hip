@@ -4,13 +4,11 @@
 // MODE 1 (filter).  d = 128 / 256 here, 384 / 512 in hdb_mfma_f8_lds_b.hip.
 #include "hdb_mfma_f8_lds.h"
 
-extern "C" int hdb_launch_mfma_scan_f8_lds(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                           const float* qsq, int blocks, void* stream) {
+extern "C" int hdb_launch_mfma_scan_f8_lds(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 128: return launch_f8_lds<128>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        case 256: return launch_f8_lds<256>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        default: return hdb_launch_mfma_scan_f8_lds_wide(args, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+        case 128: return launch_f8_lds<128>(a, *l);
+        case 256: return launch_f8_lds<256>(a, *l);
+        default: return hdb_launch_mfma_scan_f8_lds_wide(args, l);
     }
 }

@@ -2,13 +2,11 @@
 // queries take 144 / 192 registers.  A translation unit of its own so that the instantiations compile in parallel.
 #include "hdb_mfma_f8_lds.h"
 
-extern "C" int hdb_launch_mfma_scan_f8_lds_wide(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                                const float* qsq, int blocks, void* stream) {
+extern "C" int hdb_launch_mfma_scan_f8_lds_wide(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 384: return launch_f8_lds<384>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        case 512: return launch_f8_lds<512>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
+        case 384: return launch_f8_lds<384>(a, *l);
+        case 512: return launch_f8_lds<512>(a, *l);
         default: return (int)hipErrorNotSupported;
     }
 }

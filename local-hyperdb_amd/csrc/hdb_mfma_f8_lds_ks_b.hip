@@ -2,8 +2,7 @@
 // hdb_mfma_f8_lds_ks.hip): 192 registers of query parts.  A translation unit of its own so that the instantiations compile in parallel.
 #include "hdb_mfma_f8_lds.h"
 
-extern "C" int hdb_launch_mfma_kslice_f8_lds_wide(const ScanArgs* a, int dslice, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                                  const float* qsq, int blocks, void* stream) {
-    if (dslice == 512) return launch_f8_lds_kslice<512>(*a, mode, q, sqnorm, qsq, nq_launch, blocks, (hipStream_t)stream);
+extern "C" int hdb_launch_mfma_kslice_f8_lds_wide(const ScanArgs* a, const MfmaLaunch* l) {
+    if (l->width == 512) return launch_f8_lds_kslice<512>(*a, *l);
     return (int)hipErrorNotSupported;
 }

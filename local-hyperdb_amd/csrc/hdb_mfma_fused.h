@@ -1228,11 +1228,10 @@ static int launch_fused_one(const ScanArgs& a, const FusedArgs& f, const float* 
 
 template <typename E, int VQ, int D, int R>
 static int launch_fused(const ScanArgs& a, const FusedArgs& f, int blocks, hipStream_t st) {
-    const bool bias = a.bias != nullptr;
-    if (a.metric == HDB_DOT) return bias ? launch_fused_one<E, VQ, D, R, 0, true>(a, f, nullptr, blocks, st) : launch_fused_one<E, VQ, D, R, 0, false>(a, f, nullptr, blocks, st);
-    if (a.metric == HDB_COSINE) return bias ? launch_fused_one<E, VQ, D, R, 1, true>(a, f, a.inv_norm, blocks, st) : launch_fused_one<E, VQ, D, R, 1, false>(a, f, a.inv_norm, blocks, st);
-    if (a.metric == HDB_PEARSON) return bias ? launch_fused_one<E, VQ, D, R, 3, true>(a, f, a.inv_norm, blocks, st) : launch_fused_one<E, VQ, D, R, 3, false>(a, f, a.inv_norm, blocks, st);   // a.inv_norm carries 1/(sd_v d)
-    if constexpr (sizeof(E) == 4 || D != 768)       // euclidean: a.inv_norm carries ||v||^2 (set by the host; unused by the float32 flavour); fp16 d = 768 spills 3 registers with it
-        if (a.metric == HDB_EUCLIDEAN) return bias ? launch_fused_one<E, VQ, D, R, 2, true>(a, f, a.inv_norm, blocks, st) : launch_fused_one<E, VQ, D, R, 2, false>(a, f, a.inv_norm, blocks, st);
-    return (int)hipErrorNotSupported;
+    // a.inv_norm carries the per-row array of every metric here: 1/||v||, pearson's 1/(sd_v d), euclidean's ||v||^2 (set by the host;
+    // unused by the float32 flavour)
+    return hdb_metric_ladder<true>(a, a.inv_norm, [&](auto metric, auto bias, const float* aux0) {
+        if constexpr (metric.value == 2 && sizeof(E) != 4 && D == 768) return (int)hipErrorNotSupported;       // fp16 d = 768 spills 3 registers with euclidean
+        else return launch_fused_one<E, VQ, D, R, metric.value, bias.value != 0>(a, f, aux0, blocks, st);
+    });
 }

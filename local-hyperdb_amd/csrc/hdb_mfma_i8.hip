@@ -4,13 +4,11 @@
 // here, 384 / 512 in hdb_mfma_i8_b.hip.
 #include "hdb_mfma_f8.h"
 
-extern "C" int hdb_launch_mfma_scan_i8(const ScanArgs* args, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                       const float* qsq, int blocks, void* stream) {
+extern "C" int hdb_launch_mfma_scan_i8(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 128: return launch_f8<128, HdbRowCvtI8>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        case 256: return launch_f8<256, HdbRowCvtI8>(a, mode, q, sqnorm, qsq, nq_launch, blocks, st);
-        default: return hdb_launch_mfma_scan_i8_wide(args, mode, nq_launch, q, sqnorm, qsq, blocks, stream);
+        case 128: return launch_f8<128, HdbRowCvtI8>(a, *l);
+        case 256: return launch_f8<256, HdbRowCvtI8>(a, *l);
+        default: return hdb_launch_mfma_scan_i8_wide(args, l);
     }
 }

@@ -148,6 +148,37 @@ typedef __attribute__((address_space(1))) unsigned int hdb_gu32;
 
 template <int V> struct HdbIC { static constexpr int value = V; };
 
+// ---- the ladders of the launchers (host): run-time metric, bias and mode -> template arguments, written ONCE ----
+// The metric and bias ladder: go(HdbIC<METRIC>, HdbIC<HAS_BIAS>, aux0) with the per-row array the metric's epilogue reads -- dot (0)
+// none, cosine (1) a.inv_norm, euclidean (2) `sqnorm`; PEARSON (the single launches, hdb_mfma_fused.h) adds pearson (3) with
+// a.inv_norm.  Any other metric is hipErrorNotSupported.  `go` is a generic lambda that names the kernel.
+template <bool PEARSON = false, typename F>
+static int hdb_metric_ladder(const ScanArgs& a, const float* sqnorm, F&& go) {
+    const float* const none = nullptr;
+    const bool b = a.bias != nullptr;
+    if (a.metric == HDB_DOT) return b ? go(HdbIC<0>{}, HdbIC<1>{}, none) : go(HdbIC<0>{}, HdbIC<0>{}, none);
+    if (a.metric == HDB_COSINE) return b ? go(HdbIC<1>{}, HdbIC<1>{}, a.inv_norm) : go(HdbIC<1>{}, HdbIC<0>{}, a.inv_norm);
+    if constexpr (PEARSON)
+        if (a.metric == HDB_PEARSON) return b ? go(HdbIC<3>{}, HdbIC<1>{}, a.inv_norm) : go(HdbIC<3>{}, HdbIC<0>{}, a.inv_norm);
+    if (a.metric == HDB_EUCLIDEAN) return b ? go(HdbIC<2>{}, HdbIC<1>{}, sqnorm) : go(HdbIC<2>{}, HdbIC<0>{}, sqnorm);
+    return (int)hipErrorNotSupported;
+}
+// The mode ladder over it: go(HdbIC<MODE>, HdbIC<METRIC>, HdbIC<HAS_BIAS>, aux0) for a mode of the launcher's list MODES,
+// hipErrorNotSupported for any other.  Mode 3 -- the raw partial sums of a K slice -- has no metric: <3, 0, false> only.
+// (The lists are written last mode first -- <1, 0>, <1, 2, 0>, <1, 0, 3>: hipcc emits the kernels of the LAST mode of a list first,
+// and written so every unit keeps its kernels in the order 0, [2,] 1 or 3, 0, 1 that its code object has always had, byte for byte:
+// tools/device_code_identity.sh.  Which mode runs does not depend on the order.)
+template <int... MODES, typename F>
+static int hdb_mode_ladder(const ScanArgs& a, int mode, const float* sqnorm, F&& go) {
+    int rc = (int)hipErrorNotSupported;
+    auto one = [&](auto m) {
+        if constexpr (decltype(m)::value == 3) return go(m, HdbIC<0>{}, HdbIC<0>{}, (const float*)nullptr);
+        else return hdb_metric_ladder(a, sqnorm, [&](auto metric, auto bias, const float* aux0) { return go(m, metric, bias, aux0); });
+    };
+    (void)((mode == MODES && ((rc = one(HdbIC<MODES>{})), true)) || ...);
+    return rc;
+}
+
 // Element tag of the float32 row scan that multiplies in THREE bf16 PARTS (below): the bytes in memory are plain float32
 struct hdb_f32s { float x; __device__ __forceinline__ operator float() const { return x; } };
 typedef __bf16 hdb_bf16x8 __attribute__((ext_vector_type(8)));
@@ -1424,89 +1455,68 @@ static size_t mfma_batch_lds_bytes(int stage_bytes) {
 }
 
 template <typename E, int MF, int QT, int D, int R, int RS, int MODE, int METRIC, bool HAS_BIAS, int KP = 1>
-static int launch_one(const ScanArgs& a, const void* q16, const float* aux0, const float* qsq, const float* qscl, int nq_launch, int blocks, hipStream_t st,
-                      const BatchArgs* f) {
+static int launch_one(const ScanArgs& a, const MfmaLaunch& l, const float* aux0) {
     auto kern = hdb_mfma_kernel<E, MF, QT, D, R, RS, MODE, METRIC, HAS_BIAS, 8, false, KP>;
     const size_t lds = MODE == 2 ? mfma_batch_lds_bytes(R * D * (int)sizeof(E)) : mfma_lds_bytes(R * D * (int)sizeof(E));
     static unsigned long long attr_done = 0;          // per instantiation, one bit per device
     hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(kern), (int)lds, &attr_done);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(blocks, (nq_launch + (8 / RS / KP) * MF * QT - 1) / ((8 / RS / KP) * MF * QT));
+    const dim3 grid(l.blocks, (l.nq_launch + (8 / RS / KP) * MF * QT - 1) / ((8 / RS / KP) * MF * QT));
+    // mode 2 (the whole call in one launch) takes BatchArgs; q / qsq / qscl are unused there (the kernel prepares the queries)
+    const BatchArgs* f = MODE == 2 ? l.f : nullptr;
     if (MODE == 2 && (grid.y != 1 || !f || a.q0 != 0)) return (int)hipErrorInvalidValue;
     BatchArgs fa = BatchArgs();
     if (f) fa = *f;
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, a, (const E*)q16, aux0, qsq, qscl, a.q0 + nq_launch, fa);
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)l.stream, a, (const E*)l.q, aux0, l.qsq, l.qscl, a.q0 + l.nq_launch, fa);
     return (int)hipGetLastError();
 }
 
 // One K slice of a wide-row scan (hdb_mfma_ksplit.hip): mode 3 = raw partial sums out, 0 / 1 = the last slice with the metric's epilogue
 template <typename E, int D, int R, int MODE, int METRIC, bool HAS_BIAS, int KP = 1>
-static int launch_kslice_one(const ScanArgs& a, const void* q16, const float* aux0, const float* qsq, const float* qscl, int nq_launch, int blocks, hipStream_t st) {
+static int launch_kslice_one(const ScanArgs& a, const MfmaLaunch& l, const float* aux0) {
     auto kern = hdb_mfma_kernel<E, 16, 1, D, R, 1, MODE, METRIC, HAS_BIAS, 8, true, KP>;
     const size_t lds = mfma_lds_bytes(R * D * (int)sizeof(E));
     static unsigned long long attr_done = 0;
     hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(kern), (int)lds, &attr_done);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(blocks, (nq_launch + 8 / KP * 16 - 1) / (8 / KP * 16));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, a, (const E*)q16, aux0, qsq, qscl, a.q0 + nq_launch, BatchArgs());
+    const dim3 grid(l.blocks, (l.nq_launch + 8 / KP * 16 - 1) / (8 / KP * 16));
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)l.stream, a, (const E*)l.q, aux0, l.qsq, l.qscl, a.q0 + l.nq_launch, BatchArgs());
     return (int)hipGetLastError();
 }
-template <typename E, int D, int R, int KP = 1>
-static int launch_kslice(const ScanArgs& a, int mode, const void* q16, const float* sqnorm, const float* qsq, const float* qscl, int nq_launch, int blocks, hipStream_t st) {
-    if (mode == 3) return launch_kslice_one<E, D, R, 3, 0, false, KP>(a, q16, nullptr, qsq, qscl, nq_launch, blocks, st);
-    const bool b = a.bias != nullptr;
-#define HDB_KS_CASE(MODE_)                                                                                                                        \
-    if (a.metric == HDB_DOT) return b ? launch_kslice_one<E, D, R, MODE_, 0, true, KP>(a, q16, nullptr, qsq, qscl, nq_launch, blocks, st)              \
-                                      : launch_kslice_one<E, D, R, MODE_, 0, false, KP>(a, q16, nullptr, qsq, qscl, nq_launch, blocks, st);            \
-    if (a.metric == HDB_COSINE) return b ? launch_kslice_one<E, D, R, MODE_, 1, true, KP>(a, q16, a.inv_norm, qsq, qscl, nq_launch, blocks, st)        \
-                                         : launch_kslice_one<E, D, R, MODE_, 1, false, KP>(a, q16, a.inv_norm, qsq, qscl, nq_launch, blocks, st);      \
-    if (a.metric == HDB_EUCLIDEAN) return b ? launch_kslice_one<E, D, R, MODE_, 2, true, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st)         \
-                                            : launch_kslice_one<E, D, R, MODE_, 2, false, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st);
-    if (mode == 0) { HDB_KS_CASE(0) } else { HDB_KS_CASE(1) }
-#undef HDB_KS_CASE
-    return (int)hipErrorNotSupported;
+// MODES: 0, 1 and 3 for a slice of a wide row (launch_kslice); 0 and 1 for a padded row (launch_anyd, hdb_mfma_anyd.h)
+template <typename E, int D, int R, int KP, int... MODES>
+static int launch_kslice_modes(const ScanArgs& a, const MfmaLaunch& l) {
+    return hdb_mode_ladder<MODES...>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_kslice_one<E, D, R, mode.value, metric.value, bias.value != 0, KP>(a, l, aux0);
+    });
 }
+template <typename E, int D, int R, int KP = 1>
+static int launch_kslice(const ScanArgs& a, const MfmaLaunch& l) { return launch_kslice_modes<E, D, R, KP, 1, 0, 3>(a, l); }
 
 // the four-wave measurement variant of the filter pass (dot product, no bias)
 template <typename E, int MF, int QT, int D, int R>
-static int launch_four_waves(const ScanArgs& a, const void* q16, const float* qscl, int nq_launch, int blocks, hipStream_t st) {
+static int launch_four_waves(const ScanArgs& a, const MfmaLaunch& l) {
     auto kern = hdb_mfma_kernel<E, MF, QT, D, R, 1, 1, 0, false, 4>;
     const size_t lds = mfma_lds_bytes(R * D * (int)sizeof(E));
     static unsigned long long attr_done = 0;
     hipError_t e = hdb_lds_attr_once(reinterpret_cast<const void*>(kern), (int)lds, &attr_done);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid(blocks, (nq_launch + 4 * MF * QT - 1) / (4 * MF * QT));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a, (const E*)q16, nullptr, nullptr, qscl, a.q0 + nq_launch, BatchArgs());
+    const dim3 grid(l.blocks, (l.nq_launch + 4 * MF * QT - 1) / (4 * MF * QT));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)l.stream, a, (const E*)l.q, nullptr, nullptr, l.qscl, a.q0 + l.nq_launch, BatchArgs());
     return (int)hipGetLastError();
 }
 
-template <typename E, int MF, int QT, int D, int R, int RS, int MODE, int KP = 1>
-static int launch_metric(const ScanArgs& a, const void* q16, const float* sqnorm, const float* qsq, const float* qscl, int nq_launch, int blocks, hipStream_t st,
-                         const BatchArgs* f) {
-    const bool b = a.bias != nullptr;
-    if (a.metric == HDB_DOT) return b ? launch_one<E, MF, QT, D, R, RS, MODE, 0, true, KP>(a, q16, nullptr, qsq, qscl, nq_launch, blocks, st, f)
-                                      : launch_one<E, MF, QT, D, R, RS, MODE, 0, false, KP>(a, q16, nullptr, qsq, qscl, nq_launch, blocks, st, f);
-    if (a.metric == HDB_COSINE) return b ? launch_one<E, MF, QT, D, R, RS, MODE, 1, true, KP>(a, q16, a.inv_norm, qsq, qscl, nq_launch, blocks, st, f)
-                                         : launch_one<E, MF, QT, D, R, RS, MODE, 1, false, KP>(a, q16, a.inv_norm, qsq, qscl, nq_launch, blocks, st, f);
-    if (a.metric == HDB_EUCLIDEAN) return b ? launch_one<E, MF, QT, D, R, RS, MODE, 2, true, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f)
-                                            : launch_one<E, MF, QT, D, R, RS, MODE, 2, false, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-    return (int)hipErrorNotSupported;
+// a whole row of a geometry of its own, for the modes of the launcher's list
+template <typename E, int MF, int QT, int D, int R, int RS, int KP, int... MODES>
+static int launch_modes(const ScanArgs& a, const MfmaLaunch& l) {
+    return hdb_mode_ladder<MODES...>(a, l.mode, l.sqnorm, [&](auto mode, auto metric, auto bias, const float* aux0) {
+        return launch_one<E, MF, QT, D, R, RS, mode.value, metric.value, bias.value != 0, KP>(a, l, aux0);
+    });
 }
-
-// the multi-kernel pipeline only (bf16 rows): MODE 0 = scores, MODE 1 = filter; no single launch is instantiated
-template <typename E, int MF, int QT, int D, int R, int RS = 1>
-static int launch_mode01(const ScanArgs& a, int mode, const void* q, const float* sqnorm, const float* qsq, int nq_launch, int blocks, hipStream_t st) {
-    if (mode == 0) return launch_metric<E, MF, QT, D, R, RS, 0>(a, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, nullptr);
-    if (mode == 1) return launch_metric<E, MF, QT, D, R, RS, 1>(a, q, sqnorm, qsq, nullptr, nq_launch, blocks, st, nullptr);
-    return (int)hipErrorNotSupported;
-}
-
-// mode 2 (the whole call in one launch) takes BatchArgs; q16 / qsq / qscl are unused there (the kernel prepares the queries)
+// fp16 and float32 rows: MODE 0 = scores, MODE 1 = filter, MODE 2 = the whole call in one launch
 template <typename E, int MF, int QT, int D, int R, int RS = 1, int KP = 1>
-static int launch_mode(const ScanArgs& a, int mode, const void* q16, const float* sqnorm, const float* qsq, const float* qscl, int nq_launch, int blocks, hipStream_t st,
-                       const BatchArgs* f = nullptr) {
-    if (mode == 0) return launch_metric<E, MF, QT, D, R, RS, 0, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, nullptr);
-    if (mode == 2) return launch_metric<E, MF, QT, D, R, RS, 2, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-    return launch_metric<E, MF, QT, D, R, RS, 1, KP>(a, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, nullptr);
-}
+static int launch_mode(const ScanArgs& a, const MfmaLaunch& l) { return launch_modes<E, MF, QT, D, R, RS, KP, 1, 2, 0>(a, l); }
+// the multi-kernel pipeline only (bf16 rows): no single launch is instantiated
+template <typename E, int MF, int QT, int D, int R, int RS = 1>
+static int launch_mode01(const ScanArgs& a, const MfmaLaunch& l) { return launch_modes<E, MF, QT, D, R, RS, 1, 1, 0>(a, l); }
 

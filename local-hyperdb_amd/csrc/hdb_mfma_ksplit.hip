@@ -15,28 +15,27 @@
 
 // args->ks_partial_out: [nq_launch][ks_ld] float32 scratch of the caller (MODE 0 passes may alias it with args->scores: the last
 // slice overwrites the sums with the scores, element by element, by the lane that read them)
-extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, int mode, int nq_launch, const void* q, const float* sqnorm,
-                                      const float* qsq, const float* qscl, int blocks, void* stream) {
+// l: the launch as the router built it (mode: the last slice's; qscl: nullptr for every row type but fp16, whose queries alone are
+// scaled copies); every slice gets a copy with its own mode and width
+extern "C" int hdb_launch_mfma_ksplit(const ScanArgs* args, int dtype, const MfmaLaunch* l) {
     const KsGeom g = dtype == HDB_F8E4M3 ? ks_geom_f8(args->d) : dtype == HDB_B1 ? ks_geom_b1(args->d) : ks_geom(dtype, args->d);       // (float8, packed bits: the opt-in lists, no part of ks_geom)
     if (!g.slices || !args->ks_partial_out) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
     for (int s = 0; s < g.slices; ++s) {
         ScanArgs a = *args;
         a.ks_pitch = hdb_row_bytes(dtype, args->d); a.ks_off = g.off[s]; a.ks_dfull = args->d;
         if (dtype == HDB_B1) a.ks_off = g.off[s] * 8;         // (packed bits: the kernel takes the ELEMENT offset -- into the query as it is, an eighth of it into the row)
         a.ks_partial_in = s == 0 ? nullptr : args->ks_partial_out;
-        const int m = s + 1 < g.slices ? 3 : mode;
-        const int w = g.width[s];
+        MfmaLaunch sl = *l;
+        sl.mode = s + 1 < g.slices ? 3 : l->mode;
+        sl.width = g.width[s];
         int rc;
-        if (dtype == HDB_F8E4M3 && args->f8_lds) rc = hdb_launch_mfma_kslice_f8_lds(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (blocks: a limit, each slice sizes its own grid)
-        else if (dtype == HDB_F8E4M3) rc = hdb_launch_mfma_kslice_f8(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
-        else if (dtype == HDB_B1) rc = hdb_launch_mfma_kslice_b1(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
-        else if (dtype == HDB_BF16) rc = hdb_launch_mfma_kslice_bf16(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);       // (float32 queries as they are: no qscl)
-        else if (dtype == HDB_F32 && args->f32_split) rc = hdb_launch_mfma_kslice_f32s(&a, w, m, nq_launch, q, sqnorm, qsq, blocks, stream);
-        else if (dtype == HDB_F32) rc = w == 512 ? launch_kslice<float, 512, 16>(a, m, q, sqnorm, qsq, nullptr, nq_launch, blocks, st)
-                                                 : launch_kslice<float, 768, 16>(a, m, q, sqnorm, qsq, nullptr, nq_launch, blocks, st);
-        else rc = w == 1024 ? launch_kslice<_Float16, 1024, 16>(a, m, q, sqnorm, qsq, qscl, nq_launch, blocks, st)
-                            : launch_kslice<_Float16, 1536, 16>(a, m, q, sqnorm, qsq, qscl, nq_launch, blocks, st);
+        if (dtype == HDB_F8E4M3 && args->f8_lds) rc = hdb_launch_mfma_kslice_f8_lds(&a, &sl);       // (blocks: a limit, each slice sizes its own grid)
+        else if (dtype == HDB_F8E4M3) rc = hdb_launch_mfma_kslice_f8(&a, &sl);
+        else if (dtype == HDB_B1) rc = hdb_launch_mfma_kslice_b1(&a, &sl);
+        else if (dtype == HDB_BF16) rc = hdb_launch_mfma_kslice_bf16(&a, &sl);
+        else if (dtype == HDB_F32 && args->f32_split) rc = hdb_launch_mfma_kslice_f32s(&a, &sl);
+        else if (dtype == HDB_F32) rc = sl.width == 512 ? launch_kslice<float, 512, 16>(a, sl) : launch_kslice<float, 768, 16>(a, sl);
+        else rc = sl.width == 1024 ? launch_kslice<_Float16, 1024, 16>(a, sl) : launch_kslice<_Float16, 1536, 16>(a, sl);
         if (rc) return rc;
     }
     return 0;

@@ -2,12 +2,9 @@
 // the geometries compile in parallel (each carries 3 modes x 3 metrics x {bias, no bias} kernels).
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f16_narrow(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-        const float* qsq, const float* qscl, int blocks, int variant, void* stream, const BatchArgs* f) {
+extern "C" int hdb_launch_mfma_scan_f16_narrow(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
-    (void)variant;
-    if (a.d == 128) return launch_mode<_Float16, 16, 1, 128, 64>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-    if (a.d == 256) return launch_mode<_Float16, 16, 1, 256, 64>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
+    if (a.d == 128) return launch_mode<_Float16, 16, 1, 128, 64>(a, *l);
+    if (a.d == 256) return launch_mode<_Float16, 16, 1, 256, 64>(a, *l);
     return (int)hipErrorNotSupported;
 }

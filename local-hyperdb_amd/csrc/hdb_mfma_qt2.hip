@@ -3,15 +3,13 @@
 // 129..256 queries then reads V once instead of once per 128 queries.  d = 768 spills with two tiles and keeps one.
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                            const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f) {
+extern "C" int hdb_launch_mfma_scan_f16_qt2(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 128: return launch_mode<_Float16, 16, 2, 128, 64>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 256: return launch_mode<_Float16, 16, 2, 256, 64>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 512: return launch_mode<_Float16, 16, 2, 512, 32>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 640: return launch_mode<_Float16, 16, 2, 640, 32>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
+        case 128: return launch_mode<_Float16, 16, 2, 128, 64>(a, *l);
+        case 256: return launch_mode<_Float16, 16, 2, 256, 64>(a, *l);
+        case 512: return launch_mode<_Float16, 16, 2, 512, 32>(a, *l);
+        case 640: return launch_mode<_Float16, 16, 2, 640, 32>(a, *l);
         default: return (int)hipErrorNotSupported;
     }
 }

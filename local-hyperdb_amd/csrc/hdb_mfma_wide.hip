@@ -3,15 +3,13 @@
 // compile in parallel with hdb_mfma.hip.
 #include "hdb_mfma_kernel.h"
 
-extern "C" int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, int mode, int nq_launch, const void* q16, const float* sqnorm,
-                                             const float* qsq, const float* qscl, int blocks, void* stream, const BatchArgs* f) {
+extern "C" int hdb_launch_mfma_scan_f16_wide(const ScanArgs* args, const MfmaLaunch* l) {
     const ScanArgs& a = *args;
-    hipStream_t st = (hipStream_t)stream;
     switch (a.d) {
-        case 896: return launch_mode<_Float16, 16, 1, 896, 16>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 1152: return launch_mode<_Float16, 16, 1, 1152, 16>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 1280: return launch_mode<_Float16, 16, 1, 1280, 16>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
-        case 1408: return launch_mode<_Float16, 16, 1, 1408, 16>(a, mode, q16, sqnorm, qsq, qscl, nq_launch, blocks, st, f);
+        case 896: return launch_mode<_Float16, 16, 1, 896, 16>(a, *l);
+        case 1152: return launch_mode<_Float16, 16, 1, 1152, 16>(a, *l);
+        case 1280: return launch_mode<_Float16, 16, 1, 1280, 16>(a, *l);
+        case 1408: return launch_mode<_Float16, 16, 1, 1408, 16>(a, *l);
         default: return (int)hipErrorNotSupported;
     }
 }

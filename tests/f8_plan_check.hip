@@ -4,7 +4,8 @@
 //    (sign, exponent - 7, mantissa / 8; exponent 0 = subnormal; 0x7F / 0xFF = NaN), computed here with ldexp;
 // 2) the capability rules (csrc/hdb_caps.h): the matrix cores take d = 128 / 256 / 384 / 512 in 16-row tiles and nothing else (no
 //    padded widths, no K slices), no single launch, no LDS tile kernel for any width; the grid of the VALU scan grows for 256- /
-//    384- / 512-byte rows and is what it was for every other dtype and width;
+//    384- / 512-byte rows and is what it was for every other dtype and width; the register kernels' grid (hdb_mfma_reg_blocks) is
+//    max_blocks or four workgroups per CU, at most the tiles, at least one;
 // 3) plan_topk (csrc/hdb_plan.h) over n x d x nq x k x metric x bias / mask x finite x exact x options: never the shadow, the plane,
 //    a matrix-core single launch or the tile kernel; the matrix cores EXACTLY for 5 or more dot / cosine / euclidean / pearson
 //    queries on a finite matrix of the four widths above 8 192 rows with use_mfma on (the finiteness is asked exactly where it
@@ -70,6 +71,14 @@ int main() {
           hdb_scan_auto_blocks(HDB_F8E4M3, 272, true, false) == 512 && hdb_scan_auto_blocks(HDB_F8E4M3, 100, false, false) == 512, "other float8 rows");
     for (int dt : {(int)HDB_F16, (int)HDB_F32, (int)HDB_F64, (int)HDB_BF16}) for (int rb : {256, 384, 512, 768, 1536, 3072})
         CHECK(hdb_scan_auto_blocks(dt, rb, true, false) == 512 && hdb_scan_auto_blocks(dt, rb, true, true) == 256, "dtype %d, %d-byte rows", dt, rb);
+
+    // the grid of the register kernels (float8, int8, packed bits): the rule against the expression the router spelled out three times
+    for (int cus : {1, 256}) for (int max_blocks : {-2, 0, 1, 7, 5000})
+    for (int64_t ntiles : {(int64_t)0, (int64_t)1, (int64_t)3, (int64_t)4 * cus - 1, (int64_t)4 * cus, (int64_t)4 * cus + 1, (int64_t)10000000}) {
+        const int64_t want8 = max_blocks > 0 ? max_blocks : 4 * (int64_t)cus;
+        const int blocks8 = (int)(ntiles < want8 ? (ntiles < 1 ? 1 : ntiles) : want8);
+        CHECK(hdb_mfma_reg_blocks(ntiles, cus, max_blocks) == blocks8 && blocks8 >= 1, "ntiles %lld cus %d max_blocks %d", (long long)ntiles, cus, max_blocks);
+    }
 
     // ---- 3: the planner ----
     long plans = 0;

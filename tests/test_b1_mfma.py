@@ -301,3 +301,12 @@ def test_base_aligned_to_four_bytes_only(d):
     finally:
         odd.close()
         even.close()
+
+
+# every packed-bit shard launcher of the matrix-core scan x {dot, cosine, euclidean} x {no bias, bias} (tests/launcher_cells.py;
+# profiles/mfma_launch_coverage.txt): whole rows and K slices (d = 640: slices of 384 / 256, d = 1024: of 512); 5 queries and 17,
+# where the register kernel's query groups per workgroup go from one to two
+@pytest.mark.parametrize("d,nq", [(128, 5), (128, 17), (256, 5), (384, 5), (512, 5), (512, 17), (640, 5), (640, 17), (1024, 5)])
+def test_every_b1_launcher_metric_and_bias(orc, d, nq):
+    import launcher_cells
+    launcher_cells.check_launcher_cells(orc, "b1", d, nq, {"b1_mfma_min_q": 5}, TOL, {"mfma": 1, "fused": 0})

@@ -499,3 +499,11 @@ def test_facade_bfloat16_two_devices():
     _same_answers(two.query(Q[0], top_k=10), one.query(Q[0], top_k=10))
     for got, want in zip(two.query_batch(Q, top_k=10), one.query_batch(Q, top_k=10)):
         _same_answers(got, want)
+
+
+# every bfloat16 shard launcher of the matrix-core scan x {dot, cosine, euclidean} x {no bias, bias} (tests/launcher_cells.py;
+# profiles/mfma_launch_coverage.txt): whole rows 128 / 256 and 384 / 512, K slices of 256 / 384 (d = 640) and of 512 (d = 1024, 4096)
+@pytest.mark.parametrize("d", [128, 256, 384, 512, 640, 1024, 4096])
+def test_every_bf16_launcher_metric_and_bias(orc, d):
+    import launcher_cells
+    launcher_cells.check_launcher_cells(orc, "bf16", d, 5, {"bf16_ks_min_q": 5}, TOL, {"mfma": 1, "fused": 0})

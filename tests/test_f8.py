@@ -568,3 +568,18 @@ def test_two_shards_on_one_device(ranking):
     finally:
         one.close()
         two.close()
+
+
+# every float8 shard launcher of the matrix-core scan x {dot, cosine, euclidean} x {no bias, bias} (tests/launcher_cells.py;
+# profiles/mfma_launch_coverage.txt): registers and LDS, whole rows and K slices (d = 640: slices of 384 / 256, d = 1024: of 512);
+# 5 queries and 17, where the register kernels' query groups per workgroup go from one to two
+_F8_LAUNCHERS = [("regs", d, nq, {}, 0) for d in (128, 256, 384, 512) for nq in (5, 17)] + \
+                [("regs-kslice", d, nq, {"f8_ks_min_q": 5}, 0) for d in (640, 1024) for nq in (5, 17)] + \
+                [("lds", d, 5, {"f8_lds_min_q": 5}, 1) for d in (128, 256, 384, 512)] + \
+                [("lds-kslice", d, 17, {"f8_ks_min_q": 5, "f8_lds_min_q": 5}, 1) for d in (640, 1024)]
+
+
+@pytest.mark.parametrize("launcher,d,nq,opts,lds", _F8_LAUNCHERS, ids=[f"{c[0]}-{c[1]}-{c[2]}" for c in _F8_LAUNCHERS])
+def test_every_f8_launcher_metric_and_bias(orc, launcher, d, nq, opts, lds):
+    import launcher_cells
+    launcher_cells.check_launcher_cells(orc, "f8", d, nq, opts, TOL, {"mfma": 1, "fused": 0, "f8_lds": lds})

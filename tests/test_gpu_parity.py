@@ -2239,3 +2239,37 @@ def test_bits_local_flavour_equals_the_exchange_and_reports_clusters(n, d):
         assert float(hs[0][0]) == d and float(hs[0][20]) == d - 20
     finally:
         ix.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# every fp16 / float32 shard launcher of the matrix-core scan x {dot, cosine, euclidean} x {no bias, bias} (tests/launcher_cells.py;
+# profiles/mfma_launch_coverage.txt): the narrowest and the widest width of each launcher, 5 queries; 129 where two query tiles ride
+# ------------------------------------------------------------------------------------------------
+_F16_LAUNCHERS = [("narrow", 128, 5, {}), ("narrow", 256, 5, {}), ("d384", 384, 5, {}), ("d384-two-tiles", 384, 129, {}),
+                  ("d384-variant32", 384, 129, {"mfma_variant": 32}), ("mid", 512, 5, {}), ("mid", 768, 5, {}), ("wide", 896, 5, {}),
+                  ("wide", 1408, 5, {}), ("1k", 1024, 5, {}), ("1k", 1536, 5, {}), ("qt2", 128, 129, {}), ("qt2", 640, 129, {}),
+                  ("ksplit", 2048, 5, {}), ("ksplit", 4096, 5, {}), ("anyd_a", 96, 5, {}), ("anyd_a", 296, 5, {}), ("anyd_b", 504, 5, {}),
+                  ("anyd_b", 1000, 5, {})]
+
+
+@pytest.mark.parametrize("launcher,d,nq,opts", _F16_LAUNCHERS, ids=[f"{c[0]}-{c[1]}-{c[2]}" for c in _F16_LAUNCHERS])
+def test_every_fp16_launcher_metric_and_bias(orc, launcher, d, nq, opts):
+    import launcher_cells
+    launcher_cells.check_launcher_cells(orc, "f16", d, nq, dict(opts, use_batch1=0), 1e-3, {"mfma": 1, "fused": 0})
+
+
+_F32 = {"f32_split": 0}
+_F32S = {"f32_split": 1, "f32_split_min_q": 5}
+_F32_LAUNCHERS = [("f32", 128, _F32, 0), ("f32", 256, _F32, 0), ("f32_wide", 384, _F32, 0), ("f32_wide", 768, _F32, 0),
+                  ("f32s", 128, _F32S, 1), ("f32s", 256, _F32S, 1), ("f32s_wide", 384, _F32S, 1), ("f32s_wide", 768, _F32S, 1),
+                  ("ksplit", 1024, _F32, 0), ("ksplit", 1536, _F32, 0), ("kslice_f32s", 1024, _F32S, 1), ("kslice_f32s", 1536, _F32S, 1),
+                  ("anyd_c", 100, _F32, 0), ("anyd_c", 300, _F32, 0), ("anyd_d", 400, _F32, 0), ("anyd_d", 600, _F32, 0),
+                  ("anyd_e", 100, _F32S, 1), ("anyd_e", 300, _F32S, 1), ("anyd_f", 400, _F32S, 1), ("anyd_f", 600, _F32S, 1)]
+
+
+@pytest.mark.parametrize("launcher,d,opts,split", _F32_LAUNCHERS, ids=[f"{c[0]}-{c[1]}" for c in _F32_LAUNCHERS])
+def test_every_float32_launcher_metric_and_bias(orc, launcher, d, opts, split):
+    import launcher_cells
+    # (the plan multiplies dot_product in float32 whatever the option says: the bf16-part launchers have no dot cell to reach)
+    stats = {"mfma": 1, "fused": 0, "f32_split": {"dot_product": 0, "cosine_similarity": split, "euclidean_metric": split}}
+    launcher_cells.check_launcher_cells(orc, "f32", d, 5, dict(opts, use_batch1=0), 1e-5, stats)

@@ -421,3 +421,12 @@ def test_facade_int8(tmp_path, orc):
     assert back.vectors.dtype == np.float32 and np.array_equal(back.vectors, db.vectors)
     a, b = back.query(Q[1], top_k=10), db.query(Q[1], top_k=10)
     assert [r[2] for r in a] == [r[2] for r in b] and [float(r[1]) for r in a] == [float(r[1]) for r in b]
+
+
+# both int8 shard launchers of the matrix-core scan x {dot, cosine, euclidean} x {no bias, bias} (tests/launcher_cells.py;
+# profiles/mfma_launch_coverage.txt); 5 queries and 17, where the register kernel's query groups per workgroup go from one to two
+@pytest.mark.parametrize("nq", [5, 17])
+@pytest.mark.parametrize("d", [128, 256, 384, 512])
+def test_every_i8_launcher_metric_and_bias(orc, d, nq):
+    import launcher_cells
+    launcher_cells.check_launcher_cells(orc, "i8", d, nq, {}, TOL, {"mfma": 1, "fused": 0})
