@@ -186,7 +186,7 @@ __device__ __forceinline__ uint32_t hdb_finalize_body(unsigned long long* buf, c
 // needs no LDS copy of the list, no separate min/max pass and no copy-back: four barriers instead of eleven
 // (profiles/r4_finalize_fast.txt).  Loads -> per-wave min/max (DPP) -> 1024 shift bins between the smallest and the largest key ->
 // wave 0 alone scans the bins from the top -> entries in or above the bin of the kk-th largest go to a short LDS list -> rank sort.
-// Anything else (more than 8 entries per thread, a fix-up functor, very short or very tie-heavy lists) takes hdb_finalize_body;
+// Anything else (more than 16 entries per thread -- NE; 4096 / 8192 entries at 256 / 512 threads --, a fix-up functor, very short or very tie-heavy lists) takes hdb_finalize_body;
 // both produce identical results (the survivors always contain the true top-kk; the order is the total order of the packed entries).
 // `have_floor_key`: the caller passes the floor as an orderable key of the SCORE domain instead of floor_ptr / floor_mul.
 // LDS: hist (1024 u32) | wave minima / maxima (32 u32) | ctl (16 u32) | survivors (1024 u64) = 12.5 KiB at `buf`.
