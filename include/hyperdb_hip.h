@@ -610,7 +610,15 @@ void hdb_group_destroy(hdb_group* g);
  *   use_fused (0: never the single-launch pipeline), fused_timeout_us (bound of its in-kernel spins, default 2000),
  *   host_poll (0: hdb_topk_host always waits on the stream instead of polling the status words of a pinned record),
  *   dyn_tiles (0: the batched MFMA filter pass always splits its tiles statically; default 1 = tiles from a counter for
- *   long passes over rows of >= 768 bytes with up to 64 queries).
+ *   long passes over rows of >= 768 bytes with up to 64 queries), dyn_min_mb (... for passes of at least this many MiB of V per
+ *   workgroup, default 16, >= 0), dyn_heavy (1: also when all eight waves multiply; default 0),
+ *   bits_local (0: the bit metrics' single launch never takes its local flavour, every workgroup its own threshold).
+ *   The local flavour of the 1-4-query single launch (short matrices: no row sample, no exchange): use_local (0: never), local_m
+ *   (rows every workgroup emits at least, 0 = automatic, 0 .. 64), local_max_tiles (tiles per workgroup up to which it is taken,
+ *   default 4, >= 1), local_small (1: also on matrices of up to 8192 rows), local_max_q (calls of up to this many queries, default 1).
+ *   The row list (hdb_index_set_row_subset, above): use_subset (0: never the list -- the mask), subset_min_n (matrices of at least
+ *   this many rows; -1, also for any negative value: the measured rule), subset_ratio (the list while m * ceil(nq / 4) *
+ *   subset_ratio <= n; -1, also for any negative value: the measured rule; otherwise at least 1).
  *   Dispatch of few-query calls (-1 = the measured rule): fused_max_q (the 1-4-query single launch takes
  *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bf16_ks_min_q
  *   (bfloat16 rows wider than 512 elements: K slices from this many queries on, never fewer than 5), f8_ks_min_q (float8 rows wider
@@ -639,7 +647,9 @@ void hdb_group_destroy(hdb_group* g);
  *   maxsim_team (hdb_maxsim_host: lanes per group of its reduction, 0 = the rule, 1 | 4 | 16 | 64).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
- *   2 the batched single launch, 3 the bit-metric single launch), host_direct, chunks, sample_rows, sample_m,
+ *   2 the batched single launch, 3 the bit-metric single launch), local (1: that single launch in its local flavour), f32_split
+ *   (1: a float32 batch multiplied as bf16 parts), f8_lds (1: float8 rows expanded in LDS), subset (1: the last call scored from
+ *   the row list), host_direct, chunks, sample_rows, sample_m,
  *   scan_launches, scan_time_ns (sum over the profiled launches), cand_cap, n, ws_bytes, quant, quant_cands, quant_cands_min, quant_cands_median,
  *   quant_bytes, quant_auto, plane, plane_bytes, plane_survivors, plane_overflows, plane_blocks (workgroups of the last call's
  *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second

@@ -560,125 +560,52 @@ extern "C" int hdb_index_set_groups(hdb_index* ix, const int32_t* dev_groups, in
 
 extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(HDB_ERR_ARG, "hdb_set_option: null argument");
-    if (!strcmp(name, "max_blocks")) ix->opt.max_blocks = value;
-    else if (!strcmp(name, "force_exact")) ix->opt.force_exact = value;
-    else if (!strcmp(name, "sample_target")) ix->opt.sample_target = value;
-    else if (!strcmp(name, "mfma_min_q")) ix->opt.mfma_min_q = value;
-    else if (!strcmp(name, "use_mfma")) ix->opt.use_mfma = value;
-    else if (!strcmp(name, "exact_bytes")) ix->opt.exact_bytes = std::max<int64_t>(1 << 20, value);
-    else if (!strcmp(name, "finalize_threads")) { if (value == 256 || value == 512 || value == 1024) ix->opt.finalize_threads = value; }
-    else if (!strcmp(name, "mfma_variant")) { if (value == 16 || value == 32 || value == 64) ix->opt.mfma_variant = value; }
-    else if (!strcmp(name, "host_direct")) ix->opt.host_direct = value;
-    else if (!strcmp(name, "use_fused")) ix->opt.use_fused = value;
-    else if (!strcmp(name, "use_batch1")) ix->opt.use_batch1 = value;
-    else if (!strcmp(name, "use_local")) ix->opt.use_local = value;
-    else if (!strcmp(name, "local_max_q")) ix->opt.local_max_q = value;
-    else if (!strcmp(name, "local_max_tiles")) ix->opt.local_max_tiles = std::max<int64_t>(1, value);
-    else if (!strcmp(name, "local_small")) ix->opt.local_small = value;
-    else if (!strcmp(name, "local_m")) ix->opt.local_m = std::max<int64_t>(0, std::min<int64_t>(value, 64));
-    else if (!strcmp(name, "use_l1_tile")) ix->opt.use_l1_tile = value;
-    else if (!strcmp(name, "l1_packed")) ix->opt.l1_packed = value;
-    else if (!strcmp(name, "host_poll")) ix->opt.host_poll = value;
-    else if (!strcmp(name, "dyn_tiles")) ix->opt.dyn_tiles = value;
-    else if (!strcmp(name, "dyn_min_mb")) ix->opt.dyn_min_mb = std::max<int64_t>(0, value);
-    else if (!strcmp(name, "dyn_heavy")) ix->opt.dyn_heavy = value;
-    else if (!strcmp(name, "fused_timeout_us")) ix->opt.fused_timeout_us = std::max<int64_t>(1, value);
-    else if (!strcmp(name, "bits_fused")) ix->opt.bits_fused = value;
-    else if (!strcmp(name, "bits_local")) ix->opt.bits_local = value;
-    else if (!strcmp(name, "fused_max_q")) ix->opt.fused_max_q = value;
-    else if (!strcmp(name, "f32_min_q")) ix->opt.f32_min_q = value;
-    else if (!strcmp(name, "f32_split")) ix->opt.f32_split = value;
-    else if (!strcmp(name, "f32_split_min_q")) ix->opt.f32_split_min_q = value;
-    else if (!strcmp(name, "bf16_ks_min_q")) ix->opt.bf16_ks_min_q = value;
-    else if (!strcmp(name, "f8_ks_min_q")) ix->opt.f8_ks_min_q = value < 0 ? -1 : value;
-    else if (!strcmp(name, "f8_lds_min_q")) ix->opt.f8_lds_min_q = value < 0 ? -1 : value;
-    else if (!strcmp(name, "b1_mfma_min_q")) ix->opt.b1_mfma_min_q = value < 0 ? -1 : value;
-    else if (!strcmp(name, "bf16_quant")) ix->opt.bf16_quant = value ? 1 : 0;
-    else if (!strcmp(name, "f8_lds_waves")) { if (value == 0 || value == 4 || value == 8) ix->opt.f8_lds_waves = value; }
-    else if (!strcmp(name, "bits_max_q")) ix->opt.bits_max_q = value;
-    else if (!strcmp(name, "use_quant")) ix->opt.use_quant = value;
-    else if (!strcmp(name, "quant_min_n")) ix->opt.quant_min_n = value;
-    else if (!strcmp(name, "auto_quant")) ix->opt.auto_quant = value;
-    else if (!strcmp(name, "quant_batch_min_n")) ix->opt.quant_batch_min_n = value;
-    else if (!strcmp(name, "quant_batch_kernel")) ix->opt.quant_batch_kernel = value ? 1 : 0;
-    else if (!strcmp(name, "quant_max_k")) ix->opt.quant_max_k = std::max<int64_t>(1, std::min<int64_t>(value, 128));
-    else if (!strcmp(name, "use_plane")) ix->opt.use_plane = value;
-    else if (!strcmp(name, "plane_min_n")) ix->opt.plane_min_n = value;
-    else if (!strcmp(name, "plane_cap_rows")) ix->opt.plane_cap_rows = std::max<int64_t>(0, value);
-    else if (!strcmp(name, "plane_wg_per_cu")) ix->opt.plane_wg_per_cu = std::max<int64_t>(0, std::min<int64_t>(value, 8));
-    else if (!strcmp(name, "use_subset")) ix->opt.use_subset = value;
-    else if (!strcmp(name, "subset_min_n")) ix->opt.subset_min_n = value < 0 ? -1 : value;
-    else if (!strcmp(name, "subset_ratio")) ix->opt.subset_ratio = value < 0 ? -1 : std::max<int64_t>(1, value);
-    else if (!strcmp(name, "rerank_chunk")) ix->opt.rerank_chunk = std::max<int64_t>(0, std::min<int64_t>(value, HDB_RERANK_MAXQ));
-    else if (!strcmp(name, "group_oversample")) ix->opt.group_oversample = std::max<int64_t>(1, std::min<int64_t>(value, HDB_GROUP_OVERSAMPLE_MAX));
-    else if (!strcmp(name, "group_fast_rounds")) ix->opt.group_fast_rounds = std::max<int64_t>(0, std::min<int64_t>(value, HDB_GROUP_ROUNDS_MAX));
-    else if (!strcmp(name, "maxsim_team")) { if (value == 0 || value == 1 || value == 4 || value == 16 || value == 64) ix->opt.maxsim_team = value; }
-    else if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
+    // (the two names that are no member of hdb_options; every other name and its rule: HDB_OPTIONS, hdb_plan.h)
+    if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
-    else return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
+    else if (!hdb_option_set(ix->opt, name, value)) return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
+    return HDB_OK;
+}
+
+// the statistics that live in device words: wait for the device, then copy `bytes` of them to the host
+static int read_device_stat(hdb_index* ix, void* dst, const void* src, size_t bytes) {
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return HDB_OK;
 }
 
 extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     if (!ix || !name || !value) return fail(HDB_ERR_ARG, "hdb_get_stat: null argument");
-    if (!strcmp(name, "sample_rows")) *value = ix->st.sample_rows;
-    else if (!strcmp(name, "sample_m")) *value = ix->st.sample_m;
-    else if (!strcmp(name, "path")) *value = ix->st.path;
-    else if (!strcmp(name, "chunks")) *value = ix->st.chunks;
-    else if (!strcmp(name, "mfma")) *value = ix->st.mfma;
-    else if (!strcmp(name, "f32_split")) *value = ix->st.f32s;
-    else if (!strcmp(name, "f8_lds")) *value = ix->st.f8_lds;
-    else if (!strcmp(name, "f8_lds_min_q")) *value = f8_lds_first_q(ix->opt, ix->dtype, ix->d);      // the threshold in force for this index, 0 = never
+    // the statistics of the last call (TopkStats) by their names: HDB_STATS, hdb_plan.h; below, what is computed or the index's own
+    for (const hdb_stat_entry& e : HDB_STATS) if (!strcmp(name, e.name)) { *value = ix->st.*e.member; return HDB_OK; }
+    int rc = HDB_OK;
+    if (!strcmp(name, "f8_lds_min_q")) *value = f8_lds_first_q(ix->opt, ix->dtype, ix->d);      // the threshold in force for this index, 0 = never
     else if (!strcmp(name, "b1_mfma_min_q")) *value = b1_mfma_first_q(ix->opt, ix->dtype, ix->d);      // likewise, for a packed-bit index
     else if (!strcmp(name, "host_direct")) *value = ix->st_host_direct;
-    else if (!strcmp(name, "fused")) *value = ix->st.fused;
-    else if (!strcmp(name, "local")) *value = ix->st.local;
     else if (!strcmp(name, "cand_cap")) *value = HDB_CAND_CAP;
-    else if (!strcmp(name, "quant")) *value = ix->st.quant;
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;
     else if (!strcmp(name, "quant_bytes")) *value = ix->qmode == HDB_QUANT_I8 ? ix->n * (int64_t)(ix->qP + 12) : 0;
-    else if (!strcmp(name, "plane")) *value = ix->st.plane;
-    else if (!strcmp(name, "plane_blocks")) *value = ix->st.plane_blocks;      // workgroups of the last call's plane pass (0: it did not take the plane)
-    else if (!strcmp(name, "subset")) *value = ix->st.subset;
     else if (!strcmp(name, "subset_rows")) *value = ix->subset_m;
-    else if (!strcmp(name, "rerank")) *value = ix->st.rerank;
-    else if (!strcmp(name, "grouped")) *value = ix->st.grouped;
-    else if (!strcmp(name, "group_k")) *value = ix->st.group_k;
-    else if (!strcmp(name, "group_rounds")) *value = ix->st.group_rounds;
-    else if (!strcmp(name, "group_exact")) *value = ix->st.group_exact;
-    else if (!strcmp(name, "maxsim")) *value = ix->st.maxsim;
-    else if (!strcmp(name, "maxsim_chunks")) *value = ix->st.maxsim_chunks;
-    else if (!strcmp(name, "maxsim_team")) *value = ix->st.maxsim_team;
-    else if (!strcmp(name, "maxsim_sorted")) *value = ix->st.maxsim_sorted;
     else if (!strcmp(name, "maxsim_bytes")) *value = (int64_t)((ix->grp_rows.cap + ix->grp_off.cap) * sizeof(uint32_t));      // the inverted index of the groups, as held
     else if (!strcmp(name, "plane_bytes")) *value = (ix->qmode == HDB_QUANT_I8 && ix->pnib) ? ix->n * (int64_t)plane_row_bytes(ix->qP) : 0;
     else if (!strcmp(name, "plane_survivors") || !strcmp(name, "plane_overflows")) {      // synchronise the device
         // plane_survivors: rows the last call's pass over the plane kept (0 when it did not take the plane); plane_overflows: calls
         // of this index so far that kept more than plane_cap_rows of them (the plane let more through than it is worth)
         int h[HDB_QSTAT_WORDS] = {0, 0, 0, 0};
-        if (ix->qstat) {
-            HIP_TRY(hipSetDevice(ix->device));
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(h, ix->qstat, sizeof(h), hipMemcpyDeviceToHost));
-        }
+        if (ix->qstat && (rc = read_device_stat(ix, h, ix->qstat, sizeof(h))) != HDB_OK) return rc;
         *value = name[6] == 's' ? (ix->st.plane ? (int64_t)(uint32_t)h[1] : 0) : (int64_t)(uint32_t)h[2];
     }
     else if (!strcmp(name, "quant_cands")) {          // synchronises the device
         int h = 0;
-        if (ix->st.quant && ix->qstat) {
-            HIP_TRY(hipSetDevice(ix->device));
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(&h, ix->qstat, sizeof(int), hipMemcpyDeviceToHost));
-        }
+        if (ix->st.quant && ix->qstat && (rc = read_device_stat(ix, &h, ix->qstat, sizeof(int))) != HDB_OK) return rc;
         *value = h;
     }
     else if (!strcmp(name, "quant_cands_min") || !strcmp(name, "quant_cands_median")) {     // batches: over the lists of the last chunk; synchronises
         int64_t v = 0;
         if (ix->st.quant && ix->qb_cnt && ix->qb_cnt_n > 0) {
-            HIP_TRY(hipSetDevice(ix->device));
-            HIP_TRY(hipDeviceSynchronize());
             std::vector<uint32_t> raw((size_t)ix->qb_cnt_n * HDB_CNT_STRIDE), c((size_t)ix->qb_cnt_n);
-            HIP_TRY(hipMemcpy(raw.data(), ix->qb_cnt, raw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if ((rc = read_device_stat(ix, raw.data(), ix->qb_cnt, raw.size() * sizeof(uint32_t))) != HDB_OK) return rc;
             for (int q = 0; q < ix->qb_cnt_n; ++q) c[q] = raw[(size_t)q * HDB_CNT_STRIDE];
             std::sort(c.begin(), c.end());
             v = name[13] == 'i' ? c.front() : c[c.size() / 2];

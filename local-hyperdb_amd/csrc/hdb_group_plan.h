@@ -11,10 +11,7 @@
 //                  best and demote launches between the score pass and the selection (group_exact_call below).
 // A list of n rows is the whole ranking: a round at k' = n is never short, so no round follows it.
 #pragma once
-#include "hdb_plan.h"
-
-#define HDB_GROUP_OVERSAMPLE_MAX 64
-#define HDB_GROUP_ROUNDS_MAX 2
+#include "hdb_plan.h"          // (HDB_GROUP_OVERSAMPLE_MAX and HDB_GROUP_ROUNDS_MAX: beside the option table that clamps to them)
 
 struct GroupRounds {
     int rounds = 0;                               // fast rounds the call may run (0: the exact pass answers every query)

@@ -9,6 +9,7 @@
 #pragma once
 #include "hdb_ws.h"
 #include <algorithm>
+#include <cstring>
 
 // ---- options (hdb_set_option), embedded in the index as ix->opt ----------------------------------------------------------------
 struct hdb_options {
@@ -68,6 +69,57 @@ struct hdb_options {
     int64_t maxsim_team = 0;          // hdb_maxsim_host: lanes that own one group in its reduction (0: the rule, hdb_maxsim_team_rule; 1 | 4 | 16 | 64 = fixed, A/B runs and tests); changes no answer
 };
 #define HDB_RERANK_MAXQ 256
+#define HDB_GROUP_OVERSAMPLE_MAX 64
+#define HDB_GROUP_ROUNDS_MAX 2
+
+// The ONE list of the option names: every member of hdb_options with the rule hdb_set_option applies to a value before it stores it.
+//   HDB_OPT_CLAMP  max(lo, min(value, hi)) -- plain assignment where the bounds are the type's, "negative becomes -1" where lo is -1
+//   HDB_OPT_SET    one of `set` (its first `hi` entries); any other value is ignored and the call still succeeds
+//   HDB_OPT_RATIO  negative becomes -1, otherwise at least 1
+//   HDB_OPT_BOOL   0 or 1
+// hdb_set_option (hdb_api.hip), the host check programs (tests/plan_check.h) and the documentation guard (tests/test_abi.py) all read it.
+enum { HDB_OPT_CLAMP, HDB_OPT_SET, HDB_OPT_RATIO, HDB_OPT_BOOL };
+struct hdb_option_entry { const char* name; int64_t hdb_options::*member; int rule; int64_t lo, hi; int64_t set[5]; };
+#define HDB_OPT(n)               {#n, &hdb_options::n, HDB_OPT_CLAMP, INT64_MIN, INT64_MAX, {}}
+#define HDB_OPT_MIN(n, lo)       {#n, &hdb_options::n, HDB_OPT_CLAMP, lo, INT64_MAX, {}}
+#define HDB_OPT_RANGE(n, lo, hi) {#n, &hdb_options::n, HDB_OPT_CLAMP, lo, hi, {}}
+#define HDB_OPT_IN(n, cnt, ...)  {#n, &hdb_options::n, HDB_OPT_SET, 0, cnt, {__VA_ARGS__}}
+#define HDB_OPT_FLAG(n)          {#n, &hdb_options::n, HDB_OPT_BOOL, 0, 1, {}}
+static constexpr hdb_option_entry HDB_OPTIONS[] = {
+    HDB_OPT(max_blocks), HDB_OPT(force_exact), HDB_OPT(sample_target), HDB_OPT(mfma_min_q), HDB_OPT(use_mfma),
+    HDB_OPT_MIN(exact_bytes, 1 << 20), HDB_OPT(bits_fused), HDB_OPT(bits_local), HDB_OPT(fused_max_q), HDB_OPT(f32_min_q),
+    HDB_OPT(f32_split), HDB_OPT(f32_split_min_q), HDB_OPT(bf16_ks_min_q), HDB_OPT_MIN(f8_ks_min_q, -1), HDB_OPT_MIN(f8_lds_min_q, -1),
+    HDB_OPT_MIN(b1_mfma_min_q, -1), HDB_OPT_FLAG(bf16_quant), HDB_OPT_IN(f8_lds_waves, 3, 0, 4, 8),
+    HDB_OPT(bits_max_q), HDB_OPT(host_direct), HDB_OPT(dyn_tiles), HDB_OPT_MIN(dyn_min_mb, 0), HDB_OPT(dyn_heavy), HDB_OPT(host_poll),
+    HDB_OPT(use_fused), HDB_OPT(use_local), HDB_OPT_RANGE(local_m, 0, 64), HDB_OPT_MIN(local_max_tiles, 1), HDB_OPT(local_small),
+    HDB_OPT(local_max_q), HDB_OPT(use_l1_tile), HDB_OPT(l1_packed), HDB_OPT(use_batch1), HDB_OPT_MIN(fused_timeout_us, 1),
+    HDB_OPT_IN(finalize_threads, 3, 256, 512, 1024), HDB_OPT_IN(mfma_variant, 3, 16, 32, 64), HDB_OPT(use_quant), HDB_OPT(quant_min_n),
+    HDB_OPT_RANGE(quant_max_k, 1, 128), HDB_OPT(auto_quant), HDB_OPT(quant_batch_min_n), HDB_OPT_FLAG(quant_batch_kernel),
+    HDB_OPT(use_plane), HDB_OPT(plane_min_n), HDB_OPT_MIN(plane_cap_rows, 0), HDB_OPT_RANGE(plane_wg_per_cu, 0, 8), HDB_OPT(use_subset),
+    HDB_OPT_MIN(subset_min_n, -1), {"subset_ratio", &hdb_options::subset_ratio, HDB_OPT_RATIO, -1, INT64_MAX, {}}, HDB_OPT_RANGE(rerank_chunk, 0, HDB_RERANK_MAXQ),
+    HDB_OPT_RANGE(group_oversample, 1, HDB_GROUP_OVERSAMPLE_MAX), HDB_OPT_RANGE(group_fast_rounds, 0, HDB_GROUP_ROUNDS_MAX),
+    HDB_OPT_IN(maxsim_team, 5, 0, 1, 4, 16, 64),
+};
+#undef HDB_OPT
+#undef HDB_OPT_MIN
+#undef HDB_OPT_RANGE
+#undef HDB_OPT_IN
+#undef HDB_OPT_FLAG
+static_assert(sizeof(HDB_OPTIONS) / sizeof(HDB_OPTIONS[0]) == sizeof(hdb_options) / sizeof(int64_t), "every member of hdb_options has one entry in HDB_OPTIONS");
+// -> whether `name` is an option; the value is stored under the entry's rule
+static inline bool hdb_option_set(hdb_options& o, const char* name, int64_t value) {
+    for (const hdb_option_entry& e : HDB_OPTIONS) {
+        if (std::strcmp(name, e.name) != 0) continue;
+        switch (e.rule) {
+        case HDB_OPT_CLAMP: o.*e.member = std::max(e.lo, std::min(value, e.hi)); break;
+        case HDB_OPT_SET:   for (int64_t i = 0; i < e.hi; ++i) if (value == e.set[i]) o.*e.member = value; break;
+        case HDB_OPT_RATIO: o.*e.member = value < 0 ? -1 : std::max<int64_t>(1, value); break;
+        default:            o.*e.member = value ? 1 : 0; break;
+        }
+        return true;
+    }
+    return false;
+}
 
 // ---- what the planner is told ---------------------------------------------------------------------------------------------------
 struct TopkFacts {
@@ -99,6 +151,19 @@ enum TopkPath {
 struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0;
                    int64_t grouped = 0, group_k = 0, group_rounds = 0, group_exact = 0;        // hdb_topk_grouped_host writes these four behind its last inner call
                    int64_t maxsim = 0, maxsim_chunks = 0, maxsim_team = 0, maxsim_sorted = 0; };      // hdb_maxsim_host writes these four behind its plan's
+// The ONE list of its members: X(name of the stat in hdb_get_stat, member).  hdb_get_stat answers these names from the table,
+// plan_diff compares them, the documentation guard (tests/test_abi.py) reads the names.
+#define HDB_STAT_FIELDS(X) \
+    X(sample_rows, sample_rows) X(sample_m, sample_m) X(path, path) X(chunks, chunks) X(mfma, mfma) X(fused, fused) X(local, local) \
+    X(f32_split, f32s) X(quant, quant) X(plane, plane) X(subset, subset) X(f8_lds, f8_lds) X(plane_blocks, plane_blocks) X(rerank, rerank) \
+    X(grouped, grouped) X(group_k, group_k) X(group_rounds, group_rounds) X(group_exact, group_exact) \
+    X(maxsim, maxsim) X(maxsim_chunks, maxsim_chunks) X(maxsim_team, maxsim_team) X(maxsim_sorted, maxsim_sorted)
+struct hdb_stat_entry { const char* name; int64_t TopkStats::*member; };
+#define X(name, member) {#name, &TopkStats::member},
+static constexpr hdb_stat_entry HDB_STATS[] = { HDB_STAT_FIELDS(X) };
+#undef X
+static_assert(sizeof(HDB_STATS) / sizeof(HDB_STATS[0]) == sizeof(TopkStats) / sizeof(int64_t), "every member of TopkStats has one entry in HDB_STAT_FIELDS");
+
 struct TopkPlan {
     TopkPath path = HDB_PATH_EMPTY;
     uint32_t kk = 0; int W = 0;
@@ -127,6 +192,31 @@ struct TopkPlan {
     bool shadow() const { return path == HDB_PATH_QUANT || path == HDB_PATH_QUANT_BATCH; }
     bool single_launch() const { return path == HDB_PATH_FUSED || path == HDB_PATH_BITS1 || path == HDB_PATH_BATCH1; }
 };
+// The ONE list of its members (qs and stats: member by member below).  A member that is not listed here does not compile:
+#define TOPK_PLAN_FIELDS(X) \
+    X(path) X(kk) X(W) X(bits) X(pearson) X(exact) X(small) X(mfma) X(f32s) X(ksplit) X(l1tile) X(local) X(exact_req) X(f8_lds) X(subset) \
+    X(prep) X(fold_small) X(q16_in_prep) X(f16_queries) X(mask_fold) X(tile_rows) X(s_tiles) X(s_stride) X(s_rows) X(ld_s) X(ld_n) X(m) \
+    X(cq_max) X(ld_scores) X(ld_ks) X(sort_n) X(n_best) X(local_slot) X(local_m) X(bits_local) X(npass) X(mflavour) X(build_needed) \
+    X(plane_wanted) X(qb_int8) X(P) X(nsub) X(pl_cap) X(pl_blocks) X(qs.s_tiles) X(qs.s_stride) X(qs.s_rows) X(qs.ld_s)
+// (members of an aggregate: the most initializers T{...} takes; hdb_any converts to every member's type, so each stands for one member)
+struct hdb_any { template <class T> operator T() const; };
+template <class T, class = void, class... A> struct hdb_arity { static constexpr size_t value = sizeof...(A) - 1; };
+template <class T, class... A> struct hdb_arity<T, decltype(void(T{A{}...})), A...> : hdb_arity<T, void, A..., hdb_any> {};
+#define X(f) +1
+static_assert(hdb_arity<TopkPlan>::value == (0 TOPK_PLAN_FIELDS(X)) - 4 + 2 && hdb_arity<QuantSample>::value == 4,
+              "every member of TopkPlan is listed in TOPK_PLAN_FIELDS (qs as its four members, stats through HDB_STAT_FIELDS)");
+#undef X
+// -> the name of the first member in which two plans differ, nullptr when they are equal.  A check that means "equal except X" resets
+// X on both sides first.
+static inline const char* plan_diff(const TopkPlan& a, const TopkPlan& b) {
+#define X(f) if (!(a.f == b.f)) return #f;
+    TOPK_PLAN_FIELDS(X)
+#undef X
+#define X(name, f) if (a.stats.f != b.stats.f) return "stats." #f;
+    HDB_STAT_FIELDS(X)
+#undef X
+    return nullptr;
+}
 
 #define HDB_FUSED_MAXQ_RULE 4
 static inline bool is_bits_metric(int metric) { return metric == HDB_HAMMING || metric == HDB_JACCARD; }

@@ -11,26 +11,8 @@
 //    automatic build stays an fp16 rule), and field for field the plan the same facts get with use_quant = 0 -- the library
 //    before the option, where no bfloat16 call could reach the shadow rules.
 // Prints "plans N" and "F failures"; exit status 1 on any failure.
-#include "hdb_plan.h"
+#include "plan_check.h"
 #include <cstdio>
-
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
-
-static bool same_plan(const TopkPlan& a, const TopkPlan& b) {
-    return a.path == b.path && a.kk == b.kk && a.W == b.W && a.bits == b.bits && a.pearson == b.pearson && a.exact == b.exact && a.small == b.small &&
-           a.mfma == b.mfma && a.f32s == b.f32s && a.ksplit == b.ksplit && a.l1tile == b.l1tile && a.local == b.local && a.f8_lds == b.f8_lds &&
-           a.subset == b.subset && a.prep == b.prep && a.fold_small == b.fold_small && a.q16_in_prep == b.q16_in_prep && a.f16_queries == b.f16_queries &&
-           a.mask_fold == b.mask_fold && a.tile_rows == b.tile_rows && a.s_tiles == b.s_tiles && a.s_stride == b.s_stride && a.s_rows == b.s_rows &&
-           a.ld_s == b.ld_s && a.ld_n == b.ld_n && a.m == b.m && a.cq_max == b.cq_max && a.ld_scores == b.ld_scores && a.ld_ks == b.ld_ks &&
-           a.sort_n == b.sort_n && a.local_slot == b.local_slot && a.local_m == b.local_m && a.npass == b.npass && a.bits_local == b.bits_local &&
-           a.mflavour == b.mflavour && a.build_needed == b.build_needed && a.plane_wanted == b.plane_wanted && a.qb_int8 == b.qb_int8 &&
-           a.P == b.P && a.nsub == b.nsub && a.pl_cap == b.pl_cap &&
-           a.stats.sample_rows == b.stats.sample_rows && a.stats.sample_m == b.stats.sample_m && a.stats.path == b.stats.path &&
-           a.stats.chunks == b.stats.chunks && a.stats.mfma == b.stats.mfma && a.stats.fused == b.stats.fused && a.stats.local == b.stats.local &&
-           a.stats.f32s == b.stats.f32s && a.stats.quant == b.stats.quant && a.stats.plane == b.stats.plane && a.stats.subset == b.stats.subset &&
-           a.stats.f8_lds == b.stats.f8_lds;
-}
 
 int main() {
     CHECK(hdb_options().bf16_quant == 0, "the option is off by default");
@@ -84,7 +66,7 @@ int main() {
             // a bfloat16 call the shadow does not take is the call of the index without one
             TopkFacts f0 = f; f0.qmode = HDB_QUANT_NONE; f0.plane_present = false;
             const TopkPlan p0 = plan_topk(f0, o, c, [&] { return fin != 0; });
-            CHECK(same_plan(p, p0), WHERE);
+            CHECK_SAME_PLAN(p, p0, WHERE);
         }
 
         // ---- B: no shadow (variants 0 and 1: default options and quant_min_n = 0) ----
@@ -99,7 +81,7 @@ int main() {
             hdb_options off = o;
             off.use_quant = 0; off.auto_quant = 0;
             const TopkPlan b0 = plan_topk(g, off, c, [&] { return fin != 0; });
-            CHECK(same_plan(b, b0), WHERE);
+            CHECK_SAME_PLAN(b, b0, WHERE);
             // 1-4 queries stay on the VALU scan, whatever the matrix holds
             if (nq <= 4) CHECK(!b.mfma && b.stats.mfma == 0 && asked_b == 0, WHERE);
         }
@@ -122,6 +104,6 @@ int main() {
         CHECK(!p.shadow() && p.stats.quant == 0, "dtype %d", dtype);
     }
     CHECK(taken > 1000 && planes > 50, "the grid reached the shadow %ld times, the plane %ld times", taken, planes);
-    std::printf("plans %ld\n shadow %ld plane %ld\n %ld failures\n", plans, taken, planes, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("plans %ld\n shadow %ld plane %ld\n", plans, taken, planes);
+    return check_done();
 }

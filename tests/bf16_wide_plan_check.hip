@@ -7,11 +7,8 @@
 //    pearson queries on a finite matrix take the matrix cores through K slices, everything else keeps the VALU scan; with the default
 //    (-1) the slices start at the width's measured threshold (hdb_mfma_bf16_ks_min_q: 5 at d = 1024 / 4096, 9 elsewhere).
 // Prints "plans N" and "F failures"; exit status 1 on any failure.
-#include "hdb_plan.h"
+#include "plan_check.h"
 #include <cstdio>
-
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
 
 struct Want { int dtype, d, slices; int width[HDB_KS_MAX_SLICES]; };
 static const Want WANT[] = {
@@ -138,6 +135,6 @@ int main() {
         const TopkPlan p = plan_topk(f, o, TopkCall{5, 50, HDB_COSINE, true, false}, [] { return true; });
         CHECK(p.mfma && !p.ksplit && p.ld_ks == 0, "bf16 d %d, 5 queries", d);
     }
-    std::printf("plans %ld\n %ld failures\n", plans, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("plans %ld\n", plans);
+    return check_done();
 }

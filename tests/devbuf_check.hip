@@ -11,14 +11,9 @@
 #include <map>
 
 #include "hdb_devbuf.h"
+#include "plan_check.h"
 
-static long g_fail = 0, g_points = 0;
-#define CHECK(cond, ...)                                                     \
-    do {                                                                     \
-        if (!(cond)) {                                                       \
-            if (++g_fail <= 20) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } \
-        }                                                                    \
-    } while (0)
+static long g_points = 0;
 
 struct FakeMem {
     static std::map<void*, size_t> live;      // block -> bytes
@@ -204,6 +199,6 @@ int main() {
     check_small();
     FakeMem::arm(0, 0);
     CHECK(FakeMem::live.empty() && FakeMem::live_bytes == 0, "at exit: %zu live blocks, %zu bytes", FakeMem::live.size(), FakeMem::live_bytes);
-    std::printf("devbuf_check: %ld points, %ld allocations, %ld frees, %ld failures\n", g_points, FakeMem::allocs, FakeMem::frees, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("devbuf_check: %ld points, %ld allocations, %ld frees\n", g_points, FakeMem::allocs, FakeMem::frees);
+    return check_done();
 }

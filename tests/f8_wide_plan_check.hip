@@ -12,26 +12,10 @@
 //    plan of the same shape under bf16_ks_min_q = 5;
 // 5) other values: 9 starts at 9 queries, -1 at hdb_mfma_f8_ks_min_q(d), 3 is clamped to 5.
 // Prints "plans N" and "F failures"; exit status 1 on any failure.
-#include "hdb_plan.h"
+#include "plan_check.h"
 #include <cstdio>
 
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
-
-static bool same_plan(const TopkPlan& a, const TopkPlan& b) {
-    return a.path == b.path && a.kk == b.kk && a.W == b.W && a.bits == b.bits && a.pearson == b.pearson && a.exact == b.exact && a.small == b.small &&
-           a.mfma == b.mfma && a.f32s == b.f32s && a.ksplit == b.ksplit && a.l1tile == b.l1tile && a.local == b.local && a.subset == b.subset &&
-           a.prep == b.prep && a.fold_small == b.fold_small && a.q16_in_prep == b.q16_in_prep && a.f16_queries == b.f16_queries &&
-           a.mask_fold == b.mask_fold && a.tile_rows == b.tile_rows && a.s_tiles == b.s_tiles && a.s_stride == b.s_stride && a.s_rows == b.s_rows &&
-           a.ld_s == b.ld_s && a.ld_n == b.ld_n && a.m == b.m && a.cq_max == b.cq_max && a.ld_scores == b.ld_scores && a.ld_ks == b.ld_ks &&
-           a.sort_n == b.sort_n && a.npass == b.npass && a.bits_local == b.bits_local &&
-           a.stats.sample_rows == b.stats.sample_rows && a.stats.sample_m == b.stats.sample_m && a.stats.path == b.stats.path &&
-           a.stats.chunks == b.stats.chunks && a.stats.mfma == b.stats.mfma && a.stats.fused == b.stats.fused && a.stats.local == b.stats.local &&
-           a.stats.f32s == b.stats.f32s && a.stats.quant == b.stats.quant && a.stats.plane == b.stats.plane && a.stats.subset == b.stats.subset;
-}
-
 // bfloat16's sliced widths, as literals: 640 .. 1536 in steps of 128, 2048, 3072, 4096
-static bool sliced_width(int d) { return (d >= 640 && d <= 1536 && d % 128 == 0) || d == 2048 || d == 3072 || d == 4096; }
 
 int main() {
     // ---- 1, 2: the slice lists and the caps of the default dispatch ----
@@ -100,7 +84,7 @@ int main() {
                 hdb_options ob = o; ob.use_mfma = 0;
                 TopkPlan b = plan_topk(fb, ob, c, [&] { return fin != 0; });
                 if (p.mfma) { b.mfma = true; b.stats.mfma = sorted ? 0 : 1; b.mask_fold = f.has_mask && !sorted; }
-                CHECK(same_plan(p, b), WHERE);
+                CHECK_SAME_PLAN(p, b, WHERE);
                 continue;
             }
             const int first = opt == 5 ? 5 : opt == 9 ? 9 : opt == 3 ? 5 : hdb_mfma_f8_ks_min_q(d);
@@ -124,7 +108,7 @@ int main() {
             TopkFacts fb = f; fb.dtype = HDB_BF16;
             hdb_options ob = o; ob.bf16_ks_min_q = first;
             const TopkPlan b = plan_topk(fb, ob, c, [&] { return fin != 0; });
-            CHECK(same_plan(p, b), WHERE);
+            CHECK_SAME_PLAN(p, b, WHERE);
         }
     }
     // the option reaches the sliced widths only: whole rows keep their 5 whatever it says
@@ -147,6 +131,6 @@ int main() {
         plans += 2;
         CHECK(!p8.ksplit && !p8.mfma && p12.ksplit && p12.mfma, "mfma_min_q = 12");
     }
-    std::printf("plans %ld\n %ld failures\n", plans, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("plans %ld\n", plans);
+    return check_done();
 }

@@ -13,13 +13,11 @@
 //     a tile of 16 records (16 bytes per row whatever U is) without overlap, inside hdb_plane_rec_bytes(rows) for a ragged row count.
 // It prints "patterns P", "sums S", "tiles T" and " F failures"; exit status 1 on any failure.
 #include "hdb_common.h"
+#include "plan_check.h"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
-
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
 
 static float bf(uint32_t code) { uint32_t u = code << 16; float f; std::memcpy(&f, &u, 4); return f; }
 
@@ -91,6 +89,6 @@ int main() {
     }
     // the fields of a block lie inside it, one after the other
     CHECK(HDB_PLANE_BLOCK_K == 0 && HDB_PLANE_BLOCK_RC == 32 && HDB_PLANE_BLOCK_TILE == 48 && HDB_PLANE_BLOCK_TILE + 16 == HDB_PLANE_BLOCK_BYTES, "fields");
-    std::printf("patterns %ld\nsums %ld\ntiles %ld\n %ld failures\n", patterns, sums, tiles, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("patterns %ld\nsums %ld\ntiles %ld\n", patterns, sums, tiles);
+    return check_done();
 }

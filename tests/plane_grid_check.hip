@@ -14,12 +14,10 @@
 // (A walk is repeated only for a grid not yet seen with that sample.)
 // It prints "table J WG WAVES" for J = 1 .. 4, "rules R", "walks W", "tiles T" and " F failures"; exit status 1 on any failure.
 #include "hdb_ws.h"
+#include "plan_check.h"
 #include <cstdio>
 #include <set>
 #include <vector>
-
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
 
 static long g_tiles = 0;
 
@@ -97,6 +95,6 @@ int main() {
     CHECK(hdb_quant_plane_blocks(0, 3, 256, 0, 0) == 1 && hdb_quant_plane_blocks(1000000, 3, 0, 0, 0) >= 1, "edges");
     CHECK(hdb_quant_plane_blocks(1000000, 3, 256, 99, 0) == 8 * 256 && hdb_quant_plane_blocks(1000000, 3, 256, -5, 0) == hdb_quant_plane_wg_per_cu(3) * 256, "edges");
     CHECK(hdb_quant_plane_dbg_blocks(625000, 0) == 1024 && hdb_quant_plane_dbg_blocks(625000, 3) == 3 && hdb_quant_plane_dbg_blocks(9, 0) == 2, "dbg");
-    std::printf("rules %ld\nwalks %ld\ntiles %ld\n %ld failures\n", rules, walks, g_tiles, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("rules %ld\nwalks %ld\ntiles %ld\n", rules, walks, g_tiles);
+    return check_done();
 }

@@ -16,11 +16,9 @@
 // restatement of hdb_tile_index that tests/test_plane_skip.py plants its rows with -- then "plans P", "tiles T" and " F failures";
 // exit status 1 on any failure.
 #include "hdb_ws.h"
+#include "plan_check.h"
 #include <cstdio>
 #include <vector>
-
-static long g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (++g_fail <= 40) { std::printf("FAIL %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
 
 static long g_tiles = 0;
 
@@ -88,6 +86,6 @@ int main() {
     const int64_t strides[] = {1, 2, 3, 7, 31, 32, 1000};
     const int64_t ws[] = {0, 1, 2, 3, 17, 136, 1000, 19531, 4000000};
     for (int64_t s : strides) for (int64_t w : ws) std::printf("index %lld %lld %lld\n", (long long)w, (long long)s, (long long)hdb_tile_index(w, s));
-    std::printf("plans %ld\ntiles %ld\n %ld failures\n", plans, g_tiles, g_fail);
-    return g_fail ? 1 : 0;
+    std::printf("plans %ld\ntiles %ld\n", plans, g_tiles);
+    return check_done();
 }

@@ -143,3 +143,68 @@ def test_host_merge_ties_padding_and_interleaved_rows(parts, k, levels):
             want_i[q, i], want_s[q, i] = r, -ns
     gi, gs, gst = _native.merge_topk_host(recs, parts, nq, k, np.empty(nb, dtype=np.uint8))
     assert np.array_equal(gi, want_i) and np.array_equal(gs, want_s) and np.array_equal(gst, want_st)
+
+
+def _tables():
+    """-> (the option names and defaults, the names of the plain statistics) as csrc/hdb_plan.h lists them: HDB_OPTIONS, HDB_STAT_FIELDS."""
+    text = open(os.path.join(ROOT, "local-hyperdb_amd", "csrc", "hdb_plan.h")).read()
+    members = re.findall(r"^    int64_t (\w+) = ([^;]+);", text.split("struct hdb_options {", 1)[1].split("};", 1)[0], re.M)
+    defaults = {name: eval(value.replace("(int64_t)", "")) for name, value in members}
+    table = text.split("HDB_OPTIONS[] = {", 1)[1].split("};", 1)[0]
+    options = re.findall(r"HDB_OPT(?:_[A-Z]+)?\((\w+)", table) + re.findall(r'\{"(\w+)"', table)
+    assert sorted(options) == sorted(defaults) and len(options) > 50, "one entry of HDB_OPTIONS per member of hdb_options"
+    stats = re.findall(r"X\((\w+), \w+\)", text.split("#define HDB_STAT_FIELDS(X)", 1)[1].split("struct hdb_stat_entry", 1)[0])
+    assert len(stats) > 20 and "f32_split" in stats
+    return [(name, defaults[name]) for name in options], stats
+
+
+def test_every_option_and_stat_of_the_tables_is_documented():
+    """The comment above hdb_set_option in include/hyperdb_hip.h names every option under "Options:" and every plain statistic under
+    "Stats:"."""
+    text = open(os.path.join(ROOT, "include", "hyperdb_hip.h")).read()
+    comment = text.split("/* Tuning knobs / introspection", 1)[1].split("*/", 1)[0]
+    doc_options, doc_stats = comment.split("\n * Stats:", 1)
+    assert " * Options:" in doc_options
+    options, stats = _tables()
+    missing = [name for name, _ in options if not re.search(rf"\b{name}\b", doc_options)]
+    assert not missing, f"options the header does not document: {missing}"
+    missing = [name for name in stats if not re.search(rf"\b{name}\b", doc_stats)]
+    assert not missing, f"statistics the header does not document: {missing}"
+
+
+@pytest.mark.gpu
+def test_option_and_stat_tables_on_a_live_index():
+    """Every name of the two tables through the C ABI of a 64 x 8 float32 index; an unknown name is HDB_ERR_ARG with its message; an
+    option set to a value its rule rewrites (f8_lds_min_q = -7 is stored as -1, and means nothing to a float32 index) changes no answer."""
+    import numpy as np
+    from hyperdb import _native
+    rng = np.random.default_rng(7)
+    V = rng.standard_normal((64, 8)).astype(np.float32)
+    Q = rng.standard_normal((3, 8)).astype(np.float32)
+    lib = _native.lib()
+    options, stats = _tables()
+    fresh = _native.GpuIndex(V)
+    ix = _native.GpuIndex(V)
+    try:
+        for name, default in options:
+            assert lib.hdb_set_option(ix._h, name.encode(), default) == 0, name
+        want = fresh.topk(Q, 5, _native.METRIC_IDS["cosine_similarity"])
+        got = ix.topk(Q, 5, _native.METRIC_IDS["cosine_similarity"])
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        value = ctypes.c_int64(-1)
+        for name in stats:
+            assert lib.hdb_get_stat(ix._h, name.encode(), ctypes.byref(value)) == 0, name
+            assert value.value == fresh.stat(name), name
+        assert lib.hdb_set_option(ix._h, b"no_such_option", 1) == -1
+        assert lib.hdb_last_error() == b"hdb_set_option: unknown option no_such_option"
+        assert lib.hdb_get_stat(ix._h, b"no_such_stat", ctypes.byref(value)) == -1
+        assert lib.hdb_last_error() == b"hdb_get_stat: unknown stat no_such_stat"
+        ix.set_option("f8_lds_min_q", -7)
+        assert ix.stat("f8_lds_min_q") == 0          # (the threshold in force: never, the index is not float8)
+        for metric in ("cosine_similarity", "dot_product", "euclidean_metric"):
+            want = fresh.topk(Q, 5, _native.METRIC_IDS[metric])
+            got = ix.topk(Q, 5, _native.METRIC_IDS[metric])
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), metric
+    finally:
+        ix.close()
+        fresh.close()

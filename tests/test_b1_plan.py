@@ -7,32 +7,11 @@ matrix-core, single-launch or tile-kernel rule admits the dtype; the tables of a
 admitted width; over the int8 check's grid every packed-bit plan keeps off the matrix cores, the shadow, the plane, the tile
 kernel and the row list, equals the int8 plan for the bit metrics and the int8 plan with use_mfma = 0 for the others.
 No GPU call, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
-
-
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
+import host_check
 
 
 def test_packed_bit_pitch_rules_and_plans(tmp_path):
-    exe = str(tmp_path / "b1_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "b1_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
-    plans = [int(line.split()[1]) for line in run.stdout.splitlines() if line.startswith("plans ")]
+    out = host_check.run(host_check.build("b1_plan_check", tmp_path))
+    plans = [int(line.split()[1]) for line in out.splitlines() if line.startswith("plans ")]
     assert plans and plans[0] > 100_000, "the program planned the whole grid"

@@ -12,21 +12,14 @@ hdb_devbuf.h is the only file under csrc/ that does, and the pinned host buffers
 group_pinned and freed there and in hdb_group_destroy only.  No GPU is used."""
 import os
 import re
-import shutil
-import subprocess
+
+import host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
 DEVBUF_H = "hdb_devbuf.h"
 _DEVICE = re.compile(r"\bhip(?:Malloc|Free)\w*")          # (hipHostMalloc / hipHostFree do not start like this)
 _PINNED = re.compile(r"\bhipHost(?:Malloc|Free)\b")
-
-
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
 
 
 def _strip(text):
@@ -54,17 +47,7 @@ def _without_body(text, func):
 
 
 def test_devbuf_over_a_counting_allocator(tmp_path):
-    exe = str(tmp_path / "devbuf_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "devbuf_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    out = host_check.run(host_check.build("devbuf_check", tmp_path))
 
 
 def test_the_scanner_sees_calls_and_bodies():

@@ -7,32 +7,11 @@ plan takes the flavour; with n or -1 a plan takes it exactly where it is on the 
 elements, or K slices under f8_ks_min_q) outside the full sort with max(n, 5, mfma_min_q) queries -- never for another dtype, small
 matrices, row-list calls, matrices that are not finite or manhattan; and every other field of every plan equals the plan with the
 option off.  No GPU call, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
-
-
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
+import host_check
 
 
 def test_lds_flavour_geometry_and_plans(tmp_path):
-    exe = str(tmp_path / "f8_lds_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "f8_lds_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
-    plans = [int(line.split()[1]) for line in run.stdout.splitlines() if line.startswith("plans ")]
+    out = host_check.run(host_check.build("f8_lds_plan_check", tmp_path))
+    plans = [int(line.split()[1]) for line in out.splitlines() if line.startswith("plans ")]
     assert plans and plans[0] > 100_000, "the program planned the whole grid"

@@ -7,32 +7,11 @@ that are multiples of 8; the caps of the default dispatch (hdb_mfma_ksplit_slice
 for float8 beyond 512 elements; with default options no float8 plan takes the slices; with f8_ks_min_q = 5 the slices are planned
 exactly for 5+ dot / cosine / euclidean / pearson queries on a finite matrix of a sliced width, as the bfloat16 plan of the same
 shape; 9 starts at 9 queries, -1 follows hdb_mfma_f8_ks_min_q, 3 is clamped to 5.  No GPU call, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
-
-
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
+import host_check
 
 
 def test_slice_lists_and_plans_of_wide_f8_rows(tmp_path):
-    exe = str(tmp_path / "f8_wide_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "f8_wide_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
-    plans = [int(line.split()[1]) for line in run.stdout.splitlines() if line.startswith("plans ")]
+    out = host_check.run(host_check.build("f8_wide_plan_check", tmp_path))
+    plans = [int(line.split()[1]) for line in out.splitlines() if line.startswith("plans ")]
     assert plans and plans[0] > 10_000, "the program planned the whole grid"

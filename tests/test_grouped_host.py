@@ -4,16 +4,15 @@ workspace of the call (csrc/hdb_group_plan.h, TopkWs) and the codes the facade b
 import ctypes
 import inspect
 import os
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import host_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
 NAMES = ("hdb_index_set_groups", "hdb_topk_grouped_host", "hdb_collapse_groups")
 
 
@@ -180,27 +179,10 @@ def test_collapse_groups_host_on_hand_written_lists():
     assert i.tolist() == [[0, 2], [9, -1]] and st.tolist() == [0, 0]
 
 
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
-
-
 def test_group_plan_and_workspace(tmp_path):
     """tests/group_plan_check.hip, compiled and run like tests/rerank_ws_check.hip: host code under AddressSanitizer and UBSan.  The
     round schedule over (n, k, oversample, rounds), the exact plan over shapes, dtypes and metrics, size equals placement."""
-    exe = str(tmp_path / "group_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "group_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    out = host_check.run(host_check.build("group_plan_check", tmp_path))
 
 
 def _facade(n_rows, docs, sources, dead=(), metadata_keys=()):

@@ -6,12 +6,12 @@ import glob
 import inspect
 import os
 import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
+
+import host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
@@ -169,26 +169,9 @@ def test_maxsim_host_against_brute_force():
         maxsim_host(V, sets, groups[:-1], 3, "dot_product")
 
 
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
-
-
 def test_maxsim_plan_and_workspace(tmp_path):
     """tests/maxsim_plan_check.hip, compiled and run like tests/group_plan_check.hip: host code under AddressSanitizer and UBSan."""
-    exe = str(tmp_path / "maxsim_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "maxsim_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    out = host_check.run(host_check.build("maxsim_plan_check", tmp_path))
 
 
 def test_workspace_areas_are_declared_once():

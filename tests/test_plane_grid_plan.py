@@ -9,9 +9,9 @@ plane_blocks with it) and pins the restatement's table against the one the progr
 No GPU call, nothing loaded into Python."""
 import os
 import re
-import subprocess
 
-from test_plane_skip_plan import CSRC, ROOT, _hipcc
+import host_check
+from host_check import CSRC
 
 
 def wg_table():
@@ -31,21 +31,11 @@ def plane_blocks(nwalk, wg_per_cu, cus, max_blocks):
 
 
 def test_the_rule_and_the_walk_at_its_grids(tmp_path):
-    exe = str(tmp_path / "plane_grid_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "plane_grid_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
-    assert "rules 2592\n" in run.stdout, "6 sizes, 4 widths, 3 devices, 9 settings of plane_wg_per_cu, 4 of max_blocks"
-    table = [tuple(int(x) for x in line.split()[1:]) for line in run.stdout.splitlines() if line.startswith("table ")]
+    out = host_check.run(host_check.build("plane_grid_check", tmp_path))
+    assert "rules 2592\n" in out, "6 sizes, 4 widths, 3 devices, 9 settings of plane_wg_per_cu, 4 of max_blocks"
+    table = [tuple(int(x) for x in line.split()[1:]) for line in out.splitlines() if line.startswith("table ")]
     assert [j for j, _, _ in table] == [1, 2, 3, 4] and [wg for _, wg, _ in table] == wg_table()
     for j, wg, waves in table:
         assert 1 <= wg <= waves <= 8, f"J = {j}: {wg} workgroups per CU, {waves} waves per SIMD compiled"
-    walks = int(next(line.split()[1] for line in run.stdout.splitlines() if line.startswith("walks ")))
+    walks = int(next(line.split()[1] for line in out.splitlines() if line.startswith("walks ")))
     assert walks >= 6 * 4 * 3, "every size and width is walked at several grids"

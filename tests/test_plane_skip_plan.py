@@ -7,12 +7,8 @@ them) and grids of 1, 3 and 1024 workgroups, and checks that the visited tiles a
 once, and that every sampled tile is hdb_tile_index(w, stride).  It also prints hdb_tile_index for a fixed list of (w, stride): this
 file compares them with tile_index below, the Python restatement tests/test_plane_skip.py plants its rows with.
 No GPU call, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
+import host_check
 
 
 def tile_index(t, stride):
@@ -23,27 +19,10 @@ def tile_index(t, stride):
     return t * stride + (h >> 8) % stride
 
 
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
-
-
 def test_walk_is_the_complement_of_the_sample(tmp_path):
-    exe = str(tmp_path / "plane_skip_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "plane_skip_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
-    assert "plans 51\n" in run.stdout, "7 sizes and 10 forced plans, three grids each"
-    pinned = [tuple(int(x) for x in line.split()[1:]) for line in run.stdout.splitlines() if line.startswith("index ")]
+    out = host_check.run(host_check.build("plane_skip_check", tmp_path))
+    assert "plans 51\n" in out, "7 sizes and 10 forced plans, three grids each"
+    pinned = [tuple(int(x) for x in line.split()[1:]) for line in out.splitlines() if line.startswith("index ")]
     assert len(pinned) == 63
     for w, stride, value in pinned:
         assert tile_index(w, stride) == value, f"tile_index({w}, {stride}) = {tile_index(w, stride)}, the library says {value}"

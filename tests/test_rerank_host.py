@@ -2,15 +2,14 @@
 the candidate check of the Python binding and the workspace layout (RerankWs, csrc/hdb_ws.h).  No GPU is used."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
 NAMES = ("hdb_rerank", "hdb_rerank_host", "hdb_two_stage_host")
 
 
@@ -95,24 +94,7 @@ def test_python_entry_points_exist():
         ranking.rank_two_stage(object(), object(), np.zeros((1, 4)))
 
 
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
-
-
 def test_rerank_workspace_layout(tmp_path):
     """RerankWs over nq x chunk x m x d x pearson, compiled and run like tests/ws_layout_check.hip: host code under AddressSanitizer
     and UBSan, size equals placement at every point."""
-    exe = str(tmp_path / "rerank_ws_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "rerank_ws_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    out = host_check.run(host_check.build("rerank_ws_check", tmp_path))

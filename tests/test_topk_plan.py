@@ -10,22 +10,14 @@ call per line, its inputs and the statistics that library defined on the call's 
   * test_live_library_matches_the_table (GPU): the rows of up to 70 001 stored rows, run again on the built library."""
 import json
 import os
-import shutil
-import subprocess
 import sys
 
 import pytest
 
+import host_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "local-hyperdb_amd", "csrc")
 TABLE = os.path.join(ROOT, "tests", "golden", "dispatch_table.jsonl")
-
-
-def _hipcc():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    found = hipcc if os.path.exists(hipcc) else shutil.which("hipcc")
-    assert found, "hipcc not found (the library is built with it)"
-    return found
 
 
 def _table():
@@ -34,20 +26,10 @@ def _table():
 
 
 def test_plan_reproduces_the_table(tmp_path):
-    exe = str(tmp_path / "topk_plan_check")
-    build = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC,
-                            os.path.join(ROOT, "tests", "topk_plan_check.hip"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout + build.stderr
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, TABLE], capture_output=True, text=True, env=env)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert " 0 failures" in run.stdout and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr
+    out = host_check.run(host_check.build("topk_plan_check", tmp_path), TABLE)
     lines = _table()
     assert "header" in lines[0] and lines[0]["rows"] == len(lines) - 1
-    assert f"rows {len(lines) - 1}\n" in run.stdout, "the program read every row of the table"
+    assert f"rows {len(lines) - 1}\n" in out, "the program read every row of the table"
 
 
 @pytest.mark.gpu
