@@ -543,6 +543,61 @@ int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_score, int32_t 
 int hdb_maxsim_host(hdb_index* ix, const void* dev_Q, const int32_t* host_off, int32_t ns, int32_t k, int metric,
                     void* host_record, void* stream);   /* record: hdb_packed_bytes(ns, k); indices are GROUP ids */
 
+/* Diverse top-k: maximal marginal relevance (MMR) over a call's candidates -- a hit is paid for its relevance and charged for being
+ * a near copy of a hit already chosen (the search_type "mmr" of retrieval stacks).  Grouping covers "ten chunks of one document"; this
+ * covers ten near-identical chunks of ten different documents.
+ * Semantics.  Input per query: a list (id_i, r_i), i = 0 .. m - 1, as hdb_topk, hdb_rerank, hdb_two_stage_host and hdb_collapse_groups
+ * return it: ids carry row_base, the relevance r_i is the list's float32 score with bias, mask and path already in it; the list need
+ * not be sorted.  An id < 0 is padding and so is an entry at -inf; an id outside [row_base, row_base + n) is skipped and sets
+ * HDB_Q_BADROW -- it is compared against the bounds before any address is formed from it, nothing is read for it --; an id listed
+ * twice counts once, at its first list position.  The surviving entries, in list order, are the query's candidates.  The handle's
+ * bias, mask, row list and groups are not read.
+ *   p(a, b), the similarity of two stored rows under pair_metric (HDB_DOT, HDB_COSINE, HDB_EUCLIDEAN), no bias, no mask: stored
+ *   values widened exactly to the accumulate type (float32; double for an HDB_F64 index, the result cast to float32), products
+ *   accumulated with explicit fma in element order e = 0 .. d - 1; euclidean sums the squared differences themselves, as the VALU
+ *   scan does, and is 1 / (1 + sqrt(sum)) -- never ||a||^2 + ||b||^2 - 2 a.b, which cancels on the near copies this call exists
+ *   for; cosine is dot * inv_norm[lower row] * inv_norm[higher row] from the index's cache (zero norm: 1); NaN -> -inf.  p is
+ *   evaluated once per unordered pair and mirrored, and depends on the two rows only: not on list positions, tiles, the other
+ *   candidates or the other queries.
+ *   Selection, with lam = (float)lambda, oml = 1.0f - lam: step 0 picks the candidate with the largest r_i; step t >= 1 picks the
+ *   unselected candidate with the largest val_i = canon(lam * r_i - oml * pen_i), pen_i = max over the selected s of p(i, s) -- two
+ *   rounded float32 products and one rounded subtraction, no contraction; canon: NaN -> -inf.  Ties go to the lowest list position.
+ *   Every candidate is eligible until it is chosen (one at val = -inf is picked when nothing better is left); the call stops after
+ *   min(k, candidates) picks.
+ * Output: [nq][k] ids and their relevances r IN PICK ORDER -- not re-sorted by score --, tail -1 / -inf.  Status word: HDB_Q_NAN is
+ * carried over from the word that came in, HDB_Q_BADROW is set as above, every other bit is cleared.  lambda = 1 returns the first k
+ * candidates by (relevance descending, position ascending); lambda = 0 picks by relevance first and then whatever is least like
+ * anything already chosen.
+ *
+ * hdb_mmr: the primitive; it takes any ranked list, so it composes with hdb_topk, hdb_rerank, two-stage and hdb_collapse_groups.
+ * 1 <= k <= m <= HDB_MAX_K and lambda in [0, 1] (anything else, NaN included: HDB_ERR_ARG), a pair_metric other than the three:
+ * HDB_ERR_UNSUPPORTED, nq < 0: HDB_ERR_ARG, nq == 0: HDB_OK -- all judged before the handle, and the handle (NULL: HDB_ERR_ARG;
+ * HDB_B1: HDB_ERR_UNSUPPORTED, a bits index is a first stage) before any HIP call.  The six byte-addressed dtypes
+ * are served, any d.  Outputs must not overlap inputs.  dev_status [nq] is read and written, and may be NULL.
+ * hdb_mmr_host: one call for the common case -- hdb_topk of m (<= n, else HDB_ERR_ARG) rows per query under `metric` (any metric
+ * hdb_topk takes, the bit metrics included) into a device record, on whatever path that call takes; its status words are read back
+ * and failed queries re-run exactly; hdb_mmr over the record; the packed record (hdb_packed_bytes(nq, k)) goes to host memory and
+ * `stream` is synchronised.  nq >= 1.
+ * How it runs (local-hyperdb_amd/csrc/hdb_mmr_plan.h, hdb_mmr.hip).  Queries go in chunks of cq = clamp(exact_bytes / (mp^2 4), 1,
+ * min(nq, 256)), mp = m rounded up to 16: the pair matrices P [cq][mp][mp] of a chunk live in the workspace.  Three launches per
+ * chunk: prep (one workgroup per query validates and compacts the list in list order; first occurrences by the sort of
+ * hdb_collapse_groups), pairs (grid = tile pairs ti <= tj x queries; 16-lane groups gather candidate rows in 16-byte pieces into LDS,
+ * one pair per thread, no atomics) and select (one workgroup per query, min(k, candidates) steps: val, a 64-bit argmax by wave
+ * shuffles and one LDS exchange, one coalesced row of P to raise the penalties).  Separate launches: the kernel boundary makes P
+ * visible; nothing spins on a flag.
+ * Options: none of its own; chunking obeys exact_bytes.
+ * Stats: mmr (1 after either call; hdb_topk, hdb_rerank, the grouped call and the multi-vector call set it to 0; an MMR call sets
+ * rerank = grouped = maxsim = 0), mmr_chunks; after hdb_mmr_host the other stats are those of its hdb_topk.
+ * Not built: a one-workgroup flavour that keeps P in LDS for m up to about 190 and drops two launches; p computed on the fly without
+ * the m^2 matrix for large batches; the matrix cores for the pair pass; manhattan / pearson / bit-metric pair similarity and HDB_B1
+ * handles; m > 2048; several GPUs / shards; MMR inside the grouped and the multi-vector call (compose through hdb_mmr); returning
+ * the val of each pick. */
+int hdb_mmr(hdb_index* ix, const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, double lambda,
+            int pair_metric, int64_t* dev_idx_out, float* dev_score_out, int32_t* dev_status /* read and written, may be NULL */,
+            void* stream);
+int hdb_mmr_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t m, int32_t k, int metric, double lambda, int pair_metric,
+                 void* host_record /* hdb_packed_bytes(nq, k) */, void* stream);
+
 /* Merge `parts` per-shard top-k lists (the all-gathered [parts][nq][k] buffers of the row-sharded
  * index) into the global top-k per query, same ordering rule.  Every part list must be ordered as hdb_topk writes
  * it: score descending, row ascending, unused slots (index -1) at the end. */
@@ -655,7 +710,7 @@ void hdb_group_destroy(hdb_group* g);
  *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second
  *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0), grouped, group_k,
  *   group_rounds, group_exact (hdb_topk_grouped_host, above), maxsim, maxsim_chunks, maxsim_team, maxsim_sorted, maxsim_bytes
- *   (hdb_maxsim_host, above). */
+ *   (hdb_maxsim_host, above), mmr, mmr_chunks (hdb_mmr / hdb_mmr_host, above). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

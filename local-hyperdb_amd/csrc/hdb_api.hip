@@ -23,6 +23,7 @@
 #include "hdb_plan.h"
 #include "hdb_group_plan.h"
 #include "hdb_maxsim_plan.h"
+#include "hdb_mmr_plan.h"
 #include "hdb_devbuf.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
@@ -148,7 +149,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 111; }
+extern "C" int hdb_version(void) { return 112; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 // The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
@@ -1766,6 +1767,81 @@ extern "C" int hdb_collapse_groups(const int64_t* dev_idx, const float* dev_scor
     LAUNCH_TRY(hdb_launch_group_collapse(dev_idx, dev_score, nq, m, k, dev_groups, n_groups, n, row_base, dev_idx_out, dev_score_out, dev_status,
                                          dev_status, HDB_Q_NAN, stream));
     return HDB_OK;
+}
+
+// ---- diverse top-k: maximal marginal relevance over a call's candidates (hdb_mmr.hip, hdb_mmr_plan.h) ---------------------------------
+// What is decided from the numbers alone comes first, before the handle is looked at and before any HIP call.
+static int mmr_sizes(const char* who, int32_t nq, int32_t m, int32_t k, double lambda, int pair_metric, bool host) {
+    if (m < 1 || m > HDB_MAX_K) return fail(HDB_ERR_ARG, std::string(who) + ": m (entries per query) must be in [1, 2048]");
+    if (k < 1 || k > m) return fail(HDB_ERR_ARG, std::string(who) + ": k must be in [1, m]");
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(HDB_ERR_ARG, std::string(who) + ": lambda must be in [0, 1]");
+    if (!mmr_pair_metric_ok(pair_metric)) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": pair_metric must be dot, cosine or euclidean; the others are not built");
+    if (host ? nq <= 0 : nq < 0) return fail(HDB_ERR_ARG, std::string(who) + (host ? ": nq must be positive" : ": nq must be >= 0"));
+    return HDB_OK;
+}
+static int mmr_handle(const char* who, const hdb_index* ix) {
+    if (!ix) return fail(HDB_ERR_ARG, std::string(who) + ": null index");
+    if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": a packed-bit index is a first stage: pair similarity of packed bits is not built");
+    return HDB_OK;
+}
+// Per chunk of queries: list preparation, the pair matrix, the selection.  status_in / status_out: [nq] or NULL, may be one array.
+// The statistics of the call before it stay (hdb_mmr_host: those of its hdb_topk); the ranking flags become this call's.
+static int mmr_impl(hdb_index* ix, const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, double lambda,
+                    int pair_metric, int64_t* dev_idx_out, float* dev_score_out, const int32_t* status_in, int32_t* status_out, hipStream_t st) {
+    const MmrPlan p = mmr_plan(nq, m, ix->opt.exact_bytes);
+    MmrWs w;
+    const int rc = ws_lay(ix, w, p.cq, p.mp);
+    if (rc) return rc;
+    ix->st.rerank = ix->st.grouped = ix->st.maxsim = 0;
+    ix->st.mmr = 1; ix->st.mmr_chunks = 0;
+    for (int q0 = 0; q0 < nq; q0 += p.cq) {
+        const int cq = std::min(p.cq, nq - q0);
+        LAUNCH_TRY(hdb_launch_mmr_prep(dev_idx + (int64_t)q0 * m, dev_score + (int64_t)q0 * m, cq, m, p.mp, ix->n, ix->row_base, w.rows, w.rel, w.cnt,
+                                       status_in ? status_in + q0 : nullptr, status_out ? status_out + q0 : nullptr, st));
+        LAUNCH_TRY(hdb_launch_mmr_pairs(ix->V, ix->dtype, ix->d, pair_metric, ix->inv_norm, w.rows, w.cnt, cq, p.mp, w.P, st));
+        LAUNCH_TRY(hdb_launch_mmr_select(w.rows, w.rel, w.cnt, cq, p.mp, w.P, (float)lambda, k, ix->row_base, dev_idx_out + (int64_t)q0 * k,
+                                         dev_score_out + (int64_t)q0 * k, st));
+        ix->st.mmr_chunks++;
+    }
+    return HDB_OK;
+}
+
+extern "C" int hdb_mmr(hdb_index* ix, const int64_t* dev_idx, const float* dev_score, int32_t nq, int32_t m, int32_t k, double lambda,
+                       int pair_metric, int64_t* dev_idx_out, float* dev_score_out, int32_t* dev_status, void* stream) {
+    int rc = mmr_sizes("hdb_mmr", nq, m, k, lambda, pair_metric, false); if (rc) return rc;
+    if (nq == 0) return HDB_OK;
+    rc = mmr_handle("hdb_mmr", ix); if (rc) return rc;
+    if (!dev_idx || !dev_score || !dev_idx_out || !dev_score_out) return fail(HDB_ERR_ARG, "hdb_mmr: null argument");
+    HIP_TRY(hipSetDevice(ix->device));
+    return mmr_impl(ix, dev_idx, dev_score, nq, m, k, lambda, pair_metric, dev_idx_out, dev_score_out, dev_status, dev_status, (hipStream_t)stream);
+}
+
+// hdb_topk of m rows per query into a device record of its own, its status words read back and the failed queries re-run exactly (as
+// hdb_two_stage_host does for its first stage); the [nq][m] record then goes straight into the selection, whose answer is the
+// caller's record.
+extern "C" int hdb_mmr_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t m, int32_t k, int metric, double lambda, int pair_metric,
+                            void* host_record, void* stream) {
+    int rc = mmr_sizes("hdb_mmr_host", nq, m, k, lambda, pair_metric, true); if (rc) return rc;
+    rc = mmr_handle("hdb_mmr_host", ix); if (rc) return rc;
+    if (!dev_Q || !host_record) return fail(HDB_ERR_ARG, "hdb_mmr_host: null argument");
+    if ((int64_t)m > ix->n) return fail(HDB_ERR_ARG, "hdb_mmr_host: m must be at most min(2048, n)");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    HostRec rec1;                                     // (the ranked lists stay on the device: opened, never closed)
+    rc = hostrec_open(ix->rec1, nq, m, nullptr, false, rec1); if (rc) return rc;
+    const PackedRec& r1 = rec1.view;
+    rc = topk_impl(ix, dev_Q, nq, m, metric, r1.idx, r1.score, r1.status, stream, false); if (rc) return rc;
+    std::vector<int32_t> h_st((size_t)nq);
+    HIP_TRY(hipMemcpyAsync(h_st.data(), r1.status, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const TopkStats first_stats = ix->st;
+    bool ran = false;
+    rc = rerun_flagged(ix, dev_Q, nq, m, metric, r1, h_st.data(), st, &ran); if (rc) return rc;
+    if (ran) ix->st = first_stats;                    // the rule of this call: it reports its first attempt, as hdb_two_stage_host does
+    HostRec rec;
+    rc = hostrec_open(ix->rec, nq, k, host_record, false, rec); if (rc) return rc;
+    rc = mmr_impl(ix, r1.idx, r1.score, nq, m, k, lambda, pair_metric, rec.view.idx, rec.view.score, r1.status, rec.view.status, st); if (rc) return rc;
+    return hostrec_close(rec, st);
 }
 
 extern "C" int hdb_merge_topk(const int64_t* dev_idx_parts, const float* dev_score_parts, int32_t parts, int32_t nq,

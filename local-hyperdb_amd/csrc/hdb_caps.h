@@ -567,3 +567,10 @@ static inline int hdb_maxsim_team_rule(int64_t n, int64_t n_groups) {
     const int64_t mean = n_groups > 0 ? n / n_groups : n;
     return mean <= 4 ? 1 : mean <= 32 ? 4 : mean <= 256 ? 16 : 64;
 }
+
+// ---- hdb_mmr.hip: diverse top-k (maximal marginal relevance) ----
+// The pair pass works on tiles of HDB_MMR_TILE candidates: a workgroup of HDB_MMR_TILE^2 threads, one pair each.  Every extent
+// that depends on a list length m uses m rounded up to the tile.
+#define HDB_MMR_TILE 16
+#define HDB_MMR_SELECT_THREADS 256        // hdb_mmr_select_kernel: candidate c belongs to thread c mod 256, HDB_MAX_K / 256 = 8 per thread
+static inline int hdb_mmr_mp(int m) { return (m + HDB_MMR_TILE - 1) / HDB_MMR_TILE * HDB_MMR_TILE; }

@@ -20,11 +20,12 @@
 // The library does not trust the ids: every kernel compares an id against [0, n_groups) before an address is formed from it.  A
 // row with an id outside is treated as masked and reported (HDB_Q_BADROW); nothing is indexed with it.
 #include "hdb_common.h"
+#include "hdb_first_occ.h"
 #include "../../include/hyperdb_hip.h"
 #include <algorithm>
 
 #define HDB_GROUP_MAXM 2048
-#define HDB_GROUP_NONE 0xFFFFFFFFFFFFFFFFull
+#define HDB_GROUP_NONE HDB_FIRST_NONE
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Collapse.  idx / score: [nq][m] as hdb_topk writes them (row_base added; -1 = padding).  An entry at -inf is an excluded row
@@ -68,23 +69,8 @@ __global__ __launch_bounds__(1024) void hdb_group_collapse_kernel(const int64_t*
         first[i] = 0;
     }
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {               // bitonic network, ascending: the sentinels end up behind the keys
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (P >> 1); t += 1024) {
-                const int i = ((t / stride) * (stride << 1)) + (t % stride), j = i + stride;
-                const bool asc = (i & size) == 0;
-                const unsigned long long x = key[i], y = key[j];
-                if (asc ? (x > y) : (x < y)) { key[i] = y; key[j] = x; }
-            }
-            __syncthreads();
-        }
-    }
-    // a key that opens a run of equal group ids is its group's first occurrence in the list: mark its list position
-    for (int i = tid; i < P; i += 1024) {
-        const unsigned long long kx = key[i];
-        if (kx != HDB_GROUP_NONE && (i == 0 || (uint32_t)(key[i - 1] >> 32) != (uint32_t)(kx >> 32))) first[(uint32_t)kx] = 1;
-    }
-    __syncthreads();
+    // a key that opens a run of equal group ids is its group's first occurrence in the list: its list position gets marked
+    hdb_mark_first_occurrences(key, first, P, tid, 1024);
     // the marks, prefix-summed in list order: thread t owns positions [t per, (t + 1) per)
     const int per = (P + 1023) / 1024;
     const int i0 = tid * per;

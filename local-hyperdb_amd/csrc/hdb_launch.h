@@ -171,6 +171,18 @@ int hdb_launch_maxsim_reduce(const float* sbuf, int64_t ld_n, int cq, int32_t v0
                              const uint32_t* grp_off, const uint32_t* grp_rows, int sorted, int64_t n_groups, float* acc, int64_t ld_g,
                              int team, void* stream);
 
+// ---- hdb_mmr.hip: diverse top-k (maximal marginal relevance over a call's candidates) ----
+// Three launches per chunk of nq queries, mp = hdb_mmr_mp(m) (hdb_caps.h).  prep: the lists [nq][m] -> candidates in list order, rows /
+// rel [nq][mp] and cnt [nq]; status_in / status_out may be the same array or NULL (HDB_Q_NAN is carried, HDB_Q_BADROW set, the rest
+// cleared).  pairs: P [nq][mp][mp] float32, the similarity of every two candidates under dot / cosine / euclidean, mirrored; the
+// diagonal is not written.  select: min(k, count) picks per query into idx_out / score_out [nq][k], then the -1 / -inf tail.
+int hdb_launch_mmr_prep(const int64_t* idx, const float* score, int nq, int m, int mp, int64_t n, int64_t row_base, uint32_t* rows,
+                        float* rel, int32_t* cnt, const int32_t* status_in, int32_t* status_out, void* stream);
+int hdb_launch_mmr_pairs(const void* V, int dtype, int d, int pair_metric, const float* inv_norm, const uint32_t* rows,
+                         const int32_t* cnt, int nq, int mp, float* P, void* stream);
+int hdb_launch_mmr_select(const uint32_t* rows, const float* rel, const int32_t* cnt, int nq, int mp, const float* P, float lam,
+                          int k, int64_t row_base, int64_t* idx_out, float* score_out, void* stream);
+
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);

@@ -150,14 +150,16 @@ enum TopkPath {
 // statistics of one call (hdb_get_stat); every call writes all of them
 struct TopkStats { int64_t sample_rows = 0, sample_m = 0, path = 0, chunks = 0, mfma = 0, fused = 0, local = 0, f32s = 0, quant = 0, plane = 0, subset = 0, f8_lds = 0, plane_blocks = 0, rerank = 0;
                    int64_t grouped = 0, group_k = 0, group_rounds = 0, group_exact = 0;        // hdb_topk_grouped_host writes these four behind its last inner call
-                   int64_t maxsim = 0, maxsim_chunks = 0, maxsim_team = 0, maxsim_sorted = 0; };      // hdb_maxsim_host writes these four behind its plan's
+                   int64_t maxsim = 0, maxsim_chunks = 0, maxsim_team = 0, maxsim_sorted = 0;        // hdb_maxsim_host writes these four behind its plan's
+                   int64_t mmr = 0, mmr_chunks = 0; };                                                // hdb_mmr / hdb_mmr_host write these two behind the calls inside them
 // The ONE list of its members: X(name of the stat in hdb_get_stat, member).  hdb_get_stat answers these names from the table,
 // plan_diff compares them, the documentation guard (tests/test_abi.py) reads the names.
 #define HDB_STAT_FIELDS(X) \
     X(sample_rows, sample_rows) X(sample_m, sample_m) X(path, path) X(chunks, chunks) X(mfma, mfma) X(fused, fused) X(local, local) \
     X(f32_split, f32s) X(quant, quant) X(plane, plane) X(subset, subset) X(f8_lds, f8_lds) X(plane_blocks, plane_blocks) X(rerank, rerank) \
     X(grouped, grouped) X(group_k, group_k) X(group_rounds, group_rounds) X(group_exact, group_exact) \
-    X(maxsim, maxsim) X(maxsim_chunks, maxsim_chunks) X(maxsim_team, maxsim_team) X(maxsim_sorted, maxsim_sorted)
+    X(maxsim, maxsim) X(maxsim_chunks, maxsim_chunks) X(maxsim_team, maxsim_team) X(maxsim_sorted, maxsim_sorted) \
+    X(mmr, mmr) X(mmr_chunks, mmr_chunks)
 struct hdb_stat_entry { const char* name; int64_t TopkStats::*member; };
 #define X(name, member) {#name, &TopkStats::member},
 static constexpr hdb_stat_entry HDB_STATS[] = { HDB_STAT_FIELDS(X) };

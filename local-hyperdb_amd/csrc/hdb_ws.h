@@ -99,6 +99,18 @@ struct MaxsimWs {
     }
 };
 
+// hdb_mmr: the buffers of one chunk of cq queries (hdb_mmr_plan.h).  mp: the list length rounded up to the pair tile -- the
+// candidates' local rows and relevances in list order, their counts, and the pair matrix P [cq][mp][mp].
+struct MmrWs {
+    uint32_t* rows; float* rel; int32_t* cnt; float* P;
+    void lay(Bump& b, int cq, int mp) {
+        rows = b.take<uint32_t>((size_t)cq * mp);
+        rel = b.take<float>((size_t)cq * mp);
+        cnt = b.take<int32_t>((size_t)cq);
+        P = b.take<float>((size_t)cq * mp * mp);
+    }
+};
+
 // hdb_rerank: per-query words of the whole call, then the buffers of one chunk of cq queries.  m: the caller's list length -- the
 // prepared lists (valid, ascending, unique local rows) have that leading dimension; the packed entries keep the leading dimension
 // HDB_CAND_CAP the finalize kernel is launched with.  pearson: the centred queries.

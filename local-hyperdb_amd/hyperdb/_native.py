@@ -37,6 +37,7 @@ CAND_CAP = 8192                         # longest candidate list of a rerank cal
 HDB_QUANT_NONE, HDB_QUANT_I8 = 0, 1
 QUANT_MODES = {None: HDB_QUANT_NONE, "int8": HDB_QUANT_I8}
 HDB_MAX_K = 2048
+PAIR_METRICS = ("dot_product", "cosine_similarity", "euclidean_metric")      # what two stored rows can be compared by (hdb_mmr)
 MERGE_DEVICE_CAP = 8192      # hdb_merge_topk / hdb_merge_topk_packed rank parts*k entries per query in LDS; beyond: hdb_merge_topk_host
 
 NAN_MESSAGE = "Vectors and query_vector should not contain NaN values."   # reference ranking_algorithm.py:151
@@ -52,6 +53,7 @@ EXPORTS = (
     "hdb_rerank", "hdb_rerank_host", "hdb_two_stage_host",
     "hdb_index_set_groups", "hdb_topk_grouped_host", "hdb_collapse_groups",
     "hdb_maxsim_host",
+    "hdb_mmr", "hdb_mmr_host",
 )
 
 
@@ -104,6 +106,8 @@ def _load():
     lib.hdb_topk_grouped_host.argtypes = [vp, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_collapse_groups.argtypes = [vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_maxsim_host.argtypes = [vp, vp, vp, i32, i32, ctypes.c_int, vp, vp]
+    lib.hdb_mmr.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_double, ctypes.c_int, vp, vp, vp, vp]
+    lib.hdb_mmr_host.argtypes = [vp, vp, i32, i32, i32, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp, vp]
     lib.hdb_merge_topk_packed.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_host.argtypes = [vp, i32, i32, i32, vp]
     lib.hdb_host_exchange_merge.argtypes = [vp, i64, i32, i32, ctypes.c_uint64, vp, i32, i32, vp, ctypes.c_double]
@@ -967,6 +971,55 @@ class GpuIndex:
         self._raise_rerank_status(slot[4])
         return slot[2].copy(), slot[3].copy()
 
+    # -- diverse top-k: maximal marginal relevance over a call's candidates ------------------------
+    def mmr_device(self, idx, scores, k, lambda_mult=0.5, pair_metric_id=None, status=None):
+        """Enqueue the diverse top-k of ranked lists (hdb_mmr): ``idx`` (int64) / ``scores`` (float32) ``[nq, m]``,
+        ``1 <= k <= m <= 2048``, CUDA tensors on the index's device or host arrays -- what topk_device, rerank_device, a two-stage call or
+        collapse_groups return goes in as it is.  Pick t >= 1 is the unpicked candidate with the largest
+        ``lambda_mult * relevance - (1 - lambda_mult) * max similarity to a pick``; ``pair_metric_id``: dot, cosine (the default) or
+        euclidean between stored rows.  ``status``: the lists' int32 status words, whose Q_NAN bits are carried over.  Returns CUDA
+        tensors ``(idx [nq, k], scores [nq, k], status [nq])`` IN PICK ORDER, tail ``-1`` / ``-inf``; Q_BADROW: an id outside the
+        index was skipped.  ValueError for sizes or a lambda outside [0, 1]; NotImplementedError for another pair metric or a
+        ``storage="bits"`` index."""
+        it = torch.as_tensor(idx).to(self.device, torch.int64).contiguous()
+        st_ = torch.as_tensor(scores).to(self.device, torch.float32).contiguous()
+        if it.dim() != 2 or st_.shape != it.shape:
+            raise ValueError(f"mmr_device: idx and scores must be 2-D [nq, m] of one shape, got {tuple(it.shape)} and {tuple(st_.shape)}")
+        nq, m, k = int(it.shape[0]), int(it.shape[1]), int(k)
+        pm = METRIC_IDS["cosine_similarity"] if pair_metric_id is None else int(pair_metric_id)
+        out_i = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=self.device)
+        out_s = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=self.device)
+        if status is None:
+            out_st = torch.zeros((nq,), dtype=torch.int32, device=self.device)
+        else:
+            out_st = torch.as_tensor(status).to(self.device, torch.int32).reshape(-1).clone()
+            if int(out_st.numel()) != nq:
+                raise ValueError(f"mmr_device: {int(out_st.numel())} status words for {nq} lists")
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_mmr(self._h, ctypes.c_void_p(it.data_ptr()), ctypes.c_void_p(st_.data_ptr()), nq, m, k, float(lambda_mult), pm,
+                                ctypes.c_void_p(out_i.data_ptr()), ctypes.c_void_p(out_s.data_ptr()), ctypes.c_void_p(out_st.data_ptr()),
+                                _stream_ptr(self.device)), "hdb_mmr")
+        return out_i, out_s, out_st
+
+    def mmr(self, Q, m, k, metric_id, lambda_mult=0.5, pair_metric_id=None):
+        """One C call (hdb_mmr_host): the top-m of every query under ``metric_id`` (mask and bias of the handle applied), then the
+        diverse k of those m -> numpy (int64 [nq,k], float32 [nq,k]) (copies), in pick order; the scores are the relevances.
+        ``pair_metric_id`` defaults to ``metric_id`` where that is dot, cosine or euclidean, to cosine otherwise.  ValueError on a NaN
+        query, on sizes (``1 <= k <= m <= min(n, 2048)``) and on a lambda outside [0, 1]."""
+        qt = self._query_tensor(Q, batched=True)
+        nq, m, k = int(qt.shape[0]), int(m), int(k)
+        if nq == 0:
+            raise ValueError("mmr: need at least one query")
+        if pair_metric_id is None:
+            pair_metric_id = int(metric_id) if int(metric_id) in (0, 1, 2) else METRIC_IDS["cosine_similarity"]
+        slot = self._record_slot(nq, k) if 1 <= k <= HDB_MAX_K else (None, None)
+        with torch.cuda.device(self.device):
+            _check(_lib.hdb_mmr_host(self._h, ctypes.c_void_p(qt.data_ptr()), nq, m, k, int(metric_id), float(lambda_mult), int(pair_metric_id),
+                                     ctypes.c_void_p(slot[1]), _stream_ptr(self.device)), "hdb_mmr_host")
+        if (slot[4] & Q_NAN).any():
+            raise ValueError(NAN_MESSAGE)
+        return slot[2].copy(), slot[3].copy()
+
     def topk(self, Q, k, metric_id):
         """Top-k of a query batch on the host: (int64 [nq,k], float32 [nq,k]) (copies)."""
         idx, sc, st = self.topk_views(Q, k, metric_id)
@@ -1167,6 +1220,85 @@ def maxsim_host(V, query_sets, groups, k, metric, bias=None, mask=None, n_groups
         out_i[s, :order.size] = order
         out_s[s, :order.size] = total[order]
     return out_i, out_s
+
+
+def _pair_matrix_host(X, pair_metric):
+    """float64 similarities of every two rows of X by the metric's definition, rounded to float32, NaN -> -inf."""
+    c = X.shape[0]
+    with np.errstate(all="ignore"):
+        if pair_metric == "euclidean_metric":                 # the differences themselves, row by row
+            P = np.empty((c, c), np.float64)
+            for i in range(c):
+                D = X - X[i]
+                P[i] = 1.0 / (1.0 + np.sqrt((D * D).sum(axis=1)))
+        else:
+            P = X @ X.T
+            if pair_metric == "cosine_similarity":
+                norm = np.sqrt((X * X).sum(axis=1))
+                inv = np.where(norm > 0, 1.0 / np.where(norm > 0, norm, 1.0), 1.0)      # (zero norm: 1, as the index's cache)
+                P = P * inv[:, None] * inv[None, :]
+        P = P.astype(np.float32)
+    return np.where(np.isnan(P), np.float32(-np.inf), P)
+
+
+def mmr_host(V, idx, scores, k, lambda_mult, pair_metric, row_base=0):
+    """The contract of hdb_mmr in numpy: ranked lists ``idx`` / ``scores`` ``[nq, m]`` over the rows of ``V`` -> ``(idx [nq, k] int64,
+    scores [nq, k] float32, status [nq] int32)`` in pick order, tail ``-1`` / ``-inf``.  A negative id or an entry at ``-inf`` is
+    padding; an id outside ``[row_base, row_base + n)`` is skipped and sets Q_BADROW; an id listed twice counts once, at its first
+    position.  Step 0 picks the largest relevance; step t the unpicked candidate with the largest
+    ``canon(lam * r - (1 - lam) * pen)`` in float32 -- every operation rounded on its own --, ``pen`` the largest pair similarity to
+    a pick; ties go to the lowest list position.  Pair similarities (``pair_metric``: a name of PAIR_METRICS or its id) are float64,
+    rounded to float32."""
+    if not isinstance(pair_metric, str):
+        pair_metric = {v: n_ for n_, v in METRIC_IDS.items()}.get(int(pair_metric), pair_metric)
+    if pair_metric not in PAIR_METRICS:
+        raise NotImplementedError(f"mmr_host: pair metric {pair_metric!r} is not one of {PAIR_METRICS}")
+    V = np.asarray(V, dtype=np.float64)
+    idx = np.asarray(idx, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float32)
+    nq, m = idx.shape
+    n, k = int(V.shape[0]), int(k)
+    lam = np.float32(lambda_mult)
+    oml = np.float32(1.0) - lam
+    out_i = np.full((nq, k), -1, np.int64)
+    out_s = np.full((nq, k), -np.inf, np.float32)
+    status = np.zeros(nq, np.int32)
+    for q in range(nq):
+        seen, rows, rel = set(), [], []
+        for j in range(m):
+            r = int(idx[q, j])
+            if r < 0 or scores[q, j] == -np.inf:
+                continue
+            if r < row_base or r - row_base >= n:
+                status[q] |= Q_BADROW
+                continue
+            if r in seen:
+                continue
+            seen.add(r)
+            rows.append(r - row_base)
+            rel.append(scores[q, j])
+        c = len(rows)
+        if c == 0:
+            continue
+        rows = np.asarray(rows, dtype=np.int64)
+        rel = np.asarray(rel, dtype=np.float32)
+        rel = np.where(np.isnan(rel), np.float32(-np.inf), rel) + np.float32(0.0)
+        P = _pair_matrix_host(V[rows], pair_metric)
+        pen = np.full(c, -np.inf, np.float32)
+        free = np.ones(c, bool)
+        for t in range(min(k, c)):
+            if t == 0:
+                val = rel
+            else:
+                with np.errstate(all="ignore"):
+                    val = lam * rel - oml * pen
+                val = np.where(np.isnan(val), np.float32(-np.inf), val)
+            left = np.flatnonzero(free)
+            s = int(left[np.argmax(val[left])])               # (argmax: the first of equal values, the lowest position)
+            out_i[q, t], out_s[q, t] = rows[s] + row_base, rel[s]
+            free[s] = False
+            pen = np.maximum(pen, P[s])
+    return out_i, out_s, status
 
 
 def collapse_groups(idx, scores, groups, k, n_groups=None, row_base=0):

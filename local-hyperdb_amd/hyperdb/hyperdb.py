@@ -690,7 +690,7 @@ class HyperDB:
             self._group_cache.move_to_end(group_by)
         return hit
 
-    def _execute(self, Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, group_by=None):
+    def _execute(self, Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, group_by=None, diverse=None):
         if self._index is None or not self.documents:
             raise Exception("The database is empty. Cannot proceed with the query.")
         if metric not in _METRICS:
@@ -699,6 +699,8 @@ class HyperDB:
         ix = self._index
         if group_by is not None and isinstance(ix, GpuGroup):
             raise NotImplementedError("group_by on several devices is not built: a group can span shards")
+        if diverse is not None and isinstance(ix, GpuGroup):
+            raise NotImplementedError("query_diverse needs one device: the candidates of a query live on different shards")
         # (one query: a NaN anywhere makes q.q a NaN -- a dot product instead of an isnan pass and a reduction)
         if ix.has_nan or (math.isnan(float(np.dot(Q[0], Q[0]))) if len(Q) == 1 and Q.dtype.kind == "f" else bool(np.isnan(Q).any())):
             raise ValueError(ranking.NAN_MESSAGE)
@@ -716,7 +718,12 @@ class HyperDB:
                 if sh.n:
                     sh.set_row_subset(None if masks is None else masks[p], None if lists is None else lists[p])
                     sh.set_bias(None if bias is None else bias[p])
-            if group_by is None:
+            if diverse is not None:                   # a diverse top_k of the fetch_k best (GpuIndex.mmr), in pick order
+                fetch_k, lambda_mult = diverse
+                m = min(n_avail, _native.HDB_MAX_K, 4 * int(top_k)) if fetch_k is None else min(int(fetch_k), n_avail)
+                pm = metric if metric in _native.PAIR_METRICS else "cosine_similarity"
+                idx, sc = ix.mmr(Q, max(m, int(top_k)), int(top_k), METRIC_IDS[metric], float(lambda_mult), METRIC_IDS[pm])
+            elif group_by is None:
                 idx, sc = ix.topk(Q, int(top_k), METRIC_IDS[metric])
             else:                                     # one hit per group: the best row of each, top_k groups (GpuIndex.topk_grouped)
                 codes, n_groups = self._groups_for(group_by)
@@ -763,6 +770,25 @@ class HyperDB:
         the key.  ``group_by=None`` is :meth:`query` exactly.  One device only (NotImplementedError with ``devices=[...]``).
         (:meth:`query` itself keeps the reference's parameter list; :meth:`query_batch` takes ``group_by`` as its last keyword.)"""
         return self._query_one(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)
+
+    def query_diverse(self, query_input, top_k=5, fetch_k=None, lambda_mult=0.5, return_similarities=True, filters=None, recency_bias=0,
+                      timestamp_key=None, metric='cosine_similarity'):
+        """Additive: :meth:`query` with a diverse answer -- maximal marginal relevance (``search_type="mmr"`` of retrievers).  The
+        ``fetch_k`` best documents (default ``min(documents, 2048, 4 * top_k)``) are fetched as :meth:`query` ranks them, filters and
+        recency applied, and ``top_k`` of them are picked one after the other: the first by score, each later one by
+        ``lambda_mult * score - (1 - lambda_mult) * (largest similarity to a document already picked)``, so near copies of a hit
+        do not fill the list.  Returns what :meth:`query` returns, IN PICK ORDER (the scores are the relevances, not sorted);
+        ``lambda_mult=1`` is :meth:`query`.  Documents are compared by ``metric`` where that is dot, cosine or euclidean, by cosine
+        otherwise.  Not cached; one device only (NotImplementedError with ``devices=[...]``).  (:meth:`query` itself keeps the
+        reference's parameter list.)"""
+        if self._index is None or not self.documents:
+            raise Exception("The database is empty. Cannot proceed with the query.")
+        if not 0.0 <= float(lambda_mult) <= 1.0:
+            raise ValueError(f"lambda_mult must be in [0, 1], got {lambda_mult!r}")
+        Q = self._query_vectors(query_input)
+        if len(Q) != 1:
+            raise ValueError("query_diverse() takes one query.")
+        return self._execute(Q, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, None, (fetch_k, lambda_mult))[0]
 
     def _group_key(self, group_by, doc):
         """What a group is called in the results of :meth:`query_multi`: the ``source_indices`` entry, or the metadata value -- ``None``

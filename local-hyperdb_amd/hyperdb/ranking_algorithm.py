@@ -16,7 +16,7 @@ reference's return types (int64 indices, float64 scores, ValueError on NaN / unk
 
 Additive surface (the reference has no batched call): :func:`rank_batch`; every query against its own list of rows:
 :func:`rerank_batch`; a cheap index in front of an exact one in one call: :func:`rank_two_stage`; one hit per group of rows (a
-document's chunks): :func:`rank_grouped`.
+document's chunks): :func:`rank_grouped`; a diverse top-k (maximal marginal relevance): :func:`rank_mmr`.
 
 There is NO CPU fallback: without the HIP library importing this module fails, and without a GPU every
 call raises ``HyperDBNativeError`` instead of silently computing on the host.
@@ -36,7 +36,7 @@ __all__ = [
     "get_norm_vector", "dot_product", "cosine_similarity", "euclidean_metric", "manhattan_distance",
     "jaccard_similarity", "pearson_correlation", "check_and_binarize_vectors", "hamming_distance",
     "hyperDB_ranking_algorithm_sort", "rank_batch", "register_vectors", "ResidentVectors",
-    "rerank_batch", "rank_two_stage", "rank_grouped", "rank_maxsim",
+    "rerank_batch", "rank_two_stage", "rank_grouped", "rank_maxsim", "rank_mmr",
 ]
 
 _GPU_METRICS = tuple(METRIC_IDS)      # all seven metrics of the reference's dispatch table have kernels
@@ -493,6 +493,60 @@ def rank_maxsim(vectors, query_sets, groups=None, top_k=5, metric='cosine_simila
         finally:
             ix.set_groups(None)
         return gid.astype(np.int64), sc.astype(np.float64)
+    finally:
+        if owned:
+            ix.close()
+
+
+def rank_mmr(vectors, query_vectors, top_k=5, fetch_k=None, lambda_mult=0.5, metric='cosine_similarity', pair_metric=None, timestamps=None,
+             recency_bias=0):
+    """Additive: a diverse top-k -- maximal marginal relevance.  The ``fetch_k`` best rows of every query are fetched as
+    :func:`rank_batch` ranks them (recency applied), and ``top_k`` of them are picked one after the other: the first by relevance,
+    each later one by ``lambda_mult * relevance - (1 - lambda_mult) * (largest similarity to a row already picked)``.  A near copy
+    of a hit already chosen pays for it; ``lambda_mult=1`` is :func:`rank_batch`, ``0`` is relevance first and then the least
+    similar.
+
+    Returns ``(int64 (Q, k) rows, float64 (Q, k) relevances)`` IN PICK ORDER, ``k = min(top_k, n)``.  ``fetch_k=None`` means
+    ``min(n, 2048, 4 * top_k)`` (the factor of ``oversample``, by analogy and not measured); at most 2048.  ``pair_metric`` -- dot,
+    cosine or euclidean between stored rows -- defaults to ``metric`` where that is one of the three, to cosine otherwise; another
+    one raises NotImplementedError, and so does a ``storage="bits"`` handle.  ``vectors`` is a registered handle on one device or a
+    raw matrix registered for the call; sharded and group handles raise NotImplementedError: the candidates' rows live on
+    different shards."""
+    one_device = "rank_mmr: needs an index on one device; the candidates of a query live on different shards of a sharded handle"
+    if isinstance(vectors, ResidentVectors) and not isinstance(vectors.index, GpuIndex) or isinstance(vectors, GpuGroup):
+        raise NotImplementedError(one_device)
+    ix, _, owned = _resolve(vectors)
+    try:
+        if not isinstance(ix, GpuIndex):
+            raise NotImplementedError(one_device)
+        qh = _query_host(query_vectors)
+        if qh.ndim == 1:
+            qh = qh.reshape(1, -1)
+        _validate_metric(metric)
+        pm = pair_metric if pair_metric is not None else (metric if metric in _native.PAIR_METRICS else "cosine_similarity")
+        _validate_metric(pm)
+        if pm not in _native.PAIR_METRICS:
+            raise NotImplementedError(f"rank_mmr: pair_metric {pm!r} is not built (dot, cosine and euclidean are)")
+        if ix.dtype == _native.HDB_B1:
+            raise NotImplementedError("rank_mmr: a storage='bits' index is a first stage; pair similarity of packed bits is not built")
+        if not 0.0 <= float(lambda_mult) <= 1.0:
+            raise ValueError(f"rank_mmr: lambda_mult must be in [0, 1], got {lambda_mult!r}")
+        if ix.has_nan or np.isnan(qh).any():
+            raise ValueError(NAN_MESSAGE)
+        if ix.n == 0:
+            raise ValueError("vectors is empty")
+        k = max(0, min(int(top_k), ix.n))
+        if k == 0:
+            return np.zeros((qh.shape[0], 0), np.int64), np.zeros((qh.shape[0], 0), np.float64)
+        m = min(ix.n, _native.HDB_MAX_K, 4 * k) if fetch_k is None else min(int(fetch_k), ix.n)
+        m = max(m, k)
+        had_bias = _apply_recency(ix, timestamps, recency_bias)
+        try:
+            idx, sc = ix.mmr(qh, m, k, METRIC_IDS[metric], float(lambda_mult), METRIC_IDS[pm])
+        finally:
+            if had_bias:
+                ix.set_bias(None)
+        return idx.astype(np.int64), sc.astype(np.float64)
     finally:
         if owned:
             ix.close()
