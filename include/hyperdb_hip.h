@@ -598,6 +598,51 @@ int hdb_mmr(hdb_index* ix, const int64_t* dev_idx, const float* dev_score, int32
 int hdb_mmr_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t m, int32_t k, int metric, double lambda, int pair_metric,
                  void* host_record /* hdb_packed_bytes(nq, k) */, void* stream);
 
+/* Range search: every row at or above a score threshold, per query -- near-duplicate detection ("every chunk with cosine >= 0.95"),
+ * score cut-offs in retrieval ("everything relevant, not the best ten"), epsilon-neighbourhoods, FAISS's range_search.  The size of
+ * the answer is a fact of the data.
+ * Semantics.  For query q with threshold t_q, row r is returned when the row mask keeps it, its ranked score s -- the metric's score
+ * with the handle's bias added, NaN -> -inf, -0 -> +0: the float32 every exact call of this handle ranks by, the bits hdb_topk_exact
+ * gives that row in a call of the same queries -- satisfies s >= t_q in float32, and s > -inf.  The threshold lives in the score domain:
+ * higher is better for every metric (euclidean is 1 / (1 + ||v - q||), manhattan 1 / (1 + sum |v - q|); a distance bound D is the
+ * threshold 1 / (1 + D)).  t_q is a float32, one per query; NaN and +inf are HDB_ERR_ARG, -inf returns every eligible row.  Order
+ * inside a query: sorted != 0 -- score descending, then row ascending, the tie rule of every other call; sorted == 0 -- row ascending.
+ * (Euclidean: the score pass stays on the VALU scan, which sums the differences themselves; the matrix cores' ||v||^2 + ||q||^2 -
+ * 2 v.q cancels exactly on the near-duplicates a high threshold selects.)  A row list set beside the mask is not read: the mask serves.
+ * Result: CSR, as FAISS returns it.  host_lims [nq + 1] int64, lims[0] = 0: query q owns entries lims[q] .. lims[q + 1] of idx (int64,
+ * row_base added) and score (float32), lims[nq] entries each.
+ *
+ * hdb_range_host: does the work.  The entries stay on the device in buffers the index owns; the call fills host_lims and synchronises
+ * `stream`.  nq >= 0 (nq == 0 and an empty index: all lims 0).  Served: every dtype (HDB_B1 included) with dot, cosine, euclidean,
+ * manhattan and pearson; hamming and jaccard return HDB_ERR_UNSUPPORTED.  A query that holds a NaN: HDB_ERR_ARG naming HDB_Q_NAN.
+ * hdb_range_fetch: copies the host_lims[nq] entries of the last hdb_range_host call of this handle to host_idx / host_score (both may
+ * be NULL when there are none).  Without such a call, after one that failed, or after the matrix changed (hdb_index_update / _extend /
+ * _gather): HDB_ERR_ARG.
+ * Budget.  An entry costs 20 device bytes (packed key, index, score).  A call whose entries exceed range_bytes fails with
+ * HDB_ERR_NOMEM -- the message names the entries found so far and the budget --, nothing is truncated.  hdb_set_option "range_bytes"
+ * sets it (>= 0; default HDB_RANGE_BYTES_DEFAULT = 1 GiB, beside exact_bytes' 1 GiB); it is the index's, not a member of the plan's
+ * option table: no plan reads it.
+ * How it runs (local-hyperdb_amd/csrc/hdb_range_plan.h, hdb_range.hip).  Queries go through the exact score pass of the multi-kernel
+ * pipeline in chunks of cq <= 256 (128 in K slices) whose scores sbuf[cq][n] stay inside exact_bytes -- VALU scan on matrices of up
+ * to 8192 rows, the matrix cores where the plan of a call of that many queries says so.  Per chunk: count (a workgroup per tile of
+ * HDB_RANGE_TILE rows and query: 16-byte loads, wave ballots, one LDS reduction, no atomics), offsets (a workgroup per query scans
+ * its tile counts), the host reads the per-query counts (the one synchronisation of a chunk), checks the budget and grows the
+ * buffer keeping earlier chunks; emit (the count's tiling: a passing row's slot is its segment start + tile offset + ballot rank --
+ * one owner per slot, row-ascending, the same bits on every run); sort (sorted != 0: a workgroup per segment of up to
+ * HDB_RANGE_LDS_SORT entries, bitonic in 64 KiB of LDS on the packed 64-bit keys; longer segments: rocPRIM's radix sort per segment,
+ * stat range_long).  One unpack launch per call turns the keys into idx / score.
+ * Stats: range (1 after such a call; every other ranking call sets it to 0), range_total (entries of the call), range_chunks,
+ * range_long (segments that took the long sort); mfma / path are those of the score pass.
+ * Not built: a threshold epilogue inside the scan / matrix-core kernels that skips the sbuf round trip (the follow-up); a per-query
+ * result limit; row-list (hdb_index_set_row_subset) calls; several GPUs / shards; hamming / jaccard; a self-join near_duplicates
+ * helper that walks the index's own rows in blocks of 256. */
+#define HDB_RANGE_TILE 4096
+#define HDB_RANGE_LDS_SORT 8192
+#define HDB_RANGE_BYTES_DEFAULT ((int64_t)1 << 30)
+int hdb_range_host(hdb_index* ix, const void* dev_Q, int32_t nq, const float* host_thr /* [nq] */, int metric, int sorted,
+                   int64_t* host_lims /* [nq + 1] */, void* stream);
+int hdb_range_fetch(hdb_index* ix, int64_t* host_idx, float* host_score);   /* host_lims[nq] entries each */
+
 /* Merge `parts` per-shard top-k lists (the all-gathered [parts][nq][k] buffers of the row-sharded
  * index) into the global top-k per query, same ordering rule.  Every part list must be ordered as hdb_topk writes
  * it: score descending, row ascending, unused slots (index -1) at the end. */
@@ -700,6 +745,7 @@ void hdb_group_destroy(hdb_group* g);
  *   group_oversample (hdb_topk_grouped_host: rows per wanted group in the first fast round, 1 .. 64, default 4), group_fast_rounds
  *   (0 .. 2, default 2; 0: every query through the exact grouped pass).
  *   maxsim_team (hdb_maxsim_host: lanes per group of its reduction, 0 = the rule, 1 | 4 | 16 | 64).
+ *   range_bytes (hdb_range_host: device bytes its result may take, 20 per entry, >= 0; default 1 GiB, like exact_bytes).
  *   max_blocks < 0 asks for -max_blocks workgroups per CU in the batched MFMA scan (measured: no gain).
  * Stats:    path (0 small, 1 sampled threshold, 2 exact, 3 full sort), mfma, fused (0 multi-kernel, 1 the 1-4-query single launch,
  *   2 the batched single launch, 3 the bit-metric single launch), local (1: that single launch in its local flavour), f32_split
@@ -710,7 +756,8 @@ void hdb_group_destroy(hdb_group* g);
  *   pass over the plane, 0 when it did not take it), rerank (1: the last call was hdb_rerank / hdb_rerank_host or the second
  *   stage of hdb_two_stage_host; then chunks counts its chunks and every other stat of the call is 0), grouped, group_k,
  *   group_rounds, group_exact (hdb_topk_grouped_host, above), maxsim, maxsim_chunks, maxsim_team, maxsim_sorted, maxsim_bytes
- *   (hdb_maxsim_host, above), mmr, mmr_chunks (hdb_mmr / hdb_mmr_host, above). */
+ *   (hdb_maxsim_host, above), mmr, mmr_chunks (hdb_mmr / hdb_mmr_host, above), range, range_total, range_chunks, range_long
+ *   (hdb_range_host, above). */
 int hdb_set_option(hdb_index* ix, const char* name, int64_t value);
 int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value);
 

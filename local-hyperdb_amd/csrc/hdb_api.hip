@@ -24,6 +24,7 @@
 #include "hdb_group_plan.h"
 #include "hdb_maxsim_plan.h"
 #include "hdb_mmr_plan.h"
+#include "hdb_range_plan.h"
 #include "hdb_devbuf.h"
 #include "../../include/hyperdb_hip.h"
 #include <string>
@@ -113,6 +114,14 @@ struct hdb_index {
     bool plane_declined = false;      // no memory for it (the shadow alone serves): stands until hdb_index_update / hdb_index_quantize
     bool qauto = false;               // the shadow was built by the index itself (auto_quant): its calls return the matrix cores' bits
     bool qauto_declined = false;      // ... or could not be (memory): the decision stands until the matrix changes
+    // the result of the last hdb_range_host call (owned; hdb_range.hip): packed keys while the call runs, then indices and scores for
+    // hdb_range_fetch -- rng_total entries, good (rng_valid) until the next range call or a change of the matrix
+    DevBuf<unsigned long long> rng_keys;
+    DevBuf<int64_t> rng_idx;
+    DevBuf<float> rng_score;
+    int64_t rng_total = 0;
+    bool rng_valid = false;
+    int64_t range_bytes = HDB_RANGE_BYTES_DEFAULT;     // the budget of those three (hdb_set_option "range_bytes")
     // scratch (owned)
     DevBuf<char> ws;
     hdb_options opt;                  // hdb_set_option (hdb_plan.h)
@@ -149,7 +158,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 112; }
+extern "C" int hdb_version(void) { return 113; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 // The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
@@ -192,6 +201,7 @@ static void matrix_changed(hdb_index* ix, int64_t kept_rows, hipStream_t st) {
     ix->bias = nullptr; ix->mask = nullptr;            // per-row inputs of the old matrix no longer apply
     ix->rows = nullptr; ix->subset_m = 0;
     ix->groups = nullptr; ix->n_groups = 0; ix->grp_valid = false;
+    ix->rng_valid = false;                             // (a range result describes the old rows)
     ix->build_stream = st;
 }
 // New blocks for the per-row caches.  The two change together: they are built beside the index and swapped in (caches_commit) after
@@ -561,8 +571,9 @@ extern "C" int hdb_index_set_groups(hdb_index* ix, const int32_t* dev_groups, in
 
 extern "C" int hdb_set_option(hdb_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(HDB_ERR_ARG, "hdb_set_option: null argument");
-    // (the two names that are no member of hdb_options; every other name and its rule: HDB_OPTIONS, hdb_plan.h)
+    // (the three names that are no member of hdb_options -- no plan reads them; every other name and its rule: HDB_OPTIONS, hdb_plan.h)
     if (!strcmp(name, "profile")) { ix->profile = value; ix->ev_used = 0; }
+    else if (!strcmp(name, "range_bytes")) ix->range_bytes = std::max<int64_t>(value, 0);
     else if (!strcmp(name, "host_timing_reset")) { ix->ht_pre_ns = ix->ht_launch_ns = ix->ht_wait_ns = ix->ht_calls = ix->ht_attr_ns = 0; }
     else if (!hdb_option_set(ix->opt, name, value)) return fail(HDB_ERR_ARG, std::string("hdb_set_option: unknown option ") + name);
     return HDB_OK;
@@ -1792,7 +1803,7 @@ static int mmr_impl(hdb_index* ix, const int64_t* dev_idx, const float* dev_scor
     MmrWs w;
     const int rc = ws_lay(ix, w, p.cq, p.mp);
     if (rc) return rc;
-    ix->st.rerank = ix->st.grouped = ix->st.maxsim = 0;
+    ix->st.rerank = ix->st.grouped = ix->st.maxsim = ix->st.range = 0;
     ix->st.mmr = 1; ix->st.mmr_chunks = 0;
     for (int q0 = 0; q0 < nq; q0 += p.cq) {
         const int cq = std::min(p.cq, nq - q0);
@@ -1842,6 +1853,133 @@ extern "C" int hdb_mmr_host(hdb_index* ix, const void* dev_Q, int32_t nq, int32_
     rc = hostrec_open(ix->rec, nq, k, host_record, false, rec); if (rc) return rc;
     rc = mmr_impl(ix, r1.idx, r1.score, nq, m, k, lambda, pair_metric, rec.view.idx, rec.view.score, r1.status, rec.view.status, st); if (rc) return rc;
     return hostrec_close(rec, st);
+}
+
+// ---- range search: every row at or above a per-query threshold (hdb_range.hip, hdb_range_plan.h) ---------------------------------------
+// Room for `total` packed keys, the first `keep` of them (the earlier chunks' segments) kept; half as much again, inside the budget.
+static int range_room(hdb_index* ix, int64_t total, int64_t keep, hipStream_t st) {
+    if ((size_t)total <= ix->rng_keys.cap) return HDB_OK;
+    const int64_t most = ix->range_bytes / hdb_range_result_bytes(1);
+    const hipError_t e = ix->rng_keys.grow_keep((size_t)std::min<int64_t>(most, total + total / 2 + 1024), (size_t)keep, st);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(HDB_ERR_NOMEM, std::string("hdb_range_host: the result buffer: ") + hipGetErrorString(e)); }
+    return HDB_OK;
+}
+// The segments of one chunk in (score descending, row ascending) order: one launch for those the LDS sort takes, the cold path for
+// each longer one.  lims: the chunk's cq + 1 segment starts on the host.
+static int range_sort(hdb_index* ix, const int64_t* lims, int cq, const int64_t* dev_qoff, hipStream_t st) {
+    bool lds = false;
+    int64_t longest = 0;
+    for (int q = 0; q < cq; ++q) {
+        const int64_t cnt = lims[q + 1] - lims[q];
+        lds = lds || (cnt >= 2 && cnt <= HDB_RANGE_LDS_SORT);
+        if (cnt > HDB_RANGE_LDS_SORT) { longest = std::max(longest, cnt); ix->st.range_long++; }
+    }
+    if (lds) LAUNCH_TRY(hdb_launch_range_sort(ix->rng_keys, dev_qoff, cq, st));
+    if (longest == 0) return HDB_OK;
+    size_t temp_bytes = 0;
+    LAUNCH_TRY(hdb_range_sort_temp_bytes(longest, &temp_bytes));
+    DevBuf<unsigned long long> out;
+    DevBuf<char> temp;
+    HIP_TRY(out.alloc((size_t)longest));
+    HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 16)));
+    for (int q = 0; q < cq; ++q) {
+        const int64_t cnt = lims[q + 1] - lims[q];
+        if (cnt > HDB_RANGE_LDS_SORT) LAUNCH_TRY(hdb_launch_range_sort_long(temp, temp_bytes, ix->rng_keys + lims[q], out, cnt, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                 // (the temporaries go when this function returns)
+    return HDB_OK;
+}
+
+extern "C" int hdb_range_host(hdb_index* ix, const void* dev_Q, int32_t nq, const float* host_thr, int metric, int sorted, int64_t* host_lims,
+                              void* stream) {
+    // what the numbers alone decide, then the handle, then the device
+    if (nq < 0) return fail(HDB_ERR_ARG, "hdb_range_host: nq must be >= 0");
+    if (!host_lims || (nq > 0 && !host_thr)) return fail(HDB_ERR_ARG, "hdb_range_host: null argument (host_thr, host_lims)");
+    for (int32_t q = 0; q < nq; ++q)
+        if (std::isnan(host_thr[q]) || host_thr[q] == INFINITY)
+            return fail(HDB_ERR_ARG, "hdb_range_host: the threshold of query " + std::to_string(q) + " is NaN or +inf (a finite value or -inf)");
+    if (!ix) return fail(HDB_ERR_ARG, "hdb_range_host: null index");
+    int rc = ranking_metric("hdb_range_host", "range calls are", metric); if (rc) return rc;
+    ix->rng_valid = false; ix->rng_total = 0;
+    for (int32_t q = 0; q <= nq; ++q) host_lims[q] = 0;
+    stats_begin(ix, TopkStats()); ix->st.range = 1;
+    if (nq == 0 || ix->n == 0) { ix->rng_valid = true; return HDB_OK; }
+    if (!dev_Q) return fail(HDB_ERR_ARG, "hdb_range_host: query pointer is null");
+    if (ix->n > 0xFFFFFFFFll) return fail(HDB_ERR_UNSUPPORTED, "hdb_range_host: more than 2^32 - 1 rows are not built");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the score pass: the exact shape of run_pipeline for the nq queries, cut by the chunk plan
+    TopkPlan p;
+    rc = plan_call(ix, range_call(nq, metric), p); if (rc) return rc;
+    if (!range_shape(p)) return fail(HDB_ERR_UNSUPPORTED, "hdb_range_host: this call has no exact score pass");
+    const int64_t n = ix->n;
+    const RangePlan rp = range_plan(n, nq, p.ksplit ? 128 : 256, ix->opt.exact_bytes);
+    p.cq_max = rp.cq;
+    stats_begin(ix, p.stats);          // (here, not sooner: the statistics are those of the plan as used)
+    ix->st.range = 1; ix->st.range_chunks = range_chunks(rp, nq); ix->st.chunks = ix->st.range_chunks;
+    RangeWs w;
+    rc = ws_lay(ix, w, (int)nq, (int)ix->d, p.W, p.cq_max, p.ld_scores, p.ld_ks, rp.ntiles);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(w.thr, host_thr, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+    TopkEnv e; e.w = w.t; e.sort_temp = 0;
+    const TopkArgs c{dev_Q, nq, 1, metric, nullptr, nullptr, nullptr, st};
+    rc = topk_prologue(ix, c, p, e); if (rc) return rc;
+    bool f32s = false;
+    rc = exact_parts(ix, p, w.t.qnan, nq, st, f32s); if (rc) return rc;
+    std::vector<int> h_qnan((size_t)nq);               // (the preparation's NaN words: read with the first chunk's counts)
+    std::vector<uint32_t> h_cnt((size_t)p.cq_max);
+    bool q16_ready = p.q16_in_prep;
+    for (int q0 = 0; q0 < nq; q0 += p.cq_max) {
+        const int cq = std::min<int>(p.cq_max, nq - q0);
+        QueryBufs qb; ScanArgs a;
+        rc = chunk_args(ix, p, e, f32s, nq, q0, cq, n, q16_ready, st, qb, a); if (rc) return rc;
+        rc = score_chunk(ix, p, a, qb, cq, w.t.sbuf, st); if (rc) return rc;
+        LAUNCH_TRY(hdb_launch_range_count(w.t.sbuf, p.ld_n, n, cq, w.thr + q0, rp.ntiles, w.tcnt, st));
+        LAUNCH_TRY(hdb_launch_range_offsets(w.tcnt, rp.ntiles, cq, w.qcnt, st));
+        // the one synchronisation of a chunk: its counts decide the budget, the buffer and the segment starts
+        hipError_t he = hipMemcpyAsync(h_cnt.data(), w.qcnt, (size_t)cq * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess && q0 == 0) he = hipMemcpyAsync(h_qnan.data(), w.t.qnan, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st);
+        const hipError_t se = hipStreamSynchronize(st);                    // (also where a copy failed: nothing is in flight into the vectors afterwards)
+        HIP_TRY(he); HIP_TRY(se);
+        if (q0 == 0)
+            for (int32_t q = 0; q < nq; ++q)
+                if (h_qnan[q] & 1) return fail(HDB_ERR_ARG, "hdb_range_host: query " + std::to_string(q) + " holds a NaN (HDB_Q_NAN)");
+        int64_t* const lims = host_lims + q0;
+        for (int q = 0; q < cq; ++q) lims[q + 1] = lims[q] + (int64_t)h_cnt[q];
+        const int64_t total = lims[cq];
+        if (hdb_range_result_bytes(total) > ix->range_bytes)
+            return fail(HDB_ERR_NOMEM, "hdb_range_host: " + std::to_string(total) + " results up to query " + std::to_string(q0 + cq - 1) + " need " +
+                                           std::to_string(hdb_range_result_bytes(total)) + " bytes, the budget range_bytes is " + std::to_string(ix->range_bytes));
+        if (total == lims[0]) continue;                // (nothing passed in this chunk)
+        rc = range_room(ix, total, lims[0], st); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(w.qoff, lims, ((size_t)cq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(hdb_launch_range_emit(w.t.sbuf, p.ld_n, n, cq, w.thr + q0, rp.ntiles, w.tcnt, w.qoff, ix->rng_keys, st));
+        if (sorted) { rc = range_sort(ix, lims, cq, w.qoff, st); if (rc) return rc; }
+    }
+    const int64_t total = host_lims[nq];
+    if (total > 0) {
+        if ((size_t)total > ix->rng_idx.cap) {
+            const size_t cap = std::max<size_t>(ix->rng_keys.cap, (size_t)total);        // (the three grow together)
+            hipError_t he = ix->rng_idx.alloc(cap);
+            if (he == hipSuccess) he = ix->rng_score.alloc(cap);
+            if (he != hipSuccess) { (void)hipGetLastError(); return fail(HDB_ERR_NOMEM, std::string("hdb_range_host: the result buffer: ") + hipGetErrorString(he)); }
+        }
+        LAUNCH_TRY(hdb_launch_range_unpack(ix->rng_keys, total, ix->row_base, ix->rng_idx, ix->rng_score, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    ix->rng_total = total; ix->rng_valid = true; ix->st.range_total = total;
+    return HDB_OK;
+}
+
+extern "C" int hdb_range_fetch(hdb_index* ix, int64_t* host_idx, float* host_score) {
+    if (!ix) return fail(HDB_ERR_ARG, "hdb_range_fetch: null index");
+    if (!ix->rng_valid) return fail(HDB_ERR_ARG, "hdb_range_fetch: no range result to fetch (no hdb_range_host call yet, it failed, or the matrix changed since)");
+    if (ix->rng_total == 0) return HDB_OK;
+    if (!host_idx || !host_score) return fail(HDB_ERR_ARG, "hdb_range_fetch: null argument");
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipMemcpy(host_idx, ix->rng_idx, (size_t)ix->rng_total * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_score, ix->rng_score, (size_t)ix->rng_total * sizeof(float), hipMemcpyDeviceToHost));
+    return HDB_OK;
 }
 
 extern "C" int hdb_merge_topk(const int64_t* dev_idx_parts, const float* dev_score_parts, int32_t parts, int32_t nq,

@@ -183,6 +183,21 @@ int hdb_launch_mmr_pairs(const void* V, int dtype, int d, int pair_metric, const
 int hdb_launch_mmr_select(const uint32_t* rows, const float* rel, const int32_t* cnt, int nq, int mp, const float* P, float lam,
                           int k, int64_t row_base, int64_t* idx_out, float* score_out, void* stream);
 
+// ---- hdb_range.hip: range search (every row at or above a per-query threshold) ----
+// Per chunk of cq queries over sbuf [cq][ld_n] (ntiles tiles of HDB_RANGE_TILE rows per query).  count: tcnt [cq][ntiles] passing rows
+// per tile.  offsets: tcnt scanned in place per query (exclusive), qcnt [cq] the totals.  emit: the packed entry of every passing row
+// at keys[qoff[q] + toff[q][tile] + its rank in the tile], row-ascending; qoff [cq + 1] the segment starts.  sort: every segment of
+// 2 .. HDB_RANGE_LDS_SORT keys descending, in place; sort_long: one longer segment through `out` (cnt keys) and rocPRIM's scratch.
+// unpack: keys [total] -> idx (row_base added), score.
+int hdb_launch_range_count(const float* sbuf, int64_t ld_n, int64_t n, int cq, const float* thr, int64_t ntiles, uint32_t* tcnt, void* stream);
+int hdb_launch_range_offsets(uint32_t* tcnt, int64_t ntiles, int cq, uint32_t* qcnt, void* stream);
+int hdb_launch_range_emit(const float* sbuf, int64_t ld_n, int64_t n, int cq, const float* thr, int64_t ntiles, const uint32_t* toff,
+                          const int64_t* qoff, unsigned long long* keys, void* stream);
+int hdb_launch_range_sort(unsigned long long* keys, const int64_t* qoff, int cq, void* stream);
+int hdb_range_sort_temp_bytes(int64_t cnt, size_t* bytes);
+int hdb_launch_range_sort_long(void* temp, size_t temp_bytes, unsigned long long* keys, unsigned long long* out, int64_t cnt, void* stream);
+int hdb_launch_range_unpack(const unsigned long long* keys, int64_t total, int64_t row_base, int64_t* idx, float* score, void* stream);
+
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 int hdb_launch_qb_scan(const QuantArgs* args, int mode, float* wstat, int64_t wld, int max_blocks, void* stream);
 int hdb_launch_qb_thr(const float* vals, int64_t n, int64_t ld, int nq, uint32_t m, float* thr, void* stream);

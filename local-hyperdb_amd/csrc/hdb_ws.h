@@ -99,6 +99,21 @@ struct MaxsimWs {
     }
 };
 
+// hdb_range_host: the main pipeline's layout for the call's nq queries in chunks of cq (exact shape: ld_scores = all rows), then the
+// call's thresholds, and per chunk the tile counters tcnt [cq][ntiles] (the count pass; scanned in place into tile offsets), the
+// per-query totals qcnt and the segment starts qoff [cq + 1] (hdb_range_plan.h).
+struct RangeWs {
+    TopkWs t;
+    float* thr; uint32_t* tcnt; uint32_t* qcnt; int64_t* qoff;
+    void lay(Bump& b, int nq, int d, int W, int cq, int64_t ld_scores, int64_t ld_ks, int64_t ntiles) {
+        t.lay(b, nq, d, W, cq, ld_scores, ld_ks, 0, 0, 0);
+        thr = b.take<float>((size_t)nq);
+        tcnt = b.take<uint32_t>((size_t)cq * (size_t)ntiles);
+        qcnt = b.take<uint32_t>((size_t)cq);
+        qoff = b.take<int64_t>((size_t)cq + 1);
+    }
+};
+
 // hdb_mmr: the buffers of one chunk of cq queries (hdb_mmr_plan.h).  mp: the list length rounded up to the pair tile -- the
 // candidates' local rows and relevances in list order, their counts, and the pair matrix P [cq][mp][mp].
 struct MmrWs {

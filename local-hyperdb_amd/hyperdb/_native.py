@@ -54,6 +54,7 @@ EXPORTS = (
     "hdb_index_set_groups", "hdb_topk_grouped_host", "hdb_collapse_groups",
     "hdb_maxsim_host",
     "hdb_mmr", "hdb_mmr_host",
+    "hdb_range_host", "hdb_range_fetch",
 )
 
 
@@ -108,6 +109,8 @@ def _load():
     lib.hdb_maxsim_host.argtypes = [vp, vp, vp, i32, i32, ctypes.c_int, vp, vp]
     lib.hdb_mmr.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_double, ctypes.c_int, vp, vp, vp, vp]
     lib.hdb_mmr_host.argtypes = [vp, vp, i32, i32, i32, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp, vp]
+    lib.hdb_range_host.argtypes = [vp, vp, i32, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.hdb_range_fetch.argtypes = [vp, vp, vp]
     lib.hdb_merge_topk_packed.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int, vp]
     lib.hdb_merge_topk_host.argtypes = [vp, i32, i32, i32, vp]
     lib.hdb_host_exchange_merge.argtypes = [vp, i64, i32, i32, ctypes.c_uint64, vp, i32, i32, vp, ctypes.c_double]
@@ -738,6 +741,29 @@ class GpuIndex:
             raise ValueError(NAN_MESSAGE)
         return slot[2].copy(), slot[3].copy()
 
+    def range(self, Q, thr, metric_id, sort=True):
+        """Range search (hdb_range_host + hdb_range_fetch): every row whose ranked score is at or above the query's threshold ->
+        numpy ``(lims int64 [nq + 1], idx int64 [total], scores float32 [total])``, the CSR layout of FAISS ``range_search``: query
+        ``q`` owns ``lims[q] .. lims[q + 1]``.  ``thr``: a scalar for all queries or one value per query, rounded to float32, in the
+        score domain the engine ranks by (higher is better for every metric); ``-inf`` returns every eligible row, NaN and ``+inf``
+        raise ValueError.  ``sort=True``: score descending, row ascending inside a query; ``False``: row ascending.  Bias and row
+        mask of the handle apply; rows at ``-inf`` are never returned.  A NaN query raises ValueError; hamming / jaccard:
+        NotImplementedError; a result beyond the option ``range_bytes``: HyperDBNativeError (status -4) naming the total."""
+        qt = self._query_tensor(Q, batched=True)
+        nq = int(qt.shape[0])
+        t = check_thresholds(thr, nq)
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        with torch.cuda.device(self.device):
+            rc = _lib.hdb_range_host(self._h, ctypes.c_void_p(qt.data_ptr()), nq, t.ctypes.data_as(ctypes.c_void_p), int(metric_id),
+                                     1 if sort else 0, lims.ctypes.data_as(ctypes.c_void_p), _stream_ptr(self.device))
+            if rc == -1 and b"HDB_Q_NAN" in _lib.hdb_last_error():
+                raise ValueError(NAN_MESSAGE)
+            _check(rc, "hdb_range_host")
+            total = int(lims[nq])
+            idx, sc = np.empty(total, dtype=np.int64), np.empty(total, dtype=np.float32)
+            _check(_lib.hdb_range_fetch(self._h, idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p)), "hdb_range_fetch")
+        return lims, idx, sc
+
     # -- options / stats -----------------------------------------------------------------------
     def set_option(self, name, value):
         """An option of the index by its C name (include/hyperdb_hip.h lists them), e.g. ``set_option("b1_mfma_min_q", 5)``: a
@@ -1220,6 +1246,50 @@ def maxsim_host(V, query_sets, groups, k, metric, bias=None, mask=None, n_groups
         out_i[s, :order.size] = order
         out_s[s, :order.size] = total[order]
     return out_i, out_s
+
+
+def check_thresholds(thr, nq):
+    """The thresholds of a range call -> contiguous float32 ``[nq]``: a scalar is broadcast, anything else must hold one value per
+    query; values are rounded to float32; NaN and ``+inf`` raise ValueError (``-inf``: every eligible row)."""
+    t = np.asarray(thr, dtype=np.float64)
+    if t.ndim == 0:
+        t = np.full(nq, float(t))
+    t = t.reshape(-1)
+    if t.size != nq:
+        raise ValueError(f"range: need one threshold per query ({nq}) or a scalar, got {t.size}")
+    if np.isnan(t).any() or np.isposinf(t).any():
+        raise ValueError("range: a threshold is NaN or +inf (a finite value, or -inf for every eligible row)")
+    with np.errstate(over="ignore"):
+        t = np.ascontiguousarray(t, dtype=np.float32)
+    if np.isposinf(t).any():
+        raise ValueError("range: a threshold rounds to +inf in float32")
+    return t
+
+
+def range_host(V, Q, thr, metric, bias=None, mask=None, sort=True):
+    """The contract of hdb_range_host in numpy, float64: ``(lims int64 [nq + 1], idx int64 [total], scores float64 [total])``.  Row
+    ``r`` belongs to query ``q`` when the mask keeps it, ``s = score + bias`` (NaN -> ``-inf``) is at or above the float32 threshold
+    and ``s > -inf``.  Order inside a query: ``sort`` -- score descending, row ascending; otherwise row ascending."""
+    if metric in ("hamming_distance", "jaccard_similarity"):
+        raise NotImplementedError(f"range_host: {metric} range calls are not built")
+    V = np.asarray(V)
+    Q = np.asarray(Q, dtype=np.float64)
+    Q = Q.reshape(1, -1) if Q.ndim == 1 else Q
+    n, nq = int(V.shape[0]), int(Q.shape[0])
+    t = check_thresholds(thr, nq).astype(np.float64)
+    keep = np.ones(n, dtype=bool) if mask is None else np.asarray(mask).reshape(-1) != 0
+    b = np.zeros(n) if bias is None else np.asarray(bias, dtype=np.float64).reshape(-1)
+    lims, idx, sc = np.zeros(nq + 1, dtype=np.int64), [], []
+    for q in range(nq):
+        s = (_host_scores(V, Q[q], metric) + b) if n else np.zeros(0)
+        s = np.where(np.isnan(s), -np.inf, s) + 0.0
+        rows = np.flatnonzero(keep & (s >= t[q]) & (s > -np.inf))
+        if sort:
+            rows = rows[np.lexsort((rows, -s[rows]))]
+        idx.append(rows)
+        sc.append(s[rows])
+        lims[q + 1] = lims[q] + rows.size
+    return lims, np.concatenate(idx).astype(np.int64) if idx else np.zeros(0, np.int64), np.concatenate(sc) if sc else np.zeros(0)
 
 
 def _pair_matrix_host(X, pair_metric):

@@ -849,6 +849,41 @@ class HyperDB:
             ix.set_groups(None)
         return self._multi_results(group_by, codes.cpu().numpy(), gids[0], sc[0], keep, return_similarities)
 
+    def query_range(self, query_input, min_score, return_similarities=True, filters=None, metric='cosine_similarity'):
+        """Additive: every document whose score is at or above ``min_score`` -- not the best ``top_k`` -- as a list of
+        ``(document, score)``, best first (ties in store order), or the documents alone with ``return_similarities=False``.
+        ``min_score`` lives in the score domain :meth:`query` ranks by: higher is better for every metric (``euclidean_metric`` is
+        ``1 / (1 + distance)``).  ``filters`` become the row mask, as in :meth:`query`.  No recency bias (a cut-off on a biased
+        score has no fixed meaning across calls), not cached, one device only (NotImplementedError with ``devices=[...]``);
+        hamming and jaccard are not built (NotImplementedError)."""
+        if self._index is None or not self.documents:
+            raise Exception("The database is empty. Cannot proceed with the query.")
+        if metric not in _METRICS:
+            raise ValueError(f"Invalid metric '{metric}'. Supported: " + ", ".join(f"'{m}'" for m in _METRICS))
+        ranking._validate_metric(metric)
+        ix = self._index
+        if isinstance(ix, GpuGroup):
+            raise NotImplementedError("query_range on several devices is not built")
+        Q = self._query_vectors(query_input)
+        if len(Q) != 1:
+            raise ValueError("query_range() takes one query.")
+        if ix.has_nan or bool(np.isnan(Q).any()):
+            raise ValueError(ranking.NAN_MESSAGE)
+        masks, n_avail, _, _ = self._mask_for(filters)
+        if n_avail == 0:
+            print("INFO: No document matches your query with the brute-force method and the current filters.")
+            return []
+        try:
+            ix.set_row_mask(None if masks is None else masks[0])
+            ix.set_bias(None)
+            _, rows, sc = ix.range(Q, min_score, METRIC_IDS[metric], sort=True)
+        finally:
+            ix.set_row_mask(None)
+        docs = self._docs_of_rows(rows).tolist()
+        if not return_similarities:
+            return [self.documents[r] for r in docs]
+        return [(self.documents[r], s_) for r, s_ in zip(docs, sc.tolist())]
+
     def _query_one(self, query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by):
         key = self._hashable_key(query_input, top_k, return_similarities, filters, recency_bias, timestamp_key, metric, ann_percent, group_by)
         if key in self._cache:

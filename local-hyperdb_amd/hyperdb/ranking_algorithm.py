@@ -36,7 +36,7 @@ __all__ = [
     "get_norm_vector", "dot_product", "cosine_similarity", "euclidean_metric", "manhattan_distance",
     "jaccard_similarity", "pearson_correlation", "check_and_binarize_vectors", "hamming_distance",
     "hyperDB_ranking_algorithm_sort", "rank_batch", "register_vectors", "ResidentVectors",
-    "rerank_batch", "rank_two_stage", "rank_grouped", "rank_maxsim", "rank_mmr",
+    "rerank_batch", "rank_two_stage", "rank_grouped", "rank_maxsim", "rank_mmr", "rank_range",
 ]
 
 _GPU_METRICS = tuple(METRIC_IDS)      # all seven metrics of the reference's dispatch table have kernels
@@ -493,6 +493,38 @@ def rank_maxsim(vectors, query_sets, groups=None, top_k=5, metric='cosine_simila
         finally:
             ix.set_groups(None)
         return gid.astype(np.int64), sc.astype(np.float64)
+    finally:
+        if owned:
+            ix.close()
+
+
+def rank_range(vectors, query_vectors, min_score, metric='cosine_similarity', sort=True):
+    """Additive: range search -- every row whose score is at or above ``min_score``, not a fixed number of them (near-duplicate
+    detection, score cut-offs, epsilon-neighbourhoods; FAISS ``range_search``).
+
+    ``query_vectors`` is a ``(d,)`` or ``(Q, d)`` array; ``min_score`` a scalar for all queries or one value per query, in the score
+    domain the engine ranks by: higher is better for every metric (``euclidean_metric`` is ``1 / (1 + distance)``, so "within
+    distance D" is ``min_score = 1 / (1 + D)``; ``manhattan_distance`` likewise).  Values are rounded to float32; ``-inf`` returns
+    every row that has a score, NaN and ``+inf`` raise ValueError.  Returns ``(lims int64 (Q + 1,), idx int64 (total,), scores
+    float64 (total,))``: query ``q`` owns ``idx[lims[q]:lims[q + 1]]`` -- score descending, row ascending with ``sort=True``, row
+    ascending otherwise.  A bias or row mask set on the handle applies.  ``vectors`` is a registered handle on one device or a raw
+    matrix registered for the call; sharded and group handles raise NotImplementedError, and so do hamming and jaccard."""
+    one_device = "rank_range: needs an index on one device; sharded and group handles are not built"
+    if isinstance(vectors, ResidentVectors) and not isinstance(vectors.index, GpuIndex) or isinstance(vectors, GpuGroup):
+        raise NotImplementedError(one_device)
+    ix, _, owned = _resolve(vectors)
+    try:
+        if not isinstance(ix, GpuIndex):
+            raise NotImplementedError(one_device)
+        qh = _query_host(query_vectors)
+        if qh.ndim == 1:
+            qh = qh.reshape(1, -1)
+        _validate_metric(metric)
+        thr = _native.check_thresholds(min_score, int(qh.shape[0]))
+        if ix.has_nan or np.isnan(qh).any():
+            raise ValueError(NAN_MESSAGE)
+        lims, idx, sc = ix.range(qh, thr, METRIC_IDS[metric], sort=sort)
+        return lims, idx, sc.astype(np.float64)
     finally:
         if owned:
             ix.close()
