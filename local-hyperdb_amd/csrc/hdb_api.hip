@@ -846,7 +846,9 @@ static int shadow_prepare(hdb_index* ix, const TopkPlan& p, int nq, hipStream_t 
 // the scaled fp16 copy, codes of the rounded query), the filter pass copies every candidate's row into a compact matrix as it emits
 // it, the MODE 0 launch of the matrix-core scan scores that, the finalize packs those scores into the list before it selects.
 // Launches: query prep, sample pass, filter pass, MODE 0, finalize -- five with the threshold folded into the passes (nsub), six
-// with hdb_sample_thr_kernel; the explicit shadow has two query prep launches and hdb_quant_rescore_kernel in MODE 0's place.
+// with hdb_sample_thr_kernel; the explicit shadow has two query prep launches and, in MODE 0's place, the gather scorer
+// of hdb_rerank.hip (hdb_rerank_score_kernel, rows taken from the entries): the one kernel that scores listed rows with the
+// row scan's bits.
 static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
     const void* dev_Q = c.Q; const int32_t nq = c.nq, k = c.k; const int metric = c.metric; hipStream_t st = c.st;
     int64_t* dev_idx = c.idx; float* dev_score = c.score; int32_t* dev_status = c.status;      // (the call, under the names the body uses)
@@ -898,8 +900,10 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         s.scores = w.gsc; s.ld = (int64_t)crow;
         LAUNCH_TRY(hdb_launch_mfma_scan(&s, ix->dtype, 0, nq, w.q16, w.ginv, w.qsq, w.qscl, (int)ix->opt.max_blocks, (int)ix->opt.mfma_variant, st, nullptr));
     } else {
-        LAUNCH_TRY(hdb_launch_quant_rescore(ix->V, ix->d, ix->dtype, (const float*)dev_Q, nq, metric, ix->inv_norm, w.qinv, ix->bias, ix->mask,
-                                            w.cand, w.cnt, HDB_CAND_CAP, st));
+        // the gather scorer on the entries the filter pass left (no row list): the VALU scan's bits; a masked row is among them, -inf here
+        ScanArgs s; base_args(ix, s, dev_Q, metric);
+        s.qinv = w.qinv; s.bias = ix->bias; s.cnt = w.cnt; s.cand = w.cand; s.nq = nq;
+        LAUNCH_TRY(hdb_launch_rerank_score(&s, ix->dtype, nq, st));
     }
     LAUNCH_TRY(hdb_launch_quant_finalize(w.cand, w.cnt, HDB_CAND_CAP, nq, (uint32_t)k, kk, ix->row_base, dev_idx, dev_score, dev_status, w.qnan,
                                          w.qaux, w.thr, ix->qstat, mflavour ? w.cand : nullptr, w.gsc, (int64_t)crow, st));

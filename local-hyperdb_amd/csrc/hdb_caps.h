@@ -23,6 +23,12 @@ static inline int hdb_scan_auto_blocks(int dtype, int row_bytes, bool vec, bool 
     }
     return wide_rows ? 256 : 512;
 }
+// The 16-byte flavour of the scan: rows are whole 16-byte pieces of a 16-byte aligned matrix, and one query in the accumulate type
+// (8 bytes per element for a float64 index, 4 for every other) fits the 60 KiB of LDS a scan kernel allows its queries.  The lane
+// split of a row's sum depends on this choice, and the gather scorer (hdb_rerank.hip) owes the scan's bits: both launchers ask here.
+static inline bool hdb_scan_rows_in_pieces(int64_t row_bytes, const void* base, int d, int elem_bytes) {
+    return row_bytes % 16 == 0 && ((uintptr_t)base & 15) == 0 && (size_t)d * (elem_bytes == 8 ? 8 : 4) <= 60 * 1024;
+}
 
 // ---- hdb_bscan.hip: float32 queries against packed-bit rows (HDB_B1) ----
 // One thread per row.  A query lives in LDS as a NIBBLE TABLE, T[d / 4][16] floats = 16 d bytes: entry [j][m] is the sum of the four

@@ -1,6 +1,6 @@
 // hdb_emit.h -- the shared epilogue of the row scans (hdb_scan.hip, hdb_bscan.hip): raw row sum -> final score, then store / filter,
 // and the per-block survivor stage behind the filter.  One text for both units, so a row's score is finished the same way whatever
-// kernel summed it.
+// kernel summed it; its first half, raw sum -> score before bias (hdb_sum_score), also serves hdb_rerank.hip and hdb_mmr.hip.
 #pragma once
 #include "hdb_common.h"
 #include "../../include/hyperdb_hip.h"
@@ -31,21 +31,22 @@ __device__ __forceinline__ void hdb_stage_flush(const ScanArgs& a, HdbStage& st,
     }
 }
 
+// Raw row sum -> score before bias: the one text of every unit that finishes a row-scan sum (hdb_emit below, the gather scorer of
+// hdb_rerank.hip, hdb_mmr_pairs_kernel).  Cosine multiplies by rscale[r], then by qscale[q] -- the cached 1/||v|| and 1/||q||;
+// hdb_mmr_pairs_kernel passes the second row's 1/||v|| where the query's scale goes.  Neither is read for another metric.
+template <typename Acc>
+__device__ __forceinline__ float hdb_sum_score(int metric, Acc sum, const float* rscale, int64_t r, const float* qscale, int64_t q) {
+    if (metric == HDB_EUCLIDEAN) return (float)(Acc(1) / (Acc(1) + sqrt(sum)));      // 1/(1+||v-q||), :49-51
+    if (metric == HDB_MANHATTAN) return (float)(Acc(1) / (Acc(1) + sum));            // 1/(1+sum|v-q|), :59-60
+    if (metric == HDB_EUCLIDEAN_DIST) return (float)sqrt(sum);
+    if (metric == HDB_COSINE) return (float)sum * rscale[r] * qscale[q];             // :37-41 with cached norms
+    return (float)sum;                                                               // dot / hamming
+}
+
 // Shared epilogue: raw row sum -> final score of hyperDB_ranking_algorithm_sort, then store / filter.
 template <int MODE, typename Acc>
 __device__ __forceinline__ void hdb_emit(const ScanArgs& a, int q, int64_t row, int64_t out_i, Acc sum, HdbStage* stg = nullptr, int slot = 0) {
-    float s;
-    if (a.metric == HDB_EUCLIDEAN) {
-        s = (float)(Acc(1) / (Acc(1) + sqrt(sum)));                       // 1/(1+||v-q||), :49-51
-    } else if (a.metric == HDB_MANHATTAN) {
-        s = (float)(Acc(1) / (Acc(1) + sum));                             // 1/(1+sum|v-q|), :59-60
-    } else if (a.metric == HDB_EUCLIDEAN_DIST) {
-        s = (float)sqrt(sum);
-    } else if (a.metric == HDB_COSINE) {
-        s = (float)sum * a.inv_norm[row] * a.qinv[q];                      // :37-41 with cached norms
-    } else {
-        s = (float)sum;                                                    // dot / hamming
-    }
+    float s = hdb_sum_score(a.metric, sum, a.inv_norm, row, a.qinv, q);
     if (a.bias) s += a.bias[row];                                          // recency, :186
     const bool masked = a.mask && !a.mask[row];                            // filtered-out row
     if (masked) s = -INFINITY;

@@ -126,9 +126,6 @@ int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux, const flo
 int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int blocks, void* stream);
 int hdb_launch_quant_scan(const QuantArgs* args, int mode, int max_blocks, void* stream);
 int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int max_blocks, void* stream);
-int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
-                             const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
-                             const uint32_t* cnt, uint32_t cap, void* stream);
 int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq, uint32_t k, uint32_t kk,
                               int64_t row_base, int64_t* idx_out, float* score_out, int32_t* status, const int* qnan,
                               const float* qaux, const float* thr, int* stat, unsigned long long* cand_rw, const float* sc, int64_t ld,
@@ -136,7 +133,8 @@ int hdb_launch_quant_finalize(const unsigned long long* cand, const uint32_t* cn
 
 // ---- hdb_rerank.hip: exact scores of per-query candidate lists ----
 // prep: cand [nq][m] caller ids -> rows [nq][m] valid, ascending, unique local rows, cnt[q * HDB_CNT_STRIDE] of them, status[q]
-// score: ScanArgs as for the VALU scan, with rows = those lists, m = their leading dimension, cnt / cand / cap the packed lists out
+// score: ScanArgs as for the VALU scan, with rows = those lists, m = their leading dimension, cnt / cand / cap the packed lists out;
+//        rows = nullptr: the rows are those of the entries already in cand (the int8 shadow's candidates), rewritten in place
 int hdb_launch_rerank_prep(const int64_t* cand, int m, int nq, int64_t n, int64_t row_base, const uint8_t* mask, const int* qnan,
                            int64_t* rows, uint32_t* cnt, int32_t* status, void* stream);
 int hdb_launch_rerank_score(const ScanArgs* args, int dtype, int nq_launch, void* stream);

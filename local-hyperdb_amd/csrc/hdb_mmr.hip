@@ -30,6 +30,7 @@
 // multiplies by the cached 1/||v|| of the LOWER row first, so the value does not depend on which of the two stands first in a list.
 #include "hdb_common.h"
 #include "hdb_unpack.h"
+#include "hdb_emit.h"        // hdb_sum_score
 #include "hdb_first_occ.h"
 #include "../../include/hyperdb_hip.h"
 #include <algorithm>
@@ -188,11 +189,8 @@ __global__ __launch_bounds__(HDB_MMR_TILE * HDB_MMR_TILE) void hdb_mmr_pairs_ker
     }
     if (!active) return;
     const uint32_t ra = list[ci], rb = list[cj];
-    float s;                                                  // hdb_emit's epilogue, without bias
-    if (metric == HDB_EUCLIDEAN) s = (float)(Acc(1) / (Acc(1) + sqrt(acc)));
-    else if (metric == HDB_COSINE) s = (float)acc * inv_norm[min(ra, rb)] * inv_norm[max(ra, rb)];
-    else s = (float)acc;
-    s = hdb_canon(s);
+    // hdb_emit's epilogue, without bias; the launcher admits dot, cosine and euclidean only
+    const float s = hdb_canon(hdb_sum_score(metric, acc, inv_norm, min(ra, rb), inv_norm, max(ra, rb)));
     float* Pq = P + (int64_t)q * mp * mp;
     Pq[(int64_t)ci * mp + cj] = s;
     Pq[(int64_t)cj * mp + ci] = s;
@@ -217,16 +215,11 @@ extern "C" int hdb_launch_mmr_pairs(const void* V, int dtype, int d, int pair_me
     if (!V || d < 1 || nq < 1 || nq > 65535 || mp < HDB_MMR_TILE || mp > HDB_MMR_MAXM || mp % HDB_MMR_TILE != 0) return (int)hipErrorInvalidValue;
     if (pair_metric != HDB_DOT && pair_metric != HDB_COSINE && pair_metric != HDB_EUCLIDEAN) return (int)hipErrorInvalidValue;
     if (pair_metric == HDB_COSINE && !inv_norm) return (int)hipErrorInvalidValue;
-    if (hdb_elem_bytes(dtype) == 0) return (int)hipErrorInvalidValue;      // (packed bits have no byte-addressed elements)
     const int64_t row_bytes = hdb_row_bytes(dtype, d);
-    if (dtype == HDB_F16) mmr_pairs_launch<__half>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else if (dtype == HDB_F32) mmr_pairs_launch<float>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else if (dtype == HDB_BF16) mmr_pairs_launch<hdb_bf16>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else if (dtype == HDB_F8E4M3) mmr_pairs_launch<hdb_f8>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else if (dtype == HDB_I8) mmr_pairs_launch<hdb_i8>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else if (dtype == HDB_F64) mmr_pairs_launch<double>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
-    else return (int)hipErrorInvalidValue;
-    return (int)hipGetLastError();
+    const bool built = hdb_with_elem(dtype, [&](auto* tag) {      // (packed bits have no byte-addressed elements)
+        mmr_pairs_launch<hdb_elem_of<decltype(tag)>>(V, d, row_bytes, pair_metric, inv_norm, rows, cnt, nq, mp, P, st);
+    });
+    return built ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -42,10 +42,9 @@
 // hdb_scan_generic_kernel instantiated for hdb_bf16 run the same fma chain per lane and the same tree on the widened values (the
 // products of an 8-bit and a 24-bit significand are not exact in float32, as for float32 rows; (2) counts every rounding).  The
 // euclidean interval reads the float32 sqnorm cache, which hdb_rownorm_kernel<hdb_bf16> fills with the same chain and tree as for
-// the other types (squares of bfloat16 numbers are exact in float32: within gamma a fortiori).  The rescoring kernel's bfloat16
-// instantiation unpacks a 16-byte piece as hdb_scan.hip's hdb_unpack does -- even element the low half of its word, odd element the
-// high half -- so the lanes' partial sums are the scan's.  A default bfloat16 index answers 1-4 queries on that scan: the shadow
-// returns the default path's bits.
+// the other types (squares of bfloat16 numbers are exact in float32: within gamma a fortiori).  The rescoring kernel
+// unpacks a 16-byte piece with the scan's own hdb_unpack (hdb_unpack.h), so the lanes' partial sums are the scan's.  A default
+// bfloat16 index answers 1-4 queries on that scan: the shadow returns the default path's bits.
 //
 // ---- The matrix-core flavour (automatic shadow of an fp16 index, hdb_api.hip) --------------------------------------------
 // A default fp16 index answers 1-4-query calls on the matrix cores, so the shadow it builds for itself must return THOSE bits.
@@ -68,7 +67,9 @@
 //   query prep (hdb_qprep_kernel: 1/||q||, NaN flags) -> quantized query prep (codes, s_q, N_q, D_q)
 //   -> int8 scan over a strided row sample (MODE 0: lower bounds)  -> T_s = m-th largest sampled lower bound (hdb_sample_thr)
 //   -> int8 scan over all rows (MODE 1: row r is a candidate of q when its upper bound >= T_s)
-//   -> exact rescoring of the candidates from the original matrix -> finalize with the floor T_s.
+//   -> exact rescoring of the candidates from the original matrix (the gather scorer of hdb_rerank.hip, hdb_launch_rerank_score,
+//      reading the rows from the entries the filter pass left and rewriting them in place; a masked row gets -inf there, this
+//      unit's filter does not drop it) -> finalize with the floor T_s.
 // (matrix-core flavour: ONE query prep launch; the threshold rides in the two passes -- QuantArgs::nsub, hdb_quant.h -- when the
 //  sample is large enough; the kernel that emits a candidate copies its row into the compact matrix, so rescoring = the MODE 0
 //  launch of hdb_mfma_kernel.h.)
@@ -138,6 +139,7 @@
 // hi5 >= hi; a sampled row with hi < T_s that hi5 let through was queued for nothing (the drain drops it).  The drain evaluates and
 // emits on the same condition either way: the candidate set is unchanged, plane_survivors counts at most what it counted.
 #include "hdb_common.h"
+#include "hdb_unpack.h"      // hdb_to_f (the row quantizer)
 #include "hdb_quant.h"
 #include "hdb_finalize.h"
 #include "../../include/hyperdb_hip.h"
@@ -148,31 +150,6 @@ __device__ __forceinline__ float hq_up(double x) {
     float f = (float)x;
     if ((double)f < x) f = nextafterf(f, INFINITY);
     return f;
-}
-
-__device__ __forceinline__ float hq_f(__half v) { return __half2float(v); }
-__device__ __forceinline__ float hq_f(hdb_bf16 v) { return hdb_bf16_to_f(v); }
-__device__ __forceinline__ float hq_f(float v) { return v; }
-
-template <typename T> struct HqElem;
-template <> struct HqElem<__half> { static constexpr int EPC = 8; };
-template <> struct HqElem<hdb_bf16> { static constexpr int EPC = 8; };
-template <> struct HqElem<float> { static constexpr int EPC = 4; };
-
-__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[8], __half*) {
-    const __half2* h = reinterpret_cast<const __half2*>(&raw);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { float2 f = __half22float2(h[i]); x[2 * i] = f.x; x[2 * i + 1] = f.y; }
-}
-// bfloat16 pairs in the order of hdb_scan.hip's hdb_unpack: the even element is the low half of its word, the odd one the high half
-__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[8], hdb_bf16*) {
-    const unsigned int w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(w[i] << 16); x[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
-}
-__device__ __forceinline__ void hq_unpack(const uint4& raw, float (&x)[4], float*) {
-    x[0] = __uint_as_float(raw.x); x[1] = __uint_as_float(raw.y);
-    x[2] = __uint_as_float(raw.z); x[3] = __uint_as_float(raw.w);
 }
 
 // code of one element: rne(x / s) clamped to [-127, 127] (|x| <= 127 s up to the rounding of s), 0 for s == 0
@@ -199,7 +176,7 @@ __global__ __launch_bounds__(256) void hdb_quant_rows_kernel(const T* V, int64_t
         double ss = 0.0;
         bool has_nan = false, has_inf = false;
         for (int e = lane; e < d; e += 64) {
-            const float x = hq_f(row[e]);
+            const float x = hdb_to_f(row[e]);
             if (x != x) has_nan = true;
             else if (x - x != 0.f) has_inf = true;
             amax = fmaxf(amax, fabsf(x));
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(256) void hdb_quant_rows_kernel(const T* V, int64_t
         for (int e = lane; e < P; e += 64) {
             int c = 0;
             if (e < d && !bad) {
-                const double x = (double)hq_f(row[e]);
+                const double x = (double)hdb_to_f(row[e]);
                 c = hq_code(x, s);
                 const double eps = x - (double)s * (double)c;       // exact in float64: s has 24 bits, c 8
                 ee += eps * eps;
@@ -1051,86 +1028,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------------
-// Exact rescoring of the candidates from the ORIGINAL matrix.  A 16-lane group takes one candidate and forms its lanes' partial
-// sums exactly as hdb_scan_kernel (VEC: 16-byte pieces, lane l16 takes pieces l16 + 16 j, a dead piece adds (0 * q)) or
-// hdb_scan_generic_kernel (elements l16 + 16 i) does, then runs hdb_rows4_sum with the candidate in all four row slots and keeps
-// the lane that owns row slot (row & 3) -- the slot the row has in its dense tile -- so the same tree adds the same partials in the
-// same order.  hdb_emit's epilogue follows; the packed key is rewritten.
-// ------------------------------------------------------------------------------------------------------------------------
-struct RescoreArgs {
-    const void* V; int32_t d; int32_t row_bytes; int32_t nchunks;
-    const float* Q;           // [nq][d] float32, as the caller passed them
-    int32_t metric;
-    const float* inv_norm; const float* qinv; const float* bias; const uint8_t* mask;
-    unsigned long long* cand; const uint32_t* cnt; uint32_t cap;
-};
-
-template <typename T, int ACC, bool VEC>
-__global__ __launch_bounds__(256) void hdb_quant_rescore_kernel(RescoreArgs a) {
-    using Acc = float;
-    constexpr int EPC = HqElem<T>::EPC;
-    const int q = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, l16 = lane & 15;
-    const uint32_t total = min(a.cnt[q * HDB_CNT_STRIDE], a.cap);
-    const float* qv = a.Q + (int64_t)q * a.d;
-    const char* Vb = reinterpret_cast<const char*>(a.V);
-    const T* Vt = reinterpret_cast<const T*>(a.V);
-    for (uint32_t base = ((uint32_t)blockIdx.x * 4 + wave) * 4; base < total; base += gridDim.x * 16) {     // (wave-uniform)
-        const uint32_t i = base + g;
-        const bool valid = i < total;
-        const unsigned long long ent = valid ? a.cand[(int64_t)q * a.cap + i] : 0ull;
-        const uint32_t row = valid ? 0xFFFFFFFFu - (uint32_t)(ent & 0xFFFFFFFFull) : 0u;
-        Acc acc = Acc(0);
-        if constexpr (VEC) {
-            const char* pr = Vb + (int64_t)row * a.row_bytes;
-            const int nj = (a.nchunks + 15) >> 4;
-            for (int j = 0; j < nj; ++j) {
-                const int c = l16 + 16 * j;
-                const bool live = c < a.nchunks;
-                const int cc = live ? c : a.nchunks - 1;
-                const uint4 raw = *reinterpret_cast<const uint4*>(pr + (int64_t)cc * 16);
-                Acc x[EPC];
-                hq_unpack(raw, x, (T*)nullptr);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    const Acc qe = qv[cc * EPC + e];
-                    if (ACC == 1) {
-                        const Acc df = live ? x[e] - qe : Acc(0);
-                        acc += df * df;
-                    } else {
-                        acc += (live ? x[e] : Acc(0)) * qe;
-                    }
-                }
-            }
-        } else {
-            for (int e = l16; e < a.d; e += 16) {
-                const Acc qe = qv[e];
-                const Acc x = (Acc)hq_f(Vt[(int64_t)row * a.d + e]);
-                if (ACC == 1) { const Acc df = x - qe; acc += df * df; }
-                else acc += x * qe;
-            }
-        }
-        const Acc sum = hdb_rows4_sum(acc, acc, acc, acc, l16);
-        if (valid && (l16 & 3) == 0 && hdb_owned_row(l16) == (int)(row & 3u)) {
-            float s;                                      // hdb_emit, MODE 1
-            if (a.metric == HDB_EUCLIDEAN) {
-                s = (float)(Acc(1) / (Acc(1) + sqrt(sum)));
-            } else if (a.metric == HDB_COSINE) {
-                s = (float)sum * a.inv_norm[row] * a.qinv[q];
-            } else {
-                s = (float)sum;
-            }
-            if (a.bias) s += a.bias[row];
-            const bool masked = a.mask && !a.mask[row];
-            if (masked) s = -INFINITY;
-            s = hdb_canon(s);
-            a.cand[(int64_t)q * a.cap + i] = hdb_pack(s, row);
-        }
-    }
-}
-
 // Finalize: hdb_finalize_fast over the rescored list with the floor T_s (see "Completeness" above).  A query with an infinite
 // element, or one the quantized prep could not take, is reported as HDB_Q_UNDERFLOW: hdb_topk_host re-runs it exactly.
 __global__ __launch_bounds__(1024) void hdb_quant_finalize_kernel(const unsigned long long* cand, const uint32_t* cnt, uint32_t cap, uint32_t k,
@@ -1275,37 +1172,6 @@ extern "C" int hdb_launch_quant_scan_one(const QuantArgs* args, int mode, int ma
 #define HQ_ONE(NJ_) hipLaunchKernelGGL((hdb_quant_scan_kernel<2, 1, NJ_>), dim3(blocks), dim3(256), lds, st, a)
     if (nj == 1) HQ_ONE(1); else if (nj == 2) HQ_ONE(2); else if (nj == 3) HQ_ONE(3); else HQ_ONE(0);
 #undef HQ_ONE
-    return (int)hipGetLastError();
-}
-
-extern "C" int hdb_launch_quant_rescore(const void* V, int d, int dtype, const float* Q, int nq, int metric, const float* inv_norm,
-                                        const float* qinv, const float* bias, const uint8_t* mask, unsigned long long* cand,
-                                        const uint32_t* cnt, uint32_t cap, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    RescoreArgs a;
-    a.V = V; a.d = d; a.Q = Q; a.metric = metric; a.inv_norm = inv_norm; a.qinv = qinv; a.bias = bias; a.mask = mask;
-    a.cand = cand; a.cnt = cnt; a.cap = cap;
-    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_BF16) return (int)hipErrorInvalidValue;      // (the dtypes that have a shadow)
-    a.row_bytes = (int32_t)hdb_row_bytes(dtype, d);
-    a.nchunks = a.row_bytes / 16;
-    // the same choice as hdb_launch_scan: 16-byte pieces when rows are whole pieces of an aligned matrix
-    const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(V) & 15) == 0) && ((size_t)d * 4 <= 60 * 1024);
-    const bool euc = metric == HDB_EUCLIDEAN;
-    const dim3 grid((cap + 15) / 16 < 128 ? (cap + 15) / 16 : 128, nq);
-#define HQ_RESCORE(T_, ACC_, VEC_) hipLaunchKernelGGL((hdb_quant_rescore_kernel<T_, ACC_, VEC_>), grid, dim3(256), 0, st, a)
-    if (dtype == HDB_F16) {
-        if (vec) { if (euc) HQ_RESCORE(__half, 1, true); else HQ_RESCORE(__half, 0, true); }
-        else { if (euc) HQ_RESCORE(__half, 1, false); else HQ_RESCORE(__half, 0, false); }
-    } else if (dtype == HDB_BF16) {
-        if (vec) { if (euc) HQ_RESCORE(hdb_bf16, 1, true); else HQ_RESCORE(hdb_bf16, 0, true); }
-        else { if (euc) HQ_RESCORE(hdb_bf16, 1, false); else HQ_RESCORE(hdb_bf16, 0, false); }
-    } else if (dtype == HDB_F32) {
-        if (vec) { if (euc) HQ_RESCORE(float, 1, true); else HQ_RESCORE(float, 0, true); }
-        else { if (euc) HQ_RESCORE(float, 1, false); else HQ_RESCORE(float, 0, false); }
-    } else {
-        return (int)hipErrorInvalidValue;
-    }
-#undef HQ_RESCORE
     return (int)hipGetLastError();
 }
 

@@ -525,16 +525,23 @@ static void launch_scan_t(const ScanArgs& a, int nq_launch, int blocks, bool vec
     }
 }
 
+template <bool LIST>
+static bool launch_scan_dtype(const ScanArgs& a, int dtype, int mode, int nq_launch, int blocks, bool vec, hipStream_t st) {
+    return hdb_with_elem(dtype, [&](auto* tag) {
+        using T = hdb_elem_of<decltype(tag)>;
+        if (mode == 0) launch_scan_t<T, 0, LIST>(a, nq_launch, blocks, vec, st);
+        else launch_scan_t<T, 1, LIST>(a, nq_launch, blocks, vec, st);
+    });
+}
+
 // Entry used by hdb_api.hip.  mode: 0 = write scores, 1 = threshold filter.
 extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream) {
     if (dtype == HDB_B1) return hdb_launch_bscan(args, mode, nq_launch, max_blocks, stream);      // packed-bit rows: hdb_bscan.hip
     ScanArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
-    const int elem = hdb_elem_bytes(dtype);
     a.row_bytes = (int32_t)hdb_row_bytes(dtype, a.d);
     a.nchunks = a.row_bytes / 16;
-    const bool vec = (a.row_bytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(a.V) & 15) == 0) &&
-                     ((size_t)a.d * (elem == 8 ? 8 : 4) <= 60 * 1024);
+    const bool vec = hdb_scan_rows_in_pieces(a.row_bytes, a.V, a.d, hdb_elem_bytes(dtype));
     // grid: every wave keeps a whole tile in flight.  With 12 KiB tiles (768-byte rows) 2 workgroups (8 waves) per CU
     // is the measured optimum (6.8 TB/s); with the 24 KiB tiles of the unrolled 1536-byte-row variant one workgroup
     // per CU is (N=1M fp32 d=384: 237 vs 246 us; N=10M: 7.02 vs 6.78 TB/s) -- the same ~100 KiB in flight per CU
@@ -544,19 +551,9 @@ extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq
     const int auto_blocks = hdb_scan_auto_blocks(dtype, a.row_bytes, vec, wide_rows);
     const int blocks = hdb_grid_for(a.ntiles, 4, max_blocks > 0 ? max_blocks : auto_blocks);
     // (a.rows: the row-list flavour, a compile-time sibling of every kernel -- the dense ones carry no test for it)
-#define HDB_SCAN_DISPATCH(LIST_)                                                                                                   \
-    do {                                                                                                                           \
-        if (dtype == HDB_F16) { if (mode == 0) launch_scan_t<__half, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<__half, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-        else if (dtype == HDB_F32) { if (mode == 0) launch_scan_t<float, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<float, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-        else if (dtype == HDB_BF16) { if (mode == 0) launch_scan_t<hdb_bf16, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_bf16, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-        else if (dtype == HDB_F8E4M3) { if (mode == 0) launch_scan_t<hdb_f8, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_f8, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-        else if (dtype == HDB_I8) { if (mode == 0) launch_scan_t<hdb_i8, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<hdb_i8, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-        else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;                                                                \
-        else { if (mode == 0) launch_scan_t<double, 0, LIST_>(a, nq_launch, blocks, vec, st); else launch_scan_t<double, 1, LIST_>(a, nq_launch, blocks, vec, st); } \
-    } while (0)
-    if (a.rows) HDB_SCAN_DISPATCH(true); else HDB_SCAN_DISPATCH(false);
-#undef HDB_SCAN_DISPATCH
-    return (int)hipGetLastError();
+    const bool built = a.rows ? launch_scan_dtype<true>(a, dtype, mode, nq_launch, blocks, vec, st)
+                              : launch_scan_dtype<false>(a, dtype, mode, nq_launch, blocks, vec, st);
+    return built ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // Exact path of a row-list call: hdb_launch_collect left entries that carry list POSITIONS (the score buffer's index); rewrite
@@ -625,14 +622,11 @@ extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, fl
         return (int)hipGetLastError();
     }
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
-    if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rownorm_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, inv_norm, sqnorm, nan_flag);
-    else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rownorm_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, inv_norm, sqnorm, nan_flag);
-    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, inv_norm, sqnorm, nan_flag);
-    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, inv_norm, sqnorm, nan_flag);
-    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_rownorm_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, inv_norm, sqnorm, nan_flag);
-    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
-    else hipLaunchKernelGGL(hdb_rownorm_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, inv_norm, sqnorm, nan_flag);
-    return (int)hipGetLastError();
+    const bool built = hdb_with_elem(dtype, [&](auto* tag) {
+        using T = hdb_elem_of<decltype(tag)>;
+        hipLaunchKernelGGL(hdb_rownorm_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)V, n, d, inv_norm, sqnorm, nan_flag);
+    });
+    return built ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 extern "C" int hdb_launch_qprep2(const void* Q, int nq, int d, bool f64, float* qinv, float* qsq, int* qnan, void* q16, float* qscl,
@@ -654,26 +648,16 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
         hipLaunchKernelGGL(hdb_b1_signpack_kernel, dim3(hdb_grid_for(n * (d / 32), 256, 4096)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, row0, bits);
         return (int)hipGetLastError();
     }
-    if (d % 32 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0) {
-        const int blocks = hdb_grid_for((n + 7) / 8, 4, 4096);      // a wave per eight rows
-        if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
-        else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_wide_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
-        else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
-        else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
-        else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_signpack_wide_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, row0, bits);
-        else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
-        else hipLaunchKernelGGL(hdb_signpack_wide_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
-        return (int)hipGetLastError();
-    }
-    const int blocks = hdb_grid_for(n, 4, 4096);
-    if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_signpack_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, row0, bits);
-    else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_signpack_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, row0, bits);
-    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, row0, bits);
-    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, row0, bits);
-    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_signpack_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, row0, bits);
-    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
-    else hipLaunchKernelGGL(hdb_signpack_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, row0, bits);
-    return (int)hipGetLastError();
+    const bool wide = d % 32 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
+    const int blocks = wide ? hdb_grid_for((n + 7) / 8, 4, 4096) : hdb_grid_for(n, 4, 4096);      // a wave per eight rows | per row
+    const bool built = wide ? hdb_with_elem(dtype, [&](auto* tag) {
+        using T = hdb_elem_of<decltype(tag)>;
+        hipLaunchKernelGGL(hdb_signpack_wide_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)V, n, d, row0, bits);
+    }) : hdb_with_elem(dtype, [&](auto* tag) {
+        using T = hdb_elem_of<decltype(tag)>;
+        hipLaunchKernelGGL(hdb_signpack_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)V, n, d, row0, bits);
+    });
+    return built ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 extern "C" int hdb_launch_qsign(const void* Q, int nq, int d, bool f64, int W, uint32_t* qbits, void* stream) {
@@ -805,14 +789,11 @@ extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, f
         return (int)hipGetLastError();
     }
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);
-    if (dtype == HDB_F16) hipLaunchKernelGGL(hdb_rowstats_kernel<__half>, dim3(blocks), dim3(256), 0, st, (const __half*)V, n, d, pscale);
-    else if (dtype == HDB_F32) hipLaunchKernelGGL(hdb_rowstats_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)V, n, d, pscale);
-    else if (dtype == HDB_BF16) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_bf16>, dim3(blocks), dim3(256), 0, st, (const hdb_bf16*)V, n, d, pscale);
-    else if (dtype == HDB_F8E4M3) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_f8>, dim3(blocks), dim3(256), 0, st, (const hdb_f8*)V, n, d, pscale);
-    else if (dtype == HDB_I8) hipLaunchKernelGGL(hdb_rowstats_kernel<hdb_i8>, dim3(blocks), dim3(256), 0, st, (const hdb_i8*)V, n, d, pscale);
-    else if (dtype != HDB_F64) return (int)hipErrorInvalidValue;
-    else hipLaunchKernelGGL(hdb_rowstats_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)V, n, d, pscale);
-    return (int)hipGetLastError();
+    const bool built = hdb_with_elem(dtype, [&](auto* tag) {
+        using T = hdb_elem_of<decltype(tag)>;
+        hipLaunchKernelGGL(hdb_rowstats_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)V, n, d, pscale);
+    });
+    return built ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 extern "C" int hdb_launch_qcentre(const void* Q, int nq, int d, bool f64, void* Qc, float* qscale, void* stream) {
     hipStream_t st = (hipStream_t)stream;

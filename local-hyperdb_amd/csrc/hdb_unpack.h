@@ -1,8 +1,11 @@
 // hdb_unpack.h -- how a stored row becomes accumulate-type values: the element traits of every stored dtype, the widening of one
-// 16-byte piece (hdb_unpack) and of one element (hdb_to_f).  One text for the VALU scan (hdb_scan.hip) and the units that must
-// reproduce its partial sums bit for bit (hdb_rerank.hip).
+// 16-byte piece (hdb_unpack) and of one element (hdb_to_f), and the host's way from a dtype code to the element type
+// (hdb_with_elem).  One text for the VALU scan (hdb_scan.hip), the gather scorer that must reproduce its partial sums bit for bit
+// (hdb_rerank.hip: per-query candidate lists and the candidates of the int8 shadow), the pair kernel (hdb_mmr.hip) and the
+// shadow's row quantizer (hdb_quant.hip).
 #pragma once
 #include "hdb_common.h"
+#include <type_traits>
 
 template <typename T> struct Elem;
 template <> struct Elem<__half> { using Acc = float;  static constexpr int EPC = 8; };
@@ -11,6 +14,23 @@ template <> struct Elem<hdb_f8> { using Acc = float; static constexpr int EPC = 
 template <> struct Elem<hdb_i8> { using Acc = float; static constexpr int EPC = 16; };
 template <> struct Elem<float>  { using Acc = float;  static constexpr int EPC = 4; };
 template <> struct Elem<double> { using Acc = double; static constexpr int EPC = 2; };
+
+// The ladder from a dtype code to the element type, once: calls f with a null pointer of the element type (the tag hdb_unpack
+// takes; in a generic lambda, T = hdb_elem_of<decltype(tag)>).  false: no byte-addressed elements -- packed bits, or no such dtype.
+// The order is the order of the kernels in a unit's code object (instantiation order decides it): a new dtype goes at the end.
+// Units that build fewer types on purpose keep a ladder of their own (hdb_launch_quant_rows, hdb_l1_tile.hip, hdb_quant_mfma.hip).
+template <typename P> using hdb_elem_of = std::remove_pointer_t<P>;
+template <typename F>
+static inline bool hdb_with_elem(int dtype, F&& f) {
+    if (dtype == HDB_F16) f((__half*)nullptr);
+    else if (dtype == HDB_F32) f((float*)nullptr);
+    else if (dtype == HDB_BF16) f((hdb_bf16*)nullptr);
+    else if (dtype == HDB_F8E4M3) f((hdb_f8*)nullptr);
+    else if (dtype == HDB_I8) f((hdb_i8*)nullptr);
+    else if (dtype == HDB_F64) f((double*)nullptr);
+    else return false;
+    return true;
+}
 
 __device__ __forceinline__ void hdb_unpack(const uint4& raw, float (&x)[8], __half*) {
     const __half2* h = reinterpret_cast<const __half2*>(&raw);

@@ -128,6 +128,9 @@ def _check_case(ix, Q, k, metric, bias=None, mask=None, what=""):
 SHAPES = [
     ("f16", 384, 20000), ("f16", 384, 1000000), ("f16", 768, 20000), ("f16", 300, 20000), ("f16", 300, 1000000),
     ("f32", 384, 20000), ("f32", 384, 1000000), ("f32", 768, 20000), ("f32", 100, 20000), ("f32", 100, 1000000),
+    # rows of 256, 384 and 512 bytes: the unrolled narrow-row forms of the gather scorer, one (256 bytes) or four candidates per step (the plan takes the shadow
+    # at each of these widths: plan_topk has no rule on d for an explicit shadow)
+    ("f16", 128, 20000), ("f16", 192, 20000), ("f16", 256, 20000),
 ]
 
 
