@@ -36,8 +36,14 @@ typedef struct hdb_index hdb_index;
  * HDB_B1 = 10 is a matrix of packed bits, one bit per element: `d` counts bits and is a multiple of 32, a row is d / 32 uint32 words
  * (row-major, 4-byte aligned) and element e of a row is bit e & 31 of word e >> 5 -- np.packbits(.., bitorder="little") read as
  * little-endian words, the bit order of the sign cache.  The matrix is the 0/1 matrix the bits stand for: 1.0 where the bit is set.
- * Codes 4, 6, 8 and 9 are unassigned and refused by hdb_index_create, like every other value not listed here. */
-enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5, HDB_I8 = 7, HDB_B1 = 10 };
+ * HDB_MXF4 = 13 is a matrix of OCP microscaling FP4 rows (MXFP4): `d` counts elements and is a multiple of 32; a stored row is
+ * [d / 2 code bytes][d / 32 scale bytes][zero padding] at a pitch of round_up(d / 2 + d / 32, 16) bytes (d = 384: 208) behind a
+ * 16-byte aligned base.  Element e has code (byte[e >> 1] >> 4 (e & 1)) & 15, an e2m1 number (bit 3 the sign, the magnitudes
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6}: torch.float4_e2m1fn_x2's order, the even element in the low nibble), and the value code x
+ * 2^(s - 127), s the e8m0 scale byte of its block of 32 (torch.float8_e8m0fnu); s = 255 makes the block NaN.  Every value widens to
+ * float32 exactly; the matrix is that widening.
+ * Codes 4, 6, 8, 9, 11 and 12 are unassigned and refused by hdb_index_create, like every other value not listed here. */
+enum hdb_dtype { HDB_F16 = 0, HDB_F32 = 1, HDB_F64 = 2, HDB_BF16 = 3, HDB_F8E4M3 = 5, HDB_I8 = 7, HDB_B1 = 10, HDB_MXF4 = 13 };
 
 /* metric strings of hyperDB_ranking_algorithm_sort's dispatch table (ranking_algorithm.py:155-163). */
 enum hdb_metric {
@@ -383,7 +389,28 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit); the
  *     matrix cores unless b1_mfma_min_q asks for them.
  * Stats: mfma = 0 (1 on the matrix-core path of b1_mfma_min_q), quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics'
- * single launch); b1_mfma_min_q = the threshold in force for this index, 0 = never. */
+ * single launch); b1_mfma_min_q = the threshold in force for this index, 0 = never.
+ * MXFP4 matrices (HDB_MXF4).  Layout: the dtype paragraph above; d % 32 == 0 (HDB_ERR_ARG otherwise), d <= 7680, a 16-byte aligned
+ * base.  Queries are float32 x d.  Contract: every metric is the reference's arithmetic on the exactly widened float32 matrix --
+ * scores within 1e-5 * max(1, |s|), hamming exact, jaccard 1e-6; no approximate filter, nothing is rescored.  A scale byte of 255 is
+ * a NaN block: hdb_index_has_nan is 1, as for a NaN of any dtype.  Scale bytes below 3 give values below 2^-126, float32
+ * sub-normals: they follow the float32 multiplication of the kernel that widens them (the scale float is the byte << 23, so a scale
+ * byte of 0 reads as 0) -- not covered by the contract.  Row caches: ||v||^2 per block from exact integers, the pearson scale in
+ * float64, the sign cache x > 0 = a non-zero magnitude, a clear sign bit and a scale that is no NaN.
+ *   - dot / cosine / pearson / euclidean / manhattan: hdb_f4scan.hip on hdb_scan.hip's 16-row tile, one, two or four queries per
+ *     pass, through the small, sampled, exact and full-sort pipelines, with bias, mask and the strided sample.  Rows of up to 512
+ *     elements (up to 1024 with one or two queries per pass) keep the query in registers, wider ones in LDS with one query per pass
+ *     (a launch of more queries runs several passes); ONE summation order
+ *     per row: the sample pass, the filter pass, hdb_topk_exact and hdb_scores return the same float32 bits for a row, whatever
+ *     the grid and the number of queries.  5+ queries run as four-query passes.
+ *   - hamming / jaccard: the bit kernels that every dtype uses, on the sign cache (fused = 3 for 1-4 queries).
+ *   - never: the matrix cores, the single launches of the float paths, the manhattan tile kernel, the int8 shadow and its plane
+ *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit).
+ *   Composite calls treat it as they treat HDB_B1: a first stage of hdb_two_stage_host, grouped, multi-vector and range calls are
+ *   served; rerank onto it and the pair similarity of hdb_mmr return HDB_ERR_UNSUPPORTED.
+ * Not built: the bf16 matrix cores for batches (v_cvt_scalef32_pk_bf16_fp4 into the float8 fragment path), the scaled fp4 MFMA (it
+ * would round the query), MXFP6 / MXFP8 / NVFP4, shadows and planes, row lists, several GPUs, rerank onto an MXFP4 index.
+ * Stats: mfma = 0, quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics' single launch). */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 

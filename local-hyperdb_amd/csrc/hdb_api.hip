@@ -158,7 +158,7 @@ static int ws_lay(hdb_index* ix, WS& w, Ext... ext) {
     return HDB_OK;
 }
 
-extern "C" int hdb_version(void) { return 113; }
+extern "C" int hdb_version(void) { return 114; }
 extern "C" const char* hdb_last_error(void) { return g_err.c_str(); }
 
 // The three arrays of a packed record (hdb_packed_bytes is its size): [nq][k] ids, [nq][k] scores, [nq] status words
@@ -343,6 +343,7 @@ extern "C" int hdb_index_quantize(hdb_index* ix, int mode, void* stream) {
     if (ix->dtype == HDB_F8E4M3) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: float8 (e4m3) matrices have no int8 shadow: one byte per element already");
     if (ix->dtype == HDB_I8) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: int8 matrices have no int8 shadow: one byte per element already");
     if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: packed-bit matrices have no int8 shadow: one bit per element already");
+    if (ix->dtype == HDB_MXF4) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: MXFP4 matrices have no int8 shadow: half a byte per element already");
     if (ix->dtype != HDB_F16 && ix->dtype != HDB_F32 && ix->dtype != HDB_BF16) return fail(HDB_ERR_UNSUPPORTED, "hdb_index_quantize: only float16 / float32 matrices have an int8 shadow");
     HIP_TRY(qstat_alloc(ix, st));
     ix->qP = (int32_t)align_up((size_t)ix->d, 16);
@@ -405,11 +406,13 @@ extern "C" int hdb_index_create(hdb_index** out, const void* dev_V, int64_t n, i
     if (!out) return fail(HDB_ERR_ARG, "hdb_index_create: out is null");
     if (n < 0 || d <= 0) return fail(HDB_ERR_ARG, "hdb_index_create: need n >= 0 and d > 0");
     if (n > 0 && !dev_V) return fail(HDB_ERR_ARG, "hdb_index_create: matrix pointer is null");
-    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3 && dtype != HDB_I8 && dtype != HDB_B1) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3/i8/b1");
+    if (dtype != HDB_F16 && dtype != HDB_F32 && dtype != HDB_F64 && dtype != HDB_BF16 && dtype != HDB_F8E4M3 && dtype != HDB_I8 && dtype != HDB_B1 && dtype != HDB_MXF4) return fail(HDB_ERR_ARG, "hdb_index_create: dtype must be f16/f32/f64/bf16/f8e4m3/i8/b1/mxf4");
+    if (dtype == HDB_MXF4 && d % 32 != 0) return fail(HDB_ERR_ARG, "hdb_index_create: an MXFP4 matrix needs d (elements per row) to be a multiple of 32");
     if (dtype == HDB_B1 && d % 32 != 0) return fail(HDB_ERR_ARG, "hdb_index_create: a packed-bit matrix needs d (bits per row) to be a multiple of 32");
     if (n >= ((int64_t)1 << 32) - 1) return fail(HDB_ERR_ARG, "hdb_index_create: at most 2^32-2 rows per shard");
     if ((int64_t)d * 8 > 60 * 1024) return fail(HDB_ERR_ARG, "hdb_index_create: d too large for the query LDS tile");
     if (dtype == HDB_B1 && n > 0 && (reinterpret_cast<uintptr_t>(dev_V) & 3) != 0) return fail(HDB_ERR_ARG, "hdb_index_create: a packed-bit matrix must be 4-byte aligned");
+    if (dtype == HDB_MXF4 && n > 0 && (reinterpret_cast<uintptr_t>(dev_V) & 15) != 0) return fail(HDB_ERR_ARG, "hdb_index_create: an MXFP4 matrix must be 16-byte aligned");
     HIP_TRY(hipSetDevice(device));
     hdb_index* ix = new hdb_index();
     ix->d = d; ix->dtype = dtype; ix->device = device; ix->row_base = row_base;
@@ -1498,6 +1501,7 @@ static int rerank_impl(const char* who, hdb_index* ix, const void* dev_Q, int32_
     if (nq == 0) return HDB_OK;
     if (!dev_Q || !dev_cand || !dev_idx || !dev_score) return fail(HDB_ERR_ARG, std::string(who) + ": null argument");
     if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": a packed-bit index is a first stage: rerank onto packed bits is not built");
+    if (ix->dtype == HDB_MXF4) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": an MXFP4 index is a first stage: rerank onto MXFP4 rows is not built");
     int rc = ranking_metric(who, "rerank is", metric); if (rc) return rc;
     HIP_TRY(hipSetDevice(ix->device));
     const bool f64 = ix->dtype == HDB_F64, pearson = metric == HDB_PEARSON;
@@ -1797,6 +1801,7 @@ static int mmr_sizes(const char* who, int32_t nq, int32_t m, int32_t k, double l
 static int mmr_handle(const char* who, const hdb_index* ix) {
     if (!ix) return fail(HDB_ERR_ARG, std::string(who) + ": null index");
     if (ix->dtype == HDB_B1) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": a packed-bit index is a first stage: pair similarity of packed bits is not built");
+    if (ix->dtype == HDB_MXF4) return fail(HDB_ERR_UNSUPPORTED, std::string(who) + ": an MXFP4 index is a first stage: pair similarity of MXFP4 rows is not built");
     return HDB_OK;
 }
 // Per chunk of queries: list preparation, the pair matrix, the selection.  status_in / status_out: [nq] or NULL, may be one array.

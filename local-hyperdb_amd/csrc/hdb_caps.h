@@ -55,6 +55,33 @@ static inline int hdb_bscan_auto_blocks(int d, int qt, int cus) {
     return per_cu * (cus > 0 ? cus : 1);
 }
 
+// ---- hdb_f4scan.hip: float32 queries against MXFP4 rows (HDB_MXF4) ----
+// The flavour of a width (NJ of hdb_f4scan_kernel) and the queries of a pass.  1 = one chunk step per row with the query fragments in
+// registers (d <= 512: 32 registers per query, one, two or four queries per pass); 2 = two steps (d <= 1024: 64 registers per query, so
+// one or two queries -- four would keep 256 registers of fragments beside the sums and the tile); 0 = the runtime loop with the query
+// in LDS (4 d bytes inside the 60 KiB every scan kernel allows its queries), ONE query per pass.  A launch of more queries than a pass
+// takes runs several passes (grid.y).  Measured (whole cosine top-100 calls, p50 in us; DESIGN.md, "MXFP4 matrices"): LDS passes of
+// two and four queries were built first and lost to smaller passes -- 2M x 1024, four queries: 1 458 against 646 as two two-query
+// register passes (profiles/f4_time.txt); 2M x 2048, two / four queries: 1 159 / 2 892 against 828 / 1 581 as one-query passes -- so
+// the register flavour is preferred wherever it exists and the LDS flavour is built for one query only.
+#define HDB_F4SCAN_LDS_BYTES (60 * 1024)
+static inline int hdb_f4scan_lds_bytes(int d) { return d * 4; }
+// queries per pass for a launch that could fill `want` (1 | 2 | 4); -1 = no such row
+static inline int hdb_f4scan_qt(int d, int want) {
+    if (d <= 0 || d % 32 != 0) return -1;
+    if (d <= 512) return want;
+    if (d <= 1024) return want < 2 ? want : 2;
+    return hdb_f4scan_lds_bytes(d) <= HDB_F4SCAN_LDS_BYTES ? 1 : -1;
+}
+static inline int hdb_f4scan_nj(int d) { return d <= 512 ? 1 : d <= 1024 ? 2 : 0; }
+// workgroups per CU of a launch when the caller sets no limit: the fewest waves per SIMD any kernel of the flavour and pass size is
+// compiled for ("MXFP4 matrices", the register table): one step 4 / 3 / 2 for 1 / 2 / 4 queries per pass, two steps 3 / 2
+// for 1 / 2, the LDS loop 2 (its dot kernel alone would take 4).  Derived from the register counts; the grid was not varied on the GPU.
+static inline int hdb_f4scan_auto_blocks(int qt, int nj, int cus) {
+    const int per_cu = nj == 1 ? (qt == 4 ? 2 : qt == 2 ? 3 : 4) : nj == 2 ? (qt == 2 ? 2 : 3) : 2;
+    return per_cu * (cus > 0 ? cus : 1);
+}
+
 // ---- hdb_mfma_ksplit.hip: K slices of rows too wide for one wave's query fragments ----
 // The slice list of a width: slice s covers `width[s]` elements of every row from byte `off[s]` of the stored row on; the widths
 // add up to d and every one of them is a slice geometry that is instantiated for the dtype (float32 512 / 768, fp16 1024 / 1536,

@@ -17,7 +17,25 @@ __host__ __device__ __forceinline__ int hdb_elem_bytes(int dtype) {
 __host__ __device__ __forceinline__ int64_t hdb_row_bytes(int dtype, int d) {
     if (d <= 0) return 0;
     if (dtype == 10) return d % 32 == 0 ? (int64_t)(d / 8) : 0;
+    if (dtype == 13) return d % 32 == 0 ? (int64_t)((d / 2 + d / 32 + 15) / 16 * 16) : 0;      // MXFP4: codes, scales, padding (below)
     return (int64_t)d * hdb_elem_bytes(dtype);
+}
+// An MXFP4 row (dtype 13, OCP microscaling): [d / 2 code bytes][d / 32 scale bytes][zero padding] at the pitch above; d counts
+// elements and is a multiple of 32.  Element e has code (byte[e >> 1] >> 4 (e & 1)) & 15 -- an e2m1 number: bit 3 the sign, the
+// magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- and the value code x 2^(s - 127) with s = scale byte e >> 5 (e8m0); s = 255 makes the
+// block NaN.  The scale float is s << 23, as the scan kernels form it: exact for s >= 1, and 0 for s = 0 where 2^-127 is meant
+// (values below 2^-126 are float32 sub-normals and follow the float32 multiplication of the unit that widens them).  Plain
+// arithmetic, so host code (tests) computes the same values; the scan converts with v_cvt_scalef32_pk_f32_fp4 (hdb_f4scan.hip).
+__host__ __device__ __forceinline__ float hdb_mxf4_scale_f(unsigned int s) { return __builtin_bit_cast(float, s << 23); }
+// twice the magnitude of a code: the integers {0, 1, 2, 3, 4, 6, 8, 12}
+__host__ __device__ __forceinline__ int hdb_mxf4_mag2(unsigned int code) {
+    const int m = (int)(code & 7u);
+    return m < 2 ? m : (2 | (m & 1)) << ((m >> 1) - 1);
+}
+__host__ __device__ __forceinline__ float hdb_mxf4_to_f(unsigned int code, unsigned int s) {
+    if (s == 255u) return __builtin_bit_cast(float, 0x7FC00000u);
+    const float r = (float)hdb_mxf4_mag2(code) * 0.5f * hdb_mxf4_scale_f(s);
+    return (code & 8u) ? -r : r;
 }
 // A bfloat16 as it lies in memory: the upper 16 bits of the float32 of the same value, so widening is a shift and exact.
 struct hdb_bf16 { unsigned short bits; };

@@ -537,6 +537,7 @@ static bool launch_scan_dtype(const ScanArgs& a, int dtype, int mode, int nq_lau
 // Entry used by hdb_api.hip.  mode: 0 = write scores, 1 = threshold filter.
 extern "C" int hdb_launch_scan(const ScanArgs* args, int dtype, int mode, int nq_launch, int max_blocks, void* stream) {
     if (dtype == HDB_B1) return hdb_launch_bscan(args, mode, nq_launch, max_blocks, stream);      // packed-bit rows: hdb_bscan.hip
+    if (dtype == HDB_MXF4) return hdb_launch_f4scan(args, mode, nq_launch, max_blocks, stream);   // MXFP4 rows: hdb_f4scan.hip
     ScanArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     a.row_bytes = (int32_t)hdb_row_bytes(dtype, a.d);
@@ -613,9 +614,78 @@ __global__ __launch_bounds__(256) void hdb_b1_signpack_kernel(const uint32_t* V,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// MXFP4 rows (HDB_MXF4: hdb_common.h has the layout).  One thread per row, so a row's caches do not depend on where it stands.
+// ||v||^2: twice a magnitude is an integer of at most 12, so a block's sum of (2 m)^2 is an exact integer (<= 4608) and its
+// share is that integer x 2^(s - 128) x 2^(s - 128), exact until it leaves float32 range; the blocks are added in order with
+// float32 adds.  A scale byte of 255 is a NaN block: the NaN flag, as a NaN element of any dtype.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hdb_f4_rownorm_kernel(const char* V, int64_t n, int d, int pitch, float* inv_norm, float* sqnorm, int* nan_flag) {
+    const int nblk = d >> 5;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const char* p = V + r * (int64_t)pitch;
+        float ss = 0.f;
+        for (int c = 0; c < nblk; ++c) {
+            const uint4 raw = *reinterpret_cast<const uint4*>(p + 16 * c);
+            const unsigned int s = *reinterpret_cast<const uint8_t*>(p + (d >> 1) + c);
+            const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+            int isum = 0;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) { const int m2 = hdb_mxf4_mag2(w[i >> 3] >> (4 * (i & 7))); isum += m2 * m2; }
+            const float half = 0.5f * hdb_mxf4_scale_f(s);
+            ss += s == 255u ? NAN : ((float)isum * half) * half;
+        }
+        if (ss != ss) atomicOr(nan_flag, 1);
+        else if (ss - ss != 0.f) atomicOr(nan_flag, HDB_FLAG_INF | HDB_FLAG_L1_WIDE);
+        else if (ss > HDB_L1_PK_MAX * HDB_L1_PK_MAX) atomicOr(nan_flag, HDB_FLAG_L1_WIDE);
+        sqnorm[r] = ss;
+        inv_norm[r] = (ss == 0.f) ? 1.0f : 1.f / sqrtf(ss);
+    }
+}
+// pearson row scale 1 / (sd d), two passes in float64 (mean, then centred squares) as hdb_rowstats_kernel; a constant row: NaN
+__global__ __launch_bounds__(256) void hdb_f4_rowstats_kernel(const char* V, int64_t n, int d, int pitch, float* pscale) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(V + r * (int64_t)pitch);
+        auto elem = [&](int e) { return (double)hdb_mxf4_to_f((unsigned int)p[e >> 1] >> (4 * (e & 1)), p[(d >> 1) + (e >> 5)]); };
+        double sum = 0.0;
+        for (int e = 0; e < d; ++e) sum += elem(e);
+        const double mean = sum / (double)d;
+        double ss = 0.0;
+        for (int e = 0; e < d; ++e) { const double df = elem(e) - mean; ss = fma(df, df, ss); }
+        const double sd = sqrt(ss / (double)d);
+        pscale[r] = (sd == 0.0) ? NAN : (float)(1.0 / (sd * (double)d));
+    }
+}
+// the sign cache: word w of a row is MX block w; x > 0 = a non-zero magnitude, a clear sign bit and a scale that is no NaN
+__global__ __launch_bounds__(256) void hdb_f4_signpack_kernel(const char* V, int64_t n, int d, int pitch, int64_t row0, uint32_t* bits) {
+    const int W = d >> 5;
+    const int64_t total = n * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / W;
+        const int w = (int)(i - r * W);
+        const char* p = V + r * (int64_t)pitch;
+        const uint4 raw = *reinterpret_cast<const uint4*>(p + 16 * w);
+        const unsigned int s = *reinterpret_cast<const uint8_t*>(p + (d >> 1) + w);
+        const uint32_t cw[4] = {raw.x, raw.y, raw.z, raw.w};
+        uint32_t m = 0u;
+#pragma unroll
+        for (int e = 0; e < 32; ++e) {
+            const uint32_t code = (cw[e >> 3] >> (4 * (e & 7))) & 15u;
+            m |= (uint32_t)((code & 8u) == 0u && (code & 7u) != 0u) << e;
+        }
+        bits[hdb_bits_word(row0 + r, w, W)] = s == 255u ? 0u : m;
+    }
+}
+
 extern "C" int hdb_launch_rownorm(const void* V, int64_t n, int d, int dtype, float* inv_norm, float* sqnorm,
                                   int* nan_flag, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (dtype == HDB_MXF4) {
+        const int pitch = (int)hdb_row_bytes(dtype, d);
+        if (pitch <= 0 || (reinterpret_cast<uintptr_t>(V) & 15) != 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_f4_rownorm_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const char*)V, n, d, pitch, inv_norm, sqnorm, nan_flag);
+        return (int)hipGetLastError();
+    }
     if (dtype == HDB_B1) {
         if (d % 32 != 0) return (int)hipErrorInvalidValue;
         hipLaunchKernelGGL(hdb_b1_rownorm_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, inv_norm, sqnorm);
@@ -646,6 +716,12 @@ extern "C" int hdb_launch_signpack(const void* V, int64_t n, int d, int dtype, i
     if (dtype == HDB_B1) {
         if (d % 32 != 0) return (int)hipErrorInvalidValue;
         hipLaunchKernelGGL(hdb_b1_signpack_kernel, dim3(hdb_grid_for(n * (d / 32), 256, 4096)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, row0, bits);
+        return (int)hipGetLastError();
+    }
+    if (dtype == HDB_MXF4) {
+        const int pitch = (int)hdb_row_bytes(dtype, d);
+        if (pitch <= 0 || (reinterpret_cast<uintptr_t>(V) & 15) != 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_f4_signpack_kernel, dim3(hdb_grid_for(n * (d / 32), 256, 4096)), dim3(256), 0, st, (const char*)V, n, d, pitch, row0, bits);
         return (int)hipGetLastError();
     }
     const bool wide = d % 32 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
@@ -786,6 +862,12 @@ extern "C" int hdb_launch_rowstats(const void* V, int64_t n, int d, int dtype, f
     if (dtype == HDB_B1) {
         if (d % 32 != 0) return (int)hipErrorInvalidValue;
         hipLaunchKernelGGL(hdb_b1_rowstats_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const uint32_t*)V, n, d / 32, d, pscale);
+        return (int)hipGetLastError();
+    }
+    if (dtype == HDB_MXF4) {
+        const int pitch = (int)hdb_row_bytes(dtype, d);
+        if (pitch <= 0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(hdb_f4_rowstats_kernel, dim3(hdb_grid_for(n, 256, 2048)), dim3(256), 0, st, (const char*)V, n, d, pitch, pscale);
         return (int)hipGetLastError();
     }
     const int blocks = hdb_grid_for((n + 15) / 16, 4, 2048);

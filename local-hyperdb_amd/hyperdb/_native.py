@@ -20,6 +20,7 @@ HDB_F16, HDB_F32, HDB_F64, HDB_BF16 = 0, 1, 2, 3
 HDB_F8E4M3 = 5                          # OCP float8 e4m3 (torch.float8_e4m3fn); 4 is unassigned and refused by the library
 HDB_I8 = 7                              # signed 8-bit integers (np.int8 / torch.int8), on request: storage="int8"; 6 is unassigned
 HDB_B1 = 10                             # packed bits, one bit per element, on request: storage="bits"; 8 and 9 are unassigned
+HDB_MXF4 = 13                           # MXFP4 rows (e2m1 codes, one e8m0 scale per 32), on request: storage="mxfp4"; 11 and 12 are unassigned
 METRIC_IDS = {
     "dot_product": 0,
     "cosine_similarity": 1,
@@ -158,17 +159,23 @@ _STORED2HDB = dict(_TORCH2HDB)
 _STORED2HDB[torch.int8] = HDB_I8
 # ... and torch.uint8: the packed rows of a bits index (storage="bits"); without the keyword a uint8 input is widened to float64
 _STORED2HDB[torch.uint8] = HDB_B1
-STORAGE_MODES = (None, "int8", "bits")
+STORAGE_MODES = (None, "int8", "bits", "mxfp4")
 BITORDERS = ("big", "little")
 BITS_SINGLE_INDEX = ("storage='bits' is built for a single index on one device only (GpuIndex, register_vectors without "
                      "devices=): no GpuGroup, no sharded index, no HyperDB facade")
+MXFP4_SINGLE_INDEX = BITS_SINGLE_INDEX.replace("'bits'", "'mxfp4'")
 
 
 def storage_mode(storage):
-    """A ``storage=`` argument: None (the input's own dtype policy), "int8" or "bits"; anything else raises ValueError."""
+    """A ``storage=`` argument: None (the input's own dtype policy), "int8", "bits" or "mxfp4"; anything else raises ValueError."""
     if storage is not None and not isinstance(storage, str) or storage not in STORAGE_MODES:
-        raise ValueError(f"storage must be None, 'int8' or 'bits', got {storage!r}")
+        raise ValueError(f"storage must be None, 'int8', 'bits' or 'mxfp4', got {storage!r}")
     return storage
+
+
+def single_index_only(storage):
+    """The refusal of what is built for one index on one device only (storage="bits" / "mxfp4"), or None."""
+    return {"bits": BITS_SINGLE_INDEX, "mxfp4": MXFP4_SINGLE_INDEX}.get(storage_mode(storage))
 
 
 def bit_order(bitorder):
@@ -246,6 +253,105 @@ def to_bits(data, device, bitorder="big"):
 def unpack_bits_host(packed, bitorder):
     """Packed uint8 ``[..., d/8]`` (numpy) -> the float32 0/1 array ``[..., d]``."""
     return np.unpackbits(np.ascontiguousarray(packed), axis=-1, bitorder=bitorder).astype(np.float32)
+
+
+# ---- MXFP4 (storage="mxfp4", HDB_MXF4): OCP microscaling, e2m1 elements with one e8m0 power-of-two scale per 32 elements ----------
+_F4X2 = getattr(torch, "float4_e2m1fn_x2", None)
+_E8M0 = getattr(torch, "float8_e8m0fnu", None)
+MXFP4_MAGNITUDES = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=np.float32)     # code & 7; bit 3 is the sign
+_MXFP4_POLICY = ("storage='mxfp4' takes a pair (codes, scales): uint8 [n, d/2] and uint8 [n, d/32] (numpy or torch, host or device), or "
+                 "torch.float4_e2m1fn_x2 and torch.float8_e8m0fnu tensors of those shapes, d a multiple of 32, and quantises "
+                 "nothing itself: convert other data with hyperdb._native.to_mxfp4(X) first")
+
+
+def mxfp4_pitch(d):
+    """Bytes of one stored MXFP4 row of d elements: codes, scales, zero padding to a multiple of 16 (hdb_row_bytes)."""
+    return (d // 2 + d // 32 + 15) // 16 * 16
+
+
+def _mxfp4_check(data):
+    """The input policy of storage="mxfp4" -> (codes, scales) as 2-D uint8 arrays / tensors; ValueError naming to_mxfp4 otherwise."""
+    if not isinstance(data, (tuple, list)) or len(data) != 2:
+        raise ValueError(f"{_MXFP4_POLICY}; got {type(data).__name__}")
+    pair = []
+    for x, own in zip(data, (_F4X2, _E8M0)):
+        if isinstance(x, torch.Tensor):
+            x = x.detach()
+            if own is not None and x.dtype == own:
+                x = x.view(torch.uint8)
+            ok = x.dtype == torch.uint8
+        else:
+            ok = isinstance(x, np.ndarray) and x.dtype == np.uint8
+        if not ok or len(x.shape) != 2:
+            raise ValueError(f"{_MXFP4_POLICY}; got {getattr(x, 'dtype', type(x).__name__)} data of shape {tuple(getattr(x, 'shape', ()))}")
+        pair.append(x)
+    codes, scales = pair
+    n, d = int(codes.shape[0]), 2 * int(codes.shape[1])
+    if d == 0 or d % 32 != 0 or tuple(scales.shape) != (n, d // 32):
+        raise ValueError(f"{_MXFP4_POLICY}; got codes {tuple(codes.shape)} and scales {tuple(scales.shape)}")
+    return codes, scales
+
+
+def to_mxfp4_rows(data, device):
+    """A pair (codes, scales) -> the stored rows, contiguous torch.uint8 ``[n, P(d)]`` on `device`: per row the d/2 code bytes,
+    the d/32 scale bytes, zero padding (include/hyperdb_hip.h, HDB_MXF4).  ValueError naming to_mxfp4 for anything else."""
+    codes, scales = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in _mxfp4_check(data))
+    n, half = int(codes.shape[0]), int(codes.shape[1])
+    out = torch.zeros((n, mxfp4_pitch(2 * half)), dtype=torch.uint8, device=device)
+    out[:, :half] = codes.to(device)
+    out[:, half:half + int(scales.shape[1])] = scales.to(device)
+    return out
+
+
+def pack_mxfp4_rows(codes, scales):
+    """(codes, scales) -> the stored rows as a host array, uint8 ``[n, P(d)]``."""
+    return to_mxfp4_rows((codes, scales), torch.device("cpu")).numpy()
+
+
+def split_mxfp4_rows(rows, d):
+    """Stored rows uint8 ``[n, P(d)]`` (numpy) -> (codes ``[n, d/2]``, scales ``[n, d/32]``), copies."""
+    return np.ascontiguousarray(rows[:, :d // 2]), np.ascontiguousarray(rows[:, d // 2:d // 2 + d // 32])
+
+
+def mxfp4_to_float(codes, scales):
+    """(codes, scales) -> the float32 matrix ``[n, d]`` they stand for, exactly: element e of a row is nibble e & 1 of code byte
+    e >> 1 (the even element in the low nibble), sign x magnitude x 2^(scale byte - 127); a scale byte of 255 is a NaN block."""
+    codes, scales = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in _mxfp4_check((codes, scales)))
+    n, d = codes.shape[0], 2 * codes.shape[1]
+    c = np.stack([codes & 15, codes >> 4], axis=-1).reshape(n, d)
+    v = np.where(c & 8, np.float32(-1), np.float32(1)) * MXFP4_MAGNITUDES[c & 7]
+    with np.errstate(over="ignore"):                    # (scale byte 254 takes the magnitudes 2 .. 6 past the largest float32: +-inf)
+        two_k = np.ldexp(np.float32(1), scales.astype(np.int32) - 127).astype(np.float32)
+        two_k[scales == 255] = np.nan
+        return (v.reshape(n, d // 32, 32) * two_k[:, :, None]).reshape(n, d).astype(np.float32)
+
+
+def to_mxfp4(X):
+    """Finite float data ``[n, d]``, d a multiple of 32 -> (codes uint8 ``[n, d/2]``, scales uint8 ``[n, d/32]``) by the OCP
+    rule: per block of 32 the shared exponent is floor(log2(amax)) - 2 clamped to [-127, 127] (an all-zero block: scale byte
+    127), the elements are divided by it, rounded to nearest even onto the e2m1 grid and saturated at +-6.  On the host."""
+    if isinstance(X, torch.Tensor):
+        X = X.detach().cpu().to(torch.float64).numpy()
+    a = np.asarray(X)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.number) or np.issubdtype(a.dtype, np.complexfloating):
+        raise ValueError("to_mxfp4: vectors must be numeric")
+    if a.ndim != 2 or a.shape[1] == 0 or a.shape[1] % 32 != 0:
+        raise ValueError(f"to_mxfp4: vectors must be 2-D with d a multiple of 32, got shape {tuple(a.shape)}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("to_mxfp4: vectors must be finite (a NaN block is scale byte 255, written by hand)")
+    n, d = a.shape
+    blocks = a.reshape(n, d // 32, 32)
+    amax = np.abs(blocks).max(axis=-1)
+    expo = np.clip(np.frexp(amax)[1] - 1 - 2, -127, 127)          # frexp: amax = m 2^ex, m in [0.5, 1), so floor(log2) = ex - 1
+    expo[amax == 0] = 0
+    x = np.abs(np.ldexp(blocks, -expo[:, :, None]))
+    # the e2m1 grid has steps of 0.5 below 2, of 1 up to 4 and of 2 beyond; np.rint rounds ties to even multiples of the step, which
+    # are the codes with a clear mantissa bit
+    mag = np.where(x < 2, np.rint(x * 2) / 2, np.where(x < 4, np.rint(x), np.minimum(np.rint(x / 2) * 2, 6.0)))
+    code = np.searchsorted(MXFP4_MAGNITUDES.astype(np.float64), mag).astype(np.uint8) | (np.signbit(blocks).astype(np.uint8) << 3)
+    code = code.reshape(n, d // 2, 2)
+    return (code[:, :, 0] | (code[:, :, 1] << 4)).astype(np.uint8), (expo + 127).astype(np.uint8)
 
 
 def to_i8(data):
@@ -350,11 +456,14 @@ class GpuIndex:
         self.bitorder = bit_order(bitorder)    # storage="bits": the order of the caller's packed bytes (the device holds "little")
         if storage == "bits":
             _bits_check(vectors)               # (the input policy: ValueError before a GPU is asked for)
+        if storage == "mxfp4":
+            _mxfp4_check(vectors)              # (likewise)
         require_gpu()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
-        t = to_bits(vectors, self.device, bitorder) if storage == "bits" else to_device_matrix(vectors, self.device, storage)
+        t = (to_bits(vectors, self.device, bitorder) if storage == "bits" else to_mxfp4_rows(vectors, self.device) if storage == "mxfp4"
+             else to_device_matrix(vectors, self.device, storage))
         if t.dim() != 2:
             # reference: non-2-D vectors make the metric functions raise (tests/test_ranking_algorithm.py:107-114)
             raise ValueError(f"vectors must be 2-D (N x d), got shape {tuple(t.shape)}")
@@ -362,10 +471,12 @@ class GpuIndex:
         self.n, self.d = int(t.shape[0]), int(t.shape[1])
         if storage == "bits":
             self.d *= 8                        # d counts bits; V is the uint8 tensor [n, d / 8]
+        if storage == "mxfp4":
+            self.d = 2 * int(_mxfp4_check(vectors)[0].shape[1])      # d counts elements; V is the uint8 tensor [n, P(d)] of stored rows
         if self.d == 0:
             raise ValueError("vectors must have d > 0")
         self._cols = int(t.shape[1])           # columns of the stored tensor: d, or d / 8 bytes of a bits index
-        self.dtype = _STORED2HDB[t.dtype]
+        self.dtype = HDB_MXF4 if storage == "mxfp4" else _STORED2HDB[t.dtype]
         self.storage = storage                 # "int8": append / update convert with to_i8; "bits": with to_bits
         self.row_base = int(row_base)
         self._h = ctypes.c_void_p()
@@ -410,6 +521,8 @@ class GpuIndex:
             rows = to_f8(rows)                              # float data into a float8 index: torch's conversion, on the host
         if self.dtype == HDB_B1:
             t = to_bits(rows, self.device, self.bitorder)          # (packed uint8 or bool rows only -- ValueError before anything is stored)
+        elif self.dtype == HDB_MXF4:
+            t = to_mxfp4_rows(rows, self.device)                   # (a pair (codes, scales) only -- ValueError before anything is stored)
         else:
             t = to_device_matrix(rows, self.device, self.storage)      # (an int8 index: to_i8 -- ValueError before anything is stored)
         if t.dim() == 1:
@@ -446,11 +559,14 @@ class GpuIndex:
             vectors = to_f8(vectors)                        # ... into a float8 index: torch's conversion, on the host, as append does
         if self.dtype == HDB_B1:
             t = to_bits(vectors, self.device, self.bitorder)       # (a bits index: packed uint8 or bool rows, as append does)
+        elif self.dtype == HDB_MXF4:
+            t = to_mxfp4_rows(vectors, self.device)                # (an MXFP4 index: a pair (codes, scales), as append does)
         else:
             t = to_device_matrix(vectors, self.device, self.storage)   # (an int8 index: to_i8, as append does)
         if self.dtype == HDB_BF16 and t.dtype != torch.bfloat16:
             t = t.to(torch.bfloat16)                        # float data into a bf16 index: round to nearest even, as append does
-        if t.dim() != 2 or int(t.shape[1]) != self._cols or _STORED2HDB.get(t.dtype) != self.dtype:
+        stored = HDB_MXF4 if self.dtype == HDB_MXF4 else _STORED2HDB.get(t.dtype)      # (stored MXFP4 rows are uint8 too)
+        if t.dim() != 2 or int(t.shape[1]) != self._cols or stored != self.dtype:
             raise ValueError("update: matrix must keep d and dtype")
         self.V, self.n = t, int(t.shape[0])
         self._bias = self._mask = self._nan = None
@@ -500,6 +616,8 @@ class GpuIndex:
         the exact float32 widening (numpy has no bfloat16), and so do a float8 index (widened on the host) and an int8 index."""
         if self.dtype == HDB_B1:
             return unpack_bits_host(self.V.cpu().numpy(), "little")
+        if self.dtype == HDB_MXF4:
+            return mxfp4_to_float(*self.host_mxfp4())
         if self.V.dtype == torch.int8:
             return self.V.cpu().numpy().astype(np.float32)
         if self.V.dtype == torch.bfloat16:
@@ -514,6 +632,12 @@ class GpuIndex:
             raise ValueError("host_bits: only a storage='bits' index holds packed rows")
         v = reverse_bits8(self.V) if self.bitorder == "big" else self.V
         return v.cpu().numpy()
+
+    def host_mxfp4(self):
+        """An MXFP4 index (storage="mxfp4"): the stored rows as the pair (codes uint8 ``[n, d/2]``, scales uint8 ``[n, d/32]``)."""
+        if self.dtype != HDB_MXF4:
+            raise ValueError("host_mxfp4: only a storage='mxfp4' index holds MXFP4 rows")
+        return split_mxfp4_rows(self.V.cpu().numpy(), self.d)
 
     def _bits_query(self, q):
         """A bits index: a uint8 query of d/8 bytes (or [nq, d/8]) is packed in the index's bitorder -> its 0/1 float32 form (binary

@@ -30,8 +30,8 @@ def _bounds(n, parts):
 
 class GpuGroup:
     def __init__(self, vectors, devices, storage=None):
-        if _native.storage_mode(storage) == "bits":
-            raise NotImplementedError(_native.BITS_SINGLE_INDEX)
+        if _native.single_index_only(storage):
+            raise NotImplementedError(_native.single_index_only(storage))
         _native.require_gpu()
         devices = [torch.device("cuda", d) if isinstance(d, int) else torch.device(d) for d in devices]
         if not devices:

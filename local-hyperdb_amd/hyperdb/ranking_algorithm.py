@@ -48,15 +48,15 @@ class ResidentVectors:
 
     def __init__(self, vectors, device=None, devices=None, quantize=None, storage=None, bitorder="big"):
         _native.quant_mode(quantize)                     # (ValueError before anything is uploaded)
-        if _native.storage_mode(storage) == "bits" and devices:
-            raise NotImplementedError(_native.BITS_SINGLE_INDEX)
+        if _native.single_index_only(storage) and devices:
+            raise NotImplementedError(_native.single_index_only(storage))
         self.index = (GpuGroup(vectors, devices, storage=storage) if devices
                       else GpuIndex(vectors, device=device, storage=storage, bitorder=bitorder))
         if quantize is not None:
             _native.request_shadow(self.index, quantize)     # (a bfloat16 matrix: sets bf16_quant first)
         arr_dtype = vectors.dtype if hasattr(vectors, "dtype") else None
-        if storage in ("int8", "bits"):
-            arr_dtype = None                             # the STORED dtype decides: an int8 / packed-bit index answers in float32
+        if storage in ("int8", "bits", "mxfp4"):
+            arr_dtype = None                             # the STORED dtype decides: an int8 / packed-bit / MXFP4 index answers in float32
         self.np_dtype = _np_dtype_of(arr_dtype, self.index)
 
     @property
@@ -81,7 +81,11 @@ def register_vectors(vectors, device=None, devices=None, quantize=None, storage=
     ``[n, d/8]`` (``np.packbits`` order; see ``_native.pack_bits``) or a 2-D bool array ``[n, d]``; every metric is the reference's
     arithmetic on the 0/1 matrix the bits stand for, with float32 queries of d elements and float32 scores.  ``bitorder``
     ("big", np.packbits' default, or "little") names the order of the packed bytes; a uint8 query of d/8 bytes is taken as packed
-    in the same order."""
+    in the same order.
+    ``storage="mxfp4"`` (one device only) keeps MXFP4 rows, half a byte per element plus one scale byte per 32: ``vectors`` is a
+    pair ``(codes, scales)`` -- uint8 ``[n, d/2]`` and ``[n, d/32]``, or torch.float4_e2m1fn_x2 / torch.float8_e8m0fnu tensors;
+    ``_native.to_mxfp4`` makes one from float data -- and every metric is the reference's arithmetic on the float32 matrix the
+    pair stands for (``_native.mxfp4_to_float``), with float32 queries of d elements and float32 scores."""
     return ResidentVectors(vectors, device=device, devices=devices, quantize=quantize, storage=storage, bitorder=bitorder)
 
 
@@ -561,6 +565,8 @@ def rank_mmr(vectors, query_vectors, top_k=5, fetch_k=None, lambda_mult=0.5, met
             raise NotImplementedError(f"rank_mmr: pair_metric {pm!r} is not built (dot, cosine and euclidean are)")
         if ix.dtype == _native.HDB_B1:
             raise NotImplementedError("rank_mmr: a storage='bits' index is a first stage; pair similarity of packed bits is not built")
+        if ix.dtype == _native.HDB_MXF4:
+            raise NotImplementedError("rank_mmr: a storage='mxfp4' index is a first stage; pair similarity of MXFP4 rows is not built")
         if not 0.0 <= float(lambda_mult) <= 1.0:
             raise ValueError(f"rank_mmr: lambda_mult must be in [0, 1], got {lambda_mult!r}")
         if ix.has_nan or np.isnan(qh).any():
