@@ -764,7 +764,8 @@ void hdb_group_destroy(hdb_group* g);
  *   nothing on other dtypes),
  *   auto_quant (1: a large float16 index builds its own shadow on the first eligible call; 0: never), quant_batch_min_n (batches
  *   of 5+ queries through that shadow: -1 the measured rule, >= 0 from this many rows on), quant_batch_kernel (1: int8 matrix
- *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane),
+ *   cores, 0: the v_dot4 scan four queries at a time), use_plane (0: one-query calls never pre-filter through the 5-bit plane;
+ *   1: the pass reads the fifth bit only for the rows its four-bit bound keeps where that was measured to pay, 2: never, 3: always),
  *   plane_min_n (-1: the measured rule), plane_cap_rows (0: n / 8; kept rows beyond which a call counts in plane_overflows -- a
  *   statistic: no call is answered differently for it), plane_wg_per_cu (workgroups per CU of the pass over the plane: 0 the
  *   measured table, 1 .. 8 that many -- for A/B runs, no call is answered differently for it).

@@ -890,7 +890,9 @@ static int quant_topk(hdb_index* ix, const TopkArgs& c, const TopkPlan& p) {
         a.pl_nib = ix->pnib; a.pl_bit = ix->pbit; a.pl_rec = ix->prec; a.pl_units = ix->pU;
         a.pl_cnt = pl_cnt; a.pl_cap = p.pl_cap;
         a.pl_s_tiles = (uint32_t)sp.s_tiles; a.pl_s_stride = (uint32_t)sp.s_stride;      // ... and walks the other tiles
-        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, 0, p.pl_blocks, st));      // (the grid is the plan's: stat plane_blocks)
+        // (stage A where hdb_quant_plane_stage_a says so -- the function the plan sized the grid by; stat plane_blocks)
+        const bool stage_a = hdb_quant_plane_stage_a(n, hdb_quant_plane_j(ix->pU), ix->opt.use_plane) != 0;
+        LAUNCH_TRY(hdb_launch_quant_plane_scan(&a, stage_a ? 0 : 2, p.pl_blocks, st));
     } else {
         LAUNCH_TRY(hdb_launch_quant_scan(&a, 1, (int)ix->opt.max_blocks, st));
     }

@@ -461,6 +461,39 @@ static_assert(hdb_quant_plane_wg_per_cu(1) >= 1 && hdb_quant_plane_wg_per_cu(1) 
               hdb_quant_plane_wg_per_cu(3) >= 1 && hdb_quant_plane_wg_per_cu(3) <= hdb_quant_plane_waves(3) &&
               hdb_quant_plane_wg_per_cu(4) >= 1 && hdb_quant_plane_wg_per_cu(4) <= hdb_quant_plane_waves(4),
               "a default grid of the plane pass asks for more waves per SIMD than its kernel is compiled for");
+// Stage A (hdb_quant.hip, "Stage A": the bit words are read for the rows the nibbles cannot reject) adds a dependent round trip to
+// every step, so it wants more waves than the one-stage pass and pays only where the stream is long.  Measured with
+// tools/time_plane_stage.py (one handle, the two passes alternating call by call, p50 of a call in us), stage A at its best grid /
+// the one-stage pass at its table grid, run 1 and run 2 (profiles/plane_bit_time.txt):
+//   J = 3 (d = 384), 5 or 6: 5M 275.5 / 278.3 and 279.0 / 280.6, 6M 312.1 / 320.9 and 315.2 / 317.9, 7M 360.5 / 365.2 and 357.6 /
+//     364.5, 8M 385.1 / 396.3 and 380.6 / 396.8, 10M 450.3 / 469.5 and 444.9 / 469.6; a loss at 2M at every grid.  A win of 1 %
+//     at 5M .. 7M, of 3 .. 5 % from 8M on                                                                        -> from 8M rows, grid 5
+//   J = 2 (d = 256), 7: 2M a loss, 5M 210.6 / 211.8 and 206.9 / 210.1, 8M 281.2 / 297.8 and 278.0 / 294.9, 10M 328.5 / 347.7 and
+//     322.3 / 344.1 (6 is behind 7 at 5M .. 10M in both runs)                                                    -> from 8M rows, grid 7
+//   J = 4 (d = 512), 5: 5M 353.6 / 356.5 and 356.5 / 351.0, 8M 526.1 / 524.8 and 522.5 / 521.3, 10M 600.7 / 616.3 and 594.2 / 610.4:
+//     a win in both runs at 10M only                                                                             -> not by default
+//   J = 1 (d = 128): a loss at 2M and 8M at every grid (one run)                                                 -> not by default
+// HDB_PLANE_A_WAVES: what the compiler gives <J, false> with stage A (profiles/plane_bit_kernel_resources.txt).
+// HDB_PLANE_A_WG_PER_CU: the grid of a pass with stage A; HDB_PLANE_A_DEFAULT: the J at which use_plane = 1 takes it, from
+// HDB_PLANE_A_MIN_ROWS rows on.  use_plane = 2 never takes it, use_plane = 3 always (tests, A/B runs).
+#define HDB_PLANE_A_MIN_ROWS 8000000
+#define HDB_PLANE_A_WAVES {7, 7, 6, 5}
+#define HDB_PLANE_A_WG_PER_CU {4, 7, 5, 5}
+#define HDB_PLANE_A_DEFAULT {0, 1, 1, 0}
+static constexpr int hdb_quant_plane_a_waves(int J) { constexpr int t[4] = HDB_PLANE_A_WAVES; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
+static constexpr int hdb_quant_plane_a_wg_per_cu(int J) { constexpr int t[4] = HDB_PLANE_A_WG_PER_CU; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
+static constexpr bool hdb_quant_plane_a_default(int J) { constexpr int t[4] = HDB_PLANE_A_DEFAULT; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1] != 0; }
+static_assert(hdb_quant_plane_a_wg_per_cu(1) >= 1 && hdb_quant_plane_a_wg_per_cu(1) <= hdb_quant_plane_a_waves(1) &&
+              hdb_quant_plane_a_wg_per_cu(2) >= 1 && hdb_quant_plane_a_wg_per_cu(2) <= hdb_quant_plane_a_waves(2) &&
+              hdb_quant_plane_a_wg_per_cu(3) >= 1 && hdb_quant_plane_a_wg_per_cu(3) <= hdb_quant_plane_a_waves(3) &&
+              hdb_quant_plane_a_wg_per_cu(4) >= 1 && hdb_quant_plane_a_wg_per_cu(4) <= hdb_quant_plane_a_waves(4),
+              "a grid of the plane pass with stage A asks for more waves per SIMD than its kernel is compiled for");
+// -> workgroups per CU of the pass with stage A, or 0: the one-stage pass and its table.  The one place that decides: the plan
+// sizes the grid by it and quant_topk picks the kernel by it.
+static inline int hdb_quant_plane_stage_a(int64_t n, int J, int64_t use_plane) {
+    const bool take = use_plane == 3 || (use_plane == 1 && n >= HDB_PLANE_A_MIN_ROWS && hdb_quant_plane_a_default(J));
+    return take ? hdb_quant_plane_a_wg_per_cu(J) : 0;
+}
 // wg_per_cu: 0 = the table, 1 .. 8 = that many; max_blocks > 0 caps the result as it caps every grid
 static inline int hdb_quant_plane_blocks(int64_t nwalk, int J, int cus, int wg_per_cu, int max_blocks) {
     const int per_cu = wg_per_cu >= 1 ? (wg_per_cu < 8 ? wg_per_cu : 8) : hdb_quant_plane_wg_per_cu(J);
@@ -514,7 +547,8 @@ __host__ __device__ __forceinline__ int64_t hdb_plane_skip_tile(const HdbSkipPos
 // (zero).  A hot block: 16 bfloat16 k_hi (row r's scale -- s_r, cosine: s_r / ||v_r|| -- rounded UP), 16 bytes rc = ceil(2 R_r),
 // then four float32 words of the tile: E*, T* (the maxima of E_r and T_r over the tile's rows, cosine: of E_r / ||v_r|| and
 // T_r / ||v_r||, rounded up), F* (the bound's absolute floor 2^-100 (d + 8), cosine: times the largest 1 / ||v_r||, rounded up)
-// and a zero.  Pass 1 reads one block per tile; the numbers only ever widen its bound, and no bit of them reaches an answer.
+// and R4* (the largest ||rho4_r|| of the tile's rows, rounded up: stage A's residual bound, the same in both blocks).  Pass 1 reads one
+// block per tile; the numbers only ever widen its bound, and no bit of them reaches an answer.
 // (__host__ __device__: hdb_quant_plane_rows_kernel writes with these functions, hdb_quant_plane_scan_kernel reads with them and
 // tests/plane_block_check.hip runs them on the host.)
 #define HDB_PLANE_TILE_BYTES 256
@@ -523,7 +557,7 @@ __host__ __device__ __forceinline__ int64_t hdb_plane_skip_tile(const HdbSkipPos
 #define HDB_PLANE_BLOCK_COSINE 1
 #define HDB_PLANE_BLOCK_K 0           // byte offsets inside a hot block: 16 x bf16 k_hi,
 #define HDB_PLANE_BLOCK_RC 32         // 16 x u8 rc,
-#define HDB_PLANE_BLOCK_TILE 48       // {E*, T*, F*, 0} float32
+#define HDB_PLANE_BLOCK_TILE 48       // {E*, T*, F*, R4*} float32
 // bytes of the record array for `rows` rows: whole tiles (16 bytes per row all the same)
 __host__ __device__ __forceinline__ int64_t hdb_plane_rec_bytes(int64_t rows) { return (rows + 15) / 16 * HDB_PLANE_TILE_BYTES; }
 __host__ __device__ __forceinline__ int64_t hdb_plane_block_off(int64_t tile, int flavour) {
@@ -566,6 +600,21 @@ __host__ __device__ __forceinline__ float hdb_plane_up(double x) {
     if ((double)f < x) f = hdb_plane_bits_f(hdb_plane_f_bits(f) + 1u);
     return f;
 }
+// Stage A of the plane pass bounds a row from its nibbles alone: c = 16 n - 120 + rho4, rho4 in [-8, 7], and the fourth tile word of a
+// hot block is R4*, the largest ||rho4_r|| over the tile's rows.  ss4 is a row's integer sum of rho4^2 over j < d (at most 64 x 512).
+__host__ __device__ __forceinline__ int hdb_plane_rho4(int c) { return c - (16 * (((c >> 3) + 16) >> 1) - 120); }
+__host__ __device__ __forceinline__ float hdb_plane_r4_up(uint32_t ss4) { return hdb_plane_up(sqrt((double)ss4) * (1.0 + 0x1p-40)); }
+// The interval of fl(C) both stages put through the bound: fc the float32 of the integer centre (C5 or C4), Uf = fl(N_c R) with
+// R >= ||rho|| (hdb_quant.hip, (4) and "Stage A"): ch >= fl(C) >= cl.
+__host__ __device__ __forceinline__ void hdb_plane_interval(float fc, float Uf, float& ch, float& cl) {
+    ch = fc + Uf; cl = fc - Uf;
+    ch = ch + (fabsf(ch) * 0x1p-20f + 1.f);
+    cl = cl - (fabsf(cl) * 0x1p-20f + 1.f);
+}
+// Stage B numbers the bit words of the rows it keeps idx = slot U + unit, idx < 32 U <= 512: slot = idx / U as one multiply (the
+// reciprocal errs by less than U / 2^16 per unit of idx, 512 x 16 < 2^16; tests/plane_bit_check.hip divides every pair)
+__host__ __device__ __forceinline__ uint32_t hdb_plane_rcp_u(uint32_t U) { return (65536u + U - 1u) / U; }
+__host__ __device__ __forceinline__ uint32_t hdb_plane_div_u(uint32_t idx, uint32_t rcp_u) { return (idx * rcp_u) >> 16; }
 
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 // widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan

@@ -56,7 +56,7 @@ struct hdb_options {
     int64_t auto_quant = 1;           // fp16 matrix, 1-4 dot / cosine queries on the matrix cores: build the shadow on the first eligible call of a large index
     int64_t quant_batch_min_n = -1;   // ... batches of 5+ queries: from this many rows on (-1: the measured rule, quant_batch_rule)
     int64_t quant_batch_kernel = 1;   // ... their filter pass: 1 = int8 matrix cores (hdb_quant_mfma.hip), 0 = the v_dot4 scan, four queries per pass
-    int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch)
+    int64_t use_plane = 1;            // one dot / cosine query: pre-filter the shadow's rows through the 5-bit plane (0: never -- the manual switch; 2: without stage A, 3: stage A at every size)
     int64_t plane_min_n = -1;         // ... from this many rows on (-1: the measured rule, HDB_PLANE_MIN_ROWS)
     int64_t plane_cap_rows = 0;       // ... kept rows beyond which a call counts in the stat plane_overflows (0: n / 8); changes no answer
     int64_t plane_wg_per_cu = 0;      // ... workgroups per CU of its pass: 0 = the measured table (HDB_PLANE_WG_PER_CU, hdb_caps.h), 1 .. 8 = fixed (A/B runs); changes no answer
@@ -311,9 +311,12 @@ static inline void plan_quant(TopkPlan& p, const TopkFacts& ix, const hdb_option
                      ix.n >= (o.plane_min_n >= 0 ? o.plane_min_n : (int64_t)HDB_PLANE_MIN_ROWS);
     p.pl_cap = plane_list_cap(o, ix.n);
     // the plane pass walks the tiles the sample did not take; its grid follows the device and the measured table (hdb_caps.h)
-    if (p.plane_wanted)
-        p.pl_blocks = hdb_quant_plane_blocks((ix.n + 15) / 16 - p.qs.s_tiles, hdb_quant_plane_j(hdb_quant_plane_units(p.P)), ix.cus,
-                                             (int)o.plane_wg_per_cu, (int)o.max_blocks);
+    // (a pass with stage A has a grid of its own, hdb_quant_plane_stage_a)
+    if (p.plane_wanted) {
+        const int J = hdb_quant_plane_j(hdb_quant_plane_units(p.P)), wg_a = hdb_quant_plane_stage_a(ix.n, J, o.use_plane);
+        p.pl_blocks = hdb_quant_plane_blocks((ix.n + 15) / 16 - p.qs.s_tiles, J, ix.cus,
+                                             o.plane_wg_per_cu >= 1 ? (int)o.plane_wg_per_cu : wg_a, (int)o.max_blocks);
+    }
     if (mflavour) {
         // the threshold folded into the two passes (QuantArgs::nsub) while the sample's grid has at least the 1024 subsets
         // hdb_sample_thr_kernel works with; smaller samples keep that kernel

@@ -138,6 +138,19 @@
 // (hdb_plane_skip_*, hdb_caps.h) and queues the sampled rows with !(hi < T_s) from the list.  Streamed, such a row was queued because
 // hi5 >= hi; a sampled row with hi < T_s that hi5 let through was queued for nothing (the drain drops it).  The drain evaluates and
 // emits on the same condition either way: the candidate set is unchanged, plane_survivors counts at most what it counted.
+// Stage A (hdb_quant_plane_scan_kernel<J, false>; where it is taken: hdb_quant_plane_stage_a, hdb_caps.h).  The 48 bytes of bit words
+// of a row are read only where its nibbles cannot reject it.  With n = u >> 1 the stored nibble and b = u & 1,
+//     c = 8 (2n + b) - 124 + rho = 16 n - 120 + rho4,   rho4 = 8b - 4 + rho in [-8, 7],
+// so with C4 = 16 sum_j c_qj n_rj - 120 sum_j c_qj (exact in int32: |16 S4| <= 16 x 127 x 15 x 512) and R4 = ||rho4_r|| over j < d
+//     |C - C4| = |sum_j c_qj rho4_rj| <= N_c R4 <= N_c R4*,   R4* the largest R4 of the tile's rows, rounded up (fourth tile word of a
+// hot block, the same in both; a padding element j >= d has rho4 = -8 against c_qj = 0).  ch4 and cl4 are formed from fl(C4) and
+// fl(N_c R4*) exactly as ch and cl from fl(C5) and fl(N_c R) (hdb_plane_interval): the roundings are 2^-24 (|C4| + 2 N_c R4*) with
+// N_c R4* <= 1016 d, |C4| <= 127^2 d + 1016 d, below 0.6 for d <= 512, under the absolute 1.  Everything after (4) uses only
+// ch >= fl(C) >= cl, and stage A runs that very code (hq_plane_hi) on (ch4, cl4): hi4 >= hi, MODE 1's upper bound, for every row.
+// A row with hi4 < T_s (a NaN never drops) would be dropped by MODE 1, and is dropped here before its bit words are read.  The
+// rows stage A keeps get S1 = sum_j c_qj b_rj from their bit words; 8 (2 S4 + S1) - 124 sum c_q is the integer C5 of the one-stage
+// decode, hi5 is evaluated from it by the same code, and !(hi5 < T_s) decides the queue as before: plane_survivors is what the
+// one-stage pass counts (hi4 < T_s implies hi5 < T_s only up to the two bounds' slacks, so it can only stay equal or fall).
 #include "hdb_common.h"
 #include "hdb_unpack.h"      // hdb_to_f (the row quantizer)
 #include "hdb_quant.h"
@@ -689,7 +702,7 @@ __global__ __launch_bounds__(256) void hdb_quant_scan_kernel(QuantArgs a) {
 // The 5-bit plane.  Derivation from the codes of the 16-row tiles [t0, t1), rows below n: a wave per tile, four rows at a time, 16
 // lanes per row; lane l16 packs unit l16 (32 elements: one 16-byte piece of nibbles, one word of bits), the group sums the squared
 // residuals of the elements below d.  Lanes 0-15 then hold one row of the tile each and write its two hot blocks (hdb_caps.h): the
-// maxima E*, T*, F* are tile state, so a tile is always derived whole, from all of its rows (plane_rows, hdb_api.hip, rounds to
+// maxima E*, T*, F*, R4* are tile state, so a tile is always derived whole, from all of its rows (plane_rows, hdb_api.hip, rounds to
 // tiles), and the rows at or beyond n take no part in them.  inv_norm must hold the tile's rows already.
 // ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t* codes, const float* aux, const float* inv_norm, int64_t t0,
@@ -699,11 +712,11 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
     for (int64_t t = t0 + wave; t < t1; t += nwaves) {                       // (wave-uniform)
-        int ssr[4];
+        int ssr[4], ssr4[4];
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int64_t r = t * 16 + 4 * it + g;
-            int ss = 0;
+            int ss = 0, ss4 = 0;
             if (r < n && l16 < U) {
                 const int8_t* src = codes + r * (int64_t)P + 32 * l16;
                 uint4 raw[2];
@@ -719,7 +732,8 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
                         const int h = c >> 3;
                         const uint32_t u5 = (uint32_t)(h + 16);
                         const int rho = c - (8 * h + 4);
-                        if (32 * l16 + 4 * w + b < d) ss += rho * rho;
+                        const int rho4 = hdb_plane_rho4(c);                  // (c = 16 (u5 >> 1) - 120 + rho4: stage A's residual)
+                        if (32 * l16 + 4 * w + b < d) { ss += rho * rho; ss4 += rho4 * rho4; }
                         nw[w >> 1] |= (u5 >> 1) << (8 * b + 4 * (w & 1));
                         bw |= (u5 & 1u) << (8 * b + w);
                     }
@@ -728,21 +742,22 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
                 bitw[r * (int64_t)U + l16] = bw;
             }
 #pragma unroll
-            for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+            for (int o = 8; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, 64); ss4 += __shfl_xor(ss4, o, 64); }
+            ssr4[it] = ss4;
             ssr[it] = ss;                                                    // (every lane of group g: row 4 it + g; at most 16 d, exact)
         }
         // lane e < 16 takes row e = 4 it + g of the tile from group g = e & 3, pass it = e >> 2
-        int ss = 0;
+        int ss = 0, ss4 = 0;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int v = __shfl(ssr[it], 16 * (lane & 3), 64);
-            if (((lane >> 2) & 3) == it) ss = v;
+            const int v = __shfl(ssr[it], 16 * (lane & 3), 64), v4 = __shfl(ssr4[it], 16 * (lane & 3), 64);
+            if (((lane >> 2) & 3) == it) { ss = v; ss4 = v4; }
         }
         const int64_t r = t * 16 + l16;
         const bool valid = lane < 16 && r < n;
         const double absmin = 0x1p-100 * (double)(d + 8);
         double kd = 0.0, kc = 0.0;
-        float ed = 0.f, td = 0.f, fd = 0.f, ec = 0.f, tc = 0.f, fc = 0.f;
+        float ed = 0.f, td = 0.f, fd = 0.f, ec = 0.f, tc = 0.f, fc = 0.f, r4 = 0.f;
         uint32_t rcode = 0u;
         if (valid) {
             const float s = aux[3 * r + HDB_QROW_S], e = aux[3 * r + HDB_QROW_E], tt = aux[3 * r + HDB_QROW_T];
@@ -751,11 +766,13 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
             ed = e; td = tt; fd = hdb_plane_up(absmin);
             ec = hdb_plane_up((double)e * inv); tc = hdb_plane_up((double)tt * inv); fc = hdb_plane_up(absmin * inv * (1.0 + 0x1p-40));
             rcode = hdb_plane_rc_encode((uint32_t)ss);
+            r4 = hdb_plane_r4_up((uint32_t)ss4);
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) {                                    // (a NaN of a non-finite row is dropped or kept: such an index takes no quantized call)
             ed = fmaxf(ed, __shfl_xor(ed, o, 64)); td = fmaxf(td, __shfl_xor(td, o, 64)); fd = fmaxf(fd, __shfl_xor(fd, o, 64));
             ec = fmaxf(ec, __shfl_xor(ec, o, 64)); tc = fmaxf(tc, __shfl_xor(tc, o, 64)); fc = fmaxf(fc, __shfl_xor(fc, o, 64));
+            r4 = fmaxf(r4, __shfl_xor(r4, o, 64));
         }
         if (lane < 16) {
             char* tile = reinterpret_cast<char*>(rec) + hdb_plane_block_off(t, 0);
@@ -766,7 +783,7 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
                 reinterpret_cast<uint8_t*>(blk + HDB_PLANE_BLOCK_RC)[l16] = (uint8_t)rcode;
                 if (l16 == 0)
                     *reinterpret_cast<float4*>(blk + HDB_PLANE_BLOCK_TILE) =
-                        fl == HDB_PLANE_BLOCK_COSINE ? make_float4(ec, tc, fc, 0.f) : make_float4(ed, td, fd, 0.f);
+                        fl == HDB_PLANE_BLOCK_COSINE ? make_float4(ec, tc, fc, r4) : make_float4(ed, td, fd, r4);
             }
             if (l16 < 8) *reinterpret_cast<uint4*>(tile + 2 * HDB_PLANE_BLOCK_BYTES + 16 * l16) = make_uint4(0u, 0u, 0u, 0u);      // reserved
         }
@@ -792,14 +809,48 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
 //  narrow widths a wave per SIMD; with the cap the allocator keeps a handful of scalars in vector lanes around the drain instead.
 //  QuantArgs stays the first parameter: hq_args_in_memory.  The empty asm statements here and in the drain only steer the register
 //  allocator; the figures they buy are in profiles/quant_inpass_kernel_resources.txt with the compiler they were taken with.)
+// STAGE_A (the default of the stream; header, "Stage A"): a step streams the nibbles only and bounds every row from them, hi4 >= hi5's
+// own target hi.  The rows with !(hi4 < T_s) -- about one in eight -- are compacted by ballot and popcount (sel: the epilogue lane of
+// slot p), and their U bit words are loaded one word per lane, word idx = p U + unit in rounds of 64, multiplied against the eight
+// query words of the unit and left in part[wave] (flat: 32 U <= 128 J words) for the row's lane to add: S = 2 S4 + S1 is the sum the
+// one-stage decode forms, and hi5 comes from the one expression (hq_plane_hi).  Without STAGE_A (use_plane = 2, and the debug
+// flavour) both planes are read for every row.
 #define HQ_PL_QUEUE 48
-template <int J, bool DBG>
+// The coarse upper bound of a row from an interval of fl(C): fc the float of the integer centre (C5 or C4), Uf >= the Cauchy-Schwarz
+// half-width N_c R (header, (4) and "Stage A").  Everything behind ch >= fl(C) >= cl is the same for both stages.
+__device__ __forceinline__ float hq_plane_hi(float fc, float Uf, uint32_t kcode, float e_s, float t_s, float f_s, float q_s, float q_n, float q_d,
+                                             float q_inv, bool cosine, bool has_bias, float bias) {
+    float ch, cl;
+    hdb_plane_interval(fc, Uf, ch, cl);
+    const float k_hi = hdb_plane_k_hi(kcode), k_lo = hdb_plane_k_lo(k_hi);
+    float k_up = q_s * k_hi, k_dn = q_s * k_lo;
+    k_up = k_up + k_up * 0x1p-20f;
+    k_dn = k_dn - k_dn * 0x1p-20f;
+    const float A5 = (ch >= 0.f ? k_up : k_dn) * ch, Al = (cl >= 0.f ? k_dn : k_up) * cl;
+    const float Amax = fmaxf(fabsf(A5), fabsf(Al));
+    const float c0 = (q_n * e_s + q_d * t_s) * (1.f + 0x1p-10f);
+    const float B5 = c0 + fabsf(A5) * 0x1p-10f + f_s;
+    const float Bmax = c0 + Amax * 0x1p-10f + f_s;
+    const float Mx = Amax + Bmax;
+    float X = (A5 + B5) + (Mx * 0x1p-18f + 1e-30f);
+    float mM = Mx * (1.f + 0x1p-17f);
+    if (cosine) { X = X * q_inv; mM = mM * q_inv; }            // (1 / ||v_r|| is in k_hi, E*, T*, F* already)
+    const float Z = mM + fabsf(bias);
+    float h = X;
+    if (has_bias) h += bias;
+    float hi = h + (Z * 0x1p-18f + 4e-30f);
+    if (hi != hi) hi = INFINITY;
+    return hi;
+}
+template <int J, bool DBG, bool STAGE_A = !DBG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_quant_plane_scan_kernel(QuantArgs a) {
+    static_assert(!(DBG && STAGE_A), "the debug flavour reads both planes for every row");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int4* qs = reinterpret_cast<int4*>(smem);                       // [2 U] query codes, zero past P: MODE 1's layout for one query
     __shared__ int part[4][2][64 * J];
     __shared__ HqStage stage;
     __shared__ uint32_t queue[4][HQ_PL_QUEUE];
+    __shared__ uint32_t sel[STAGE_A ? 4 : 1][32];
     __shared__ uint32_t surv_cnt;
     const int U = a.pl_units, nch = a.P >> 4;
     if (threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
@@ -827,6 +878,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
     }
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x3 __attribute__((ext_vector_type(3)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const uint32_t rcp_u = hdb_plane_rcp_u((uint32_t)U);               // (stage B: slot and unit of a bit word, without a division)
     const int64_t ntiles = a.ntiles;
     const int et = lane >> 4, er = lane & 15;                       // epilogue lanes 0-31: tile et of the pair, row er
     int qn = 0;                                                     // rows in this wave's queue (wave-uniform)
@@ -879,7 +932,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             for (int j = 0; j < J; ++j) {
                 if (ln < pieces_left - 64 * j) {
                     nv[tt][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(nb + (uint32_t)ln * 16u) + 64 * j);     // (piece ln + 64 j: scalar base, 32-bit lane offset)
-                    bv[tt][j] = __builtin_nontemporal_load(bb + (uint32_t)ln + 64 * j);
+                    bv[tt][j] = STAGE_A ? 0u : __builtin_nontemporal_load(bb + (uint32_t)ln + 64 * j);      // (stage A: the bit words wait for the rows it keeps)
                 } else {
                     nv[tt][j] = u32x4{0u, 0u, 0u, 0u};
                     bv[tt][j] = 0u;
@@ -889,8 +942,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         // the row terms of the epilogue lanes, issued with the plane loads
         const int64_t row = (et ? tl[1] : tl[0]) * 16 + er;
         const bool rvalid = lane < 32 && row < a.n;      // (no tile: row = 16 ntiles >= n)
-        // (the hot block of the lane's tile, hdb_caps.h: its own k_hi and rc, and the tile's {E*, T*, F*, 0} -- 64 bytes per tile)
-        f32x3 tm = f32x3{0.f, 0.f, 0.f};                 // (three words, not the block's four: a fourth register nobody reads is reused at once, and that write waits for every load in flight)
+        // (the hot block of the lane's tile, hdb_caps.h: its own k_hi and rc, and the tile's {E*, T*, F*, R4*} -- 64 bytes per tile)
+        // (without stage A three words, not the block's four: a fourth register nobody reads is reused at once, and that write waits for
+        //  every load in flight; stage A reads the fourth, R4*)
+        f32x3 tm = f32x3{0.f, 0.f, 0.f};
+        float r4s = 0.f;
         uint32_t kcode = 0u, rcode = 0u;
         float bias = 0.f;
         bool masked = false;
@@ -900,7 +956,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             //  cost the headline 13 us against these -- profiles/plane_block_time.txt, "variant")
             kcode = reinterpret_cast<const uint16_t*>(blk + HDB_PLANE_BLOCK_K)[er];
             rcode = reinterpret_cast<const uint8_t*>(blk + HDB_PLANE_BLOCK_RC)[er];
-            tm = *reinterpret_cast<const f32x3*>(blk + HDB_PLANE_BLOCK_TILE);
+            if (STAGE_A) {
+                const f32x4 t4 = *reinterpret_cast<const f32x4*>(blk + HDB_PLANE_BLOCK_TILE);
+                tm = f32x3{t4.x, t4.y, t4.z}; r4s = t4.w;
+            } else {
+                tm = *reinterpret_cast<const f32x3*>(blk + HDB_PLANE_BLOCK_TILE);
+            }
             if (a.bias) bias = a.bias[row];
             if (a.mask) masked = !a.mask[row];
         }
@@ -918,8 +979,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
                 int s = 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const uint32_t lo = ((w4[i] << 1) & 0x1E1E1E1Eu) | ((bw >> (2 * i)) & 0x01010101u);
-                    const uint32_t hi = ((w4[i] >> 3) & 0x1E1E1E1Eu) | ((bw >> (2 * i + 1)) & 0x01010101u);
+                    // (stage A: the nibbles n = u >> 1 as they lie, no bit merge -- S4 = sum_j c_qj n_rj)
+                    const uint32_t lo = STAGE_A ? (w4[i] & 0x0F0F0F0Fu) : (((w4[i] << 1) & 0x1E1E1E1Eu) | ((bw >> (2 * i)) & 0x01010101u));
+                    const uint32_t hi = STAGE_A ? ((w4[i] >> 4) & 0x0F0F0F0Fu) : (((w4[i] >> 3) & 0x1E1E1E1Eu) | ((bw >> (2 * i + 1)) & 0x01010101u));
                     s = __builtin_amdgcn_sdot4((int)lo, qw[2 * i], s, false);
                     s = __builtin_amdgcn_sdot4((int)hi, qw[2 * i + 1], s, false);
                 }
@@ -937,36 +999,59 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         __builtin_amdgcn_wave_barrier();                 // (the next step's stores stay behind these loads)
         float hi5 = -INFINITY;
         const bool dead = !rvalid || masked || q_bad;
-        if (!dead) {
-            const float fc = (float)(8 * S - 124 * q_cs);
-            const float Uf = q_cn * hdb_plane_rc_decode(rcode);
-            float ch = fc + Uf, cl = fc - Uf;
-            ch = ch + (fabsf(ch) * 0x1p-20f + 1.f);
-            cl = cl - (fabsf(cl) * 0x1p-20f + 1.f);
-            const float k_hi = hdb_plane_k_hi(kcode), k_lo = hdb_plane_k_lo(k_hi);
-            float k_up = q_s * k_hi, k_dn = q_s * k_lo;
-            k_up = k_up + k_up * 0x1p-20f;
-            k_dn = k_dn - k_dn * 0x1p-20f;
-            const float A5 = (ch >= 0.f ? k_up : k_dn) * ch, Al = (cl >= 0.f ? k_dn : k_up) * cl;
-            const float Amax = fmaxf(fabsf(A5), fabsf(Al));
-            const float c0 = (q_n * tm.x + q_d * tm.y) * (1.f + 0x1p-10f);
-            const float B5 = c0 + fabsf(A5) * 0x1p-10f + tm.z;
-            const float Bmax = c0 + Amax * 0x1p-10f + tm.z;
-            const float Mx = Amax + Bmax;
-            float X = (A5 + B5) + (Mx * 0x1p-18f + 1e-30f);
-            float mM = Mx * (1.f + 0x1p-17f);
-            if (cosine) { X = X * q_inv; mM = mM * q_inv; }            // (1 / ||v_r|| is in k_hi, E*, T*, F* already)
-            const float Z = mM + fabsf(bias);
-            float h = X;
-            if (a.bias) h += bias;
-            hi5 = h + (Z * 0x1p-18f + 4e-30f);
-            if (hi5 != hi5) hi5 = INFINITY;
+        bool live = !dead;                               // (stage A: the rows whose bit words are read)
+        int S1 = 0;
+        if constexpr (STAGE_A) {
+            if (live) {
+                const float hi4 = hq_plane_hi((float)(16 * S - 120 * q_cs), q_cn * r4s, kcode, tm.x, tm.y, tm.z, q_s, q_n, q_d, q_inv, cosine,
+                                              a.bias != nullptr, bias);
+                live = !(hi4 < q_thr);                   // (a NaN never drops)
+            }
+            const uint32_t k4 = (uint32_t)__ballot(live);                        // (epilogue lanes 0-31)
+            if (k4 == 0u) continue;                      // (wave-uniform)
+            const int slot = __popc(k4 & ((1u << (lane & 31)) - 1u));
+            if (live) sel[wave][slot] = (uint32_t)lane;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // stage B: bit word idx = slot U + unit of the kept rows, one per lane, against the eight query words of its unit
+            int* part1 = &part[wave][0][0];              // (32 U <= 128 J words; the S4 reads are behind the barrier above)
+            const int nw = __popc(k4) * U;               // (at most 32 U)
+#pragma unroll 1
+            for (int base = 0; base < nw; base += 64) {
+                const int idx = base + lane;
+                if (idx < nw) {
+                    const int sl = (int)hdb_plane_div_u((uint32_t)idx, rcp_u), un = idx - sl * U;
+                    const uint32_t el = sel[wave][sl];
+                    const int64_t off = ((el >> 4) ? tl[1] : tl[0]) * (int64_t)npieces + (int64_t)((int)(el & 15u) * U + un);     // (a row below n: inside the plane)
+                    const uint32_t bw = a.pl_bit[off];
+                    const int4 x = qs[2 * un], y = qs[2 * un + 1];
+                    const int qw[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                    int s = 0;
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) s = __builtin_amdgcn_sdot4((int)((bw >> g) & 0x01010101u), qw[g], s, false);
+                    part1[idx] = s;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (live)
+                for (int i = 0; i < U; ++i) S1 += part1[slot * U + i];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();             // (the next step's stores stay behind these loads)
+        }
+        if (live) {
+            // (stage A: S is S4 and 8 (2 S4 + S1) - 124 sum c_q is the integer the one-stage decode forms)
+            const int S5 = STAGE_A ? 2 * S + S1 : S;
+            hi5 = hq_plane_hi((float)(8 * S5 - 124 * q_cs), q_cn * hdb_plane_rc_decode(rcode), kcode, tm.x, tm.y, tm.z, q_s, q_n, q_d, q_inv, cosine,
+                              a.bias != nullptr, bias);
         }
         if (DBG) {
             if (rvalid) a.dbg[row] = hi5;
             continue;
         }
-        const bool keep = !dead && !(hi5 < q_thr);
+        const bool keep = live && !(hi5 < q_thr);
         const unsigned long long km = __ballot(keep);
         if (km == 0ull) continue;                        // (wave-uniform)
         if (keep) queue[wave][qn + __popcll(km & ((1ull << lane) - 1ull))] = (uint32_t)row;
@@ -1139,23 +1224,27 @@ extern "C" int hdb_launch_quant_plane_rows(const int8_t* codes, const float* aux
                        t0, t1, n, d, P, U, nib, bitw, rec);
     return (int)hipGetLastError();
 }
-// dbg = false: pass 1 (candidates of the rows the plane keeps; the threshold as MODE 1 takes it, folded or a.thr); dbg = true: hi5 of every row -> a.dbg (tests)
+// dbg = 0: pass 1 (candidates of the rows the plane keeps; the threshold as MODE 1 takes it, folded or a.thr); dbg = 1: hi5 of every row -> a.dbg (tests);
+// dbg = 2: pass 1 without stage A, both planes read for every row (option use_plane = 2: the same candidates, for A/B runs)
 // blocks: the grid, from the plan (hdb_quant_plane_blocks; dbg: hdb_quant_plane_dbg_blocks).  Any count gives the same candidates --
 // only gridDim.x enters the kernel, as the walk's step and the list phase's stride.
 extern "C" int hdb_launch_quant_plane_scan(const QuantArgs* args, int dbg, int blocks, void* stream) {
     const QuantArgs& a = *args;
     const int U = a.pl_units;
+    if (dbg < 0 || dbg > 2) return (int)hipErrorInvalidValue;
+    const bool pass1 = dbg != 1;
     if (blocks < 1 || blocks > (1 << 22)) return (int)hipErrorInvalidValue;           // (blocks x 256 list slots per round fit 32 bits)
     if (a.nq != 1 || U < 1 || U > 16 || U != hdb_quant_plane_units(a.P) || (a.metric != HDB_DOT && a.metric != HDB_COSINE)) return (int)hipErrorInvalidValue;
-    if (!dbg && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
-    if (!dbg && (!a.cnt || !a.cand || !a.pl_cnt || !hq_copy_args_ok(a))) return (int)hipErrorInvalidValue;
+    if (pass1 && a.nsub != 0 && (a.nsub > HDB_QUANT_NSUB_MAX || !a.wmax || !a.thr_out)) return (int)hipErrorInvalidValue;
+    if (pass1 && (!a.cnt || !a.cand || !a.pl_cnt || !hq_copy_args_ok(a))) return (int)hipErrorInvalidValue;
     // the tiles the sample pass took are not walked (dbg: every tile is): its windows lie inside the matrix and its list is there
     if (a.ntiles < 0 || a.ntiles > 0x10000000) return (int)hipErrorInvalidValue;      // (a row number has 32 bits: hdb_pack)
-    if (!dbg && a.pl_s_tiles != 0u && (!a.pl_hi || a.pl_s_stride < 1u || (uint64_t)a.pl_s_tiles * a.pl_s_stride > (uint64_t)a.ntiles)) return (int)hipErrorInvalidValue;
+    if (pass1 && a.pl_s_tiles != 0u && (!a.pl_hi || a.pl_s_stride < 1u || (uint64_t)a.pl_s_tiles * a.pl_s_stride > (uint64_t)a.ntiles)) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)U * 32;
     hipStream_t st = (hipStream_t)stream;
     const int J = hdb_quant_plane_j(U);
-#define HQ_PLANE(J_) do { if (dbg) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, true>), dim3(blocks), dim3(256), lds, st, a); \
+#define HQ_PLANE(J_) do { if (dbg == 1) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, true>), dim3(blocks), dim3(256), lds, st, a); \
+                          else if (dbg == 2) hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, false, false>), dim3(blocks), dim3(256), lds, st, a); \
                           else hipLaunchKernelGGL((hdb_quant_plane_scan_kernel<J_, false>), dim3(blocks), dim3(256), lds, st, a); } while (0)
     if (J == 1) HQ_PLANE(1); else if (J == 2) HQ_PLANE(2); else if (J == 3) HQ_PLANE(3); else HQ_PLANE(4);
 #undef HQ_PLANE
