@@ -404,13 +404,22 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     per row: the sample pass, the filter pass, hdb_topk_exact and hdb_scores return the same float32 bits for a row, whatever
  *     the grid and the number of queries.  5+ queries run as four-query passes.
  *   - hamming / jaccard: the bit kernels that every dtype uses, on the sign cache (fused = 3 for 1-4 queries).
- *   - never: the matrix cores, the single launches of the float paths, the manhattan tile kernel, the int8 shadow and its plane
- *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit).
+ *   - on request (option b1_mfma_min_q, 0 = never by default): batches of 5+ dot / cosine / euclidean / pearson queries on whole
+ *     rows of 128 / 256 / 384 / 512 elements of a FINITE matrix go to the bf16 matrix cores (hdb_mfma_f4.h): one 16-byte load per MX
+ *     block, v_cvt_scalef32_pk_bf16_fp4 with the block scale into the A fragments, the query as three exact bf16 parts -- every
+ *     product exact, float32 accumulation, the 1e-5 contract without rescoring (euclidean re-scores near-duplicates from the widened
+ *     row; a query that equals a stored row finds it at rank 0).  b1_mfma_min_q = n >= 1: from max(n, 5, mfma_min_q) queries on;
+ *     -1 = never for MXFP4 (hdb_mfma_f4_min_q(d) is 0).  A matrix holding an overflowing block, other widths, manhattan, the bit
+ *     metrics, 1-4 queries and use_mfma = 0 keep the VALU scan and its bits.  The scores of the two paths differ inside the band.
+ *   - never: the single launches of the float paths, the manhattan tile kernel, the int8 shadow and its plane
+ *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit); the
+ *     matrix cores unless b1_mfma_min_q asks for them.
  *   Composite calls treat it as they treat HDB_B1: a first stage of hdb_two_stage_host, grouped, multi-vector and range calls are
  *   served; rerank onto it and the pair similarity of hdb_mmr return HDB_ERR_UNSUPPORTED.
- * Not built: the bf16 matrix cores for batches (v_cvt_scalef32_pk_bf16_fp4 into the float8 fragment path), the scaled fp4 MFMA (it
+ * Not built: K slices for rows wider than 512 elements and an LDS-expanded flavour of the matrix-core path, the scaled fp4 MFMA (it
  * would round the query), MXFP6 / MXFP8 / NVFP4, shadows and planes, row lists, several GPUs, rerank onto an MXFP4 index.
- * Stats: mfma = 0, quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics' single launch). */
+ * Stats: mfma = 0 (1 on the matrix-core path of b1_mfma_min_q), quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics'
+ * single launch); b1_mfma_min_q = the threshold in force for this index, 0 = never. */
 int hdb_topk(hdb_index* ix, const void* dev_Q, int32_t nq, int32_t k, int metric,
              int64_t* dev_idx, float* dev_score, int32_t* dev_status, void* stream);
 
@@ -752,8 +761,9 @@ void hdb_group_destroy(hdb_group* g);
  *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), f8_lds_min_q
  *   (float8 batches with the rows expanded to bf16 in LDS once per workgroup: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q)
  *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), b1_mfma_min_q
- *   (packed-bit batches on the bf16 matrix cores: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q) queries on; -1 =
- *   hdb_mfma_b1_min_q(d), 0 there = never), bits_max_q
+ *   (sub-byte rows on the bf16 matrix cores -- packed-bit batches, and MXFP4 batches on finite matrices of d = 128 / 256 / 384 / 512:
+ *   0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_b1_min_q(d), 0 there = never, and never
+ *   for MXFP4), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan),
  *   l1_packed (0: that tile kernel always subtracts in float32; default 1 = packed fp16 differences on fp16 rows while every query

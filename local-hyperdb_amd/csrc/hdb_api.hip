@@ -596,7 +596,7 @@ extern "C" int hdb_get_stat(hdb_index* ix, const char* name, int64_t* value) {
     for (const hdb_stat_entry& e : HDB_STATS) if (!strcmp(name, e.name)) { *value = ix->st.*e.member; return HDB_OK; }
     int rc = HDB_OK;
     if (!strcmp(name, "f8_lds_min_q")) *value = f8_lds_first_q(ix->opt, ix->dtype, ix->d);      // the threshold in force for this index, 0 = never
-    else if (!strcmp(name, "b1_mfma_min_q")) *value = b1_mfma_first_q(ix->opt, ix->dtype, ix->d);      // likewise, for a packed-bit index
+    else if (!strcmp(name, "b1_mfma_min_q")) *value = b1_mfma_first_q(ix->opt, ix->dtype, ix->d);      // likewise, for a packed-bit or an MXFP4 index
     else if (!strcmp(name, "host_direct")) *value = ix->st_host_direct;
     else if (!strcmp(name, "cand_cap")) *value = HDB_CAND_CAP;
     else if (!strcmp(name, "quant_auto")) *value = (ix->qmode == HDB_QUANT_I8 && ix->qauto) ? 1 : 0;

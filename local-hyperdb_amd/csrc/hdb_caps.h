@@ -267,6 +267,26 @@ static inline int hdb_mfma_b1_min_q(int d) {
     return d == 384 ? 8 : (d == 128 || d == 256 || d == 512 || d == 1024 || d == 4096) ? 5 : d == 768 ? 16 : 0;
 }
 
+// ---- hdb_mfma_f4*.hip: MXFP4 rows on the bf16 matrix pipe (hdb_mfma_f4.h; OPT-IN through the same b1_mfma_min_q, 0 = never by default) ----
+// Like the packed-bit rules these are no part of hdb_mfma_supported / hdb_mfma_tile_rows / hdb_mfma_batch_capacity, which keep
+// answering "no" for HDB_MXF4.  Whole rows of 128 / 256 / 384 / 512 elements -- whole groups of four MX blocks, one 16-byte load per
+// lane and group -- in 16-row tiles read straight from global memory; no K slices.
+static inline int hdb_mfma_f4_tile_rows(int d) { return (d == 128 || d == 256 || d == 384 || d == 512) ? 16 : 0; }
+// ... and the number of queries of a call from which an MXFP4 index takes the matrix cores when b1_mfma_min_q = -1; 0 = never, at
+// EVERY width: -1 is pinned as "never" for MXFP4 (tests/mxf4_plan_check.hip), so the path is reached with n >= 1 only.
+// For whoever moves it, the measured crossovers -- the smallest measured batch size from which the matrix cores beat the VALU scan's
+// four-query passes (hdb_f4scan.hip) by more than the repeated contender's spread at every larger measured size.  One box, one run,
+// the contenders alternating call by call, top-100 through rank_batch, p50 of 60 calls in us, matrix cores vs VALU scan on the same
+// handle at 5 / 8 / 16 / 64 / 128 queries, cosine; spread = the two p50s of the repeated matrix-core contender, at most 0.8 % except
+// 2M x 128 (1.4-10.5 %) (tools/time_f4_mfma.py -> profiles/f4_mfma_time.txt):
+//   10M x 384:   457 vs  2 057,   472 vs  2 424,   495 vs  4 746, 1 507 vs 18 417, 2 971 vs 36 562      -> 5 (4.5x; euclidean 488 vs 2 462: 5.0x)
+//    2M x 128:    85 vs    393,    92 vs    464,   101 vs    902,   215 vs  3 523,   360 vs  6 971      -> 5 (4.6x)
+//    2M x 256:   125 vs    405,   132 vs    478,   141 vs    934,   316 vs  3 655,   509 vs  7 246      -> 5 (3.2x)
+//    2M x 384:   147 vs    432,   151 vs    507,   172 vs    992,   387 vs  3 831,   717 vs  7 566      -> 5 (2.9x)
+//    2M x 512:   221 vs    457,   231 vs    531,   254 vs  1 032,   631 vs  3 962, 1 200 vs  7 808      -> 5 (2.1x)
+// No measured batch size loses; 5 is the smallest the plan offers.  Fewer queries were not measured on this path.
+static inline int hdb_mfma_f4_min_q(int d) { (void)d; return 0; }
+
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
 

@@ -91,6 +91,11 @@ HDB_GEOM_DECL(hdb_launch_mfma_scan_i8);                 // int8 rows: the float8
 HDB_GEOM_DECL(hdb_launch_mfma_scan_i8_wide);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_b1);                 // packed-bit rows: bits expanded to bf16 0.0 / 1.0 per fragment in registers (hdb_mfma_b1.h; opt-in, b1_mfma_min_q)
 HDB_GEOM_DECL(hdb_launch_mfma_scan_b1_wide);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f4);                 // MXFP4 rows: one 16-byte load per MX block, codes to bf16 with the block scale per fragment (hdb_mfma_f4.h; opt-in, b1_mfma_min_q)
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_wide);
+// hdb_launch_rescore_euclid's case for MXFP4 rows (hdb_mfma_f4.hip: the widening is the scan's)
+int hdb_launch_rescore_euclid_f4(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int d,
+                                 const float* Q, const float* qsq, int q0, const float* bias, void* stream);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f8_lds);             // float8 rows expanded to bf16 in LDS (hdb_mfma_f8_lds.h; ScanArgs::f8_lds = waves per workgroup); blocks: the most workgroups the launch may take
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f8_lds_wide);
 // the K-slice driver (hdb_mfma_ksplit.hip) and one slice of l->width elements (args: the slice's ks_* fields set)

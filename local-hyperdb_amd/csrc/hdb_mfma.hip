@@ -119,11 +119,13 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
         return pad <= 384 ? hdb_launch_mfma_anyd_c(args, &l) : hdb_launch_mfma_anyd_d(args, &l);
     }
     if (dtype == HDB_F32) return (a.f32_split > 0 && hdb_mfma_f32_split_min_q(a.d) > 0) ? hdb_launch_mfma_scan_f32s(args, &l) : hdb_launch_mfma_scan_f32(args, &l);
-    if (dtype == HDB_F8E4M3 || dtype == HDB_I8 || dtype == HDB_B1) {
-        // one-byte and packed-bit rows: the register kernels (hdb_mfma_f8.h; int8 with another row converter, hdb_mfma_i8.hip; packed
-        // bits when the plan asked, b1_mfma_min_q, hdb_mfma_b1.h) -- no LDS ring and 16-row tiles, a wave per tile, hdb_mfma_reg_blocks
+    if (dtype == HDB_F8E4M3 || dtype == HDB_I8 || dtype == HDB_B1 || dtype == HDB_MXF4) {
+        // one-byte and sub-byte rows: the register kernels (hdb_mfma_f8.h; int8 with another row converter, hdb_mfma_i8.hip; packed
+        // bits and MXFP4 when the plan asked, b1_mfma_min_q, hdb_mfma_b1.h / hdb_mfma_f4.h) -- no LDS ring and 16-row tiles, a wave per
+        // tile, hdb_mfma_reg_blocks
         if (mode == 2) return (int)hipErrorNotSupported;
         l.blocks = hdb_mfma_reg_blocks(a.ntiles, cus, max_blocks);
+        if (dtype == HDB_MXF4) return hdb_mfma_f4_tile_rows(a.d) > 0 ? hdb_launch_mfma_scan_f4(args, &l) : (int)hipErrorNotSupported;
         if (dtype == HDB_I8) return hdb_launch_mfma_scan_i8(args, &l);
         if (dtype == HDB_B1) return hdb_mfma_b1_ks_slices(a.d) > 0 ? hdb_launch_mfma_ksplit(args, dtype, &l) : hdb_launch_mfma_scan_b1(args, &l);
         // float8 with the rows expanded in LDS once per workgroup (the plan asked, f8_lds_min_q, hdb_mfma_f8_lds.h): a grid of stages,
@@ -162,6 +164,7 @@ static int launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, 
 extern "C" int hdb_launch_rescore_euclid(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V,
                                          int dtype, int d, const float* Q, const float* qsq, int q0, const float* bias, void* stream) {
     switch (dtype) {                    // (the dtypes of the matrix-core scan)
+        case HDB_MXF4: return hdb_launch_rescore_euclid_f4(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);      // (block rows: hdb_mfma_f4.hip)
         case HDB_B1: return launch_rescore_euclid<HdbB1Word>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
         case HDB_I8: return launch_rescore_euclid<hdb_i8>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);
         case HDB_F8E4M3: return launch_rescore_euclid<hdb_f8>(cand, cnt, cap, nq_launch, V, d, Q, qsq, q0, bias, stream);

@@ -29,7 +29,7 @@ struct hdb_options {
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
     int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
-    int64_t b1_mfma_min_q = 0;        // packed-bit batches on the bf16 matrix cores (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never)
+    int64_t b1_mfma_min_q = 0;        // sub-byte rows on the bf16 matrix cores -- packed-bit batches (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices) and MXFP4 batches (hdb_mfma_f4.h; d = 128 .. 512 whole, finite matrices): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never; MXFP4: hdb_mfma_f4_min_q(d), 0 at every width)
     int64_t bf16_quant = 0;           // bfloat16 matrices: hdb_index_quantize(HDB_QUANT_I8) builds an explicit int8 shadow (0, the default: the call is refused; opt-in).  Means nothing on other types; the plan does not read it
     int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
@@ -396,9 +396,12 @@ static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
 
 // The number of queries of a call from which a packed-bit index takes the matrix cores (b1_mfma_min_q; the stat of the same name):
 // the option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never (the default, and every width without a kernel)
+// (an MXFP4 index reads the same option -- "sub-byte rows on the bf16 matrix cores" -- for whole rows of 128 .. 512 elements,
+//  hdb_mfma_f4.h; its measured rule, hdb_mfma_f4_min_q, is 0 at every width: -1 means never there)
 static inline int64_t b1_mfma_first_q(const hdb_options& o, int dtype, int d) {
-    if (dtype != HDB_B1 || (hdb_mfma_b1_tile_rows(d) <= 0 && hdb_mfma_b1_ks_slices(d) <= 0)) return 0;
-    const int64_t rule = o.b1_mfma_min_q > 0 ? o.b1_mfma_min_q : o.b1_mfma_min_q < 0 ? (int64_t)hdb_mfma_b1_min_q(d) : 0;
+    const bool f4 = dtype == HDB_MXF4;
+    if (f4 ? hdb_mfma_f4_tile_rows(d) <= 0 : (dtype != HDB_B1 || (hdb_mfma_b1_tile_rows(d) <= 0 && hdb_mfma_b1_ks_slices(d) <= 0))) return 0;
+    const int64_t rule = o.b1_mfma_min_q > 0 ? o.b1_mfma_min_q : o.b1_mfma_min_q < 0 ? (int64_t)(f4 ? hdb_mfma_f4_min_q(d) : hdb_mfma_b1_min_q(d)) : 0;
     return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
 }
 
@@ -484,7 +487,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const int metric_mm = is_pearson ? (int)HDB_COSINE : metric;
     const bool f8ks_call = f8_ks_first > 0 && nq >= f8_ks_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
     // (packed-bit rows reach the matrix cores on request only as well, b1_mfma_min_q != 0 -- whole rows of up to 512 elements and the
-    //  K slices of wider ones, hdb_mfma_b1.h.  The matrix is always finite -- its flag word is never written -- so nothing is asked.)
+    //  K slices of wider ones, hdb_mfma_b1.h.  The matrix is always finite -- its flag word is never written -- so nothing is asked.
+    //  MXFP4 rows join through the same option, whole rows of up to 512 elements only, hdb_mfma_f4.h -- and only while finite, below.)
     const int64_t b1_first = b1_mfma_first_q(o, ix.dtype, ix.d);
     const bool b1_call = b1_first > 0 && nq >= b1_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
     bool mfma = o.use_mfma && !is_ham && !small && !tiny && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
@@ -497,7 +501,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // inf x 0 = NaN where np.dot gives inf, so a matrix that is not finite stays on the VALU scan
     // (float8 rows: a NaN code times a zero part is NaN where the VALU scan's NaN -> -inf ranking is the contract; same rule)
     // (int8 rows are always finite -- 512 x 128^2 is far from overflow -- and the flag their row norms leave says so: the same question, always yes)
-    if (mfma && (ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3 || ix.dtype == HDB_I8)) mfma = finite();
+    // (MXFP4 rows, when b1_mfma_min_q sent the call here: a block whose values overflow to inf would meet zero parts; same rule)
+    if (mfma && (ix.dtype == HDB_BF16 || ix.dtype == HDB_F8E4M3 || ix.dtype == HDB_I8 || ix.dtype == HDB_MXF4)) mfma = finite();
     // fp16 / float32 rows narrower than the geometry they ride (hdb_mfma_anyd.h): the chunks past the end of a row are chunk 0 of
     // the row again and meet zero query fragments -- an infinite element in a row's first 16 bytes gives inf x 0 = NaN there where
     // np.dot gives the infinity.  Same rule: a matrix that is not finite stays on the VALU scan.
