@@ -411,12 +411,18 @@ int hdb_scores(hdb_index* ix, const void* dev_q, int metric, float* dev_out, voi
  *     row; a query that equals a stored row finds it at rank 0).  b1_mfma_min_q = n >= 1: from max(n, 5, mfma_min_q) queries on;
  *     -1 = never for MXFP4 (hdb_mfma_f4_min_q(d) is 0).  A matrix holding an overflowing block, other widths, manhattan, the bit
  *     metrics, 1-4 queries and use_mfma = 0 keep the VALU scan and its bits.  The scores of the two paths differ inside the band.
+ *   - on request, two options together (b1_mfma_min_q = n >= 1 AND f8_ks_min_q != 0, the latter read on an MXFP4 index as "rows wider
+ *     than 512 elements of the opt-in matrix-core flavours"): the same calls on rows of d = S x W elements, a multiple of 128 in
+ *     640 .. 4096 except 1408 and the like (hdb_mfma_f4_wide_geom, hdb_caps.h), in ONE launch without a partial-sum workspace -- the
+ *     S = 2 .. 8 waves of a workgroup each take W elements of every row of a tile and add their accumulators through LDS in a fixed
+ *     order (hdb_mfma_f4_wide.h).  From max(5, mfma_min_q, b1_mfma_min_q, f8_ks_min_q) queries on; f8_ks_min_q = -1 reads
+ *     hdb_mfma_f4_wide_min_q(d).  Either option alone, and everything the whole rows leave to the VALU scan, keep the VALU scan.
  *   - never: the single launches of the float paths, the manhattan tile kernel, the int8 shadow and its plane
  *     (hdb_index_quantize returns HDB_ERR_UNSUPPORTED), the row list (a call with a list set is the masked call, bit for bit); the
  *     matrix cores unless b1_mfma_min_q asks for them.
  *   Composite calls treat it as they treat HDB_B1: a first stage of hdb_two_stage_host, grouped, multi-vector and range calls are
  *   served; rerank onto it and the pair similarity of hdb_mmr return HDB_ERR_UNSUPPORTED.
- * Not built: K slices for rows wider than 512 elements and an LDS-expanded flavour of the matrix-core path, the scaled fp4 MFMA (it
+ * Not built: an LDS-expanded flavour of the matrix-core path, a default rule for it, d = 1408 on the matrix cores, the scaled fp4 MFMA (it
  * would round the query), MXFP6 / MXFP8 / NVFP4, shadows and planes, row lists, several GPUs, rerank onto an MXFP4 index.
  * Stats: mfma = 0 (1 on the matrix-core path of b1_mfma_min_q), quant = 0, plane = 0, subset = 0, fused = 0 (3 for the bit metrics'
  * single launch); b1_mfma_min_q = the threshold in force for this index, 0 = never. */
@@ -758,12 +764,13 @@ void hdb_group_destroy(hdb_group* g);
  *   Dispatch of few-query calls (-1 = the measured rule): fused_max_q (the 1-4-query single launch takes
  *   calls of up to this many queries), f32_min_q (float32 matrices: the matrix-core scan from this many queries on), bf16_ks_min_q
  *   (bfloat16 rows wider than 512 elements: K slices from this many queries on, never fewer than 5), f8_ks_min_q (float8 rows wider
- *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d)), f8_lds_min_q
+ *   than 512 elements: 0 = never, the default; n >= 1 = K slices from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_f8_ks_min_q(d);
+ *   on an MXFP4 index, beside b1_mfma_min_q >= 1: != 0 opens rows wider than 512 elements, hdb_mfma_f4_wide.h, -1 = hdb_mfma_f4_wide_min_q(d)), f8_lds_min_q
  *   (float8 batches with the rows expanded to bf16 in LDS once per workgroup: 0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q)
  *   queries on; -1 = hdb_mfma_f8_lds_min_q(d), 0 there = never), f8_lds_waves (waves per workgroup of that flavour: 0 = by the launch's queries, the default; 4 | 8), b1_mfma_min_q
  *   (sub-byte rows on the bf16 matrix cores -- packed-bit batches, and MXFP4 batches on finite matrices of d = 128 / 256 / 384 / 512:
  *   0 = never, the default; n >= 1 = from max(n, 5, mfma_min_q) queries on; -1 = hdb_mfma_b1_min_q(d), 0 there = never, and never
- *   for MXFP4), bits_max_q
+ *   for MXFP4; MXFP4 rows of 640 .. 4096 elements need n >= 1 here AND f8_ks_min_q != 0), bits_max_q
  *   (hamming / jaccard: single launches of four queries up to this many queries, more through the six launches in one go);
  *   use_batch1 (0: never the batched single launch), use_l1_tile (0: manhattan batches stay with the 4-query scan),
  *   l1_packed (0: that tile kernel always subtracts in float32; default 1 = packed fp16 differences on fp16 rows while every query

@@ -286,6 +286,63 @@ static inline int hdb_mfma_f4_tile_rows(int d) { return (d == 128 || d == 256 ||
 //    2M x 512:   221 vs    457,   231 vs    531,   254 vs  1 032,   631 vs  3 962, 1 200 vs  7 808      -> 5 (2.1x)
 // No measured batch size loses; 5 is the smallest the plan offers.  Fewer queries were not measured on this path.
 static inline int hdb_mfma_f4_min_q(int d) { (void)d; return 0; }
+// Rows wider than 512 elements (hdb_mfma_f4_wide.h; OPT-IN through b1_mfma_min_q >= 1 TOGETHER WITH f8_ks_min_q != 0, plan_topk): no K
+// slices and no partial-sum workspace -- the S waves of one workgroup each take W elements of every row of a tile and add their
+// accumulators through LDS, in one launch.  -> {W, S} with d = S W, 2 <= S <= 8, d a multiple of 128 in 640 .. 4096; {0, 0} for
+// every other width (1408 = 11 x 128 among them), which keeps the VALU scan.  W is the first of 256, 384, 512, 128 that fits (256
+// balances the registers of a wave -- 96 of query parts, three waves per SIMD -- against the matrix instructions per barrier, 24),
+// except where a measurement moved it:
+//   256:  768 = 3 W, 1024 = 4 W, 1280 = 5 W, 1792 = 7 W                   384: 1152 = 3 W, 1536 = 4 W, 1920 = 5 W, 2304 = 6 W, 2688 = 7 W, 3072 = 8 W
+//   512: 2048 = 4 W, 2560 = 5 W, 3584 = 7 W, 4096 = 8 W                   128:  640 = 5 W,  896 = 7 W
+// Measured (tools/time_f4_wide.py, cosine top-100, p50 of 60 calls in us at 5 / 16 / 128 queries, runs of their own on one box, the
+// repeated contender at most 2.9 % apart):
+//   1M x 1536: 6 x 256 448 / 496 / 3 249, 4 x 384 311 / 349 / 2 099, 3 x 512 369 / 404 / 2 558     -> 4 x 384
+//   2M x 2048: 8 x 256 897 / 946 / 6 638, 4 x 512 740 / 773 / 5 347                                -> 4 x 512
+//   2M x 1024: 4 x 256 371 / 397 / 2 565, 2 x 512 386 / 402 / 2 817                                -> 4 x 256 (the first that fits)
+//   2M x  768: 3 x 256 283 / 319 / 2 117, 2 x 384 282 / 316 / 2 096                                -> 3 x 256 (inside the spread)
+// Four waves -- one per SIMD and workgroup -- won wherever they were a choice; the widths of five to eight waves were not compared.
+// (The geometry is no option: each run was made with this function edited by hand and the library rebuilt; the three runs are kept
+//  in profiles/f4_wide_geom_time.txt, the geometry of each named.)
+// Like the rules above these are no part of hdb_mfma_supported / hdb_mfma_tile_rows / hdb_mfma_ksplit_slices / hdb_mfma_batch_capacity.
+struct HdbF4WideGeom { int w, s; };
+static inline HdbF4WideGeom hdb_mfma_f4_wide_geom(int d) {
+    if (d < 640 || d > 4096 || d % 128 != 0) return {0, 0};
+    if (d == 1536) return {384, 4};
+    if (d == 2048) return {512, 4};
+    static const int ws[] = {256, 384, 512, 128};
+    for (int w : ws)
+        if (d % w == 0 && d / w >= 2 && d / w <= 8) return {w, d / w};
+    return {0, 0};
+}
+// workgroups of a launch over `ntiles` 16-row tiles: max_blocks when the caller set one, else as many as a CU holds at the
+// kernels' register counts (profiles/f4_wide_kernel_resources.txt: 4 / 3 / 2 / 2 waves per SIMD at W = 128 / 256 / 384 / 512, sixteen
+// SIMD-waves to a CU at most) -- the register kernels' rule (hdb_mfma_reg_blocks) with the workgroups of S waves counted.
+// The waves per SIMD are COPIED from that table, nothing ties them to the kernels: a compiler that moves a width across a register
+// boundary (W = 256 above 168 registers, W = 128 above 128) leaves this grid larger than what is resident -- still correct, the
+// workgroups then run one after the other -- and the table and these numbers want redoing together.  The counts per CU are argued from
+// the registers, not measured against other grids; in particular that ONE workgroup per CU is enough for S = 7 and 8 was not measured.
+static inline int hdb_mfma_f4_wide_blocks(int64_t ntiles, int cus, int max_blocks, int d) {
+    const HdbF4WideGeom g = hdb_mfma_f4_wide_geom(d);
+    if (g.s <= 0) return 0;
+    const int per_simd = g.w == 128 ? 4 : g.w == 256 ? 3 : 2;
+    const int per_cu = 4 * per_simd / g.s > 1 ? 4 * per_simd / g.s : 1;
+    return hdb_mfma_reg_blocks(ntiles, cus, max_blocks > 0 ? max_blocks : per_cu * cus);
+}
+// ... and the number of queries of a call from which such a width takes the matrix cores when f8_ks_min_q = -1 (b1_mfma_min_q >= 1
+// given): the smallest measured batch size from which the wide rows beat the VALU passes of the same handle (hdb_f4scan.hip: two
+// queries per pass up to d = 1024, one beyond) by more than the repeated contender's spread at every larger measured size.
+// Measured, one box, one run, the contenders alternating call by call, top-100 through rank_batch, p50 of 60 calls in us, wide rows vs
+// VALU passes at 5 / 8 / 16 / 64 / 128 queries, cosine; spread = the two p50s of the repeated wide-row contender, at most 3.0 %
+// (tools/time_f4_wide.py -> profiles/f4_wide_time.txt):
+//    2M x  768:   282 vs   787,   299 vs 1 098,   318 vs  2 146, 1 169 vs  8 375,  2 119 vs 16 670      -> 5 (2.8x; euclidean 267 vs 889: 3.3x)
+//    2M x 1024:   371 vs   896,   382 vs 1 229,   400 vs  2 315, 1 322 vs  9 064,  2 574 vs 18 041      -> 5 (2.4x)
+//    1M x 1536:   311 vs   804,   331 vs 1 239,   349 vs  2 416, 1 128 vs  9 368,  2 150 vs 18 677      -> 5 (2.6x)
+//    2M x 2048:   743 vs 2 016,   748 vs 3 004,   773 vs  5 963, 2 734 vs 23 421,  5 360 vs 46 557      -> 5 (2.7x)
+//  375k x 4096:   389 vs   727,   411 vs 1 089,   451 vs  2 086, 1 423 vs  8 130,  2 705 vs 16 136      -> 5 (1.9x)
+//   10M x 1024: 1 518 vs 4 260, 1 504 vs 5 726, 1 559 vs 11 253, 5 951 vs 44 273, 11 505 vs 88 230      -> 5 (2.8x)
+// No measured batch size loses to the VALU passes; 5 is the smallest the plan offers, and the widths between were not measured.
+// (What does lose, at 64 / 128 queries, is the comparison with OTHER indices: README, "Where it loses".)
+static inline int hdb_mfma_f4_wide_min_q(int d) { (void)d; return 5; }
 
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }

@@ -125,6 +125,10 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
         // tile, hdb_mfma_reg_blocks
         if (mode == 2) return (int)hipErrorNotSupported;
         l.blocks = hdb_mfma_reg_blocks(a.ntiles, cus, max_blocks);
+        if (dtype == HDB_MXF4 && hdb_mfma_f4_wide_geom(a.d).s > 0) {       // wider than 512 elements: S waves per tile, workgroups of their own size
+            l.blocks = hdb_mfma_f4_wide_blocks(a.ntiles, cus, max_blocks, a.d);
+            return hdb_launch_mfma_scan_f4_wide_rows(args, &l);
+        }
         if (dtype == HDB_MXF4) return hdb_mfma_f4_tile_rows(a.d) > 0 ? hdb_launch_mfma_scan_f4(args, &l) : (int)hipErrorNotSupported;
         if (dtype == HDB_I8) return hdb_launch_mfma_scan_i8(args, &l);
         if (dtype == HDB_B1) return hdb_mfma_b1_ks_slices(a.d) > 0 ? hdb_launch_mfma_ksplit(args, dtype, &l) : hdb_launch_mfma_scan_b1(args, &l);

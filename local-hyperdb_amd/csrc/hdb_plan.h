@@ -27,9 +27,9 @@ struct hdb_options {
     int64_t f32_split = 1;            // ... as bf16 parts (hdb_mfma_f32s.hip) where that flavour exists, the matrix is finite and the call has at least
     int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
-    int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d)
+    int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d).  On an MXFP4 index it is read as "rows wider than 512 elements of the opt-in matrix-core flavours": with b1_mfma_min_q >= 1 beside it, != 0 opens the wide rows (hdb_mfma_f4_wide.h; -1 = hdb_mfma_f4_wide_min_q(d))
     int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
-    int64_t b1_mfma_min_q = 0;        // sub-byte rows on the bf16 matrix cores -- packed-bit batches (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices) and MXFP4 batches (hdb_mfma_f4.h; d = 128 .. 512 whole, finite matrices): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never; MXFP4: hdb_mfma_f4_min_q(d), 0 at every width)
+    int64_t b1_mfma_min_q = 0;        // sub-byte rows on the bf16 matrix cores -- packed-bit batches (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices) and MXFP4 batches (hdb_mfma_f4.h; d = 128 .. 512 whole, finite matrices; 640 .. 4096 split over the waves of a workgroup, hdb_mfma_f4_wide.h, only with n >= 1 here AND f8_ks_min_q != 0): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never; MXFP4: hdb_mfma_f4_min_q(d), 0 at every width)
     int64_t bf16_quant = 0;           // bfloat16 matrices: hdb_index_quantize(HDB_QUANT_I8) builds an explicit int8 shadow (0, the default: the call is refused; opt-in).  Means nothing on other types; the plan does not read it
     int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
     int64_t bits_max_q = -1;          // hamming / jaccard: the single launch (four queries at a time) up to this many queries
@@ -398,8 +398,16 @@ static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
 // the option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never (the default, and every width without a kernel)
 // (an MXFP4 index reads the same option -- "sub-byte rows on the bf16 matrix cores" -- for whole rows of 128 .. 512 elements,
 //  hdb_mfma_f4.h; its measured rule, hdb_mfma_f4_min_q, is 0 at every width: -1 means never there)
+// (MXFP4 rows WIDER than 512 elements, hdb_mfma_f4_wide.h, take two options together: b1_mfma_min_q >= 1 asks for sub-byte rows on the
+//  matrix cores and f8_ks_min_q != 0 for "rows wider than 512 elements of the opt-in matrix-core flavours" -- n >= 1 there raises
+//  the threshold to n, -1 reads hdb_mfma_f4_wide_min_q(d).  Either option alone leaves such a width on the VALU scan.)
 static inline int64_t b1_mfma_first_q(const hdb_options& o, int dtype, int d) {
     const bool f4 = dtype == HDB_MXF4;
+    if (f4 && hdb_mfma_f4_wide_geom(d).s > 0) {
+        if (o.b1_mfma_min_q < 1 || o.f8_ks_min_q == 0) return 0;
+        const int64_t wide = o.f8_ks_min_q > 0 ? o.f8_ks_min_q : (int64_t)hdb_mfma_f4_wide_min_q(d);
+        return std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), o.b1_mfma_min_q), wide);
+    }
     if (f4 ? hdb_mfma_f4_tile_rows(d) <= 0 : (dtype != HDB_B1 || (hdb_mfma_b1_tile_rows(d) <= 0 && hdb_mfma_b1_ks_slices(d) <= 0))) return 0;
     const int64_t rule = o.b1_mfma_min_q > 0 ? o.b1_mfma_min_q : o.b1_mfma_min_q < 0 ? (int64_t)(f4 ? hdb_mfma_f4_min_q(d) : hdb_mfma_b1_min_q(d)) : 0;
     return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
@@ -488,7 +496,8 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     const bool f8ks_call = f8_ks_first > 0 && nq >= f8_ks_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
     // (packed-bit rows reach the matrix cores on request only as well, b1_mfma_min_q != 0 -- whole rows of up to 512 elements and the
     //  K slices of wider ones, hdb_mfma_b1.h.  The matrix is always finite -- its flag word is never written -- so nothing is asked.
-    //  MXFP4 rows join through the same option, whole rows of up to 512 elements only, hdb_mfma_f4.h -- and only while finite, below.)
+    //  MXFP4 rows join through the same option -- whole rows of up to 512 elements, hdb_mfma_f4.h, and, with f8_ks_min_q != 0 beside
+    //  it, wider rows split over the waves of a workgroup, hdb_mfma_f4_wide.h -- and only while finite, below.)
     const int64_t b1_first = b1_mfma_first_q(o, ix.dtype, ix.d);
     const bool b1_call = b1_first > 0 && nq >= b1_first && (metric_mm == HDB_DOT || metric_mm == HDB_COSINE || metric_mm == HDB_EUCLIDEAN);
     bool mfma = o.use_mfma && !is_ham && !small && !tiny && ((nq >= min_q && hdb_mfma_supported(ix.dtype, ix.d, metric_mm)) || f8ks_call || b1_call);
@@ -511,7 +520,7 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // fp16 matrix reads the shadow instead and rescoring returns the matrix cores' bits (quant_topk, mflavour).  The index builds
     // the shadow on its first such call (build_needed); an explicit shadow (hdb_index_quantize) keeps its own rule and the VALU bits above.
     const bool f8ks = mfma && f8ks_call;
-    const bool b1mm = mfma && b1_call, b1ks = b1mm && hdb_mfma_b1_ks_slices(ix.d) > 0;
+    const bool b1mm = mfma && b1_call, b1ks = b1mm && ix.dtype == HDB_B1 && hdb_mfma_b1_ks_slices(ix.d) > 0;      // (wide MXFP4 rows: one launch, no slices)
     const bool auto_q = auto_quant_call(ix, o, c, mfma, exact, small);
     if (auto_q && nq >= 1 && nq <= 4 &&
         // (rows wider than 512 elements join only on request: their bounds pass too many candidates on large matrices, see quant_sample_target)
