@@ -538,25 +538,30 @@ static_assert(hdb_quant_plane_wg_per_cu(1) >= 1 && hdb_quant_plane_wg_per_cu(1) 
               hdb_quant_plane_wg_per_cu(3) >= 1 && hdb_quant_plane_wg_per_cu(3) <= hdb_quant_plane_waves(3) &&
               hdb_quant_plane_wg_per_cu(4) >= 1 && hdb_quant_plane_wg_per_cu(4) <= hdb_quant_plane_waves(4),
               "a default grid of the plane pass asks for more waves per SIMD than its kernel is compiled for");
-// Stage A (hdb_quant.hip, "Stage A": the bit words are read for the rows the nibbles cannot reject) adds a dependent round trip to
-// every step, so it wants more waves than the one-stage pass and pays only where the stream is long.  Measured with
-// tools/time_plane_stage.py (one handle, the two passes alternating call by call, p50 of a call in us), stage A at its best grid /
-// the one-stage pass at its table grid, run 1 and run 2 (profiles/plane_bit_time.txt):
-//   J = 3 (d = 384), 5 or 6: 5M 275.5 / 278.3 and 279.0 / 280.6, 6M 312.1 / 320.9 and 315.2 / 317.9, 7M 360.5 / 365.2 and 357.6 /
-//     364.5, 8M 385.1 / 396.3 and 380.6 / 396.8, 10M 450.3 / 469.5 and 444.9 / 469.6; a loss at 2M at every grid.  A win of 1 %
-//     at 5M .. 7M, of 3 .. 5 % from 8M on                                                                        -> from 8M rows, grid 5
-//   J = 2 (d = 256), 7: 2M a loss, 5M 210.6 / 211.8 and 206.9 / 210.1, 8M 281.2 / 297.8 and 278.0 / 294.9, 10M 328.5 / 347.7 and
-//     322.3 / 344.1 (6 is behind 7 at 5M .. 10M in both runs)                                                    -> from 8M rows, grid 7
-//   J = 4 (d = 512), 5: 5M 353.6 / 356.5 and 356.5 / 351.0, 8M 526.1 / 524.8 and 522.5 / 521.3, 10M 600.7 / 616.3 and 594.2 / 610.4:
-//     a win in both runs at 10M only                                                                             -> not by default
-//   J = 1 (d = 128): a loss at 2M and 8M at every grid (one run)                                                 -> not by default
-// HDB_PLANE_A_WAVES: what the compiler gives <J, false> with stage A (profiles/plane_bit_kernel_resources.txt).
+// Stage A (hdb_quant.hip, "Stage A": the bit words are read for the rows the nibbles cannot reject) puts the rows it keeps in a
+// wave-private queue and reads their bit words 16 rows at a time: one dependent round trip in about four steps, where it was one a
+// step, and the occupancy of the one-stage pass or better.  With that it no longer wants more waves than the one-stage pass, and it
+// pays from 5M rows at three of the four widths.  Measured with tools/time_plane_stage.py (one handle, the two passes alternating
+// call by call, p50 of a call in us), stage A at the grid named / the one-stage pass at its table grid, run 1 and run 2
+// (profiles/plane_queue_time.txt; every grid and size is there):
+//   J = 3 (d = 384), 4: 2M 161.8 / 161.1 and 167.6 / 166.5 (a loss), 2.5M 179.4 / 180.3 and 184.1 / 184.5 (inside the spread), 5M
+//     271.6 / 279.1 and 276.6 / 285.5, 8M 375.8 / 394.4 and 380.4 / 398.2, 10M 441.3 / 467.8 and 446.2 / 474.3.  4 is ahead of 5 in
+//     both runs at 5M, 8M and 10M (10M: 447.4 and 452.0 with 5); 3 is level with 4 at 10M and behind it below       -> from 5M rows, grid 4
+//   J = 2 (d = 256), 4: 2M 130.6 / 132.4 and 132.4 / 132.7 (inside the spread), 5M 199.9 / 210.8 and 201.5 / 211.9, 8M 273.2 / 294.9
+//     and 274.1 / 296.3, 10M 311.5 / 344.5 and 313.6 / 347.0; 4 is ahead of 6 and 7 in both runs at 5M .. 10M (10M: 317.8 and 319.7
+//     with 7), 8 loses everywhere                                                                                    -> from 5M rows, grid 4
+//   J = 1 (d = 128), 7: 2M 109.1 / 110.7 and 111.9 / 113.1, 5M 152.2 / 166.9 and 155.1 / 169.6, 10M 220.6 / 258.5 and 223.6 / 261.5
+//     (the one-stage pass at ITS best grid, 7, not its table's: 5M 156.9 and 159.9, 10M 232.2 and 234.8)              -> from 5M rows, grid 7
+//   J = 4 (d = 512), 4: 2M a loss, 5M 348.4 / 348.8 and 353.1 / 354.4 (inside the spread), 10M 603.6 / 619.5 and 606.9 / 626.4; 8M
+//     was not measured (its list overflows at this seed): a win of 2.5 .. 3 % at 10M only                            -> not by default
+// HDB_PLANE_A_WAVES: what the compiler gives <J, false> with stage A (profiles/plane_queue_kernel_resources.txt).
 // HDB_PLANE_A_WG_PER_CU: the grid of a pass with stage A; HDB_PLANE_A_DEFAULT: the J at which use_plane = 1 takes it, from
-// HDB_PLANE_A_MIN_ROWS rows on.  use_plane = 2 never takes it, use_plane = 3 always (tests, A/B runs).
-#define HDB_PLANE_A_MIN_ROWS 8000000
-#define HDB_PLANE_A_WAVES {7, 7, 6, 5}
-#define HDB_PLANE_A_WG_PER_CU {4, 7, 5, 5}
-#define HDB_PLANE_A_DEFAULT {0, 1, 1, 0}
+// HDB_PLANE_A_MIN_ROWS rows on (never below 2M, the smallest size timed).  use_plane = 2 never takes it, use_plane = 3 always (tests,
+// A/B runs).
+#define HDB_PLANE_A_MIN_ROWS 5000000
+#define HDB_PLANE_A_WAVES {8, 8, 7, 6}
+#define HDB_PLANE_A_WG_PER_CU {7, 4, 4, 4}
+#define HDB_PLANE_A_DEFAULT {1, 1, 1, 0}
 static constexpr int hdb_quant_plane_a_waves(int J) { constexpr int t[4] = HDB_PLANE_A_WAVES; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
 static constexpr int hdb_quant_plane_a_wg_per_cu(int J) { constexpr int t[4] = HDB_PLANE_A_WG_PER_CU; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1]; }
 static constexpr bool hdb_quant_plane_a_default(int J) { constexpr int t[4] = HDB_PLANE_A_DEFAULT; return t[J < 1 ? 0 : J > 4 ? 3 : J - 1] != 0; }
@@ -688,10 +693,30 @@ __host__ __device__ __forceinline__ void hdb_plane_interval(float fc, float Uf, 
     ch = ch + (fabsf(ch) * 0x1p-20f + 1.f);
     cl = cl - (fabsf(cl) * 0x1p-20f + 1.f);
 }
-// Stage B numbers the bit words of the rows it keeps idx = slot U + unit, idx < 32 U <= 512: slot = idx / U as one multiply (the
-// reciprocal errs by less than U / 2^16 per unit of idx, 512 x 16 < 2^16; tests/plane_bit_check.hip divides every pair)
+// idx = slot U + unit, idx < 32 U <= 512: slot = idx / U as one multiply (the reciprocal errs by less than U / 2^16 per unit of
+// idx, 512 x 16 < 2^16; tests/plane_bit_check.hip divides every pair).  Stage B numbered its bit words so while it ran inside every
+// step; the pass now takes them 16 rows at a time with the map below and divides nowhere in the stream.
 __host__ __device__ __forceinline__ uint32_t hdb_plane_rcp_u(uint32_t U) { return (65536u + U - 1u) / U; }
 __host__ __device__ __forceinline__ uint32_t hdb_plane_div_u(uint32_t idx, uint32_t rcp_u) { return (idx * rcp_u) >> 16; }
+// Piece f of a 16-row tile is of row (slot) f / U, unit f % U: a lane of the plane pass forms this once per piece it takes, f =
+// lane + 64 j, and keeps it in one register -- 2 unit (where the unit's eight query words lie in qs, in 16-byte words) in the low
+// byte, the slot above it; a piece past 16 U is of slot 16, no row.  The stream uses the query offset; stage B takes 16 pending
+// rows as one virtual tile of bit words with the same map, word f of pending row `slot` at pl_bit[row U + unit]
+// (tests/plane_queue_check.hip checks every pair against plain division).
+#define HDB_PLANE_VT_ROWS 16
+__host__ __device__ __forceinline__ uint32_t hdb_plane_vt_map(uint32_t f, uint32_t U) {
+    return f < HDB_PLANE_VT_ROWS * U ? (2u * (f % U)) | ((f / U) << 8) : (uint32_t)HDB_PLANE_VT_ROWS << 8;
+}
+__host__ __device__ __forceinline__ uint32_t hdb_plane_vt_qoff(uint32_t map) { return map & 0xFFu; }
+__host__ __device__ __forceinline__ uint32_t hdb_plane_vt_slot(uint32_t map) { return map >> 8; }
+__host__ __device__ __forceinline__ int64_t hdb_plane_vt_word(int64_t row, uint32_t map, uint32_t U) {
+    return row * (int64_t)U + (int64_t)(hdb_plane_vt_qoff(map) >> 1);
+}
+// Stage A's pending rows: an entry carries what hi5 needs beside the bit words, so the flush reads neither the hot block nor the
+// bias again (a re-read that missed L2 would fetch a 128-byte line per kept row).  32 bytes, two 16-byte LDS words:
+// {row, S4, k_hi code | rc << 16, E*} {T*, F*, bias, 0}.
+struct HdbPlanePending { uint32_t row; int32_t s4; uint32_t krc; float e_s, t_s, f_s, bias; uint32_t pad; };
+static_assert(sizeof(HdbPlanePending) == 32, "a pending row of the plane pass is two 16-byte LDS words");
 
 // ---- hdb_quant_mfma.hip: batches through the shadow on the int8 matrix cores ----
 // widths the int8 matrix-core filter and the block-diagonal rescoring take: whole 64-byte k-steps and a geometry of the fp16 scan

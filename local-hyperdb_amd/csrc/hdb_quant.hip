@@ -810,11 +810,16 @@ __global__ __launch_bounds__(256) void hdb_quant_plane_rows_kernel(const int8_t*
 //  QuantArgs stays the first parameter: hq_args_in_memory.  The empty asm statements here and in the drain only steer the register
 //  allocator; the figures they buy are in profiles/quant_inpass_kernel_resources.txt with the compiler they were taken with.)
 // STAGE_A (the default of the stream; header, "Stage A"): a step streams the nibbles only and bounds every row from them, hi4 >= hi5's
-// own target hi.  The rows with !(hi4 < T_s) -- about one in eight -- are compacted by ballot and popcount (sel: the epilogue lane of
-// slot p), and their U bit words are loaded one word per lane, word idx = p U + unit in rounds of 64, multiplied against the eight
-// query words of the unit and left in part[wave] (flat: 32 U <= 128 J words) for the row's lane to add: S = 2 S4 + S1 is the sum the
-// one-stage decode forms, and hi5 comes from the one expression (hq_plane_hi).  Without STAGE_A (use_plane = 2, and the debug
-// flavour) both planes are read for every row.
+// own target hi.  The rows with !(hi4 < T_s) -- about one in eight -- are appended by ballot and popcount to a second wave-private
+// queue, pend (HdbPlanePending, hdb_caps.h: the row with S4, its codes, the tile's terms and its bias, 32 bytes, so that stage B
+// reads neither the hot block nor the bias again).  While 16 or more are pending the wave takes the top 16 as one VIRTUAL TILE of bit
+// words (flush): 16 rows x U words is the shape of a nibble tile, lane l takes words l + 64 j of pending row (l + 64 j) / U, unit
+// (l + 64 j) % U -- the map qoff[j] already holds (hdb_plane_vt_map) -- issues its J loads together, multiplies each against the eight
+// query words of its unit and leaves the sums in part[wave][0] for the row's lane to add: S = 2 S4 + S1 is the sum the one-stage
+// decode forms, and hi5 comes from the one expression (hq_plane_hi) with the entry's terms.  One dependent round trip for 16 kept
+// rows, about one in four steps, where reading them inside the step took one per step; nothing of stage B is live across the
+// stream's loads.  A step appends at most 32 to fewer than 16: 48 entries; what is pending after the walk goes as a ragged tile,
+// ahead of the sampled rows' list.  Without STAGE_A (use_plane = 2, and the debug flavour) both planes are read for every row.
 #define HQ_PL_QUEUE 48
 // The coarse upper bound of a row from an interval of fl(C): fc the float of the integer centre (C5 or C4), Uf >= the Cauchy-Schwarz
 // half-width N_c R (header, (4) and "Stage A").  Everything behind ch >= fl(C) >= cl is the same for both stages.
@@ -850,7 +855,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
     __shared__ int part[4][2][64 * J];
     __shared__ HqStage stage;
     __shared__ uint32_t queue[4][HQ_PL_QUEUE];
-    __shared__ uint32_t sel[STAGE_A ? 4 : 1][32];
+    __shared__ __attribute__((aligned(16))) HdbPlanePending pend[STAGE_A ? 4 : 1][STAGE_A ? HQ_PL_QUEUE : 1];      // (stage A: rows whose bit words are due)
     __shared__ uint32_t surv_cnt;
     const int U = a.pl_units, nch = a.P >> 4;
     if (threadIdx.x < 4) stage.cnt[threadIdx.x] = 0u;
@@ -870,19 +875,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (the tile number stays scalar)
     const int npieces = 16 * U;
     // where the query words of piece lane + 64 j lie in qs: the decode reads them there, piece by piece, and holds one offset per j
+    // (stage A: the offset with the piece's slot above it, hdb_plane_vt_map -- stage B's flush takes its bit words by the same map)
     int qoff[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const int f = lane + 64 * j;
-        qoff[j] = f < npieces ? 2 * (f % U) : 0;
+        qoff[j] = STAGE_A ? (int)hdb_plane_vt_map((uint32_t)f, (uint32_t)U) : f < npieces ? 2 * (f % U) : 0;
     }
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x3 __attribute__((ext_vector_type(3)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t rcp_u = hdb_plane_rcp_u((uint32_t)U);               // (stage B: slot and unit of a bit word, without a division)
     const int64_t ntiles = a.ntiles;
     const int et = lane >> 4, er = lane & 15;                       // epilogue lanes 0-31: tile et of the pair, row er
     int qn = 0;                                                     // rows in this wave's queue (wave-uniform)
+    int pn = 0;                                                     // stage A: rows pending in pend[wave] (wave-uniform)
     uint32_t nsurv = 0u;                                            // rows this wave kept (wave-uniform)
     // `m` queued rows from entry `base` on as one MODE 1 tile (m <= 16)
     auto drain = [&](int base, int m) {
@@ -900,6 +906,72 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         hq_rows4_bounds<1, 0, 1>(a, qs, qc, rr, l16, row, [&](int, float, float hi, bool masked) {     // (one piece in flight: few registers)
             if (!masked && !q_bad && hi >= q_thr) hq_emit(stage, 0, hi, row);
         });
+    };
+    // Stage B: `m` pending rows from entry `base` on as one virtual tile of bit words (m <= 16; word f = lane + 64 j is of pending row
+    // f / U, unit f % U, the map of a nibble tile).  All J loads of a lane are issued together -- one round trip for 16 rows, where a
+    // step's own kept rows took one per step -- and decoded into part[wave][0]; lane s < m adds the U sums of entry base + s and
+    // evaluates hi5 from the entry's terms; a keeper goes to the survivor queue, and the drain fires as in the one-stage pass.
+    // (Called between steps only: the step's reads of part[wave] are behind a wave barrier, and nothing of the stream is live.)
+    auto flush = [&](int base, int m) {
+        if constexpr (STAGE_A) {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));                 // (as in the drain: nothing of the flush is formed ahead of the loop and held through the stream)
+            uint32_t bw[J], vm[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                vm[j] = (uint32_t)qoff[j];
+                asm volatile("" : "+v"(vm[j]));          // (slot and unit are taken apart here, from the one register a piece keeps)
+                const int sl = (int)hdb_plane_vt_slot(vm[j]);
+                bw[j] = 0u;                              // (no row: a zero word adds nothing)
+                if (sl < m)                              // (a row below n: inside the plane)
+                    bw[j] = a.pl_bit[hdb_plane_vt_word((int64_t)pend[wave][base + sl].row, vm[j], (uint32_t)U)];
+            }
+            __builtin_amdgcn_sched_barrier(0);           // loads ahead of every use
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const int qo = (int)hdb_plane_vt_qoff(vm[j]);
+                const int4 x = qs[qo], y = qs[qo + 1];
+                const int qw[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                int s = 0;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) s = __builtin_amdgcn_sdot4((int)((bw[j] >> g) & 0x01010101u), qw[g], s, false);
+                part[wave][0][ln + 64 * j] = s;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            bool keep = false;
+            uint32_t row = 0u;
+            if (ln < m) {
+                const uint4 e0 = reinterpret_cast<const uint4*>(&pend[wave][base + ln])[0];
+                const uint4 e1 = reinterpret_cast<const uint4*>(&pend[wave][base + ln])[1];
+                int S1 = 0;
+                for (int i = 0; i < U; ++i) S1 += part[wave][0][ln * U + i];
+                // (S4 from the entry: 8 (2 S4 + S1) - 124 sum c_q is the integer the one-stage decode forms)
+                const int S5 = 2 * (int)e0.y + S1;
+                const float hi5 = hq_plane_hi((float)(8 * S5 - 124 * q_cs), q_cn * hdb_plane_rc_decode(e0.z >> 16), e0.z & 0xFFFFu, hdb_plane_bits_f(e0.w),
+                                              hdb_plane_bits_f(e1.x), hdb_plane_bits_f(e1.y), q_s, q_n, q_d, q_inv, cosine, a.bias != nullptr,
+                                              hdb_plane_bits_f(e1.z));
+                keep = !(hi5 < q_thr);                   // (a NaN never drops)
+                row = e0.x;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();             // (the next stores to part and pend stay behind these loads)
+            const uint32_t km = (uint32_t)__ballot(keep);                         // (lanes 0-15)
+            if (km == 0u) return;                        // (wave-uniform)
+            if (keep) queue[wave][qn + __popc(km & ((1u << (ln & 31)) - 1u))] = row;
+            const int nk = __popc(km);
+            qn += nk; nsurv += (uint32_t)nk;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (qn >= 16) {
+                qn -= 16; drain(qn, 16);                 // (fewer than 16 were queued and at most 16 came)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();         // (the next append stays behind the drain's loads)
+            }
+        }
     };
 
     // The walk: position tp of the tiles the sample pass did not take (hdb_caps.h; DBG, or no list: every tile), two positions per
@@ -970,7 +1042,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         // nothing but themselves: the barrier keeps the words of the next j from being read, and held, ahead of their piece)
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            const int4 x = qs[qoff[j]], y = qs[qoff[j] + 1];
+            int qo = qoff[j];
+            if constexpr (STAGE_A) {
+                asm volatile("" : "+v"(qo));             // (the offset is masked out where it is used, not once ahead of the loop)
+                qo = (int)hdb_plane_vt_qoff((uint32_t)qo);
+            }
+            const int4 x = qs[qo], y = qs[qo + 1];
             const int qw[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
@@ -999,9 +1076,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         __builtin_amdgcn_wave_barrier();                 // (the next step's stores stay behind these loads)
         float hi5 = -INFINITY;
         const bool dead = !rvalid || masked || q_bad;
-        bool live = !dead;                               // (stage A: the rows whose bit words are read)
-        int S1 = 0;
+        bool live = !dead;
         if constexpr (STAGE_A) {
+            // the rows the four-bit bound keeps wait in pend[wave] with their terms; stage B takes them 16 at a time
             if (live) {
                 const float hi4 = hq_plane_hi((float)(16 * S - 120 * q_cs), q_cn * r4s, kcode, tm.x, tm.y, tm.z, q_s, q_n, q_d, q_inv, cosine,
                                               a.bias != nullptr, bias);
@@ -1009,42 +1086,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
             }
             const uint32_t k4 = (uint32_t)__ballot(live);                        // (epilogue lanes 0-31)
             if (k4 == 0u) continue;                      // (wave-uniform)
-            const int slot = __popc(k4 & ((1u << (lane & 31)) - 1u));
-            if (live) sel[wave][slot] = (uint32_t)lane;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // stage B: bit word idx = slot U + unit of the kept rows, one per lane, against the eight query words of its unit
-            int* part1 = &part[wave][0][0];              // (32 U <= 128 J words; the S4 reads are behind the barrier above)
-            const int nw = __popc(k4) * U;               // (at most 32 U)
-#pragma unroll 1
-            for (int base = 0; base < nw; base += 64) {
-                const int idx = base + lane;
-                if (idx < nw) {
-                    const int sl = (int)hdb_plane_div_u((uint32_t)idx, rcp_u), un = idx - sl * U;
-                    const uint32_t el = sel[wave][sl];
-                    const int64_t off = ((el >> 4) ? tl[1] : tl[0]) * (int64_t)npieces + (int64_t)((int)(el & 15u) * U + un);     // (a row below n: inside the plane)
-                    const uint32_t bw = a.pl_bit[off];
-                    const int4 x = qs[2 * un], y = qs[2 * un + 1];
-                    const int qw[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-                    int s = 0;
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) s = __builtin_amdgcn_sdot4((int)((bw >> g) & 0x01010101u), qw[g], s, false);
-                    part1[idx] = s;
-                }
+            if (live) {
+                uint4* e = reinterpret_cast<uint4*>(&pend[wave][pn + __popc(k4 & ((1u << (ln & 31)) - 1u))]);
+                e[0] = make_uint4((uint32_t)row, (uint32_t)S, kcode | (rcode << 16), hdb_plane_f_bits(tm.x));
+                e[1] = make_uint4(hdb_plane_f_bits(tm.y), hdb_plane_f_bits(tm.z), hdb_plane_f_bits(bias), 0u);
             }
+            pn += __popc(k4);                            // (at most 32 to fewer than 16)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (live)
-                for (int i = 0; i < U; ++i) S1 += part1[slot * U + i];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();             // (the next step's stores stay behind these loads)
+            while (pn >= 16) { pn -= 16; flush(pn, 16); }
+            continue;
         }
         if (live) {
-            // (stage A: S is S4 and 8 (2 S4 + S1) - 124 sum c_q is the integer the one-stage decode forms)
-            const int S5 = STAGE_A ? 2 * S + S1 : S;
-            hi5 = hq_plane_hi((float)(8 * S5 - 124 * q_cs), q_cn * hdb_plane_rc_decode(rcode), kcode, tm.x, tm.y, tm.z, q_s, q_n, q_d, q_inv, cosine,
+            hi5 = hq_plane_hi((float)(8 * S - 124 * q_cs), q_cn * hdb_plane_rc_decode(rcode), kcode, tm.x, tm.y, tm.z, q_s, q_n, q_d, q_inv, cosine,
                               a.bias != nullptr, bias);
         }
         if (DBG) {
@@ -1067,6 +1122,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void hdb_
         }
     }
     if (!DBG) {
+        if (STAGE_A && pn > 0) { flush(0, pn); pn = 0; }                                 // what is pending, as a ragged tile
         // The sampled rows: their upper bounds are in the list the sample pass left, slot 16 w + r for row r of window w's tile.  A wave
         // loads 64 slots at a time (the next 64 in flight behind them) and appends the rows with !(hi < T_s) half by half -- at most 32 to
         // fewer than 16, as a step of the stream does -- and drains as the stream does.  hi is MODE 1's own (hq_rows4_bounds, same
