@@ -1194,7 +1194,7 @@ static int chunk_args(hdb_index* ix, const TopkPlan& p, const TopkEnv& e, bool f
     base_args(ix, a, e.Qeff, e.metric_eff);
     if (p.pearson) a.inv_norm = ix->pscale;
     a.q0 = q0; a.bias = e.bias_eff; a.mask = e.mask_eff; a.f32_split = f32s ? 1 : 0;
-    a.f8_lds = !p.f8_lds ? 0 : ix->opt.f8_lds_waves ? (int)ix->opt.f8_lds_waves : hdb_mfma_f8_lds_auto_waves(cq);
+    a.f8_lds = !p.f8_lds ? 0 : ix->dtype == HDB_MXF4 ? 1 : ix->opt.f8_lds_waves ? (int)ix->opt.f8_lds_waves : hdb_mfma_f8_lds_auto_waves(cq);      // (MXFP4, hdb_mfma_f4_lds.h: always four waves)
     a.thr = w.thr; a.cnt = w.cnt; a.cand = w.cand;
     a.ntiles = (n + p.tile_rows - 1) / p.tile_rows;
     if (p.subset) { a.rows = ix->rows; a.m = ix->subset_m; a.mask = nullptr; a.bias = ix->bias; }

@@ -344,6 +344,37 @@ static inline int hdb_mfma_f4_wide_blocks(int64_t ntiles, int cus, int max_block
 // (What does lose, at 64 / 128 queries, is the comparison with OTHER indices: README, "Where it loses".)
 static inline int hdb_mfma_f4_wide_min_q(int d) { (void)d; return 5; }
 
+// ---- hdb_mfma_f4_lds*.hip: MXFP4 whole rows for large batches, the query parts in LDS (hdb_mfma_f4_lds.h; OPT-IN, f8_lds_min_q >= 1
+// beside b1_mfma_min_q >= 1) ----
+// Whole rows of 128 / 256 / 384 / 512 elements, the register flavour's widths; the wide rows above never take this flavour.  A
+// workgroup of four waves keeps the three bf16 parts of G groups of 16 queries in LDS, 3 KiB per k-step and group:
+//   d        128    256    384    512
+//   G          4      4      4      3
+//   LDS    48 KiB 96 KiB 144 KiB 144 KiB      (one workgroup per CU: 160 KiB)
+static constexpr int hdb_mfma_f4_lds_supported(int d) { return d == 128 || d == 256 || d == 384 || d == 512; }
+static constexpr int hdb_mfma_f4_lds_groups(int d) { return !hdb_mfma_f4_lds_supported(d) ? 0 : d == 512 ? 3 : 4; }
+static constexpr int hdb_mfma_f4_lds_bytes(int d) { return d / 32 * hdb_mfma_f4_lds_groups(d) * 3 * 1024; }
+// workgroups of a launch in x over `ntiles` 16-row tiles: persistent, one per CU (or `limit`, the caller's max_blocks), and never
+// more than there are steps of eight tiles -- two per wave; grid.y counts the blocks of 16 G queries
+static inline int hdb_mfma_f4_lds_blocks(int64_t ntiles, int cus, int limit) {
+    const int64_t want = limit > 0 ? limit : cus, steps = (ntiles + 7) / 8;
+    const int64_t b = steps < want ? steps : want;
+    return b < 1 ? 1 : (int)b;
+}
+// ... and the number of queries of a call from which this flavour is used when f8_lds_min_q = -1; 0 = never, at EVERY width: like
+// hdb_mfma_f4_min_q, -1 stays "never" for MXFP4 until a measured rule exists, so the path is reached with n >= 1 only.
+// For whoever moves it, the measured crossovers.  One box, one run, the contenders alternating call by call, cosine top-100 through
+// rank_batch, p50 of 60 calls in us, LDS flavour vs register flavour on the same handle at 16 / 32 / 64 / 128 / 256 queries; spread =
+// the two p50s of the repeated LDS contender, at most 0.9 % except 10M x 384 from 64 queries (4.4-7.6 %) and 2M x 384 / 512 at 256
+// (4.7 / 1.8 %) (tools/time_f4_lds.py -> profiles/f4_lds_time.txt):
+//   10M x 384:   824 vs   499, 1 028 vs   814, 1 499 vs 1 445, 2 917 vs 2 816, 5 703 vs 5 575      -> never (0.96-0.98 from 64 on, inside the spread)
+//    2M x 128:   161 vs   101,   188 vs   128,   259 vs   212,   285 vs   344,   503 vs   599      -> 128 (1.21x; 64 queries 0.82x)
+//    2M x 256:   191 vs   134,   241 vs   199,   322 vs   305,   584 vs   486, 1 112 vs   904      -> never (0.70-0.95)
+//    2M x 384:   232 vs   175,   274 vs   240,   387 vs   376,   703 vs   690, 1 338 vs 1 319      -> never (0.97-0.99 from 64 on)
+//    2M x 512:   249 vs   257,   308 vs   380,   546 vs   620,   924 vs 1 173, 1 794 vs 2 311      -> 16 (1.03x; 1.14-1.29x from 32 on)
+// Fewer than 16 queries were not measured.
+static inline int hdb_mfma_f4_lds_min_q(int d) { (void)d; return 0; }
+
 // ---- hdb_mfma_qt2.hip: two query tiles per wave ----
 static inline int hdb_mfma_qt2_supported(int d) { return d == 128 || d == 256 || d == 512 || d == 640; }
 

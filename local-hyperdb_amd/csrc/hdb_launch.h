@@ -95,6 +95,8 @@ HDB_GEOM_DECL(hdb_launch_mfma_scan_f4);                 // MXFP4 rows: one 16-by
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_wide);
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_wide_rows);       // MXFP4 rows wider than 512 elements: the waves of a workgroup split K and add through LDS, one launch (hdb_mfma_f4_wide.h; slice width 128 / 256 here, 384 / 512 in _b)
 HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_wide_rows_b);
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_lds);             // MXFP4 whole rows for large batches: query parts in LDS, two converted tiles per wave in registers (hdb_mfma_f4_lds.h; ScanArgs::f8_lds = 1); blocks: the grid's x
+HDB_GEOM_DECL(hdb_launch_mfma_scan_f4_lds_wide);
 // hdb_launch_rescore_euclid's case for MXFP4 rows (hdb_mfma_f4.hip: the widening is the scan's)
 int hdb_launch_rescore_euclid_f4(unsigned long long* cand, const uint32_t* cnt, uint32_t cap, int nq_launch, const void* V, int d,
                                  const float* Q, const float* qsq, int q0, const float* bias, void* stream);

@@ -129,6 +129,10 @@ extern "C" int hdb_launch_mfma_scan(const ScanArgs* args, int dtype, int mode, i
             l.blocks = hdb_mfma_f4_wide_blocks(a.ntiles, cus, max_blocks, a.d);
             return hdb_launch_mfma_scan_f4_wide_rows(args, &l);
         }
+        if (dtype == HDB_MXF4 && a.f8_lds && hdb_mfma_f4_lds_supported(a.d)) {      // large batches (the plan asked, f8_lds_min_q): query parts in LDS, one workgroup per CU, eight tiles per step
+            l.blocks = hdb_mfma_f4_lds_blocks(a.ntiles, cus, max_blocks);
+            return hdb_launch_mfma_scan_f4_lds(args, &l);
+        }
         if (dtype == HDB_MXF4) return hdb_mfma_f4_tile_rows(a.d) > 0 ? hdb_launch_mfma_scan_f4(args, &l) : (int)hipErrorNotSupported;
         if (dtype == HDB_I8) return hdb_launch_mfma_scan_i8(args, &l);
         if (dtype == HDB_B1) return hdb_mfma_b1_ks_slices(a.d) > 0 ? hdb_launch_mfma_ksplit(args, dtype, &l) : hdb_launch_mfma_scan_b1(args, &l);

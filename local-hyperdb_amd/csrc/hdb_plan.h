@@ -28,7 +28,7 @@ struct hdb_options {
     int64_t f32_split_min_q = -1;     //     this many queries (-1: hdb_mfma_f32_split_min_q(d), the measured crossover)
     int64_t bf16_ks_min_q = -1;       // bfloat16 rows in K slices (d > 512): from this many queries on, never fewer than 5 (-1: hdb_mfma_bf16_ks_min_q(d), measured per width)
     int64_t f8_ks_min_q = 0;          // float8 rows in K slices (d > 512, hdb_mfma_f8_ks.hip): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_ks_min_q(d).  On an MXFP4 index it is read as "rows wider than 512 elements of the opt-in matrix-core flavours": with b1_mfma_min_q >= 1 beside it, != 0 opens the wide rows (hdb_mfma_f4_wide.h; -1 = hdb_mfma_f4_wide_min_q(d))
-    int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never)
+    int64_t f8_lds_min_q = 0;         // float8 batches on the matrix cores with the rows expanded to bf16 in LDS once per workgroup (hdb_mfma_f8_lds.h): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_f8_lds_min_q(d) (0 there: never).  On an MXFP4 index it is read as "LDS flavour of the opt-in matrix-core path": with b1_mfma_min_q >= 1 beside it, n >= 1 sends whole rows of 128 .. 512 elements to the kernel that keeps the query parts in LDS (hdb_mfma_f4_lds.h) from max(n, that option's threshold) queries on; -1 = hdb_mfma_f4_lds_min_q(d), 0 at every width: never
     int64_t b1_mfma_min_q = 0;        // sub-byte rows on the bf16 matrix cores -- packed-bit batches (hdb_mfma_b1.h; d = 128 .. 512 whole, 640 .. 4096 in K slices) and MXFP4 batches (hdb_mfma_f4.h; d = 128 .. 512 whole, finite matrices; 640 .. 4096 split over the waves of a workgroup, hdb_mfma_f4_wide.h, only with n >= 1 here AND f8_ks_min_q != 0): 0 = never (the default: opt-in), n >= 1 = from max(n, 5, mfma_min_q) queries on, -1 = hdb_mfma_b1_min_q(d) (0 there: never; MXFP4: hdb_mfma_f4_min_q(d), 0 at every width)
     int64_t bf16_quant = 0;           // bfloat16 matrices: hdb_index_quantize(HDB_QUANT_I8) builds an explicit int8 shadow (0, the default: the call is refused; opt-in).  Means nothing on other types; the plan does not read it
     int64_t f8_lds_waves = 0;         // ... in workgroups of this many waves: 0 = by the launch's queries (hdb_mfma_f8_lds_auto_waves), 4 | 8 = fixed (A/B runs)
@@ -174,7 +174,7 @@ struct TopkPlan {
     bool bits = false, pearson = false;                 // the metric's family
     bool exact = false, small = false, mfma = false, f32s = false, ksplit = false, l1tile = false, local = false;
     bool exact_req = false;                             // the caller asked for the exact selection (f32s: only while no query holds an infinity, run_pipeline)
-    bool f8_lds = false;                                // float8 rows: every matrix-core launch of the call expands its rows in LDS (hdb_mfma_f8_lds.h)
+    bool f8_lds = false;                                // float8 rows: every matrix-core launch of the call expands its rows in LDS (hdb_mfma_f8_lds.h); MXFP4 whole rows: every launch keeps the query parts in LDS (hdb_mfma_f4_lds.h)
     bool subset = false;                                // the pipeline scores the rows of the index's list: every extent below is that of a matrix of subset_m rows
     // prologue of the paths that prepare their queries with launches of their own (full sort, pipeline)
     bool prep = false, fold_small = false, q16_in_prep = false, f16_queries = false, mask_fold = false;
@@ -386,14 +386,6 @@ static inline bool subset_rule(const TopkFacts& ix, const hdb_options& o, const 
     return ix.subset_m <= ix.n / (((int64_t)c.nq + 3) / 4 * ratio);
 }
 
-// The number of queries of a call from which a float8 index expands its rows in LDS (f8_lds_min_q; the stat of the same name): the
-// option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never
-static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
-    if (dtype != HDB_F8E4M3) return 0;
-    const int64_t rule = o.f8_lds_min_q > 0 ? o.f8_lds_min_q : o.f8_lds_min_q < 0 ? (int64_t)hdb_mfma_f8_lds_min_q(d) : 0;
-    return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
-}
-
 // The number of queries of a call from which a packed-bit index takes the matrix cores (b1_mfma_min_q; the stat of the same name):
 // the option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never (the default, and every width without a kernel)
 // (an MXFP4 index reads the same option -- "sub-byte rows on the bf16 matrix cores" -- for whole rows of 128 .. 512 elements,
@@ -413,7 +405,24 @@ static inline int64_t b1_mfma_first_q(const hdb_options& o, int dtype, int d) {
     return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
 }
 
-// finite(): "are all rows of the matrix finite with a finite sum of squares?"
+// The number of queries of a call from which a float8 index expands its rows in LDS (f8_lds_min_q; the stat of the same name): the
+// option, or the measured rule of the width, never below 5 or mfma_min_q; 0 = never
+// (an MXFP4 index reads the same option as "LDS flavour of the opt-in matrix-core path", hdb_mfma_f4_lds.h: only where b1_mfma_min_q
+//  already sends whole rows of 128 .. 512 elements to the matrix cores, and never below that option's threshold; the wide rows never.
+//  Its measured rule, hdb_mfma_f4_lds_min_q, is 0 at every width: -1 means never there)
+static inline int64_t f8_lds_first_q(const hdb_options& o, int dtype, int d) {
+    if (dtype == HDB_MXF4) {
+        const int64_t b1 = b1_mfma_first_q(o, dtype, d);
+        if (b1 <= 0 || !hdb_mfma_f4_lds_supported(d) || hdb_mfma_f4_wide_geom(d).s > 0) return 0;
+        const int64_t rule = o.f8_lds_min_q > 0 ? o.f8_lds_min_q : o.f8_lds_min_q < 0 ? (int64_t)hdb_mfma_f4_lds_min_q(d) : 0;
+        return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), std::max<int64_t>(b1, rule)) : 0;
+    }
+    if (dtype != HDB_F8E4M3) return 0;
+    const int64_t rule = o.f8_lds_min_q > 0 ? o.f8_lds_min_q : o.f8_lds_min_q < 0 ? (int64_t)hdb_mfma_f8_lds_min_q(d) : 0;
+    return rule > 0 ? std::max<int64_t>(std::max<int64_t>(o.mfma_min_q, 5), rule) : 0;
+}
+
+// finite():"are all rows of the matrix finite with a finite sum of squares?"
 template <typename Finite>
 static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, const TopkCall& c, Finite&& finite_fn) {
     int fin_known = -1;                                      // several rules below read the answer: the question is asked once
@@ -605,8 +614,10 @@ static inline TopkPlan plan_topk(const TopkFacts& ix, const hdb_options& o, cons
     // float8 batches with the rows expanded in LDS once per workgroup (f8_lds_min_q, opt-in): whatever the float8 matrix cores take --
     // a whole row or the K slices -- from the threshold's number of queries on; sample, filter and exact pass alike.  Nothing else of
     // the plan changes: the tiles stay 16 rows, so the sample rows, the thresholds and with them the answers are the register flavour's
+    // (MXFP4 whole rows on the matrix cores, b1mm: the flavour with the query parts in LDS, hdb_mfma_f4_lds.h -- same tiles, same bits)
     const int64_t f8_lds_first = f8_lds_first_q(o, ix.dtype, ix.d);
-    p.f8_lds = mfma && ix.dtype == HDB_F8E4M3 && !full_sort && (f8ks || hdb_mfma_f8_lds_supported(ix.d)) && f8_lds_first > 0 && nq >= f8_lds_first;
+    const bool lds_rows = ix.dtype == HDB_F8E4M3 ? (f8ks || hdb_mfma_f8_lds_supported(ix.d)) : (ix.dtype == HDB_MXF4 && b1mm && hdb_mfma_f4_lds_supported(ix.d));
+    p.f8_lds = mfma && lds_rows && !full_sort && f8_lds_first > 0 && nq >= f8_lds_first;
     p.stats.f8_lds = p.f8_lds ? 1 : 0;
     p.exact = exact; p.exact_req = exact_req; p.small = small; p.mfma = mfma; p.f32s = f32s; p.ksplit = ksplit; p.local = local_ok;
     p.tile_rows = tile_rows; p.s_tiles = s_tiles; p.s_stride = s_stride; p.m = m; p.s_rows = s_rows; p.ld_s = ld_s; p.ld_n = ld_n;
